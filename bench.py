@@ -27,11 +27,13 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 PEAK_BF16_TFLOPS = 2500.0   # dense bf16 MFMA, /opt/skills/guides/MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0
+DUMP_PARAM_SAMPLES = 1 << 22   # --dump-outputs: params.npy = 16 MB of float32
 
 
 def fwd_flops_per_grid(cfg, R):
@@ -93,6 +95,9 @@ def main():
     ap.add_argument("--no-sweep", action="store_true", help="skip the 1/4/8 grids-per-GPU sweep legs (config.sweep)")
     ap.add_argument("--e2e", action="store_true", help="also time Trainer.fit on host-resident synthetic scenes (uint8 and fp32 storage)")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from Python each step instead of replaying the captured HIP graph")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0): loss.npy [loss, loss_rgb, loss_alpha], grad_norm.npy "
+                         "(pre-clip), and params.npy, a fixed seeded sample of the flat parameter buffer after the step")
     args = ap.parse_args()
 
     from nerf_mae_amd import ops
@@ -176,9 +181,16 @@ def main():
 
     comm_events = {}
 
-    def run_leg(nb, steps, warmup, use_reducer=True, comm_timing_key=None):
+    # --dump-outputs: the flat fp32 parameter buffer is too large to write whole (76 M values for swin_s), so a fixed seeded sample of it is written
+    dump_idx = None
+    if args.dump_outputs:
+        n = model._flat.numel()
+        dump_idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_PARAM_SAMPLES), replace=False))).to(dev)
+
+    def run_leg(nb, steps, warmup, use_reducer=True, comm_timing_key=None, outputs=None):
         """`steps` timed steps at nb grids per GPU -> (seconds [max over ranks], last loss).  comm_timing_key: HIP events around every gradient exchange
-        (comm stream) and at the join (compute stream) during the timed steps -> comm_events[key] (per-range all-reduce ms, exposed ms from timestamps)"""
+        (comm stream) and at the join (compute stream) during the timed steps -> comm_events[key] (per-range all-reduce ms, exposed ms from timestamps).
+        outputs: a dict, filled after the timed steps with what the last of them computed (see --dump-outputs)"""
         grids = grids_all[:nb]
         graphed = None
         red = reducer if use_reducer else None
@@ -194,23 +206,23 @@ def main():
             opt.set_hyper(lr=lr, beta1=b1)
             bm = draw_block_mask((g, g, g), 0.75, rng=mask_rng)   # per-step python-random mask, as the reference
             if graphed is not None:
-                return graphed(None, bm)[0]
+                return graphed(None, bm)
             model.zero_grad()
-            loss, l_rgb, l_a = model(grids, block_mask=bm)
-            loss.backward()
+            losses = model(grids, block_mask=bm)
+            losses[0].backward()
             if red is not None:
                 red.finish()
             opt.step()
-            return loss
+            return losses
 
         for _ in range(warmup):
-            loss = step()
+            losses = step()
         barrier()
         if comm_timing_key is not None and red is not None:
             red.timing_begin()
         t0 = time.perf_counter()
         for _ in range(steps):
-            loss = step()
+            losses = step()
         barrier()
         dt = time.perf_counter() - t0
         if comm_timing_key is not None and red is not None:
@@ -219,12 +231,20 @@ def main():
             t = torch.tensor([dt], device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = t.item()
-        lv = loss.item()
+        if outputs is not None:
+            outputs.update(loss=torch.stack([v.detach().float() for v in losses]).cpu().numpy(), grad_norm=opt.norm.float().cpu().numpy(),
+                           params=model._flat.index_select(0, dump_idx).cpu().numpy())
+        lv = losses[0].item()
         del graphed
         torch.cuda.empty_cache()
         return dt, lv
 
-    dt, loss_val = run_leg(Bg, args.steps, args.warmup)
+    dumped = {} if args.dump_outputs else None
+    dt, loss_val = run_leg(Bg, args.steps, args.warmup, outputs=dumped)
+    if dumped and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     grids_per_s = args.steps * Bg * world / dt
     cfg = SWIN_CONFIGS[args.backbone]
     flops_fb = 3.0 * fwd_flops_per_grid(cfg, R)

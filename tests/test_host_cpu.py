@@ -158,4 +158,8 @@ def test_capi_rejects_null_required_pointers_without_touching_the_device():
     assert L.nmh_conv3d_k3_c64(null, null, null, 1, 8, 8, 8, 64, 64, 0, null, null, null) == -4
     assert L.nmh_set_prezeroed_arena(null, 4096) == -4 and L.nmh_set_prezeroed_arena(null, -1) == -4
     assert L.nmh_set_prezeroed_arena(null, 0) == 0      # bytes = 0 removes the arena
+    from nerf_mae_amd import ops
+    ar = ops.AccArena._inst
+    if ar is not None:   # the arena is process-wide state: give back the one an earlier GPU test of this session registered
+        assert L.nmh_set_prezeroed_arena(ctypes.c_void_p(ar.buf.data_ptr()), ar.BYTES) == 0
     assert L.nmh_error_string(-4).decode().startswith("nmh:")
