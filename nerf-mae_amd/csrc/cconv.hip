@@ -51,8 +51,7 @@ struct CConvArgs {
 __host__ __device__ __forceinline__ int cc_ncnt(int a) { return (a == 0 || a == 3) ? 2 : 1; }
 __host__ __device__ __forceinline__ int cc_nfirst(int a) { return a == 0 ? -1 : 0; }
 
-// DBG (diagnostic builds, NMH_CCONV_DBG): 1 = no output stores, 2 = no weight DMA / waits (stale weights), 4 = no MFMAs, 8 = no epilogue at all.  0 = product.
-template <int DBG, bool CZ = false>
+template <bool CZ = false>
 __global__ __launch_bounds__(512) void cconv_fwd_kernel(CConvArgs a) {
   using namespace cc;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -73,7 +72,6 @@ __global__ __launch_bounds__(512) void cconv_fwd_kernel(CConvArgs a) {
 
   // half-chunk h (9 lane-linear 1-KB images: blocks 3 (h & 1) .. +2 of chunk h / 2) -> ring slot: wave w takes image w, wave 0 also image 8
   auto w_dma = [&](int h, int slot) {
-    if (DBG & 2) return;
     const char* src = reinterpret_cast<const char*>(a.Wcp) + (long)h * WHALF;
     char* dst = wbuf + slot * WHALF;
     int lv = lane;
@@ -194,8 +192,7 @@ __global__ __launch_bounds__(512) void cconv_fwd_kernel(CConvArgs a) {
               // half-chunk h has landed once at most the pieces of the two younger half-chunks (and, in front of a group's first one, the 16
               // output stores of the previous group, which are younger still) are outstanding: vector-memory operations retire in order
               const bool after_epi = half == 0 && gi > 0 && iz == 0 && iy == 0 && s == 0;
-              if (DBG & 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-              else if (wave == 0) {
+              if (wave == 0) {
                 if (after_epi) asm volatile("s_waitcnt vmcnt(20) lgkmcnt(0)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
               } else {
@@ -219,23 +216,11 @@ __global__ __launch_bounds__(512) void cconv_fwd_kernel(CConvArgs a) {
 #pragma unroll
                 for (int n = 0; n < 3; ++n)
 #pragma unroll
-                  for (int m = 0; m < 2; ++m) {
-                    if (DBG & 4) { asm volatile("" ::"v"(wf[kk * 3 + n].v), "v"(xf[BLK_NX[k]][m].v)); }
-                    else mma(acc[BLK_AX[k]][n][m], wf[kk * 3 + n], xf[BLK_NX[k]][m]);
-                  }
+                  for (int m = 0; m < 2; ++m) mma(acc[BLK_AX[k]][n][m], wf[kk * 3 + n], xf[BLK_NX[k]][m]);
               }
             }
           }
         }
-      if (DBG & 8) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-#pragma unroll
-          for (int n = 0; n < 3; ++n)
-#pragma unroll
-            for (int m = 0; m < 2; ++m) asm volatile("" ::"v"(acc[p][n][m]));
-        continue;
-      }
       // ---- epilogue of the group: lane (li, g) owns channels 12 g .. 12 g + 11 (rows 4 g + r of channel tile n <-> channel 12 g + 4 n + r)
       const int zf = 4 * (z0 + z_l) + az;
       const int kz = zf == 0 ? 0 : (zf == F - 1 ? 2 : 1);
@@ -286,10 +271,8 @@ __global__ __launch_bounds__(512) void cconv_fwd_kernel(CConvArgs a) {
           for (int q = 0; q < 6; ++q) w6[q] = pk_bf16(vv[q >> 1][(q & 1) * 2], vv[q >> 1][(q & 1) * 2 + 1]);
           bf16_t* dst = drow + p * 48;
           // (non-temporal stores measured slower: 1.95 vs 1.48 ms at 8 grids -- the 24-byte pieces of a voxel row no longer merge in L2)
-          if (!(DBG & 1)) {
-            *reinterpret_cast<uint4*>(dst) = make_uint4(w6[0], w6[1], w6[2], w6[3]);
-            *reinterpret_cast<uint2*>(dst + 8) = make_uint2(w6[4], w6[5]);
-          } else asm volatile("" ::"v"(w6[0]), "v"(w6[1]), "v"(w6[2]), "v"(w6[3]), "v"(w6[4]), "v"(w6[5]));
+          *reinterpret_cast<uint4*>(dst) = make_uint4(w6[0], w6[1], w6[2], w6[3]);
+          *reinterpret_cast<uint2*>(dst + 8) = make_uint2(w6[4], w6[5]);
         }
       }
       if (a.stats_acc) {
@@ -594,28 +577,21 @@ int k_cconv_fwd(const void* X, const void* Wcp, const float* delta, void* Y, int
   if (mhat) {
     static NmhPerDeviceOnce attr_cz;
     if (attr_cz.need()) {
-      hipError_t e = hipFuncSetAttribute((const void*)cconv_fwd_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+      hipError_t e = hipFuncSetAttribute((const void*)cconv_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
       if (e != hipSuccess) return (int)e;
       attr_cz.set();
     }
-    hipLaunchKernelGGL((cconv_fwd_kernel<0, true>), dim3((unsigned)nb), dim3(512), LDS_BYTES, st, a);
+    hipLaunchKernelGGL((cconv_fwd_kernel<true>), dim3((unsigned)nb), dim3(512), LDS_BYTES, st, a);
     NMH_CHECK_LAUNCH();
     return 0;
   }
-  static const int dbg = getenv("NMH_CCONV_DBG") ? atoi(getenv("NMH_CCONV_DBG")) : 0;
-#define CC_LAUNCH(D)                                                                                                              \
-  {                                                                                                                               \
-    static NmhPerDeviceOnce attr;                                                                                                     \
-    if (attr.need()) {                                                                                                                  \
-      hipError_t e = hipFuncSetAttribute((const void*)cconv_fwd_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); \
-      if (e != hipSuccess) return (int)e;                                                                                         \
-      attr.set();                                                                                                                \
-    }                                                                                                                             \
-    hipLaunchKernelGGL(cconv_fwd_kernel<D>, dim3((unsigned)nb), dim3(512), LDS_BYTES, st, a);                                     \
+  static NmhPerDeviceOnce attr_set;
+  if (attr_set.need()) {
+    hipError_t e = hipFuncSetAttribute((const void*)cconv_fwd_kernel<>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    if (e != hipSuccess) return (int)e;
+    attr_set.set();
   }
-  if (dbg == 1) CC_LAUNCH(1) else if (dbg == 2) CC_LAUNCH(2) else if (dbg == 4) CC_LAUNCH(4) else if (dbg == 8) CC_LAUNCH(8) else if (dbg == 6) CC_LAUNCH(6)
-  else if (dbg == 10) CC_LAUNCH(10) else if (dbg == 12) CC_LAUNCH(12) else if (dbg == 14) CC_LAUNCH(14) else CC_LAUNCH(0)
-#undef CC_LAUNCH
+  hipLaunchKernelGGL(cconv_fwd_kernel<>, dim3((unsigned)nb), dim3(512), LDS_BYTES, st, a);
   NMH_CHECK_LAUNCH();
   return 0;
 }

@@ -68,9 +68,8 @@ __device__ __forceinline__ void c48_tile_origin(const C48Args& a, long t, int& b
   x0 = __builtin_amdgcn_readfirstlane((int)xt * c48::TX);
 }
 
-// DBG (diagnostic builds only, NMH_C48_DBG): 1 = no output stores, 2 = no halo prefetch / LDS refill, 4 = no weight DMA and no
-// chunk barriers, 8 = no MFMAs (operand traffic only), 16 = no operand reads in the k-loop (MFMAs only).  DBG = 0 is the product.
-template <int DBG, bool MB = false, bool RB = false, bool CZ = false>
+// The leading parameter is always 0; it stays because bench.py attributes FLOPs and PMC traffic by the name text `conv48_kernel<0, false, `.
+template <int, bool MB = false, bool RB = false, bool CZ = false>
 __global__ __launch_bounds__(512) void conv48_kernel(C48Args a) {
   using namespace c48;
   constexpr long WBLK = (long)NSTEP * 3 * 512;   // elements of one (cob, cib) weight image
@@ -94,7 +93,7 @@ __global__ __launch_bounds__(512) void conv48_kernel(C48Args a) {
   // offset in the sample, its LDS row -- is wave-uniform and lives on the scalar unit (the line's offset is the buffer instruction's SGPR offset); the lane part
   // (x range test, byte offset of the chunk in the line) is the same for every line of a tile: two VGPRs per tile.  The request costs no vector instruction,
   // where the chunk-id mapping of rounds 2-5 (13 requests of tid + 512 i) spent ~18 per request on two divisions by multiply-shift, four multiplies and the
-  // range tests: ~230 VALU instructions per tile and wave in a kernel whose MFMA stream has no idle issue slots (NMH_C48_DBG=2: the prefetch cost 11 % of it).
+  // range tests: ~230 VALU instructions per tile and wave in a kernel whose MFMA stream has no idle issue slots (the prefetch cost 11 % of it).
   // 16 requests instead of 13 (the second request of a line has 44 live lanes).  The requests of the NEXT tile are dealt one at a time over the k-steps of the
   // current one (a burst backs up the CU's vector-memory path); `bytes` = 0 when there is no next tile: still issued (no branch in the k-loop), reads zero.
   constexpr unsigned OOB = 0x80000000u;   // >= num_records with or without the SGPR offset added (samples are < 2 GiB)
@@ -171,7 +170,6 @@ __global__ __launch_bounds__(512) void conv48_kernel(C48Args a) {
 #pragma unroll
   for (int i = 0; i < HREG; ++i) halo_gload_one(i, cb, cz0, cy0, sample_bytes);
   w_dma(wfirst, 0, 0);
-  if (DBG & 4) w_dma(wfirst, 1, 1);
   halo_sstore();
   __syncthreads();
   int wb = 0;  // LDS buffer holding chunk 0 of the current tile
@@ -210,20 +208,6 @@ __global__ __launch_bounds__(512) void conv48_kernel(C48Args a) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xf, 0xf, true));
     return v;
   };
-  // DBG & 32: per-wave cycle accounting (s_memtime) of the tile phases, written to stats_acc reinterpreted as int64 [block][wave][12]
-  long long ph[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) ph[i] = 0;
-  long long tlast = 0;
-  auto stamp = [&](int slot) {
-    if (DBG & 32) {
-      const long long now = (long long)__builtin_amdgcn_s_memtime();
-      ph[slot] += now - tlast;
-      tlast = now;
-    }
-  };
-  if (DBG & 32) tlast = (long long)__builtin_amdgcn_s_memtime();
-  const long long tbegin = tlast;
   f32x4 acc[4][3];
   for (;;) {
     // next work item: (t, cob, cib + 1) -> (t, cob + 1, 0) -> (t + jstride, 0, 0); with split units t = (tile, cob):
@@ -238,10 +222,9 @@ __global__ __launch_bounds__(512) void conv48_kernel(C48Args a) {
       } else if (nco == a.ncob) { nco = 0; tn = t + jstride; }
     }
     const bool has_next = tn < tend;
-    const bool pf_next = has_next && !(DBG & 2);
     int nb = cb, nz0 = cz0, ny0 = cy0, nx0 = cx0;
     if (has_next && (!MB || tn != t)) c48_tile_origin(a, split ? tn / a.ncob : tn, nb, nz0, ny0, nx0);
-    const unsigned nbytes = pf_next ? sample_bytes : 0u;
+    const unsigned nbytes = has_next ? sample_bytes : 0u;
     halo_voff(nx0, nci);   // lane offsets of the next tile's requests
     const bf16_t* const wcur = MB ? a.Wk + (long)(cob * a.ncib + cib) * WBLK : a.Wk + (long)cb * a.wk_sample_stride;
     const bf16_t* const wnxt = MB ? a.Wk + (long)(nco * a.ncib + nci) * WBLK : a.Wk + (long)nb * a.wk_sample_stride;
@@ -278,61 +261,46 @@ __global__ __launch_bounds__(512) void conv48_kernel(C48Args a) {
       // VMEM issue is dealt over the k-steps: steps 0-3 carry this wave's (<= 4) DMA instructions for the next weight chunk, later steps
       // the halo requests of the next tile (HSLOT: 4+3+3+3 = 13 over chunks 0-3).  vmcnt retires in order, so "vmcnt(#halo requests of
       // this chunk)" at the chunk barrier means "the DMA and everything older has landed" while the newest requests stay in flight.
-      const bool do_dma = !(DBG & 4);  // (the chunk-0 image requested during the last tile is simply never read)
       const char* wsrc = wbuf + ((wb + ck) & 1) * WCHUNK;
       constexpr int NST4 = NSTEP - 4 * CSTEPS;
       const int nst = (ck < 4) ? CSTEPS : NST4;
       const int hbase = 4 * ck;          // first halo request index of this chunk
       const int hcnt = ck < 4 ? 4 : 0;   // (16 = 4 + 4 + 4 + 4 over chunks 0-3)
-      if (!(DBG & 16) || ck == 0) ld_frags(0, wsrc, 0, ck * CSTEPS);
-      if ((DBG & 16) && ck == 0) ld_frags(1, wsrc, 1, 1);
+      ld_frags(0, wsrc, 0, ck * CSTEPS);
 #pragma unroll
       for (int sl = 0; sl < CSTEPS; ++sl) {
         if (sl < nst) {
-          if (!(DBG & 16) && sl + 1 < nst) ld_frags((sl + 1) & 1, wsrc, sl + 1, ck * CSTEPS + sl + 1);
-          if (do_dma && sl < 4) w_dma_one(ck < 4 ? wcur : wnxt, nxt, (wb + ck + 1) & 1, sl);
+          if (sl + 1 < nst) ld_frags((sl + 1) & 1, wsrc, sl + 1, ck * CSTEPS + sl + 1);
+          if (sl < 4) w_dma_one(ck < 4 ? wcur : wnxt, nxt, (wb + ck + 1) & 1, sl);   // (on the last tile the chunk-0 image is simply never read)
           if (sl >= 4) {
             // chunk 0: steps 4,5,6,8; chunks 1-3: steps 4,6,8
             const int k = (hcnt == 4) ? (sl == 4 ? 0 : sl == 5 ? 1 : sl == 6 ? 2 : sl == 8 ? 3 : -1) : (hcnt == 3) ? (sl == 4 ? 0 : sl == 6 ? 1 : sl == 8 ? 2 : -1) : -1;
             if (k >= 0) halo_gload_one(hbase + k, nb, nz0, ny0, nbytes);
           }
-          if (DBG & 8) {
 #pragma unroll
-            for (int n = 0; n < 3; ++n) asm volatile("" ::"v"(bf[sl & 1][n].v));
+          for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(af[sl & 1][i].v));
-          } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-              for (int n = 0; n < 3; ++n) mma(acc[i][n], bf[sl & 1][n], af[sl & 1][i]);  // acc = (W . X^T) tile: rows co, cols voxel
-          }
+            for (int n = 0; n < 3; ++n) mma(acc[i][n], bf[sl & 1][n], af[sl & 1][i]);  // acc = (W . X^T) tile: rows co, cols voxel
         }
       }
-      stamp(ck == 0 ? 0 : ck == 1 ? 2 : 4);
-      if (!(DBG & 4)) {
-        if (hcnt == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else if (hcnt == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (DBG & 32) stamp(ck == 0 ? 1 : ck == 1 ? 3 : 5);
-        __builtin_amdgcn_s_barrier();
-      }
-      stamp(ck == 0 ? 9 : ck == 1 ? 10 : 11);
+      if (hcnt == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else if (hcnt == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
     }
     wb ^= 1;  // 5 chunks: chunk 0 of the next tile landed in the other buffer
 
     // the next tile's halo goes to LDS first (the barrier closing weight chunk 4 guarantees every wave is done reading the old one, its
     // vmcnt(0) that the registers have landed): the 13 ds_write_b128 are only issued here and drain while the epilogue below keeps the
     // VALU and the vector-memory path busy
-    if (pf_next) halo_sstore();
-    stamp(7);
+    if (has_next) halo_sstore();
 
     // ---- epilogue: transposed accumulators (row 4g + r of co-tile n = channel 12g + 4n + r, col = voxel x = li): every lane owns 12
     //      consecutive channels of one voxel per x-line -> a 16-byte and an 8-byte bf16 store straight from registers, no LDS restaging ----
     if (!MB || cib == a.ncib - 1) {
       const int b = cb, z0 = cz0, y0 = cy0, x0 = cx0;
       const int z = z0 + z_l, x = x0 + li;
-      const bool stats = !MB && !(DBG & 32) && a.stats_acc;
+      const bool stats = !MB && a.stats_acc;
       if (stats && b != st_b) {
         stats_flush();
         if (st_b >= 0) scur ^= 1;
@@ -344,7 +312,7 @@ __global__ __launch_bounds__(512) void conv48_kernel(C48Args a) {
       const int ldy = MB ? a.ldy : 48;
       bf16_t* const dst0 = a.Y + ((((long)b * a.D + z) * a.H + (y0 + y_l)) * a.W + x) * ldy + (MB ? cob * 48 : 0) + 12 * g;
       const long rowstride = (long)a.W * ldy;
-      const bool zx_ok = z < a.D && x < a.W && (!(DBG & 1) || a.accumulate == 77);
+      const bool zx_ok = z < a.D && x < a.W;
       auto epilogue = [&](auto with_stats) {
         constexpr bool ST = decltype(with_stats)::value;
         // RB: the matching values of Y1 (24 bytes per line) and the lane's 12 channel means are requested first -- the halo registers are free by now --
@@ -451,21 +419,10 @@ __global__ __launch_bounds__(512) void conv48_kernel(C48Args a) {
       if (stats || RB) epilogue(std::true_type{});
       else epilogue(std::false_type{});
     }
-    stamp(6);
     cb = nb; cz0 = nz0; cy0 = ny0; cx0 = nx0;
     __syncthreads();
-    stamp(8);
     if (!has_next) break;
     t = tn; cob = nco; cib = nci;
-  }
-  if (DBG & 32) {
-    if (lane == 0) {
-      long long* o = reinterpret_cast<long long*>(a.stats_acc) + ((long)blockIdx.x * 8 + wave) * 16;
-#pragma unroll
-      for (int i = 0; i < 12; ++i) o[i] = ph[i];
-      o[12] = (long long)__builtin_amdgcn_s_memtime() - tbegin;
-    }
-    return;
   }
   if (a.stats_acc) stats_flush();
 }
@@ -488,8 +445,7 @@ int k_conv48(const void* X, const void* Wk, void* Y, int B, int D, int H, int W,
   a.accumulate = accumulate;
   a.stats_acc = stats_acc;
   a.ncib = a.ncob = 1; a.ldx = a.ldy = 48; a.cosplit = 0;
-  static const int dbg = getenv("NMH_C48_DBG") ? atoi(getenv("NMH_C48_DBG")) : 0;
-  if (stats_acc && !(dbg & 32)) {
+  if (stats_acc) {
     hipError_t e = nmh_zero_async(stats_acc, sizeof(double) * 2 * 48 * B, st);
     if (e != hipSuccess) return (int)e;
   }
@@ -500,17 +456,6 @@ int k_conv48(const void* X, const void* Wk, void* Y, int B, int D, int H, int W,
     attr_set.set();
   }
   long nb = a.total < 256 ? ((a.total + 7) / 8 * 8) : 256;
-  if (dbg) {  // timing decomposition only: results are wrong by construction
-#define C48_DBG_CASE(D) case D: { hipFuncSetAttribute((const void*)conv48_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); \
-    hipLaunchKernelGGL(conv48_kernel<D>, dim3((unsigned)nb), dim3(512), LDS_BYTES, st, a); break; }
-    switch (dbg) {
-      C48_DBG_CASE(1) C48_DBG_CASE(2) C48_DBG_CASE(3) C48_DBG_CASE(4) C48_DBG_CASE(7) C48_DBG_CASE(8) C48_DBG_CASE(15) C48_DBG_CASE(16) C48_DBG_CASE(23) C48_DBG_CASE(32)
-      default: return -1;
-    }
-#undef C48_DBG_CASE
-    NMH_CHECK_LAUNCH();
-    return 0;
-  }
   if (Y1) {
     static NmhPerDeviceOnce attr_rb;
     if (attr_rb.need()) {
@@ -570,12 +515,12 @@ int k_conv48_mb(const void* X, const void* Wk, void* Y, int B, int D, int H, int
 // ================================================================================================================
 // Weight gradient of the same layer: dW[co][ci][tap] += sum_v dY[v][co] * X[v + tap][ci]      (Cin = Cout = 48, bf16)
 //
-// Persistent 1024-thread workgroups (16 waves, 4 per SIMD, <=128 VGPRs) walk 4x4x16 voxel tiles.  Per tile the X halo
+// Persistent 512-thread workgroups (8 waves, 2 per SIMD, <=256 VGPRs) walk 4x4x16 voxel tiles.  Per tile the X halo
 // (6x6x18 voxels, 62 KB) and the dY tile (256 voxels, 24 KB, double-buffered by LDS-DMA) sit in LDS exactly as they lie in
 // memory ([voxel][channel], 96-B rows), and BOTH MFMA operands are contraction-major, i.e. read with ds_read_b64_tr_b16
 // (rows = 8 consecutive x, conflict-free at a 96-B stride).  A k-step is 32 voxels = two adjacent x-lines.  The 27 taps x 3
-// ci-tiles = 81 output column blocks are dealt round-robin to the 16 waves (5-6 blocks x 3 co-tiles = <=18 accumulator tiles
-// per wave); a tap shift is just a different LDS base address.  Accumulators persist across all tiles of the workgroup and
+// ci-tiles = 81 output column blocks are dealt round-robin to the 8 waves (10 blocks x 3 co-tiles = 30 accumulator tiles
+// per wave, one more on waves 1-3); a tap shift is just a different LDS base address.  Accumulators persist across all tiles of the workgroup and
 // are flushed once to a per-workgroup fp32 partial, summed into the PyTorch-layout gradient by a second tiny kernel.
 // ================================================================================================================
 namespace w48 {
@@ -618,10 +563,10 @@ template <int N, int I = 0, class F> __device__ __forceinline__ void w48_static_
   }
 }
 
-template <int NW, int DBG = 0, bool RAW = false>  // waves per workgroup: 16 (<=128 VGPRs, 5 blocks/wave) or 8 (<=256 VGPRs, 10 blocks/wave); RAW: inline-asm transpose reads
-__global__ __launch_bounds__(64 * NW) void conv48_wgrad_kernel(W48Args a) {
+// 8 waves per workgroup (<=256 VGPRs, 10 blocks per wave: measured 5 % faster than 16 waves x 5 blocks)
+__global__ __launch_bounds__(512) void conv48_wgrad_kernel(W48Args a) {
   using namespace w48;
-  constexpr int NT = 64 * NW, HREG = (HCH + NT - 1) / NT, UPW = NUNIT / NW;
+  constexpr int NW = 8, NT = 64 * NW, HREG = (HCH + NT - 1) / NT, UPW = NUNIT / NW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* halo = smem;
   char* dyb = smem + HALO;
@@ -664,7 +609,7 @@ __global__ __launch_bounds__(64 * NW) void conv48_wgrad_kernel(W48Args a) {
       if (cid < HCH) reinterpret_cast<uint4*>(halo)[cid] = hreg[i];  // halo image is dense: chunk id == LDS chunk index
     }
   };
-  constexpr int NDMA = (DCH + NT - 1) / NT;  // DMA instructions per wave and tile: 3 (8 waves) or 2 (16 waves, the second one on waves 0-7)
+  constexpr int NDMA = (DCH + NT - 1) / NT;  // DMA instructions per wave and tile: 3
   auto dy_dma_one = [&](int j, int b, int z0, int y0, int x0, int buf, bool on) {
     const int u0 = wave * 64 + NT * j;
     if (u0 < DCH) {
@@ -686,7 +631,7 @@ __global__ __launch_bounds__(64 * NW) void conv48_wgrad_kernel(W48Args a) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // this wave's output blocks: unit u = wave + 16*idx -> (tap = u/3, ci-tile = u%3); LDS byte offset of the shifted window
+  // this wave's output blocks: unit u = wave + 8*idx -> (tap = u/3, ci-tile = u%3); LDS byte offset of the shifted window
   int uoff[UPW];
 #pragma unroll
   for (int i = 0; i < UPW; ++i) {
@@ -699,7 +644,7 @@ __global__ __launch_bounds__(64 * NW) void conv48_wgrad_kernel(W48Args a) {
   const int xoff = 2 * PLANE + 2 * LINE + 2 * 96 + 2 * 32;
   const bool has_x = wave >= 1 && wave <= 3;
   const int lane_off = (4 * g + (p >> 2)) * 96 + (p & 3) * 8;  // row (x) and 8-byte column piece supplied by this lane
-  const unsigned halo_u = lds_addr_u(halo), dyb_u = lds_addr_u(dyb), dy_lane_off = (unsigned)lane_off;   // (RAW: the dY tile has the same 96-byte rows)
+  const unsigned halo_u = lds_addr_u(halo), dyb_u = lds_addr_u(dyb), dy_lane_off = (unsigned)lane_off;   // (the dY tile has the same 96-byte rows)
   unsigned u_ad[UPW], x_ad = halo_u + (unsigned)(lane_off + xoff);
 #pragma unroll
   for (int i = 0; i < UPW; ++i) u_ad[i] = halo_u + (unsigned)(lane_off + uoff[i]);
@@ -716,77 +661,37 @@ __global__ __launch_bounds__(64 * NW) void conv48_wgrad_kernel(W48Args a) {
     halo_sstore();
   }
   __syncthreads();
-  long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
-  auto stamp = [&](int slot) {
-    if (DBG) { const long long now = (long long)__builtin_amdgcn_s_memtime(); ph[slot] += now - tlast; tlast = now; }
-  };
-  if (DBG) tlast = (long long)__builtin_amdgcn_s_memtime();
   for (; t < tend; t += jstride) {
     const long tn = t + jstride;
     const bool has_next = tn < tend;
     int nb = 0, nz0 = 0, ny0 = 0, nx0 = 0;
     if (has_next) w48_tile_origin(a, tn, nb, nz0, ny0, nx0);
-    stamp(0);
-    const char* dyc = dyb + cur * DYT;
     unsigned dy_ad[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) dy_ad[c] = dyb_u + (unsigned)(cur * DYT + c * 32) + dy_lane_off;
     w48_static_for<8>([&](auto KS) __attribute__((always_inline)) {
       constexpr int ks = decltype(KS)::value;
-      // lines 2ks, 2ks+1 of the tile: (z_l, y_l) = (ks>>1, (ks&1)*2) and y_l+1
-      const int lbase = (ks >> 1) * PLANE + ((ks & 1) * 2) * LINE + lane_off;
-      if constexpr (!RAW) {
-      Frag<bf16_t> af[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) af[c] = lds_frag_t(dyc, 96, ks * 32, c * 16, lane, (bf16_t*)nullptr);
-      // VMEM schedule of the next tile: DMA instruction ks on the first NDMA steps; halo requests 1,1,1,2,2,1 (8 waves) or 1,1,1,1
-      // (16 waves) on steps 0-5, so the last two steps (~2k cycles) give the newest requests time to land before the tile barrier
-      if (ks < NDMA) dy_dma_one(ks, nb, nz0, ny0, nx0, cur ^ 1, has_next);
-      {
-        constexpr int h8[9] = {0, 1, 2, 3, 5, 7, 8, 8, 8}, h4[9] = {0, 1, 2, 3, 4, 4, 4, 4, 4};
-        const int h0 = HREG == 8 ? h8[ks] : h4[ks], h1 = HREG == 8 ? h8[ks + 1] : h4[ks + 1];
-#pragma unroll
-        for (int i = 0; i < HREG; ++i)
-          if (i >= h0 && i < h1) halo_gload_one(i, nb, nz0, ny0, nx0, has_next);
-      }
-#pragma unroll
-      for (int i = 0; i < UPW; ++i) {
-        const char* pb = halo + lbase + uoff[i];
-        bf16x4 lo = ds_read_tr16(pb), hi = ds_read_tr16(pb + LINE);
-        Frag<bf16_t> bfr;
-        bfr.v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) mma(acc[i][c], af[c], bfr);
-      }
-      if (has_x) {
-        const char* pb = halo + lbase + xoff;
-        bf16x4 lo = ds_read_tr16(pb), hi = ds_read_tr16(pb + LINE);
-        Frag<bf16_t> bfr;
-        bfr.v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        if (wave == 1) mma(accx, af[0], bfr);
-        else if (wave == 2) mma(accx, af[1], bfr);
-        else mma(accx, af[2], bfr);
-      }
-      } else {
-      // RAW (round 5): the builtin transpose read is ordered behind EVERY pending vector-memory operation (`s_waitcnt vmcnt(0)`: hipcc cannot tell the dY
-      // buffer / halo being read from the dY buffer being filled by LDS-DMA) -- i.e. behind the next tile's DMA and halo requests issued one k-step earlier,
-      // the prefetch this loop exists to hide.  Raw reads (common.hpp), software-pipelined by hand: the operands of unit pair j + 1 are requested before the
-      // MFMAs of pair j; lgkmcnt(0) only (scalar loads the compiler may have in flight return out of order, so a counted wait would not be safe).
+      // Raw transpose reads (round 5): the builtin transpose read is ordered behind EVERY pending vector-memory operation (`s_waitcnt vmcnt(0)`: hipcc cannot
+      // tell the dY buffer / halo being read from the dY buffer being filled by LDS-DMA) -- i.e. behind the next tile's DMA and halo requests issued one k-step
+      // earlier, the prefetch this loop exists to hide.  Raw reads (common.hpp), software-pipelined by hand: the operands of unit pair j + 1 are requested
+      // before the MFMAs of pair j; lgkmcnt(0) only (scalar loads the compiler may have in flight return out of order, so a counted wait would not be safe).
       constexpr int GU = 2, NG = (UPW + GU - 1) / GU;
-      // (the k-step's tile offsets go into the instructions' immediate field: the address registers -- one per unit, three for dY -- are the same in all 8 steps)
+      // lines 2ks, 2ks+1 of the tile: (z_l, y_l) = (ks>>1, (ks&1)*2) and y_l+1.  The k-step's tile offsets go into the instructions' immediate field: the
+      // address registers -- one per unit, three for dY -- are the same in all 8 steps
       constexpr int LB = (ks >> 1) * PLANE + ((ks & 1) * 2) * LINE, DB = ks * 32 * 96;
       TrFrag fa[3], fb[2][GU], fx;
 #pragma unroll
       for (int c = 0; c < 3; ++c) tr_read_raw<16 * 96, DB>(fa[c], dy_ad[c]);
 #pragma unroll
       for (int u = 0; u < GU; ++u) tr_read_raw<LINE, LB>(fb[0][u], u_ad[u]);
+      // VMEM schedule of the next tile: DMA instruction ks on the first NDMA steps; halo requests 1,1,1,2,2,1 on steps 0-5, so the last
+      // two steps (~2k cycles) give the newest requests time to land before the tile barrier
       if (ks < NDMA) dy_dma_one(ks, nb, nz0, ny0, nx0, cur ^ 1, has_next);
       {
-        constexpr int h8[9] = {0, 1, 2, 3, 5, 7, 8, 8, 8}, h4[9] = {0, 1, 2, 3, 4, 4, 4, 4, 4};
-        const int h0 = HREG == 8 ? h8[ks] : h4[ks], h1 = HREG == 8 ? h8[ks + 1] : h4[ks + 1];
+        constexpr int h8[9] = {0, 1, 2, 3, 5, 7, 8, 8, 8};
 #pragma unroll
         for (int i = 0; i < HREG; ++i)
-          if (i >= h0 && i < h1) halo_gload_one(i, nb, nz0, ny0, nx0, has_next);
+          if (i >= h8[ks] && i < h8[ks + 1]) halo_gload_one(i, nb, nz0, ny0, nx0, has_next);
       }
 #pragma unroll
       for (int j = 0; j < NG; ++j) {
@@ -819,22 +724,11 @@ __global__ __launch_bounds__(64 * NW) void conv48_wgrad_kernel(W48Args a) {
         else if (wave == 2) mma(accx, tr_frag(fa[1]), bfr);
         else mma(accx, tr_frag(fa[2]), bfr);
       }
-      }
     });
-    stamp(1);
     __syncthreads();  // everyone is done with halo / dY[cur]; the barrier also drains this wave's DMA + prefetch loads
-    stamp(2);
     if (has_next) halo_sstore();
-    stamp(3);
     __syncthreads();
-    stamp(4);
     cur ^= 1;
-  }
-  if (DBG) {   // (stamps live behind the partial sums: the accumulators must still be flushed or the MFMAs are dead code)
-    if (lane == 0) {
-      long long* o = reinterpret_cast<long long*>(a.ws + 256L * PARTIAL) + ((long)blockIdx.x * NW + wave) * 8;
-      for (int i = 0; i < 8; ++i) o[i] = ph[i];
-    }
   }
   // flush: ws[block][u][ct][row 16][col 16]
   float* wsb = a.ws + ((long)blockIdx.y * gridDim.x + blockIdx.x) * PARTIAL;
@@ -885,7 +779,7 @@ __global__ void conv48_wgrad_reduce_kernel(const float* ws, float* dW, int nbloc
   dW[((long)(os * 48 + ct * 16 + row) * Cin + cs * 48 + cit * 16 + col) * 27 + tap] += s;
 }
 
-long k_conv48_wgrad_ws_floats() { return 256L * w48::PARTIAL + 65536; }  // (+ room for the diagnostic phase counters)
+long k_conv48_wgrad_ws_floats() { return 256L * w48::PARTIAL; }   // <= 256 workgroups in total (launch_wgrad_halo)
 
 static int launch_wgrad_halo(const void* dY, const void* X, float* dW, float* ws, int B, int D, int H, int W, int Cin, int Cout, hipStream_t st, const float* scale_stats = nullptr) {
   using namespace w48;
@@ -900,8 +794,7 @@ static int launch_wgrad_halo(const void* dY, const void* X, float* dW, float* ws
   const int nsub = (Cin / 48) * (Cout / 48);
   static NmhPerDeviceOnce attr_set;
   if (attr_set.need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv48_wgrad_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv48_wgrad_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    hipError_t e = hipFuncSetAttribute((const void*)conv48_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     if (e != hipSuccess) return (int)e;
     attr_set.set();
   }
@@ -920,27 +813,7 @@ static int launch_wgrad_halo(const void* dY, const void* X, float* dW, float* ws
     if (nb < 1) nb = 1;
     if (nb > a.total) nb = (int)a.total;
   }
-  static const int nw = getenv("NMH_W48_WAVES") ? atoi(getenv("NMH_W48_WAVES")) : 8;  // 8 waves x 10 blocks measured 5 % faster than 16 x 5
-  static const int wdbg = getenv("NMH_W48_DBG") ? atoi(getenv("NMH_W48_DBG")) : 0;
-  if (wdbg) {   // phase cycle counters into ws (int64 [block][wave][8]); no gradient is produced
-    hipFuncSetAttribute((const void*)conv48_wgrad_kernel<8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    hipLaunchKernelGGL((conv48_wgrad_kernel<8, 1>), dim3(nb, nsub), dim3(512), LDS_BYTES, st, a);
-    NMH_CHECK_LAUNCH();
-    hipLaunchKernelGGL(conv48_wgrad_reduce_kernel, dim3((PARTIAL + 255) / 256, nsub), dim3(256), 0, st, ws, dW, nb, a.nci, Cin);
-    NMH_CHECK_LAUNCH();
-    return 0;
-  }
-  static const int raw = getenv("NMH_W48_RAW") ? atoi(getenv("NMH_W48_RAW")) : 1;
-  if (nw == 8 && raw) {
-    static NmhPerDeviceOnce raw_set;
-    if (raw_set.need()) {
-      hipError_t e = hipFuncSetAttribute((const void*)conv48_wgrad_kernel<8, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      if (e != hipSuccess) return (int)e;
-      raw_set.set();
-    }
-    hipLaunchKernelGGL((conv48_wgrad_kernel<8, 0, true>), dim3(nb, nsub), dim3(512), LDS_BYTES, st, a);
-  } else if (nw == 8) hipLaunchKernelGGL(conv48_wgrad_kernel<8>, dim3(nb, nsub), dim3(512), LDS_BYTES, st, a);
-  else hipLaunchKernelGGL(conv48_wgrad_kernel<16>, dim3(nb, nsub), dim3(1024), LDS_BYTES, st, a);
+  hipLaunchKernelGGL(conv48_wgrad_kernel, dim3(nb, nsub), dim3(512), LDS_BYTES, st, a);
   NMH_CHECK_LAUNCH();
   hipLaunchKernelGGL(conv48_wgrad_reduce_kernel, dim3((PARTIAL + 255) / 256, nsub), dim3(256), 0, st, ws, dW, nb, a.nci, Cin, scale_stats, B);
   NMH_CHECK_LAUNCH();

@@ -1386,7 +1386,6 @@ __global__ __launch_bounds__(256) void tail_fwd_kernel(const T* __restrict__ x, 
 //    [voxel][48] (96-byte rows: conflict-free ds_read_b64_tr_b16) and read back transposed as B fragments: 12 MFMAs per 32 voxels replace
 //    the per-lane FMAs.  The LeakyReLU slope enters as lr = slope + (1 - slope) [d0 > 0] when the block combines its sums, so no operand
 //    carries the inexact bf16 value of the slope.
-template <bool NT>
 __global__ __launch_bounds__(256) void tail_fwd_mfma_kernel(const bf16_t* __restrict__ x, const float* __restrict__ stats, const bf16_t* __restrict__ r, LossArgs a,
                                                             long V, float slope, long vpb) {
   constexpr int C = 48, OPB = 32 * 96, WLDS = 4 * OPB;   // per wave: 4 operand images of 32 voxel rows x 96 bytes
@@ -1447,15 +1446,9 @@ __global__ __launch_bounds__(256) void tail_fwd_mfma_kernel(const bf16_t* __rest
   auto issue = [&](long base, Ops& o) {   // base + 32 <= V (V is a multiple of 64: R is a multiple of 4)
     const char* const xs_ = reinterpret_cast<const char*>(xb) + base * (C * 2);   // uniform part of the address: scalar registers
     const char* const rs_ = reinterpret_cast<const char*>(rb) + base * (C * 2);
-    if (NT) {   // one-pass operands far larger than the caches: non-temporal
-      auto ldn = [](const char* p) { const u32x4 w = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)); return make_uint4(w[0], w[1], w[2], w[3]); };
-      o.x[0] = ldn(xs_ + xoff); o.r[0] = ldn(rs_ + xoff); o.x[1] = ldn(xs_ + (xoff + 16u * C * 2u)); o.r[1] = ldn(rs_ + (xoff + 16u * C * 2u));
-      o.x[2] = ldn(xs_ + xoff2); o.r[2] = ldn(rs_ + xoff2);
-    } else {
-      o.x[0] = *reinterpret_cast<const uint4*>(xs_ + xoff); o.r[0] = *reinterpret_cast<const uint4*>(rs_ + xoff);
-      o.x[1] = *reinterpret_cast<const uint4*>(xs_ + (xoff + 16u * C * 2u)); o.r[1] = *reinterpret_cast<const uint4*>(rs_ + (xoff + 16u * C * 2u));
-      o.x[2] = *reinterpret_cast<const uint4*>(xs_ + xoff2); o.r[2] = *reinterpret_cast<const uint4*>(rs_ + xoff2);
-    }
+    o.x[0] = *reinterpret_cast<const uint4*>(xs_ + xoff); o.r[0] = *reinterpret_cast<const uint4*>(rs_ + xoff);
+    o.x[1] = *reinterpret_cast<const uint4*>(xs_ + (xoff + 16u * C * 2u)); o.r[1] = *reinterpret_cast<const uint4*>(rs_ + (xoff + 16u * C * 2u));
+    o.x[2] = *reinterpret_cast<const uint4*>(xs_ + xoff2); o.r[2] = *reinterpret_cast<const uint4*>(rs_ + xoff2);
     const long vq = base + 16 * tl_ + 4 * g;
     const unsigned vox = (unsigned)vq, tq = vox / Ru, zq = tq / Ru;
     const int x0 = (int)(vox - tq * Ru), yy = (int)(tq - zq * Ru), zz = (int)zq;
@@ -1658,7 +1651,6 @@ __global__ __launch_bounds__(256) void tail_fwd_mfma_kernel(const bf16_t* __rest
 #ifndef TAILC_RS
 #define TAILC_RS 112
 #endif
-template <int DBG>
 __global__ __launch_bounds__(512) void tail_fwd_coarse_kernel(const bf16_t* __restrict__ x, const float* __restrict__ stats, const bf16_t* __restrict__ xcoarse,
                                                               const bf16_t* __restrict__ Wr, const float* __restrict__ bt, LossArgs a, long V, float slope, int cpb,
                                                               unsigned mg1, unsigned mg2) {
@@ -1814,14 +1806,12 @@ __global__ __launch_bounds__(512) void tail_fwd_coarse_kernel(const bf16_t* __re
 #pragma unroll
       for (int cb = 0; cb < 3; ++cb) {
         r[t][cb] = bb[cb];
-        if (!(DBG & 1))
 #pragma unroll
-          for (int ks = 0; ks < 3; ++ks) {
-            Frag<bf16_t> wf;
-            wf.v = *reinterpret_cast<const bf16x8*>(wsm + ((t * 3 + cb) * 3 + ks) * 1024);
-            mma(r[t][cb], wf, xcf[ks]);
-          }
-        else r[t][cb][0] += __uint_as_float(o.xc[cb].x & 0x3f800000u);
+        for (int ks = 0; ks < 3; ++ks) {
+          Frag<bf16_t> wf;
+          wf.v = *reinterpret_cast<const bf16x8*>(wsm + ((t * 3 + cb) * 3 + ks) * 1024);
+          mma(r[t][cb], wf, xcf[ks]);
+        }
       }
     uint4 y0, y1, y2, mp, mxp, xp;
     unsigned sb0, sb1, sb2;
@@ -1858,7 +1848,7 @@ __global__ __launch_bounds__(512) void tail_fwd_coarse_kernel(const bf16_t* __re
       l_rgb += occ ? d0f * d0f + d1f * d1f + d2f * d2f : 0.f; l_a += rm ? d3f * d3f : 0.f;
       n_rgb += occ ? 1.f : 0.f; n_a += rm ? 1.f : 0.f;
       ds0 += q0; ds1 += q1; ds2 += q2; ds3 += q3;
-      if (!(DBG & 4) || q0 == 12345.f) *reinterpret_cast<float4*>(a.dp + ((long)b * V + vq) * 4) = make_float4(q0, q1, q2, q3);
+      *reinterpret_cast<float4*>(a.dp + ((long)b * V + vq) * 4) = make_float4(q0, q1, q2, q3);
       if (a.pred) { a.pred[((long)b * 4 + 0) * V + vq] = p0; a.pred[((long)b * 4 + 1) * V + vq] = p1; a.pred[((long)b * 4 + 2) * V + vq] = p2; a.pred[((long)b * 4 + 3) * V + vq] = p3; }
       bf16_t* const dt_ = reinterpret_cast<bf16_t*>(dT) + g * 16 + vi;   // [o][tile][16]
       const unsigned q01 = pk_bf16(q0, q1), q23 = pk_bf16(q2, q3);
@@ -1867,7 +1857,7 @@ __global__ __launch_bounds__(512) void tail_fwd_coarse_kernel(const bf16_t* __re
     issueT(ox.v0, ot);   // (ox.v0: already that of the step after next)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if (lane < 32 && (!(DBG & 4) || sb0 == 0x12345u))   // lane = 16 tile + cell
+    if (lane < 32)   // lane = 16 tile + cell
       *reinterpret_cast<uint2*>(a.sign_mask + ((long)b * V + o.vox + g) * 8) = *reinterpret_cast<const uint2*>(sm + lane * 8);
     Frag<bf16_t> df;
     {
@@ -1876,7 +1866,6 @@ __global__ __launch_bounds__(512) void tail_fwd_coarse_kernel(const bf16_t* __re
       const bool t1 = (vi & 4) != 0;
       df.v = __builtin_bit_cast(bf16x8, make_uint4(t1 ? 0u : w.x, t1 ? 0u : w.y, t1 ? w.x : 0u, t1 ? w.y : 0u));
     }
-    if (!(DBG & 2))
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -1975,24 +1964,17 @@ int k_tail_fwd_coarse(const LossArgs& a, const void* x, const float* stats, cons
   constexpr int LDS = 36 * 1024 + 8 * 4 * 32 * TAILC_RS + 8 * 256 + 8 * 256 + 6 * 1024;
   static NmhPerDeviceOnce attr_set;
   if (attr_set.need()) {
-    e = hipFuncSetAttribute((const void*)tail_fwd_coarse_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)tail_fwd_coarse_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)tail_fwd_coarse_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)tail_fwd_coarse_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)tail_fwd_coarse_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    e = hipFuncSetAttribute((const void*)tail_fwd_coarse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     if (e != hipSuccess) return (int)e;
     attr_set.set();
   }
-  static const int dbg = getenv("NMH_TAILC_DBG") ? atoi(getenv("NMH_TAILC_DBG")) : 0;   // timing experiments only (wrong results): 1 no residual MFMAs, 2 no reduction GEMMs, 4 no stores
   static const int cpb_env = getenv("NMH_TAILC_CPB") ? atoi(getenv("NMH_TAILC_CPB")) : 0;
   const int ncell = gd * gd * gd;
   int cpb = cpb_env > 0 ? (cpb_env + 63) / 64 * 64 : 4096;   // (8 x 160^3 inside the step: 42.38 ms with 2048, 42.20 with 4096, 42.87 with 1024)
   if (cpb > (ncell + 63) / 64 * 64) cpb = (ncell + 63) / 64 * 64;
   const unsigned mg1 = (unsigned)((0x100000000ULL + (unsigned)gd - 1) / (unsigned)gd), mg2 = (unsigned)((0x100000000ULL + (unsigned)(gd * gd) - 1) / (unsigned)(gd * gd));
   dim3 grid((unsigned)((ncell + cpb - 1) / cpb), 16, a.B);
-#define TC_LAUNCH(D) hipLaunchKernelGGL(tail_fwd_coarse_kernel<D>, grid, dim3(512), LDS, st, (const bf16_t*)x, stats, (const bf16_t*)xcoarse, (const bf16_t*)Wr, bt, a, V, slope, cpb, mg1, mg2)
-  if (dbg == 1) TC_LAUNCH(1); else if (dbg == 2) TC_LAUNCH(2); else if (dbg == 4) TC_LAUNCH(4); else if (dbg == 7) TC_LAUNCH(7); else TC_LAUNCH(0);
-#undef TC_LAUNCH
+  hipLaunchKernelGGL(tail_fwd_coarse_kernel, grid, dim3(512), LDS, st, (const bf16_t*)x, stats, (const bf16_t*)xcoarse, (const bf16_t*)Wr, bt, a, V, slope, cpb, mg1, mg2);
   NMH_CHECK_LAUNCH();
   return 0;
 }
@@ -2017,9 +1999,7 @@ int k_tail_fwd(const LossArgs& a, const void* x, const float* stats, const void*
     if (use_mfma && a.dt == NMH_DT_BF16 && C == 48 && !out && a.R % 4 == 0 && V < (1L << 31) && slope > 0.f && slope < 1.f) {
       const long vpm = (vpb + 127) / 128 * 128;   // whole 32-voxel steps per wave
       dim3 gm((unsigned)((V + vpm - 1) / vpm), a.B);
-      static const int tnt = getenv("NMH_TAIL_FWD_NT") ? atoi(getenv("NMH_TAIL_FWD_NT")) : 0;   // measured inside the step: 49.78 ms with, 49.51 without (three alternating runs each)
-      if (tnt && in_apply_streaming(V, a.B, C, a.dt)) hipLaunchKernelGGL(tail_fwd_mfma_kernel<true>, gm, dim3(256), 4 * 4 * 32 * 96 + 4 * 256, st, (const bf16_t*)x, stats, (const bf16_t*)r, a, V, slope, vpm);
-      else hipLaunchKernelGGL(tail_fwd_mfma_kernel<false>, gm, dim3(256), 4 * 4 * 32 * 96 + 4 * 256, st, (const bf16_t*)x, stats, (const bf16_t*)r, a, V, slope, vpm);
+      hipLaunchKernelGGL(tail_fwd_mfma_kernel, gm, dim3(256), 4 * 4 * 32 * 96 + 4 * 256, st, (const bf16_t*)x, stats, (const bf16_t*)r, a, V, slope, vpm);
       NMH_CHECK_LAUNCH();
       return 0;
     }

@@ -25,8 +25,6 @@
 // step slower (+2.5 ... +6.5 ms, DESIGN_HISTORY.md section 11) and round 5 removed them: the backward is the unfused, token-ordered chain of model._BlockFn.)
 #include "common.hpp"
 #include "kernels.hpp"
-#include <cstdlib>
-#include <cstdio>
 #include <type_traits>
 
 namespace sw {
@@ -88,7 +86,7 @@ template <int OFF> __device__ __forceinline__ void dma16(const char* src, char* 
 }
 
 // ---- a wave's private weight stream: linear in global memory, A steps of it in flight / unread in the wave's LDS ring ----
-template <int A, int DBG = 0> struct WStream {
+template <int A> struct WStream {
   const char* gsrc;     // wave's stream (global)
   char* ring;           // wave's ring (LDS), A * STEP_BYTES
   int total;            // steps in the stream
@@ -100,11 +98,9 @@ template <int A, int DBG = 0> struct WStream {
     asm volatile("" : "+v"(lv));
     const char* s = gsrc + (long)is_step * STEP_BYTES + lv * 16;
     char* d = ring + is_slot * STEP_BYTES;
-    if (!(DBG & 1)) {
-      // two address / M0 set-ups per step: the instruction's immediate offset advances the global AND the LDS address (13 bits: four pieces per base)
-      dma16<0>(s, d); dma16<1024>(s, d); dma16<2048>(s, d); dma16<3072>(s, d);
-      dma16<0>(s + 4096, d + 4096); dma16<1024>(s + 4096, d + 4096);
-    }
+    // two address / M0 set-ups per step: the instruction's immediate offset advances the global AND the LDS address (13 bits: four pieces per base)
+    dma16<0>(s, d); dma16<1024>(s, d); dma16<2048>(s, d); dma16<3072>(s, d);
+    dma16<0>(s + 4096, d + 4096); dma16<1024>(s + 4096, d + 4096);
     is_step = is_step + 1 == total ? 0 : is_step + 1;   // behind the end the stream wraps: the in-flight count stays constant (the data is never used)
     is_slot = is_slot + 1 == A ? 0 : is_slot + 1;
   }
@@ -284,25 +280,17 @@ __device__ __forceinline__ void ln_exchange(const bf16_t* __restrict__ x, RowFn&
 struct MlpFwdArgs {
   const bf16_t* x1; const float* gamma; const float* beta; const char* wstream; const float* b1; const float* b2;
   const float* rowscale; int rows_per_scale;
-  bf16_t* x2; bf16_t* x1n; bf16_t* hp; float* mean; float* rstd; long M; float eps; long long* ts; bf16_t* hact;
+  bf16_t* x2; bf16_t* x1n; bf16_t* hp; float* mean; float* rstd; long M; float eps; long long* ts /* unused */; bf16_t* hact;
   float* part; int* cnt;   // SPLIT: fp32 partial outputs [tile][segment][wave][24 tiles][64 lanes][4] and one arrival counter per row tile (zero between launches)
 };
 
 template <int NW, int A> constexpr int mlp_lds() { return NW * A * STEP_BYTES + (12 * NW * 1024 > 2 * NW * 4096 ? 12 * NW * 1024 : 2 * NW * 4096) + 4 * 96 * NW * 4; }
 
-// DBG & 8: wave 0 of workgroup 0 records the shader clock at phase boundaries (launchers print the differences)
-template <int DBG> __device__ __forceinline__ void stamp(long long* ts, int i) {
-  if ((DBG & 8) && ts && blockIdx.x == 0 && threadIdx.x == 0) ts[i] = (long long)__builtin_readcyclecounter();
-}
-template <int DBG> __device__ __forceinline__ void mmad(f32x4& acc, const Frag<bf16_t>& a, const Frag<bf16_t>& b) {   // DBG & 2: timing-only builds without the MFMAs
-  if (DBG & 2) asm volatile("" ::"v"(a.v), "v"(b.v)); else mma(acc, a, b);
-}
-
 // SPLIT: one workgroup per (row tile, segment of the hidden units); the workgroups of a tile leave their fp32 partial products in a.part, and the
 // one that arrives last (a.cnt) adds the others' to its own and runs the epilogue.  Block b -> tile 8 (b / 16) + b % 8, segment (b / 8) % 2: the
 // two workgroups of a tile are 8 blocks apart (same XCD under the round-robin block placement; correctness does not depend on it: the partials
 // and the counter are accessed device-coherently).
-template <int NW, int A, int DBG = 0, bool SPLIT = false>
+template <int NW, int A, bool SPLIT = false>
 __global__ __launch_bounds__(64 * NW) void swin_mlp_fwd_kernel(MlpFwdArgs a) {
   constexpr int KS = 3 * NW, C = 32 * KS, H = 4 * C, TPS = 4 / NW;   // TPS: row tiles whose activation a step of the first product carries
   constexpr int NSEG = mlp_segments(NW), R = MLP_ROUNDS / NSEG, SEG_STEPS = 2 * R * NW, MYSEG = SPLIT ? 1 : NSEG;
@@ -316,12 +304,10 @@ __global__ __launch_bounds__(64 * NW) void swin_mlp_fwd_kernel(MlpFwdArgs a) {
   const long rbase = tile * 64;
   if (SPLIT && rbase >= a.M) return;
 
-  stamp<DBG>(a.ts, 0);
-  WStream<A, DBG> ws;
+  WStream<A> ws;
   ws.init(a.wstream + ((long)wave * (NSEG * SEG_STEPS) + (long)seg0 * SEG_STEPS) * STEP_BYTES, smem + wave * A * STEP_BYTES, MYSEG * SEG_STEPS);
   Frag<bf16_t> wf[G];
   ws.start(wf, lane);
-  stamp<DBG>(a.ts, 1);
 
   Frag<bf16_t> af[4][KS];
   long rows[4];
@@ -365,7 +351,7 @@ __global__ __launch_bounds__(64 * NW) void swin_mlp_fwd_kernel(MlpFwdArgs a) {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) h[t][m][r] = (DBG & 4) ? h[t][m][r] : gelu_fast_f(h[t][m][r]);
+      for (int r = 0; r < 4; ++r) h[t][m][r] = gelu_fast_f(h[t][m][r]);
     const Frag<bf16_t> hf = pack_tr(h[0][m], h[1][m]);
     lds_write16(exch_a + ((c & 1) * NW + wave) * 4096 + m * 1024 + lane * 16, hf.v);
     if (a.hact && rows[m] >= 0) *reinterpret_cast<bf16x8*>(a.hact + (hprow[m] - a.hp) + 32 * NW * c) = hf.v;   // (only for the unfused backward)
@@ -390,7 +376,7 @@ __global__ __launch_bounds__(64 * NW) void swin_mlp_fwd_kernel(MlpFwdArgs a) {
 #pragma unroll
           for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int m = 0; m < 4; ++m) mmad<DBG>(h[t][m], w[2 * q + t], af[m][3 * u + q]);
+            for (int m = 0; m < 4; ++m) mma(h[t][m], w[2 * q + t], af[m][3 * u + q]);
         if (decltype(with_act)::value) {
 #pragma unroll
           for (int mm = 0; mm < TPS; ++mm) act_tile(c_act, hp, u * TPS + mm, bb);
@@ -412,7 +398,7 @@ __global__ __launch_bounds__(64 * NW) void swin_mlp_fwd_kernel(MlpFwdArgs a) {
 #pragma unroll
         for (int n = 0; n < 6; ++n)
 #pragma unroll
-          for (int m = 0; m < 4; ++m) mmad<DBG>(out[n][m], w[n], hf[m]);
+          for (int m = 0; m < 4; ++m) mma(out[n][m], w[n], hf[m]);
         if (u + 1 < NW) {
 #pragma unroll
           for (int m = 0; m < 4; ++m) hf[m] = hn[m];
@@ -420,20 +406,15 @@ __global__ __launch_bounds__(64 * NW) void swin_mlp_fwd_kernel(MlpFwdArgs a) {
       });
   };
 
-  stamp<DBG>(a.ts, 2);
 #pragma unroll 1
   for (int sg = 0; sg < MYSEG; ++sg) {
     const int c0 = (seg0 + sg) * R, cl = c0 + R - 1;
     fc1(hcur, std::false_type{}, 0, hcur);
-    if (sg == 0) stamp<DBG>(a.ts, 3);
 #pragma unroll 1
     for (int c = c0; c < cl; ++c) {
       fc1(hnxt, std::true_type{}, c, hcur);
-      if (c == 2) stamp<DBG>(a.ts, 4);
       wg_barrier();
-      if (c == 2) stamp<DBG>(a.ts, 5);
       fc2(c);
-      if (c == 2) stamp<DBG>(a.ts, 6);
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -449,7 +430,6 @@ __global__ __launch_bounds__(64 * NW) void swin_mlp_fwd_kernel(MlpFwdArgs a) {
     wg_barrier();
     fc2(cl);
   }
-  stamp<DBG>(a.ts, 7);
 
   if (SPLIT) {
     // partial products of this segment -> a.part (1 KB per store instruction, lane-linear), then the arrival counter of the tile
@@ -537,9 +517,7 @@ __global__ __launch_bounds__(64 * NW) void swin_mlp_fwd_kernel(MlpFwdArgs a) {
       }
     }
   }
-  stamp<DBG>(a.ts, 8);
   ws.drain();
-  stamp<DBG>(a.ts, 9);
 }
 
 // ================================================================================================
@@ -549,7 +527,7 @@ struct AttnFwdArgs {
   const bf16_t* x; const float* gamma; const float* beta; const char* wstream; const float* bqkv; const float* table; const float* bproj;
   const float* rowscale; int rows_per_scale;
   bf16_t* xnw; float* mean; float* rstd; bf16_t* qkv; bf16_t* o; float* lse; bf16_t* x1;
-  WinMap wm; float eps; long long* ts;
+  WinMap wm; float eps; long long* ts /* unused */;
   int tok_saves;   // xnw and o are written in TOKEN order ([T][C], pad rows dropped) -- the operands of token-ordered weight gradients (nmh_window_attn_bwd_tokens)
 };
 
@@ -570,7 +548,7 @@ template <int NW, int A> constexpr int attn_fwd_lds() {
   return NW * A * STEP_BYTES + (scratch > exch ? scratch : exch);
 }
 
-template <int NW, int A, int DBG = 0>
+template <int NW, int A>
 __global__ __launch_bounds__(64 * NW) void swin_attn_fwd_kernel(AttnFwdArgs a) {
   constexpr int KS = 3 * NW, C = 32 * KS, HEADS = KS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -583,12 +561,10 @@ __global__ __launch_bounds__(64 * NW) void swin_attn_fwd_kernel(AttnFwdArgs a) {
   const int nW = (a.wm.PH >> 2) * (a.wm.PW >> 2) * (a.wm.PD >> 2);
   const bool shifted = (a.wm.s0 + a.wm.s1 + a.wm.s2) > 0;
 
-  stamp<DBG>(a.ts, 0);
-  WStream<A, DBG> ws;
+  WStream<A> ws;
   ws.init(a.wstream + (long)wave * (4 * KS) * STEP_BYTES, smem + wave * A * STEP_BYTES, 4 * KS);
   Frag<bf16_t> wf[G];
   ws.start(wf, lane);
-  stamp<DBG>(a.ts, 1);
 
   // ---- gather + LN1 (the LayerNorm tile uses the scratch area before the bias table is staged there)
   Frag<bf16_t> xn[4][KS];
@@ -618,7 +594,6 @@ __global__ __launch_bounds__(64 * NW) void swin_attn_fwd_kernel(AttnFwdArgs a) {
     }
   }
   wg_barrier();
-  stamp<DBG>(a.ts, 2);
 
   Frag<bf16_t> of[3][4];      // this wave's heads: O fragments (token tile m, k = the head's 32 features)
   const float scale = 0.17677669529663689f;  // 32^-0.5
@@ -641,9 +616,8 @@ __global__ __launch_bounds__(64 * NW) void swin_attn_fwd_kernel(AttnFwdArgs a) {
 #pragma unroll
         for (int i = 0; i < 6; ++i)
 #pragma unroll
-          for (int m = 0; m < 4; ++m) mmad<DBG>(acc[i][m], w[i], xn[m][k]);
+          for (int m = 0; m < 4; ++m) mma(acc[i][m], w[i], xn[m][k]);
       });
-    if (j == 1) stamp<DBG>(a.ts, 3);
     // bias, stores in the unfused layout qkv[row][3C] (the packed pair of tiles = 8 consecutive features of the lane's token: 16-byte stores), V tile to LDS
     Frag<bf16_t> qf[4], kf[4];
 #pragma unroll
@@ -661,7 +635,6 @@ __global__ __launch_bounds__(64 * NW) void swin_attn_fwd_kernel(AttnFwdArgs a) {
       for (int t = 0; t < 2; ++t) lds_write8(sV_a + (16 * m + li) * VRS + (16 * t + 4 * g) * 2, pack4(acc[4 + t][m]));   // feature 8g+4t+r at column 16t+4g+r
     }
     lgk0();
-    if (j == 1) stamp<DBG>(a.ts, 4);
     // S^T = K Q^T: key j = 16 jt + 4 g + r, query i = 16 it + li
     f32x4 s[4][4];
 #pragma unroll
@@ -701,7 +674,6 @@ __global__ __launch_bounds__(64 * NW) void swin_attn_fwd_kernel(AttnFwdArgs a) {
         for (int r = 0; r < 4; ++r) s[jt][it][r] *= inv;
       if (g == 0) a.lse[(win * HEADS + h) * 64 + i] = mx + __logf(sum);
     }
-    if (j == 1) stamp<DBG>(a.ts, 5);
     // O^T = V^T P^T: feature 8 g + 4 dt + r of query li
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
@@ -729,7 +701,6 @@ __global__ __launch_bounds__(64 * NW) void swin_attn_fwd_kernel(AttnFwdArgs a) {
   }
 
   // ---- O of all heads to every wave (the exchange area aliases the attention scratch: everyone is done with it first)
-  stamp<DBG>(a.ts, 6);
   wg_barrier();
   const unsigned ex_a = lds_addr(scratch);
 #pragma unroll
@@ -742,7 +713,6 @@ __global__ __launch_bounds__(64 * NW) void swin_attn_fwd_kernel(AttnFwdArgs a) {
 #pragma unroll
     for (int k = 0; k < KS; ++k) xn[m][k].v = *reinterpret_cast<const bf16x8*>(scratch + (k * 4 + m) * 1024 + lane * 16);
 
-  stamp<DBG>(a.ts, 7);
   // ---- proj: this wave's 96 output channels
   f32x4 pacc[6][4];
 #pragma unroll
@@ -755,9 +725,8 @@ __global__ __launch_bounds__(64 * NW) void swin_attn_fwd_kernel(AttnFwdArgs a) {
 #pragma unroll
       for (int n = 0; n < 6; ++n)
 #pragma unroll
-        for (int m = 0; m < 4; ++m) mmad<DBG>(pacc[n][m], w[n], xn[m][k]);
+        for (int m = 0; m < 4; ++m) mma(pacc[n][m], w[n], xn[m][k]);
     });
-  stamp<DBG>(a.ts, 8);
   {
     uint4 xres[4][3];
     float4 bpv[6];
@@ -791,9 +760,7 @@ __global__ __launch_bounds__(64 * NW) void swin_attn_fwd_kernel(AttnFwdArgs a) {
       }
     }
   }
-  stamp<DBG>(a.ts, 9);
   ws.drain();
-  stamp<DBG>(a.ts, 10);
 }
 
 
@@ -822,15 +789,6 @@ template <class K> int set_lds(K kernel, int bytes) {   // per device: a second 
   return 0;
 }
 constexpr int RING_A = 4;
-long long* ts_buf() { static long long* p = nullptr; if (!p) { hipMalloc(&p, 64 * sizeof(long long)); hipMemset(p, 0, 64 * sizeof(long long)); } return p; }
-void ts_print(const char* what, int n, hipStream_t st) {
-  long long h[64];
-  hipStreamSynchronize(st);
-  hipMemcpy(h, ts_buf(), sizeof(h), hipMemcpyDeviceToHost);
-  fprintf(stderr, "[swin ts] %s:", what);
-  for (int i = 1; i < n; ++i) fprintf(stderr, " %d-%d: %lld", i - 1, i, h[i] - h[i - 1]);
-  fprintf(stderr, "  total %lld\n", h[n - 1] - h[0]);
-}
 }  // namespace
 
 int k_swin_supported(int C) { return C == 96 || C == 192 || C == 384; }
@@ -870,27 +828,11 @@ long k_swin_mlp_split_ws_bytes(long M, int C) {
 }
 template <int NW> static int launch_mlp_fwd(const sw::MlpFwdArgs& a, hipStream_t st) {
   constexpr int lds = sw::mlp_lds<NW, RING_A>();
-  const int dbg = getenv("NMH_SWIN_DBG") ? atoi(getenv("NMH_SWIN_DBG")) : 0;   // timing-only variants (wrong results): 1 no weight DMA, 2 no MFMAs, 4 no GELU / softmax
-  if (NW == 4 && dbg) {
-#define DBG_CASE(D) case D: if (int e = set_lds(sw::swin_mlp_fwd_kernel<4, RING_A, D>, lds)) return e; \
-    hipLaunchKernelGGL((sw::swin_mlp_fwd_kernel<4, RING_A, D>), dim3((unsigned)((a.M + 63) / 64)), dim3(256), lds, st, a); break;
-    if (dbg == 8) {
-      sw::MlpFwdArgs b = a; b.ts = ts_buf();
-      if (int e = set_lds(sw::swin_mlp_fwd_kernel<4, RING_A, 8>, lds)) return e;
-      hipLaunchKernelGGL((sw::swin_mlp_fwd_kernel<4, RING_A, 8>), dim3((unsigned)((a.M + 63) / 64)), dim3(256), lds, st, b);
-      ts_print("mlp_fwd  start|ln|fc1(0)|.. round2: fc1+act|barrier|fc2 ..|tail|epilogue|drain", 10, st);
-      return 0;
-    }
-    switch (dbg) { DBG_CASE(1) DBG_CASE(2) DBG_CASE(3) DBG_CASE(4) DBG_CASE(6) DBG_CASE(7) default: return -4; }
-#undef DBG_CASE
-    NMH_CHECK_LAUNCH();
-    return 0;
-  }
   if constexpr (NW == 4) {
     if (a.part) {   // (k_swin_mlp_fwd: a workspace was passed and the row tiles alone would leave half of the CUs idle)
-      if (int e = set_lds(sw::swin_mlp_fwd_kernel<NW, RING_A, 0, true>, lds)) return e;
+      if (int e = set_lds(sw::swin_mlp_fwd_kernel<NW, RING_A, true>, lds)) return e;
       const long tiles = (a.M + 63) / 64;
-      hipLaunchKernelGGL((sw::swin_mlp_fwd_kernel<NW, RING_A, 0, true>), dim3((unsigned)((tiles + 7) / 8 * 16)), dim3(64 * NW), lds, st, a);
+      hipLaunchKernelGGL((sw::swin_mlp_fwd_kernel<NW, RING_A, true>), dim3((unsigned)((tiles + 7) / 8 * 16)), dim3(64 * NW), lds, st, a);
       NMH_CHECK_LAUNCH();
       return 0;
     }
@@ -919,23 +861,6 @@ int k_swin_mlp_fwd(const void* x1, const float* gamma, const float* beta, const 
 
 template <int NW> static int launch_attn_fwd(const sw::AttnFwdArgs& a, long nwin, hipStream_t st) {
   constexpr int lds = sw::attn_fwd_lds<NW, RING_A>();
-  const int dbg_all = getenv("NMH_SWIN_DBG") ? atoi(getenv("NMH_SWIN_DBG")) : 0;
-  const int dbg = dbg_all & 3;
-  if (NW == 4 && dbg_all == 8) {
-    sw::AttnFwdArgs b = a; b.ts = ts_buf();
-    if (int e = set_lds(sw::swin_attn_fwd_kernel<4, RING_A, 8>, lds)) return e;
-    hipLaunchKernelGGL((sw::swin_attn_fwd_kernel<4, RING_A, 8>), dim3((unsigned)nwin), dim3(256), lds, st, b);
-    ts_print("attn_fwd  start|ln+table|heads0..: qkv(1)|pack+stores(1)|S+softmax(1)|PV(1)+head2|exchange|proj|epilogue|drain", 11, st);
-    return 0;
-  }
-  if (NW == 4 && dbg) {
-#define DBG_CASE(D) case D: if (int e = set_lds(sw::swin_attn_fwd_kernel<4, RING_A, D>, lds)) return e; \
-    hipLaunchKernelGGL((sw::swin_attn_fwd_kernel<4, RING_A, D>), dim3((unsigned)nwin), dim3(256), lds, st, a); break;
-    switch (dbg) { DBG_CASE(1) DBG_CASE(2) DBG_CASE(3) default: return -4; }
-#undef DBG_CASE
-    NMH_CHECK_LAUNCH();
-    return 0;
-  }
   if (int e = set_lds(sw::swin_attn_fwd_kernel<NW, RING_A>, lds)) return e;
   hipLaunchKernelGGL((sw::swin_attn_fwd_kernel<NW, RING_A>), dim3((unsigned)nwin), dim3(64 * NW), lds, st, a);
   NMH_CHECK_LAUNCH();

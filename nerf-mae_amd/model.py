@@ -394,12 +394,6 @@ class _BlockFn(torch.autograd.Function):
                 q.flush_due()   # the previous stage's weight gradients fork off BEHIND this stage's first input-gradient kernel (ops.WgradQueue.request_flush)
             wgrad(dx2, h_act, b.mlp[3], rowscale=sd2)
             wgrad(dh, x1n, b.mlp[0])
-            if q is not None and ops.EARLY_MLP_WGRAD:
-                # (NMH_EARLY_MLP_WGRAD=1, off by default) every block that takes the fused MLP backward -- with the default MLP_FUSED_WIDTHS = {96} that is
-                # stage 0, the end of the backward pass: the MLP pair's gradients -- 10 of the block's 16 operand passes -- start under the block's own
-                # attention-branch chain instead of waiting for the stage flush.  The flush is a background flush of EVERYTHING queued so far (LayerNorm /
-                # pad items included): it splits the stage's grouped launches per block
-                q.flush()
         else:
             dh = ops.gemm_nt(dx2, pk[key + "fc2.wT"].view(4 * C, C), act=2, C2=h_pre, rowscale=sd2, rows_per_scale=tps)
             if q is not None:
@@ -699,11 +693,7 @@ class _UpBlockFn(torch.autograd.Function):
         defer = ops.DEFER_DECODER_WGRAD and getattr(m, "_wq", None) is not None and not (ctx.c48 or ctx.c64)
 
         def side(fn):
-            if defer and ops.DEC_WGRAD_NOW:
-                # issued right away on the forked side stream (no join before the end of the backward pass): the small decoder levels' input-gradient chain
-                # is a string of latency-bound launches that leaves most of the chip idle, the side stream has nothing else to do there
-                m._wq.launch_now(fn)
-            elif defer:
+            if defer:
                 m._wq.defer(fn)
             else:
                 with ops.side_stream(enable=not (ctx.c48 or ctx.c64)):
@@ -735,26 +725,16 @@ class _UpBlockFn(torch.autograd.Function):
         if not cdg:
             conv(dy1.view(B, S, S, S, Cout), "c1.wd", Cc, out=dcat.view(B, S, S, S, Cc), accumulate=not m.has_proj)
         if ctx.cc:   # decoder1: conv1's weight gradient through the composition (a quarter of the FLOPs, contraction over the coarse cells; csrc/cconv.hip)
-            # the persistent G kernel on the main stream; reduce / border sums / chain rules (0.5 ms of small launches that only feed weight gradients) behind
-            # it on the side stream, or with the encoder's next weight-gradient flush
-            cw = lambda ph: ops.cconv_wgrad(x.view(B, v, v, v, Cin), dy1.view(B, S, S, S, Cout), pk.cconv[3], m.transp_conv.bias, g_c1, B, v,  # noqa: E731
-                                            dWt=_gradbuf(m.transp_conv.weight) if cdg else None, dbt=_gradbuf(m.transp_conv.bias) if cdg else None, phase=ph)
-            if not ops.side_stream.enabled or not ops.CCONV_WGRAD_SPLIT:
-                cw(0)
-            else:
-                cw(1)
-                if ops.DEFER_DECODER_WGRAD and getattr(m, "_wq", None) is not None:
-                    m._wq.defer(lambda: cw(2))
-                else:
-                    with ops.side_stream():
-                        cw(2)
+            # all on the main stream: the persistent G kernel, then its reduce / border sums / chain rules
+            ops.cconv_wgrad(x.view(B, v, v, v, Cin), dy1.view(B, S, S, S, Cout), pk.cconv[3], m.transp_conv.bias, g_c1, B, v,
+                            dWt=_gradbuf(m.transp_conv.weight) if cdg else None, dbt=_gradbuf(m.transp_conv.bias) if cdg else None)
         else:
             side(lambda: wgrad(dy1.view(B, S, S, S, Cout), cat.view(B, S, S, S, Cc), g_c1))
         if m.has_proj:
             ops.gemm_nt(dy3, pk[key + "c3.wT"].view(Cc, Cout), out=dcat, accumulate=True)
             g_c3 = _gradbuf(m.conv_block.conv3.weight)
             if defer:
-                (m._wq.launch_now if ops.DEC_WGRAD_NOW else m._wq.defer)(lambda: ops.gemm_tn(dy3, cat, g_c3))
+                m._wq.defer(lambda: ops.gemm_tn(dy3, cat, g_c3))
             else:
                 with ops.side_stream():
                     ops.gemm_tn(dy3, cat, g_c3)
@@ -767,12 +747,8 @@ class _UpBlockFn(torch.autograd.Function):
         if cdg:
             ops.cconv_dgrad(dy1, pk.cconv[5], B, v, add=dx, out=dx)
         g_tw, g_tb = _gradbuf(m.transp_conv.weight), _gradbuf(m.transp_conv.bias)
-        if (ctx.c48 or ctx.c64) and ops.UPW_EARLY and ops.WQ_LATE_JOIN and ops.side_stream.enabled and getattr(m, "_wq", None) is not None:
-            # decoder1 (the FIRST block of the backward pass): queued, its 1.5 ms would join the weight gradients of every later level in front of the
-            # encoder's on the side stream, which is busy from the stage-3 flush to the end of the step; issued here it runs under the small decoder levels
-            m._wq.launch_now(lambda: ops.upconv_wgrad(dcat, x, g_tw, g_tb, B, v, k, Cin, Cout))
-        elif defer or (ops.DEFER_DECODER_WGRAD and getattr(m, "_wq", None) is not None):
-            (m._wq.launch_now if ops.DEC_WGRAD_NOW else m._wq.defer)(lambda: ops.upconv_wgrad(dcat, x, g_tw, g_tb, B, v, k, Cin, Cout))
+        if ops.DEFER_DECODER_WGRAD and getattr(m, "_wq", None) is not None:   # (decoder1 too: only its conv weight gradients stay out of the queue)
+            m._wq.defer(lambda: ops.upconv_wgrad(dcat, x, g_tw, g_tb, B, v, k, Cin, Cout))
         else:
             with ops.side_stream():
                 ops.upconv_wgrad(dcat, x, g_tw, g_tb, B, v, k, Cin, Cout)
@@ -1150,17 +1126,6 @@ class SwinTransformer_MAE3D_New(nn.Module):
             self._packer.wait_late()
         grouped = ops.GROUPED_WGRAD and self.compute_dtype == torch.bfloat16 and torch.is_grad_enabled() and x.requires_grad
         groups = red.chunk_groups if (red is not None and si == getattr(red, "chunk_stage", -1) and red.chunk_groups) else [list(self.stages[si])]
-        if red is None and grouped and ops.STAGE_FLUSH_BLOCKS > 0 and len(groups) == 1:
-            # a long stage (stage 2: 18 blocks) flushes its queued weight gradients every STAGE_FLUSH_BLOCKS blocks: flushed once at the stage's end they all
-            # run under stage 1 / stage 0, while the side stream idles for the last two thirds of the stage's own input-gradient chain (round-5 trace)
-            nblk = sum(1 for mod in groups[0] if isinstance(mod, SwinBlock3D))
-            if nblk > ops.STAGE_FLUSH_BLOCKS:
-                from .dist import stage_chunk_groups
-                groups = stage_chunk_groups(self, si, -(-nblk // ops.STAGE_FLUSH_BLOCKS))
-        if red is None and si == 0 and grouped and ops.STAGE0_BLOCK_FLUSH and len(groups) == 1 and len(groups[0]) > 1:
-            # stage 0 is the END of the backward pass: flushed as a whole, all of its weight gradients run exposed after the last input-gradient
-            # kernel; per block, the second block's run under the first block's chain
-            groups = [[mod] for mod in groups[0]]
         for k, grp in enumerate(groups):
             if red is not None:
                 x = red.trigger(x, red.seg_stage(si, k))  # backward reaching here => this range's gradients are complete

@@ -58,8 +58,7 @@ class side_stream:
             return self
         dev = torch.cuda.current_device()
         if dev not in side_stream._streams:
-            prio = __import__("os").environ.get("NMH_SIDE_PRIORITY")   # (experiment: HIP stream priority of the side queue; larger = lower)
-            side_stream._streams[dev] = torch.cuda.Stream(device=dev) if prio is None else torch.cuda.Stream(device=dev, priority=int(prio))
+            side_stream._streams[dev] = torch.cuda.Stream(device=dev)
         self.s = side_stream._streams[dev]
         self.s.wait_stream(torch.cuda.current_stream())
         self.ctx = torch.cuda.stream(self.s)
@@ -163,20 +162,15 @@ class _TnProblem(ctypes.Structure):   # include/nerfmae_hip.h: nmh_tn_problem
 
 GROUPED_WGRAD = __import__("os").environ.get("NMH_TNG", "1") != "0"
 DEFER_DECODER_WGRAD = __import__("os").environ.get("NMH_DEFER_DEC", "1") == "1"
-DEC_WGRAD_NOW = __import__("os").environ.get("NMH_DEC_WGRAD_NOW", "0") == "1"   # small decoder levels: weight gradients issued on the side stream as soon as their operands exist instead of with the stage-3 flush
-UPW_EARLY = __import__("os").environ.get("NMH_UPW_EARLY", "0") == "1"   # decoder1 transpose-conv weight gradient on the side stream at the end of its block instead of queued (measured 51.1 / 51.0 vs 50.9 / 51.0 ms: off)
 WQ_LATE_JOIN = __import__("os").environ.get("NMH_WQ_LATE_JOIN", "1") == "1"   # weight-gradient queue: join only at the end of the backward pass
 # A stage's flush forks off behind the FIRST input-gradient kernel of the next stage instead of in front of it (round 5).  In the captured graph both are
 # successors of the stage's last kernel; the HIP graph executor keeps the successor captured first on the predecessor's queue and gives the other one a new
 # queue plus a cross-queue wait -- and that wait was released only ~10 side kernels later (1 grid: 0.58 ms with the input-gradient queue idle at the
 # stage 3 -> 2 boundary, profiles/r5k_timeline_1grids.txt 6.86 -> 7.43 ms).  Captured first, the chain stays on its queue and the side launches take the wait.
 WQ_FLUSH_AFTER_FIRST = __import__("os").environ.get("NMH_WQ_FLUSH_AFTER_FIRST", "1") == "1"
-STAGE0_BLOCK_FLUSH = __import__("os").environ.get("NMH_STAGE0_BLOCK_FLUSH", "0") == "1"   # stage 0 flushes its queued weight gradients per block (measured 52.2-52.4 vs 52.0 ms at 8 grids: off)
 
 
 TNG_FOREGROUND = __import__("os").environ.get("NMH_TNG_FOREGROUND", "1") != "0"
-EARLY_MLP_WGRAD = __import__("os").environ.get("NMH_EARLY_MLP_WGRAD", "0") == "1"   # stage-0 blocks flush the MLP pair's weight gradients right behind the fused MLP backward
-STAGE_FLUSH_BLOCKS = int(__import__("os").environ.get("NMH_STAGE_FLUSH_BLOCKS", "0"))   # single GPU: encoder stages longer than this flush their queued weight gradients in groups of this many blocks (0: once per stage)
 
 
 class _LnReduceItem(ctypes.Structure):   # include/nerfmae_hip.h: nmh_ln_reduce_item
@@ -252,16 +246,6 @@ class WgradQueue:
             lst = groups[key] = []
             self.defer(lambda: window_pad_rows_colsum_grouped(lst, geom))   # (the list object: filled until the flush runs the closure)
         groups[key].append((x, out))
-
-    def launch_now(self, fn):
-        """issue a weight-gradient launch on the forked side stream right away (no join: the closure keeps its operands alive until the end-of-backward
-        join) -- for work whose operands are ready long before the next flush"""
-        with side_stream():
-            fn()
-        self.inflight.append(fn)
-        if not self._cb:
-            self._cb = True
-            torch.autograd.Variable._execution_engine.queue_callback(self._final)
 
     def add(self, A, B, dW, dbias=None, rowscale=None, rows_per_sample=None):
         _chk(A, B, dW, dbias, rowscale)
@@ -547,7 +531,6 @@ def upconv4_fwd(x, Wup, bt, out, B, v):
 
 
 CCONV_WGRAD = __import__("os").environ.get("NMH_CCONV_WGRAD", "1") != "0"   # conv1's weight gradient through the composition (with NMH_CCONV)
-CCONV_WGRAD_SPLIT = __import__("os").environ.get("NMH_CCONV_WGRAD_SPLIT", "0") != "0"   # its small launches on the side stream (measured: 52.36 vs 52.34 ms at 8 grids, 29.70 vs 29.64 at 4 -- off)
 _CCW_WS = {}
 
 
