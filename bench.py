@@ -6,13 +6,17 @@ One "step" = zero_grad + forward + backward (+ gradient all-reduce when N>1) + c
 
 Workload of `value`: BASELINE.json's headline config read literally -- swin_s, GLOBAL batch 8 x (4 x 160^3), DP = N: at N = 1 the
 whole batch of 8 grids runs on the one GPU, at N = 8 every GPU steps on 1 grid ("scaling": "strong").  `--batch-per-gpu B` fixes the
-per-GPU batch instead (weak scaling).  The same JSON line carries, under config.sweep, the 1-, 4- and 8-grids-per-GPU figures of this
-GPU (the headline's weak-scaling share, the reference's training recipe of train_mae3d.sh, and the whole headline batch).
+per-GPU batch instead (weak scaling).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: the 3x3x3 48->48 decoder conv, MFMA-bound; plus the three slowest
-HBM-bound kernels against 8 TB/s) and `cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample).
+A plain run does what the headline needs and nothing else: set up, warm up, time the steps, write --dump-outputs, print ONE JSON line
+(rank 0).  `--full` adds everything else this script measures, in the same line: under config.sweep the 1-, 4- and 8-grids-per-GPU
+figures of this GPU (the headline's weak-scaling share, the reference's training recipe of train_mae3d.sh, and the whole headline batch),
+at N > 1 the exposed gradient exchange, `roofline` (dominant kernel: the 3x3x3 48->48 decoder conv, MFMA-bound; plus the three slowest
+HBM-bound kernels against 8 TB/s), the fp32 mode and the other backbones from child runs, and `cpu_baseline` (the CPU oracle timed on the
+host cores on a bounded sample).  --no-sweep / --no-kernel-timing / --no-cpu-baseline leave parts of it out.
 
   python bench.py --gpus 1 --steps 10 --warmup 3
+  python bench.py --gpus 1 --steps 10 --warmup 3 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -90,9 +94,12 @@ def main():
                     help="fix the grids per GPU per step instead (weak scaling): 1 = the headline's share at DP=8, 4 = the reference's training "
                          "recipe (train_mae3d.sh: batch 32 on 8 GPUs; BASELINE configs[1])")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the 1/4/8 grids-per-GPU sweep legs (config.sweep)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything the headline does not need: the grids-per-GPU sweep, the exposed gradient "
+                         "exchange (N > 1), per-kernel and roofline figures, the fp32 mode, the other backbones and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-kernel and roofline figures")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: skip the 1/4/8 grids-per-GPU sweep legs (config.sweep)")
     ap.add_argument("--e2e", action="store_true", help="also time Trainer.fit on host-resident synthetic scenes (uint8 and fp32 storage)")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from Python each step instead of replaying the captured HIP graph")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -162,9 +169,14 @@ def main():
     # split over the ranks); config.sweep adds the weak legs at 8 and 1 grids per GPU, each with its own comm_ms_exposed
     sweep_sizes = [] if (args.no_sweep or args.eager) else [b for b in ((1, 4, 8) if world == 1 else (8, 1)) if b != Bg]
     nmax = max([Bg] + sweep_sizes)
+    # rank r's scenes take slots r * nmax + i whether or not the sweep runs, so a plain run steps on the same scenes as a --full one; it makes
+    # only the Bg it steps on
+    if not args.full:
+        sweep_sizes = []
+    nscenes = max([Bg] + sweep_sizes)
     # stored-format scenes (W,L,H,4 with raw density) go through the product input pipeline (density->alpha, layout, padding on the GPU)
-    scenes = [data.synthetic_scene(exts[(rank * nmax + i) % 3], seed=rank * 131 + i) for i in range(nmax)]
-    xb0, ext0 = data.GridBatcher(R, dev, normalize_density=True)(scenes, flags=[0] * nmax)
+    scenes = [data.synthetic_scene(exts[(rank * nmax + i) % 3], seed=rank * 131 + i) for i in range(nscenes)]
+    xb0, ext0 = data.GridBatcher(R, dev, normalize_density=True)(scenes, flags=[0] * nscenes)
     grids_all = [xb0[i, :, :e[0], :e[1], :e[2]].contiguous() for i, e in enumerate(ext0.tolist())]
     del xb0
     mask_rng = random.Random(1000 + rank)
@@ -251,7 +263,7 @@ def main():
     frac = lambda gps_per_gpu: round(gps_per_gpu * flops_fb / (PEAK_BF16_TFLOPS * 1e12), 4)  # noqa: E731
 
     comm_exposed = None
-    if world > 1:
+    if world > 1 and args.full:
         # the same K steps without the gradient exchange (every rank steps on its local gradients): the difference is the part of the
         # all-reduce that the backward did not hide
         dt_local, _ = run_leg(Bg, args.steps, args.warmup, use_reducer=False)
@@ -274,7 +286,9 @@ def main():
     sweep["%d_grids_per_gpu" % Bg] = {"grids_per_s": round(grids_per_s, 3), "ms_per_step": round(1e3 * dt / args.steps, 3),
                                       "whole_step_mfma_frac": frac(grids_per_s / world)}
     if world > 1:
-        sweep["%d_grids_per_gpu" % Bg].update({"scaling": scaling, "global_batch": Bg * world, "comm_ms_exposed": comm_exposed})
+        sweep["%d_grids_per_gpu" % Bg].update({"scaling": scaling, "global_batch": Bg * world})
+        if args.full:
+            sweep["%d_grids_per_gpu" % Bg]["comm_ms_exposed"] = comm_exposed
 
     # per-kernel durations with HIP events on the launch stream: a few extra eager steps on the same model/data right after
     # the timed region (graph replays cannot carry per-launch events; the kernels, shapes and data are identical).  The side stream
@@ -282,7 +296,7 @@ def main():
     # weight-gradient GEMMs overlap other kernels; rocprofv3 of the replay shows the same per-launch time, profiles/)
     prof = None
     ksteps = min(3, args.steps)
-    if not args.no_kernel_timing and rank == 0:
+    if args.full and not args.no_kernel_timing and rank == 0:
         side_was, ops.side_stream.enabled = ops.side_stream.enabled, False
         red_was, model._reducer = model._reducer, None
         ops.PROFILE = {}
@@ -297,7 +311,8 @@ def main():
         prof, ops.PROFILE = ops.PROFILE, None
         ops.side_stream.enabled = side_was
         model._reducer = red_was
-    barrier()
+    if args.full:
+        barrier()
 
     headline = (args.backbone == "swin_s" and R == 160 and args.dtype == "bf16")
     out = {
@@ -316,8 +331,9 @@ def main():
     }
     if world > 1:
         out["config"]["collective_ranks_verified"] = rccl_ranks
-        out["config"]["comm_ms_exposed"] = comm_exposed
         out["config"]["grad_comm_dtype"] = "bf16" if (reducer is not None and reducer.comm_dtype == torch.bfloat16) else "fp32"
+    if world > 1 and args.full:
+        out["config"]["comm_ms_exposed"] = comm_exposed
         # one record for the scaling run: `value` / config.sweep[<Bg>] = the strong leg (global batch 8 over N ranks), config.sweep["8_grids_per_gpu"] /
         # ["1_grids_per_gpu"] = the weak legs; comm_ms_exposed = step time with minus without the exchange (same K steps), comm_events = HIP-event
         # timestamps of a short extra leg: every range's all-reduce on the comm stream and what the compute stream waited for at the join
@@ -448,13 +464,13 @@ def main():
     if args.e2e and rank == 0 and world == 1:
         out["config"]["e2e"] = e2e_leg(model, args, R, sweep)
 
-    if rank == 0 and world == 1 and args.dtype == "bf16" and not (args.no_sweep or args.eager) and os.environ.get("NMH_BENCH_INNER") != "1":
+    if args.full and rank == 0 and world == 1 and args.dtype == "bf16" and not (args.no_sweep or args.eager) and os.environ.get("NMH_BENCH_INNER") != "1":
         fp = fp32_mode_leg(args)
         if fp:
             out["config"]["fp32_mode"] = fp
         if args.backbone == "swin_s" and os.environ.get("NMH_BENCH_OTHER_BACKBONES", "1") != "0":
             out["config"]["other_backbones"] = other_backbones_leg(args)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, R, exts)
     if rank == 0:
         print(json.dumps(out))

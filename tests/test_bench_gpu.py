@@ -13,14 +13,28 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("loss", "grad_norm", "params")
 
 
-def _bench(out_dir):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--resolution", "32", "--backbone", "swin_t",
-           "--no-cpu-baseline", "--no-kernel-timing", "--no-sweep", "--dump-outputs", str(out_dir)]
+def _run(*args):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--resolution", "32", "--backbone", "swin_t"] + list(args)
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
-    return json.loads(lines[0]), {n: np.load(os.path.join(out_dir, n + ".npy")) for n in NAMES}
+    return json.loads(lines[0])
+
+
+def _bench(out_dir):
+    d = _run("--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-kernel-timing", "--no-sweep", "--dump-outputs", str(out_dir))
+    return d, {n: np.load(os.path.join(out_dir, n + ".npy")) for n in NAMES}
+
+
+def test_bench_plain_run_is_lean():
+    """without --full the line carries the headline figure of the timed steps and none of the extra measurements"""
+    d = _run("--steps", "2", "--warmup", "1")
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "grids/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert "roofline" not in d and "cpu_baseline" not in d
+    assert list(d["config"]["sweep"]) == ["%d_grids_per_gpu" % d["config"]["grids_per_gpu"]]
+    assert not {"fp32_mode", "other_backbones", "timed_kernel_ms_per_step"} & set(d["config"])
 
 
 def test_bench_dump_outputs(tmp_path):

@@ -284,7 +284,7 @@ def test_bench_launches_its_own_ranks():
     env = dict(os.environ, NMH_BENCH_BACKEND="gloo", NMH_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--resolution", "32", "--backbone", "swin_t",
-                          "--no-cpu-baseline", "--no-kernel-timing"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline", "--no-kernel-timing"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
