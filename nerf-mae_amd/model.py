@@ -227,6 +227,12 @@ class _Packer:
         return self.views[key]
 
 
+def centered_wgrad_ok(B: int, S: int) -> bool:
+    """the part of decoder1's centered-form gate that conv2's scaled weight gradient (ops.conv3d_k3_c48_wgrad_scaled) needs on a B x S^3 map: every one
+    of its 8 XCD tile ranges of 4x4x16 tiles lies inside one sample (the entry refuses other shapes)"""
+    return B in (1, 2, 4, 8) and S % 16 == 0 and ((S // 4) ** 2 * (S // 16)) % (8 // B) == 0
+
+
 def _gradbuf(p: nn.Parameter) -> Tensor:
     if p.grad is None:
         p.grad = torch.zeros_like(p)
@@ -572,7 +578,7 @@ class _UpBlockFn(torch.autograd.Function):
         # centered form (csrc/cconv.hip, round 6): the mean of conv1's output comes from the coarse tensor, conv1 stores z = lrelu(y1 - mean), 1 / std goes into conv2's
         # weights per sample; the backward reads z.  Needs the launches that read it (fused sums in conv2's input gradient, the background InstanceNorm backward, the
         # scaled weight-gradient reduce: B in {1, 2, 4, 8}) -- otherwise the classic form below
-        cz = (cc is not None and ops.CCONV_CENTERED and cc[6] is not None and B in (1, 2, 4, 8) and S % 16 == 0 and ((S // 4) ** 2 * (S // 16)) % (8 // B) == 0
+        cz = (cc is not None and ops.CCONV_CENTERED and cc[6] is not None and centered_wgrad_ok(B, S)
               and ops.C48_BWD_REDUCE and ops.INBWD_BG
               and ops.side_stream.enabled and ops.CCONV_WGRAD and v <= 40 and cc[5] is not None)
         ctx.cz = cz
