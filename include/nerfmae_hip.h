@@ -377,6 +377,26 @@ NMH_API int nmh_voxel_sr_loss_bwd(const float* pred, const float* target, int B,
  * (mIoULoss_new, metrics.py:194-245); out fp32[2] = {loss, mean soft IoU}.  _bwd: dlogits = gscale * d(loss)/d(logits).  K <= 32. */
 NMH_API int nmh_masked_ce_fwd(const float* logits, const float* labels, const float* class_weights, int B, int K, int64_t V, double* sums, double* iou_sums, float* out, void* stream);
 NMH_API int nmh_masked_ce_bwd(const float* logits, const float* labels, const float* class_weights, int B, int K, int64_t V, const double* sums, float gscale, float* dlogits, void* stream);
+/* ---- the reference's two native (CUDA) ops, both on the downstream path that the pretrained encoder + FPN feeds ----
+ * Rotated 3-D RoIAlign (nerf_rpn/model/rotated_align/src/cuda_3d/ROIAlignRotated3D_cuda.cu RoIAlignRotated3DForward / ...BackwardFeature, bound by
+ * rotated_align/roi_align_rotate_3d.py:10-47, used by detector.py:192-193).  rois [N][8] fp32 = {batch index, centre (w,l,h), size (w,l,h), angle in
+ * degrees}; centre and size are multiplied by spatial_scale, sizes clamped to >= 1; a bin is the mean over sampling_ratio^3 trilinear samples
+ * (sampling_ratio <= 0: ceil(size / pooled) per axis), rotated about the h axis.
+ *   layout 0: input channels-last (B,W,L,H,C) in dt (0 fp32, 1 bf16; fp32 accumulation), out [N,PW,PL,PH,C] in dt; C % 8 == 0, else -2;
+ *   layout 1: input NCWLH fp32 (the reference's layout), out [N,C,PW,PL,PH] fp32; dt must be 0.
+ * _bwd: dinput (the input's shape, ALWAYS fp32, zeroed by the caller) += the adjoint of dout (out's shape and type), by fp32 atomic adds.
+ * Voxel (x,y,z) is element (x*L + y)*H + z.  The reference indexes (x*W + y)*L + z in the forward and mixes x*L / x*W in the backward, which is the
+ * same element only when W == L == H: identical to the reference on cubic maps, correct on the rest.  An ROI whose batch index is outside [0, B)
+ * gives zeros and no gradient.  N == 0 returns 0 without a launch. */
+NMH_API int nmh_roi_align_rotated_3d_fwd(int layout, int dt, const void* input, const float* rois, void* out, int N, int B, int W, int L, int H, int C, int PW, int PL, int PH, float spatial_scale, int sampling_ratio, void* stream);
+NMH_API int nmh_roi_align_rotated_3d_bwd(int layout, int dt, const void* dout, const float* rois, float* dinput, int N, int B, int W, int L, int H, int C, int PW, int PL, int PH, float spatial_scale, int sampling_ratio, void* stream);
+/* Vertex sort of the oriented-box IoU losses (nerf_rpn/model/rotated_iou/cuda_op/sort_vert_kernel.cu:42-130, bound by cuda_op/sort_vert.cpp and
+ * cuda_ext.py:7-22, called from box_intersection_2d.py:141): vertices [B,N,M,2] fp32 centred on the polygon, mask [B,N,M] one byte each,
+ * num_valid [B,N] -> idx [B,N,9]: the masked vertices in increasing polar angle over [0, 2 pi), entry num_valid repeats entry 0, the rest (and
+ * all nine when num_valid < 3) are the first unmasked j >= 8; two identical boxes (num_valid == 8, entries 0-3 again in 4-7) give entry 4 = entry 0
+ * and pads after it.  A vertex with y == 0, where the reference's comparison returns nothing, sorts by its angle (x > 0: 0, x < 0: pi).
+ * 9 <= M <= 32, else -4.  B*N == 0 returns 0 without a launch. */
+NMH_API int nmh_sort_vertices(const float* vertices, const unsigned char* mask, const int* num_valid, int* idx, int B, int N, int M, void* stream);
 /* Per-step host parameters of the training step in ONE launch, passed as kernel arguments (no host-to-device copies):
  *  - block_bits (HOST, nb^3 bits, bit (a*nb+b)*nb+c = 1: the 4x4x4-token block (a,b,c) is removed; window_masking_3d's raster order,
  *    swin_mae3d.py:1366-1373) is expanded to the token mask tokmask[g^3] (device, uint8; tokens outside the nb^3 blocks stay 0);

@@ -539,6 +539,26 @@ int nmh_masked_ce_bwd(const float* logits, const float* labels, const float* cla
   if (!logits || !labels || !sums || !dlogits) return -4;
   return k_masked_ce_bwd(logits, labels, class_weights, B, K, (long)V, sums, gscale, dlogits, ST);
 }
+int nmh_roi_align_rotated_3d_fwd(int layout, int dt, const void* input, const float* rois, void* out, int N, int B, int W, int L, int H, int C, int PW, int PL, int PH,
+                                 float spatial_scale, int sampling_ratio, void* stream) {
+  CLR();
+  if (N <= 0) return 0;
+  REQ(input, rois, out);
+  return k_roi_align_rotated_3d_fwd(layout, dt, input, rois, out, N, B, W, L, H, C, PW, PL, PH, spatial_scale, sampling_ratio, ST);
+}
+int nmh_roi_align_rotated_3d_bwd(int layout, int dt, const void* dout, const float* rois, float* dinput, int N, int B, int W, int L, int H, int C, int PW, int PL, int PH,
+                                 float spatial_scale, int sampling_ratio, void* stream) {
+  CLR();
+  if (N <= 0) return 0;
+  REQ(dout, rois, dinput);
+  return k_roi_align_rotated_3d_bwd(layout, dt, dout, rois, dinput, N, B, W, L, H, C, PW, PL, PH, spatial_scale, sampling_ratio, ST);
+}
+int nmh_sort_vertices(const float* vertices, const unsigned char* mask, const int* num_valid, int* idx, int B, int N, int M, void* stream) {
+  CLR();
+  if (B <= 0 || N <= 0) return 0;
+  REQ(vertices, mask, num_valid, idx);
+  return k_sort_vertices(vertices, mask, num_valid, idx, B, N, M, ST);
+}
 int nmh_step_params(const uint32_t* block_bits, int nb, int g, unsigned char* tokmask, const float* hyper, float* hyper_dev, const int* extents, int n_ext, int* extents_dev,
                     void* stream) {
   CLR();

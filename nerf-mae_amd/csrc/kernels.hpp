@@ -268,6 +268,13 @@ int k_sr_loss_fwd(const float* pred, const float* tgt, int B, long V, double* su
 int k_sr_loss_bwd(const float* pred, const float* tgt, int B, long V, const double* sums, float gscale, float* dpred, hipStream_t st);
 int k_masked_ce_fwd(const float* logits, const float* labels, const float* cw, int B, int K, long V, double* sums, double* iou, float* out, hipStream_t st);
 int k_masked_ce_bwd(const float* logits, const float* labels, const float* cw, int B, int K, long V, const double* sums, float gscale, float* dlogits, hipStream_t st);
+// ---- rotated.hip (the reference's two native downstream ops: rotated 3-D RoIAlign, polygon vertex sort) ----
+// layout 0: channels-last (B,W,L,H,C) in dt -> [N,PW,PL,PH,C] in dt; layout 1: NCWLH fp32 -> [N,C,PW,PL,PH] fp32.  dx is fp32 in both and is added to.
+int k_roi_align_rotated_3d_fwd(int layout, int dt, const void* x, const float* rois, void* out, int N, int B, int W, int L, int H, int C, int PW, int PL, int PH,
+                               float spatial_scale, int sampling_ratio, hipStream_t st);
+int k_roi_align_rotated_3d_bwd(int layout, int dt, const void* dout, const float* rois, float* dx, int N, int B, int W, int L, int H, int C, int PW, int PL, int PH,
+                               float spatial_scale, int sampling_ratio, hipStream_t st);
+int k_sort_vertices(const float* vertices, const unsigned char* mask, const int* num_valid, int* idx, int B, int N, int M, hipStream_t st);
 int k_step_params(const unsigned* bits, int nb, int g, unsigned char* tokmask, const float* hyper_host, float* hyper_dev, const int* ext_host, int n_ext, int* ext_dev, hipStream_t st);
 int k_grad_cast(int to_bf16, const void* src, void* dst, long n, float scale, hipStream_t st);
 

@@ -1418,3 +1418,55 @@ def masked_ce_bwd(logits, labels, class_weights, sums, gscale, dlogits):
     _chk(logits, labels, class_weights, sums, dlogits)
     B, K = logits.shape[:2]
     lib().call("nmh_masked_ce_bwd", logits, labels, class_weights, B, K, logits[0, 0].numel(), sums, gscale, dlogits, _st())
+
+
+# ---- the reference's two native downstream ops (csrc/rotated.hip) ------------------------------------------------------------------
+ROI_CHANNELS_LAST, ROI_NCWLH = 0, 1
+
+
+def _roi_args(rois, output_size):
+    if rois.dim() != 2 or rois.shape[1] != 8 or rois.dtype != torch.float32:
+        raise RuntimeError("rois must be an fp32 [N, 8] tensor: batch index, centre (w,l,h), size (w,l,h), angle in degrees")
+    pw, pl, ph = (int(v) for v in output_size)
+    return pw, pl, ph
+
+
+def roi_align_rotated_3d_fwd(x, rois, output_size, spatial_scale, sampling_ratio, layout):
+    """layout ROI_CHANNELS_LAST: x (B,W,L,H,C) fp32|bf16 -> [N,PW,PL,PH,C] in x's dtype; ROI_NCWLH: x (B,C,W,L,H) fp32 -> [N,C,PW,PL,PH]"""
+    _chk(x, rois)
+    pw, pl, ph = _roi_args(rois, output_size)
+    n = rois.shape[0]
+    if layout == ROI_CHANNELS_LAST:
+        B, W, L, H, C = x.shape
+        out = torch.empty((n, pw, pl, ph, C), dtype=x.dtype, device=x.device)
+    else:
+        B, C, W, L, H = x.shape
+        out = torch.empty((n, C, pw, pl, ph), dtype=x.dtype, device=x.device)
+    lib().call("nmh_roi_align_rotated_3d_fwd", layout, dt_of(x), x, rois, out, n, B, W, L, H, C, pw, pl, ph, spatial_scale, sampling_ratio, _st())
+    return out
+
+
+def roi_align_rotated_3d_bwd(dout, rois, input_shape, output_size, spatial_scale, sampling_ratio, layout):
+    """-> fp32 gradient of shape input_shape (zeroed here, then summed into by fp32 atomic adds), whatever dout's dtype"""
+    _chk(dout, rois)
+    pw, pl, ph = _roi_args(rois, output_size)
+    if layout == ROI_CHANNELS_LAST:
+        B, W, L, H, C = input_shape
+    else:
+        B, C, W, L, H = input_shape
+    dx = torch.zeros(tuple(input_shape), dtype=torch.float32, device=dout.device)
+    lib().call("nmh_roi_align_rotated_3d_bwd", layout, dt_of(dout), dout, rois, dx, rois.shape[0], B, W, L, H, C, pw, pl, ph, spatial_scale, sampling_ratio, _st())
+    return dx
+
+
+def sort_vertices(vertices, mask, num_valid):
+    """vertices [B,N,M,2] fp32, mask [B,N,M] bool, num_valid [B,N] int32 -> idx [B,N,9] int32"""
+    _chk(vertices, mask, num_valid)
+    if vertices.dtype != torch.float32 or mask.dtype != torch.bool or num_valid.dtype != torch.int32:
+        raise RuntimeError("sort_vertices needs fp32 vertices, a bool mask and int32 num_valid")
+    B, N, M = mask.shape
+    if tuple(vertices.shape) != (B, N, M, 2) or tuple(num_valid.shape) != (B, N):
+        raise RuntimeError("sort_vertices: vertices [B,N,M,2], mask [B,N,M], num_valid [B,N]")
+    idx = torch.empty((B, N, 9), dtype=torch.int32, device=vertices.device)
+    lib().call("nmh_sort_vertices", vertices, mask, num_valid, idx, B, N, M, _st())
+    return idx
