@@ -19,7 +19,7 @@ import random
 import os
 import struct
 from functools import partial
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -117,7 +117,7 @@ class _Packer:
     def __init__(self):
         self.items = []  # (key, param, mode, dims, numel)
         self.views = {}
-        self.cconv = None   # (decoder1 UpBlock3D, composed weight buffer, border table) when the composed forward applies
+        self.dec1 = None    # _Dec1Pack of the MAE decoder1 when its composed ConvTranspose o conv1 kernels apply
         self.swin_early = self.swin_late = None   # ctypes item arrays of the fused Swin-block weight streams (csrc/swin_block.hip), stages < / >= LATE_STAGE
 
     def add(self, key: str, p: nn.Parameter, mode: int):
@@ -201,18 +201,8 @@ class _Packer:
                 self._late_pending = True
             if sp < n:
                 ops.pack_weights(self.dt, self.descs, self.blk2desc[sp:], self.blkstart[sp:], n - sp)
-            if self.cconv is not None:    # decoder1: ConvTranspose o conv1 composed weights (csrc/cconv.hip), from the fp32 masters
-                up, Wcp, delta, ws, Wup, Wdp, mtab, Wres = self.cconv
-                if mtab is not None:   # + the table the centered forward's mean comes from
-                    ops.cconv_pack_centered(up.transp_conv.weight, up.conv_block.conv1.weight, up.transp_conv.bias, Wcp, delta, ws, mtab)
-                else:
-                    ops.cconv_pack(up.transp_conv.weight, up.conv_block.conv1.weight, up.transp_conv.bias, Wcp, delta, ws)
-                if Wup is not None:
-                    ops.upconv4_pack(ws, Wup)
-                if Wres is not None:   # the same weights as the fragments of the tail that forms the residual itself
-                    ops.tail_residual_pack(ws, Wres)
-                if Wdp is not None:
-                    ops.cconv_dgrad_pack(Wcp, Wdp)
+            if self.dec1 is not None:
+                self.dec1.pack()
 
     @staticmethod
     def join():
@@ -227,10 +217,136 @@ class _Packer:
         return self.views[key]
 
 
+class _Dec1Pack:
+    """operands of the MAE decoder1's composed ConvTranspose o conv1 kernels (csrc/cconv.hip), derived from the fp32 masters on every `_Packer.run`;
+    the optional buffers are None when the switch of the path that reads them was off at construction"""
+
+    def __init__(self, block: "UpBlock3D", device):
+        bf = dict(dtype=torch.bfloat16, device=device)
+        self.block = block
+        self.composed = torch.empty(ops.cconv_pack_numel(), **bf)                       # composed weights, fragment order of cconv_fwd
+        self.border = torch.empty((27, 48), device=device)                              # border / delta table of the composed bias
+        self.workspace = torch.empty(ops.cconv_pack_ws_floats(), dtype=torch.float32, device=device)   # the two weights as fp32 rows (cconv_wgrad reads it)
+        self.upconv4 = torch.empty(ops.upconv4_pack_numel(), **bf)                      # transpose-conv fragments of the persistent upconv4_fwd
+        self.dgrad = torch.empty(ops.cconv_dgrad_pack_numel(), **bf) if ops.CCONV_WGRAD else None    # composed weights, fragment order of cconv_dgrad
+        self.mean_table = torch.empty((27, 96, 48), dtype=torch.float32, device=device) if ops.CCONV_CENTERED else None   # centered form: conv1's output mean
+        self.tail_residual = torch.empty(ops.tail_residual_pack_numel(), **bf) if ops.TAIL_FROM_COARSE else None   # transpose-conv fragments of the tail
+
+    def optional(self) -> frozenset:
+        """names of the optional buffers held (an input of plan_up_block)"""
+        return frozenset(n for n in ("dgrad", "mean_table", "tail_residual") if getattr(self, n) is not None)
+
+    def pack(self):
+        up = self.block
+        Wt, W1, bt = up.transp_conv.weight, up.conv_block.conv1.weight, up.transp_conv.bias
+        if self.mean_table is not None:   # + the table the centered forward's mean comes from
+            ops.cconv_pack_centered(Wt, W1, bt, self.composed, self.border, self.workspace, self.mean_table)
+        else:
+            ops.cconv_pack(Wt, W1, bt, self.composed, self.border, self.workspace)
+        ops.upconv4_pack(self.workspace, self.upconv4)
+        if self.tail_residual is not None:   # the same weights as the fragments of the tail that forms the residual itself
+            ops.tail_residual_pack(self.workspace, self.tail_residual)
+        if self.dgrad is not None:
+            ops.cconv_dgrad_pack(self.composed, self.dgrad)
+
+
 def centered_wgrad_ok(B: int, S: int) -> bool:
     """the part of decoder1's centered-form gate that conv2's scaled weight gradient (ops.conv3d_k3_c48_wgrad_scaled) needs on a B x S^3 map: every one
     of its 8 XCD tile ranges of 4x4x16 tiles lies inside one sample (the entry refuses other shapes)"""
     return B in (1, 2, 4, 8) and S % 16 == 0 and ((S // 4) ** 2 * (S // 16)) % (8 // B) == 0
+
+
+class UpSwitches(NamedTuple):
+    """the `ops` switches and thresholds `plan_up_block` depends on, as plain values"""
+    tail_from_coarse: bool
+    tail_sign_mask: bool
+    cconv_wgrad: bool
+    cconv_centered: bool
+    c48_bwd_reduce: bool
+    inbwd_bg: bool
+    defer_decoder_wgrad: bool
+    side_stream: bool
+    c48mb_min_voxels: int
+    c64_min_voxels: int
+
+    @classmethod
+    def current(cls) -> "UpSwitches":
+        return cls(ops.TAIL_FROM_COARSE, ops.TAIL_SIGN_MASK, ops.CCONV_WGRAD, ops.CCONV_CENTERED, ops.C48_BWD_REDUCE, ops.INBWD_BG, ops.DEFER_DECODER_WGRAD,
+                   ops.side_stream.enabled, ops.C48MB_MIN_VOXELS, ops.C64_MIN_VOXELS)
+
+
+# conv family -> packed layouts of (conv1 forward, conv1 input gradient, conv2 forward, conv2 input gradient), in order of preference
+_CONV_LAYOUTS = {
+    "c48": ("c1.wk", "c1.wkd", "c2.wk", "c2.wkd"),          # Cin = Cout = 48 in bf16: LDS-halo kernel with fragment-ordered weights
+    "c48mb": ("c1.wkm", "c1.wkmd", "c2.wkm", "c2.wkmd"),    # multiples of 48 at a volume that fills the chip (40^3, 96 / 192 channels): the same kernel on 48-channel blocks
+    "c64": ("c1.w64", "c1.w64d", "c2.w64", "c2.w64d"),      # multiples of 64 (swin_b): LDS-halo kernel on 64-channel blocks
+    "generic": ("c1.w", "c1.wd", "c2.w", "c2.wd"),
+}
+
+
+class UpPlan(NamedTuple):
+    """which kernels one decoder level runs, forward and backward: decided once per forward by `plan_up_block`, kept on ctx (the layout of the saved tensors
+    depends on it, and the switches it is derived from are module globals that a test or a caller may change between forward and backward)"""
+    family: str              # key of _CONV_LAYOUTS; the four layout keys below are its row
+    c1_fwd: str
+    c1_dgrad: str
+    c2_fwd: str
+    c2_dgrad: str
+    proj: bool               # skip connection concatenated, 1x1 projection on the residual branch (UpBlock3D ties both to use_skip)
+    epilogue_stats: bool     # InstanceNorm statistics come out of the conv epilogue (no extra pass over the 160^3 tensor)
+    composed_fwd: bool       # decoder1: y1 straight from the coarse map with the composed weights (4x fewer FLOPs; cat is only the residual)
+    # decoder1: conv1's weight gradient through the composition (a quarter of the FLOPs, contraction over the coarse cells), and conv1's input gradient on the
+    # fine grid is never formed -- dx and the transpose conv's parameter gradients take their conv1 part through the composition, dcat keeps the residual branch's alone
+    composed_bwd: bool
+    # centered form (csrc/cconv.hip): the mean of conv1's output comes from the coarse tensor, conv1 stores z = lrelu(y1 - mean) in place of y1 (a1 is not formed),
+    # 1 / std goes into conv2's weights per sample; the backward reads z.  Needs the launches that read it (fused sums in conv2's input gradient, the background
+    # InstanceNorm backward, the scaled weight-gradient reduce: B in {1, 2, 4, 8})
+    centered: bool
+    # decoder1 in training: the residual u = ConvT(x) is read by the tail forward alone (the composed kernels take conv1's passes through the coarse tensor, the
+    # tail backward reads a sign mask), and the tail forms it from x on the matrix cores -- u (`cat`) is never stored (csrc/norm.hip: tail_fwd_coarse_kernel)
+    residual_in_tail: bool
+    fused_tail: bool         # d0 = lrelu(IN(y2) + cat) is consumed inside the tail kernels and rebuilt from (y2, cat) in the backward -- never stored
+    x_grad: bool             # the tail forward writes d(pred) for the backward
+    tail_bwd_sums: bool      # the reductions of the tail BACKWARD (InstanceNorm-backward sums, head weight gradient) are taken by the tail forward's pass
+    sign_mask: bool          # ... and then the sign of d0 is all the tail backward still needs of it: 6 bytes per voxel instead of the residual row
+    fused_reduce: bool       # the InstanceNorm-backward sums of (da1, y1) come out of conv2's input-gradient epilogue (no separate pass over both 160^3 tensors)
+    # decoder1: the HBM-bound InstanceNorm backward (needs conv2's input gradient only) streams on a forked stream UNDER conv2's weight gradient, as one small
+    # workgroup per CU beside the persistent kernel's (csrc/norm.hip: in_bwd_apply_bg_kernel); joined in front of its first consumer
+    # (the transpose conv's input gradient, a 4000-workgroup GEMM, does not ride along: one of its workgroups per CU at a time crawls -- 2.7 ms for 0.64)
+    bg_norm_bwd: bool
+    # Conv weight gradients run on the forked side stream -- except the persistent 160^3 kernels (c48 / c64), which own every CU: overlapping them with the next
+    # MFMA kernel OR with the HBM-bound InstanceNorm passes AS THEY ARE (100 k workgroups of 120 VGPRs) measured slower (51.2 vs 50.4 ms at 4 grids, 34.8 vs 30.8 ms
+    # at 1), so they stay on the main stream; only the pass as ONE small workgroup per CU (bg_norm_bwd) does overlap.
+    wgrad_main_stream: bool
+    defer_conv_wgrad: bool   # small-level conv weight gradients: queued on the encoder's weight-gradient queue and issued with its next flush, one fork for all of them
+    defer_upconv_wgrad: bool # the transpose conv's weight gradient likewise (decoder1 too: only its conv weight gradients stay out of the queue)
+
+
+def plan_up_block(cin: int, cout: int, k: int, has_proj: bool, layouts, dec1, B: int, v: int, dtype, x_grad: bool, tail: bool, tail_sums: bool,
+                  has_queue: bool, sw: UpSwitches) -> UpPlan:
+    """layouts: the keys of _CONV_LAYOUTS' rows packed for the block; dec1: `_Dec1Pack.optional()` of the record built for THIS block, or None;
+    tail / tail_sums: a loss tail is attached / its model's fuse_tail_sums; has_queue: the block has a weight-gradient queue.  Pure: plain values in, UpPlan out."""
+    S = v * k
+    bf16 = dtype == torch.bfloat16
+    fits = S ** 3 * (2 * cout if has_proj else cout) * 2 < 2 ** 32
+    has = lambda fam: all(n in layouts for n in _CONV_LAYOUTS[fam])  # noqa: E731
+    family = ("c48" if has("c48") else "c48mb" if has("c48mb") and S ** 3 >= sw.c48mb_min_voxels > 0 and fits
+              else "c64" if has("c64") and S ** 3 >= sw.c64_min_voxels > 0 and fits else "generic")
+    c48 = family == "c48"
+    composed_fwd = c48 and dec1 is not None and v % 8 == 0 and not has_proj
+    composed_bwd = composed_fwd and sw.cconv_wgrad and v <= 40 and "dgrad" in dec1
+    fused_tail = tail and not has_proj
+    tail_bwd_sums = tail and x_grad and tail_sums
+    sign_mask = tail_bwd_sums and sw.tail_sign_mask and bf16 and cout == 48 and fused_tail and S % 4 == 0
+    fused_reduce = c48 and sw.c48_bwd_reduce and S % 16 == 0
+    centered = (composed_bwd and sw.cconv_centered and "mean_table" in dec1 and centered_wgrad_ok(B, S) and sw.c48_bwd_reduce and sw.inbwd_bg and sw.side_stream)
+    residual_in_tail = (composed_bwd and sw.tail_from_coarse and "tail_residual" in dec1 and sign_mask and k == 4 and ops.tail_from_coarse_ok(S, cout, cin, dtype))
+    queue = sw.defer_decoder_wgrad and has_queue
+    main = family in ("c48", "c64")
+    return UpPlan(family, *_CONV_LAYOUTS[family], proj=has_proj, epilogue_stats=main, composed_fwd=composed_fwd, composed_bwd=composed_bwd, centered=centered,
+                  residual_in_tail=residual_in_tail, fused_tail=fused_tail, x_grad=x_grad, tail_bwd_sums=tail_bwd_sums, sign_mask=sign_mask, fused_reduce=fused_reduce,
+                  bg_norm_bwd=centered or (fused_reduce and sw.inbwd_bg and cout == 48 and bf16 and sw.side_stream), wgrad_main_stream=main,
+                  defer_conv_wgrad=queue and not main, defer_upconv_wgrad=queue)
 
 
 def _gradbuf(p: nn.Parameter) -> Tensor:
@@ -523,6 +639,16 @@ class _MergeFn(torch.autograd.Function):
         return dx, None, None
 
 
+def _conv3(family: str, X, W, Cout, stats_acc=None, **kw):
+    """3x3x3 conv by the kernel of an UpPlan's family, W the packed layout of that family (_CONV_LAYOUTS)"""
+    if family == "c48":
+        return ops.conv3d_k3_c48(X, W, stats_acc=stats_acc, **kw)
+    if family == "c64":
+        return ops.conv3d_k3_c64(X, W, Cout, stats_acc=stats_acc, **kw)
+    assert stats_acc is None   # (UpPlan.epilogue_stats: these two have no statistics epilogue)
+    return (ops.conv3d_k3_c48mb if family == "c48mb" else ops.conv3d_k3)(X, W, Cout, **kw)
+
+
 class _UpBlockFn(torch.autograd.Function):
     """ConvTranspose3d(k=s) -> cat(skip) -> UnetResBlock (unetr_block.py:57-71,193-200), channels-last."""
 
@@ -534,142 +660,108 @@ class _UpBlockFn(torch.autograd.Function):
         m: "UpBlock3D" = mod
         pk, key = m._pk, m._key
         k, Cin, Cout = m.k, m.cin, m.cout
-        k3, V = k ** 3, (v * k) ** 3
+        k3, S = k ** 3, v * k
+        V = S ** 3
         dev, dtype = x.device, x.dtype
-        has_skip = skip is not None
-        Cc = 2 * Cout if has_skip else Cout
-        cc = pk.cconv if ((key + "c1.wk") in pk.views and pk.cconv is not None and pk.cconv[0] is m and v % 8 == 0 and not has_skip) else None
-        # decoder1 in training (round 6): the residual u = ConvT(x) is read by the tail forward alone (the composed kernels take conv1's passes through the coarse
-        # tensor, the tail backward reads a sign mask), and the tail forms it from x on the matrix cores -- u is never stored (csrc/norm.hip: tail_fwd_coarse_kernel)
-        rx = (cc is not None and ops.TAIL_FROM_COARSE and cc[7] is not None and tail is not None and not m.has_proj and ctx.needs_input_grad[0]
-              and tail[0].fuse_tail_sums and ops.TAIL_SIGN_MASK and ops.CCONV_WGRAD and v <= 40 and cc[5] is not None and k == 4 and (key + "c2.wk") in pk.views
-              and ops.tail_from_coarse_ok(v * k, Cout, Cin, dtype))
-        ctx.rx = rx
-        cat = None if rx else torch.empty((B * V, Cc), dtype=dtype, device=dev)
-        if rx:
-            pass
-        elif cc is not None and cc[4] is not None:   # decoder1: persistent kernel, coarse fragments in registers (csrc/cconv.hip)
-            ops.upconv4_fwd(x.view(B, v, v, v, Cin), cc[4], m.transp_conv.bias, cat, B, v)
-        else:
-            ops.upconv_fwd(x, pk[key + "t.w"].view(k3 * Cout, Cin), m.transp_conv.bias, cat, B, v, k, Cin, Cout)   # pixel shuffle in the epilogue
-        if has_skip:
-            ops.copy_cols(skip.reshape(B * V, Cout), cat[:, Cout:])
-        S = v * k
+        p = ctx.plan = m._plan(B, v, dtype, ctx.needs_input_grad[0], tail)
+        d1 = pk.dec1
+        Cc = 2 * Cout if p.proj else Cout
+        xc = x.view(B, v, v, v, Cin)
         new_acc = lambda: ops.acc_zeros((B, Cout, 2), dev)   # noqa: E731  (one slice per reduction: arena slices are single-use)
+        # ---- residual branch: transpose conv (+ skip)
+        cat = None
+        if not p.residual_in_tail:
+            cat = torch.empty((B * V, Cc), dtype=dtype, device=dev)
+            if p.composed_fwd:   # decoder1: persistent kernel, coarse fragments in registers (csrc/cconv.hip)
+                ops.upconv4_fwd(xc, d1.upconv4, m.transp_conv.bias, cat, B, v)
+            else:
+                ops.upconv_fwd(x, pk[key + "t.w"].view(k3 * Cout, Cin), m.transp_conv.bias, cat, B, v, k, Cin, Cout)   # pixel shuffle in the epilogue
+        if p.proj:
+            ops.copy_cols(skip.reshape(B * V, Cout), cat[:, Cout:])
+        # ---- conv1 + statistics -> InstanceNorm -> LeakyReLU
         scratch = new_acc()
-        ctx.c64 = False
-        c48 = (key + "c1.wk") in pk.views and (key + "c2.wk") in pk.views
-        c48mb = (not c48 and (key + "c1.wkm") in pk.views and (key + "c2.wkm") in pk.views and S ** 3 >= ops.C48MB_MIN_VOXELS > 0
-                 and S ** 3 * Cc * 2 < 2 ** 32)
-        c64 = (not c48 and not c48mb and (key + "c1.w64") in pk.views and (key + "c2.w64") in pk.views and S ** 3 >= ops.C64_MIN_VOXELS > 0
-               and S ** 3 * Cc * 2 < 2 ** 32)
-        if c48:   # Cin = Cout = 48 in bf16: LDS-halo kernel with fragment-ordered weights ("c1.w" -> "c1.wk", "c1.wd" -> "c1.wkd")
-            conv = lambda X, nm, co, **kw: ops.conv3d_k3_c48(X, pk[key + nm.replace(".w", ".wk")], **kw)  # noqa: E731
-        elif c48mb:  # channel counts multiples of 48 at a volume that fills the chip (40^3, 96 / 192 channels): the same kernel on 48-channel blocks
-            conv = lambda X, nm, co, **kw: ops.conv3d_k3_c48mb(X, pk[key + nm.replace(".w", ".wkm")], co, **kw)  # noqa: E731
-        elif c64:  # channel counts multiples of 64 (swin_b): LDS-halo kernel on 64-channel blocks ("c1.w" -> "c1.w64", "c1.wd" -> "c1.w64d")
-            conv = lambda X, nm, co, **kw: ops.conv3d_k3_c64(X, pk[key + nm.replace(".w", ".w64")], co, **kw)  # noqa: E731
-        else:
-            conv = lambda X, nm, co, **kw: ops.conv3d_k3(X, pk[key + nm], co, **kw)  # noqa: E731
-        ctx.c64 = c64
-        halo_stats = c48 or c64    # InstanceNorm statistics come out of the conv epilogue
         st1 = torch.empty((B, Cout, 2), device=dev)
-        cc = cc if c48 else None
-        # centered form (csrc/cconv.hip, round 6): the mean of conv1's output comes from the coarse tensor, conv1 stores z = lrelu(y1 - mean), 1 / std goes into conv2's
-        # weights per sample; the backward reads z.  Needs the launches that read it (fused sums in conv2's input gradient, the background InstanceNorm backward, the
-        # scaled weight-gradient reduce: B in {1, 2, 4, 8}) -- otherwise the classic form below
-        cz = (cc is not None and ops.CCONV_CENTERED and cc[6] is not None and centered_wgrad_ok(B, S)
-              and ops.C48_BWD_REDUCE and ops.INBWD_BG
-              and ops.side_stream.enabled and ops.CCONV_WGRAD and v <= 40 and cc[5] is not None)
-        ctx.cz = cz
-        if cz:
-            mhat = ops.cconv_output_mean(x.view(B, v, v, v, Cin), cc[6], cc[2], B, v)
-            y1 = ops.cconv_fwd_centered(x.view(B, v, v, v, Cin), cc[1], cc[2], mhat, B, v, stats_acc=scratch).view(B * V, Cout)   # (y1 holds z)
-            ops.instnorm_finalize(scratch, st1, B, V, Cout)    # (mean of y1 - mhat: ~ 0; rstd)
-        elif cc is not None:   # decoder1: y1 straight from the coarse map with the composed weights (4x fewer FLOPs; cat is only the residual)
-            y1 = ops.cconv_fwd(x.view(B, v, v, v, Cin), cc[1], cc[2], B, v, stats_acc=scratch).view(B * V, Cout)
-            ops.instnorm_finalize(scratch, st1, B, V, Cout)
-        elif halo_stats:   # InstanceNorm statistics come out of the conv epilogue (no extra pass over the 160^3 tensor)
-            y1 = conv(cat.view(B, S, S, S, Cc), "c1.w", Cout, stats_acc=scratch).view(B * V, Cout)
+        if p.centered:
+            mhat = ops.cconv_output_mean(xc, d1.mean_table, d1.border, B, v)
+            y1 = ops.cconv_fwd_centered(xc, d1.composed, d1.border, mhat, B, v, stats_acc=scratch).view(B * V, Cout)   # (y1 holds z; statistics of y1 - mhat: mean ~ 0, rstd)
+        elif p.composed_fwd:
+            y1 = ops.cconv_fwd(xc, d1.composed, d1.border, B, v, stats_acc=scratch).view(B * V, Cout)
+        else:
+            y1 = _conv3(p.family, cat.view(B, S, S, S, Cc), pk[key + p.c1_fwd], Cout, stats_acc=scratch if p.epilogue_stats else None).view(B * V, Cout)
+        if p.epilogue_stats:
             ops.instnorm_finalize(scratch, st1, B, V, Cout)
         else:
-            y1 = conv(cat.view(B, S, S, S, Cc), "c1.w", Cout).view(B * V, Cout)
             ops.instnorm_stats(y1, st1, scratch, B, V, Cout)
         a1 = None
-        if not cz:
+        if not p.centered:
             a1 = torch.empty_like(y1)
             ops.instnorm_apply(y1, st1, a1, B, V, Cout)
+        # ---- conv2 + statistics
         st2 = torch.empty((B, Cout, 2), device=dev)
         scratch = new_acc()
-        if cz:
+        if p.centered:
             wk2 = torch.empty(B * ops.C48_IMG, dtype=dtype, device=dev)
             ops.conv48_pack_scaled(m.conv_block.conv2.weight, st1, wk2, B)
             y2 = ops.conv3d_k3_c48_per_sample(y1.view(B, S, S, S, Cout), wk2, stats_acc=scratch).view(B * V, Cout)
-            ops.instnorm_finalize(scratch, st2, B, V, Cout)
-        elif halo_stats:
-            y2 = conv(a1.view(B, S, S, S, Cout), "c2.w", Cout, stats_acc=scratch).view(B * V, Cout)
+        else:
+            y2 = _conv3(p.family, a1.view(B, S, S, S, Cout), pk[key + p.c2_fwd], Cout, stats_acc=scratch if p.epilogue_stats else None).view(B * V, Cout)
+        if p.epilogue_stats:
             ops.instnorm_finalize(scratch, st2, B, V, Cout)
         else:
-            y2 = conv(a1.view(B, S, S, S, Cout), "c2.w", Cout).view(B * V, Cout)
             ops.instnorm_stats(y2, st2, scratch, B, V, Cout)
+        # ---- last InstanceNorm + residual + LeakyReLU: the block's output, or inside the tail
         y3 = st3 = None
-        fused_tail = tail is not None and not m.has_proj
-        # fused tail: d0 = lrelu(IN(y2) + cat) is consumed inside the tail kernels and rebuilt from (y2, cat) in the backward -- never stored
-        out = None if fused_tail else torch.empty_like(y2)
-        if m.has_proj:
+        out = None if p.fused_tail else torch.empty_like(y2)
+        if p.proj:
             y3 = ops.gemm_nt(cat, pk[key + "c3.w"].view(Cout, Cc))
             st3 = torch.empty((B, Cout, 2), device=dev)
             ops.instnorm_stats(y3, st3, new_acc(), B, V, Cout)
             ops.instnorm_apply(y2, st2, out, B, V, Cout, r=y3, stats_r=st3, rmode=2)
-        elif not fused_tail:
+        elif not p.fused_tail:
             ops.instnorm_apply(y2, st2, out, B, V, Cout, r=cat, rmode=1)
-        ctx.m, ctx.dims, ctx.conv, ctx.c48 = m, (B, v, has_skip), conv, c48
-        ctx.cc = cc is not None and ops.CCONV_WGRAD and v <= 40
+        ctx.m, ctx.dims = m, (B, v)
         ctx.saved = (x, cat, y1, st1, a1, y2, st2, y3, st3, out)
         ctx.tail = None
-        if tail is not None:
-            assert not m.has_proj
-            model, xb, extents, tokmask, pred_out = tail
-            lsums = torch.empty(8, dtype=torch.float64, device=dev)
-            losses = torch.empty(3, device=dev)
-            dpred = torch.empty((B * V, 4), device=dev) if ctx.needs_input_grad[0] else None
-            # the reductions of the tail BACKWARD (InstanceNorm-backward sums, head weight gradient) are taken by the same pass
-            bsum = torch.empty(B * Cout * 4 + 4 * Cout, dtype=torch.float64, device=dev) if (dpred is not None and model.fuse_tail_sums) else None
-            # last InstanceNorm + residual + LeakyReLU, the 1x1 head and the loss terms in one pass over (y2, cat)
-            # with the backward's sums taken here, the sign of d0 is all the tail backward still needs of it: 6 bytes per voxel instead of the residual row
-            smask = (torch.empty((B * V, 8), dtype=torch.uint8, device=dev)
-                     if (bsum is not None and ops.TAIL_SIGN_MASK and dtype == torch.bfloat16 and Cout == 48 and out is None and S % 4 == 0) else None)
-            if rx:
-                assert smask is not None and bsum is not None and dpred is not None
-                ops.mae_tail_fwd_from_coarse(y2, st2, x.view(B, v, v, v, Cin), cc[7], m.transp_conv.bias, model.out.conv.weight, model.out.conv.bias, xb, extents, tokmask,
-                                             B, S, Cout, lsums, losses, dpred, bsum, smask, pred=pred_out)
-            else:
-                ops.mae_tail_fwd(y2, st2, cat, out, model.out.conv.weight, model.out.conv.bias, xb, extents, tokmask, B, S, Cout, lsums, losses,
-                                 pred_out, dpred, bwd_sums=bsum, sign_mask=smask)
-            ctx.tail = (model, lsums, dpred, bsum, smask)
-            return losses
-        return out
+        if tail is None:
+            return out
+        assert p.fused_tail
+        model, xb, extents, tokmask, pred_out = tail
+        lsums = torch.empty(8, dtype=torch.float64, device=dev)
+        losses = torch.empty(3, device=dev)
+        dpred = torch.empty((B * V, 4), device=dev) if p.x_grad else None
+        bsum = torch.empty(B * Cout * 4 + 4 * Cout, dtype=torch.float64, device=dev) if p.tail_bwd_sums else None
+        smask = torch.empty((B * V, 8), dtype=torch.uint8, device=dev) if p.sign_mask else None
+        # the 1x1 head and the loss terms in the same pass over (y2, cat)
+        if p.residual_in_tail:
+            ops.mae_tail_fwd_from_coarse(y2, st2, xc, d1.tail_residual, m.transp_conv.bias, model.out.conv.weight, model.out.conv.bias, xb, extents, tokmask,
+                                         B, S, Cout, lsums, losses, dpred, bsum, smask, pred=pred_out)
+        else:
+            ops.mae_tail_fwd(y2, st2, cat, out, model.out.conv.weight, model.out.conv.bias, xb, extents, tokmask, B, S, Cout, lsums, losses,
+                             pred_out, dpred, bwd_sums=bsum, sign_mask=smask)
+        ctx.tail = (model, lsums, dpred, bsum, smask)
+        return losses
 
     @staticmethod
     def backward(ctx, dout):
-        m = ctx.m
-        B, v, has_skip = ctx.dims
+        m, p = ctx.m, ctx.plan
+        B, v = ctx.dims
         x, cat, y1, st1, a1, y2, st2, y3, st3, out = ctx.saved
         pk, key = m._pk, m._key
         k, Cin, Cout = m.k, m.cin, m.cout
         k3, S = k ** 3, v * k
         V = S ** 3
-        Cc = cat.shape[1] if cat is not None else Cout
+        Cc = 2 * Cout if p.proj else Cout
         dev, dtype = x.device, x.dtype
+        # ---- last InstanceNorm + residual (or the tail): dy2, and the residual branch's gradient into dcat
         sums2 = ops.acc_zeros((B, Cout, 2), dev)
         dy2 = torch.empty_like(y2)
         dcat = torch.empty((B * V, Cc), dtype=dtype, device=dev)
         if ctx.tail is not None:   # d(loss)/d(losses[0]) == 1 (the reference calls loss.backward()); d(d0) is never materialised
             model, lsums, dpred, bsum, smask = ctx.tail
             ops.mae_tail_bwd(None, y2, st2, dpred, lsums, model.out.conv.weight, sums2, dy2, dcat,
-                             _gradbuf(model.out.conv.weight), _gradbuf(model.out.conv.bias), B, V, Cout, r=None if smask is not None else cat, bwd_sums=bsum,
+                             _gradbuf(model.out.conv.weight), _gradbuf(model.out.conv.bias), B, V, Cout, r=None if p.sign_mask else cat, bwd_sums=bsum,
                              sign_mask=smask)
-        elif m.has_proj:
+        elif p.proj:
             dout = dout.contiguous()
             sums3 = ops.acc_zeros((B, Cout, 2), dev)
             dy3 = torch.empty_like(y3)
@@ -679,81 +771,64 @@ class _UpBlockFn(torch.autograd.Function):
             dout = dout.contiguous()
             ops.instnorm_bwd_reduce(dout, out, y2, st2, sums2, B, V, Cout, rmode=1)
             ops.instnorm_bwd_apply(dout, out, y2, st2, sums2, dy2, B, V, Cout, rmode=1, dr=dcat)  # dcat <- g (plain residual)
-        conv = ctx.conv
-        wgrad = ops.conv3d_k3_c48_wgrad if ctx.c48 else ops.conv3d_k3_wgrad
-        sums1 = ops.acc_zeros((B, Cout, 2), dev)
-        fused_red = ctx.c48 and ops.C48_BWD_REDUCE and S % 16 == 0
-        cz = getattr(ctx, "cz", False)
-        if cz:          # centered form: y1 holds z = lrelu(conv1's output - mean)
-            da1 = ops.conv3d_k3_c48_bwd_reduce_centered(dy2.view(B, S, S, S, Cout), pk[key + "c2.wkd"], y1, st1, sums1).view(B * V, Cout)
-        elif fused_red:   # the InstanceNorm-backward sums of (da1, y1) come out of the conv epilogue (no separate pass over both 160^3 tensors)
-            da1 = ops.conv3d_k3_c48_bwd_reduce(dy2.view(B, S, S, S, Cout), pk[key + "c2.wkd"], y1, st1, sums1).view(B * V, Cout)
-        else:
-            da1 = conv(dy2.view(B, S, S, S, Cout), "c2.wd", Cout).view(B * V, Cout)
-        # Weight gradients run on the forked side stream -- except the persistent 160^3 kernels, which own every CU: overlapping
-        # them with the next MFMA kernel OR with the HBM-bound InstanceNorm passes AS THEY ARE (100 k workgroups of 120 VGPRs) measured slower
-        # (51.2 vs 50.4 ms at 4 grids, 34.8 vs 30.8 ms at 1), so they stay on the main stream.  Round 5: the pass as ONE small workgroup per CU that
-        # fits beside the weight gradient's (`bg` below) does overlap.
-        # small-level weight gradients: forked to the side stream -- or (NMH_DEFER_DEC) queued on the encoder's weight-gradient queue and issued
-        # with its next flush, one fork for all of them
-        defer = ops.DEFER_DECODER_WGRAD and getattr(m, "_wq", None) is not None and not (ctx.c48 or ctx.c64)
+        # ---- conv2: input gradient, weight gradient beside the InstanceNorm backward behind conv1
+        wgrad = ops.conv3d_k3_c48_wgrad if p.family == "c48" else ops.conv3d_k3_wgrad
 
-        def side(fn):
-            if defer:
+        def side(fn):   # (UpPlan.wgrad_main_stream / defer_conv_wgrad)
+            if p.defer_conv_wgrad:
                 m._wq.defer(fn)
             else:
-                with ops.side_stream(enable=not (ctx.c48 or ctx.c64)):
+                with ops.side_stream(enable=not p.wgrad_main_stream):
                     fn()
+        sums1 = ops.acc_zeros((B, Cout, 2), dev)
+        dy2v = dy2.view(B, S, S, S, Cout)
+        if p.fused_reduce:   # (centered form: y1 holds z = lrelu(conv1's output - mean))
+            reduce = ops.conv3d_k3_c48_bwd_reduce_centered if p.centered else ops.conv3d_k3_c48_bwd_reduce
+            da1 = reduce(dy2v, pk[key + p.c2_dgrad], y1, st1, sums1).view(B * V, Cout)
+        else:
+            da1 = _conv3(p.family, dy2v, pk[key + p.c2_dgrad], Cout).view(B * V, Cout)
         g_c2, g_c1 = _gradbuf(m.conv_block.conv2.weight), _gradbuf(m.conv_block.conv1.weight)
         dy1 = torch.empty_like(dy2)  # (dy2 is still being read by the side-stream wgrad)
-        bg = cz or (ops.INBWD_BG and ctx.c48 and fused_red and Cout == 48 and dtype == torch.bfloat16 and ops.side_stream.enabled)
-        if cz:
+        if p.bg_norm_bwd:
             with ops.side_stream():
-                ops.instnorm_bwd_apply_bg_centered(da1, y1, st1, sums1, dy1, B, V, Cout)
-            ops.conv3d_k3_c48_wgrad_scaled(dy2.view(B, S, S, S, Cout), y1.view(B, S, S, S, Cout), st1, g_c2)
-        elif bg:
-            # decoder1: the HBM-bound InstanceNorm backward (needs conv2's input gradient only) streams on a forked stream UNDER conv2's weight gradient, as one
-            # small workgroup per CU beside the persistent kernel's (csrc/norm.hip: in_bwd_apply_bg_kernel); joined in front of its first consumer
-            # (the transpose conv's input gradient, a 4000-workgroup GEMM, does not ride along: one of its workgroups per CU at a time crawls -- 2.7 ms for 0.64)
-            with ops.side_stream():
-                ops.instnorm_bwd_apply_bg(da1, y1, st1, sums1, dy1, B, V, Cout)
-        if not cz:
-            side(lambda: wgrad(dy2.view(B, S, S, S, Cout), a1.view(B, S, S, S, Cout), g_c2))
-        if not fused_red and not cz:
+                (ops.instnorm_bwd_apply_bg_centered if p.centered else ops.instnorm_bwd_apply_bg)(da1, y1, st1, sums1, dy1, B, V, Cout)
+        if p.centered:
+            ops.conv3d_k3_c48_wgrad_scaled(dy2v, y1.view(B, S, S, S, Cout), st1, g_c2)
+        else:
+            side(lambda: wgrad(dy2v, a1.view(B, S, S, S, Cout), g_c2))
+        if not p.fused_reduce:
             ops.instnorm_bwd_reduce(da1, None, y1, st1, sums1, B, V, Cout, rmode=0)   # sign(a1) == sign(y1 - mean): a1 is not re-read
-        if bg:
+        if p.bg_norm_bwd:
             ops.join_side()
         else:
             ops.instnorm_bwd_apply(da1, None, y1, st1, sums1, dy1, B, V, Cout, rmode=0)
-        # decoder1 with the composed kernels: conv1's input gradient on the fine grid is never formed -- dx and the transpose conv's parameter gradients
-        # take their conv1 part through the composition (cconv_dgrad below, cconv_wgrad's G blocks), dcat keeps the residual branch's gradient alone
-        cdg = ctx.cc and pk.cconv[5] is not None
-        if not cdg:
-            conv(dy1.view(B, S, S, S, Cout), "c1.wd", Cc, out=dcat.view(B, S, S, S, Cc), accumulate=not m.has_proj)
-        if ctx.cc:   # decoder1: conv1's weight gradient through the composition (a quarter of the FLOPs, contraction over the coarse cells; csrc/cconv.hip)
+        # ---- conv1: input gradient into dcat, weight gradient -- or both through the composition (UpPlan.composed_bwd)
+        dy1v = dy1.view(B, S, S, S, Cout)
+        if p.composed_bwd:
             # all on the main stream: the persistent G kernel, then its reduce / border sums / chain rules
-            ops.cconv_wgrad(x.view(B, v, v, v, Cin), dy1.view(B, S, S, S, Cout), pk.cconv[3], m.transp_conv.bias, g_c1, B, v,
-                            dWt=_gradbuf(m.transp_conv.weight) if cdg else None, dbt=_gradbuf(m.transp_conv.bias) if cdg else None)
+            ops.cconv_wgrad(x.view(B, v, v, v, Cin), dy1v, pk.dec1.workspace, m.transp_conv.bias, g_c1, B, v, dWt=_gradbuf(m.transp_conv.weight), dbt=_gradbuf(m.transp_conv.bias))
         else:
-            side(lambda: wgrad(dy1.view(B, S, S, S, Cout), cat.view(B, S, S, S, Cc), g_c1))
-        if m.has_proj:
+            _conv3(p.family, dy1v, pk[key + p.c1_dgrad], Cc, out=dcat.view(B, S, S, S, Cc), accumulate=not p.proj)
+            side(lambda: wgrad(dy1v, cat.view(B, S, S, S, Cc), g_c1))
+        if p.proj:
             ops.gemm_nt(dy3, pk[key + "c3.wT"].view(Cc, Cout), out=dcat, accumulate=True)
             g_c3 = _gradbuf(m.conv_block.conv3.weight)
-            if defer:
+            if p.defer_conv_wgrad:
                 m._wq.defer(lambda: ops.gemm_tn(dy3, cat, g_c3))
             else:
                 with ops.side_stream():
                     ops.gemm_tn(dy3, cat, g_c3)
+        # ---- transpose conv (+ skip)
         dskip = None
-        if has_skip:
+        if p.proj:
             dskip = torch.empty((B * V, Cout), dtype=dtype, device=dev)
             ops.copy_cols(dcat[:, Cout:], dskip)
         dx = torch.empty((B * v ** 3, Cin), dtype=dtype, device=dev)
         ops.upconv_dgrad(dcat, pk[key + "t.wd"].view(Cin, k3 * Cout), dx, B, v, k, Cin, Cout)   # reads dcat through the pixel shuffle
-        if cdg:
-            ops.cconv_dgrad(dy1, pk.cconv[5], B, v, add=dx, out=dx)
+        if p.composed_bwd:
+            ops.cconv_dgrad(dy1, pk.dec1.dgrad, B, v, add=dx, out=dx)
         g_tw, g_tb = _gradbuf(m.transp_conv.weight), _gradbuf(m.transp_conv.bias)
-        if ops.DEFER_DECODER_WGRAD and getattr(m, "_wq", None) is not None:   # (decoder1 too: only its conv weight gradients stay out of the queue)
+        if p.defer_upconv_wgrad:
             m._wq.defer(lambda: ops.upconv_wgrad(dcat, x, g_tw, g_tb, B, v, k, Cin, Cout))
         else:
             with ops.side_stream():
@@ -893,6 +968,16 @@ class UpBlock3D(nn.Module):
         self.transp_conv = nn.ConvTranspose3d(cin, cout, k, stride=k)
         self.conv_block = ResBlock3D(2 * cout if use_skip else cout, cout)
         self.has_proj = use_skip
+
+    _wq = None   # the model's weight-gradient queue (set by its _build_packer; a block packed on its own, as by heads.py, has none)
+
+    def _plan(self, B, v, dtype, x_grad, tail) -> UpPlan:
+        """plan_up_block on this block's packed layouts, the tail = (model, ...) of _UpBlockFn.forward and the switches as they are now"""
+        pk = self._pk
+        layouts = {n for row in _CONV_LAYOUTS.values() for n in row if self._key + n in pk.views}
+        dec1 = pk.dec1.optional() if (pk.dec1 is not None and pk.dec1.block is self) else None
+        return plan_up_block(self.cin, self.cout, self.k, self.has_proj, layouts, dec1, B, v, dtype, x_grad, tail is not None,
+                             tail is not None and tail[0].fuse_tail_sums, self._wq is not None, UpSwitches.current())
 
     def forward(self, x, skip=None, tail=None):
         """channels-last (B,v,v,v,Cin) [+ skip (B,kv,kv,kv,Cout)] -> (B,kv,kv,kv,Cout), or the loss triple when `tail` is given"""
@@ -1041,12 +1126,7 @@ class SwinTransformer_MAE3D_New(nn.Module):
         d1 = getattr(self, "decoder1", None)
         if (ops.CCONV and d1 is not None and self.compute_dtype == torch.bfloat16 and (d1.cin, d1.cout, d1.k) == (96, 48, 4) and not d1.has_proj
                 and (self.resolution // 4) % 8 == 0):
-            P.cconv = (d1, torch.empty(ops.cconv_pack_numel(), dtype=torch.bfloat16, device=device), torch.empty((27, 48), device=device),
-                       torch.empty(ops.cconv_pack_ws_floats(), dtype=torch.float32, device=device),
-                       torch.empty(ops.upconv4_pack_numel(), dtype=torch.bfloat16, device=device) if ops.UPCONV4 else None,
-                       torch.empty(ops.cconv_dgrad_pack_numel(), dtype=torch.bfloat16, device=device) if (ops.CCONV_DGRAD and ops.CCONV_WGRAD) else None,
-                       torch.empty((27, 96, 48), dtype=torch.float32, device=device) if ops.CCONV_CENTERED else None,
-                       torch.empty(ops.tail_residual_pack_numel(), dtype=torch.bfloat16, device=device) if ops.TAIL_FROM_COARSE else None)
+            P.dec1 = _Dec1Pack(d1, device)
         self._packer = P
         self._pk = P
         self._wq = ops.WgradQueue()   # deferred encoder weight gradients (grouped launches, issued per stage)

@@ -472,9 +472,6 @@ def cconv_fwd(x, Wcp, delta, B, v, out=None, stats_acc=None):
     return out
 
 
-CCONV_DGRAD = __import__("os").environ.get("NMH_CCONV_DGRAD", "1") != "0"   # decoder1: input gradient through the composition (with NMH_CCONV_WGRAD)
-
-
 def cconv_dgrad_pack_numel() -> int:
     return int(lib().call("nmh_cconv_dgrad_pack_numel"))
 
@@ -501,9 +498,6 @@ def cconv_dgrad(dy1, Wdp, B, v, add=None, out=None):
     if ev is not None:
         ev.record(torch.cuda.current_stream())
     return out
-
-
-UPCONV4 = __import__("os").environ.get("NMH_UPCONV4", "1") != "0"   # decoder1's transpose conv as the persistent kernel of csrc/cconv.hip (with NMH_CCONV)
 
 
 def upconv4_pack_numel() -> int:

@@ -163,3 +163,106 @@ def test_capi_rejects_null_required_pointers_without_touching_the_device():
     if ar is not None:   # the arena is process-wide state: give back the one an earlier GPU test of this session registered
         assert L.nmh_set_prezeroed_arena(ctypes.c_void_p(ar.buf.data_ptr()), ar.BYTES) == 0
     assert L.nmh_error_string(-4).decode().startswith("nmh:")
+
+
+# ---- the decoder up-block's plan (model.plan_up_block): which kernels a decoder level runs, asked with plain values
+def _layouts(*families):
+    from nerf_mae_amd.model import _CONV_LAYOUTS
+    return {n for f in families + ("generic",) for n in _CONV_LAYOUTS[f]}
+
+
+def _switches(**kw):
+    from nerf_mae_amd.model import UpSwitches
+    on = dict(tail_from_coarse=True, tail_sign_mask=True, cconv_wgrad=True, cconv_centered=True, c48_bwd_reduce=True, inbwd_bg=True, defer_decoder_wgrad=True,
+              side_stream=True, c48mb_min_voxels=32768, c64_min_voxels=32768)   # the defaults of the ops switches
+    return UpSwitches(**dict(on, **kw))
+
+
+DEC1_BUFFERS = frozenset({"dgrad", "mean_table", "tail_residual"})
+
+
+def _mae_decoder1(B=8, v=40, dtype=torch.bfloat16, x_grad=True, tail=True, dec1=DEC1_BUFFERS, sw=None):
+    """decoder1 of swin_t / swin_s (96 -> 48, k = 4, no skip) in training with the fused tail, behind the model's weight-gradient queue"""
+    from nerf_mae_amd.model import plan_up_block
+    layouts = _layouts("c48") if dtype == torch.bfloat16 else _layouts()
+    return plan_up_block(96, 48, 4, False, layouts, dec1, B, v, dtype, x_grad, tail, tail, True, sw or _switches())
+
+
+def test_up_block_plan_of_the_mae_decoder1():
+    from nerf_mae_amd.model import _CONV_LAYOUTS
+    p = _mae_decoder1()
+    assert p.family == "c48" and (p.c1_fwd, p.c1_dgrad, p.c2_fwd, p.c2_dgrad) == _CONV_LAYOUTS["c48"] == ("c1.wk", "c1.wkd", "c2.wk", "c2.wkd")
+    assert p.epilogue_stats and p.composed_fwd and p.composed_bwd and p.centered and p.residual_in_tail and p.fused_tail and p.sign_mask and p.tail_bwd_sums
+    assert p.fused_reduce and p.bg_norm_bwd and p.wgrad_main_stream and not p.defer_conv_wgrad and p.defer_upconv_wgrad and not p.proj and p.x_grad
+    for B in (1, 2, 4, 8):
+        assert _mae_decoder1(B=B) == p
+    assert _mae_decoder1(B=3) == p._replace(centered=False)          # centered_wgrad_ok: the scaled weight-gradient reduce takes B in {1, 2, 4, 8}
+    assert _mae_decoder1(B=2, v=16) == p and _mae_decoder1(B=2, v=8) == p   # 64^3 and 32^3, the sizes of the GPU tests
+    # the residual is formed in the tail only in training with the fused tail: otherwise `cat` is stored
+    nograd = _mae_decoder1(x_grad=False)
+    assert nograd == p._replace(residual_in_tail=False, x_grad=False, tail_bwd_sums=False, sign_mask=False)
+    notail = _mae_decoder1(tail=False)
+    assert notail == p._replace(residual_in_tail=False, fused_tail=False, tail_bwd_sums=False, sign_mask=False)
+    # a switch changes its own field alone
+    assert _mae_decoder1(sw=_switches(cconv_centered=False)) == p._replace(centered=False)
+    assert _mae_decoder1(sw=_switches(tail_from_coarse=False)) == p._replace(residual_in_tail=False)
+    # ... and so does the buffer a switch that was off when the packer was built leaves out
+    assert _mae_decoder1(dec1=DEC1_BUFFERS - {"mean_table"}) == p._replace(centered=False)
+    assert _mae_decoder1(dec1=DEC1_BUFFERS - {"tail_residual"}) == p._replace(residual_in_tail=False)
+    # 120^3 (v = 30 is no multiple of 8): no decoder-1 record is built
+    p120 = _mae_decoder1(v=30, dec1=None)
+    assert p120.family == "c48" and p120.epilogue_stats and not (p120.composed_fwd or p120.composed_bwd or p120.centered or p120.residual_in_tail)
+    assert p120.fused_tail and p120.sign_mask and not p120.fused_reduce and not p120.bg_norm_bwd      # (120 % 16 != 0)
+    with pytest.raises(AttributeError):
+        p.centered = False
+
+
+def test_up_block_plan_in_fp32_is_the_generic_path():
+    from nerf_mae_amd.model import _CONV_LAYOUTS, build_model
+    p = _mae_decoder1(dtype=torch.float32, dec1=None)
+    assert p.family == "generic" and (p.c1_fwd, p.c1_dgrad, p.c2_fwd, p.c2_dgrad) == _CONV_LAYOUTS["generic"] == ("c1.w", "c1.wd", "c2.w", "c2.wd")
+    assert not (p.epilogue_stats or p.composed_fwd or p.composed_bwd or p.centered or p.residual_in_tail or p.sign_mask or p.fused_reduce or p.bg_norm_bwd)
+    assert p.fused_tail and p.tail_bwd_sums and not p.wgrad_main_stream and p.defer_conv_wgrad and p.defer_upconv_wgrad
+    # the same answer from a block's own packer (the layouts and the absent decoder-1 record are read off it)
+    m = build_model("swin_t", resolution=32, compute_dtype=torch.float32)
+    m.flatten_parameters(torch.device("cpu"))
+    assert m._packer.dec1 is None
+    q = m.decoder1._plan(2, 8, torch.float32, True, (m,))
+    assert (q.family, q.composed_fwd, q.centered, q.fused_tail, q.proj) == ("generic", False, False, True, False)
+    assert m.decoder2._plan(2, 4, torch.float32, True, None).proj
+
+
+def test_up_block_plan_of_the_other_levels_and_backbones():
+    from nerf_mae_amd.model import plan_up_block
+    bf, sw = torch.bfloat16, _switches()
+    # swin_s decoder2 at 160^3: 192 -> 96, k = 2, skip, S = 40
+    p = plan_up_block(192, 96, 2, True, _layouts("c48mb"), None, 8, 20, bf, True, False, False, True, sw)
+    assert p.family == "c48mb" and (p.c1_fwd, p.c2_dgrad) == ("c1.wkm", "c2.wkmd") and p.proj and not p.epilogue_stats and not p.wgrad_main_stream
+    assert p.defer_conv_wgrad and p.defer_upconv_wgrad and not (p.composed_fwd or p.centered or p.fused_tail or p.fused_reduce or p.bg_norm_bwd)
+    assert plan_up_block(192, 96, 2, True, _layouts("c48mb"), None, 8, 8, bf, True, False, False, True, sw).family == "generic"   # 16^3: below C48MB_MIN_VOXELS
+    # swin_b at 160^3: decoder1 128 -> 64 (k = 4, no skip) and decoder2 256 -> 128 (S = 40)
+    for args in ((128, 64, 4, False, _layouts("c64"), None, 8, 40), (256, 128, 2, True, _layouts("c64"), None, 8, 20)):
+        p = plan_up_block(*args, bf, True, not args[3], not args[3], True, sw)
+        assert p.family == "c64" and (p.c1_fwd, p.c1_dgrad) == ("c1.w64", "c1.w64d") and p.epilogue_stats and p.wgrad_main_stream
+        assert not p.defer_conv_wgrad and p.defer_upconv_wgrad and not (p.composed_fwd or p.composed_bwd or p.centered or p.residual_in_tail or p.sign_mask)
+    # the voxel heads' decoder1 (heads.py): skip, generic layouts only, packed on its own (no queue)
+    p = plan_up_block(96, 48, 4, True, _layouts(), None, 2, 8, bf, True, False, False, False, sw)
+    assert p.family == "generic" and p.proj and not (p.composed_fwd or p.composed_bwd or p.centered or p.defer_conv_wgrad or p.defer_upconv_wgrad)
+
+
+def test_decoder1_pack_record_names_its_buffers(monkeypatch):
+    from nerf_mae_amd import ops
+    from nerf_mae_amd.model import UpBlock3D, _Dec1Pack
+    blk = UpBlock3D(96, 48, 4, use_skip=False)
+    for name in ("CCONV_WGRAD", "CCONV_CENTERED", "TAIL_FROM_COARSE"):
+        monkeypatch.setattr(ops, name, True)
+    d = _Dec1Pack(blk, torch.device("cpu"))
+    assert d.block is blk and d.optional() == DEC1_BUFFERS
+    assert d.composed.numel() == ops.cconv_pack_numel() and d.composed.dtype == torch.bfloat16 and d.border.shape == (27, 48)
+    assert d.workspace.numel() == ops.cconv_pack_ws_floats() and d.workspace.dtype == torch.float32
+    assert d.upconv4.numel() == ops.upconv4_pack_numel() and d.dgrad.numel() == ops.cconv_dgrad_pack_numel()
+    assert d.mean_table.shape == (27, 96, 48) and d.tail_residual.numel() == ops.tail_residual_pack_numel()
+    monkeypatch.setattr(ops, "CCONV_CENTERED", False)
+    monkeypatch.setattr(ops, "CCONV_WGRAD", False)
+    d = _Dec1Pack(blk, torch.device("cpu"))
+    assert d.mean_table is None and d.dgrad is None and d.optional() == {"tail_residual"}
