@@ -673,11 +673,13 @@ LN_DEFER_PARAM_GRADS = __import__("os").environ.get("NMH_LN_DEFER", "1") != "0"
 EMBED_KEPT = __import__("os").environ.get("NMH_EMBED_KEPT", "1") != "0"   # patch embed (im2row, GEMM, LayerNorm, weight gradient) on the kept tokens only
 
 
-def embed_kept_rows(mask, cap_rows):
-    """token mask [n] uint8 (1 = removed) -> int32 rowmap [n + 2] (include/nerfmae_hip.h: nmh_patch_embed_kept_rows)"""
-    _chk(mask)
+def embed_kept_rows(mask, cap_rows, out=None):
+    """token mask [n] uint8 (1 = removed) -> int32 rowmap [n + 2] (include/nerfmae_hip.h: nmh_patch_embed_kept_rows); out: an int32 [n + 2] buffer to fill"""
+    _chk(mask, out)
     n = mask.numel()
-    rowmap = torch.empty(n + 2, dtype=torch.int32, device=mask.device)
+    if out is not None and (out.dtype != torch.int32 or out.numel() != n + 2):
+        raise RuntimeError("embed_kept_rows: out must be int32 [n + 2]")
+    rowmap = torch.empty(n + 2, dtype=torch.int32, device=mask.device) if out is None else out
     lib().call("nmh_patch_embed_kept_rows", mask, n, int(cap_rows), rowmap, _st())
     return rowmap
 
