@@ -397,6 +397,28 @@ NMH_API int nmh_roi_align_rotated_3d_bwd(int layout, int dt, const void* dout, c
  * and pads after it.  A vertex with y == 0, where the reference's comparison returns nothing, sorts by its angle (x > 0: 0, x < 0: pi).
  * 9 <= M <= 32, else -4.  B*N == 0 returns 0 without a launch. */
 NMH_API int nmh_sort_vertices(const float* vertices, const unsigned char* mask, const int* num_valid, int* idx, int B, int N, int M, void* stream);
+/* ---- oriented 3-D box IoU / GIoU / DIoU losses, all-pairs IoU and rotated NMS (csrc/rotated_iou.hip) ----
+ * Boxes are fp32 rows (x, y, z, w, l, h, theta), theta in RADIANS about the third axis (the RoIAlign entries above take degrees).
+ * Paired losses (nerf_rpn/model/rotated_iou/oriented_iou_loss.py:82-148 cal_iou_3d / cal_giou_3d / cal_diou_3d, over box_intersection_2d.py:11-176 and
+ * min_enclosing_box.py:25-166; called from fcos/loss.py:135-171 and rpn.py:143-156).  mode: 0 IoU, 1 GIoU "smallest", 2 GIoU "aligned", 3 DIoU "smallest",
+ * 4 DIoU "aligned".  box1, box2 [npairs][7] -> iou, u3d, z_range, loss, w_c, h_c [npairs] and corners1, corners2 [npairs][4][2] (the BEV corners of
+ * box2corners_th); every output but iou may be NULL, loss is required in modes 1-4 and untouched in mode 0.
+ * _bwd recomputes the geometry from the boxes: g_iou, g_u3d, g_loss [npairs] (NULL = zero; bit 0 / 1 / 2 of g_one set:
+ * that gradient is ONE float for all pairs, the expanded gradient of a sum()) -> dbox1, dbox2 [npairs][7], written not added; a NULL dbox
+ * skips that side.  A pair without BEV overlap gets an exactly zero gradient from the intersection area.  npairs == 0 returns 0 without a launch. */
+NMH_API int nmh_obb_iou_fwd(int mode, const float* box1, const float* box2, int64_t npairs, float* iou, float* u3d, float* z_range, float* loss, float* w_c, float* h_c, float* corners1, float* corners2, void* stream);
+NMH_API int nmh_obb_iou_bwd(int mode, const float* box1, const float* box2, int64_t npairs, const float* g_iou, const float* g_u3d, const float* g_loss, int g_one, float* dbox1, float* dbox2, void* stream);
+/* box_iou_3d (nerf_rpn/model/fcos/utils.py:212-255, model/utils.py:215-412): boxes1 [N][ncols] x boxes2 [M][ncols] -> iou [N][M], without the N x M x 7
+ * repeat.  ncols 7: oriented boxes as above; ncols 6: (x1,y1,z1,x2,y2,z2) with the closed form of _box_inter_union_3d (fcos/utils.py:285-297).  A pair
+ * without z overlap or BEV overlap is exactly 0.  N <= 1048560. */
+NMH_API int nmh_obb_iou_pairwise(int ncols, const float* boxes1, const float* boxes2, int N, int M, float* iou, void* stream);
+/* nms / batched_nms (nerf_rpn/model/fcos/utils.py:109-158): boxes [N][ncols] already ordered by descending score, category [N] int32 or NULL.
+ * _mask: mask [N][ceil(N/64)] 64-bit words, bit k of word (i, j) = iou(i, 64 j + k) > iou_threshold and 64 j + k > i (and equal categories);
+ * words with j < floor(i / 64) are zero by definition, never read by _scan and not written (only the upper triangle of
+ * 64 x 64 blocks is launched): a caller that reads the mask itself must skip or clear them.
+ * _scan: the greedy walk over the rows on the device: keep [N] int32 receives the kept positions in order, count [1] their number.  N <= 16384, else -4. */
+NMH_API int nmh_obb_nms_mask(int ncols, const float* boxes, const int* category, int N, float iou_threshold, uint64_t* mask, void* stream);
+NMH_API int nmh_obb_nms_scan(const uint64_t* mask, int N, int* keep, int* count, void* stream);
 /* Per-step host parameters of the training step in ONE launch, passed as kernel arguments (no host-to-device copies):
  *  - block_bits (HOST, nb^3 bits, bit (a*nb+b)*nb+c = 1: the 4x4x4-token block (a,b,c) is removed; window_masking_3d's raster order,
  *    swin_mae3d.py:1366-1373) is expanded to the token mask tokmask[g^3] (device, uint8; tokens outside the nb^3 blocks stay 0);

@@ -559,6 +559,45 @@ int nmh_sort_vertices(const float* vertices, const unsigned char* mask, const in
   REQ(vertices, mask, num_valid, idx);
   return k_sort_vertices(vertices, mask, num_valid, idx, B, N, M, ST);
 }
+int nmh_obb_iou_fwd(int mode, const float* box1, const float* box2, int64_t npairs, float* iou, float* u3d, float* z_range, float* loss, float* w_c, float* h_c, float* corners1,
+                    float* corners2, void* stream) {
+  CLR();
+  if (mode < 0 || mode > 4 || npairs < 0) return -4;
+  if (npairs == 0) return 0;
+  REQ(box1, box2, iou);
+  if (mode != 0 && !loss) return -4;
+  return k_obb_iou_fwd(mode, box1, box2, (long)npairs, iou, u3d, z_range, loss, w_c, h_c, corners1, corners2, ST);
+}
+int nmh_obb_iou_bwd(int mode, const float* box1, const float* box2, int64_t npairs, const float* g_iou, const float* g_u3d, const float* g_loss, int g_one, float* dbox1,
+                    float* dbox2, void* stream) {
+  CLR();
+  if (mode < 0 || mode > 4 || npairs < 0 || g_one < 0 || g_one > 7) return -4;
+  if (npairs == 0 || (!dbox1 && !dbox2)) return 0;
+  REQ(box1, box2);
+  return k_obb_iou_bwd(mode, box1, box2, (long)npairs, g_iou, g_u3d, g_loss, g_one, dbox1, dbox2, ST);
+}
+int nmh_obb_iou_pairwise(int ncols, const float* boxes1, const float* boxes2, int N, int M, float* iou, void* stream) {
+  CLR();
+  if ((ncols != 6 && ncols != 7) || N < 0 || M < 0) return -4;
+  if (N == 0 || M == 0) return 0;
+  REQ(boxes1, boxes2, iou);
+  return k_obb_iou_pairwise(ncols, boxes1, boxes2, N, M, iou, ST);
+}
+int nmh_obb_nms_mask(int ncols, const float* boxes, const int* category, int N, float iou_threshold, uint64_t* mask, void* stream) {
+  CLR();
+  if ((ncols != 6 && ncols != 7) || N < 0 || N > NMH_OBB_NMS_MAX) return -4;
+  if (N == 0) return 0;
+  REQ(boxes, mask);
+  return k_obb_nms_mask(ncols, boxes, category, N, iou_threshold, (unsigned long long*)mask, ST);
+}
+int nmh_obb_nms_scan(const uint64_t* mask, int N, int* keep, int* count, void* stream) {
+  CLR();
+  if (N < 0 || N > NMH_OBB_NMS_MAX) return -4;
+  REQ(count);
+  if (N == 0) return k_fill_f32((float*)count, 0.f, 1, ST);   // an int 0 has the bits of 0.f
+  REQ(mask, keep);
+  return k_obb_nms_scan((const unsigned long long*)mask, N, keep, count, ST);
+}
 int nmh_step_params(const uint32_t* block_bits, int nb, int g, unsigned char* tokmask, const float* hyper, float* hyper_dev, const int* extents, int n_ext, int* extents_dev,
                     void* stream) {
   CLR();

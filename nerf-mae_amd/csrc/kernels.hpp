@@ -275,6 +275,14 @@ int k_roi_align_rotated_3d_fwd(int layout, int dt, const void* x, const float* r
 int k_roi_align_rotated_3d_bwd(int layout, int dt, const void* dout, const float* rois, float* dx, int N, int B, int W, int L, int H, int C, int PW, int PL, int PH,
                                float spatial_scale, int sampling_ratio, hipStream_t st);
 int k_sort_vertices(const float* vertices, const unsigned char* mask, const int* num_valid, int* idx, int B, int N, int M, hipStream_t st);
+// ---- rotated_iou.hip (oriented 3-D box IoU / GIoU / DIoU losses, all-pairs IoU, rotated NMS) ----
+// mode: 0 IoU, 1 GIoU smallest, 2 GIoU aligned, 3 DIoU smallest, 4 DIoU aligned.  Boxes [n][7] fp32 (x,y,z,w,l,h,theta in radians).
+#define NMH_OBB_NMS_MAX 16384
+int k_obb_iou_fwd(int mode, const float* b1, const float* b2, long n, float* iou, float* u3d, float* zr, float* loss, float* wc, float* hc, float* c1, float* c2, hipStream_t st);
+int k_obb_iou_bwd(int mode, const float* b1, const float* b2, long n, const float* g_iou, const float* g_u3d, const float* g_loss, int g_one, float* d1, float* d2, hipStream_t st);
+int k_obb_iou_pairwise(int ncols, const float* b1, const float* b2, int N, int M, float* iou, hipStream_t st);
+int k_obb_nms_mask(int ncols, const float* boxes, const int* cat, int N, float thr, unsigned long long* mask, hipStream_t st);
+int k_obb_nms_scan(const unsigned long long* mask, int N, int* keep, int* count, hipStream_t st);
 int k_step_params(const unsigned* bits, int nb, int g, unsigned char* tokmask, const float* hyper_host, float* hyper_dev, const int* ext_host, int n_ext, int* ext_dev, hipStream_t st);
 int k_grad_cast(int to_bf16, const void* src, void* dst, long n, float scale, hipStream_t st);
 

@@ -1466,3 +1466,63 @@ def sort_vertices(vertices, mask, num_valid):
     idx = torch.empty((B, N, 9), dtype=torch.int32, device=vertices.device)
     lib().call("nmh_sort_vertices", vertices, mask, num_valid, idx, B, N, M, _st())
     return idx
+
+
+# ---- oriented 3-D box IoU / GIoU / DIoU, all-pairs IoU, rotated NMS (csrc/rotated_iou.hip) -------------------------------------------
+OBB_IOU, OBB_GIOU_SMALLEST, OBB_GIOU_ALIGNED, OBB_DIOU_SMALLEST, OBB_DIOU_ALIGNED = range(5)
+OBB_NMS_MAX = 16384
+
+
+def obb_iou_fwd(mode, box1, box2, want_u3d=True, want_z_range=False, want_corners=False):
+    """box1, box2 (..., 7) fp32 contiguous, same shape -> (iou, u3d, z_range, loss, corners1, corners2); entries not asked for (and loss in
+    OBB_IOU mode) are None.  Nothing but the outputs is allocated and the host does not wait."""
+    _chk(box1, box2)
+    lead, n = tuple(box1.shape[:-1]), box1.numel() // 7
+    new = lambda *tail: torch.empty(lead + tail, dtype=torch.float32, device=box1.device)   # noqa: E731
+    iou = new()
+    u3d = new() if want_u3d else None
+    zr = new() if want_z_range else None
+    loss = new() if mode != OBB_IOU else None
+    c1, c2 = (new(4, 2), new(4, 2)) if want_corners else (None, None)
+    lib().call("nmh_obb_iou_fwd", mode, box1, box2, n, iou, u3d, zr, loss, None, None, c1, c2, _st())
+    return iou, u3d, zr, loss, c1, c2
+
+
+def obb_iou_bwd(mode, box1, box2, g_iou, g_u3d, g_loss, need1, need2):
+    """-> (dbox1, dbox2) in the boxes' shape, None for a side that is not needed; a None incoming gradient is zero, and one that is a single
+    value expanded over all pairs (every stride 0: the gradient of a sum()) is read as that one value, not copied"""
+    gs, g_one = [], 0
+    for k, g in enumerate((g_iou, g_u3d, g_loss)):
+        if g is not None and g.numel() > 1 and all(s == 0 for s in g.stride()):
+            g, g_one = g.as_strided((), ()), g_one | (1 << k)
+        gs.append(g)
+    g_iou, g_u3d, g_loss = gs
+    _chk(box1, box2, g_iou, g_u3d, g_loss)
+    d1 = torch.empty_like(box1) if need1 else None
+    d2 = torch.empty_like(box2) if need2 else None
+    lib().call("nmh_obb_iou_bwd", mode, box1, box2, box1.numel() // 7, g_iou, g_u3d, g_loss, g_one, d1, d2, _st())
+    return d1, d2
+
+
+def obb_iou_pairwise(boxes1, boxes2):
+    """[N,7] x [M,7] oriented or [N,6] x [M,6] axis-aligned fp32 -> iou [N,M]"""
+    _chk(boxes1, boxes2)
+    N, M, ncols = boxes1.shape[0], boxes2.shape[0], boxes1.shape[1]
+    iou = torch.empty((N, M), dtype=torch.float32, device=boxes1.device)
+    lib().call("nmh_obb_iou_pairwise", ncols, boxes1, boxes2, N, M, iou, _st())
+    return iou
+
+
+def obb_nms(boxes_sorted, categories, iou_threshold):
+    """boxes_sorted [N,7|6] fp32 in descending score order, categories int32 [N] or None -> (keep int32 [N] positions, count int32 [1]) on the device"""
+    _chk(boxes_sorted, categories)
+    N, ncols = boxes_sorted.shape
+    if N > OBB_NMS_MAX:
+        raise ValueError(f"rotated NMS supports at most {OBB_NMS_MAX} boxes, got {N}")
+    dev = boxes_sorted.device
+    mask = torch.empty((N, (N + 63) // 64), dtype=torch.int64, device=dev)
+    keep = torch.empty((N,), dtype=torch.int32, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    lib().call("nmh_obb_nms_mask", ncols, boxes_sorted, categories, N, iou_threshold, mask, _st())
+    lib().call("nmh_obb_nms_scan", mask, N, keep, count, _st())
+    return keep, count
