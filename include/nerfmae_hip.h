@@ -419,6 +419,37 @@ NMH_API int nmh_obb_iou_pairwise(int ncols, const float* boxes1, const float* bo
  * _scan: the greedy walk over the rows on the device: keep [N] int32 receives the kept positions in order, count [1] their number.  N <= 16384, else -4. */
 NMH_API int nmh_obb_nms_mask(int ncols, const float* boxes, const int* category, int N, float iou_threshold, uint64_t* mask, void* stream);
 NMH_API int nmh_obb_nms_scan(const uint64_t* mask, int N, int* keep, int* count, void* stream);
+/* ---- FCOS target assignment and training losses (csrc/fcos.hip; semantics and the dense layout are stated in that file's header) ----
+ * Common arguments.  level_dims: HOST int [nlevels][4] = (w, l, h, stride), 1 <= nlevels <= 4; N scenes, 1 <= N <= 64; else -4.  Level k has n_k = w l h
+ * locations per scene; dense index p = N (n_0 + .. + n_{k-1}) + scene n_k + location, P = N sum n_k.  "Level tables" are HOST arrays of nlevels DEVICE
+ * pointers to the head's own per-level tensors, (N, 1, w, l, h) for the logits and (N, 6|8, w, l, h) for the regression, read and differentiated in place.
+ * scalars: DEVICE float [2] = (valid positives, sum of their centerness targets).  partials: DEVICE float workspace [2 nmh_fcos_num_blocks()].
+ * world = world_size >= 1.  Every reduction is per-workgroup partials plus one fixed-order pass: deterministic, no atomics.  Nothing waits on the host. */
+NMH_API int64_t nmh_fcos_num_blocks(int nlevels, const int* level_dims, int N);
+/* prepare_targets, compute_targets_for_locations[_obb], get_sample_region, compute_centerness_targets (nerf_rpn/model/fcos/loss.py:210-445) with
+ * compute_locations / compute_padding_masks (fcos/fcos.py:282-299) and encode_fcos_obb (fcos/utils.py:64-105).  boxes [box_offsets[N]][ncols] DEVICE,
+ * ncols 6 (x0,y0,z0,x1,y1,z1) or 7 (x,y,z,w,l,h,theta); box_offsets HOST int [N+1], ascending from 0.  Validity: masks (level table of one byte per
+ * location, (N, w, l, h)) if given, else location < grid_sizes [N][3] (DEVICE int) if given, else all valid.  radius = center_sampling_radius (<= 0: none).
+ * -> labels [P] (0 / 1), targets [P][6|8], gt_index [P] (row within the scene, -1: none), ctr_targets [P], valid [P] bytes, scalars [2]. */
+NMH_API int nmh_fcos_assign(int nlevels, const int* level_dims, int N, int ncols, const float* boxes, const int* box_offsets, const int* grid_sizes, const unsigned char* const* masks, float radius, int norm_targets, float* labels, float* targets, int* gt_index, float* ctr_targets, unsigned char* valid, float* partials, float* scalars, void* stream);
+/* torchvision.ops.sigmoid_focal_loss(alpha 0.25, gamma 2, reduction "sum") over the valid locations / max(scalars[0] / world, 1) (fcos/loss.py:538-542),
+ * logits read through the level table cls (C = 1) -> loss [1].  _bwd: dcls (level table, the logits' layout) = g_loss[0] d loss / d logit, every
+ * element written (0 where invalid); g_loss NULL = zero. */
+NMH_API int nmh_fcos_focal_fwd(int nlevels, const int* level_dims, int N, const float* const* cls, const float* labels, const unsigned char* valid, const float* scalars, float world, float* partials, float* loss, void* stream);
+NMH_API int nmh_fcos_focal_bwd(int nlevels, const int* level_dims, int N, const float* const* cls, const float* labels, const unsigned char* valid, const float* scalars, float world, const float* g_loss, float* const* dcls, void* stream);
+/* Regression and centerness losses on the valid positives, densely masked (fcos/loss.py:544-577): ncols 6: IOULoss (loss.py:77-132), loss_type 0 iou,
+ * 1 linear_iou, 2 giou; ncols 8: RotatedIOULoss (loss.py:135-171) over decode_fcos_obb (fcos/utils.py:12-61), loss_type 0 iou, 1 linear_iou, 2 giou, 3 diou
+ * ("smallest" enclosing forms), add_l1: SmoothL1 on columns 6:8 (loss.py:570-577); each weighted by the centerness target and divided by
+ * scalars[1] / world (0 if scalars[1] == 0) -> reg_loss [1]; BCE-with-logits of the centerness logits against the centerness targets /
+ * max(scalars[0] / world, 1) -> ctr_loss [1].  _bwd: dreg, dctr (level tables in the inputs' layouts) = g_reg[0] d reg_loss + g_ctr[0] d ctr_loss, by hand
+ * through the pair geometry and the decode; every element written, exactly 0 where label == 0 or invalid; NULL g = zero. */
+NMH_API int nmh_fcos_pos_fwd(int nlevels, const int* level_dims, int N, int ncols, int loss_type, int add_l1, const float* const* reg, const float* const* ctr, const float* labels, const float* targets, const float* ctr_targets, const unsigned char* valid, const float* scalars, float world, float* partials, float* reg_loss, float* ctr_loss, void* stream);
+NMH_API int nmh_fcos_pos_bwd(int nlevels, const int* level_dims, int N, int ncols, int loss_type, int add_l1, const float* const* reg, const float* const* ctr, const float* labels, const float* targets, const float* ctr_targets, const unsigned char* valid, const float* scalars, float world, const float* g_reg, const float* g_ctr, float* const* dreg, float* const* dctr, void* stream);
+/* encode_fcos_obb / decode_fcos_obb (fcos/utils.py:64-105, 12-61) on their own: locations [n][3], boxes [n][7] -> out [n][8]; locations [n][3],
+ * regression [n][8] -> boxes [n][7] (theta by atan2); _bwd: gbox [n][7] -> dregression [n][8] (the locations' gradient is gbox[:, :3]).  n == 0: no launch. */
+NMH_API int nmh_fcos_obb_encode(const float* locations, const float* boxes, int64_t n, float* out, void* stream);
+NMH_API int nmh_fcos_obb_decode_fwd(const float* locations, const float* regression, int64_t n, float* boxes, void* stream);
+NMH_API int nmh_fcos_obb_decode_bwd(const float* regression, const float* gbox, int64_t n, float* dregression, void* stream);
 /* Per-step host parameters of the training step in ONE launch, passed as kernel arguments (no host-to-device copies):
  *  - block_bits (HOST, nb^3 bits, bit (a*nb+b)*nb+c = 1: the 4x4x4-token block (a,b,c) is removed; window_masking_3d's raster order,
  *    swin_mae3d.py:1366-1373) is expanded to the token mask tokmask[g^3] (device, uint8; tokens outside the nb^3 blocks stay 0);

@@ -598,6 +598,60 @@ int nmh_obb_nms_scan(const uint64_t* mask, int N, int* keep, int* count, void* s
   REQ(mask, keep);
   return k_obb_nms_scan((const unsigned long long*)mask, N, keep, count, ST);
 }
+int64_t nmh_fcos_num_blocks(int nlevels, const int* level_dims, int N) { return k_fcos_num_blocks(nlevels, level_dims, N); }
+int nmh_fcos_assign(int nlevels, const int* level_dims, int N, int ncols, const float* boxes, const int* box_offsets, const int* grid_sizes, const unsigned char* const* masks, float radius,
+                    int norm_targets, float* labels, float* targets, int* gt_index, float* ctr_targets, unsigned char* valid, float* partials, float* scalars, void* stream) {
+  CLR();
+  REQ(level_dims, box_offsets, labels, targets, gt_index, ctr_targets, valid, partials, scalars);
+  return k_fcos_assign(nlevels, level_dims, N, ncols, boxes, box_offsets, grid_sizes, masks, radius, norm_targets, labels, targets, gt_index, ctr_targets, valid, partials, scalars, ST);
+}
+int nmh_fcos_focal_fwd(int nlevels, const int* level_dims, int N, const float* const* cls, const float* labels, const unsigned char* valid, const float* scalars, float world,
+                       float* partials, float* loss, void* stream) {
+  CLR();
+  REQ(level_dims, cls, labels, valid, scalars, partials, loss);
+  return k_fcos_focal_fwd(nlevels, level_dims, N, cls, labels, valid, scalars, world, partials, loss, ST);
+}
+int nmh_fcos_focal_bwd(int nlevels, const int* level_dims, int N, const float* const* cls, const float* labels, const unsigned char* valid, const float* scalars, float world,
+                       const float* g_loss, float* const* dcls, void* stream) {
+  CLR();
+  REQ(level_dims, cls, labels, valid, scalars, dcls);
+  return k_fcos_focal_bwd(nlevels, level_dims, N, cls, labels, valid, scalars, world, g_loss, dcls, ST);
+}
+int nmh_fcos_pos_fwd(int nlevels, const int* level_dims, int N, int ncols, int loss_type, int add_l1, const float* const* reg, const float* const* ctr, const float* labels,
+                     const float* targets, const float* ctr_targets, const unsigned char* valid, const float* scalars, float world, float* partials, float* reg_loss, float* ctr_loss,
+                     void* stream) {
+  CLR();
+  REQ(level_dims, reg, ctr, labels, targets, ctr_targets, valid, scalars, partials, reg_loss, ctr_loss);
+  return k_fcos_pos_fwd(nlevels, level_dims, N, ncols, loss_type, add_l1, reg, ctr, labels, targets, ctr_targets, valid, scalars, world, partials, reg_loss, ctr_loss, ST);
+}
+int nmh_fcos_pos_bwd(int nlevels, const int* level_dims, int N, int ncols, int loss_type, int add_l1, const float* const* reg, const float* const* ctr, const float* labels,
+                     const float* targets, const float* ctr_targets, const unsigned char* valid, const float* scalars, float world, const float* g_reg, const float* g_ctr,
+                     float* const* dreg, float* const* dctr, void* stream) {
+  CLR();
+  REQ(level_dims, reg, ctr, labels, targets, ctr_targets, valid, scalars, dreg, dctr);
+  return k_fcos_pos_bwd(nlevels, level_dims, N, ncols, loss_type, add_l1, reg, ctr, labels, targets, ctr_targets, valid, scalars, world, g_reg, g_ctr, dreg, dctr, ST);
+}
+int nmh_fcos_obb_encode(const float* locations, const float* boxes, int64_t n, float* out, void* stream) {
+  CLR();
+  if (n < 0) return -4;
+  if (n == 0) return 0;
+  REQ(locations, boxes, out);
+  return k_fcos_obb_encode(locations, boxes, (long)n, out, ST);
+}
+int nmh_fcos_obb_decode_fwd(const float* locations, const float* regression, int64_t n, float* boxes, void* stream) {
+  CLR();
+  if (n < 0) return -4;
+  if (n == 0) return 0;
+  REQ(locations, regression, boxes);
+  return k_fcos_obb_decode_fwd(locations, regression, (long)n, boxes, ST);
+}
+int nmh_fcos_obb_decode_bwd(const float* regression, const float* gbox, int64_t n, float* dregression, void* stream) {
+  CLR();
+  if (n < 0) return -4;
+  if (n == 0) return 0;
+  REQ(regression, gbox, dregression);
+  return k_fcos_obb_decode_bwd(regression, gbox, (long)n, dregression, ST);
+}
 int nmh_step_params(const uint32_t* block_bits, int nb, int g, unsigned char* tokmask, const float* hyper, float* hyper_dev, const int* extents, int n_ext, int* extents_dev,
                     void* stream) {
   CLR();

@@ -283,6 +283,24 @@ int k_obb_iou_bwd(int mode, const float* b1, const float* b2, long n, const floa
 int k_obb_iou_pairwise(int ncols, const float* b1, const float* b2, int N, int M, float* iou, hipStream_t st);
 int k_obb_nms_mask(int ncols, const float* boxes, const int* cat, int N, float thr, unsigned long long* mask, hipStream_t st);
 int k_obb_nms_scan(const unsigned long long* mask, int N, int* keep, int* count, hipStream_t st);
+// ---- fcos.hip (FCOS target assignment, focal / regression / centerness losses, encode / decode of the midpoint-offset OBB form) ----
+// dims: HOST [nlevels][4] = (w, l, h, stride); offs: HOST [N+1]; pointer tables: HOST arrays of nlevels DEVICE pointers.  Dense layout: fcos.hip.
+#define NMH_FCOS_MAX_SCENES 64
+long k_fcos_num_blocks(int nlevels, const int* dims, int N);
+int k_fcos_assign(int nlevels, const int* dims, int N, int ncols, const float* boxes, const int* offs, const int* sizes, const unsigned char* const* masks, float radius,
+                  int norm_targets, float* labels, float* targets, int* gt_index, float* ctr_t, unsigned char* valid, float* partials, float* scalars, hipStream_t st);
+int k_fcos_focal_fwd(int nlevels, const int* dims, int N, const float* const* cls, const float* labels, const unsigned char* valid, const float* scalars, float world, float* partials,
+                     float* loss, hipStream_t st);
+int k_fcos_focal_bwd(int nlevels, const int* dims, int N, const float* const* cls, const float* labels, const unsigned char* valid, const float* scalars, float world, const float* g_loss,
+                     float* const* dcls, hipStream_t st);
+int k_fcos_pos_fwd(int nlevels, const int* dims, int N, int ncols, int loss_type, int add_l1, const float* const* reg, const float* const* ctr, const float* labels, const float* targets,
+                   const float* ctr_t, const unsigned char* valid, const float* scalars, float world, float* partials, float* reg_loss, float* ctr_loss, hipStream_t st);
+int k_fcos_pos_bwd(int nlevels, const int* dims, int N, int ncols, int loss_type, int add_l1, const float* const* reg, const float* const* ctr, const float* labels, const float* targets,
+                   const float* ctr_t, const unsigned char* valid, const float* scalars, float world, const float* g_reg, const float* g_ctr, float* const* dreg, float* const* dctr,
+                   hipStream_t st);
+int k_fcos_obb_encode(const float* loc, const float* boxes, long n, float* out, hipStream_t st);
+int k_fcos_obb_decode_fwd(const float* loc, const float* reg, long n, float* out, hipStream_t st);
+int k_fcos_obb_decode_bwd(const float* reg, const float* gbox, long n, float* dreg, hipStream_t st);
 int k_step_params(const unsigned* bits, int nb, int g, unsigned char* tokmask, const float* hyper_host, float* hyper_dev, const int* ext_host, int n_ext, int* ext_dev, hipStream_t st);
 int k_grad_cast(int to_bf16, const void* src, void* dst, long n, float scale, hipStream_t st);
 

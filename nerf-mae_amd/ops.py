@@ -1526,3 +1526,102 @@ def obb_nms(boxes_sorted, categories, iou_threshold):
     lib().call("nmh_obb_nms_mask", ncols, boxes_sorted, categories, N, iou_threshold, mask, _st())
     lib().call("nmh_obb_nms_scan", mask, N, keep, count, _st())
     return keep, count
+
+
+# ---- FCOS target assignment and training losses (csrc/fcos.hip) ----------------------------------------------------------------------------
+FCOS_MAX_SCENES, FCOS_MAX_LEVELS = 64, 4
+FCOS_LOSS_TYPES = {"iou": 0, "linear_iou": 1, "giou": 2, "diou": 3}
+
+
+class FcosPlan:
+    """feature sizes [(w,l,h)] and strides of 1..4 levels, N scenes -> the host-side level table of the fcos entries, the locations per level
+    and in all (P = N sum n_k), and the size of the partial-sum workspace"""
+
+    def __init__(self, feature_sizes, strides, N):
+        feature_sizes = [tuple(int(v) for v in f) for f in feature_sizes]
+        if not 1 <= len(feature_sizes) <= FCOS_MAX_LEVELS or len(strides) != len(feature_sizes):
+            raise ValueError(f"FCOS ops take 1 to {FCOS_MAX_LEVELS} levels with one stride each, got {len(feature_sizes)} sizes and {len(strides)} strides")
+        if not 1 <= N <= FCOS_MAX_SCENES:
+            raise ValueError(f"FCOS ops take 1 to {FCOS_MAX_SCENES} scenes, got {N}")
+        self.L, self.N, self.sizes, self.strides = len(feature_sizes), int(N), feature_sizes, [int(s) for s in strides]
+        self.n = [w * l * h for w, l, h in feature_sizes]
+        self.P = self.N * sum(self.n)
+        self.dims = (ctypes.c_int * (4 * self.L))(*[v for f, s in zip(feature_sizes, self.strides) for v in (*f, s)])
+        self.nblocks = lib().cdll.nmh_fcos_num_blocks(self.L, self.dims, self.N)
+        if self.nblocks <= 0:
+            raise ValueError(f"FCOS ops: unsupported level table {feature_sizes} x {self.strides}")
+
+    def table(self, tensors):
+        """per-level device tensors -> host array of their pointers"""
+        assert len(tensors) == self.L
+        return (ctypes.c_void_p * self.L)(*[t.data_ptr() for t in tensors])
+
+    def workspace(self, device):
+        return torch.empty((2 * self.nblocks,), dtype=torch.float32, device=device)
+
+
+def fcos_assign(plan, boxes, offsets, ncols, grid_sizes, masks, radius, norm_targets):
+    """boxes [G,6|7] fp32 (may be empty), offsets host ints [N+1], grid_sizes int32 [N,3] or None, masks per-level bool / uint8 tensors or None
+    -> (labels [P], targets [P,6|8], gt_index [P] int32, ctr_targets [P], valid [P] bool, scalars [2], partials workspace)"""
+    _chk(boxes, grid_sizes, *(masks or ()))
+    dev = boxes.device
+    C = 6 if ncols == 6 else 8
+    labels = torch.empty((plan.P,), dtype=torch.float32, device=dev)
+    targets = torch.empty((plan.P, C), dtype=torch.float32, device=dev)
+    gt_index = torch.empty((plan.P,), dtype=torch.int32, device=dev)
+    ctr_t = torch.empty((plan.P,), dtype=torch.float32, device=dev)
+    valid = torch.empty((plan.P,), dtype=torch.bool, device=dev)
+    scalars = torch.empty((2,), dtype=torch.float32, device=dev)
+    partials = plan.workspace(dev)
+    offs = (ctypes.c_int * (plan.N + 1))(*offsets)
+    lib().call("nmh_fcos_assign", plan.L, plan.dims, plan.N, ncols, boxes if boxes.numel() else None, offs, grid_sizes, plan.table(masks) if masks else None, radius,
+               int(bool(norm_targets)), labels, targets, gt_index, ctr_t, valid, partials, scalars, _st())
+    return labels, targets, gt_index, ctr_t, valid, scalars, partials
+
+
+def fcos_focal_fwd(plan, cls, labels, valid, scalars, world, partials):
+    loss = torch.empty((), dtype=torch.float32, device=labels.device)
+    lib().call("nmh_fcos_focal_fwd", plan.L, plan.dims, plan.N, plan.table(cls), labels, valid, scalars, world, partials, loss, _st())
+    return loss
+
+
+def fcos_focal_bwd(plan, cls, labels, valid, scalars, world, g_loss):
+    dcls = [torch.empty_like(t) for t in cls]
+    lib().call("nmh_fcos_focal_bwd", plan.L, plan.dims, plan.N, plan.table(cls), labels, valid, scalars, world, g_loss, plan.table(dcls), _st())
+    return dcls
+
+
+def fcos_pos_fwd(plan, ncols, loss_type, add_l1, reg, ctr, labels, targets, ctr_t, valid, scalars, world, partials):
+    reg_loss = torch.empty((), dtype=torch.float32, device=labels.device)
+    ctr_loss = torch.empty((), dtype=torch.float32, device=labels.device)
+    lib().call("nmh_fcos_pos_fwd", plan.L, plan.dims, plan.N, ncols, loss_type, int(bool(add_l1)), plan.table(reg), plan.table(ctr), labels, targets, ctr_t, valid, scalars, world,
+               partials, reg_loss, ctr_loss, _st())
+    return reg_loss, ctr_loss
+
+
+def fcos_pos_bwd(plan, ncols, loss_type, add_l1, reg, ctr, labels, targets, ctr_t, valid, scalars, world, g_reg, g_ctr):
+    dreg, dctr = [torch.empty_like(t) for t in reg], [torch.empty_like(t) for t in ctr]
+    lib().call("nmh_fcos_pos_bwd", plan.L, plan.dims, plan.N, ncols, loss_type, int(bool(add_l1)), plan.table(reg), plan.table(ctr), labels, targets, ctr_t, valid, scalars, world,
+               g_reg, g_ctr, plan.table(dreg), plan.table(dctr), _st())
+    return dreg, dctr
+
+
+def fcos_obb_encode(locations, boxes):
+    _chk(locations, boxes)
+    out = torch.empty((boxes.shape[0], 8), dtype=torch.float32, device=boxes.device)
+    lib().call("nmh_fcos_obb_encode", locations, boxes, boxes.shape[0], out, _st())
+    return out
+
+
+def fcos_obb_decode_fwd(locations, regression):
+    _chk(locations, regression)
+    out = torch.empty((regression.shape[0], 7), dtype=torch.float32, device=regression.device)
+    lib().call("nmh_fcos_obb_decode_fwd", locations, regression, regression.shape[0], out, _st())
+    return out
+
+
+def fcos_obb_decode_bwd(regression, gbox):
+    _chk(regression, gbox)
+    d = torch.empty_like(regression)
+    lib().call("nmh_fcos_obb_decode_bwd", regression, gbox, regression.shape[0], d, _st())
+    return d
