@@ -349,6 +349,94 @@ def plan_up_block(cin: int, cout: int, k: int, has_proj: bool, layouts, dec1, B:
                   defer_conv_wgrad=queue and not main, defer_upconv_wgrad=queue)
 
 
+class BlockSwitches(NamedTuple):
+    """the `ops` switches and thresholds `plan_swin_block` and `flush_actions` depend on, as plain values"""
+    swin_fused: bool
+    swin_attn_widths: tuple
+    swin_attn_min_windows: int
+    swin_mlp_widths: tuple
+    swin_mlp_min_rows: int
+    mlp_fused: bool
+    mlp_fused_widths: tuple
+    mlp_fused_min_rows: int
+    token_bwd: bool
+    grouped_wgrad: bool
+    flush_after_first: bool
+
+    @classmethod
+    def current(cls) -> "BlockSwitches":
+        return cls(ops.SWIN_FUSED, ops.SWIN_ATTN_WIDTHS, ops.SWIN_ATTN_MIN_WINDOWS, ops.SWIN_MLP_WIDTHS, ops.SWIN_MLP_MIN_ROWS, ops.MLP_FUSED, ops.MLP_FUSED_WIDTHS,
+                   ops.MLP_FUSED_MIN_ROWS, ops.TOKEN_BWD, ops.GROUPED_WGRAD, ops.WQ_FLUSH_AFTER_FIRST)
+
+
+class BlockPlan(NamedTuple):
+    """which kernels one Swin block runs, forward and backward: decided once per forward by `plan_swin_block`, kept on ctx (the layout of the saved tensors
+    depends on it, and the switches it is derived from are module globals that a test or a caller may change between forward and backward)"""
+    # "fused": LN1 -> QKV -> window attention -> proj -> row scale -> + residual in ONE launch (csrc/swin_block.hip); saves what the unfused chains save
+    # "tokens": the unfused chain with token-ordered saves; "window": the unfused chain in window order
+    attn: str
+    # "lds": one launch with both weight matrices resident in LDS (csrc/mlp_fused.hip), nothing kept but x1 -- its backward recomputes the rest
+    # "stream": one launch on packed weight streams (csrc/swin_block.hip), keeps h_pre and h_act for the unfused backward; "unfused": LN2, fc1 + GELU, fc2
+    mlp: str
+    # token-ordered backward (padded stages: 10^3 tokens in 12^3 window rows): window order stays inside the attention kernels, the Linear layers of the
+    # attention branch see the real tokens only -- the forward then saves LN1(x) and o in token order, and the MLP backward forms no window-ordered dyw
+    token_bwd: bool
+    # weight / bias gradients are off the critical path.  True (bf16): they are queued (the operands stay referenced by the queue) and issued per stage as
+    # grouped launches (ops.WgradQueue); False (fp32 parity mode): one launch each on the forked side stream, joined at the end of the block's backward
+    queue_wgrad: bool
+
+
+def plan_swin_block(C: int, heads: int, hidden: int, tokens: int, rows: int, B: int, dtype, x_grad: bool, has_streams: bool, mlp_lds_supported: bool,
+                    has_queue: bool, sw: BlockSwitches) -> BlockPlan:
+    """tokens / rows: real tokens / window-ordered rows (pads included) of all B samples; has_streams: the block has packed weight streams (SwinBlock3D._sw);
+    mlp_lds_supported: ops.mlp_fused_supported(C); has_queue: the block has a weight-gradient queue.  Pure: plain values in, BlockPlan out."""
+    assert tokens % B == 0 and rows % B == 0   # (the row scales and the queue's contraction splits are per sample)
+    bf16 = dtype == torch.bfloat16
+    # the kernels of csrc/swin_block.hip are built for heads = C / 32 and a hidden width of 4 C: anything else keeps the unfused chain.
+    # Dispatch thresholds (tools/bench_swin_block.py): a fused workgroup is one dependent chain of ~45 us whatever the launch size, so launches that
+    # cannot give most CUs a workgroup stay on the unfused kernels (one grid per GPU: 27 windows / 16 row tiles at stage 2)
+    swin = sw.swin_fused and bf16 and has_streams and heads * 32 == C and hidden == 4 * C
+    fused_attn = swin and C in sw.swin_attn_widths and rows // 64 >= sw.swin_attn_min_windows
+    # LDS-resident MLP: bf16, a width that profits and enough rows to give every CU work (fewer: too few 64-row workgroups to fill the chip, the unfused chain
+    # wins).  Measured (tools/bench_mlp_fused.py, 8 grids per GPU, forward + backward): C = 96 (persistent kernels, both weight matrices resident in LDS)
+    # 187 + 478 us against 457 + 555 us for the unfused chain; the chunk-ring kernels win the forward at C = 192 (77 vs 136 us) but lose it back in the
+    # backward (249 vs 204 us) and lose both at C = 384 (8000 rows = 125 workgroups, each a serial chain of 48 weight chunks) -- those widths stay off
+    # sw.mlp_fused_widths; C = 192 / 384 take the stream kernel instead, C = 96 keeps this one
+    lds = sw.mlp_fused and bf16 and C in sw.mlp_fused_widths and tokens >= sw.mlp_fused_min_rows and mlp_lds_supported
+    stream = not lds and swin and C in sw.swin_mlp_widths and tokens >= sw.swin_mlp_min_rows
+    # token_bwd requires mlp != "lds": that kernel's backward hands dx1 to the attention branch as the window-ordered dyw, the operand of the window-ordered
+    # backward, and has no mode that leaves it out
+    token_bwd = sw.token_bwd and rows != tokens and x_grad and not lds
+    return BlockPlan(attn="fused" if fused_attn else "tokens" if token_bwd else "window", mlp="lds" if lds else "stream" if stream else "unfused",
+                     token_bwd=bool(token_bwd), queue_wgrad=bool(sw.grouped_wgrad and bf16 and has_queue))
+
+
+def wgrad_queue_for(owner, dtype) -> Optional["ops.WgradQueue"]:
+    """the weight-gradient queue of `owner` (the model or one of its blocks) if gradients of this compute dtype go through it -- the grouped kernel takes bf16
+    operands -- else None: each weight gradient is then a launch of its own"""
+    return owner._wq if ops.GROUPED_WGRAD and dtype == torch.bfloat16 else None
+
+
+class FlushActions(NamedTuple):
+    """what the backward of a stage boundary does with the weight-gradient queue (`flush_actions`), in this order"""
+    join_before: bool
+    request: bool      # leave the flush to the next block's backward, behind its first kernel; otherwise flush now
+    foreground: bool   # a flush issued now runs (almost) alone and may split for the whole chip
+    join_after: bool
+
+
+def flush_actions(last: bool, sync_after_flush: bool, flush_after_first: bool) -> FlushActions:
+    """last: the first stage -- its flush ends the backward pass and has the chip to itself; sync_after_flush: a gradient all-reduce of the range follows
+    the flush (WgradQueue.sync_after_flush); flush_after_first: ops.WQ_FLUSH_AFTER_FIRST.  Pure."""
+    # Joining the previous stage's launch here makes the next input-gradient kernel a successor of the side chain: the HIP graph executor then puts
+    # the whole next main segment on the side chain's queue, BEHIND the weight gradients just flushed -- the trace showed the two queues alternating
+    # (>= 2 kernels in flight for 4 of 52 ms).  With the late join the side chain only hangs off the main chain (fork edges), the operands stay
+    # referenced by the queue until the end-of-backward join.
+    join_before = sync_after_flush     # the previous stage's launch (if any) has had a whole stage of input-gradient work to finish under
+    request = flush_after_first and not last and not sync_after_flush   # issued by the next block's backward behind its first kernel
+    return FlushActions(join_before, request, foreground=last, join_after=sync_after_flush)
+
+
 def _gradbuf(p: nn.Parameter) -> Tensor:
     if p.grad is None:
         p.grad = torch.zeros_like(p)
@@ -407,7 +495,7 @@ class _EmbedFn(torch.autograd.Function):
         else:
             ops.layernorm_bwd(dtok.contiguous(), y0, ln.weight, mean, rstd, dy0, _gradbuf(ln.weight), _gradbuf(ln.bias), T, C,
                               mask=mask_dev, dmask_token=_gradbuf(m.mask_token) if mask_dev is not None else None, tokens_per_sample=g ** 3)
-        q = m._wq if (ops.GROUPED_WGRAD and dy0.dtype == torch.bfloat16) else None
+        q = wgrad_queue_for(m, dy0.dtype)
         if q is not None:
             q.add(dy0, A, _gradbuf(conv.weight).view(C, 256), dbias=_gradbuf(conv.bias), rows_per_sample=cap if rowmap is not None else g ** 3)
             q.flush(foreground=True)
@@ -417,34 +505,43 @@ class _EmbedFn(torch.autograd.Function):
         return None, None, None, None
 
 
+class _BlockSaved(NamedTuple):
+    """what _BlockFn.forward keeps for its backward.  T = real tokens, rows = window-ordered rows (pads included) of the whole batch"""
+    x: Tensor                  # [T, C] the block's input
+    xnw: Tensor                # LN1(x): [T, C] in token order under plan.token_bwd, else [rows, C] in window order
+    mean1: Tensor              # [T] fp32
+    rstd1: Tensor
+    qkv: Tensor                # [rows, 3 C] in window order, every plan (pad tokens are keys / values)
+    o: Tensor                  # attention output in front of proj: [T, C] in token order under plan.token_bwd, else [rows, C] in window order
+    lse: Tensor                # [rows * heads] fp32
+    x1: Tensor                 # [T, C] x + SD(attn(LN1 x)): all the "lds" MLP keeps
+    x1n: Optional[Tensor]      # [T, C] LN2(x1); this and the four below: None under plan.mlp == "lds" (its backward recomputes them)
+    mean2: Optional[Tensor]    # [T] fp32
+    rstd2: Optional[Tensor]
+    h_pre: Optional[Tensor]    # [T, 4 C] fc1 output
+    h_act: Optional[Tensor]    # [T, 4 C] gelu(h_pre)
+    sd1: Optional[Tensor]      # [B] stochastic-depth row scales of the two branches (None: no scaling)
+    sd2: Optional[Tensor]
+
+
 class _BlockFn(torch.autograd.Function):
-    """x + SD(attn(LN1 x)); x + SD(MLP(LN2 x))  (swin_mae3d.py:366-369)."""
+    """x + SD(attn(LN1 x)); x + SD(MLP(LN2 x))  (swin_mae3d.py:366-369).  Forward and backward follow the BlockPlan taken in forward."""
 
     @staticmethod
     def forward(ctx, x, blk, geom, sd1, sd2):
         b: "SwinBlock3D" = blk
-        pk, key = b._pk, b._key
+        pk, key, sw = b._pk, b._key, b._sw
         T, C, heads = geom.tokens, b.dim, b.num_heads
         dev, dtype = x.device, x.dtype
         tps = T // geom.B
-        sw = getattr(b, "_sw", None)
-        # token-ordered backward (padded stages: 10^3 tokens in 12^3 window rows): window order stays inside the attention kernels, the Linear layers of the
-        # attention branch see the real tokens only in the backward pass -- the forward then saves LN1(x) and o in token order
-        # (the fused kernels are built for heads = C / 32 and a hidden width of 4 C: anything else keeps the unfused chain)
-        swin_shape = heads * 32 == C and b.mlp[0].out_features == 4 * C
-        fused_attn = sw is not None and swin_shape and ops.swin_attn_ok(x, C, geom)
-        # the dispatch decisions are taken ONCE, here, and kept on ctx: the layout of the saved tensors depends on them, and the thresholds / switches they
-        # are derived from are module globals that a test (or a caller) may change between forward and backward
-        ctx.tok_bwd = bool(ops.TOKEN_BWD and geom.rows != geom.tokens and ctx.needs_input_grad[0] and not ops.mlp_fused_ok(x, C, T)
-                           and (fused_attn or ops.TOKEN_BWD_UNFUSED))
-        if fused_attn:
-            # LN1 -> QKV -> window attention -> proj -> row scale -> + residual in ONE launch (csrc/swin_block.hip); saves the same tensors
+        p = b._plan(geom, dtype, ctx.needs_input_grad[0])
+        if p.attn == "fused":
             x1, xnw, mean1, rstd1, qkv, o, lse = ops.swin_attn_fwd(x, b.norm1.weight, b.norm1.bias, sw[ops.SWIN_ATTN_FWD], b.attn.qkv.bias,
                                                                    b.attn.relative_position_bias_table, b.attn.proj.bias, geom, rowscale=sd1, rows_per_scale=tps,
-                                                                   token_saves=ctx.tok_bwd)
-        elif ctx.tok_bwd:
-            # unfused chain with token-ordered saves: LN1 writes its window-ordered output (operand of the qkv product: pad tokens are keys / values) and a
-            # token-ordered copy (operand of the qkv weight gradient); the attention core scatters o to token order, proj is a plain T-row GEMM
+                                                                   token_saves=p.token_bwd)
+        elif p.attn == "tokens":
+            # LN1 writes its window-ordered output (operand of the qkv product: pad tokens are keys / values) and a token-ordered copy (operand of the
+            # qkv weight gradient); the attention core scatters o to token order, proj is a plain T-row GEMM
             xw = torch.empty((geom.rows, C), dtype=dtype, device=dev)
             xnw = torch.empty((T, C), dtype=dtype, device=dev)
             mean1, rstd1 = torch.empty(T, device=dev), torch.empty(T, device=dev)
@@ -464,13 +561,10 @@ class _BlockFn(torch.autograd.Function):
             ops.window_attn_fwd(qkv, b.attn.relative_position_bias_table, o, lse, heads, C, geom)
             x1 = torch.empty_like(x)   # x1 = x + sd1 * window_reverse(proj(o)): the reverse + residual are the GEMM's store
             ops.gemm_nt_window_scatter(o, pk[key + "proj.w"].view(C, C), x1, x, b.attn.proj.bias, sd1, tps, geom)
-        ctx.mlp_fused = ops.mlp_fused_ok(x, C, T)
-        if not ctx.mlp_fused and sw is not None and swin_shape and ops.swin_mlp_ok(x, C, T):
-            # LN2 -> fc1 -> GELU -> fc2 -> row scale -> + residual in one launch; keeps what the (unfused) backward reads, gelu(hp) included
+        if p.mlp == "stream":
             x2, x1n, h_pre, mean2, rstd2, h_act = ops.swin_mlp_fwd(x1, b.norm2.weight, b.norm2.bias, sw[ops.SWIN_MLP_FWD], b.mlp[0].bias, b.mlp[3].bias,
                                                                   rowscale=sd2, rows_per_scale=tps, want_hact=True)
-        elif ctx.mlp_fused:
-            # LN2 -> fc1 -> GELU -> fc2 -> row scale -> + residual in one launch; nothing but x1 is kept for the backward (csrc/mlp_fused.hip)
+        elif p.mlp == "lds":
             x2 = ops.mlp_fused_fwd(x1, b.norm2.weight, b.norm2.bias, pk[key + "fc1.w"].view(4 * C, C), b.mlp[0].bias, pk[key + "fc2.wT"].view(4 * C, C),
                                    b.mlp[3].bias, rowscale=sd2, rows_per_scale=tps)
             x1n = mean2 = rstd2 = h_pre = h_act = None
@@ -481,35 +575,31 @@ class _BlockFn(torch.autograd.Function):
             h_pre = torch.empty((T, 4 * C), dtype=dtype, device=dev)
             h_act = ops.gemm_nt(x1n, pk[key + "fc1.w"].view(4 * C, C), bias=b.mlp[0].bias, act=1, C2=h_pre)
             x2 = ops.gemm_nt(h_act, pk[key + "fc2.w"].view(C, 4 * C), bias=b.mlp[3].bias, resid=x1, rowscale=sd2, rows_per_scale=tps)
-        ctx.b, ctx.geom = b, geom
-        ctx.saved = (x, xnw, mean1, rstd1, qkv, o, lse, x1, x1n, mean2, rstd2, h_pre, h_act, sd1, sd2)
+        ctx.b, ctx.geom, ctx.plan = b, geom, p
+        ctx.saved = _BlockSaved(x, xnw, mean1, rstd1, qkv, o, lse, x1, x1n, mean2, rstd2, h_pre, h_act, sd1, sd2)
         return x2
 
     @staticmethod
     def backward(ctx, dx2):
-        b, geom = ctx.b, ctx.geom
-        x, xnw, mean1, rstd1, qkv, o, lse, x1, x1n, mean2, rstd2, h_pre, h_act, sd1, sd2 = ctx.saved
+        b, geom, p, s = ctx.b, ctx.geom, ctx.plan, ctx.saved
         pk, key = b._pk, b._key
         T, C, heads = geom.tokens, b.dim, b.num_heads
-        tps = T // geom.B
+        tps, rpw = T // geom.B, geom.rows // geom.B
+        x, sd1, sd2 = s.x, s.sd1, s.sd2
         dx2 = dx2.contiguous()
-        # weight/bias gradients are off the critical path.  bf16: they are queued (the operands stay referenced by the queue) and issued
-        # per stage as grouped launches (ops.WgradQueue); fp32 parity mode: one launch each on the forked side stream.
-        q = b._wq if (ops.GROUPED_WGRAD and dx2.dtype == torch.bfloat16) else None
+        q = b._wq if p.queue_wgrad else None
 
         def wgrad(A, Bm, lin, rowscale=None, rps=tps):
             if q is not None:
                 q.add(A, Bm, _gradbuf(lin.weight), dbias=_gradbuf(lin.bias), rowscale=rowscale, rows_per_sample=rps)
             else:
-                with ops.side_stream(enable=T >= ops.side_stream.min_rows):
+                with ops.side_stream():
                     ops.gemm_tn(A, Bm, _gradbuf(lin.weight), rowscale=rowscale, rows_per_scale=rps, dbias=_gradbuf(lin.bias))
-        # ---- MLP branch
-        tok_bwd = ctx.tok_bwd
-        # = sd1 * dx1 in window order (adjoint of the window reverse), second output of the LN backward; not formed by the token-ordered backward
-        dyw = None if tok_bwd else torch.empty_like(xnw)
-        if ctx.mlp_fused:
+        # ---- MLP branch -> dx1, and dyw = sd1 * dx1 in window order (adjoint of the window reverse) unless the backward stays in token order
+        dyw = None if p.token_bwd else torch.empty_like(s.xnw)
+        if p.mlp == "lds":
             # one launch: recomputes LN2 / the hidden activations, writes the operands of the two weight gradients and dx1 (+ its window-ordered copy)
-            dx1, x1n, h_act, dh = ops.mlp_fused_bwd(x1, dx2, b.norm2.weight, b.norm2.bias, pk[key + "fc1.w"].view(4 * C, C), b.mlp[0].bias,
+            dx1, x1n, h_act, dh = ops.mlp_fused_bwd(s.x1, dx2, b.norm2.weight, b.norm2.bias, pk[key + "fc1.w"].view(4 * C, C), b.mlp[0].bias,
                                                     pk[key + "fc2.wT"].view(4 * C, C), _gradbuf(b.norm2.weight), _gradbuf(b.norm2.bias),
                                                     rowscale=sd2, rows_per_scale=tps, dyw=dyw, dyw_scale=sd1, geom=geom)
             if q is not None:
@@ -517,26 +607,27 @@ class _BlockFn(torch.autograd.Function):
             wgrad(dx2, h_act, b.mlp[3], rowscale=sd2)
             wgrad(dh, x1n, b.mlp[0])
         else:
-            dh = ops.gemm_nt(dx2, pk[key + "fc2.wT"].view(4 * C, C), act=2, C2=h_pre, rowscale=sd2, rows_per_scale=tps)
+            dh = ops.gemm_nt(dx2, pk[key + "fc2.wT"].view(4 * C, C), act=2, C2=s.h_pre, rowscale=sd2, rows_per_scale=tps)
             if q is not None:
                 q.flush_due()
-            wgrad(dx2, h_act, b.mlp[3], rowscale=sd2)
+            wgrad(dx2, s.h_act, b.mlp[3], rowscale=sd2)
             dx1n = ops.gemm_nt(dh, pk[key + "fc1.wT"].view(C, 4 * C))
-            wgrad(dh, x1n, b.mlp[0])
+            wgrad(dh, s.x1n, b.mlp[0])
             dx1 = torch.empty_like(x)
-            ops.layernorm_bwd(dx1n, x1, b.norm2.weight, mean2, rstd2, dx1, _gradbuf(b.norm2.weight), _gradbuf(b.norm2.bias), T, C, dres=dx2,
-                              geom=None if tok_bwd else geom, tokens_per_sample=tps, dyw=dyw, dyw_scale=None if tok_bwd else sd1, wq=q)   # (dgamma / dbeta: partial sums now, reduced with the stage's weight gradients)
+            # (dgamma / dbeta: partial sums now, reduced with the stage's weight gradients)
+            ops.layernorm_bwd(dx1n, s.x1, b.norm2.weight, s.mean2, s.rstd2, dx1, _gradbuf(b.norm2.weight), _gradbuf(b.norm2.bias), T, C, dres=dx2,
+                              geom=None if p.token_bwd else geom, tokens_per_sample=tps, dyw=dyw, dyw_scale=None if p.token_bwd else sd1, wq=q)
         # ---- attention branch
-        if tok_bwd:
-            # xnw / o hold LN1(x) / the attention output in TOKEN order here; every GEMM below has T rows
-            dtab = _gradbuf(b.attn.relative_position_bias_table)
+        dtab = _gradbuf(b.attn.relative_position_bias_table)
+        if p.token_bwd:
+            # s.xnw / s.o hold LN1(x) / the attention output in TOKEN order; every GEMM below has T rows
             do = ops.gemm_nt(dx1, pk[key + "proj.wT"].view(C, C), rowscale=sd1, rows_per_scale=tps)           # gradient of the attention output, token order
-            wgrad(dx1, o, b.attn.proj, rowscale=sd1)
+            wgrad(dx1, s.o, b.attn.proj, rowscale=sd1)
             dqkv = torch.empty((T, 3 * C), dtype=x.dtype, device=x.device)
-            dq_pad = torch.empty_like(qkv)                                                                     # only its pad rows are written (and read)
-            ops.window_attn_bwd_tokens(qkv, b.attn.relative_position_bias_table, do, lse, dqkv, dq_pad, dtab, heads, C, geom)
+            dq_pad = torch.empty_like(s.qkv)                                                                   # only its pad rows are written (and read)
+            ops.window_attn_bwd_tokens(s.qkv, b.attn.relative_position_bias_table, do, s.lse, dqkv, dq_pad, dtab, heads, C, geom)
             dxn = ops.gemm_nt(dqkv, pk[key + "qkv.wT"].view(C, 3 * C))
-            wgrad(dqkv, xnw, b.attn.qkv)
+            wgrad(dqkv, s.xnw, b.attn.qkv)
             g_qb = _gradbuf(b.attn.qkv.bias)
             if q is not None:   # the pad rows' share of the qkv bias gradient, with the stage's weight gradients (one launch for all blocks of the flush)
                 q.add_pad_colsum(dq_pad, g_qb, geom)
@@ -544,48 +635,48 @@ class _BlockFn(torch.autograd.Function):
                 with ops.side_stream():
                     ops.window_pad_rows_colsum(dq_pad, g_qb, geom)
             dx = torch.empty_like(x)
-            ops.layernorm_bwd(dxn, x, b.norm1.weight, mean1, rstd1, dx, _gradbuf(b.norm1.weight), _gradbuf(b.norm1.bias), T, C, dres=dx1, wq=q)
+            ops.layernorm_bwd(dxn, x, b.norm1.weight, s.mean1, s.rstd1, dx, _gradbuf(b.norm1.weight), _gradbuf(b.norm1.bias), T, C, dres=dx1, wq=q)
         else:
+            # s.xnw / s.o and every gradient below are in window order (rows, pads included)
             do = ops.gemm_nt(dyw, pk[key + "proj.wT"].view(C, C))
-            wgrad(dyw, o, b.attn.proj, rps=geom.rows // geom.B)
-            dqkv = torch.empty_like(qkv)
-            ops.window_attn_bwd(qkv, b.attn.relative_position_bias_table, do, lse, dqkv, _gradbuf(b.attn.relative_position_bias_table), heads, C, geom)
-        if not tok_bwd:
+            wgrad(dyw, s.o, b.attn.proj, rps=rpw)
+            dqkv = torch.empty_like(s.qkv)
+            ops.window_attn_bwd(s.qkv, b.attn.relative_position_bias_table, do, s.lse, dqkv, dtab, heads, C, geom)
             dxnw = ops.gemm_nt(dqkv, pk[key + "qkv.wT"].view(C, 3 * C))
-            wgrad(dqkv, xnw, b.attn.qkv, rps=geom.rows // geom.B)
+            wgrad(dqkv, s.xnw, b.attn.qkv, rps=rpw)
             dx = torch.empty_like(x)
-            ops.layernorm_bwd(dxnw, x, b.norm1.weight, mean1, rstd1, dx, _gradbuf(b.norm1.weight), _gradbuf(b.norm1.bias), T, C, src_mode=1, geom=geom, dres=dx1, wq=q)
+            ops.layernorm_bwd(dxnw, x, b.norm1.weight, s.mean1, s.rstd1, dx, _gradbuf(b.norm1.weight), _gradbuf(b.norm1.bias), T, C, src_mode=1, geom=geom,
+                              dres=dx1, wq=q)
         # the block's own side-stream launches (fp32 parity mode) read temporaries of this block: join before they are released.  With the queue
         # (bf16) the operands stay referenced by it and NOTHING may be joined here: a join makes this block's successor wait for every weight
         # gradient the last flush put on the side stream -- the trace showed the two queues taking turns (>= 2 kernels in flight for 4 of 52 ms)
-        if q is None or not ops.WQ_LATE_JOIN:
+        if q is None:
             ops.join_side()
         return dx, None, None, None, None
 
 
 class _StageFlushFn(torch.autograd.Function):
     """identity at the input of an encoder stage; its backward runs when the stage's input-gradient chain is complete and issues the
-    weight gradients queued by the stage's blocks (and its patch merging) as grouped launches"""
+    weight gradients queued by the stage's blocks (and its patch merging) as grouped launches, as `flush_actions` says"""
 
     @staticmethod
     def forward(ctx, x, wq, last=False):
         ctx.wq, ctx.last = wq, last    # last: the first stage -- its flush ends the backward pass and has the chip to itself
+        ctx.flush_after_first = BlockSwitches.current().flush_after_first
         return x.view_as(x)
 
     @staticmethod
     def backward(ctx, g):
-        # Joining the previous stage's launch here makes the next input-gradient kernel a successor of the side chain: the HIP graph executor then puts
-        # the whole next main segment on the side chain's queue, BEHIND the weight gradients just flushed -- the trace showed the two queues alternating
-        # (>= 2 kernels in flight for 4 of 52 ms).  With the late join the side chain only hangs off the main chain (fork edges), the operands stay
-        # referenced by the queue until the end-of-backward join.
-        if not ops.WQ_LATE_JOIN or ctx.wq.sync_after_flush:
-            ctx.wq.join()     # the previous stage's launch (if any) has had a whole stage of input-gradient work to finish under
-        if ops.WQ_FLUSH_AFTER_FIRST and not ctx.last and not ctx.wq.sync_after_flush:
-            ctx.wq.request_flush()   # issued by the next block's backward behind its first kernel
+        wq = ctx.wq
+        act = flush_actions(ctx.last, wq.sync_after_flush, ctx.flush_after_first)
+        if act.join_before:
+            wq.join()
+        if act.request:
+            wq.request_flush()
         else:
-            ctx.wq.flush(foreground=ctx.last)
-        if ctx.wq.sync_after_flush:
-            ctx.wq.join()
+            wq.flush(foreground=act.foreground)
+        if act.join_after:
+            wq.join()
         return g, None, None
 
 
@@ -630,8 +721,9 @@ class _MergeFn(torch.autograd.Function):
         Cin = m.dim
         dy = dy.contiguous()
         dxg = ops.gemm_nt(dy, m._pk[m._key + "red.wT"].view(8 * Cin, 2 * Cin))
-        if ops.GROUPED_WGRAD and dy.dtype == torch.bfloat16:
-            m._wq.add(dy, xg, _gradbuf(m.reduction.weight), rows_per_sample=rows // geom.B)
+        q = wgrad_queue_for(m, dy.dtype)
+        if q is not None:
+            q.add(dy, xg, _gradbuf(m.reduction.weight), rows_per_sample=rows // geom.B)
         else:
             ops.gemm_tn(dy, xg, _gradbuf(m.reduction.weight))
         dx = torch.empty_like(x)
@@ -908,6 +1000,14 @@ class SwinBlock3D(nn.Module):
         hid = int(dim * mlp_ratio)
         self.mlp = nn.Sequential(nn.Linear(dim, hid), nn.GELU(), nn.Dropout(0.0), nn.Linear(hid, dim), nn.Dropout(0.0))
 
+    _sw = None   # packed weight streams of the fused kernels, by kind (set by the model's _build_swin_streams for the widths csrc/swin_block.hip supports)
+    _wq = None   # the model's weight-gradient queue (set by its _build_packer)
+
+    def _plan(self, geom: WinGeom, dtype, x_grad: bool) -> BlockPlan:
+        """plan_swin_block on this block's dimensions and packed streams, with the switches as they are now"""
+        return plan_swin_block(self.dim, self.num_heads, self.mlp[0].out_features, geom.tokens, geom.rows, geom.B, dtype, x_grad, self._sw is not None,
+                               ops.mlp_fused_supported(self.dim), self._wq is not None, BlockSwitches.current())
+
     def _sd_noise(self, B, device):
         if not self.training or self.sd_prob == 0.0:
             return None
@@ -944,8 +1044,9 @@ class _Stage(nn.Sequential):
         m._ensure_ready(x.device)
         if x.dtype != m.compute_dtype:
             x = x.to(m.compute_dtype)
-        if ops.GROUPED_WGRAD and m.compute_dtype == torch.bfloat16 and torch.is_grad_enabled() and x.requires_grad:
-            x = _StageFlushFn.apply(x, m._wq)
+        q = wgrad_queue_for(m, m.compute_dtype)
+        if q is not None and torch.is_grad_enabled() and x.requires_grad:
+            x = _StageFlushFn.apply(x, q)
         m._packer.wait_late()   # the layouts of stages >= LATE_STAGE are produced on the side stream: a stage called on its own must wait for them too
         for mod in self:
             x = mod(x.contiguous())
@@ -1210,13 +1311,13 @@ class SwinTransformer_MAE3D_New(nn.Module):
         gradients, then the trigger."""
         if si >= _Packer.LATE_STAGE:
             self._packer.wait_late()
-        grouped = ops.GROUPED_WGRAD and self.compute_dtype == torch.bfloat16 and torch.is_grad_enabled() and x.requires_grad
+        q = wgrad_queue_for(self, self.compute_dtype) if torch.is_grad_enabled() and x.requires_grad else None
         groups = red.chunk_groups if (red is not None and si == getattr(red, "chunk_stage", -1) and red.chunk_groups) else [list(self.stages[si])]
         for k, grp in enumerate(groups):
             if red is not None:
                 x = red.trigger(x, red.seg_stage(si, k))  # backward reaching here => this range's gradients are complete
-            if grouped:
-                x = _StageFlushFn.apply(x, self._wq, si == 0 and k == 0)
+            if q is not None:
+                x = _StageFlushFn.apply(x, q, si == 0 and k == 0)
             for mod in grp:
                 if isinstance(mod, SwinBlock3D):
                     x = mod(x, None if sd_noise is None else sd_noise[bi])

@@ -33,7 +33,6 @@ class side_stream:
     allocator lifetimes trivial: every tensor touched on the side stream outlives the join."""
     _streams = {}
     enabled = __import__("os").environ.get("NMH_NO_SIDE", "0") != "1"
-    min_rows = int(__import__("os").environ.get("NMH_SIDE_MIN_ROWS", "0"))  # blocks with fewer token rows stay single-stream
 
     def __init__(self, enable: bool = True):
         self.enable = enable
@@ -162,15 +161,11 @@ class _TnProblem(ctypes.Structure):   # include/nerfmae_hip.h: nmh_tn_problem
 
 GROUPED_WGRAD = __import__("os").environ.get("NMH_TNG", "1") != "0"
 DEFER_DECODER_WGRAD = __import__("os").environ.get("NMH_DEFER_DEC", "1") == "1"
-WQ_LATE_JOIN = __import__("os").environ.get("NMH_WQ_LATE_JOIN", "1") == "1"   # weight-gradient queue: join only at the end of the backward pass
 # A stage's flush forks off behind the FIRST input-gradient kernel of the next stage instead of in front of it (round 5).  In the captured graph both are
 # successors of the stage's last kernel; the HIP graph executor keeps the successor captured first on the predecessor's queue and gives the other one a new
 # queue plus a cross-queue wait -- and that wait was released only ~10 side kernels later (1 grid: 0.58 ms with the input-gradient queue idle at the
 # stage 3 -> 2 boundary, profiles/r5k_timeline_1grids.txt 6.86 -> 7.43 ms).  Captured first, the chain stays on its queue and the side launches take the wait.
 WQ_FLUSH_AFTER_FIRST = __import__("os").environ.get("NMH_WQ_FLUSH_AFTER_FIRST", "1") == "1"
-
-
-TNG_FOREGROUND = __import__("os").environ.get("NMH_TNG_FOREGROUND", "1") != "0"
 
 
 class _LnReduceItem(ctypes.Structure):   # include/nerfmae_hip.h: nmh_ln_reduce_item
@@ -279,7 +274,7 @@ class WgradQueue:
             arr[i] = _TnProblem(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), dW.data_ptr(), B.shape[1],
                                 0 if dbias is None else dbias.data_ptr(), 0 if rs is None else rs.data_ptr(), A.shape[0], A.shape[1], B.shape[1], rps)
         ws = _tn_workspace(group[0][0].device)
-        lib().call("nmh_gemm_tn_grouped_fg" if foreground and TNG_FOREGROUND else "nmh_gemm_tn_grouped", BF16, arr, len(group), ws,
+        lib().call("nmh_gemm_tn_grouped_fg" if foreground else "nmh_gemm_tn_grouped", BF16, arr, len(group), ws,
                    0 if ws is None else ws.numel(), _st())
 
     def flush(self, foreground=False):
@@ -732,23 +727,15 @@ def gemm_nt_window_scatter(A, W, out, resid, bias, rowscale, tokens_per_sample, 
     return out
 
 
-TOKEN_BWD_UNFUSED = __import__("os").environ.get("NMH_TOKEN_BWD_UNFUSED", "1") != "0"   # ... also behind the unfused attention forward (small launches, stage 3, fp32)
-TOKEN_BWD = __import__("os").environ.get("NMH_TOKEN_BWD", "1") != "0"   # padded stages behind a fused attention forward: token-ordered backward (model._BlockFn)
+# switches and thresholds of a Swin block's kernel path: model.plan_swin_block holds the rules (and the measurements behind the defaults)
+TOKEN_BWD = __import__("os").environ.get("NMH_TOKEN_BWD", "1") != "0"   # padded stages: token-ordered backward, behind the fused and the unfused attention forward
 MLP_FUSED = __import__("os").environ.get("NMH_MLP_FUSED", "1") != "0"
-MLP_FUSED_MIN_ROWS = int(__import__("os").environ.get("NMH_MLP_FUSED_MIN_ROWS", "4096"))   # fewer rows: too few 64-row workgroups to fill the chip, the unfused chain wins
-
-
-# widths that take the fused kernels by default.  Measured (tools/bench_mlp_fused.py, 8 grids per GPU, forward + backward): C = 96 (persistent
-# kernels, both weight matrices resident in LDS) 187 + 478 us against 457 + 555 us for the unfused chain; the chunk-ring kernels win the
-# forward at C = 192 (77 vs 136 us) but lose it back in the backward (249 vs 204 us) and lose both at C = 384 (8000 rows = 125 workgroups,
-# each a serial chain of 48 weight chunks) -- those widths stay on the unfused chain unless listed here
+MLP_FUSED_MIN_ROWS = int(__import__("os").environ.get("NMH_MLP_FUSED_MIN_ROWS", "4096"))
 MLP_FUSED_WIDTHS = tuple(int(v) for v in __import__("os").environ.get("NMH_MLP_FUSED_WIDTHS", "96").split(",") if v)
 
 
-def mlp_fused_ok(x, C: int, rows: int) -> bool:
-    """dispatch rule of the fused MLP kernels: bf16, a width that profits (MLP_FUSED_WIDTHS) and enough rows to give every CU work"""
-    return (MLP_FUSED and x.dtype == torch.bfloat16 and C in MLP_FUSED_WIDTHS and rows >= MLP_FUSED_MIN_ROWS
-            and bool(lib().call("nmh_mlp_fused_supported", C)))
+def mlp_fused_supported(C: int) -> bool:
+    return bool(lib().call("nmh_mlp_fused_supported", C))
 
 
 def mlp_fused_fwd(x1, gamma, beta, W1, b1, W2T, b2, rowscale=None, rows_per_scale=1, out=None, mean=None, rstd=None, eps=1e-5):
@@ -788,20 +775,10 @@ class _SwinPackItem(ctypes.Structure):   # include/nerfmae_hip.h: nmh_swin_pack_
 
 
 SWIN_FUSED = __import__("os").environ.get("NMH_SWIN", "1") != "0"
-# dispatch thresholds (tools/bench_swin_block.py): a fused workgroup is one dependent chain of ~45 us whatever the launch size, so launches that
-# cannot give most CUs a workgroup stay on the unfused kernels (one grid per GPU: 27 windows / 16 row tiles at stage 2)
 SWIN_ATTN_MIN_WINDOWS = int(__import__("os").environ.get("NMH_SWIN_ATTN_MIN_WIN", "100"))
 SWIN_MLP_MIN_ROWS = int(__import__("os").environ.get("NMH_SWIN_MLP_MIN_ROWS", "6000"))
 SWIN_MLP_WIDTHS = tuple(int(v) for v in __import__("os").environ.get("NMH_SWIN_MLP_WIDTHS", "192,384").split(",") if v)   # C = 96 keeps csrc/mlp_fused.hip (weights resident in LDS)
 SWIN_ATTN_WIDTHS = tuple(int(v) for v in __import__("os").environ.get("NMH_SWIN_ATTN_WIDTHS", "96,192,384").split(",") if v)
-
-
-def swin_attn_ok(x, C: int, geom) -> bool:
-    return SWIN_FUSED and x.dtype == torch.bfloat16 and C in SWIN_ATTN_WIDTHS and geom.rows // 64 >= SWIN_ATTN_MIN_WINDOWS
-
-
-def swin_mlp_ok(x, C: int, rows: int) -> bool:
-    return SWIN_FUSED and x.dtype == torch.bfloat16 and C in SWIN_MLP_WIDTHS and rows >= SWIN_MLP_MIN_ROWS
 
 
 def swin_supported(C: int) -> bool:

@@ -262,7 +262,7 @@ class GraphedTrainStep:
     def _split_a(self, zero=True):
         """forward + decoder backward.  The encoder features enter the decoder (and every later piece enters the next) through detached
         leaves, so each piece is its own autograd graph whose incoming gradients are the `.grad` of those leaves."""
-        from .model import _EmbedFn, _StageFlushFn, SwinBlock3D
+        from .model import _EmbedFn, _StageFlushFn, SwinBlock3D, wgrad_queue_for
         m = self.model
         if zero:
             m.zero_grad()
@@ -276,11 +276,11 @@ class GraphedTrainStep:
         f1, bi = m._run_stage(1, f0, sd, bi)
         e1 = f1.detach().requires_grad_()
         groups = self._stage2_chunks()
-        grouped = ops.GROUPED_WGRAD and m.compute_dtype == torch.bfloat16
+        q = wgrad_queue_for(m, m.compute_dtype)
         x, ins, outs = e1, [], []
         for k, grp in enumerate(groups):
             ins.append(x)
-            y = _StageFlushFn.apply(x, m._wq) if grouped else x     # backward of the group ends by issuing its queued weight gradients
+            y = _StageFlushFn.apply(x, q) if q is not None else x     # backward of the group ends by issuing its queued weight gradients
             for mod in grp:
                 if isinstance(mod, SwinBlock3D):
                     y = mod(y.contiguous(), None if sd is None else sd[bi])

@@ -250,6 +250,117 @@ def test_up_block_plan_of_the_other_levels_and_backbones():
     assert p.family == "generic" and p.proj and not (p.composed_fwd or p.composed_bwd or p.centered or p.defer_conv_wgrad or p.defer_upconv_wgrad)
 
 
+# ---- the Swin block's plan (model.plan_swin_block): which form of each branch an encoder block runs, asked with plain values
+def _block_switches(**kw):
+    from nerf_mae_amd.model import BlockSwitches
+    on = dict(swin_fused=True, swin_attn_widths=(96, 192, 384), swin_attn_min_windows=100, swin_mlp_widths=(192, 384), swin_mlp_min_rows=6000, mlp_fused=True,
+              mlp_fused_widths=(96,), mlp_fused_min_rows=4096, token_bwd=True, grouped_wgrad=True, flush_after_first=True)   # the defaults of the ops switches
+    return BlockSwitches(**dict(on, **kw))
+
+
+def _block(C, heads, tokens, rows, B, dtype=torch.bfloat16, streams=True, x_grad=True, hidden=None, lds=True, queue=True, sw=None):
+    from nerf_mae_amd.model import plan_swin_block
+    return plan_swin_block(C, heads, 4 * C if hidden is None else hidden, tokens, rows, B, dtype, x_grad, streams, lds, queue, sw or _block_switches())
+
+
+# (C, heads, tokens, rows, B), keywords -> (attn, mlp, token_bwd): swin_s at 160^3 and what the tests run
+SWIN_BLOCK_CASES = {
+    "stage 0": ((96, 3, 512000, 512000, 8), {}, ("fused", "lds", False)),
+    "stage 1": ((192, 6, 64000, 64000, 8), {}, ("fused", "stream", False)),
+    "stage 2 (10^3 in 12^3)": ((384, 12, 8000, 13824, 8), {}, ("fused", "stream", True)),
+    "stage 3 (5^3 in 8^3)": ((768, 24, 1000, 4096, 8), dict(streams=False), ("tokens", "unfused", True)),
+    "stage 2, one grid (27 windows)": ((384, 12, 1000, 1728, 1), {}, ("tokens", "unfused", True)),
+    "stage 1, one grid (125 windows)": ((192, 6, 8000, 8000, 1), {}, ("fused", "stream", False)),
+    "stage 0 at 120^3 (30^3 in 32^3): the interlock": ((96, 3, 216000, 262144, 8), {}, ("fused", "lds", False)),
+    "stage 2 without an input gradient": ((384, 12, 8000, 13824, 8), dict(x_grad=False), ("fused", "stream", False)),
+    "fp32, unpadded": ((96, 3, 1024, 1024, 2), dict(dtype=torch.float32, streams=False), ("window", "unfused", False)),
+    "fp32, padded": ((384, 12, 16, 128, 2), dict(dtype=torch.float32, streams=False), ("tokens", "unfused", True)),
+    "swin_b width": ((128, 4, 1024, 1024, 2), dict(streams=False), ("window", "unfused", False)),
+}
+
+
+def test_swin_block_plan_of_swin_s_and_of_the_test_sizes():
+    for name, (dims, kw, want) in SWIN_BLOCK_CASES.items():
+        p = _block(*dims, **kw)
+        assert (p.attn, p.mlp, p.token_bwd) == want, (name, p)
+        assert p.queue_wgrad == (kw.get("dtype") != torch.float32), (name, p)    # the grouped weight-gradient kernel takes bf16 operands
+    assert not _block(96, 3, 512000, 512000, 8, queue=False).queue_wgrad
+    assert not _block(96, 3, 512000, 512000, 8, sw=_block_switches(grouped_wgrad=False)).queue_wgrad
+    # the kernels of csrc/swin_block.hip take heads = C / 32 and a hidden width of 4 C only
+    for kw in (dict(hidden=2 * 192), dict(hidden=4 * 192, streams=False)):
+        p = _block(192, 6, 64000, 64000, 8, **kw)
+        assert (p.attn, p.mlp) == ("window", "unfused"), (kw, p)
+    p = _block(192, 4, 64000, 64000, 8)
+    assert (p.attn, p.mlp) == ("window", "unfused")
+    p = _block(384, 8, 8000, 13824, 8)
+    assert (p.attn, p.mlp, p.token_bwd) == ("tokens", "unfused", True)
+    with pytest.raises(AttributeError):
+        p.attn = "fused"
+
+
+def test_swin_block_plan_switches_change_what_they_gate_alone(monkeypatch):
+    from nerf_mae_amd import ops
+    from nerf_mae_amd.model import BlockSwitches
+    s0, s1, s2 = (_block(*SWIN_BLOCK_CASES[k][0]) for k in ("stage 0", "stage 1", "stage 2 (10^3 in 12^3)"))
+    off = _block_switches(swin_fused=False)
+    assert _block(96, 3, 512000, 512000, 8, sw=off) == s0._replace(attn="window")                     # (the LDS MLP is not a Swin kernel)
+    assert _block(192, 6, 64000, 64000, 8, sw=off) == s1._replace(attn="window", mlp="unfused")
+    assert _block(384, 12, 8000, 13824, 8, sw=off) == s2._replace(attn="tokens", mlp="unfused")
+    off = _block_switches(token_bwd=False)
+    assert _block(384, 12, 8000, 13824, 8, sw=off) == s2._replace(token_bwd=False)
+    assert _block(768, 24, 1000, 4096, 8, streams=False, sw=off) == _block(768, 24, 1000, 4096, 8, streams=False)._replace(attn="window", token_bwd=False)
+    assert _block(96, 3, 512000, 512000, 8, sw=off) == s0
+    # without the LDS kernel the next eligible form takes over: none at C = 96 by default, the stream kernel where its widths list 96
+    assert _block(96, 3, 512000, 512000, 8, lds=False) == s0._replace(mlp="unfused")
+    assert _block(96, 3, 512000, 512000, 8, sw=_block_switches(mlp_fused=False)) == s0._replace(mlp="unfused")
+    assert _block(96, 3, 512000, 512000, 8, lds=False, sw=_block_switches(swin_mlp_widths=(96, 192, 384))) == s0._replace(mlp="stream")
+    # ... and at a padded stage the token-ordered backward is free again
+    i = _block(96, 3, 216000, 262144, 8)
+    assert _block(96, 3, 216000, 262144, 8, lds=False) == i._replace(mlp="unfused", token_bwd=True)
+    # thresholds: one below keeps the unfused form
+    assert _block(192, 6, 6336, 6336, 1).attn == "window" and _block(192, 6, 6400, 6400, 1).attn == "fused"          # 99 / 100 windows
+    assert _block(192, 6, 5999, 6336, 1).mlp == "unfused" and _block(192, 6, 6000, 6336, 1).mlp == "stream"
+    assert _block(96, 3, 4095, 4096, 1).mlp == "unfused" and _block(96, 3, 4096, 4096, 1).mlp == "lds"
+    # BlockSwitches.current() reads the ops globals as they are now
+    for name, field, value in (("SWIN_ATTN_MIN_WINDOWS", "swin_attn_min_windows", 1), ("SWIN_MLP_MIN_ROWS", "swin_mlp_min_rows", 1),
+                               ("MLP_FUSED_MIN_ROWS", "mlp_fused_min_rows", 1), ("TOKEN_BWD", "token_bwd", False), ("GROUPED_WGRAD", "grouped_wgrad", False),
+                               ("WQ_FLUSH_AFTER_FIRST", "flush_after_first", False), ("SWIN_MLP_WIDTHS", "swin_mlp_widths", (384,))):
+        before = BlockSwitches.current()
+        monkeypatch.setattr(ops, name, value)
+        assert BlockSwitches.current() == before._replace(**{field: value})
+
+
+def test_swin_block_plans_itself_and_names_its_queue(monkeypatch):
+    from nerf_mae_amd import ops
+    from nerf_mae_amd.model import SwinBlock3D, build_model, wgrad_queue_for
+    for name in ("SWIN_FUSED", "MLP_FUSED", "TOKEN_BWD", "GROUPED_WGRAD"):
+        monkeypatch.setattr(ops, name, True)
+    m = build_model("swin_t", resolution=32, compute_dtype=torch.float32)
+    m.flatten_parameters(torch.device("cpu"))
+    blk = next(b for b in m.stages[2] if isinstance(b, SwinBlock3D))
+    p = blk._plan(ops.WinGeom(2, 2, 2, 2, blk.shift_size), torch.float32, True)     # 2^3 tokens in 4^3 window rows
+    assert (p.attn, p.mlp, p.token_bwd, p.queue_wgrad) == ("tokens", "unfused", True, False)
+    assert ops.mlp_fused_supported(96) and not ops.mlp_fused_supported(100)
+    assert wgrad_queue_for(m, torch.float32) is None and wgrad_queue_for(m, torch.bfloat16) is m._wq and wgrad_queue_for(blk, torch.bfloat16) is m._wq
+    monkeypatch.setattr(ops, "GROUPED_WGRAD", False)
+    assert wgrad_queue_for(m, torch.bfloat16) is None
+
+
+def test_stage_flush_policy_for_every_input():
+    """model.flush_actions against the conditions _StageFlushFn.backward held inline: join first only when an all-reduce follows the flush; leave the flush to
+    the next block unless this is the last one of the backward pass or an all-reduce waits for it; the last one runs in the foreground; join after it for an
+    all-reduce"""
+    from nerf_mae_amd.model import flush_actions
+    want = {  # (last, sync_after_flush, flush_after_first) -> (join_before, request, foreground, join_after)
+        (False, False, False): (False, False, False, False), (False, False, True): (False, True, False, False),
+        (False, True, False): (True, False, False, True), (False, True, True): (True, False, False, True),
+        (True, False, False): (False, False, True, False), (True, False, True): (False, False, True, False),
+        (True, True, False): (True, False, True, True), (True, True, True): (True, False, True, True),
+    }
+    for args, res in want.items():
+        assert tuple(flush_actions(*args)) == res, args
+
+
 def test_decoder1_pack_record_names_its_buffers(monkeypatch):
     from nerf_mae_amd import ops
     from nerf_mae_amd.model import UpBlock3D, _Dec1Pack

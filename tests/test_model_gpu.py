@@ -129,6 +129,48 @@ def test_swin_b_width_trains_in_bf16():
     assert (torch.dot(fa, fb) / (fa.norm() * fb.norm())).item() > 0.995
 
 
+def test_fused_swin_block_forms_train_at_a_small_size(monkeypatch):
+    """model._BlockFn through every form of model.BlockPlan at 32^3: at the default thresholds each block of this size runs the unfused chains; with the three
+    row / window thresholds at 1 stage 0 (8^3, C = 96) runs the fused attention with the LDS MLP, stage 1 (4^3, C = 192) the fused attention with the stream
+    MLP, stage 2 (2^3 tokens in 4^3 window rows, C = 384) the fused attention with token-ordered saves and the stream MLP, stage 3 stays unfused and
+    token-ordered.  Both runs against the oracle at the bars of test_swin_b_width_trains_in_bf16"""
+    from nerf_mae_amd import ops
+    from nerf_mae_amd.model import BlockPlan, SwinBlock3D
+    from oracle import mae3d_oracle as O
+    ora, hip = _pair(SWIN_T, torch.bfloat16, res=32, init="default")
+    xs = [O.synthetic_grid((32, 32, 32), 5), O.synthetic_grid((32, 28, 30), 6)]
+    calls = {}
+    for name in ("swin_attn_fwd", "swin_mlp_fwd", "mlp_fused_fwd"):
+        real = getattr(ops, name)
+        monkeypatch.setattr(ops, name, lambda *a, _n=name, _r=real, **k: (calls.__setitem__(_n, calls.get(_n, 0) + 1), _r(*a, **k))[1])
+    plans = []
+    real_plan = SwinBlock3D._plan
+    monkeypatch.setattr(SwinBlock3D, "_plan", lambda self, *a: (plans.append(real_plan(self, *a)), plans[-1])[1])
+    bq = dict(token_bwd=False, queue_wgrad=True)
+    unfused = [BlockPlan("window", "unfused", **bq)] * 4 + [BlockPlan("tokens", "unfused", True, True)] * 8
+    lowered = ([BlockPlan("fused", "lds", **bq)] * 2 + [BlockPlan("fused", "stream", **bq)] * 2 + [BlockPlan("fused", "stream", True, True)] * 6
+               + [BlockPlan("tokens", "unfused", True, True)] * 2)
+    for low, want in ((False, unfused), (True, lowered)):
+        if low:
+            for name in ("SWIN_ATTN_MIN_WINDOWS", "SWIN_MLP_MIN_ROWS", "MLP_FUSED_MIN_ROWS"):
+                monkeypatch.setattr(ops, name, 1)
+        calls.clear()
+        del plans[:]
+        ora.zero_grad()
+        lo, lh = _run_both(ora, hip, xs, 11)
+        assert plans == want, plans
+        assert calls == (dict(swin_attn_fwd=10, swin_mlp_fwd=8, mlp_fused_fwd=2) if low else {}), calls   # the forms under test are the ones that ran
+        assert not hip._wq.pending and not hip._wq.deferred and not hip._wq._due
+        err = abs(lh[0].item() - lo[0].item()) / abs(lo[0].item())
+        fa = torch.cat([p.grad.float().cpu().flatten() for n, p in hip.named_parameters() if p.grad is not None and p.requires_grad])
+        fb = torch.cat([dict(ora.named_parameters())[n].grad.flatten() for n, p in hip.named_parameters() if p.grad is not None and p.requires_grad])
+        cos = (torch.dot(fa, fb) / (fa.norm() * fb.norm())).item()
+        print(f"[thresholds {'lowered' if low else 'default'}] loss rel {err:.2e}, gradient cosine {cos:.5f}")
+        assert err < 2e-2
+        assert_close(lh[3], lo[3], 3e-2, "reconstructed grid", elem_mult=BF16_ELEM_MULT)
+        assert cos > 0.995
+
+
 def test_fused_and_unfused_decoder_tail_agree():
     from oracle import mae3d_oracle as O
     ora, hip = _pair(TINY, torch.float32, res=32, init="default")
