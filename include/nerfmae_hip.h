@@ -450,6 +450,23 @@ NMH_API int nmh_fcos_pos_bwd(int nlevels, const int* level_dims, int N, int ncol
 NMH_API int nmh_fcos_obb_encode(const float* locations, const float* boxes, int64_t n, float* out, void* stream);
 NMH_API int nmh_fcos_obb_decode_fwd(const float* locations, const float* regression, int64_t n, float* boxes, void* stream);
 NMH_API int nmh_fcos_obb_decode_bwd(const float* regression, const float* gbox, int64_t n, float* dregression, void* stream);
+/* ---- FCOS inference post-processing (csrc/fcos_post.hip; semantics, the stated tie rules and the slot layout are in that file's header) ----
+ * FCOSPostProcessor (nerf_rpn/model/fcos/inference.py:11-195).  level_n: HOST int [nlevels] = locations n_k per level and scene, 1 <= nlevels <= 4; N scenes,
+ * 1 <= N <= 64; pre_nms_top_n >= 1; cap = sum over the levels of min(pre_nms_top_n, n_k) <= 16384; else -4 (nmh_fcos_post_cap: -1).  Level tables as above.
+ * ncols 6: regression (N, 6, ..), boxes (x0,y0,z0,x1,y1,z1), rows of 1 + 6 floats; ncols 8: regression (N, 8, ..), boxes (x,y,z,w,l,h,theta), rows of 1 + 7;
+ * the first float of a row is the level index.  Nothing waits on the host; integer atomics only where their order cannot matter. */
+NMH_API int64_t nmh_fcos_post_cap(int nlevels, const int* level_n, int N, int pre_nms_top_n);
+/* forward_for_single_feature_map (inference.py:48-129) with clip_boxes_to_mesh / remove_small_boxes (fcos/utils.py:161-209) and decode_fcos_obb
+ * (fcos/utils.py:12-61), every (level, scene) in one launch.  locations: level table of [n_k][3]; masks: level table of one byte per location (N, n_k) or NULL;
+ * grid_sizes DEVICE int [N][3], required for ncols 6 (the clip), unused for 8.  keys: DEVICE workspace [N sum n_k] uint32.
+ * -> pre_boxes [N][cap][1+6|7], pre_scores [N][cap] (level k's slots start at sum of min(pre_nms_top_n, n_j), j < k; a slot that is unused or whose box is
+ * smaller than min_size has score -1), pre_counts [nlevels][N] = boxes with a score. */
+NMH_API int nmh_fcos_post_select(int nlevels, const int* level_n, int N, int ncols, int pre_nms_top_n, const float* const* cls, const float* const* reg, const float* const* ctr, const float* const* locations, const unsigned char* const* masks, const int* grid_sizes, float pre_nms_thresh, float min_size, uint32_t* keys, float* pre_boxes, float* pre_scores, int* pre_counts, void* stream);
+/* select_over_all_levels (inference.py:164-195) over nms (fcos/utils.py:109-124), every scene in one mask launch and one scan launch.  sorted_scores, order
+ * [N][cap]: the stable descending sort of pre_scores along cap and its int64 indices.  mask: DEVICE workspace [N][cap][ceil(cap/64)] 64-bit words;
+ * keep: DEVICE workspace [N][cap] int.  post_nms_top_n <= 0: no cut.  -> boxes [N][cap][1+6|7], scores [N][cap] in decreasing score, rows past counts[b]
+ * zero; counts [N]. */
+NMH_API int nmh_fcos_post_nms(int nlevels, const int* level_n, int N, int ncols, int pre_nms_top_n, const float* pre_boxes, const float* sorted_scores, const int64_t* order, const int* pre_counts, float nms_thresh, int post_nms_top_n, uint64_t* mask, int* keep, float* boxes, float* scores, int* counts, void* stream);
 /* Per-step host parameters of the training step in ONE launch, passed as kernel arguments (no host-to-device copies):
  *  - block_bits (HOST, nb^3 bits, bit (a*nb+b)*nb+c = 1: the 4x4x4-token block (a,b,c) is removed; window_masking_3d's raster order,
  *    swin_mae3d.py:1366-1373) is expanded to the token mask tokmask[g^3] (device, uint8; tokens outside the nb^3 blocks stay 0);

@@ -652,6 +652,22 @@ int nmh_fcos_obb_decode_bwd(const float* regression, const float* gbox, int64_t 
   REQ(regression, gbox, dregression);
   return k_fcos_obb_decode_bwd(regression, gbox, (long)n, dregression, ST);
 }
+int64_t nmh_fcos_post_cap(int nlevels, const int* level_n, int N, int pre_nms_top_n) { return level_n ? k_fcos_post_cap(nlevels, level_n, N, pre_nms_top_n) : -1; }
+int nmh_fcos_post_select(int nlevels, const int* level_n, int N, int ncols, int pre_nms_top_n, const float* const* cls, const float* const* reg, const float* const* ctr,
+                         const float* const* locations, const unsigned char* const* masks, const int* grid_sizes, float pre_nms_thresh, float min_size, uint32_t* keys,
+                         float* pre_boxes, float* pre_scores, int* pre_counts, void* stream) {
+  CLR();
+  REQ(level_n, cls, reg, ctr, locations, keys, pre_boxes, pre_scores, pre_counts);
+  return k_fcos_post_select(nlevels, level_n, N, ncols, pre_nms_top_n, cls, reg, ctr, locations, masks, grid_sizes, pre_nms_thresh, min_size, (unsigned*)keys, pre_boxes, pre_scores,
+                            pre_counts, ST);
+}
+int nmh_fcos_post_nms(int nlevels, const int* level_n, int N, int ncols, int pre_nms_top_n, const float* pre_boxes, const float* sorted_scores, const int64_t* order,
+                      const int* pre_counts, float nms_thresh, int post_nms_top_n, uint64_t* mask, int* keep, float* boxes, float* scores, int* counts, void* stream) {
+  CLR();
+  REQ(level_n, pre_boxes, sorted_scores, order, pre_counts, mask, keep, boxes, scores, counts);
+  return k_fcos_post_nms(nlevels, level_n, N, ncols, pre_nms_top_n, pre_boxes, sorted_scores, (const long*)order, pre_counts, nms_thresh, post_nms_top_n, (unsigned long long*)mask, keep,
+                         boxes, scores, counts, ST);
+}
 int nmh_step_params(const uint32_t* block_bits, int nb, int g, unsigned char* tokmask, const float* hyper, float* hyper_dev, const int* extents, int n_ext, int* extents_dev,
                     void* stream) {
   CLR();

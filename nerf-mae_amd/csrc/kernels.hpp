@@ -301,6 +301,14 @@ int k_fcos_pos_bwd(int nlevels, const int* dims, int N, int ncols, int loss_type
 int k_fcos_obb_encode(const float* loc, const float* boxes, long n, float* out, hipStream_t st);
 int k_fcos_obb_decode_fwd(const float* loc, const float* reg, long n, float* out, hipStream_t st);
 int k_fcos_obb_decode_bwd(const float* reg, const float* gbox, long n, float* dreg, hipStream_t st);
+// ---- fcos_post.hip (FCOS inference post-processing: threshold, exact top-k, decode, batched NMS, post-NMS cut) ----
+// level_n: HOST [nlevels] locations per level and scene; pointer tables as above; cap = sum over levels of min(pre_top_n, n)
+long k_fcos_post_cap(int nlevels, const int* level_n, int N, int pre_top_n);
+int k_fcos_post_select(int nlevels, const int* level_n, int N, int ncols, int pre_top_n, const float* const* cls, const float* const* reg, const float* const* ctr,
+                       const float* const* locs, const unsigned char* const* masks, const int* sizes, float pre_thresh, float min_size, unsigned* keys, float* pre_boxes,
+                       float* pre_scores, int* pre_counts, hipStream_t st);
+int k_fcos_post_nms(int nlevels, const int* level_n, int N, int ncols, int pre_top_n, const float* pre_boxes, const float* sorted_scores, const long* order, const int* pre_counts,
+                    float nms_thresh, int post_top_n, unsigned long long* mask, int* keep, float* boxes, float* scores, int* counts, hipStream_t st);
 int k_step_params(const unsigned* bits, int nb, int g, unsigned char* tokmask, const float* hyper_host, float* hyper_dev, const int* ext_host, int n_ext, int* ext_dev, hipStream_t st);
 int k_grad_cast(int to_bf16, const void* src, void* dst, long n, float scale, hipStream_t st);
 

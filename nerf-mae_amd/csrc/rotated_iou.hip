@@ -102,44 +102,6 @@ __global__ __launch_bounds__(256) void obb_iou_bwd_kernel(const float* __restric
 
 // ---- all pairs: tiles of 16 rows x 64 columns, both box tiles staged in LDS with their sin / cos taken once -------------------------
 constexpr int PW_ROWS = 16, PW_COLS = 64;
-struct BoxTile { float v[8]; };   // 7 columns: x y z w l h cos sin; 6 columns: x1 y1 z1 x2 y2 z2
-template <bool AABB>
-__device__ __forceinline__ void stage_box(const float* __restrict__ src, long i, long n, BoxTile& dst) {
-  if (i < n) {
-    if (AABB) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) dst.v[k] = src[i * 6 + k];
-      dst.v[6] = dst.v[7] = 0.f;
-    } else {
-      const Obb o = obb_load(src + i * 7);
-      dst.v[0] = o.x; dst.v[1] = o.y; dst.v[2] = o.z; dst.v[3] = o.w; dst.v[4] = o.l; dst.v[5] = o.h; dst.v[6] = o.cs; dst.v[7] = o.sn;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) dst.v[k] = 0.f;
-  }
-}
-template <bool AABB>
-__device__ __forceinline__ float tile_iou(const BoxTile& a, const BoxTile& b) {
-  if (AABB) {
-    const float ix = fmaxf(fminf(a.v[3], b.v[3]) - fmaxf(a.v[0], b.v[0]), 0.f), iy = fmaxf(fminf(a.v[4], b.v[4]) - fmaxf(a.v[1], b.v[1]), 0.f);
-    const float iz = fmaxf(fminf(a.v[5], b.v[5]) - fmaxf(a.v[2], b.v[2]), 0.f);
-    const float inter = ix * iy * iz;
-    const float va = (a.v[3] - a.v[0]) * (a.v[4] - a.v[1]) * (a.v[5] - a.v[2]), vb = (b.v[3] - b.v[0]) * (b.v[4] - b.v[1]) * (b.v[5] - b.v[2]);
-    return inter / (va + vb - inter);
-  }
-  const Obb A{a.v[0], a.v[1], a.v[2], a.v[3], a.v[4], a.v[5], a.v[6], a.v[7]}, B{b.v[0], b.v[1], b.v[2], b.v[3], b.v[4], b.v[5], b.v[6], b.v[7]};
-  // cheap rejection: no z overlap, or the circumscribed circles of the BEV rectangles are disjoint
-  const float zo = fminf(A.z + 0.5f * A.h, B.z + 0.5f * B.h) - fmaxf(A.z - 0.5f * A.h, B.z - 0.5f * B.h);
-  if (!(zo > 0.f)) return 0.f;
-  const float dx = A.x - B.x, dy = A.y - B.y, rr = 0.5f * (sqrtf(A.w * A.w + A.l * A.l) + sqrtf(B.w * B.w + B.l * B.l));
-  if (dx * dx + dy * dy >= rr * rr) return 0.f;
-  bool overlap;
-  const float inter = obb_inter2d(A, B, overlap) * zo;
-  if (!overlap) return 0.f;
-  return inter / (A.w * A.l * A.h + B.w * B.l * B.h - inter);
-}
-
 template <bool AABB>
 __global__ __launch_bounds__(256) void obb_iou_pairwise_kernel(const float* __restrict__ b1, const float* __restrict__ b2, int N, int M, float* __restrict__ iou) {
   __shared__ BoxTile rows[PW_ROWS], cols[PW_COLS];

@@ -1602,3 +1602,62 @@ def fcos_obb_decode_bwd(regression, gbox):
     d = torch.empty_like(regression)
     lib().call("nmh_fcos_obb_decode_bwd", regression, gbox, regression.shape[0], d, _st())
     return d
+
+
+# ---- FCOS inference post-processing (csrc/fcos_post.hip) -----------------------------------------------------------------------------------
+FCOS_POST_MASK_BYTES_MAX = 1 << 30          # the suppression workspace N cap^2 / 8 of one call
+
+
+class FcosPostPlan:
+    """locations per level and scene, N scenes, pre_nms_top_n -> the host-side level table of the fcos_post entries, cap = sum over the levels
+    of min(pre_nms_top_n, n_k) and the level's first slot"""
+
+    def __init__(self, level_n, N, pre_nms_top_n):
+        self.L, self.N, self.n, self.top_n = len(level_n), int(N), [int(v) for v in level_n], int(pre_nms_top_n)
+        if not 1 <= self.L <= FCOS_MAX_LEVELS:
+            raise ValueError(f"FCOS post-processing takes 1 to {FCOS_MAX_LEVELS} levels, got {self.L}")
+        if not 1 <= self.N <= FCOS_MAX_SCENES:
+            raise ValueError(f"FCOS post-processing takes 1 to {FCOS_MAX_SCENES} scenes, got {self.N}")
+        if self.top_n < 1 or min(self.n) < 1:
+            raise ValueError(f"FCOS post-processing: pre_nms_top_n >= 1 and at least one location per level, got {self.top_n} and {self.n}")
+        self.cap = sum(min(self.top_n, n) for n in self.n)
+        if self.cap > OBB_NMS_MAX:
+            raise ValueError(f"FCOS post-processing keeps at most {OBB_NMS_MAX} boxes per scene before NMS, got cap = {self.cap}; lower pre_nms_top_n")
+        self.mask_bytes = self.N * self.cap * ((self.cap + 63) // 64) * 8
+        if self.mask_bytes > FCOS_POST_MASK_BYTES_MAX:
+            raise ValueError(f"FCOS post-processing: the suppression workspace of {self.N} scenes x cap {self.cap} takes {self.mask_bytes} bytes (> {FCOS_POST_MASK_BYTES_MAX}); "
+                             "lower pre_nms_top_n or pass fewer scenes per call")
+        self.dims = (ctypes.c_int * self.L)(*self.n)
+        assert lib().cdll.nmh_fcos_post_cap(self.L, self.dims, self.N, self.top_n) == self.cap
+
+    def table(self, tensors):
+        assert len(tensors) == self.L
+        return (ctypes.c_void_p * self.L)(*[t.data_ptr() for t in tensors])
+
+
+def fcos_post_select(plan, ncols, cls, reg, ctr, locations, masks, grid_sizes, pre_nms_thresh, min_size):
+    """per-level head outputs, locations [n,3], optional per-level masks, grid_sizes int32 [N,3] (required for ncols 6) ->
+    (pre_boxes [N,cap,1+6|7], pre_scores [N,cap] (-1: no box in the slot), pre_counts [L,N] int32)"""
+    _chk(*cls, *reg, *ctr, *locations, *(masks or ()), grid_sizes)
+    dev = cls[0].device
+    row = 7 if ncols == 6 else 8
+    keys = torch.empty((plan.N * sum(plan.n),), dtype=torch.int32, device=dev)
+    pre_boxes = torch.empty((plan.N, plan.cap, row), dtype=torch.float32, device=dev)
+    pre_scores = torch.empty((plan.N, plan.cap), dtype=torch.float32, device=dev)
+    pre_counts = torch.empty((plan.L, plan.N), dtype=torch.int32, device=dev)
+    lib().call("nmh_fcos_post_select", plan.L, plan.dims, plan.N, ncols, plan.top_n, plan.table(cls), plan.table(reg), plan.table(ctr), plan.table(locations),
+               plan.table(masks) if masks else None, grid_sizes, pre_nms_thresh, min_size, keys, pre_boxes, pre_scores, pre_counts, _st())
+    return pre_boxes, pre_scores, pre_counts
+
+
+def fcos_post_nms(plan, ncols, pre_boxes, sorted_scores, order, pre_counts, nms_thresh, post_nms_top_n):
+    """the stable descending sort (sorted_scores, order int64) of pre_scores -> (boxes [N,cap,1+6|7], scores [N,cap], counts [N] int32)"""
+    _chk(pre_boxes, sorted_scores, order, pre_counts)
+    dev = pre_boxes.device
+    mask = torch.empty((plan.N, plan.cap, (plan.cap + 63) // 64), dtype=torch.int64, device=dev)
+    keep = torch.empty((plan.N, plan.cap), dtype=torch.int32, device=dev)
+    boxes, scores = torch.empty_like(pre_boxes), torch.empty_like(sorted_scores)
+    counts = torch.empty((plan.N,), dtype=torch.int32, device=dev)
+    lib().call("nmh_fcos_post_nms", plan.L, plan.dims, plan.N, ncols, plan.top_n, pre_boxes, sorted_scores, order, pre_counts, nms_thresh, int(post_nms_top_n), mask, keep,
+               boxes, scores, counts, _st())
+    return boxes, scores, counts

@@ -1,6 +1,7 @@
 """Rotated 3-D RoIAlign and vertex sort: HIP-event times at the downstream shape (C = 256, map 40^3, B = 2, pooled 7^3, sampling ratio 0,
 512 ROIs of 4-30 voxels) in both layouts, the sort at [8, 1024, 24], and the oriented-box IoU / GIoU / DIoU losses, all-pairs IoU and NMS
-(second half of this file) next to their composition from framework ops around sort_v.   python tools/bench_rotated.py [reps]
+(second half of this file) next to their composition from framework ops around sort_v, and last the FCOS inference post-processing
+(tools/bench_fcos_post.py, which also runs on its own).   python tools/bench_rotated.py [reps]
 
 Printed per kernel: microseconds (median and minimum of `reps` >= 50 timed launches after 5 warm-up launches) and, for the channels-last
 kernels, effective bytes/s: forward = (8 corner rows x C x element size x contributing samples + output bytes) / time, most of it served
@@ -224,3 +225,8 @@ with torch.no_grad():
     mc, bc = timed(lambda: comp_nms(bb, sc, 0.1), reps=5, warm=1)
     kf, kc = rotated_iou.nms(bb, sc, 0.1), comp_nms(bb, sc, 0.1)
 print(f"nms N = {NB}, threshold 0.1 ({kf.numel()} kept): fused median {mf:9.1f} us  min {bf:9.1f} us | host loop over the composition (5 reps) median {mc:9.1f} us  min {bc:9.1f} us | same result: {torch.equal(kf, kc)}")
+
+# ---- FCOS inference post-processing: the fused op, its dense form eager and replayed from a graph, and a composition of the reference's steps ----
+import bench_fcos_post  # noqa: E402
+
+bench_fcos_post.main(REPS)
