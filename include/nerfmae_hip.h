@@ -467,6 +467,29 @@ NMH_API int nmh_fcos_post_select(int nlevels, const int* level_n, int N, int nco
  * keep: DEVICE workspace [N][cap] int.  post_nms_top_n <= 0: no cut.  -> boxes [N][cap][1+6|7], scores [N][cap] in decreasing score, rows past counts[b]
  * zero; counts [N]. */
 NMH_API int nmh_fcos_post_nms(int nlevels, const int* level_n, int N, int ncols, int pre_nms_top_n, const float* pre_boxes, const float* sorted_scores, const int64_t* order, const int* pre_counts, float nms_thresh, int post_nms_top_n, uint64_t* mask, int* keep, float* boxes, float* scores, int* counts, void* stream);
+/* ---- RPN anchor target assignment, sampling and training losses (csrc/rpn.hip; semantics, tie rules and the layouts are stated in that file's header) ----
+ * RegionProposalNetwork.assign_targets_to_anchors / compute_loss (nerf_rpn/model/rpn.py:240-290, 389-419) with Matcher and
+ * BalancedPositiveNegativeSampler (model/utils.py:35-211), AnchorGenerator3D (anchor.py) and the coders' encode (coder/).
+ * Common arguments.  level_dims: HOST int [nlevels][7] = (W, H, D, stride_x, stride_y, stride_z, A), 1 <= nlevels <= 4, 1 <= A <= 32; N scenes, 1 <= N <= 64;
+ * else -4 (nmh_rpn_num_blocks: -1).  Level k has W H D A anchors per scene, anchor ((w H + h) D + d) A + a; a scene's n anchors are its levels concatenated;
+ * the dense index is scene n + anchor.  base_half: HOST float [sum A][3], the half extents of the base anchors level by level (> 0).  "Level tables" are
+ * HOST arrays of nlevels DEVICE pointers to the head's per-level tensors, (N, A, W, H, D) objectness and (N, A 6|8, W, H, D) regression, channel a C + c,
+ * read and differentiated in place.  Nothing waits on the host; atomics only on maxima and integer counts, whose results do not depend on order. */
+NMH_API int64_t nmh_rpn_num_blocks(int nlevels, const int* level_dims, int N);
+/* boxes [box_offsets[N]][ncols] DEVICE, ncols 6 (x0,y0,z0,x1,y1,z1) or 7 (x,y,z,w,l,h,theta; matched through obb2hbb_3d); box_offsets HOST int [N+1],
+ * ascending from 0.  ori_sizes DEVICE int [N][3] or NULL: an anchor at grid index >= ceil(ori / stride) on any axis is padding.  gt_max: DEVICE workspace
+ * [box_offsets[N]] uint32 (may be NULL without boxes).  -> labels [N][n] (1 / 0 / -1), matched_idxs [N][n] (box row within the scene, -1, -2),
+ * targets [N][n][6|8] (the encode of box max(matched, 0); zeros in a scene without boxes). */
+NMH_API int nmh_rpn_assign(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, const float* boxes, const int* box_offsets, const int* ori_sizes, float fg_iou_thresh, float bg_iou_thresh, uint32_t* gt_max, float* labels, int* matched_idxs, float* targets, void* stream);
+/* labels [N][n] -> flags [N][n] bytes (0 unsampled, 1 positive, 2 negative), counts [N][2] = (num_pos, num_neg) with num_pos = min(#(label >= 1), want_pos),
+ * num_neg = min(#(label == 0), batch - num_pos).  rng_state DEVICE int64 [2] = (seed, counter); the counter is incremented by the call's last launch. */
+NMH_API int nmh_rpn_sample(int N, int64_t n, const float* labels, int batch, int want_pos, int64_t* rng_state, unsigned char* flags, int* counts, void* stream);
+/* ncols 6 | 8 regression values per anchor.  partials: DEVICE float workspace [3 nmh_rpn_num_blocks()].  -> scalars DEVICE float [3] = (mean over flags != 0
+ * of BCE-with-logits(objectness, flag == 1), sum over flags == 1 of smooth-L1(beta 1/9)(regression - targets) / #(flags != 0), #(flags != 0)); the losses
+ * are 0 without a sampled anchor.  _bwd: dobj, dreg (level tables in the inputs' layouts) = g_obj[0] d scalars[0] and g_reg[0] d scalars[1], every element
+ * written, exactly 0 where flag == 0; NULL g = zero. */
+NMH_API int nmh_rpn_loss_fwd(int nlevels, const int* level_dims, int N, int ncols, const float* const* objectness, const float* const* regression, const unsigned char* flags, const float* targets, float* partials, float* scalars, void* stream);
+NMH_API int nmh_rpn_loss_bwd(int nlevels, const int* level_dims, int N, int ncols, const float* const* objectness, const float* const* regression, const unsigned char* flags, const float* targets, const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj, float* const* dreg, void* stream);
 /* Per-step host parameters of the training step in ONE launch, passed as kernel arguments (no host-to-device copies):
  *  - block_bits (HOST, nb^3 bits, bit (a*nb+b)*nb+c = 1: the 4x4x4-token block (a,b,c) is removed; window_masking_3d's raster order,
  *    swin_mae3d.py:1366-1373) is expanded to the token mask tokmask[g^3] (device, uint8; tokens outside the nb^3 blocks stay 0);

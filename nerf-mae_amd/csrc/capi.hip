@@ -668,6 +668,30 @@ int nmh_fcos_post_nms(int nlevels, const int* level_n, int N, int ncols, int pre
   return k_fcos_post_nms(nlevels, level_n, N, ncols, pre_nms_top_n, pre_boxes, sorted_scores, (const long*)order, pre_counts, nms_thresh, post_nms_top_n, (unsigned long long*)mask, keep,
                          boxes, scores, counts, ST);
 }
+int64_t nmh_rpn_num_blocks(int nlevels, const int* level_dims, int N) { return k_rpn_num_blocks(nlevels, level_dims, N); }
+int nmh_rpn_assign(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, const float* boxes, const int* box_offsets, const int* ori_sizes, float fg_iou_thresh,
+                   float bg_iou_thresh, uint32_t* gt_max, float* labels, int* matched_idxs, float* targets, void* stream) {
+  CLR();
+  REQ(level_dims, base_half, box_offsets, labels, matched_idxs, targets);
+  return k_rpn_assign(nlevels, level_dims, base_half, N, ncols, boxes, box_offsets, ori_sizes, fg_iou_thresh, bg_iou_thresh, (unsigned*)gt_max, labels, matched_idxs, targets, ST);
+}
+int nmh_rpn_sample(int N, int64_t n, const float* labels, int batch, int want_pos, int64_t* rng_state, unsigned char* flags, int* counts, void* stream) {
+  CLR();
+  REQ(labels, rng_state, flags, counts);
+  return k_rpn_sample(N, (long)n, labels, batch, want_pos, (long*)rng_state, flags, counts, ST);
+}
+int nmh_rpn_loss_fwd(int nlevels, const int* level_dims, int N, int ncols, const float* const* objectness, const float* const* regression, const unsigned char* flags,
+                     const float* targets, float* partials, float* scalars, void* stream) {
+  CLR();
+  REQ(level_dims, objectness, regression, flags, targets, partials, scalars);
+  return k_rpn_loss_fwd(nlevels, level_dims, N, ncols, objectness, regression, flags, targets, partials, scalars, ST);
+}
+int nmh_rpn_loss_bwd(int nlevels, const int* level_dims, int N, int ncols, const float* const* objectness, const float* const* regression, const unsigned char* flags,
+                     const float* targets, const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj, float* const* dreg, void* stream) {
+  CLR();
+  REQ(level_dims, objectness, regression, flags, targets, scalars, dobj, dreg);
+  return k_rpn_loss_bwd(nlevels, level_dims, N, ncols, objectness, regression, flags, targets, scalars, g_obj, g_reg, dobj, dreg, ST);
+}
 int nmh_step_params(const uint32_t* block_bits, int nb, int g, unsigned char* tokmask, const float* hyper, float* hyper_dev, const int* extents, int n_ext, int* extents_dev,
                     void* stream) {
   CLR();

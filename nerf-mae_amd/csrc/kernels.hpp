@@ -309,6 +309,17 @@ int k_fcos_post_select(int nlevels, const int* level_n, int N, int ncols, int pr
                        float* pre_scores, int* pre_counts, hipStream_t st);
 int k_fcos_post_nms(int nlevels, const int* level_n, int N, int ncols, int pre_top_n, const float* pre_boxes, const float* sorted_scores, const long* order, const int* pre_counts,
                     float nms_thresh, int post_top_n, unsigned long long* mask, int* keep, float* boxes, float* scores, int* counts, hipStream_t st);
+// ---- rpn.hip (RPN anchor target assignment, balanced sampling, objectness / box losses) ----
+// dims: HOST [nlevels][7] = (W, H, D, sx, sy, sz, A); base: HOST [sum A][3] half extents; offs: HOST [N+1]; pointer tables as above.  Layouts: rpn.hip.
+#define NMH_RPN_MAX_ANCHORS 32
+long k_rpn_num_blocks(int nlevels, const int* dims, int N);
+int k_rpn_assign(int nlevels, const int* dims, const float* base, int N, int ncols, const float* boxes, const int* offs, const int* ori, float fg, float bg, unsigned* gtmax,
+                 float* labels, int* midx, float* targets, hipStream_t st);
+int k_rpn_sample(int N, long n, const float* labels, int batch, int want_pos, long* rng, unsigned char* flags, int* counts, hipStream_t st);
+int k_rpn_loss_fwd(int nlevels, const int* dims, int N, int ncols, const float* const* obj, const float* const* reg, const unsigned char* flags, const float* targets, float* partials,
+                   float* scalars, hipStream_t st);
+int k_rpn_loss_bwd(int nlevels, const int* dims, int N, int ncols, const float* const* obj, const float* const* reg, const unsigned char* flags, const float* targets,
+                   const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj, float* const* dreg, hipStream_t st);
 int k_step_params(const unsigned* bits, int nb, int g, unsigned char* tokmask, const float* hyper_host, float* hyper_dev, const int* ext_host, int n_ext, int* ext_dev, hipStream_t st);
 int k_grad_cast(int to_bf16, const void* src, void* dst, long n, float scale, hipStream_t st);
 

@@ -1,0 +1,573 @@
+// Training path of the reference's anchor-based 3-D RegionProposalNetwork, as gfx950 kernels:
+//   rpn_gtmax / rpn_assign   assign_targets_to_anchors (nerf_rpn/model/rpn.py:240-290) over batched_box_iou / box_iou_3d (model/utils.py:371-458),
+//                            Matcher(fg, bg, allow_low_quality_matches=True) (model/utils.py:98-211), obb2hbb_3d (coder/misc.py:85-93), the padding
+//                            masks of AnchorGenerator3D.get_padding_masks (anchor.py:124-152) and the coders' encode: AABBCoder.encode_single
+//                            (coder/AABB_coder.py:7-56) or MidpointOffsetCoder.encode_single / bbox2delta_sp (coder/midpoint_offset_coder.py:106-158);
+//   rpn_sample               BalancedPositiveNegativeSampler (model/utils.py:35-95), with a counter-based hash in place of torch.randperm;
+//   rpn_loss                 compute_loss (rpn.py:389-419): BCE-with-logits over the sampled anchors and smooth-L1 (beta 1/9) over the sampled
+//                            positives, both divided by the number of sampled anchors; forward and backward.
+// fp32 throughout; nothing goes to scratch; every kernel writes only its own outputs for any input; the host never waits.
+//
+// Anchors are never stored.  Level k has a grid (W, H, D), per-axis strides (sx, sy, sz) = mesh_size // grid, and A base anchors given by their half
+// extents (hx, hy, hz): the reference's table is (-w, -h, -d, w, h, d) / 2 rounded half to even, which is symmetric.  Anchor i of the level,
+// i = ((w H + h) D + d) A + a, is (w sx - hx, h sy - hy, d sz - hz, w sx + hx, h sy + hy, d sz + hz): centred at index * stride.  A scene's anchors
+// are its levels concatenated, n = sum over k of W H D A; the dense index of (scene b, level k, anchor i) is b n + off_k + i.  Head outputs are read
+// in place: objectness of level k is (N, A, W, H, D), element (b, a, loc) at (b A + a) nloc + loc; regression is (N, A C, W, H, D), channel a C + c.
+//
+// Assignment.  Ground-truth boxes are one [G_total][6|7] array, scene b owning rows off[b] .. off[b+1]-1, staged in LDS 64 at a time.  6 columns: the box;
+// 7 columns (x, y, z, w, l, h, theta): the box obb2hbb_3d gives.  iou = inter / (vol_gt + vol_anchor - inter) in the reference's order of operations,
+// without contraction, by ONE device function, so that the two passes see the same bits.  valid: with ori_sizes, index < ceil(ori / stride) on every
+// axis; else always.
+//   pass 1: gtmax[g] = max over the scene's valid anchors of iou, by a wave reduction, an LDS atomicMax per wave and one global atomicMax per
+//           workgroup and box on the bit pattern (iou >= 0, so unsigned order is float order; a maximum does not depend on order);
+//   pass 2: best, arg = max over the scene's boxes, ties to the lowest index (DEFINED here; torch.max leaves it open);
+//           m = arg if best >= fg, -1 if best < bg, else -2;  if iou(anchor, g) == gtmax[g] for some g (bitwise): m = arg (the low-quality restore;
+//           a box that no valid anchor touches has gtmax 0 and restores every valid anchor that does not touch it, as the reference does);
+//           label = 1 if m >= 0, 0 if m == -1, -1 if m == -2;  not valid: m = -1, label = -1;  a scene without boxes: m = -1, label = 0 (-1 if not valid),
+//           targets 0;  else targets = encode(box max(m, 0), anchor).
+// Sampling.  One workgroup of 1024 lanes per scene.  Candidates: label >= 1 (positive) and label == 0 (negative).  num_pos = min(#pos, want_pos),
+// num_neg = min(#neg, batch - num_pos).  Every candidate has the key hash(seed, counter, scene, index), recomputed wherever it is needed; the num_*
+// smallest keys of a class are taken, found by a radix select over three LDS histograms (11 + 11 + 10 bits) of the complemented key; equal keys
+// at the cut go to the lower anchor index.  flags: 0 unsampled, 1 positive, 2 negative.  A second launch of one lane adds 1 to the counter.
+// Loss.  One lane per head element (b, a, loc), so the dense gradients are written coalesced.  s = number of flags != 0 over all scenes;
+//   objectness = sum over flags != 0 of bce_with_logits(x, flag == 1) / s;  box_reg = sum over flags == 1 and c of smooth_l1(pred - target; 1/9) / s;
+//   both 0 when s == 0 (the reference gives NaN there).  Forward: per-workgroup partial sums, then a fixed-order pass of one workgroup.  Backward: one
+//   pass that writes every element of both gradients, exactly 0 where flag == 0.
+#include "common.hpp"
+#include "kernels.hpp"
+#include "select_scan.hpp"
+
+namespace {
+
+constexpr int RPN_CHUNK = 64;
+constexpr int RPN_MAX_A = NMH_RPN_MAX_ANCHORS;
+
+struct RpnGeom {             // kernel argument, by value
+  int L, N;
+  int W[4], H[4], D[4], sx[4], sy[4], sz[4], A[4];
+  int nloc[4], n[4], off[4]; // locations, anchors, first anchor of the level within a scene
+  int blk0[4], bps[4];       // first workgroup of the level, workgroups per scene
+  int ntot, nblocks;
+};
+struct RpnBase { float h[4][RPN_MAX_A][3]; };       // kernel argument, by value: half extents
+struct RpnOffs { int off[NMH_FCOS_MAX_SCENES + 1]; };
+template <typename T> struct RPtr4 { T* p[4]; };
+template <typename T> __device__ __forceinline__ T rpick4(const T (&a)[4], int i) { return i == 0 ? a[0] : (i == 1 ? a[1] : (i == 2 ? a[2] : a[3])); }
+
+struct RAt { int lvl, scene, i; bool active; };
+__device__ __forceinline__ RAt rpn_where(const RpnGeom& G) {
+  RAt q;
+  int b = blockIdx.x;
+  q.lvl = 0;
+#pragma unroll
+  for (int k = 1; k < 4; ++k) if (k < G.L && b >= G.blk0[k]) q.lvl = k;
+  b -= rpick4(G.blk0, q.lvl);
+  const int bps = rpick4(G.bps, q.lvl);
+  q.scene = b / bps;
+  q.i = (b - q.scene * bps) * 256 + (int)threadIdx.x;
+  q.active = q.i < rpick4(G.n, q.lvl);
+  return q;
+}
+
+struct Box6 { float x0, y0, z0, x1, y1, z1, vol; };
+
+// the level's half extents -> LDS (the workgroup is within one level)
+__device__ __forceinline__ void rpn_stage_base(const RpnBase& B, int lvl, int A, float* __restrict__ sh) {
+  const float* __restrict__ src = &B.h[0][0][0] + lvl * RPN_MAX_A * 3;
+  for (int k = threadIdx.x; k < A * 3; k += 256) sh[k] = src[k];
+}
+
+// anchor i of the level (anchor order) and whether it lies within the scene's original size
+__device__ __forceinline__ Box6 rpn_anchor(const RpnGeom& G, const float* __restrict__ sh_base, const int* __restrict__ ori, const RAt& q, bool& valid) {
+  const int A = rpick4(G.A, q.lvl), Dk = rpick4(G.D, q.lvl), Hk = rpick4(G.H, q.lvl);
+  const int sx = rpick4(G.sx, q.lvl), sy = rpick4(G.sy, q.lvl), sz = rpick4(G.sz, q.lvl);
+  const int i = q.active ? q.i : 0;
+  const int a = i % A, loc = i / A, d = loc % Dk, h = (loc / Dk) % Hk, w = loc / (Dk * Hk);
+  const float cx = (float)(w * sx), cy = (float)(h * sy), cz = (float)(d * sz);
+  const float hx = sh_base[a * 3], hy = sh_base[a * 3 + 1], hz = sh_base[a * 3 + 2];
+  Box6 b;
+  b.x0 = cx - hx; b.y0 = cy - hy; b.z0 = cz - hz; b.x1 = cx + hx; b.y1 = cy + hy; b.z1 = cz + hz;
+  b.vol = (b.x1 - b.x0) * (b.y1 - b.y0) * (b.z1 - b.z0);
+  valid = q.active;
+  if (ori) {
+    const int ox = ori[q.scene * 3], oy = ori[q.scene * 3 + 1], oz = ori[q.scene * 3 + 2];
+    valid = valid && w < (ox + sx - 1) / sx && h < (oy + sy - 1) / sy && d < (oz + sz - 1) / sz;
+  }
+  return b;
+}
+
+template <bool ORIENTED>
+__device__ __forceinline__ Box6 rpn_gt(const float* __restrict__ b) {
+  Box6 g;
+  if (ORIENTED) {
+    const float cs = cosf(b[6]), sn = sinf(b[6]);
+    const float bx = fabsf(b[3] / 2.f * cs) + fabsf(b[4] / 2.f * sn), by = fabsf(b[3] / 2.f * sn) + fabsf(b[4] / 2.f * cs), bz = b[5] / 2.f;
+    g.x0 = b[0] - bx; g.y0 = b[1] - by; g.z0 = b[2] - bz; g.x1 = b[0] + bx; g.y1 = b[1] + by; g.z1 = b[2] + bz;
+  } else {
+    g.x0 = b[0]; g.y0 = b[1]; g.z0 = b[2]; g.x1 = b[3]; g.y1 = b[4]; g.z1 = b[5];
+  }
+  g.vol = (g.x1 - g.x0) * (g.y1 - g.y0) * (g.z1 - g.z0);
+  return g;
+}
+
+// the one IoU of both passes: no contraction, so the same inputs give the same bits in either kernel
+__device__ __forceinline__ float rpn_iou(const Box6& g, const Box6& a) {
+#pragma clang fp contract(off)
+  const float w = fmaxf(fminf(g.x1, a.x1) - fmaxf(g.x0, a.x0), 0.f);
+  const float h = fmaxf(fminf(g.y1, a.y1) - fmaxf(g.y0, a.y0), 0.f);
+  const float d = fmaxf(fminf(g.z1, a.z1) - fmaxf(g.z0, a.z0), 0.f);
+  const float inter = w * h * d;
+  const float uni = g.vol + a.vol - inter;
+  const float iou = inter / uni;
+  return iou > 0.f ? iou : 0.f;              // 0 / 0, -0 and malformed boxes: no overlap, with the bits of +0
+}
+
+// ---- assignment ------------------------------------------------------------------------------------------------------------------------
+template <bool ORIENTED>
+__global__ __launch_bounds__(256) void rpn_gtmax_kernel(RpnGeom G, RpnBase B, RpnOffs S, const float* __restrict__ boxes, const int* __restrict__ ori, unsigned* __restrict__ gtmax) {
+  __shared__ Box6 sb[RPN_CHUNK];
+  __shared__ unsigned smax[RPN_CHUNK];
+  __shared__ float sh_base[RPN_MAX_A * 3];
+  const RAt q = rpn_where(G);
+  const int t = threadIdx.x;
+  rpn_stage_base(B, q.lvl, rpick4(G.A, q.lvl), sh_base);
+  __syncthreads();
+  bool valid;
+  const Box6 a = rpn_anchor(G, sh_base, ori, q, valid);
+  const int g0 = S.off[q.scene], g1 = S.off[q.scene + 1];
+  for (int c = g0; c < g1; c += RPN_CHUNK) {         // uniform over the workgroup
+    __syncthreads();
+    if (t < RPN_CHUNK) {
+      smax[t] = 0u;
+      if (c + t < g1) sb[t] = rpn_gt<ORIENTED>(boxes + (long)(c + t) * (ORIENTED ? 7 : 6));
+    }
+    __syncthreads();
+    const int m = min(RPN_CHUNK, g1 - c);
+    for (int k = 0; k < m; ++k) {                    // every lane, so that the shuffles converge
+      unsigned bits = valid ? __float_as_uint(rpn_iou(sb[k], a)) : 0u;
+      if (__any(bits != 0u)) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) bits = max(bits, (unsigned)__shfl_xor((int)bits, o, 64));
+        if ((t & 63) == 0) atomicMax(&smax[k], bits);
+      }
+    }
+    __syncthreads();
+    if (t < m && smax[t] != 0u) atomicMax(&gtmax[c + t], smax[t]);
+  }
+}
+
+__device__ __forceinline__ void rpn_encode_aabb(const float* __restrict__ g, const Box6& a, float (&o)[8]) {
+  const float ew = a.x1 - a.x0, eh = a.y1 - a.y0, ed = a.z1 - a.z0;
+  const float ex = a.x0 + 0.5f * ew, ey = a.y0 + 0.5f * eh, ez = a.z0 + 0.5f * ed;
+  const float gw = g[3] - g[0], gh = g[4] - g[1], gd = g[5] - g[2];
+  const float gx = g[0] + 0.5f * gw, gy = g[1] + 0.5f * gh, gz = g[2] + 0.5f * gd;
+  o[0] = (gx - ex) / ew; o[1] = (gy - ey) / eh; o[2] = (gz - ez) / ed;
+  o[3] = logf(gw / ew); o[4] = logf(gh / eh); o[5] = logf(gd / ed);
+  o[6] = o[7] = 0.f;
+}
+// bbox2delta_sp: ga = the largest corner x among the corners within 0.1 of the lowest y (others count as -1000), gb likewise for y at the largest x
+__device__ __forceinline__ void rpn_encode_obb(const float* __restrict__ g, const Box6& a, float (&o)[8]) {
+  const float px = (a.x0 + a.x1) * 0.5f, py = (a.y0 + a.y1) * 0.5f, pz = (a.z0 + a.z1) * 0.5f;
+  const float pw = a.x1 - a.x0, ph = a.y1 - a.y0, pd = a.z1 - a.z0;
+  const float x = g[0], y = g[1], w = g[3], h = g[4], cs = cosf(g[6]), sn = sinf(g[6]);
+  const float bx = fabsf(w / 2.f * cs) + fabsf(h / 2.f * sn), by = fabsf(w / 2.f * sn) + fabsf(h / 2.f * cs);
+  const float hx0 = x - bx, hy0 = y - by, hx1 = x + bx, hy1 = y + by;
+  const float gx = (hx0 + hx1) * 0.5f, gy = (hy0 + hy1) * 0.5f, gw = hx1 - hx0, gh = hy1 - hy0;
+  const float v1x = w / 2.f * cs, v1y = -w / 2.f * sn, v2x = -h / 2.f * sn, v2y = -h / 2.f * cs;
+  const float X[4] = {x + v1x + v2x, x + v1x - v2x, x - v1x - v2x, x - v1x + v2x}, Y[4] = {y + v1y + v2y, y + v1y - v2y, y - v1y - v2y, y - v1y + v2y};
+  const float ymin = fminf(fminf(Y[0], Y[1]), fminf(Y[2], Y[3])), xmax = fmaxf(fmaxf(X[0], X[1]), fmaxf(X[2], X[3]));
+  float ga = -3.0e38f, gb = -3.0e38f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    ga = fmaxf(ga, fabsf(Y[k] - ymin) > 0.1f ? -1000.f : X[k]);
+    gb = fmaxf(gb, fabsf(X[k] - xmax) > 0.1f ? -1000.f : Y[k]);
+  }
+  o[0] = (gx - px) / pw; o[1] = (gy - py) / ph; o[2] = (g[2] - pz) / pd;
+  o[3] = logf(gw / pw); o[4] = logf(gh / ph); o[5] = logf(g[5] / pd);
+  o[6] = (ga - gx) / gw; o[7] = (gb - gy) / gh;
+}
+
+template <bool ORIENTED>
+__global__ __launch_bounds__(256) void rpn_assign_kernel(RpnGeom G, RpnBase B, RpnOffs S, const float* __restrict__ boxes, const int* __restrict__ ori, const unsigned* __restrict__ gtmax,
+                                                         float fg, float bg, float* __restrict__ labels, int* __restrict__ midx, float* __restrict__ targets) {
+  constexpr int C = ORIENTED ? 8 : 6, NC = ORIENTED ? 7 : 6;
+  __shared__ Box6 sb[RPN_CHUNK];
+  __shared__ unsigned sm[RPN_CHUNK];
+  __shared__ float sh_base[RPN_MAX_A * 3];
+  const RAt q = rpn_where(G);
+  const int t = threadIdx.x;
+  rpn_stage_base(B, q.lvl, rpick4(G.A, q.lvl), sh_base);
+  __syncthreads();
+  bool valid;
+  const Box6 a = rpn_anchor(G, sh_base, ori, q, valid);
+  const int g0 = S.off[q.scene], g1 = S.off[q.scene + 1];
+  float best = -1.f;
+  int bi = 0;
+  bool restore = false;
+  for (int c = g0; c < g1; c += RPN_CHUNK) {         // uniform over the workgroup
+    __syncthreads();
+    if (t < RPN_CHUNK && c + t < g1) {
+      sb[t] = rpn_gt<ORIENTED>(boxes + (long)(c + t) * NC);
+      sm[t] = gtmax[c + t];
+    }
+    __syncthreads();
+    const int m = min(RPN_CHUNK, g1 - c);
+    if (valid) {
+      for (int k = 0; k < m; ++k) {
+        const float iou = rpn_iou(sb[k], a);
+        if (iou > best) { best = iou; bi = c + k - g0; }
+        restore = restore || __float_as_uint(iou) == sm[k];
+      }
+    }
+  }
+  if (!q.active) return;
+  const long p = (long)q.scene * G.ntot + rpick4(G.off, q.lvl) + q.i;
+  float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  int m = -1;
+  float lab = valid ? 0.f : -1.f;
+  if (g1 > g0) {
+    if (valid) {
+      m = best >= fg ? bi : (best < bg ? -1 : -2);
+      if (restore) m = bi;
+      lab = m >= 0 ? 1.f : (m == -1 ? 0.f : -1.f);
+    }
+    const float* __restrict__ g = boxes + (long)(g0 + max(m, 0)) * NC;
+    if (ORIENTED) rpn_encode_obb(g, a, o);
+    else rpn_encode_aabb(g, a, o);
+  }
+  labels[p] = lab;
+  midx[p] = m;
+#pragma unroll
+  for (int k = 0; k < C; ++k) targets[p * C + k] = o[k];
+}
+
+// ---- sampling ----------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long rpn_mix64(unsigned long long x) {      // the splitmix64 finaliser
+  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27; x *= 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+__device__ __forceinline__ unsigned long long rpn_stream(long seed, long counter, int scene) {
+  return rpn_mix64(rpn_mix64((unsigned long long)seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)counter + 1ull)) ^ ((unsigned long long)(scene + 1) << 40));
+}
+// complemented hash: the largest of these are the smallest keys
+__device__ __forceinline__ unsigned rpn_key(unsigned long long stream, int idx) { return ~(unsigned)(rpn_mix64(stream + (unsigned long long)idx * 0xD1342543DE82EF95ull) >> 32); }
+__device__ __forceinline__ int rpn_class(float label) { return label >= 1.f ? 0 : (label == 0.f ? 1 : -1); }
+
+enum { SEL_NONE = 0, SEL_ALL = 1, SEL_CUT = 2 };
+
+__global__ __launch_bounds__(SEL_T) void rpn_sample_kernel(const float* __restrict__ labels, int n, int batch, int want_pos, const long* __restrict__ rng, unsigned char* __restrict__ flags,
+                                                           int* __restrict__ counts) {
+  __shared__ int hist[2][2048];
+  __shared__ int wsum[SEL_T / 64];
+  __shared__ int sh[2];
+  const int t = threadIdx.x, scene = blockIdx.x;
+  const float* __restrict__ lab = labels + (long)scene * n;
+  unsigned char* __restrict__ fl = flags + (long)scene * n;
+  const unsigned long long stream = rpn_stream(rng[0], rng[1], scene);
+
+  // pass 0: the candidates of both classes and the histograms of the top 11 bits
+  hist[0][t] = 0; hist[0][t + SEL_T] = 0; hist[1][t] = 0; hist[1][t + SEL_T] = 0;
+  __syncthreads();
+  int mine[2] = {0, 0};
+  for (int q = t; q < n; q += SEL_T) {
+    const int c = rpn_class(lab[q]);
+    if (c >= 0) {
+      atomicAdd(&hist[c][rpn_key(stream, q) >> 21], 1);
+      if (c == 0) ++mine[0]; else ++mine[1];
+    }
+  }
+  int have[2];
+  block_scan_excl(mine[0], have[0], wsum);           // its barriers also complete hist
+  block_scan_excl(mine[1], have[1], wsum);
+  int num[2];
+  num[0] = min(have[0], max(want_pos, 0));
+  num[1] = min(have[1], max(batch - num[0], 0));
+
+  // per class: take key > K, and need_eq of the eq_have keys == K (the lowest indices)
+  int mode[2];
+  unsigned K[2] = {0u, 0u};
+  int need_eq[2] = {0, 0}, eq_have[2] = {0, 0};
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    mode[c] = num[c] == 0 ? SEL_NONE : (num[c] >= have[c] ? SEL_ALL : SEL_CUT);
+    if (mode[c] != SEL_CUT) continue;                // uniform
+    int* h = hist[c];
+    radix_pick(h, num[c], wsum, sh);
+    const unsigned d0 = (unsigned)sh[0];
+    int r = sh[1];
+    __syncthreads();
+    h[t] = 0; h[t + SEL_T] = 0;
+    __syncthreads();
+    for (int q = t; q < n; q += SEL_T) {
+      if (rpn_class(lab[q]) != c) continue;
+      const unsigned key = rpn_key(stream, q);
+      if ((key >> 21) == d0) atomicAdd(&h[(key >> 10) & 2047u], 1);
+    }
+    __syncthreads();
+    radix_pick(h, r, wsum, sh);
+    const unsigned d01 = (d0 << 11) | (unsigned)sh[0];
+    r = sh[1];
+    __syncthreads();
+    h[t] = 0; h[t + SEL_T] = 0;
+    __syncthreads();
+    for (int q = t; q < n; q += SEL_T) {
+      if (rpn_class(lab[q]) != c) continue;
+      const unsigned key = rpn_key(stream, q);
+      if ((key >> 10) == d01) atomicAdd(&h[1024 + (key & 1023u)], 1);      // the upper half of the bins, so that radix_pick's scan order holds
+    }
+    __syncthreads();
+    radix_pick(h, r, wsum, sh);
+    K[c] = (d01 << 10) | (unsigned)(sh[0] - 1024);
+    need_eq[c] = sh[1];
+    eq_have[c] = h[sh[0]];
+    __syncthreads();
+  }
+
+  // flags; only a tie at a cut that is not taken whole needs the order of the indices
+  const bool ordered0 = mode[0] == SEL_CUT && need_eq[0] < eq_have[0], ordered1 = mode[1] == SEL_CUT && need_eq[1] < eq_have[1];
+  int run0 = 0, run1 = 0;
+  for (int base = 0; base < n; base += SEL_T) {      // uniform
+    const int q = base + t;
+    const int c = q < n ? rpn_class(lab[q]) : -1;
+    const unsigned key = c >= 0 ? rpn_key(stream, q) : 0u;
+    const int md = c == 0 ? mode[0] : (c == 1 ? mode[1] : SEL_NONE);
+    const unsigned Kc = c == 0 ? K[0] : K[1];
+    const bool eq = md == SEL_CUT && key == Kc;
+    bool sel = md == SEL_ALL || (md == SEL_CUT && key > Kc);
+    if (ordered0) {                                  // uniform
+      int tot;
+      const int rank = run0 + block_scan_excl(eq && c == 0 ? 1 : 0, tot, wsum);
+      run0 += tot;
+      sel = sel || (eq && c == 0 && rank < need_eq[0]);
+    } else {
+      sel = sel || (eq && c == 0);
+    }
+    if (ordered1) {                                  // uniform
+      int tot;
+      const int rank = run1 + block_scan_excl(eq && c == 1 ? 1 : 0, tot, wsum);
+      run1 += tot;
+      sel = sel || (eq && c == 1 && rank < need_eq[1]);
+    } else {
+      sel = sel || (eq && c == 1);
+    }
+    if (q < n) fl[q] = sel ? (unsigned char)(c == 0 ? 1 : 2) : (unsigned char)0;
+  }
+  if (t == 0) { counts[scene * 2] = num[0]; counts[scene * 2 + 1] = num[1]; }
+}
+
+__global__ void rpn_rng_advance_kernel(long* __restrict__ rng) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) rng[1] = rng[1] + 1;
+}
+
+// ---- losses ------------------------------------------------------------------------------------------------------------------------------
+// head order: lane j of (level, scene) is head element (a, loc) = (j / nloc, j % nloc), anchor i = loc A + a
+struct RHead { int lvl, scene, j, a, loc, nloc, A; long p; bool active; };
+__device__ __forceinline__ RHead rpn_head_where(const RpnGeom& G) {
+  const RAt q = rpn_where(G);
+  RHead r;
+  r.lvl = q.lvl; r.scene = q.scene; r.j = q.i; r.active = q.active;
+  r.nloc = rpick4(G.nloc, q.lvl); r.A = rpick4(G.A, q.lvl);
+  const int j = q.active ? q.i : 0;
+  r.a = j / r.nloc; r.loc = j - r.a * r.nloc;
+  r.p = (long)q.scene * G.ntot + rpick4(G.off, q.lvl) + (long)r.loc * r.A + r.a;
+  return r;
+}
+constexpr float RPN_BETA = 1.f / 9.f;
+__device__ __forceinline__ float rpn_sl1(float d) { const float a = fabsf(d); return a < RPN_BETA ? 0.5f * d * d / RPN_BETA : a - 0.5f * RPN_BETA; }
+__device__ __forceinline__ float rpn_sl1_grad(float d) { return fabsf(d) < RPN_BETA ? d / RPN_BETA : (d > 0.f ? 1.f : -1.f); }
+
+// sums (a, b, c) over the workgroup in a fixed order -> out[0 .. 2] (thread 0)
+__device__ __forceinline__ void block_sum3(float a, float b, float c, float* __restrict__ out) {
+  __shared__ float red[3][4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o, 64); b += __shfl_down(b, o, 64); c += __shfl_down(c, o, 64); }
+  const int t = threadIdx.x;
+  if ((t & 63) == 0) { red[0][t >> 6] = a; red[1][t >> 6] = b; red[2][t >> 6] = c; }
+  __syncthreads();
+  if (t == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void rpn_loss_fwd_kernel(RpnGeom G, RPtr4<const float> obj, RPtr4<const float> reg, const unsigned char* __restrict__ flags,
+                                                           const float* __restrict__ targets, float* __restrict__ partials) {
+  const RHead w = rpn_head_where(G);
+  float vo = 0.f, vr = 0.f, cnt = 0.f;
+  const int f = w.active ? flags[w.p] : 0;
+  if (f != 0) {
+    const float x = rpick4(obj.p, w.lvl)[(long)w.scene * w.A * w.nloc + w.j];
+    vo = fmaxf(x, 0.f) - (f == 1 ? x : 0.f) + log1pf(expf(-fabsf(x)));
+    cnt = 1.f;
+    if (f == 1) {
+      const float* __restrict__ rp = rpick4(reg.p, w.lvl) + ((long)w.scene * w.A + w.a) * C * w.nloc + w.loc;
+#pragma unroll
+      for (int k = 0; k < C; ++k) vr += rpn_sl1(rp[(long)k * w.nloc] - targets[w.p * C + k]);
+    }
+  }
+  block_sum3(vo, vr, cnt, partials + 3 * (long)blockIdx.x);
+}
+
+// one workgroup: fixed-order sum of the per-workgroup partials -> scalars = (objectness loss, box loss, number of sampled anchors)
+__global__ __launch_bounds__(256) void rpn_loss_final_kernel(const float* __restrict__ partials, int nblocks, float* __restrict__ scalars) {
+  __shared__ float s[3][256];
+  const int t = threadIdx.x;
+  float a = 0.f, b = 0.f, c = 0.f;
+  for (int i = t; i < nblocks; i += 256) { a += partials[3 * i]; b += partials[3 * i + 1]; c += partials[3 * i + 2]; }
+  s[0][t] = a; s[1][t] = b; s[2][t] = c;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) { s[0][t] += s[0][t + o]; s[1][t] += s[1][t + o]; s[2][t] += s[2][t + o]; }
+    __syncthreads();
+  }
+  if (t != 0) return;
+  const float cnt = s[2][0];
+  scalars[0] = cnt > 0.f ? s[0][0] / cnt : 0.f;
+  scalars[1] = cnt > 0.f ? s[1][0] / cnt : 0.f;
+  scalars[2] = cnt;
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void rpn_loss_bwd_kernel(RpnGeom G, RPtr4<const float> obj, RPtr4<const float> reg, const unsigned char* __restrict__ flags,
+                                                           const float* __restrict__ targets, const float* __restrict__ scalars, const float* __restrict__ g_obj,
+                                                           const float* __restrict__ g_reg, RPtr4<float> dobj, RPtr4<float> dreg) {
+  const RHead w = rpn_head_where(G);
+  if (!w.active) return;
+  const long at = (long)w.scene * w.A * w.nloc + w.j, rat = ((long)w.scene * w.A + w.a) * C * w.nloc + w.loc;
+  const int f = flags[w.p];
+  const float cnt = scalars[2];
+  float go = 0.f, gr[C];
+#pragma unroll
+  for (int k = 0; k < C; ++k) gr[k] = 0.f;
+  if (f != 0 && cnt > 0.f) {
+    const float x = rpick4(obj.p, w.lvl)[at];
+    const float e = expf(-fabsf(x)), r = 1.f / (1.f + e), sg = x >= 0.f ? r : e * r;
+    go = (sg - (f == 1 ? 1.f : 0.f)) * (g_obj ? g_obj[0] : 0.f) / cnt;
+    if (f == 1) {
+      const float* __restrict__ rp = rpick4(reg.p, w.lvl) + rat;
+      const float sc = (g_reg ? g_reg[0] : 0.f) / cnt;
+#pragma unroll
+      for (int k = 0; k < C; ++k) gr[k] = rpn_sl1_grad(rp[(long)k * w.nloc] - targets[w.p * C + k]) * sc;
+    }
+  }
+  rpick4(dobj.p, w.lvl)[at] = go;
+  float* __restrict__ dp = rpick4(dreg.p, w.lvl) + rat;
+#pragma unroll
+  for (int k = 0; k < C; ++k) dp[(long)k * w.nloc] = gr[k];
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------------
+// dims: [nlevels][7] = (W, H, D, sx, sy, sz, A)
+int make_geom(int nlevels, const int* dims, int N, RpnGeom& G) {
+  if (nlevels < 1 || nlevels > 4 || N < 1 || N > NMH_FCOS_MAX_SCENES || !dims) return -4;
+  G.L = nlevels; G.N = N;
+  long blocks = 0, off = 0;
+  for (int k = 0; k < 4; ++k) {
+    const int* d = dims + 7 * (k < nlevels ? k : nlevels - 1);
+    for (int j = 0; j < 7; ++j) if (d[j] < 1) return -4;
+    if (d[6] > RPN_MAX_A) return -4;
+    const long nloc = (long)d[0] * d[1] * d[2], n = nloc * d[6];
+    if (nloc > (1L << 28) || n > (1L << 30)) return -4;
+    G.W[k] = d[0]; G.H[k] = d[1]; G.D[k] = d[2]; G.sx[k] = d[3]; G.sy[k] = d[4]; G.sz[k] = d[5]; G.A[k] = d[6];
+    if ((long)d[0] * d[3] >= (1L << 24) || (long)d[1] * d[4] >= (1L << 24) || (long)d[2] * d[5] >= (1L << 24)) return -4;   // centres are exact in fp32
+    G.nloc[k] = (int)nloc; G.n[k] = (int)n;
+    G.bps[k] = (int)((n + 255) / 256);
+    G.blk0[k] = (int)blocks; G.off[k] = (int)off;
+    if (k < nlevels) { blocks += (long)G.bps[k] * N; off += n; }
+    if (blocks >= (1L << 31) - 1 || off > (1L << 30)) return -4;
+  }
+  G.ntot = (int)off; G.nblocks = (int)blocks;
+  return 0;
+}
+// base: [sum over levels of A][3] half extents, level by level
+int make_base(int nlevels, const int* dims, const float* base, RpnBase& B) {
+  if (!base) return -4;
+  for (int k = 0; k < 4; ++k) for (int a = 0; a < RPN_MAX_A; ++a) for (int c = 0; c < 3; ++c) B.h[k][a][c] = 1.f;
+  int at = 0;
+  for (int k = 0; k < nlevels; ++k) {
+    for (int a = 0; a < dims[7 * k + 6]; ++a, ++at) {
+      for (int c = 0; c < 3; ++c) {
+        const float v = base[at * 3 + c];
+        if (!(v > 0.f) || !(v < 1e6f)) return -4;
+        B.h[k][a][c] = v;
+      }
+    }
+  }
+  return 0;
+}
+template <typename T> RPtr4<T> make_ptrs(int nlevels, T* const* tab) {
+  RPtr4<T> r;
+  for (int k = 0; k < 4; ++k) r.p[k] = tab[k < nlevels ? k : nlevels - 1];
+  return r;
+}
+template <typename T> bool all_set(int nlevels, T* const* tab) {
+  if (!tab) return false;
+  for (int k = 0; k < nlevels; ++k) if (!tab[k]) return false;
+  return true;
+}
+
+}  // namespace
+
+long k_rpn_num_blocks(int nlevels, const int* dims, int N) {
+  RpnGeom G;
+  return make_geom(nlevels, dims, N, G) ? -1 : G.nblocks;
+}
+
+int k_rpn_assign(int nlevels, const int* dims, const float* base, int N, int ncols, const float* boxes, const int* offs, const int* ori, float fg, float bg, unsigned* gtmax,
+                 float* labels, int* midx, float* targets, hipStream_t st) {
+  RpnGeom G;
+  RpnBase B;
+  if (make_geom(nlevels, dims, N, G) || make_base(nlevels, dims, base, B) || (ncols != 6 && ncols != 7) || !offs || offs[0] != 0 || !(bg <= fg)) return -4;
+  RpnOffs S;
+  for (int b = 0; b <= NMH_FCOS_MAX_SCENES; ++b) S.off[b] = offs[b < N ? b : N];
+  for (int b = 0; b < N; ++b) if (offs[b + 1] < offs[b]) return -4;
+  const int total = offs[N];
+  if (total > 0 && (!boxes || !gtmax)) return -4;
+  if (total > 0) {
+    const int rc = k_fill_f32((float*)gtmax, 0.f, total, st);        // an unsigned 0 has the bits of 0.f
+    if (rc) return rc;
+    if (ncols == 7) hipLaunchKernelGGL(rpn_gtmax_kernel<true>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, boxes, ori, gtmax);
+    else hipLaunchKernelGGL(rpn_gtmax_kernel<false>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, boxes, ori, gtmax);
+    NMH_CHECK_LAUNCH();
+  }
+  if (ncols == 7) hipLaunchKernelGGL(rpn_assign_kernel<true>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, boxes, ori, gtmax, fg, bg, labels, midx, targets);
+  else hipLaunchKernelGGL(rpn_assign_kernel<false>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, boxes, ori, gtmax, fg, bg, labels, midx, targets);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
+
+int k_rpn_sample(int N, long n, const float* labels, int batch, int want_pos, long* rng, unsigned char* flags, int* counts, hipStream_t st) {
+  if (N < 1 || N > NMH_FCOS_MAX_SCENES || n < 1 || n > (1L << 30) || batch < 0 || want_pos < 0) return -4;
+  hipLaunchKernelGGL(rpn_sample_kernel, dim3(N), dim3(SEL_T), 0, st, labels, (int)n, batch, want_pos, rng, flags, counts);
+  NMH_CHECK_LAUNCH();
+  hipLaunchKernelGGL(rpn_rng_advance_kernel, dim3(1), dim3(64), 0, st, rng);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
+
+int k_rpn_loss_fwd(int nlevels, const int* dims, int N, int ncols, const float* const* obj, const float* const* reg, const unsigned char* flags, const float* targets, float* partials,
+                   float* scalars, hipStream_t st) {
+  RpnGeom G;
+  if (make_geom(nlevels, dims, N, G) || (ncols != 6 && ncols != 8) || !all_set(nlevels, obj) || !all_set(nlevels, reg)) return -4;
+  const RPtr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
+  if (ncols == 8) hipLaunchKernelGGL(rpn_loss_fwd_kernel<8>, dim3(G.nblocks), dim3(256), 0, st, G, O, R, flags, targets, partials);
+  else hipLaunchKernelGGL(rpn_loss_fwd_kernel<6>, dim3(G.nblocks), dim3(256), 0, st, G, O, R, flags, targets, partials);
+  NMH_CHECK_LAUNCH();
+  hipLaunchKernelGGL(rpn_loss_final_kernel, dim3(1), dim3(256), 0, st, partials, G.nblocks, scalars);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
+
+int k_rpn_loss_bwd(int nlevels, const int* dims, int N, int ncols, const float* const* obj, const float* const* reg, const unsigned char* flags, const float* targets,
+                   const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj, float* const* dreg, hipStream_t st) {
+  RpnGeom G;
+  if (make_geom(nlevels, dims, N, G) || (ncols != 6 && ncols != 8) || !all_set(nlevels, obj) || !all_set(nlevels, reg) || !all_set(nlevels, dobj) || !all_set(nlevels, dreg)) return -4;
+  const RPtr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
+  const RPtr4<float> DO = make_ptrs<float>(nlevels, dobj), DR = make_ptrs<float>(nlevels, dreg);
+  if (ncols == 8) hipLaunchKernelGGL(rpn_loss_bwd_kernel<8>, dim3(G.nblocks), dim3(256), 0, st, G, O, R, flags, targets, scalars, g_obj, g_reg, DO, DR);
+  else hipLaunchKernelGGL(rpn_loss_bwd_kernel<6>, dim3(G.nblocks), dim3(256), 0, st, G, O, R, flags, targets, scalars, g_obj, g_reg, DO, DR);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}

@@ -1661,3 +1661,79 @@ def fcos_post_nms(plan, ncols, pre_boxes, sorted_scores, order, pre_counts, nms_
     lib().call("nmh_fcos_post_nms", plan.L, plan.dims, plan.N, ncols, plan.top_n, pre_boxes, sorted_scores, order, pre_counts, nms_thresh, int(post_nms_top_n), mask, keep,
                boxes, scores, counts, _st())
     return boxes, scores, counts
+
+
+# ---- RPN anchor target assignment, sampling and training losses (csrc/rpn.hip) ---------------------------------------------------------------
+RPN_MAX_ANCHORS = 32
+
+
+class RpnPlan:
+    """grid sizes [(W,H,D)] and per-axis strides [(sx,sy,sz)] of 1..4 levels, the base anchors' half extents per level ([A_k][3] host floats), N scenes ->
+    the host-side level table of the rpn entries, the anchors per level and scene (n = sum n_k) and the size of the partial-sum workspace"""
+
+    def __init__(self, grid_sizes, strides, half_extents, N):
+        grid_sizes = [tuple(int(v) for v in g) for g in grid_sizes]
+        strides = [tuple(int(v) for v in s) for s in strides]
+        if not 1 <= len(grid_sizes) <= FCOS_MAX_LEVELS or len(strides) != len(grid_sizes) or len(half_extents) != len(grid_sizes):
+            raise ValueError(f"RPN ops take 1 to {FCOS_MAX_LEVELS} levels with strides and base anchors for each, got {len(grid_sizes)} grids, {len(strides)} strides, "
+                             f"{len(half_extents)} anchor tables")
+        if not 1 <= N <= FCOS_MAX_SCENES:
+            raise ValueError(f"RPN ops take 1 to {FCOS_MAX_SCENES} scenes, got {N}")
+        self.L, self.N, self.grids, self.strides = len(grid_sizes), int(N), grid_sizes, strides
+        self.A = [len(h) for h in half_extents]
+        if not all(1 <= a <= RPN_MAX_ANCHORS for a in self.A):
+            raise ValueError(f"RPN ops take 1 to {RPN_MAX_ANCHORS} anchors per location, got {self.A}")
+        self.nloc = [w * h * d for w, h, d in grid_sizes]
+        self.n_level = [n * a for n, a in zip(self.nloc, self.A)]
+        self.n = sum(self.n_level)
+        self.dims = (ctypes.c_int * (7 * self.L))(*[v for g, s, a in zip(grid_sizes, strides, self.A) for v in (*g, *s, a)])
+        flat = [float(v) for h in half_extents for row in h for v in row]
+        self.base = (ctypes.c_float * len(flat))(*flat)
+        self.nblocks = lib().cdll.nmh_rpn_num_blocks(self.L, self.dims, self.N)
+        if self.nblocks <= 0 or min(flat) <= 0:
+            raise ValueError(f"RPN ops: unsupported level table {grid_sizes} x {strides} x {self.A} anchors")
+
+    def table(self, tensors):
+        """per-level device tensors -> host array of their pointers"""
+        assert len(tensors) == self.L
+        return (ctypes.c_void_p * self.L)(*[t.data_ptr() for t in tensors])
+
+
+def rpn_assign(plan, boxes, offsets, ncols, ori_sizes, fg, bg):
+    """boxes [G,6|7] fp32 (may be empty), offsets host ints [N+1], ori_sizes int32 [N,3] or None ->
+    (labels [N,n] fp32, matched_idxs [N,n] int32, regression_targets [N,n,6|8] fp32)"""
+    _chk(boxes, ori_sizes)
+    dev = boxes.device
+    C = 6 if ncols == 6 else 8
+    labels = torch.empty((plan.N, plan.n), dtype=torch.float32, device=dev)
+    midx = torch.empty((plan.N, plan.n), dtype=torch.int32, device=dev)
+    targets = torch.empty((plan.N, plan.n, C), dtype=torch.float32, device=dev)
+    gtmax = torch.empty((max(offsets[-1], 1),), dtype=torch.int32, device=dev)
+    offs = (ctypes.c_int * (plan.N + 1))(*offsets)
+    lib().call("nmh_rpn_assign", plan.L, plan.dims, plan.base, plan.N, ncols, boxes if boxes.numel() else None, offs, ori_sizes, fg, bg, gtmax, labels, midx, targets, _st())
+    return labels, midx, targets
+
+
+def rpn_sample(labels, batch, want_pos, rng_state):
+    """labels [N,n] fp32, rng_state int64 [2] (seed, counter; the counter advances by one) -> (flags [N,n] uint8, counts [N,2] int32)"""
+    _chk(labels, rng_state)
+    N, n = labels.shape
+    flags = torch.empty((N, n), dtype=torch.uint8, device=labels.device)
+    counts = torch.empty((N, 2), dtype=torch.int32, device=labels.device)
+    lib().call("nmh_rpn_sample", N, n, labels, batch, want_pos, rng_state, flags, counts, _st())
+    return flags, counts
+
+
+def rpn_loss_fwd(plan, C, obj, reg, flags, targets):
+    """-> scalars [3] = (objectness loss, box loss, number of sampled anchors)"""
+    dev = flags.device
+    partials = torch.empty((3 * plan.nblocks,), dtype=torch.float32, device=dev)
+    scalars = torch.empty((3,), dtype=torch.float32, device=dev)
+    lib().call("nmh_rpn_loss_fwd", plan.L, plan.dims, plan.N, C, plan.table(obj), plan.table(reg), flags, targets, partials, scalars, _st())
+    return scalars
+
+
+def rpn_loss_bwd(plan, C, obj, reg, flags, targets, scalars, g_obj, g_reg):
+    dobj, dreg = [torch.empty_like(t) for t in obj], [torch.empty_like(t) for t in reg]
+    lib().call("nmh_rpn_loss_bwd", plan.L, plan.dims, plan.N, C, plan.table(obj), plan.table(reg), flags, targets, scalars, g_obj, g_reg, plan.table(dobj), plan.table(dreg), _st())
+    return dobj, dreg
