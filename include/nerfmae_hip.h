@@ -490,6 +490,24 @@ NMH_API int nmh_rpn_sample(int N, int64_t n, const float* labels, int batch, int
  * written, exactly 0 where flag == 0; NULL g = zero. */
 NMH_API int nmh_rpn_loss_fwd(int nlevels, const int* level_dims, int N, int ncols, const float* const* objectness, const float* const* regression, const unsigned char* flags, const float* targets, float* partials, float* scalars, void* stream);
 NMH_API int nmh_rpn_loss_bwd(int nlevels, const int* level_dims, int N, int ncols, const float* const* objectness, const float* const* regression, const unsigned char* flags, const float* targets, const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj, float* const* dreg, void* stream);
+/* ---- RPN proposals (csrc/rpn_post.hip; semantics, the stated tie, order and NaN rules and the slot layout are in that file's header) ----
+ * The inference half of RegionProposalNetwork.forward (nerf_rpn/model/rpn.py:292-370, 507-512): box_coder.decode_list, _get_top_n_idx and filter_proposals over
+ * clip_boxes_to_mesh, remove_small_boxes and batched_nms (model/utils.py).  level_dims, base_half and the level tables as for the entries above.  pre_nms_top_n >= 1;
+ * level k keeps t_k = min(pre_nms_top_n, n_k) anchors, cap = sum t_k <= 16384, else -4 (nmh_rpn_post_cap, nmh_rpn_post_mask_words: -1).  ncols 6: regression
+ * (N, A 6, ..), boxes (x0,y0,z0,x1,y1,z1); ncols 8: regression (N, A 8, ..), boxes (x,y,z,w,h,d,theta).  Nothing waits on the host. */
+NMH_API int64_t nmh_rpn_post_cap(int nlevels, const int* level_dims, int N, int pre_nms_top_n);
+/* 64-bit words of the suppression workspace of N scenes: N times the sum over the levels of t_k ceil(t_k / 64). */
+NMH_API int64_t nmh_rpn_post_mask_words(int nlevels, const int* level_dims, int N, int pre_nms_top_n);
+/* AABBCoder / MidpointOffsetCoder.decode_single of every anchor, not clipped -> boxes [N][n][6|7] in the anchor order of nmh_rpn_assign. */
+NMH_API int nmh_rpn_decode(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, const float* const* regression, float* boxes, void* stream);
+/* Every (level, scene) in one launch.  ori_sizes DEVICE int [N][3] or NULL (anchors in the padding are masked: below every logit, score 0); mesh_size HOST int [3].
+ * -> pre_keys [N][cap] int64 sort keys (high word nlevels - 1 - level; low word 0: empty slot, 1: masked anchor, else the order-preserving transform of the logit),
+ * pre_boxes [N][cap][6|7], pre_scores [N][cap] (sigmoid), pre_index [N][cap] (anchor index within the scene), pre_counts [nlevels][N] filled slots. */
+NMH_API int nmh_rpn_post_select(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int pre_nms_top_n, const float* const* objectness, const float* const* regression, const int* ori_sizes, const int* mesh_size, float score_thresh, float min_size, int64_t* pre_keys, float* pre_boxes, float* pre_scores, int* pre_index, int* pre_counts, void* stream);
+/* sorted_keys, order [N][cap]: the stable descending sort of pre_keys along cap and its int64 indices.  mask: DEVICE workspace of nmh_rpn_post_mask_words() words; keep:
+ * DEVICE workspace [N][cap] int.  post_nms_top_n >= 1.  -> boxes [N][cap][6|7], scores, levels, index [N][cap] in descending logit (ties: the lower slot), the first
+ * min(post_nms_top_n, survivors) rows; rows past counts[b] are zero. */
+NMH_API int nmh_rpn_post_nms(int nlevels, const int* level_dims, int N, int ncols, int pre_nms_top_n, const float* pre_boxes, const float* pre_scores, const int* pre_index, const int64_t* sorted_keys, const int64_t* order, const int* pre_counts, float nms_thresh, int post_nms_top_n, uint64_t* mask, int* keep, float* boxes, float* scores, int* levels, int* index, int* counts, void* stream);
 /* Per-step host parameters of the training step in ONE launch, passed as kernel arguments (no host-to-device copies):
  *  - block_bits (HOST, nb^3 bits, bit (a*nb+b)*nb+c = 1: the 4x4x4-token block (a,b,c) is removed; window_masking_3d's raster order,
  *    swin_mae3d.py:1366-1373) is expanded to the token mask tokmask[g^3] (device, uint8; tokens outside the nb^3 blocks stay 0);

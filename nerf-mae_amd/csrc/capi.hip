@@ -692,6 +692,29 @@ int nmh_rpn_loss_bwd(int nlevels, const int* level_dims, int N, int ncols, const
   REQ(level_dims, objectness, regression, flags, targets, scalars, dobj, dreg);
   return k_rpn_loss_bwd(nlevels, level_dims, N, ncols, objectness, regression, flags, targets, scalars, g_obj, g_reg, dobj, dreg, ST);
 }
+int64_t nmh_rpn_post_cap(int nlevels, const int* level_dims, int N, int pre_nms_top_n) { return level_dims ? k_rpn_post_cap(nlevels, level_dims, N, pre_nms_top_n) : -1; }
+int64_t nmh_rpn_post_mask_words(int nlevels, const int* level_dims, int N, int pre_nms_top_n) { return level_dims ? k_rpn_post_mask_words(nlevels, level_dims, N, pre_nms_top_n) : -1; }
+int nmh_rpn_decode(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, const float* const* regression, float* boxes, void* stream) {
+  CLR();
+  REQ(level_dims, base_half, regression, boxes);
+  return k_rpn_decode(nlevels, level_dims, base_half, N, ncols, regression, boxes, ST);
+}
+int nmh_rpn_post_select(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int pre_nms_top_n, const float* const* objectness, const float* const* regression,
+                        const int* ori_sizes, const int* mesh_size, float score_thresh, float min_size, int64_t* pre_keys, float* pre_boxes, float* pre_scores, int* pre_index,
+                        int* pre_counts, void* stream) {
+  CLR();
+  REQ(level_dims, base_half, objectness, regression, mesh_size, pre_keys, pre_boxes, pre_scores, pre_index, pre_counts);
+  return k_rpn_post_select(nlevels, level_dims, base_half, N, ncols, pre_nms_top_n, objectness, regression, ori_sizes, mesh_size, score_thresh, min_size, (long*)pre_keys, pre_boxes,
+                           pre_scores, pre_index, pre_counts, ST);
+}
+int nmh_rpn_post_nms(int nlevels, const int* level_dims, int N, int ncols, int pre_nms_top_n, const float* pre_boxes, const float* pre_scores, const int* pre_index,
+                     const int64_t* sorted_keys, const int64_t* order, const int* pre_counts, float nms_thresh, int post_nms_top_n, uint64_t* mask, int* keep, float* boxes,
+                     float* scores, int* levels, int* index, int* counts, void* stream) {
+  CLR();
+  REQ(level_dims, pre_boxes, pre_scores, pre_index, sorted_keys, order, pre_counts, mask, keep, boxes, scores, levels, index, counts);
+  return k_rpn_post_nms(nlevels, level_dims, N, ncols, pre_nms_top_n, pre_boxes, pre_scores, pre_index, (const long*)sorted_keys, (const long*)order, pre_counts, nms_thresh,
+                        post_nms_top_n, (unsigned long long*)mask, keep, boxes, scores, levels, index, counts, ST);
+}
 int nmh_step_params(const uint32_t* block_bits, int nb, int g, unsigned char* tokmask, const float* hyper, float* hyper_dev, const int* extents, int n_ext, int* extents_dev,
                     void* stream) {
   CLR();

@@ -320,6 +320,16 @@ int k_rpn_loss_fwd(int nlevels, const int* dims, int N, int ncols, const float* 
                    float* scalars, hipStream_t st);
 int k_rpn_loss_bwd(int nlevels, const int* dims, int N, int ncols, const float* const* obj, const float* const* reg, const unsigned char* flags, const float* targets,
                    const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj, float* const* dreg, hipStream_t st);
+// ---- rpn_post.hip (RPN proposals: decode, exact top-k per level on the raw logits, per-level NMS, post-NMS cut) ----
+// mesh: HOST [3]; ori: DEVICE [N][3] or NULL.  Slot layout, sort key and tie rules: rpn_post.hip.
+long k_rpn_post_cap(int nlevels, const int* dims, int N, int pre_top_n);
+long k_rpn_post_mask_words(int nlevels, const int* dims, int N, int pre_top_n);
+int k_rpn_decode(int nlevels, const int* dims, const float* base, int N, int ncols, const float* const* reg, float* boxes, hipStream_t st);
+int k_rpn_post_select(int nlevels, const int* dims, const float* base, int N, int ncols, int pre_top_n, const float* const* obj, const float* const* reg, const int* ori,
+                      const int* mesh, float score_thresh, float min_size, long* pre_keys, float* pre_boxes, float* pre_scores, int* pre_index, int* pre_counts, hipStream_t st);
+int k_rpn_post_nms(int nlevels, const int* dims, int N, int ncols, int pre_top_n, const float* pre_boxes, const float* pre_scores, const int* pre_index, const long* sorted_keys,
+                   const long* order, const int* pre_counts, float nms_thresh, int post_top_n, unsigned long long* mask, int* keep, float* boxes, float* scores, int* levels,
+                   int* index, int* counts, hipStream_t st);
 int k_step_params(const unsigned* bits, int nb, int g, unsigned char* tokmask, const float* hyper_host, float* hyper_dev, const int* ext_host, int n_ext, int* ext_dev, hipStream_t st);
 int k_grad_cast(int to_bf16, const void* src, void* dst, long n, float scale, hipStream_t st);
 

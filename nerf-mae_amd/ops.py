@@ -1737,3 +1737,65 @@ def rpn_loss_bwd(plan, C, obj, reg, flags, targets, scalars, g_obj, g_reg):
     dobj, dreg = [torch.empty_like(t) for t in obj], [torch.empty_like(t) for t in reg]
     lib().call("nmh_rpn_loss_bwd", plan.L, plan.dims, plan.N, C, plan.table(obj), plan.table(reg), flags, targets, scalars, g_obj, g_reg, plan.table(dobj), plan.table(dreg), _st())
     return dobj, dreg
+
+
+# ---- RPN proposals: decode, top-k per level, per-level NMS, post-NMS cut (csrc/rpn_post.hip) --------------------------------------------------
+class RpnPostPlan:
+    """RpnPlan + pre_nms_top_n -> what the selection adds to the level table: t_k = min(pre_nms_top_n, n_k) kept per level, the level's first slot,
+    cap = sum t_k and the words of the per-(scene, level) suppression matrices"""
+
+    def __init__(self, plan, pre_nms_top_n):
+        self.plan, self.top_n = plan, int(pre_nms_top_n)
+        if self.top_n < 1:
+            raise ValueError(f"RPN proposals: pre_nms_top_n >= 1, got {self.top_n}")
+        self.top = [min(self.top_n, n) for n in plan.n_level]
+        self.off = [sum(self.top[:k]) for k in range(plan.L)]
+        self.cap = sum(self.top)
+        if self.cap > OBB_NMS_MAX:
+            raise ValueError(f"RPN proposals keep at most {OBB_NMS_MAX} boxes per scene before NMS, got cap = {self.cap}; lower pre_nms_top_n")
+        self.mask_words = plan.N * sum(t * ((t + 63) // 64) for t in self.top)
+        if self.mask_words * 8 > FCOS_POST_MASK_BYTES_MAX:
+            raise ValueError(f"RPN proposals: the suppression workspace of {plan.N} scenes x cap {self.cap} takes {self.mask_words * 8} bytes (> {FCOS_POST_MASK_BYTES_MAX}); "
+                             "lower pre_nms_top_n or pass fewer scenes per call")
+        assert lib().cdll.nmh_rpn_post_cap(plan.L, plan.dims, plan.N, self.top_n) == self.cap
+        assert lib().cdll.nmh_rpn_post_mask_words(plan.L, plan.dims, plan.N, self.top_n) == self.mask_words
+
+
+def rpn_decode(plan, ncols, reg):
+    """per-level regression (N, A*6|8, W, H, D) -> the unclipped decode of every anchor [N, n, 6|7], anchor order"""
+    _chk(*reg)
+    boxes = torch.empty((plan.N, plan.n, 6 if ncols == 6 else 7), dtype=torch.float32, device=reg[0].device)
+    lib().call("nmh_rpn_decode", plan.L, plan.dims, plan.base, plan.N, ncols, plan.table(reg), boxes, _st())
+    return boxes
+
+
+def rpn_post_select(post, ncols, obj, reg, ori_sizes, mesh_size, score_thresh, min_size):
+    """-> (pre_keys [N,cap] int64, pre_boxes [N,cap,6|7], pre_scores [N,cap], pre_index [N,cap] int32, pre_counts [L,N] int32); slot layout and the sort key:
+    the header of csrc/rpn_post.hip"""
+    _chk(*obj, *reg, ori_sizes)
+    plan, dev = post.plan, obj[0].device
+    pre_keys = torch.empty((plan.N, post.cap), dtype=torch.int64, device=dev)
+    pre_boxes = torch.empty((plan.N, post.cap, 6 if ncols == 6 else 7), dtype=torch.float32, device=dev)
+    pre_scores = torch.empty((plan.N, post.cap), dtype=torch.float32, device=dev)
+    pre_index = torch.empty((plan.N, post.cap), dtype=torch.int32, device=dev)
+    pre_counts = torch.empty((plan.L, plan.N), dtype=torch.int32, device=dev)
+    mesh = (ctypes.c_int * 3)(*[int(v) for v in mesh_size])
+    lib().call("nmh_rpn_post_select", plan.L, plan.dims, plan.base, plan.N, ncols, post.top_n, plan.table(obj), plan.table(reg), ori_sizes, mesh, score_thresh, min_size,
+               pre_keys, pre_boxes, pre_scores, pre_index, pre_counts, _st())
+    return pre_keys, pre_boxes, pre_scores, pre_index, pre_counts
+
+
+def rpn_post_nms(post, ncols, pre_boxes, pre_scores, pre_index, sorted_keys, order, pre_counts, nms_thresh, post_nms_top_n):
+    """the stable descending sort (sorted_keys, order int64) of pre_keys -> (boxes [N,cap,6|7], scores [N,cap], levels, anchor index [N,cap] int32, counts [N] int32)"""
+    _chk(pre_boxes, pre_scores, pre_index, sorted_keys, order, pre_counts)
+    if int(post_nms_top_n) < 1:
+        raise ValueError(f"RPN proposals: post_nms_top_n >= 1, got {post_nms_top_n}")
+    plan, dev = post.plan, pre_boxes.device
+    mask = torch.empty((max(post.mask_words, 1),), dtype=torch.int64, device=dev)
+    keep = torch.empty((plan.N, post.cap), dtype=torch.int32, device=dev)
+    boxes, scores = torch.empty_like(pre_boxes), torch.empty_like(pre_scores)
+    levels, index = torch.empty_like(pre_index), torch.empty_like(pre_index)
+    counts = torch.empty((plan.N,), dtype=torch.int32, device=dev)
+    lib().call("nmh_rpn_post_nms", plan.L, plan.dims, plan.N, ncols, post.top_n, pre_boxes, pre_scores, pre_index, sorted_keys, order, pre_counts, nms_thresh,
+               int(post_nms_top_n), mask, keep, boxes, scores, levels, index, counts, _st())
+    return boxes, scores, levels, index, counts

@@ -1,24 +1,28 @@
-"""Training path of the reference's anchor-based 3-D region proposal network on the HIP kernels of csrc/rpn.hip, with the reference's names (the
-import swap is one line):
+"""The reference's anchor-based 3-D region proposal network on the HIP kernels of csrc/rpn.hip (training path) and csrc/rpn_post.hip (inference path), with
+the reference's names (the import swap is one line):
 
   AnchorGenerator3D            nerf_rpn/model/anchor.py:14-174 (same constructor, num_anchors_per_location, forward, get_padding_masks)
   rpn_assign_targets           RegionProposalNetwork.assign_targets_to_anchors + box_coder.encode (model/rpn.py:240-290, 524) over Matcher
                                (model/utils.py:98-211) and AABBCoder / MidpointOffsetCoder.encode_single (model/coder/)
   rpn_sample                   BalancedPositiveNegativeSampler (model/utils.py:35-95)
   RPNLossComputation           RegionProposalNetwork.compute_loss and the training half of forward (model/rpn.py:372-419, 514-534)
+  rpn_decode_proposals         box_coder.decode_list (model/coder/base_bbox_coder.py:55-86) over AABBCoder / MidpointOffsetCoder.decode_single
+  rpn_proposals_dense          _get_top_n_idx + filter_proposals (model/rpn.py:292-370) with fixed-size results and no host synchronisation, for HIP graphs
+  RPNProposalFilter            the inference half of forward (model/rpn.py:507-512): per-scene lists (boxes, level_indexes, scores)
 
 Head outputs are the per-level tensors as the head writes them, (N, A, W, H, D) objectness logits and (N, A*6|8, W, H, D) regression (channel
 a*C + c), fp32; they are read and differentiated in place (no permute, no cat).  Ground-truth boxes are one fp32 device tensor per scene, [k, 6]
 (x0,y0,z0,x1,y1,z1) or [k, 7] (x,y,z,w,l,h,theta in radians).  Per-anchor results are [N, n] over every scene's concatenated levels, anchor
 ((w*H + h)*D + d)*A + a within a level: the order of the reference's concatenated anchors.  The kernels never read an anchor tensor: they derive
 every anchor from its index, the per-axis strides mesh_size // grid_size and the base table, which is built here on the host with the
-reference's arithmetic.  Semantics: the header of csrc/rpn.hip and DESIGN.md 3.11.
+reference's arithmetic.  Semantics: the headers of csrc/rpn.hip and csrc/rpn_post.hip, DESIGN.md 3.11 and 3.12.
 
 Nothing waits for the host and every sum has a fixed order, so assignment + sampling + loss forward + backward can be captured with
 torch.cuda.graph (create the leaves on the capture stream: DESIGN.md 3.8, Capture); the sampler's counter lives on the device and advances
-inside the graph, so every replay draws a fresh sample.
+inside the graph, so every replay draws a fresh sample.  rpn_proposals_dense is capturable in the same way; RPNProposalFilter waits exactly once, to
+read the N counts that size its lists.
 
-Stated deviations from the reference:
+Stated deviations from the reference, training path:
   - the sampler does not reproduce torch.randperm's stream: a candidate's key is a hash of (seed, counter, scene, anchor index) and the num_pos /
     num_neg smallest keys are taken (uniform without replacement; equal keys at the cut go to the lower anchor index);
   - equal IoU of one anchor with several boxes goes to the lowest box index (torch.max leaves it open);
@@ -27,7 +31,18 @@ Stated deviations from the reference:
   - reg_loss_type other than "smooth_l1" raises NotImplementedError (the IoU-type losses need the differentiable decode of the proposals);
   - a scene without boxes has labels 0 (-1 in the padding) and all-zero targets (the reference takes log(0) there; nothing reads them);
   - without any sampled anchor both losses are 0 with zero gradients (the reference gives NaN);
-  - other dtypes than fp32 raise TypeError, CPU tensors RuntimeError, more than 4 levels, 64 scenes or 32 anchors per location ValueError."""
+  - other dtypes than fp32 raise TypeError, CPU tensors RuntimeError, more than 4 levels, 64 scenes or 32 anchors per location ValueError.
+Stated deviations, inference path:
+  - where topk and argsort leave tie winners and order open, they are defined on the fp32 bits of the logits (-0 below +0): a tie at a level's top-k
+    cut goes to the anchor that lies first in the objectness tensor's memory, (a, w, h, d) order; the pre-NMS slots are level-major, then that memory
+    order; the NMS order and the order of the results is descending logit, ties to the lower slot; a NaN logit is read as -inf;
+  - a masked anchor (padding) orders below every logit, is still selected when a level has fewer unmasked anchors than the cut, and then has score
+    exactly 0, as in the reference (sigmoid(-inf) = 0 and 0 >= score_thresh at the default 0.0);
+  - the oriented centre filter drops the box together with its score and level.  The reference's clip_boxes_to_mesh shortens only `boxes`, so its
+    later indexing pairs boxes with the wrong scores whenever a centre is outside; this module takes the aligned reading;
+  - the two identical-box and epsilon deviations of the IoU geometry (DESIGN.md 3.8) apply to the NMS;
+  - cap = sum over the levels of min(pre_nms_top_n, anchors of the level) above rotated_iou.NMS_MAX_BOXES raises ValueError, and so does a
+    suppression workspace above MASK_BYTES_MAX = 1 GiB: lower pre_nms_top_n or pass fewer scenes per call; post_nms_top_n < 1 raises ValueError."""
 from __future__ import annotations
 
 import itertools
@@ -41,6 +56,8 @@ from . import ops
 from .fcos_loss import _boxes, _check
 
 MAX_LEVELS, MAX_SCENES, MAX_ANCHORS = ops.FCOS_MAX_LEVELS, ops.FCOS_MAX_SCENES, ops.RPN_MAX_ANCHORS
+NMS_MAX_BOXES = ops.OBB_NMS_MAX
+MASK_BYTES_MAX = ops.FCOS_POST_MASK_BYTES_MAX
 
 
 class AnchorGenerator3D(nn.Module):
@@ -260,3 +277,87 @@ class RPNLossComputation(object):
             flags = sampled.contiguous()
         loss_obj, loss_reg = _RpnLoss.apply(plan, C, flags, reg_targets, *objectness, *pred_bbox_deltas)
         return {"loss_objectness": loss_obj, "loss_rpn_box_reg": loss_reg, "loss_rpn_box_reg_2d": torch.zeros((), dtype=torch.float32, device=boxes.device)}
+
+
+# ---- inference path --------------------------------------------------------------------------------------------------------------------------
+def _heads(name, anchor_generator, mesh_size, objectness, pred_bbox_deltas, C):
+    """the checks shared by the inference entries -> (plan, detached contiguous objectness or None, regression)"""
+    L = len(pred_bbox_deltas)
+    if L > MAX_LEVELS:
+        raise ValueError(f"{name} supports at most {MAX_LEVELS} levels, got {L}")
+    if L < 1 or (objectness is not None and len(objectness) != L):
+        raise ValueError(f"{name}: one objectness and one regression tensor per level")
+    _check(name, *(objectness or ()), *pred_bbox_deltas)
+    N = pred_bbox_deltas[0].shape[0]
+    if N > MAX_SCENES:
+        raise ValueError(f"{name} supports at most {MAX_SCENES} scenes, got {N}")
+    if any(r.dim() != 5 for r in pred_bbox_deltas):
+        raise ValueError(f"{name}: pred_bbox_deltas must be (N, A*{C}, W, H, D) per level")
+    grid_sizes = [tuple(r.shape[2:]) for r in pred_bbox_deltas]
+    plan = _plan(anchor_generator, mesh_size, grid_sizes, N, name)
+    for k, (r, g, A) in enumerate(zip(pred_bbox_deltas, grid_sizes, plan.A)):
+        if tuple(r.shape) != (N, A * C, *g) or (objectness is not None and tuple(objectness[k].shape) != (N, A, *g)):
+            raise ValueError(f"{name}: per level objectness (N,{A},W,H,D) and pred_bbox_deltas (N,{A * C},W,H,D); got "
+                             f"{tuple(objectness[k].shape) if objectness is not None else None}, {tuple(r.shape)}")
+    obj = None if objectness is None else [t.detach().contiguous() for t in objectness]
+    return plan, obj, [t.detach().contiguous() for t in pred_bbox_deltas]
+
+
+def rpn_decode_proposals(anchor_generator, mesh_size, pred_bbox_deltas, rotated=False):
+    """the unclipped decode of every anchor -> [N, n, 6] (x0,y0,z0,x1,y1,z1) or (rotated) [N, n, 7] (x,y,z,w,h,d,theta), anchor order; no gradient"""
+    C = 8 if rotated else 6
+    with torch.no_grad():
+        plan, _, reg = _heads("rpn_decode_proposals", anchor_generator, mesh_size, None, pred_bbox_deltas, C)
+        return ops.rpn_decode(plan, C, reg)
+
+
+def _select(name, anchor_generator, mesh_size, objectness, pred_bbox_deltas, original_mesh_sizes, pre_nms_top_n, score_thresh, min_size, rotated):
+    C = 8 if rotated else 6
+    plan, obj, reg = _heads(name, anchor_generator, mesh_size, objectness, pred_bbox_deltas, C)
+    post = plan.__dict__.setdefault("_post", {}).get(int(pre_nms_top_n))
+    if post is None:
+        post = plan._post[int(pre_nms_top_n)] = ops.RpnPostPlan(plan, pre_nms_top_n)
+    ori = _ori(name, original_mesh_sizes, plan.N, obj[0].device)
+    return post, C, ops.rpn_post_select(post, C, obj, reg, ori, [int(m) for m in mesh_size[-3:]], float(score_thresh), float(min_size))
+
+
+def rpn_proposals_dense(anchor_generator, mesh_size, objectness, pred_bbox_deltas, original_mesh_sizes, pre_nms_top_n, post_nms_top_n, nms_thresh, score_thresh=0.0,
+                        min_size=1e-3, rotated=False):
+    """original_mesh_sizes: list of N triples, an int32 device tensor [N, 3] (a host list costs one small copy) or None (no padding mask) ->
+    (boxes [N, cap, 6|7], scores [N, cap], levels [N, cap] int32, anchor_index [N, cap] int32, counts [N] int32), cap = sum over the levels of
+    min(pre_nms_top_n, anchors of the level); scene i's proposals are rows 0 .. counts[i]-1 in descending score, rows past them are zero.  Never waits for
+    the host; capturable with torch.cuda.graph."""
+    name = "rpn_proposals_dense"
+    if int(post_nms_top_n) < 1:
+        raise ValueError(f"{name}: post_nms_top_n >= 1, got {post_nms_top_n}")
+    with torch.no_grad():
+        post, C, (keys, pre_boxes, pre_scores, pre_index, pre_counts) = _select(name, anchor_generator, mesh_size, objectness, pred_bbox_deltas, original_mesh_sizes, pre_nms_top_n,
+                                                                                score_thresh, min_size, rotated)
+        sorted_keys, order = torch.sort(keys, dim=1, descending=True, stable=True)      # level-major, descending logit, ties to the lower slot, empty slots of a level last
+        return ops.rpn_post_nms(post, C, pre_boxes, pre_scores, pre_index, sorted_keys, order, pre_counts, float(nms_thresh), int(post_nms_top_n))
+
+
+class RPNProposalFilter(object):
+    """The inference half of the reference's RegionProposalNetwork.forward on the fused kernels: decode of the selected anchors, top-k per level,
+    clip / centre / size / score filters, NMS within each level and the post-NMS cut."""
+
+    def __init__(self, anchor_generator, pre_nms_top_n, post_nms_top_n, nms_thresh, score_thresh=0.0, rotated_bbox=False):
+        if len(anchor_generator.sizes) > MAX_LEVELS:
+            raise ValueError(f"RPNProposalFilter supports at most {MAX_LEVELS} levels, got {len(anchor_generator.sizes)}")
+        if int(pre_nms_top_n) < 1 or int(post_nms_top_n) < 1:
+            raise ValueError("RPNProposalFilter: pre_nms_top_n and post_nms_top_n >= 1")
+        self.anchor_generator = anchor_generator
+        self.pre_nms_top_n, self.post_nms_top_n = int(pre_nms_top_n), int(post_nms_top_n)
+        self.nms_thresh, self.score_thresh = float(nms_thresh), float(score_thresh)
+        self.rotate = bool(rotated_bbox)
+        self.min_size = 1e-3            # fixed by the reference (rpn.py:219)
+
+    def __call__(self, mesh_size, objectness, pred_bbox_deltas, original_mesh_sizes=None):
+        """mesh_size (X, Y, Z) of the padded batch; objectness, pred_bbox_deltas: the head's per-level lists; original_mesh_sizes: the scenes' sizes before
+        padding, used as the reference does, only when N > 1 -> (boxes, level_indexes, scores): per scene [K, 6|7] fp32, [K] int64 and [K] fp32 in decreasing
+        score.  One host synchronisation: the N counts."""
+        N = objectness[0].shape[0] if len(objectness) else 0
+        boxes, scores, levels, _, counts = rpn_proposals_dense(self.anchor_generator, mesh_size, objectness, pred_bbox_deltas, original_mesh_sizes if N > 1 else None,
+                                                               self.pre_nms_top_n, self.post_nms_top_n, self.nms_thresh, self.score_thresh, self.min_size, self.rotate)
+        counts = counts.tolist()                # the one synchronisation
+        return ([boxes[i, :k] for i, k in enumerate(counts)], [levels[i, :k].long() for i, k in enumerate(counts)], [scores[i, :k] for i, k in enumerate(counts)])
