@@ -180,6 +180,10 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ float sigmoid_stable(float x) {   // no overflow for any x: exp of a non-positive number only
+  const float e = expf(-fabsf(x)), r = 1.f / (1.f + e);
+  return x >= 0.f ? r : e * r;
+}
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_grad_f(float x) {
   return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.39894228040143268f * __expf(-0.5f * x * x);

@@ -43,6 +43,7 @@
 #include "kernels.hpp"
 #include "obb_geom.hpp"
 #include "fcos_decode.hpp"
+#include "levels4.hpp"
 
 namespace {
 
@@ -57,9 +58,6 @@ struct FcosGeom {            // kernel argument, by value
   int nblocks;
 };
 struct FcosOffs { int off[NMH_FCOS_MAX_SCENES + 1]; };
-template <typename T> struct Ptr4 { T* p[4]; };
-
-template <typename T> __device__ __forceinline__ T pick4(const T (&a)[4], int i) { return i == 0 ? a[0] : (i == 1 ? a[1] : (i == 2 ? a[2] : a[3])); }
 
 struct Where { int lvl, scene, loc, n; long p; bool active; };
 __device__ __forceinline__ Where fcos_where(const FcosGeom& G) {
@@ -447,16 +445,6 @@ int make_geom(int nlevels, const int* dims, int N, FcosGeom& G) {
   }
   G.nblocks = (int)blocks;
   return 0;
-}
-template <typename T> Ptr4<T> make_ptrs(int nlevels, T* const* tab) {
-  Ptr4<T> r;
-  for (int k = 0; k < 4; ++k) r.p[k] = tab ? tab[k < nlevels ? k : nlevels - 1] : nullptr;
-  return r;
-}
-template <typename T> bool all_set(int nlevels, T* const* tab) {
-  if (!tab) return false;
-  for (int k = 0; k < nlevels; ++k) if (!tab[k]) return false;
-  return true;
 }
 void launch_final(const float* partials, int nblocks, int what, float world, float* scalars, float* out0, float* out1, hipStream_t st) {
   hipLaunchKernelGGL(fcos_final_kernel, dim3(1), dim3(256), 0, st, partials, nblocks, what, world, scalars, out0, out1);

@@ -26,18 +26,18 @@
 // scores (the caller's sort; a dropped or unused slot carries the score -1 and sorts last).
 //
 // Algorithm.  select: one workgroup of 1024 lanes per (level, scene).  Pass 0 forms the key of every location (0: no candidate, else the bits
-// of s plus 1: s >= 0, so unsigned order is score order), stores it and counts the candidates.  If there are more candidates than t_k, a radix
-// select finds the t_k-th largest key K from three LDS histograms (11 + 11 + 10 bits, integer atomics: the sums do not depend on their order),
-// each scanned from the top by a workgroup prefix sum.  The compaction walks the locations in chunks of 1024 in ascending order; two
-// workgroup prefix sums per chunk give every lane the number of keys == K before it (the first t_k - #(key > K) of them are kept: the tie
-// rule) and its slot.  A kept box dropped by min_size keeps its slot with score -1, so slots never depend on an atomic; two runs are bit-identical.
-// nms: word (i, j) of a scene's matrix per wave, as obb_nms_mask of rotated_iou.hip, rows of cap/64 words for every scene; the grid is the
-// upper triangle for cap, and a workgroup whose columns start beyond the scene's count (read from device memory) exits at once.
+// of s plus 1: s >= 0, so unsigned order is score order), stores it, counts the candidates and fills the first histogram.  If there are more
+// candidates than t_k, the radix select of select_scan.hpp finds the t_k-th largest key over the stored keys; its ordered compaction gives every
+// kept location its slot, ties at the cut to the lower index.  A kept box dropped by min_size keeps its slot with score -1, so slots never depend
+// on an atomic; two runs are bit-identical.
+// nms: the bit matrix and the walk of nms_bits.hpp, rows of cap/64 words for every scene; the grid is the upper triangle for cap, and a
+// workgroup whose columns start beyond the scene's count (read from device memory) exits at once.
 #include "common.hpp"
 #include "kernels.hpp"
-#include "obb_geom.hpp"
+#include "nms_bits.hpp"
 #include "fcos_decode.hpp"
-#include "select_scan.hpp"          // SEL_T, block_scan_excl, radix_pick
+#include "select_scan.hpp"
+#include "levels4.hpp"
 
 namespace {
 
@@ -46,17 +46,10 @@ struct PostGeom {            // kernel argument, by value
   int n[4], top[4], off[4];  // locations, kept at most, first slot
   long p0[4];                // first key of (level, scene 0)
 };
-template <typename T> struct PPtr4 { T* p[4]; };
-template <typename T> __device__ __forceinline__ T ppick4(const T (&a)[4], int i) { return i == 0 ? a[0] : (i == 1 ? a[1] : (i == 2 ? a[2] : a[3])); }
-
-__device__ __forceinline__ float post_sigmoid(float x) {
-  const float e = expf(-fabsf(x)), r = 1.f / (1.f + e);
-  return x >= 0.f ? r : e * r;
-}
 
 template <bool ORIENTED>
-__global__ __launch_bounds__(SEL_T) void fcos_post_select_kernel(PostGeom G, PPtr4<const float> cls, PPtr4<const float> reg, PPtr4<const float> ctr, PPtr4<const float> locs,
-                                                                 PPtr4<const unsigned char> masks, int have_masks, const int* __restrict__ sizes, float thr, float min_size,
+__global__ __launch_bounds__(SEL_T) void fcos_post_select_kernel(PostGeom G, Ptr4<const float> cls, Ptr4<const float> reg, Ptr4<const float> ctr, Ptr4<const float> locs,
+                                                                 Ptr4<const unsigned char> masks, int have_masks, const int* __restrict__ sizes, float thr, float min_size,
                                                                  unsigned* __restrict__ keys, float* __restrict__ pre_boxes, float* __restrict__ pre_scores,
                                                                  int* __restrict__ pre_counts) {
   constexpr int C = ORIENTED ? 8 : 6, ROW = ORIENTED ? 8 : 7;
@@ -64,24 +57,23 @@ __global__ __launch_bounds__(SEL_T) void fcos_post_select_kernel(PostGeom G, PPt
   __shared__ int wsum[SEL_T / 64];
   __shared__ int sh[2];
   const int t = threadIdx.x, lvl = blockIdx.x / G.N, scene = blockIdx.x - lvl * G.N;
-  const int n = ppick4(G.n, lvl), top = ppick4(G.top, lvl), off = ppick4(G.off, lvl);
-  const float* __restrict__ pc = ppick4(cls.p, lvl) + (long)scene * n;
-  const float* __restrict__ pt = ppick4(ctr.p, lvl) + (long)scene * n;
-  const float* __restrict__ pr = ppick4(reg.p, lvl) + (long)scene * C * n;
-  const float* __restrict__ pl = ppick4(locs.p, lvl);
-  const unsigned char* __restrict__ pm = have_masks ? ppick4(masks.p, lvl) + (long)scene * n : nullptr;
-  unsigned* __restrict__ kk = keys + ppick4(G.p0, lvl) + (long)scene * n;
+  const int n = pick4(G.n, lvl), top = pick4(G.top, lvl), off = pick4(G.off, lvl);
+  const float* __restrict__ pc = pick4(cls.p, lvl) + (long)scene * n;
+  const float* __restrict__ pt = pick4(ctr.p, lvl) + (long)scene * n;
+  const float* __restrict__ pr = pick4(reg.p, lvl) + (long)scene * C * n;
+  const float* __restrict__ pl = pick4(locs.p, lvl);
+  const unsigned char* __restrict__ pm = have_masks ? pick4(masks.p, lvl) + (long)scene * n : nullptr;
+  unsigned* __restrict__ kk = keys + pick4(G.p0, lvl) + (long)scene * n;
 
   // pass 0: keys, the candidate count, the histogram of the top 11 bits
-  hist[t] = 0; hist[t + SEL_T] = 0;
-  __syncthreads();
+  hist_clear(hist);
   int mine = 0;
   for (int q = t; q < n; q += SEL_T) {
-    const float p = post_sigmoid(pc[q]);
+    const float p = sigmoid_stable(pc[q]);
     const bool cand = (!pm || pm[q] != 0) && p > thr;
     unsigned key = 0u;
     if (cand) {
-      key = __float_as_uint(p * post_sigmoid(pt[q])) + 1u;
+      key = __float_as_uint(p * sigmoid_stable(pt[q])) + 1u;
       atomicAdd(&hist[key >> 21], 1);
       ++mine;
     }
@@ -89,37 +81,9 @@ __global__ __launch_bounds__(SEL_T) void fcos_post_select_kernel(PostGeom G, PPt
   }
   int ncand;
   block_scan_excl(mine, ncand, wsum);      // its barriers also complete hist
-  unsigned K = 0u;                         // keep key > K, and the first need_eq of key == K
-  int need_eq = 0;
+  RadixCut cut{0u, 0};                     // keep key > K, and the first need_eq of key == K
   const int k = min(top, ncand);
-  if (ncand > top) {                       // uniform: a cut is needed
-    radix_pick(hist, k, wsum, sh);
-    const unsigned d0 = (unsigned)sh[0];
-    int r = sh[1];
-    __syncthreads();
-    hist[t] = 0; hist[t + SEL_T] = 0;
-    __syncthreads();
-    for (int q = t; q < n; q += SEL_T) {
-      const unsigned key = kk[q];
-      if ((key >> 21) == d0) atomicAdd(&hist[(key >> 10) & 2047u], 1);
-    }
-    __syncthreads();
-    radix_pick(hist, r, wsum, sh);
-    const unsigned d01 = (d0 << 11) | (unsigned)sh[0];
-    r = sh[1];
-    __syncthreads();
-    hist[t] = 0; hist[t + SEL_T] = 0;
-    __syncthreads();
-    for (int q = t; q < n; q += SEL_T) {
-      const unsigned key = kk[q];
-      if ((key >> 10) == d01) atomicAdd(&hist[1024 + (key & 1023u)], 1);      // the upper half of the bins, so that radix_pick's scan order holds
-    }
-    __syncthreads();
-    radix_pick(hist, r, wsum, sh);
-    K = (d01 << 10) | (unsigned)(sh[0] - 1024);
-    need_eq = sh[1];
-    __syncthreads();
-  }
+  if (ncand > top) cut = radix_select_rest(hist, wsum, sh, k, n, [&](int q, unsigned& key) { key = kk[q]; return true; });      // uniform: a cut is needed
 
   // ordered compaction with decode, clip, size filter and sqrt
   int run_eq = 0, run_sel = 0, emitted = 0;
@@ -127,17 +91,8 @@ __global__ __launch_bounds__(SEL_T) void fcos_post_select_kernel(PostGeom G, PPt
   for (int base = 0; base < n && run_sel < k; base += SEL_T) {       // uniform
     const int q = base + t;
     const unsigned key = q < n ? kk[q] : 0u;
-    bool sel = key > K;
-    if (need_eq > 0) {                     // uniform
-      const bool eq = key == K;
-      int tot;
-      const int rank = run_eq + block_scan_excl(eq ? 1 : 0, tot, wsum);
-      run_eq += tot;
-      sel = sel || (eq && rank < need_eq);
-    }
-    int tot;
-    const int pos = run_sel + block_scan_excl(sel ? 1 : 0, tot, wsum);
-    run_sel += tot;
+    int pos;
+    const bool sel = compact_step(key > cut.K, key == cut.K, cut.need_eq > 0, cut.need_eq, run_eq, run_sel, wsum, pos);
     if (sel && pos < top) {                // pos < k <= top for every input whose keys are ordinary numbers
       const float X = pl[(long)q * 3], Y = pl[(long)q * 3 + 1], Z = pl[(long)q * 3 + 2];
       float r[8], o[7];
@@ -184,17 +139,6 @@ __device__ __forceinline__ int scene_count(const PostGeom& G, const int* __restr
   for (int k = 0; k < 4; ++k) nb += k < G.L ? pre_counts[k * G.N + scene] : 0;
   return min(nb, G.cap);
 }
-template <bool AABB>
-__device__ __forceinline__ void stage_row(const float* __restrict__ row, BoxTile& dst) {
-  if (AABB) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) dst.v[k] = row[k];
-    dst.v[6] = dst.v[7] = 0.f;
-  } else {
-    const Obb o = obb_load(row);
-    dst.v[0] = o.x; dst.v[1] = o.y; dst.v[2] = o.z; dst.v[3] = o.w; dst.v[4] = o.l; dst.v[5] = o.h; dst.v[6] = o.cs; dst.v[7] = o.sn;
-  }
-}
 
 template <bool AABB>
 __global__ __launch_bounds__(256) void fcos_post_nms_mask_kernel(PostGeom G, const float* __restrict__ pre_boxes, const long* __restrict__ order, const int* __restrict__ pre_counts,
@@ -203,35 +147,19 @@ __global__ __launch_bounds__(256) void fcos_post_nms_mask_kernel(PostGeom G, con
   __shared__ BoxTile rows[64], cols[64];
   const int t = threadIdx.x, scene = blockIdx.y, capw = (G.cap + 63) >> 6;
   const int nb = scene_count(G, pre_counts, scene);
-  int by = 0, j = blockIdx.x;
-  while (j >= capw - by) { j -= capw - by; ++by; }    // uniform, at most capw <= 256 steps
-  j += by;
+  int by, j;
+  tri_block(blockIdx.x, capw, by, j);
   const int r0 = by * 64, c0 = j * 64;
   if (c0 >= nb) return;                                // uniform; r0 <= c0
   const long sb = (long)scene * G.cap;
   if (t < 128) {
     const int i = (t < 64 ? c0 : r0 - 64) + t;
     BoxTile& dst = t < 64 ? cols[t] : rows[t - 64];
-    if (i < nb) {
-      const long src = min(max(order[sb + i], 0L), (long)G.cap - 1);
-      stage_row<AABB>(pre_boxes + (sb + src) * ROW + 1, dst);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) dst.v[k] = 0.f;
-    }
+    if (i < nb) stage_box<AABB>(pre_boxes + sb * ROW + 1, min(max(order[sb + i], 0L), (long)G.cap - 1), (long)G.cap, dst, ROW);      // + 1: past the level column
+    else zero_box(dst);
   }
   __syncthreads();
-  const int k = t & 63, col = c0 + k;
-  const BoxTile bc = cols[k];
-#pragma unroll 1
-  for (int r = t >> 6; r < 64; r += 4) {
-    const int row = r0 + r;
-    if (row >= nb) break;                              // uniform over the wave
-    bool hit = false;
-    if (col > row && col < nb) hit = tile_iou<AABB>(rows[r], bc) > thr;
-    const unsigned long long word = __ballot(hit);
-    if (k == 0) mask[(sb + row) * capw + j] = word;
-  }
+  nms_mask_tile<AABB>(rows, cols, r0, c0, j, nb, thr, mask + sb * capw, capw, nullptr, nullptr);
 }
 
 // one workgroup per scene; cap <= 16384 (256 words of removed-set)
@@ -241,34 +169,12 @@ __global__ __launch_bounds__(256) void fcos_post_nms_scan_kernel(PostGeom G, int
   __shared__ unsigned long long removed[256], diag[64];
   __shared__ int extra;
   const int t = threadIdx.x, scene = blockIdx.x, capw = (G.cap + 63) >> 6;
-  const int N = scene_count(G, pre_counts, scene), nw = (N + 63) >> 6;
+  const int N = scene_count(G, pre_counts, scene);
   const long sb = (long)scene * G.cap;
   const unsigned long long* __restrict__ m0 = mask + sb * capw;
   int* kp = keep + sb;
-  removed[t] = 0ull;
   if (t == 0) extra = 0;
-  int cnt = 0;                             // the same in every thread
-  for (int c = 0; c < nw; ++c) {
-    __syncthreads();                       // removed[] of the previous block is complete; diag[] is free
-    if (t < 64) diag[t] = c * 64 + t < N ? m0[(long)(c * 64 + t) * capw + c] : 0ull;
-    __syncthreads();
-    unsigned long long r = removed[c];
-    const int left = N - c * 64;
-    if (left < 64) r |= ~0ull << left;     // positions past N count as removed
-    for (int k = 0; k < 64; ++k)           // row k's word only has bits above k, so bit k of r is final when it is read
-      if (!((r >> k) & 1ull)) r |= diag[k];
-    const unsigned long long kept = ~r;
-    if (t < 64 && ((kept >> t) & 1ull)) kp[cnt + __popcll(kept & ((1ull << t) - 1ull))] = c * 64 + t;
-    cnt += __popcll(kept);
-    const int nrem = nw - c - 1;           // words after the diagonal one
-    for (int q = t; q < 64 * nrem; q += 256) {
-      const int k = q / nrem, w = c + 1 + q % nrem;
-      if ((kept >> k) & 1ull) {
-        const unsigned long long m = m0[(long)(c * 64 + k) * capw + w];
-        if (m) atomicOr(&removed[w], m);
-      }
-    }
-  }
+  const int cnt = nms_greedy_walk(m0, capw, N, kp, removed, diag);      // the same in every thread
   __syncthreads();                         // kp[] is complete and visible to the workgroup
   // post-NMS cut: kept boxes are in decreasing score, so those with score >= the post_top_n-th are a prefix
   int m = cnt;
@@ -313,16 +219,6 @@ int make_post_geom(int nlevels, const int* level_n, int N, int pre_top_n, PostGe
   G.cap = (int)cap;
   return 0;
 }
-template <typename T> PPtr4<T> post_ptrs(int nlevels, T* const* tab) {
-  PPtr4<T> r;
-  for (int k = 0; k < 4; ++k) r.p[k] = tab ? tab[k < nlevels ? k : nlevels - 1] : nullptr;
-  return r;
-}
-template <typename T> bool post_all_set(int nlevels, T* const* tab) {
-  if (!tab) return false;
-  for (int k = 0; k < nlevels; ++k) if (!tab[k]) return false;
-  return true;
-}
 
 }  // namespace
 
@@ -336,11 +232,11 @@ int k_fcos_post_select(int nlevels, const int* level_n, int N, int ncols, int pr
                        float* pre_scores, int* pre_counts, hipStream_t st) {
   PostGeom G;
   if (make_post_geom(nlevels, level_n, N, pre_top_n, G) || (ncols != 6 && ncols != 8)) return -4;
-  if (!post_all_set(nlevels, cls) || !post_all_set(nlevels, reg) || !post_all_set(nlevels, ctr) || !post_all_set(nlevels, locs)) return -4;
-  if ((masks && !post_all_set(nlevels, masks)) || (ncols == 6 && !sizes)) return -4;
-  const PPtr4<const float> Cl = post_ptrs<const float>(nlevels, cls), R = post_ptrs<const float>(nlevels, reg), Ct = post_ptrs<const float>(nlevels, ctr),
-                           Lo = post_ptrs<const float>(nlevels, locs);
-  const PPtr4<const unsigned char> M = post_ptrs<const unsigned char>(nlevels, masks);
+  if (!all_set(nlevels, cls) || !all_set(nlevels, reg) || !all_set(nlevels, ctr) || !all_set(nlevels, locs)) return -4;
+  if ((masks && !all_set(nlevels, masks)) || (ncols == 6 && !sizes)) return -4;
+  const Ptr4<const float> Cl = make_ptrs<const float>(nlevels, cls), R = make_ptrs<const float>(nlevels, reg), Ct = make_ptrs<const float>(nlevels, ctr),
+                          Lo = make_ptrs<const float>(nlevels, locs);
+  const Ptr4<const unsigned char> M = make_ptrs<const unsigned char>(nlevels, masks);
   const dim3 grid((unsigned)(nlevels * N));
   if (ncols == 8) hipLaunchKernelGGL(fcos_post_select_kernel<true>, grid, dim3(SEL_T), 0, st, G, Cl, R, Ct, Lo, M, masks ? 1 : 0, sizes, pre_thresh, min_size, keys, pre_boxes, pre_scores, pre_counts);
   else hipLaunchKernelGGL(fcos_post_select_kernel<false>, grid, dim3(SEL_T), 0, st, G, Cl, R, Ct, Lo, M, masks ? 1 : 0, sizes, pre_thresh, min_size, keys, pre_boxes, pre_scores, pre_counts);

@@ -288,22 +288,23 @@ __device__ __forceinline__ void obb_pair_grad(const Obb& A, const Obb& B, float 
   }
 }
 
-// ---- a box staged in LDS for the all-pairs and NMS kernels (rotated_iou.hip, fcos_post.hip), its sin / cos taken once ---------------------------
+// ---- a box staged in LDS for the all-pairs and NMS kernels (rotated_iou.hip, nms_bits.hpp), its sin / cos taken once ------------------------------
 struct BoxTile { float v[8]; };   // 7 columns: x y z w l h cos sin; 6 columns: x1 y1 z1 x2 y2 z2
+__device__ __forceinline__ void zero_box(BoxTile& dst) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) dst.v[k] = 0.f;
+}
+// row i of src (rows of `stride` floats, the box in the first 6 | 7), zeros for i >= n
 template <bool AABB>
-__device__ __forceinline__ void stage_box(const float* __restrict__ src, long i, long n, BoxTile& dst) {
-  if (i < n) {
-    if (AABB) {
+__device__ __forceinline__ void stage_box(const float* __restrict__ src, long i, long n, BoxTile& dst, int stride = AABB ? 6 : 7) {
+  if (i >= n) return zero_box(dst);
+  if (AABB) {
 #pragma unroll
-      for (int k = 0; k < 6; ++k) dst.v[k] = src[i * 6 + k];
-      dst.v[6] = dst.v[7] = 0.f;
-    } else {
-      const Obb o = obb_load(src + i * 7);
-      dst.v[0] = o.x; dst.v[1] = o.y; dst.v[2] = o.z; dst.v[3] = o.w; dst.v[4] = o.l; dst.v[5] = o.h; dst.v[6] = o.cs; dst.v[7] = o.sn;
-    }
+    for (int k = 0; k < 6; ++k) dst.v[k] = src[i * stride + k];
+    dst.v[6] = dst.v[7] = 0.f;
   } else {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) dst.v[k] = 0.f;
+    const Obb o = obb_load(src + i * stride);
+    dst.v[0] = o.x; dst.v[1] = o.y; dst.v[2] = o.z; dst.v[3] = o.w; dst.v[4] = o.l; dst.v[5] = o.h; dst.v[6] = o.cs; dst.v[7] = o.sn;
   }
 }
 template <bool AABB>

@@ -43,15 +43,12 @@
 // reproduced; they move results by about 1e-8 relative.  For any input, non-finite values and non-positive sizes included, every kernel
 // writes only its own outputs; the values for such input are unspecified.
 //
-// NMS.  Boxes arrive ordered by descending score.  mask[i][j] (64-bit words, ceil(N/64) per row) has bit k set iff
-// iou(i, 64 j + k) > threshold, 64 j + k > i (and category equal, when categories are given: an offset-coordinates trick is not valid for
-// rotated boxes).  Words with j < floor(i / 64) (strictly below the diagonal block) are all zero by definition, are never read by the scan and
-// are NOT written: only the upper triangle of 64 x 64 blocks is launched.  One wave computes one word: lane k takes column 64 j + k and the ballot is the word.  The scan is one workgroup; per
-// block of 64 rows it resolves the block's own dependencies from the 64 diagonal words, then ORs the rows of the kept boxes into the
-// removed-set in LDS.  Kept positions and their count are written to device memory; the host is not involved.
+// NMS.  Boxes arrive ordered by descending score.  The bit matrix (64-bit words, ceil(N/64) per row, upper triangle only) and the greedy walk are those
+// of nms_bits.hpp; here a pair also needs equal categories when categories are given (an offset-coordinates trick is not valid for rotated boxes).
+// Kept positions and their count are written to device memory; the host is not involved.
 #include "common.hpp"
 #include "kernels.hpp"
-#include "obb_geom.hpp"
+#include "nms_bits.hpp"
 
 namespace {
 
@@ -126,57 +123,20 @@ __global__ __launch_bounds__(256) void obb_nms_mask_kernel(const float* __restri
   __shared__ BoxTile rows[64], cols[64];
   __shared__ int rcat[64];
   const int t = threadIdx.x, nw = (N + 63) >> 6;
-  // the grid is the upper triangle of the nw x nw blocks, row block by row block: block row `by` has the words j = by .. nw-1
-  int by = 0, j = blockIdx.x;
-  while (j >= nw - by) { j -= nw - by; ++by; }      // uniform, at most nw <= 256 steps
-  j += by;
-  const long r0 = (long)by * 64, c0 = (long)j * 64;
+  int by, j;
+  tri_block(blockIdx.x, nw, by, j);
+  const int r0 = by * 64, c0 = j * 64;
   if (t < 64) stage_box<AABB>(boxes, c0 + t, N, cols[t]);
   else if (t < 128) { stage_box<AABB>(boxes, r0 + (t - 64), N, rows[t - 64]); rcat[t - 64] = (cat && r0 + (t - 64) < N) ? cat[r0 + (t - 64)] : 0; }
   __syncthreads();
-  const int k = t & 63;
-  const long col = c0 + k;
-  const BoxTile bc = cols[k];
-  const int ccat = (cat && col < N) ? cat[col] : 0;
-#pragma unroll 1
-  for (int r = t >> 6; r < 64; r += 4) {
-    const long row = r0 + r;
-    if (row >= N) break;                   // uniform over the wave
-    bool hit = false;
-    if (col > row && col < N && ccat == rcat[r]) hit = tile_iou<AABB>(rows[r], bc) > thr;
-    const unsigned long long word = __ballot(hit);
-    if (k == 0) mask[row * nw + j] = word;
-  }
+  nms_mask_tile<AABB>(rows, cols, r0, c0, j, N, thr, mask, nw, rcat, cat);       // no early exit: every launched word is written
 }
 
 // one workgroup; N <= 16384 (256 words of removed-set)
 __global__ __launch_bounds__(256) void obb_nms_scan_kernel(const unsigned long long* __restrict__ mask, int N, int* __restrict__ keep, int* __restrict__ count) {
   __shared__ unsigned long long removed[256], diag[64];
-  const int t = threadIdx.x, nw = (N + 63) >> 6;
-  removed[t] = 0ull;
-  int cnt = 0;                             // the same in every thread
-  for (int c = 0; c < nw; ++c) {
-    __syncthreads();                       // removed[] of the previous block is complete; diag[] is free
-    if (t < 64) diag[t] = c * 64 + t < N ? mask[(long)(c * 64 + t) * nw + c] : 0ull;
-    __syncthreads();
-    unsigned long long r = removed[c];
-    const int left = N - c * 64;
-    if (left < 64) r |= ~0ull << left;     // positions past N count as removed
-    for (int k = 0; k < 64; ++k)           // row k's word only has bits above k, so bit k of r is final when it is read
-      if (!((r >> k) & 1ull)) r |= diag[k];
-    const unsigned long long kept = ~r;
-    if (t < 64 && ((kept >> t) & 1ull)) keep[cnt + __popcll(kept & ((1ull << t) - 1ull))] = c * 64 + t;
-    cnt += __popcll(kept);
-    const int nrem = nw - c - 1;           // words after the diagonal one
-    for (int q = t; q < 64 * nrem; q += 256) {
-      const int k = q / nrem, w = c + 1 + q % nrem;
-      if ((kept >> k) & 1ull) {
-        const unsigned long long m = mask[(long)(c * 64 + k) * nw + w];
-        if (m) atomicOr(&removed[w], m);
-      }
-    }
-  }
-  if (t == 0) *count = cnt;
+  const int cnt = nms_greedy_walk(mask, (N + 63) >> 6, N, keep, removed, diag);
+  if (threadIdx.x == 0) *count = cnt;
 }
 
 template <int MODE>

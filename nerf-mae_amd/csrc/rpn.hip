@@ -27,8 +27,8 @@
 //           targets 0;  else targets = encode(box max(m, 0), anchor).
 // Sampling.  One workgroup of 1024 lanes per scene.  Candidates: label >= 1 (positive) and label == 0 (negative).  num_pos = min(#pos, want_pos),
 // num_neg = min(#neg, batch - num_pos).  Every candidate has the key hash(seed, counter, scene, index), recomputed wherever it is needed; the num_*
-// smallest keys of a class are taken, found by a radix select over three LDS histograms (11 + 11 + 10 bits) of the complemented key; equal keys
-// at the cut go to the lower anchor index.  flags: 0 unsampled, 1 positive, 2 negative.  A second launch of one lane adds 1 to the counter.
+// smallest keys of a class are taken, found by the radix select of select_scan.hpp over the complemented key; equal keys at the cut go to the lower
+// anchor index.  flags: 0 unsampled, 1 positive, 2 negative.  A second launch of one lane adds 1 to the counter.
 // Loss.  One lane per head element (b, a, loc), so the dense gradients are written coalesced.  s = number of flags != 0 over all scenes;
 //   objectness = sum over flags != 0 of bce_with_logits(x, flag == 1) / s;  box_reg = sum over flags == 1 and c of smooth_l1(pred - target; 1/9) / s;
 //   both 0 when s == 0 (the reference gives NaN there).  Forward: per-workgroup partial sums, then a fixed-order pass of one workgroup.  Backward: one
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void rpn_gtmax_kernel(RpnGeom G, RpnBase B, Rp
   __shared__ float sh_base[RPN_MAX_A * 3];
   const RAt q = rpn_where(G);
   const int t = threadIdx.x;
-  rpn_stage_base(B, q.lvl, rpick4(G.A, q.lvl), sh_base);
+  rpn_stage_base(B, q.lvl, pick4(G.A, q.lvl), sh_base);
   __syncthreads();
   bool valid;
   const Box6 a = rpn_anchor(G, sh_base, ori, q, valid);
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void rpn_assign_kernel(RpnGeom G, RpnBase B, R
   __shared__ float sh_base[RPN_MAX_A * 3];
   const RAt q = rpn_where(G);
   const int t = threadIdx.x;
-  rpn_stage_base(B, q.lvl, rpick4(G.A, q.lvl), sh_base);
+  rpn_stage_base(B, q.lvl, pick4(G.A, q.lvl), sh_base);
   __syncthreads();
   bool valid;
   const Box6 a = rpn_anchor(G, sh_base, ori, q, valid);
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void rpn_assign_kernel(RpnGeom G, RpnBase B, R
     }
   }
   if (!q.active) return;
-  const long p = (long)q.scene * G.ntot + rpick4(G.off, q.lvl) + q.i;
+  const long p = (long)q.scene * G.ntot + pick4(G.off, q.lvl) + q.i;
   float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int m = -1;
   float lab = valid ? 0.f : -1.f;
@@ -214,8 +214,8 @@ __global__ __launch_bounds__(SEL_T) void rpn_sample_kernel(const float* __restri
   const unsigned long long stream = rpn_stream(rng[0], rng[1], scene);
 
   // pass 0: the candidates of both classes and the histograms of the top 11 bits
-  hist[0][t] = 0; hist[0][t + SEL_T] = 0; hist[1][t] = 0; hist[1][t + SEL_T] = 0;
-  __syncthreads();
+  hist[1][t] = 0; hist[1][t + SEL_T] = 0;
+  hist_clear(hist[0]);
   int mine[2] = {0, 0};
   for (int q = t; q < n; q += SEL_T) {
     const int c = rpn_class(lab[q]);
@@ -239,36 +239,13 @@ __global__ __launch_bounds__(SEL_T) void rpn_sample_kernel(const float* __restri
   for (int c = 0; c < 2; ++c) {
     mode[c] = num[c] == 0 ? SEL_NONE : (num[c] >= have[c] ? SEL_ALL : SEL_CUT);
     if (mode[c] != SEL_CUT) continue;                // uniform
-    int* h = hist[c];
-    radix_pick(h, num[c], wsum, sh);
-    const unsigned d0 = (unsigned)sh[0];
-    int r = sh[1];
-    __syncthreads();
-    h[t] = 0; h[t + SEL_T] = 0;
-    __syncthreads();
-    for (int q = t; q < n; q += SEL_T) {
-      if (rpn_class(lab[q]) != c) continue;
-      const unsigned key = rpn_key(stream, q);
-      if ((key >> 21) == d0) atomicAdd(&h[(key >> 10) & 2047u], 1);
-    }
-    __syncthreads();
-    radix_pick(h, r, wsum, sh);
-    const unsigned d01 = (d0 << 11) | (unsigned)sh[0];
-    r = sh[1];
-    __syncthreads();
-    h[t] = 0; h[t + SEL_T] = 0;
-    __syncthreads();
-    for (int q = t; q < n; q += SEL_T) {
-      if (rpn_class(lab[q]) != c) continue;
-      const unsigned key = rpn_key(stream, q);
-      if ((key >> 10) == d01) atomicAdd(&h[1024 + (key & 1023u)], 1);      // the upper half of the bins, so that radix_pick's scan order holds
-    }
-    __syncthreads();
-    radix_pick(h, r, wsum, sh);
-    K[c] = (d01 << 10) | (unsigned)(sh[0] - 1024);
-    need_eq[c] = sh[1];
-    eq_have[c] = h[sh[0]];
-    __syncthreads();
+    const RadixCut cut = radix_select_rest(hist[c], wsum, sh, num[c], n, [&](int q, unsigned& key) {
+      if (rpn_class(lab[q]) != c) return false;
+      key = rpn_key(stream, q);
+      return true;
+    });
+    K[c] = cut.K; need_eq[c] = cut.need_eq;
+    eq_have[c] = hist[c][1024 + (cut.K & 1023u)];     // the last histogram is left in place
   }
 
   // flags; only a tie at a cut that is not taken whole needs the order of the indices
@@ -282,22 +259,8 @@ __global__ __launch_bounds__(SEL_T) void rpn_sample_kernel(const float* __restri
     const unsigned Kc = c == 0 ? K[0] : K[1];
     const bool eq = md == SEL_CUT && key == Kc;
     bool sel = md == SEL_ALL || (md == SEL_CUT && key > Kc);
-    if (ordered0) {                                  // uniform
-      int tot;
-      const int rank = run0 + block_scan_excl(eq && c == 0 ? 1 : 0, tot, wsum);
-      run0 += tot;
-      sel = sel || (eq && c == 0 && rank < need_eq[0]);
-    } else {
-      sel = sel || (eq && c == 0);
-    }
-    if (ordered1) {                                  // uniform
-      int tot;
-      const int rank = run1 + block_scan_excl(eq && c == 1 ? 1 : 0, tot, wsum);
-      run1 += tot;
-      sel = sel || (eq && c == 1 && rank < need_eq[1]);
-    } else {
-      sel = sel || (eq && c == 1);
-    }
+    sel = ordered0 ? tie_take(sel, eq && c == 0, need_eq[0], run0, wsum) : sel || (eq && c == 0);       // uniform
+    sel = ordered1 ? tie_take(sel, eq && c == 1, need_eq[1], run1, wsum) : sel || (eq && c == 1);       // uniform
     if (q < n) fl[q] = sel ? (unsigned char)(c == 0 ? 1 : 2) : (unsigned char)0;
   }
   if (t == 0) { counts[scene * 2] = num[0]; counts[scene * 2 + 1] = num[1]; }
@@ -314,10 +277,10 @@ __device__ __forceinline__ RHead rpn_head_where(const RpnGeom& G) {
   const RAt q = rpn_where(G);
   RHead r;
   r.lvl = q.lvl; r.scene = q.scene; r.j = q.i; r.active = q.active;
-  r.nloc = rpick4(G.nloc, q.lvl); r.A = rpick4(G.A, q.lvl);
+  r.nloc = pick4(G.nloc, q.lvl); r.A = pick4(G.A, q.lvl);
   const int j = q.active ? q.i : 0;
   r.a = j / r.nloc; r.loc = j - r.a * r.nloc;
-  r.p = (long)q.scene * G.ntot + rpick4(G.off, q.lvl) + (long)r.loc * r.A + r.a;
+  r.p = (long)q.scene * G.ntot + pick4(G.off, q.lvl) + (long)r.loc * r.A + r.a;
   return r;
 }
 constexpr float RPN_BETA = 1.f / 9.f;
@@ -339,17 +302,17 @@ __device__ __forceinline__ void block_sum3(float a, float b, float c, float* __r
 }
 
 template <int C>
-__global__ __launch_bounds__(256) void rpn_loss_fwd_kernel(RpnGeom G, RPtr4<const float> obj, RPtr4<const float> reg, const unsigned char* __restrict__ flags,
+__global__ __launch_bounds__(256) void rpn_loss_fwd_kernel(RpnGeom G, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
                                                            const float* __restrict__ targets, float* __restrict__ partials) {
   const RHead w = rpn_head_where(G);
   float vo = 0.f, vr = 0.f, cnt = 0.f;
   const int f = w.active ? flags[w.p] : 0;
   if (f != 0) {
-    const float x = rpick4(obj.p, w.lvl)[(long)w.scene * w.A * w.nloc + w.j];
+    const float x = pick4(obj.p, w.lvl)[(long)w.scene * w.A * w.nloc + w.j];
     vo = fmaxf(x, 0.f) - (f == 1 ? x : 0.f) + log1pf(expf(-fabsf(x)));
     cnt = 1.f;
     if (f == 1) {
-      const float* __restrict__ rp = rpick4(reg.p, w.lvl) + ((long)w.scene * w.A + w.a) * C * w.nloc + w.loc;
+      const float* __restrict__ rp = pick4(reg.p, w.lvl) + ((long)w.scene * w.A + w.a) * C * w.nloc + w.loc;
 #pragma unroll
       for (int k = 0; k < C; ++k) vr += rpn_sl1(rp[(long)k * w.nloc] - targets[w.p * C + k]);
     }
@@ -377,9 +340,9 @@ __global__ __launch_bounds__(256) void rpn_loss_final_kernel(const float* __rest
 }
 
 template <int C>
-__global__ __launch_bounds__(256) void rpn_loss_bwd_kernel(RpnGeom G, RPtr4<const float> obj, RPtr4<const float> reg, const unsigned char* __restrict__ flags,
+__global__ __launch_bounds__(256) void rpn_loss_bwd_kernel(RpnGeom G, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
                                                            const float* __restrict__ targets, const float* __restrict__ scalars, const float* __restrict__ g_obj,
-                                                           const float* __restrict__ g_reg, RPtr4<float> dobj, RPtr4<float> dreg) {
+                                                           const float* __restrict__ g_reg, Ptr4<float> dobj, Ptr4<float> dreg) {
   const RHead w = rpn_head_where(G);
   if (!w.active) return;
   const long at = (long)w.scene * w.A * w.nloc + w.j, rat = ((long)w.scene * w.A + w.a) * C * w.nloc + w.loc;
@@ -389,18 +352,17 @@ __global__ __launch_bounds__(256) void rpn_loss_bwd_kernel(RpnGeom G, RPtr4<cons
 #pragma unroll
   for (int k = 0; k < C; ++k) gr[k] = 0.f;
   if (f != 0 && cnt > 0.f) {
-    const float x = rpick4(obj.p, w.lvl)[at];
-    const float e = expf(-fabsf(x)), r = 1.f / (1.f + e), sg = x >= 0.f ? r : e * r;
-    go = (sg - (f == 1 ? 1.f : 0.f)) * (g_obj ? g_obj[0] : 0.f) / cnt;
+    const float x = pick4(obj.p, w.lvl)[at];
+    go = (sigmoid_stable(x) - (f == 1 ? 1.f : 0.f)) * (g_obj ? g_obj[0] : 0.f) / cnt;
     if (f == 1) {
-      const float* __restrict__ rp = rpick4(reg.p, w.lvl) + rat;
+      const float* __restrict__ rp = pick4(reg.p, w.lvl) + rat;
       const float sc = (g_reg ? g_reg[0] : 0.f) / cnt;
 #pragma unroll
       for (int k = 0; k < C; ++k) gr[k] = rpn_sl1_grad(rp[(long)k * w.nloc] - targets[w.p * C + k]) * sc;
     }
   }
-  rpick4(dobj.p, w.lvl)[at] = go;
-  float* __restrict__ dp = rpick4(dreg.p, w.lvl) + rat;
+  pick4(dobj.p, w.lvl)[at] = go;
+  float* __restrict__ dp = pick4(dreg.p, w.lvl) + rat;
 #pragma unroll
   for (int k = 0; k < C; ++k) dp[(long)k * w.nloc] = gr[k];
 }
@@ -448,7 +410,7 @@ int k_rpn_loss_fwd(int nlevels, const int* dims, int N, int ncols, const float* 
                    float* scalars, hipStream_t st) {
   RpnGeom G;
   if (make_geom(nlevels, dims, N, G) || (ncols != 6 && ncols != 8) || !all_set(nlevels, obj) || !all_set(nlevels, reg)) return -4;
-  const RPtr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
+  const Ptr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
   if (ncols == 8) hipLaunchKernelGGL(rpn_loss_fwd_kernel<8>, dim3(G.nblocks), dim3(256), 0, st, G, O, R, flags, targets, partials);
   else hipLaunchKernelGGL(rpn_loss_fwd_kernel<6>, dim3(G.nblocks), dim3(256), 0, st, G, O, R, flags, targets, partials);
   NMH_CHECK_LAUNCH();
@@ -461,8 +423,8 @@ int k_rpn_loss_bwd(int nlevels, const int* dims, int N, int ncols, const float* 
                    const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj, float* const* dreg, hipStream_t st) {
   RpnGeom G;
   if (make_geom(nlevels, dims, N, G) || (ncols != 6 && ncols != 8) || !all_set(nlevels, obj) || !all_set(nlevels, reg) || !all_set(nlevels, dobj) || !all_set(nlevels, dreg)) return -4;
-  const RPtr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
-  const RPtr4<float> DO = make_ptrs<float>(nlevels, dobj), DR = make_ptrs<float>(nlevels, dreg);
+  const Ptr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
+  const Ptr4<float> DO = make_ptrs<float>(nlevels, dobj), DR = make_ptrs<float>(nlevels, dreg);
   if (ncols == 8) hipLaunchKernelGGL(rpn_loss_bwd_kernel<8>, dim3(G.nblocks), dim3(256), 0, st, G, O, R, flags, targets, scalars, g_obj, g_reg, DO, DR);
   else hipLaunchKernelGGL(rpn_loss_bwd_kernel<6>, dim3(G.nblocks), dim3(256), 0, st, G, O, R, flags, targets, scalars, g_obj, g_reg, DO, DR);
   NMH_CHECK_LAUNCH();

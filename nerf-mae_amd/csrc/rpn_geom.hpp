@@ -1,8 +1,9 @@
 // Level geometry of the RPN kernels (rpn.hip, rpn_post.hip): the by-value kernel arguments, the workgroup -> (level, scene, anchor) map, the anchor derived
-// from its index with the padding test, and the host-side builders of the arguments.  Layouts and semantics: the header of rpn.hip.
+// from its index with the padding test, and the host-side builders of the arguments (the per-level pointer plumbing: levels4.hpp).  Layouts and semantics: the header of rpn.hip.
 #pragma once
 #include "common.hpp"
 #include "kernels.hpp"
+#include "levels4.hpp"
 
 namespace {
 
@@ -16,8 +17,6 @@ struct RpnGeom {             // kernel argument, by value
   int ntot, nblocks;
 };
 struct RpnBase { float h[4][RPN_MAX_A][3]; };       // kernel argument, by value: half extents
-template <typename T> struct RPtr4 { T* p[4]; };
-template <typename T> __device__ __forceinline__ T rpick4(const T (&a)[4], int i) { return i == 0 ? a[0] : (i == 1 ? a[1] : (i == 2 ? a[2] : a[3])); }
 
 struct RAt { int lvl, scene, i; bool active; };
 __device__ __forceinline__ RAt rpn_where(const RpnGeom& G) {
@@ -26,11 +25,11 @@ __device__ __forceinline__ RAt rpn_where(const RpnGeom& G) {
   q.lvl = 0;
 #pragma unroll
   for (int k = 1; k < 4; ++k) if (k < G.L && b >= G.blk0[k]) q.lvl = k;
-  b -= rpick4(G.blk0, q.lvl);
-  const int bps = rpick4(G.bps, q.lvl);
+  b -= pick4(G.blk0, q.lvl);
+  const int bps = pick4(G.bps, q.lvl);
   q.scene = b / bps;
   q.i = (b - q.scene * bps) * 256 + (int)threadIdx.x;
-  q.active = q.i < rpick4(G.n, q.lvl);
+  q.active = q.i < pick4(G.n, q.lvl);
   return q;
 }
 
@@ -44,8 +43,8 @@ __device__ __forceinline__ void rpn_stage_base(const RpnBase& B, int lvl, int A,
 
 // anchor i of the level (anchor order) and whether it lies within the scene's original size
 __device__ __forceinline__ Box6 rpn_anchor(const RpnGeom& G, const float* __restrict__ sh_base, const int* __restrict__ ori, const RAt& q, bool& valid) {
-  const int A = rpick4(G.A, q.lvl), Dk = rpick4(G.D, q.lvl), Hk = rpick4(G.H, q.lvl);
-  const int sx = rpick4(G.sx, q.lvl), sy = rpick4(G.sy, q.lvl), sz = rpick4(G.sz, q.lvl);
+  const int A = pick4(G.A, q.lvl), Dk = pick4(G.D, q.lvl), Hk = pick4(G.H, q.lvl);
+  const int sx = pick4(G.sx, q.lvl), sy = pick4(G.sy, q.lvl), sz = pick4(G.sz, q.lvl);
   const int i = q.active ? q.i : 0;
   const int a = i % A, loc = i / A, d = loc % Dk, h = (loc / Dk) % Hk, w = loc / (Dk * Hk);
   const float cx = (float)(w * sx), cy = (float)(h * sy), cz = (float)(d * sz);
@@ -99,16 +98,6 @@ int make_base(int nlevels, const int* dims, const float* base, RpnBase& B) {
     }
   }
   return 0;
-}
-template <typename T> RPtr4<T> make_ptrs(int nlevels, T* const* tab) {
-  RPtr4<T> r;
-  for (int k = 0; k < 4; ++k) r.p[k] = tab[k < nlevels ? k : nlevels - 1];
-  return r;
-}
-template <typename T> bool all_set(int nlevels, T* const* tab) {
-  if (!tab) return false;
-  for (int k = 0; k < nlevels; ++k) if (!tab[k]) return false;
-  return true;
 }
 
 }  // namespace

@@ -27,21 +27,19 @@
 // sort of the [N][cap] keys is therefore level-major, within a level by descending logit with ties to the lower slot, the empty slots of a level last.
 //
 // Algorithm of the selection.  One workgroup of 1024 lanes per (level, scene), walking the level in memory order so that reads are coalesced.  No key array is
-// stored: every pass re-reads the logits (L2-resident) and re-forms the keys.  If n_k > t_k, a radix select finds the t_k-th largest key K from three LDS
-// histograms (11 + 11 + 10 bits, integer atomics: the sums do not depend on their order), each scanned from the top by a workgroup prefix sum
-// (select_scan.hpp).  The compaction walks chunks of 1024 in ascending offset; two workgroup prefix sums per chunk give every lane the number of keys == K
-// before it (the first t_k - #(key > K) of them are kept: the tie rule) and its slot.
+// stored: every pass re-reads the logits (L2-resident) and re-forms the keys.  If n_k > t_k, the radix select of select_scan.hpp finds the t_k-th largest key;
+// its ordered compaction walks chunks of 1024 in ascending offset and gives every kept anchor its slot, ties at the cut to the lower offset.
 //
 // NMS.  A box is suppressed iff its IoU with a kept box of the SAME level is greater than nms_thresh (pair geometry: obb_geom.hpp, 6- or 7-column form).
 // Pairs from different levels never reach the geometry: level k of scene b has its own bit matrix of t_k rows of ceil(t_k / 64) words over the level's
-// sorted boxes; only the upper triangles of 64 x 64 blocks are launched and a workgroup whose columns start beyond the level's count exits at once.  The scan is
-// one workgroup per scene that walks its levels one after the other (obb_nms_scan's walk on each), leaving per level the kept positions in descending key.
+// sorted boxes (nms_bits.hpp); only the upper triangles of 64 x 64 blocks are launched and a workgroup whose columns start beyond the level's count exits at once.  The scan is
+// one workgroup per scene that walks its levels one after the other (nms_greedy_walk on each), leaving per level the kept positions in descending key.
 // Epilogue: the global order is descending logit with ties to the lower slot; a survivor's rank is its rank in its own level plus, for every other level,
 // the number of that level's survivors before it, found by binary search in that level's descending keys (equal keys: the lower level first).  Survivors of
 // rank < post_nms_top_n are written to row rank: boxes, score, level, anchor index; rows past the count are zero.  No atomics on anything that is ordered.
 #include "common.hpp"
 #include "kernels.hpp"
-#include "obb_geom.hpp"
+#include "nms_bits.hpp"
 #include "select_scan.hpp"
 #include "rpn_geom.hpp"
 #include "rpn_decode.hpp"
@@ -56,10 +54,6 @@ struct RpnPostGeom {         // kernel argument, by value
   int mblocks;
 };
 
-__device__ __forceinline__ float rpn_sigmoid(float x) {
-  const float e = expf(-fabsf(x)), r = 1.f / (1.f + e);
-  return x >= 0.f ? r : e * r;
-}
 __device__ __forceinline__ unsigned rpn_order_bits(float x) {           // NaN reads as -inf
   const unsigned u = x != x ? 0xff800000u : __float_as_uint(x);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -69,10 +63,10 @@ __device__ __forceinline__ unsigned rpn_order_bits(float x) {           // NaN r
 struct RpnLim { int H, D, lx, ly, lz; bool on; };
 __device__ __forceinline__ RpnLim rpn_limits(const RpnGeom& G, const int* __restrict__ ori, int lvl, int scene) {
   RpnLim m;
-  m.H = rpick4(G.H, lvl); m.D = rpick4(G.D, lvl); m.on = ori != nullptr;
+  m.H = pick4(G.H, lvl); m.D = pick4(G.D, lvl); m.on = ori != nullptr;
   m.lx = m.ly = m.lz = 0;
   if (ori) {
-    const int sx = rpick4(G.sx, lvl), sy = rpick4(G.sy, lvl), sz = rpick4(G.sz, lvl);
+    const int sx = pick4(G.sx, lvl), sy = pick4(G.sy, lvl), sz = pick4(G.sz, lvl);
     m.lx = (ori[scene * 3] + sx - 1) / sx; m.ly = (ori[scene * 3 + 1] + sy - 1) / sy; m.lz = (ori[scene * 3 + 2] + sz - 1) / sz;
   }
   return m;
@@ -88,7 +82,7 @@ __device__ __forceinline__ unsigned rpn_key_at(const float* __restrict__ po, con
 }
 
 template <bool ORIENTED>
-__global__ __launch_bounds__(SEL_T) void rpn_post_select_kernel(RpnGeom G, RpnBase B, RpnPostGeom P, RPtr4<const float> obj, RPtr4<const float> reg, const int* __restrict__ ori,
+__global__ __launch_bounds__(SEL_T) void rpn_post_select_kernel(RpnGeom G, RpnBase B, RpnPostGeom P, Ptr4<const float> obj, Ptr4<const float> reg, const int* __restrict__ ori,
                                                                 float score_thresh, float min_size, long* __restrict__ pre_keys, float* __restrict__ pre_boxes,
                                                                 float* __restrict__ pre_scores, int* __restrict__ pre_index, int* __restrict__ pre_counts) {
   constexpr int C = ORIENTED ? 8 : 6, ROW = ORIENTED ? 7 : 6;
@@ -97,48 +91,15 @@ __global__ __launch_bounds__(SEL_T) void rpn_post_select_kernel(RpnGeom G, RpnBa
   __shared__ int sh[2];
   __shared__ float sh_base[RPN_MAX_A * 3];
   const int t = threadIdx.x, lvl = blockIdx.x / G.N, scene = blockIdx.x - lvl * G.N;
-  const int n = rpick4(G.n, lvl), nloc = rpick4(G.nloc, lvl), A = rpick4(G.A, lvl), top = rpick4(P.top, lvl), off = rpick4(P.off, lvl);
-  const float* __restrict__ po = rpick4(obj.p, lvl) + (long)scene * n;
-  const float* __restrict__ pr = rpick4(reg.p, lvl) + (long)scene * n * C;
+  const int n = pick4(G.n, lvl), nloc = pick4(G.nloc, lvl), A = pick4(G.A, lvl), top = pick4(P.top, lvl), off = pick4(P.off, lvl);
+  const float* __restrict__ po = pick4(obj.p, lvl) + (long)scene * n;
+  const float* __restrict__ pr = pick4(reg.p, lvl) + (long)scene * n * C;
   const RpnLim lim = rpn_limits(G, ori, lvl, scene);
   rpn_stage_base(B, lvl, A, sh_base);
 
-  unsigned K = 0u;                         // keep key > K, and the first need_eq of key == K; without a cut: every key >= 0
-  int need_eq = 0;
-  bool all = true;
-  if (n > top) {                           // uniform: a cut is needed
-    all = false;
-    hist[t] = 0; hist[t + SEL_T] = 0;
-    __syncthreads();
-    for (int q = t; q < n; q += SEL_T) atomicAdd(&hist[rpn_key_at(po, lim, nloc, q) >> 21], 1);
-    __syncthreads();
-    radix_pick(hist, top, wsum, sh);
-    const unsigned d0 = (unsigned)sh[0];
-    int r = sh[1];
-    __syncthreads();
-    hist[t] = 0; hist[t + SEL_T] = 0;
-    __syncthreads();
-    for (int q = t; q < n; q += SEL_T) {
-      const unsigned key = rpn_key_at(po, lim, nloc, q);
-      if ((key >> 21) == d0) atomicAdd(&hist[(key >> 10) & 2047u], 1);
-    }
-    __syncthreads();
-    radix_pick(hist, r, wsum, sh);
-    const unsigned d01 = (d0 << 11) | (unsigned)sh[0];
-    r = sh[1];
-    __syncthreads();
-    hist[t] = 0; hist[t + SEL_T] = 0;
-    __syncthreads();
-    for (int q = t; q < n; q += SEL_T) {
-      const unsigned key = rpn_key_at(po, lim, nloc, q);
-      if ((key >> 10) == d01) atomicAdd(&hist[1024 + (key & 1023u)], 1);       // the upper half of the bins, so that radix_pick's scan order holds
-    }
-    __syncthreads();
-    radix_pick(hist, r, wsum, sh);
-    K = (d01 << 10) | (unsigned)(sh[0] - 1024);
-    need_eq = sh[1];
-    __syncthreads();
-  }
+  const bool all = n <= top;               // uniform: no cut is needed, every anchor is kept
+  RadixCut cut{0u, 0};                     // else: keep key > K, and the first need_eq of key == K
+  if (!all) cut = radix_select(hist, wsum, sh, top, n, [&](int q, unsigned& key) { key = rpn_key_at(po, lim, nloc, q); return true; });
 
   // ordered compaction with decode, clip, centre, size and score filters
   int run_eq = 0, run_sel = 0, emitted = 0;
@@ -146,17 +107,8 @@ __global__ __launch_bounds__(SEL_T) void rpn_post_select_kernel(RpnGeom G, RpnBa
   for (int base = 0; base < n && run_sel < top; base += SEL_T) {       // uniform
     const int q = base + t;
     const unsigned key = q < n ? rpn_key_at(po, lim, nloc, q) : 0u;
-    bool sel = q < n && (all || key > K);
-    if (!all) {                            // uniform
-      const bool eq = q < n && key == K;
-      int tot;
-      const int rank = run_eq + block_scan_excl(eq ? 1 : 0, tot, wsum);
-      run_eq += tot;
-      sel = sel || (eq && rank < need_eq);
-    }
-    int tot;
-    const int pos = run_sel + block_scan_excl(sel ? 1 : 0, tot, wsum);      // its barriers also complete sh_base in the first chunk
-    run_sel += tot;
+    int pos;                               // the barriers of the step also complete sh_base in the first chunk
+    const bool sel = compact_step(q < n && (all || key > cut.K), q < n && key == cut.K, !all, cut.need_eq, run_eq, run_sel, wsum, pos);
     if (sel && pos < top) {
       const int a = q / nloc, loc = q - a * nloc;
       RAt at;
@@ -170,7 +122,7 @@ __global__ __launch_bounds__(SEL_T) void rpn_post_select_kernel(RpnGeom G, RpnBa
       const bool masked = key == 0u;
       float x = po[q];
       x = x != x ? -INFINITY : x;
-      const float score = masked ? 0.f : rpn_sigmoid(x);
+      const float score = masked ? 0.f : sigmoid_stable(x);
       const float mx = (float)P.mesh[0], my = (float)P.mesh[1], mz = (float)P.mesh[2];
       bool ok;
       if (ORIENTED) {
@@ -187,7 +139,7 @@ __global__ __launch_bounds__(SEL_T) void rpn_post_select_kernel(RpnGeom G, RpnBa
 #pragma unroll
       for (int c = 0; c < ROW; ++c) pre_boxes[slot * ROW + c] = ok ? o[c] : 0.f;
       pre_scores[slot] = ok ? score : 0.f;
-      pre_index[slot] = ok ? rpick4(G.off, lvl) + at.i : 0;
+      pre_index[slot] = ok ? pick4(G.off, lvl) + at.i : 0;
       pre_keys[slot] = hi | (long)(ok ? (masked ? 1u : key) : 0u);
       emitted += ok ? 1 : 0;
     }
@@ -208,31 +160,31 @@ __global__ __launch_bounds__(SEL_T) void rpn_post_select_kernel(RpnGeom G, RpnBa
 
 // every anchor's decode, anchor order, not clipped
 template <bool ORIENTED>
-__global__ __launch_bounds__(256) void rpn_decode_kernel(RpnGeom G, RpnBase B, RPtr4<const float> reg, float* __restrict__ boxes) {
+__global__ __launch_bounds__(256) void rpn_decode_kernel(RpnGeom G, RpnBase B, Ptr4<const float> reg, float* __restrict__ boxes) {
   constexpr int C = ORIENTED ? 8 : 6, ROW = ORIENTED ? 7 : 6;
   __shared__ float sh_base[RPN_MAX_A * 3];
   const RAt q = rpn_where(G);
-  const int A = rpick4(G.A, q.lvl), nloc = rpick4(G.nloc, q.lvl);
+  const int A = pick4(G.A, q.lvl), nloc = pick4(G.nloc, q.lvl);
   rpn_stage_base(B, q.lvl, A, sh_base);
   __syncthreads();
   bool valid;
   const Box6 anc = rpn_anchor(G, sh_base, nullptr, q, valid);
   if (!q.active) return;
   const int a = q.i % A, loc = q.i / A;
-  const float* __restrict__ pr = rpick4(reg.p, q.lvl) + ((long)q.scene * A + a) * C * nloc + loc;
+  const float* __restrict__ pr = pick4(reg.p, q.lvl) + ((long)q.scene * A + a) * C * nloc + loc;
   float r[8], o[7];
 #pragma unroll
   for (int c = 0; c < C; ++c) r[c] = pr[(long)c * nloc];
   if (ORIENTED) rpn_decode_obb(r, anc, o);
   else { r[6] = r[7] = 0.f; rpn_decode_aabb(r, anc, o); }
-  float* __restrict__ dst = boxes + ((long)q.scene * G.ntot + rpick4(G.off, q.lvl) + q.i) * ROW;
+  float* __restrict__ dst = boxes + ((long)q.scene * G.ntot + pick4(G.off, q.lvl) + q.i) * ROW;
 #pragma unroll
   for (int c = 0; c < ROW; ++c) dst[c] = o[c];
 }
 
 // ---- NMS: level k's boxes of scene b are rows order[b][o_k + 0 .. nb - 1] of pre_boxes[b] (the caller's stable descending sort of the keys) --------------
 __device__ __forceinline__ int level_count(const RpnGeom& G, const RpnPostGeom& P, const int* __restrict__ pre_counts, int lvl, int scene) {
-  return min(max(pre_counts[lvl * G.N + scene], 0), rpick4(P.top, lvl));
+  return min(max(pre_counts[lvl * G.N + scene], 0), pick4(P.top, lvl));
 }
 __device__ __forceinline__ long sorted_slot(const RpnPostGeom& P, const long* __restrict__ order, long sb, int off, int top, int i) {
   return min(max(order[sb + off + i], (long)off), (long)off + top - 1);          // within the level's slots for any input
@@ -247,11 +199,10 @@ __global__ __launch_bounds__(256) void rpn_post_nms_mask_kernel(RpnGeom G, RpnPo
   int lvl = 0;
 #pragma unroll
   for (int k = 1; k < 4; ++k) if (k < G.L && (int)blockIdx.x >= P.blk0[k]) lvl = k;
-  const int tw = rpick4(P.tw, lvl), top = rpick4(P.top, lvl), off = rpick4(P.off, lvl);
+  const int tw = pick4(P.tw, lvl), top = pick4(P.top, lvl), off = pick4(P.off, lvl);
   const int nb = level_count(G, P, pre_counts, lvl, scene);
-  int by = 0, j = (int)blockIdx.x - rpick4(P.blk0, lvl);
-  while (j >= tw - by) { j -= tw - by; ++by; }         // uniform, at most tw <= 256 steps
-  j += by;
+  int by, j;
+  tri_block((int)blockIdx.x - pick4(P.blk0, lvl), tw, by, j);
   const int r0 = by * 64, c0 = j * 64;
   if (c0 >= nb) return;                                // uniform; r0 <= c0
   const long sb = (long)scene * P.cap;
@@ -259,24 +210,10 @@ __global__ __launch_bounds__(256) void rpn_post_nms_mask_kernel(RpnGeom G, RpnPo
     const int i = (t < 64 ? c0 : r0 - 64) + t;
     BoxTile& dst = t < 64 ? cols[t] : rows[t - 64];
     if (i < nb) stage_box<AABB>(pre_boxes + sb * ROW, sorted_slot(P, order, sb, off, top, i), (long)P.cap, dst);
-    else {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) dst.v[k] = 0.f;
-    }
+    else zero_box(dst);
   }
   __syncthreads();
-  const int k = t & 63, col = c0 + k;
-  const BoxTile bc = cols[k];
-  unsigned long long* __restrict__ m0 = mask + (long)scene * P.mtot + rpick4(P.moff, lvl);
-#pragma unroll 1
-  for (int r = t >> 6; r < 64; r += 4) {
-    const int row = r0 + r;
-    if (row >= nb) break;                              // uniform over the wave
-    bool hit = false;
-    if (col > row && col < nb) hit = tile_iou<AABB>(rows[r], bc) > thr;
-    const unsigned long long word = __ballot(hit);
-    if (k == 0) m0[(long)row * tw + j] = word;
-  }
+  nms_mask_tile<AABB>(rows, cols, r0, c0, j, nb, thr, mask + (long)scene * P.mtot + pick4(P.moff, lvl), tw, nullptr, nullptr);
 }
 
 // one workgroup per scene; t_k <= 16384 (256 words of removed-set)
@@ -290,34 +227,9 @@ __global__ __launch_bounds__(256) void rpn_post_nms_scan_kernel(RpnGeom G, RpnPo
   const int t = threadIdx.x, scene = blockIdx.x;
   const long sb = (long)scene * P.cap;
   for (int lvl = 0; lvl < G.L; ++lvl) {    // uniform
-    const int tw = rpick4(P.tw, lvl), off = rpick4(P.off, lvl);
-    const int N = level_count(G, P, pre_counts, lvl, scene), nw = (N + 63) >> 6;
-    const unsigned long long* __restrict__ m0 = mask + (long)scene * P.mtot + rpick4(P.moff, lvl);
-    int* kp = keep + sb + off;
-    __syncthreads();                       // removed[] of the previous level has been read
-    removed[t] = 0ull;
-    int cnt = 0;                           // the same in every thread
-    for (int c = 0; c < nw; ++c) {
-      __syncthreads();                     // removed[] of the previous block is complete; diag[] is free
-      if (t < 64) diag[t] = c * 64 + t < N ? m0[(long)(c * 64 + t) * tw + c] : 0ull;
-      __syncthreads();
-      unsigned long long r = removed[c];
-      const int left = N - c * 64;
-      if (left < 64) r |= ~0ull << left;   // positions past N count as removed
-      for (int k = 0; k < 64; ++k)         // row k's word only has bits above k, so bit k of r is final when it is read
-        if (!((r >> k) & 1ull)) r |= diag[k];
-      const unsigned long long kept = ~r;
-      if (t < 64 && ((kept >> t) & 1ull)) kp[cnt + __popcll(kept & ((1ull << t) - 1ull))] = c * 64 + t;
-      cnt += __popcll(kept);
-      const int nrem = nw - c - 1;         // words after the diagonal one
-      for (int q = t; q < 64 * nrem; q += 256) {
-        const int k = q / nrem, w = c + 1 + q % nrem;
-        if ((kept >> k) & 1ull) {
-          const unsigned long long m = m0[(long)(c * 64 + k) * tw + w];
-          if (m) atomicOr(&removed[w], m);
-        }
-      }
-    }
+    const int tw = pick4(P.tw, lvl), off = pick4(P.off, lvl);
+    const int N = level_count(G, P, pre_counts, lvl, scene);
+    const int cnt = nms_greedy_walk(mask + (long)scene * P.mtot + pick4(P.moff, lvl), tw, N, keep + sb + off, removed, diag);      // the same in every thread
     if (t == 0) kept_n[lvl] = cnt;
   }
   __syncthreads();                         // keep[] and kept_n[] are complete and visible to the workgroup
@@ -326,14 +238,14 @@ __global__ __launch_bounds__(256) void rpn_post_nms_scan_kernel(RpnGeom G, RpnPo
   const int m = min(total, max(post_top_n, 0));
   // merge: rank in the global order (descending key, ties to the lower slot = the lower level, then the level's own order)
   for (int lvl = 0; lvl < G.L; ++lvl) {
-    const int off = rpick4(P.off, lvl), top = rpick4(P.top, lvl);
+    const int off = pick4(P.off, lvl), top = pick4(P.top, lvl);
     for (int j = t; j < kept_n[lvl]; j += 256) {
       const int pos = keep[sb + off + j];
       const unsigned key = (unsigned)(sorted_keys[sb + off + pos] & 0xffffffffl);
       int rank = j;
       for (int l2 = 0; l2 < G.L; ++l2) {
         if (l2 == lvl) continue;
-        const int off2 = rpick4(P.off, l2);
+        const int off2 = pick4(P.off, l2);
         int lo = 0, hi = kept_n[l2];       // the first entry of level l2 that does NOT come before this box
         while (lo < hi) {
           const int mid = (lo + hi) >> 1;
@@ -395,7 +307,7 @@ int k_rpn_decode(int nlevels, const int* dims, const float* base, int N, int nco
   RpnGeom G;
   RpnBase B;
   if (make_geom(nlevels, dims, N, G) || make_base(nlevels, dims, base, B) || (ncols != 6 && ncols != 8) || !all_set(nlevels, reg)) return -4;
-  const RPtr4<const float> R = make_ptrs<const float>(nlevels, reg);
+  const Ptr4<const float> R = make_ptrs<const float>(nlevels, reg);
   if (ncols == 8) hipLaunchKernelGGL(rpn_decode_kernel<true>, dim3(G.nblocks), dim3(256), 0, st, G, B, R, boxes);
   else hipLaunchKernelGGL(rpn_decode_kernel<false>, dim3(G.nblocks), dim3(256), 0, st, G, B, R, boxes);
   NMH_CHECK_LAUNCH();
@@ -409,7 +321,7 @@ int k_rpn_post_select(int nlevels, const int* dims, const float* base, int N, in
   RpnPostGeom P;
   if (!mesh || make_geom(nlevels, dims, N, G) || make_base(nlevels, dims, base, B) || make_post(G, pre_top_n, mesh, P) || (ncols != 6 && ncols != 8)) return -4;
   if (!all_set(nlevels, obj) || !all_set(nlevels, reg)) return -4;
-  const RPtr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
+  const Ptr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
   const dim3 grid((unsigned)(nlevels * N));
   if (ncols == 8) hipLaunchKernelGGL(rpn_post_select_kernel<true>, grid, dim3(SEL_T), 0, st, G, B, P, O, R, ori, score_thresh, min_size, pre_keys, pre_boxes, pre_scores, pre_index, pre_counts);
   else hipLaunchKernelGGL(rpn_post_select_kernel<false>, grid, dim3(SEL_T), 0, st, G, B, P, O, R, ori, score_thresh, min_size, pre_keys, pre_boxes, pre_scores, pre_index, pre_counts);
