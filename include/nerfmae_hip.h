@@ -508,6 +508,33 @@ NMH_API int nmh_rpn_post_select(int nlevels, const int* level_dims, const float*
  * DEVICE workspace [N][cap] int.  post_nms_top_n >= 1.  -> boxes [N][cap][6|7], scores, levels, index [N][cap] in descending logit (ties: the lower slot), the first
  * min(post_nms_top_n, survivors) rows; rows past counts[b] are zero. */
 NMH_API int nmh_rpn_post_nms(int nlevels, const int* level_dims, int N, int ncols, int pre_nms_top_n, const float* pre_boxes, const float* pre_scores, const int* pre_index, const int64_t* sorted_keys, const int64_t* order, const int* pre_counts, float nms_thresh, int post_nms_top_n, uint64_t* mask, int* keep, float* boxes, float* scores, int* levels, int* index, int* counts, void* stream);
+/* ---- RoI stage of the two-stage detector (nerf_rpn/model/detector.py; kernels and semantics: csrc/roi_head.hip) ----
+ * Proposal targets: ProposalTargetLayer._sample_rois_pytorch (detector.py:60-167) over batched_box_iou (model/utils.py:371-458).  boxes [N][cap][ncols],
+ * levels [N][cap], counts [N] are the dense results of nmh_rpn_post_nms; gt [G][ncols] with gt_labels [G] fp32 and HOST box_offsets [N+1].  Matching
+ * (max IoU, ties to the lowest box) -> max_iou, arg [N][cap].  is_sample: rng_state (seed, counter; the counter advances) drives the device sampler
+ * (foreground without, background with replacement; lists: workspace [N][2][cap]) -> keep [N][R], counts2 [N][2]; rng_state NULL: keep and counts2
+ * are the caller's.  Evaluation: R == cap, keep[r] = r below counts.  Then labels [N][R], rois [N][R][1+ncols] (level, box), gt_rois [N][R][ncols];
+ * keep -1: label -1 and zeros. */
+NMH_API int nmh_roi_targets(int N, int cap, int ncols, int R, int is_sample, const float* boxes, const int* levels, const int* counts, const float* gt, const float* gt_labels, const int* box_offsets, int want_fg, float fg_threshold, float bg_threshold, int64_t* rng_state, float* max_iou, int* arg, int* lists, int* keep, int* counts2, float* labels, float* rois, float* gt_rois, void* stream);
+/* LevelMapper.__call__ (level_mapper.py:47-59), the remap branch of ROIPool.forward (detector.py:222-236): boxes [M][stride], the box in the last ncols
+ * columns -> levels [M] = clamp(floor(canonical_level + log2(cbrt(b3 b4 b5) / canonical_scale) + eps), k_min, k_max) - k_min. */
+NMH_API int nmh_roi_level_map(int64_t M, const float* boxes, int stride, int ncols, int k_min, int k_max, float canonical_scale, float canonical_level, float eps, int* levels, void* stream);
+/* ROIPool.normal_forward (detector.py:407-438, ncols 6) and ROIPool.rotated_forward (detector.py:264-404, ncols 7) with 'pooling': the per-RoI crop or
+ * rotated 8-corner grid and the zero-padded nn.MaxPool3d, all scenes and levels in one launch.  maps: per level (N, C, W, H, D) fp32; level_dims HOST
+ * [nlevels][3]; scales HOST [nlevels]; rois [N R][1+ncols]; level_override [N R] or NULL -> out, argmax [N R][C][ow][oh][od] (argmax -1: a zero won). */
+NMH_API int nmh_roi_pool_fwd(int nlevels, const int* level_dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* const* maps, const float* rois, const int* level_override, float* out, int* argmax, void* stream);
+/* Its adjoint with respect to the maps (autograd through the same lines): fp32 atomic adds into dmaps, which the caller zeroed; a NULL level is skipped. */
+NMH_API int nmh_roi_pool_bwd(int nlevels, const int* level_dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* dout, const int* argmax, const float* rois, const int* level_override, float* const* dmaps, void* stream);
+/* Classification_Model.compute_loss (detector.py:536-559) with the targets of box_coder.encode_single (detector.py:616; coder/rotated_coder.py:19-55,
+ * coder/AABB_coder.py:7-56): cross-entropy over rows with 0 <= label < n_classes, smooth-L1 (beta 1/9) over rows with label > 0, in fixed order.
+ * rois [M][roi_stride], the box in the last ncols columns.  -> targets [M][ncols], scalars [4] = (loss_objectness, loss_rpn_box_reg, valid rows,
+ * positive rows); partials: 4 * nmh_roi_loss_blocks(M) floats. */
+NMH_API int64_t nmh_roi_loss_blocks(int64_t M);
+NMH_API int nmh_roi_loss_fwd(int64_t M, int n_classes, int ncols, const float* scores, const float* deltas, const float* labels, const float* rois, int roi_stride, const float* gt_rois, float* targets, float* partials, float* scalars, void* stream);
+/* Its backward (autograd through detector.py:536-559): every element of dscores [M][n_classes] and ddeltas [M][ncols] in one pass. */
+NMH_API int nmh_roi_loss_bwd(int64_t M, int n_classes, int ncols, const float* scores, const float* deltas, const float* labels, const float* targets, const float* scalars, const float* g_obj, const float* g_reg, float* dscores, float* ddeltas, void* stream);
+/* RotatedCoder.decode_single (coder/rotated_coder.py:57-121) / AABBCoder.decode_single (coder/AABB_coder.py:86-137), detector.py:609-611. */
+NMH_API int nmh_roi_decode(int64_t M, int ncols, const float* deltas, const float* rois, int roi_stride, float* boxes, void* stream);
 /* Per-step host parameters of the training step in ONE launch, passed as kernel arguments (no host-to-device copies):
  *  - block_bits (HOST, nb^3 bits, bit (a*nb+b)*nb+c = 1: the 4x4x4-token block (a,b,c) is removed; window_masking_3d's raster order,
  *    swin_mae3d.py:1366-1373) is expanded to the token mask tokmask[g^3] (device, uint8; tokens outside the nb^3 blocks stay 0);

@@ -752,6 +752,50 @@ int nmh_pack_weights(int dt, const void* descs_dev, const int* blk2desc_dev, con
 }
 int nmh_grad_sqnorm(const float* g, int64_t n, double* acc, void* stream) {
   CLR(); return k_sqnorm(g, (long)n, acc, ST); }
+int nmh_roi_targets(int N, int cap, int ncols, int R, int is_sample, const float* boxes, const int* levels, const int* counts, const float* gt, const float* gt_labels,
+                    const int* box_offsets, int want_fg, float fg_threshold, float bg_threshold, int64_t* rng_state, float* max_iou, int* arg, int* lists, int* keep, int* counts2,
+                    float* labels, float* rois, float* gt_rois, void* stream) {
+  CLR();
+  REQ(boxes, levels, counts, box_offsets, max_iou, arg, keep, labels, rois, gt_rois);
+  if (is_sample) REQ(counts2);
+  return k_roi_targets(N, cap, ncols, R, is_sample, boxes, levels, counts, gt, gt_labels, box_offsets, want_fg, fg_threshold, bg_threshold, (long*)rng_state, max_iou, arg, lists, keep,
+                       counts2, labels, rois, gt_rois, ST);
+}
+int nmh_roi_level_map(int64_t M, const float* boxes, int stride, int ncols, int k_min, int k_max, float canonical_scale, float canonical_level, float eps, int* levels, void* stream) {
+  CLR();
+  REQ(boxes, levels);
+  return k_roi_level_map((long)M, boxes, stride, ncols, k_min, k_max, canonical_scale, canonical_level, eps, levels, ST);
+}
+int nmh_roi_pool_fwd(int nlevels, const int* level_dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* const* maps,
+                     const float* rois, const int* level_override, float* out, int* argmax, void* stream) {
+  CLR();
+  REQ(level_dims, scales, maps, rois, out, argmax);
+  return k_roi_pool_fwd(nlevels, level_dims, scales, N, C, R, ncols, ow, oh, od, enlarge, maps, rois, level_override, out, argmax, ST);
+}
+int nmh_roi_pool_bwd(int nlevels, const int* level_dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* dout, const int* argmax,
+                     const float* rois, const int* level_override, float* const* dmaps, void* stream) {
+  CLR();
+  REQ(level_dims, scales, dout, argmax, rois, dmaps);
+  return k_roi_pool_bwd(nlevels, level_dims, scales, N, C, R, ncols, ow, oh, od, enlarge, dout, argmax, rois, level_override, dmaps, ST);
+}
+int64_t nmh_roi_loss_blocks(int64_t M) { return k_roi_loss_blocks((long)M); }
+int nmh_roi_loss_fwd(int64_t M, int n_classes, int ncols, const float* scores, const float* deltas, const float* labels, const float* rois, int roi_stride, const float* gt_rois,
+                     float* targets, float* partials, float* scalars, void* stream) {
+  CLR();
+  REQ(scores, deltas, labels, rois, gt_rois, targets, partials, scalars);
+  return k_roi_loss_fwd((long)M, n_classes, ncols, scores, deltas, labels, rois, roi_stride, gt_rois, targets, partials, scalars, ST);
+}
+int nmh_roi_loss_bwd(int64_t M, int n_classes, int ncols, const float* scores, const float* deltas, const float* labels, const float* targets, const float* scalars, const float* g_obj,
+                     const float* g_reg, float* dscores, float* ddeltas, void* stream) {
+  CLR();
+  REQ(scores, deltas, labels, targets, scalars, dscores, ddeltas);
+  return k_roi_loss_bwd((long)M, n_classes, ncols, scores, deltas, labels, targets, scalars, g_obj, g_reg, dscores, ddeltas, ST);
+}
+int nmh_roi_decode(int64_t M, int ncols, const float* deltas, const float* rois, int roi_stride, float* boxes, void* stream) {
+  CLR();
+  REQ(deltas, rois, boxes);
+  return k_roi_decode((long)M, ncols, deltas, rois, roi_stride, boxes, ST);
+}
 int nmh_clip_coef(const double* acc, float max_norm, float* coef, float* norm_out, void* stream) {
   CLR(); return k_clip_coef(acc, max_norm, coef, norm_out, ST); }
 int nmh_adamw_step(float* p, float* g, float* m, float* v, int64_t n, const float* hyper, const float* coef, void* stream) {

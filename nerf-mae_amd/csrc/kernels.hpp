@@ -330,6 +330,25 @@ int k_rpn_post_select(int nlevels, const int* dims, const float* base, int N, in
 int k_rpn_post_nms(int nlevels, const int* dims, int N, int ncols, int pre_top_n, const float* pre_boxes, const float* pre_scores, const int* pre_index, const long* sorted_keys,
                    const long* order, const int* pre_counts, float nms_thresh, int post_top_n, unsigned long long* mask, int* keep, float* boxes, float* scores, int* levels,
                    int* index, int* counts, hipStream_t st);
+// ---- roi_head.hip (RoI stage of the two-stage detector: proposal targets, pyramid RoI pooling, box-head losses, decode) ----
+// offs: HOST [N+1]; dims: HOST [nlevels][3] = (W, H, D); scales: HOST [nlevels]; maps / dmaps: HOST tables of nlevels DEVICE pointers.  Layouts: roi_head.hip.
+#define NMH_ROI_MAX_GRID 1024
+#define NMH_ROI_MAX_CELLS 4096
+#define NMH_ROI_MAX_CLASSES 1024
+int k_roi_targets(int N, int cap, int ncols, int R, int is_sample, const float* boxes, const int* levels, const int* counts, const float* gt, const float* gt_labels, const int* offs,
+                  int want_fg, float fg, float bg, long* rng, float* miou, int* arg, int* lists, int* keep, int* counts2, float* labels, float* rois, float* gt_rois,
+                  hipStream_t st);
+int k_roi_level_map(long M, const float* boxes, int stride, int ncols, int k_min, int k_max, float canonical_scale, float canonical_level, float eps, int* out, hipStream_t st);
+int k_roi_pool_fwd(int nlevels, const int* dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* const* maps, const float* rois,
+                   const int* lvl_override, float* out, int* argout, hipStream_t st);
+int k_roi_pool_bwd(int nlevels, const int* dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* dout, const int* argout,
+                   const float* rois, const int* lvl_override, float* const* dmaps, hipStream_t st);
+long k_roi_loss_blocks(long M);
+int k_roi_loss_fwd(long M, int n_classes, int ncols, const float* scores, const float* deltas, const float* labels, const float* rois, int roi_stride, const float* gt_rois,
+                   float* targets, float* partials, float* scalars, hipStream_t st);
+int k_roi_loss_bwd(long M, int n_classes, int ncols, const float* scores, const float* deltas, const float* labels, const float* targets, const float* scalars, const float* g_obj,
+                   const float* g_reg, float* dscores, float* ddeltas, hipStream_t st);
+int k_roi_decode(long M, int ncols, const float* deltas, const float* rois, int roi_stride, float* out, hipStream_t st);
 int k_step_params(const unsigned* bits, int nb, int g, unsigned char* tokmask, const float* hyper_host, float* hyper_dev, const int* ext_host, int n_ext, int* ext_dev, hipStream_t st);
 int k_grad_cast(int to_bf16, const void* src, void* dst, long n, float scale, hipStream_t st);
 

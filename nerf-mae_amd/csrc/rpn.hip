@@ -37,6 +37,7 @@
 #include "kernels.hpp"
 #include "select_scan.hpp"
 #include "rpn_geom.hpp"
+#include "rpn_shared.hpp"
 
 namespace {
 
@@ -55,18 +56,6 @@ __device__ __forceinline__ Box6 rpn_gt(const float* __restrict__ b) {
   }
   g.vol = (g.x1 - g.x0) * (g.y1 - g.y0) * (g.z1 - g.z0);
   return g;
-}
-
-// the one IoU of both passes: no contraction, so the same inputs give the same bits in either kernel
-__device__ __forceinline__ float rpn_iou(const Box6& g, const Box6& a) {
-#pragma clang fp contract(off)
-  const float w = fmaxf(fminf(g.x1, a.x1) - fmaxf(g.x0, a.x0), 0.f);
-  const float h = fmaxf(fminf(g.y1, a.y1) - fmaxf(g.y0, a.y0), 0.f);
-  const float d = fmaxf(fminf(g.z1, a.z1) - fmaxf(g.z0, a.z0), 0.f);
-  const float inter = w * h * d;
-  const float uni = g.vol + a.vol - inter;
-  const float iou = inter / uni;
-  return iou > 0.f ? iou : 0.f;              // 0 / 0, -0 and malformed boxes: no overlap, with the bits of +0
 }
 
 // ---- assignment ------------------------------------------------------------------------------------------------------------------------
@@ -103,15 +92,6 @@ __global__ __launch_bounds__(256) void rpn_gtmax_kernel(RpnGeom G, RpnBase B, Rp
   }
 }
 
-__device__ __forceinline__ void rpn_encode_aabb(const float* __restrict__ g, const Box6& a, float (&o)[8]) {
-  const float ew = a.x1 - a.x0, eh = a.y1 - a.y0, ed = a.z1 - a.z0;
-  const float ex = a.x0 + 0.5f * ew, ey = a.y0 + 0.5f * eh, ez = a.z0 + 0.5f * ed;
-  const float gw = g[3] - g[0], gh = g[4] - g[1], gd = g[5] - g[2];
-  const float gx = g[0] + 0.5f * gw, gy = g[1] + 0.5f * gh, gz = g[2] + 0.5f * gd;
-  o[0] = (gx - ex) / ew; o[1] = (gy - ey) / eh; o[2] = (gz - ez) / ed;
-  o[3] = logf(gw / ew); o[4] = logf(gh / eh); o[5] = logf(gd / ed);
-  o[6] = o[7] = 0.f;
-}
 // bbox2delta_sp: ga = the largest corner x among the corners within 0.1 of the lowest y (others count as -1000), gb likewise for y at the largest x
 __device__ __forceinline__ void rpn_encode_obb(const float* __restrict__ g, const Box6& a, float (&o)[8]) {
   const float px = (a.x0 + a.x1) * 0.5f, py = (a.y0 + a.y1) * 0.5f, pz = (a.z0 + a.z1) * 0.5f;
@@ -189,16 +169,6 @@ __global__ __launch_bounds__(256) void rpn_assign_kernel(RpnGeom G, RpnBase B, R
 }
 
 // ---- sampling ----------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long rpn_mix64(unsigned long long x) {      // the splitmix64 finaliser
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-__device__ __forceinline__ unsigned long long rpn_stream(long seed, long counter, int scene) {
-  return rpn_mix64(rpn_mix64((unsigned long long)seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)counter + 1ull)) ^ ((unsigned long long)(scene + 1) << 40));
-}
-// complemented hash: the largest of these are the smallest keys
-__device__ __forceinline__ unsigned rpn_key(unsigned long long stream, int idx) { return ~(unsigned)(rpn_mix64(stream + (unsigned long long)idx * 0xD1342543DE82EF95ull) >> 32); }
 __device__ __forceinline__ int rpn_class(float label) { return label >= 1.f ? 0 : (label == 0.f ? 1 : -1); }
 
 enum { SEL_NONE = 0, SEL_ALL = 1, SEL_CUT = 2 };
@@ -266,10 +236,6 @@ __global__ __launch_bounds__(SEL_T) void rpn_sample_kernel(const float* __restri
   if (t == 0) { counts[scene * 2] = num[0]; counts[scene * 2 + 1] = num[1]; }
 }
 
-__global__ void rpn_rng_advance_kernel(long* __restrict__ rng) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) rng[1] = rng[1] + 1;
-}
-
 // ---- losses ------------------------------------------------------------------------------------------------------------------------------
 // head order: lane j of (level, scene) is head element (a, loc) = (j / nloc, j % nloc), anchor i = loc A + a
 struct RHead { int lvl, scene, j, a, loc, nloc, A; long p; bool active; };
@@ -283,10 +249,6 @@ __device__ __forceinline__ RHead rpn_head_where(const RpnGeom& G) {
   r.p = (long)q.scene * G.ntot + pick4(G.off, q.lvl) + (long)r.loc * r.A + r.a;
   return r;
 }
-constexpr float RPN_BETA = 1.f / 9.f;
-__device__ __forceinline__ float rpn_sl1(float d) { const float a = fabsf(d); return a < RPN_BETA ? 0.5f * d * d / RPN_BETA : a - 0.5f * RPN_BETA; }
-__device__ __forceinline__ float rpn_sl1_grad(float d) { return fabsf(d) < RPN_BETA ? d / RPN_BETA : (d > 0.f ? 1.f : -1.f); }
-
 // sums (a, b, c) over the workgroup in a fixed order -> out[0 .. 2] (thread 0)
 __device__ __forceinline__ void block_sum3(float a, float b, float c, float* __restrict__ out) {
   __shared__ float red[3][4];

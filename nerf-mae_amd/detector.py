@@ -1,0 +1,457 @@
+"""The RoI (second) stage of the reference's two-stage detector on the HIP kernels of csrc/roi_head.hip, with the reference's names (the import swap
+is one line):
+
+  roi_targets_dense / ProposalTargetLayer   nerf_rpn/model/detector.py:12-167 over batched_box_iou (model/utils.py:371-458)
+  LevelMapper                               model/level_mapper.py:21-77 (with _setup_scales)
+  ROIPool                                   detector.py:170-438: normal_forward and rotated_forward with feature_extracting_type="pooling", remap
+  RCNN                                      detector.py:441-496, a torch module with the reference's state_dict keys (two small convs and two Linear layers: no hot path)
+  roi_head_loss / roi_decode / RotatedCoder  detector.py:536-559 with coder/rotated_coder.py and coder/AABB_coder.py
+  Classification_Model                      detector.py:499-627
+
+All tensors are fp32 on the device.  Boxes are [.., 6] (x0,y0,z0,x1,y1,z1) or [.., 7] (x,y,z,w,h,d,theta); RoIs carry their pyramid level in front, [.., 1+6|7].
+roi_targets_dense takes what rpn.rpn_proposals_dense returns (boxes [N,cap,6|7], levels, counts), so the first stage feeds the second without a host wait.
+Feature maps are one (N, C, W, H, D) tensor per level, as fpn.py returns them; the reference's list of per-scene lists is accepted and stacked.
+
+In sampling mode nothing waits for the host and every sum of ours has a fixed order (the scatter of the pooling backward uses fp32 atomics, as rotated.py's
+does), so targets + pooling + head + losses, forward and backward, can be captured with torch.cuda.graph; the sampler's counter lives on the device and
+advances inside the graph, so every replay draws afresh.  Evaluation with dense input waits once, for the N counts that size its lists.
+
+Stated deviations from the reference:
+  - the order of the foreground slots is ours (ascending proposal index); the losses do not depend on it;
+  - np.random's stream is not reproduced: a foreground candidate's key is a hash of (seed, counter, scene, index) and the smallest keys are taken (uniform
+    without replacement, ties at the cut to the lower index); background draw j is candidate floor(u_j n_bg) in index order with u_j a hash of (seed, counter,
+    scene, j): uniform with replacement, as the reference's floor(rand * n);
+  - equal IoU of one RoI with several boxes goes to the lowest box index (torch.max leaves it open); if bg_threshold > fg_threshold a RoI above both
+    is foreground;
+  - a scene with neither foreground nor background candidates: the reference raises; here its rows have label -1 and zero boxes, and the losses ignore them;
+  - in evaluation mode (dense entry) rows past counts[i] are zero with label -1; a scene without ground-truth boxes has IoU 0 everywhere;
+  - the axis-aligned crop: the reference's negative lower index wraps Python-style; here the crop is clamped to the map and an empty crop gives zeros;
+  - oriented RoIs: the reference's enlarge_roi writes the enlarged sizes into the caller's RoI tensor (detector.py:199-201), so with remap off
+    Classification_Model encodes, decodes and returns the ENLARGED RoIs (tests/golden/g22_roi_head.npz confirms this reading), and with remap on (where the
+    reference enlarges a copy) the original ones.  This module computes the same values but never writes into a caller's tensor;
+  - an oriented RoI's sampling grid is cut at ROI_MAX_GRID points per axis (the reference would run out of memory long before);
+  - where the zero padding or a masked point ties with a value, the value wins; among equal values the first in (x, y, z) order wins, as in nn.MaxPool3d;
+  - roi_decode has no gradient (the reference's decode only feeds outputs); RoIs get no gradient from the pooling;
+  - both losses are 0 with zero gradient when no row counts (the reference: NaN objectness without valid rows); labels outside [0, n_classes) are ignored rows
+    (F.cross_entropy raises);
+  - feature_extracting_type="interpolation" and use_cuda=True raise NotImplementedError: the launcher (run_rpn_detect.py) never sets them, and the use_cuda
+    path returns features in level order rather than RoI order;
+  - other dtypes than fp32 raise TypeError, CPU tensors RuntimeError; more than MAX_LEVELS levels, MAX_SCENES scenes, MAX_ROWS rows per scene, MAX_CELLS
+    output cells or MAX_CLASSES classes raise ValueError."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+from torch import nn
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
+
+from . import ops
+from .fcos_loss import _boxes, _check
+from .rpn import MAX_LEVELS, MAX_SCENES
+
+MAX_ROWS, MAX_CELLS, MAX_CLASSES, MAX_GRID = ops.ROI_MAX_ROWS, ops.ROI_MAX_CELLS, ops.ROI_MAX_CLASSES, ops.ROI_MAX_GRID
+
+
+def _int32(name, what, t, shape):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != tuple(shape) or not t.is_cuda:
+        raise ValueError(f"{name}: {what} must be an int32 device tensor {list(shape)}")
+    return t.contiguous()
+
+
+def _rng(name, rng_state):
+    if not isinstance(rng_state, torch.Tensor) or rng_state.dtype != torch.int64 or tuple(rng_state.shape) != (2,) or not rng_state.is_cuda:
+        raise ValueError(f"{name}: rng_state must be an int64 device tensor [2] = (seed, counter)")
+    return rng_state
+
+
+# ---- proposal targets ------------------------------------------------------------------------------------------------------------------------
+def roi_targets_dense(boxes, levels, counts, gt_boxes, gt_labels, rois_per_image, fg_rois_per_image, fg_threshold, bg_threshold, rng_state, is_sample,
+                      keep=None, keep_counts=None):
+    """boxes [N,cap,6|7], levels [N,cap] int32, counts [N] int32: rpn_proposals_dense's results; gt_boxes, gt_labels: per scene [k,6|7] and [k] fp32.
+    Sampling: R = rois_per_image rows per scene, drawn by rng_state (int64 device [2] = (seed, counter), the counter advances by one) or given by keep [N,R]
+    int32 (proposal index, -1: none) with keep_counts [N,2] int32 (foreground slots first, then background).  Evaluation: R = cap, every proposal.
+    -> (labels [N,R], rois [N,R,1+6|7], gt_rois [N,R,6|7], keep [N,R] int32, counts [N,2] int32 = (foreground, background) slots; None in evaluation)"""
+    name = "roi_targets_dense"
+    _check(name, boxes)
+    if boxes.dim() != 3 or boxes.shape[2] not in (6, 7):
+        raise ValueError(f"{name}: boxes must be [N, cap, 6|7], got {tuple(boxes.shape)}")
+    N, cap, B = boxes.shape
+    if not 1 <= N <= MAX_SCENES:
+        raise ValueError(f"{name} supports 1 to {MAX_SCENES} scenes, got {N}")
+    if not 1 <= cap <= MAX_ROWS:
+        raise ValueError(f"{name} supports 1 to {MAX_ROWS} proposals per scene, got {cap}")
+    if len(gt_boxes) != N or len(gt_labels) != N:
+        raise ValueError(f"{name}: {N} scenes but {len(gt_boxes)} box and {len(gt_labels)} label tensors")
+    levels, counts = _int32(name, "levels", levels, (N, cap)), _int32(name, "counts", counts, (N,))
+    gt, offsets = _boxes(name, gt_boxes, B)
+    _check(name, *gt_labels)
+    if any(l.numel() != b.shape[0] for l, b in zip(gt_labels, gt_boxes)):
+        raise ValueError(f"{name}: one label per ground-truth box")
+    lab = torch.cat([l.detach().reshape(-1) for l in gt_labels]).contiguous()
+    R, want_fg = cap, 0
+    if is_sample:
+        R, want_fg = int(rois_per_image), int(fg_rois_per_image)
+        if not 1 <= R <= MAX_ROWS or want_fg < 0:
+            raise ValueError(f"{name}: 1 to {MAX_ROWS} rois_per_image and fg_rois_per_image >= 0, got {R}, {want_fg}")
+        if keep is None:
+            rng_state = _rng(name, rng_state)
+        else:
+            keep, keep_counts, rng_state = _int32(name, "keep", keep, (N, R)), _int32(name, "keep_counts", keep_counts, (N, 2)), None
+    with torch.no_grad():
+        labels, rois, gt_rois, keep, counts2, _, _ = ops.roi_targets(boxes.detach().contiguous(), levels, counts, gt, lab, offsets, R, want_fg, float(fg_threshold), float(bg_threshold),
+                                                                     bool(is_sample), rng_state, keep, keep_counts)
+    return labels, rois, gt_rois, keep, counts2
+
+
+def _pack(name, all_rois, B):
+    """list of per-scene [K, 1+B] RoIs -> (boxes [N,cap,B], levels [N,cap] int32, counts [N] int32, host counts)"""
+    _check(name, *all_rois)
+    if any(r.dim() != 2 or r.shape[1] != 1 + B for r in all_rois):
+        raise ValueError(f"{name}: RoIs must be [K, {1 + B}] per scene (level, box)")
+    ks = [r.shape[0] for r in all_rois]
+    cap = max(max(ks), 1)
+    dense = torch.stack([F.pad(r.detach(), (0, 0, 0, cap - k)) for r, k in zip(all_rois, ks)])
+    counts = torch.tensor(ks, dtype=torch.int32).to(dense.device, non_blocking=True)
+    return dense[..., 1:].contiguous(), dense[..., 0].to(torch.int32).contiguous(), counts, ks
+
+
+class ProposalTargetLayer(nn.Module):
+    """The reference's constructor and forward(all_rois, gt_boxes, gt_labels, is_sample); all_rois: per scene [K, 1+6|7] with the level in column 0.
+    Sampling -> (labels [N,R], rois [N,R,1+6|7], gt_rois [N,R,6|7]); evaluation -> per-scene lists.  rng_state (int64 device [2]) is created on the first
+    sampling call from `seed`; copy into it to replay a draw.  forward_dense takes rpn_proposals_dense's results."""
+
+    def __init__(self, nclasses, batch_size=1000, fg_fraction=0.5, fg_threshold=0.5, bg_threshold=0.2, is_rotated_bbox=False, seed=0):
+        super().__init__()
+        self._num_classes = nclasses
+        self.batch_size, self.fg_fraction = batch_size, fg_fraction
+        self.fg_threshold, self.bg_threshold = fg_threshold, bg_threshold
+        self.is_rotated_bbox = is_rotated_bbox
+        self.bbox_size = 7 if is_rotated_bbox else 6
+        self.seed = int(seed)
+        self.rng_state = None
+
+    def _sizes(self, num_mesh):
+        rois_per_image = int(self.batch_size / num_mesh)
+        fg = int(np.round(self.fg_fraction * rois_per_image))
+        return rois_per_image, (1 if fg == 0 else fg)
+
+    def forward_dense(self, boxes, levels, counts, gt_boxes, gt_labels, is_sample, keep=None, keep_counts=None):
+        """-> roi_targets_dense's five results"""
+        R, fg = self._sizes(boxes.shape[0])
+        if is_sample and keep is None and self.rng_state is None:
+            self.rng_state = torch.tensor([self.seed, 0], dtype=torch.int64, device=boxes.device)
+        return roi_targets_dense(boxes, levels, counts, gt_boxes, gt_labels, R, fg, self.fg_threshold, self.bg_threshold, self.rng_state, is_sample, keep, keep_counts)
+
+    def forward(self, all_rois, gt_boxes, gt_labels, is_sample, keep=None, keep_counts=None):
+        if not (len(all_rois) == len(gt_boxes) == len(gt_labels)):
+            raise ValueError("ProposalTargetLayer: one RoI, box and label tensor per scene")
+        boxes, levels, counts, ks = _pack("ProposalTargetLayer", all_rois, self.bbox_size)
+        labels, rois, gt_rois, _, _ = self.forward_dense(boxes, levels, counts, gt_boxes, gt_labels, is_sample, keep, keep_counts)
+        if is_sample:
+            return labels, rois, gt_rois
+        return [labels[i, :k] for i, k in enumerate(ks)], [rois[i, :k] for i, k in enumerate(ks)], [gt_rois[i, :k] for i, k in enumerate(ks)]
+
+
+# ---- level mapper ----------------------------------------------------------------------------------------------------------------------------
+class LevelMapper:
+    """boxes [..., 6|7] fp32 device -> int64 levels clamp(floor(lvl0 + log2(cbrt(b3 b4 b5) / s0) + eps), k_min, k_max) - k_min.  As in the reference the
+    "volume" is the product of columns 3, 4, 5 whatever the box form."""
+
+    def __init__(self, k_min, k_max, canonical_scale=160, canonical_level=4, eps=1e-6):
+        self.k_min, self.k_max, self.s0, self.lvl0, self.eps = k_min, k_max, canonical_scale, canonical_level, eps
+
+    def levels32(self, boxes):
+        _check("LevelMapper", boxes)
+        if boxes.shape[-1] not in (6, 7):
+            raise ValueError(f"LevelMapper: boxes must be [..., 6|7], got {tuple(boxes.shape)}")
+        flat = boxes.detach().reshape(-1, boxes.shape[-1]).contiguous()
+        return ops.roi_level_map(flat, boxes.shape[-1], int(self.k_min), int(self.k_max), float(self.s0), float(self.lvl0), float(self.eps)).reshape(boxes.shape[:-1])
+
+    def __call__(self, boxlists):
+        return self.levels32(boxlists).to(torch.int64)
+
+
+def initLevelMapper(k_min, k_max, canonical_scale=160, canonical_level=4, eps=1e-6):
+    return LevelMapper(k_min, k_max, canonical_scale, canonical_level, eps)
+
+
+def _setup_scales(scales, canonical_scale, canonical_level):
+    lvl_min = -torch.log2(torch.tensor(scales[0], dtype=torch.float32)).item()
+    lvl_max = -torch.log2(torch.tensor(scales[-1], dtype=torch.float32)).item()
+    return initLevelMapper(int(lvl_min), int(lvl_max), canonical_scale=canonical_scale, canonical_level=canonical_level)
+
+
+# ---- pyramid RoI pooling -----------------------------------------------------------------------------------------------------------------------
+class _RoiPool(Function):
+    """(plan, rois [N,R,1+B], level override or None, *maps) -> [N*R, C, ow, oh, od]"""
+
+    @staticmethod
+    def forward(ctx, plan, rois, override, *maps):
+        out, arg = ops.roi_pool_fwd(plan, maps, rois, override)
+        ctx.save_for_backward(arg, rois, *([] if override is None else [override]))
+        ctx.plan = plan
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        arg, rois, *rest = ctx.saved_tensors
+        dmaps = ops.roi_pool_bwd(ctx.plan, dout.contiguous(), arg, rois, rest[0] if rest else None, ctx.needs_input_grad[3:])
+        return (None, None, None, *dmaps)
+
+
+class ROIPool(nn.Module):
+    """The reference's constructor.  forward(feature, rois, original_size=None): feature = one (N, C, W, H, D) fp32 map per level (or the reference's list
+    of per-scene lists of (C, W, H, D) maps); rois = [N, R, 1+6|7], or a list of per-scene [K, 1+6|7] ->  [N*R, C, ow, oh, od] in RoI order for a tensor,
+    the reference's per-scene list for a list.  Differentiable with respect to the maps."""
+
+    def __init__(self, output_size=[1, 1, 1], spatial_scale=[1, 1, 1, 1], enlarge_scale=0.2, is_rotated_bbox=False, feature_extracting_type="pooling", max_res=200,
+                 remap=False, use_cuda=False):
+        super().__init__()
+        if use_cuda:
+            raise NotImplementedError("ROIPool(use_cuda=True) is not built: the launcher never sets it and that path returns features in level order, not RoI order; "
+                                      "rotated.ROIAlignRotated3D is available on its own")
+        if feature_extracting_type != "pooling":
+            raise NotImplementedError(f'ROIPool(feature_extracting_type={feature_extracting_type!r}) is not built; the launcher uses "pooling"')
+        if not 1 <= len(spatial_scale) <= MAX_LEVELS:
+            raise ValueError(f"ROIPool supports 1 to {MAX_LEVELS} levels, got {len(spatial_scale)}")
+        self.output_size = tuple(int(v) for v in output_size)
+        if len(self.output_size) != 3 or min(self.output_size) < 1 or self.output_size[0] * self.output_size[1] * self.output_size[2] > MAX_CELLS:
+            raise ValueError(f"ROIPool: output_size must be three sizes >= 1 with at most {MAX_CELLS} cells, got {output_size}")
+        self.spatial_scale = [float(s) for s in spatial_scale]
+        if min(self.spatial_scale) <= 0:
+            raise ValueError("ROIPool: spatial_scale must be positive")
+        self.enlarge_scale = enlarge_scale
+        self.is_rotated_bbox = bool(is_rotated_bbox)
+        self.feature_extracting_type = feature_extracting_type
+        self.canonical_scale, self.canonical_level = max_res, len(spatial_scale)
+        self.remap, self.use_cuda = bool(remap), False
+        self.bbox_size = 7 if is_rotated_bbox else 6
+        self.map_levels = _setup_scales([1 / s for s in self.spatial_scale], self.canonical_scale, self.canonical_level)
+
+    def enlarge_roi(self, roi):
+        """the reference's arithmetic, out of place: oriented sizes times 1 + enlarge_scale; axis-aligned mid -+ (hi - lo) / 4 (1 + enlarge_scale)"""
+        if self.is_rotated_bbox:
+            return torch.cat([roi[..., :3], roi[..., 3:6] * (1 + self.enlarge_scale), roi[..., 6:]], -1)
+        extent, offset = (roi[..., 3:] - roi[..., :3]) / 2 * (1 + self.enlarge_scale), (roi[..., 3:] + roi[..., :3]) / 2
+        return torch.cat([-0.5 * extent + offset, 0.5 * extent + offset], -1)
+
+    def _maps(self, feature):
+        if len(feature) and isinstance(feature[0], (list, tuple)):
+            feature = [torch.stack([scene[k] for scene in feature]) for k in range(len(feature[0]))]
+        feature = list(feature)
+        if len(feature) != len(self.spatial_scale):
+            raise ValueError(f"ROIPool: {len(self.spatial_scale)} levels but {len(feature)} feature maps")
+        _check("ROIPool", *feature)
+        N, C = feature[0].shape[:2]
+        if any(f.dim() != 5 or tuple(f.shape[:2]) != (N, C) for f in feature):
+            raise ValueError("ROIPool: feature maps must be (N, C, W, H, D) per level with the same N and C")
+        if not 1 <= N <= MAX_SCENES:
+            raise ValueError(f"ROIPool supports 1 to {MAX_SCENES} scenes, got {N}")
+        return [f.contiguous() for f in feature]
+
+    def forward(self, feature, rois, original_size=None):
+        maps = self._maps(feature)
+        N, B = maps[0].shape[0], self.bbox_size
+        ks = None
+        if not isinstance(rois, torch.Tensor):
+            _check("ROIPool", *rois)
+            ks = [r.shape[0] for r in rois]
+            R = max(max(ks), 1)
+            rois = torch.stack([F.pad(r.detach().reshape(-1, 1 + B), (0, 0, 0, R - k)) for r, k in zip(rois, ks)])
+        _check("ROIPool", rois)
+        if rois.dim() != 3 or rois.shape[0] != N or rois.shape[2] != 1 + B:
+            raise ValueError(f"ROIPool: rois must be [N = {N}, R, {1 + B}], got {tuple(rois.shape)}")
+        if not 1 <= rois.shape[1] <= MAX_ROWS:
+            raise ValueError(f"ROIPool supports 1 to {MAX_ROWS} RoIs per scene, got {rois.shape[1]}")
+        rois = rois.detach().contiguous()
+        override = self.map_levels.levels32(rois[..., 1:]).reshape(-1).contiguous() if self.remap else None
+        plan = ops.RoiPoolPlan(maps, self.spatial_scale, self.output_size, 1 + self.enlarge_scale, B)
+        out = _RoiPool.apply(plan, rois, override, *maps)
+        if ks is None:
+            return out
+        R = rois.shape[1]
+        return [out[i * R:i * R + k] for i, k in enumerate(ks)]
+
+
+# ---- box head --------------------------------------------------------------------------------------------------------------------------------
+class RCNN(nn.Module):
+    """Two optional 3x3x3 conv + ReLU layers, then two Linear layers on the flattened (or mean-pooled) volume -> (pred_bbox_delta, pred_scores).
+    state_dict keys: layer.0, layer.2, RCNN_bbox_pred, RCNN_cls_score.  `block` is accepted and unused, as in the reference."""
+
+    def __init__(self, input_dim, block, n_classes, input_size, is_add_layer=False, is_rotated_bbox=False, is_flatten=True):
+        super().__init__()
+        self.in_planes, self.n_classes = input_dim, n_classes
+        self.is_rotated_bbox, self.is_flatten = is_rotated_bbox, is_flatten
+        self.reg_dim = 7 if is_rotated_bbox else 6
+        self.layer = None
+        if is_add_layer:
+            self.layer = nn.Sequential(nn.Conv3d(input_dim, input_dim, kernel_size=3, padding=1), nn.ReLU(inplace=True),
+                                       nn.Conv3d(input_dim, input_dim, kernel_size=3, padding=1), nn.ReLU(inplace=True))
+        width = input_dim
+        if is_flatten:
+            self.flatten_size = input_size[0] * input_size[1] * input_size[2]
+            width = input_dim * self.flatten_size
+        self.RCNN_bbox_pred = nn.Linear(width, self.reg_dim)
+        self.RCNN_cls_score = nn.Linear(width, n_classes)
+
+    def forward(self, pooling_feature):
+        x = pooling_feature if self.layer is None else self.layer(pooling_feature)
+        x = x.reshape(x.size(0), -1) if self.is_flatten else x.mean((-1, -2, -3))
+        return self.RCNN_bbox_pred(x), self.RCNN_cls_score(x)
+
+
+# ---- losses and decode -----------------------------------------------------------------------------------------------------------------------
+class _RoiHeadLoss(Function):
+    @staticmethod
+    def forward(ctx, ncols, scores, deltas, labels, rois, gt_rois):
+        scores, deltas = scores.contiguous(), deltas.contiguous()
+        scalars, targets = ops.roi_loss_fwd(ncols, scores, deltas, labels, rois, gt_rois)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(scores, deltas, labels, targets, scalars)
+        ctx.ncols = ncols
+        ctx.mark_non_differentiable(targets)
+        return scalars[0], scalars[1], targets
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_obj, g_reg, _):
+        scores, deltas, labels, targets, scalars = ctx.saved_tensors
+        if (g_obj is None and g_reg is None) or not any(ctx.needs_input_grad[1:3]):
+            return (None,) * 6
+        gs = [g if g is None else g.contiguous() for g in (g_obj, g_reg)]
+        dscores, ddeltas = ops.roi_loss_bwd(ctx.ncols, scores, deltas, labels, targets, scalars, gs[0], gs[1])
+        return (None, dscores, ddeltas, None, None, None)
+
+
+def _rows(name, what, t, M, cols):
+    _check(name, t)
+    t = t.detach().reshape(-1, t.shape[-1]) if t.dim() > 1 else t.detach().reshape(-1)
+    if t.shape[0] != M or (t.dim() == 2 and t.shape[1] not in cols):
+        raise ValueError(f"{name}: {what} must have {M} rows and {' or '.join(str(c) for c in cols)} columns, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def roi_head_loss(pred_scores, pred_bbox_deltas, labels, rois, gt_rois, return_targets=False):
+    """pred_scores [M,n_classes], pred_bbox_deltas [M,6|7], labels [M] (or [N,R]) fp32, rois [M,6|7] or [M,1+6|7], gt_rois [M,6|7] ->
+    {"loss_objectness": mean cross-entropy over rows with label >= 0, "loss_rpn_box_reg": smooth-L1 (beta 1/9) summed over rows with label > 0 / their count}
+    (and the regression targets [M,6|7] with return_targets).  Gradients go to the two head outputs."""
+    name = "roi_head_loss"
+    _check(name, pred_scores, pred_bbox_deltas)
+    if pred_scores.dim() != 2 or pred_bbox_deltas.dim() != 2 or pred_bbox_deltas.shape[1] not in (6, 7) or pred_scores.shape[0] != pred_bbox_deltas.shape[0]:
+        raise ValueError(f"{name}: pred_scores [M, n_classes] and pred_bbox_deltas [M, 6|7], got {tuple(pred_scores.shape)}, {tuple(pred_bbox_deltas.shape)}")
+    M, B = pred_bbox_deltas.shape
+    if M < 1 or not 1 <= pred_scores.shape[1] <= MAX_CLASSES:
+        raise ValueError(f"{name}: at least one row and 1 to {MAX_CLASSES} classes, got {M} rows, {pred_scores.shape[1]} classes")
+    _check(name, labels)
+    labels, rois, gt_rois = _rows(name, "labels", labels.reshape(-1), M, ()), _rows(name, "rois", rois, M, (B, B + 1)), _rows(name, "gt_rois", gt_rois, M, (B,))
+    if labels.dim() != 1 or rois.dim() != 2 or gt_rois.dim() != 2:
+        raise ValueError(f"{name}: labels [M], rois [M, {B}|{B + 1}], gt_rois [M, {B}]")
+    obj, reg, targets = _RoiHeadLoss.apply(B, pred_scores, pred_bbox_deltas, labels, rois, gt_rois)
+    loss = {"loss_objectness": obj, "loss_rpn_box_reg": reg}
+    return (loss, targets) if return_targets else loss
+
+
+def roi_decode(pred_bbox_deltas, rois):
+    """pred_bbox_deltas [M,6|7], rois [M,6|7] or [M,1+6|7] -> boxes [M,6|7]: dw, dh, dd clipped at log 2000, the angle wrapped into (-pi/2, pi/2]; no gradient"""
+    name = "roi_decode"
+    _check(name, pred_bbox_deltas)
+    if pred_bbox_deltas.dim() != 2 or pred_bbox_deltas.shape[1] not in (6, 7):
+        raise ValueError(f"{name}: pred_bbox_deltas must be [M, 6|7], got {tuple(pred_bbox_deltas.shape)}")
+    M, B = pred_bbox_deltas.shape
+    rois = _rows(name, "rois", rois, M, (B, B + 1))
+    with torch.no_grad():
+        return ops.roi_decode(B, pred_bbox_deltas.detach().contiguous(), rois)
+
+
+class RotatedCoder:
+    """RotatedCoder of the reference: encode_single(gt_rois, ex_drois) and decode_single(deltas, ex_drois) on [M, 7] boxes; no gradient"""
+    ncols = 7
+
+    def __init__(self, bbox_xform_clip=math.log(2000.0)):
+        if abs(bbox_xform_clip - math.log(2000.0)) > 1e-6:
+            raise NotImplementedError("the decode kernel clips at log(2000), the only value the reference uses")
+        self.bbox_xform_clip = bbox_xform_clip
+
+    def encode_single(self, gt_rois, ex_rois):
+        _check(type(self).__name__, gt_rois, ex_rois)
+        M = gt_rois.shape[0]
+        gt, ex = _rows("encode_single", "gt_rois", gt_rois, M, (self.ncols,)), _rows("encode_single", "ex_rois", ex_rois, M, (self.ncols,))
+        # The encode is part of the loss forward, which writes the targets of every valid row (0 <= label < n_classes, roi_head.hip's header) and zeros
+        # elsewhere: one score column and label 0 make every row valid.  If that rule changes, this must change with it; test_decode_clip_and_angle_wrap
+        # compares the result with the restatement's encode.
+        zeros = torch.zeros((M, self.ncols), dtype=torch.float32, device=gt.device)
+        with torch.no_grad():
+            return ops.roi_loss_fwd(self.ncols, zeros[:, :1].contiguous(), zeros, zeros[:, 0].contiguous(), ex, gt)[1]
+
+    def decode_single(self, deltas, ex_rois):
+        return roi_decode(deltas, ex_rois)
+
+
+class AABBCoder(RotatedCoder):
+    """AABBCoder of the reference on [M, 6] boxes"""
+    ncols = 6
+
+
+# ---- the model -------------------------------------------------------------------------------------------------------------------------------
+class Classification_Model(nn.Module):
+    """The reference's constructor and forward(rois, gt_bboxes, gt_bbox_labels, features, is_sample, is_reg) ->
+    ([per-scene RoIs (or, is_reg, decoded proposals), gt_labels], per-scene class probabilities, {"loss_objectness", "loss_rpn_box_reg"} (0 in evaluation)).
+    rois: per scene [K, 1+6|7], or the dense triple (boxes, levels, counts) of rpn_proposals_dense.  features: one (N, C, W, H, D) map per level (or per-scene
+    lists); with a feature_extractor, the per-scene raw grids [[grid], ...], which are zero-padded to a common size, stacked and run through it."""
+
+    def __init__(self, feature_extractor, sample_model, pooling_model, RCNN_model, n_classes=2, is_training=True, batch_size=20, is_rotated_bbox=False):
+        super().__init__()
+        self.batch_size = batch_size
+        self.feature_extractor, self.sample_model, self.pooling_model, self.RCNN_model = feature_extractor, sample_model, pooling_model, RCNN_model
+        self.num_class = n_classes
+        self.score_thresh = 0.7
+        self.is_training, self.is_rotated_bbox = is_training, is_rotated_bbox
+        self.reg_dim = 7 if is_rotated_bbox else 6
+        self.box_coder = RotatedCoder() if is_rotated_bbox else AABBCoder()
+
+    def transform(self, meshes):
+        if len(meshes) > 1:
+            target = np.max([m.shape for m in meshes], axis=0)
+            meshes = [F.pad(m, (0, int(target[-1] - m.shape[-1]), 0, int(target[-2] - m.shape[-2]), 0, int(target[-3] - m.shape[-3]))) for m in meshes]
+        return meshes
+
+    def compute_loss(self, pred_scores, pred_bbox_deltas, gt_labels, rois, gt_rois):
+        """as the reference's, but from the RoIs and their matched boxes: the encode is part of the fused loss"""
+        return roi_head_loss(pred_scores, pred_bbox_deltas, gt_labels, rois, gt_rois)
+
+    def forward(self, rois, gt_bboxes, gt_bbox_labels, features, is_sample=True, is_reg=False, keep=None, keep_counts=None):
+        original_size = []
+        if self.feature_extractor is not None:
+            flat = self.transform([f[0] for f in features])
+            original_size = [f.shape[1:] for f in flat]
+            features = [f.to(torch.float32) for f in self.feature_extractor(torch.stack(flat, dim=0))]
+        dense = isinstance(rois, tuple)
+        if dense:
+            boxes, levels, counts = rois
+            ks = None
+        else:
+            boxes, levels, counts, ks = _pack("Classification_Model", rois, self.reg_dim)
+        labels, sample_rois, gt_rois, _, _ = self.sample_model.forward_dense(boxes, levels, counts, gt_bboxes, gt_bbox_labels, is_sample, keep, keep_counts)
+        N, R = labels.shape
+        pooled = self.pooling_model(features, sample_rois, original_size)
+        if self.pooling_model.is_rotated_bbox and not self.pooling_model.remap:           # the reference's enlarge_roi wrote into these (module header)
+            sample_rois = torch.cat([sample_rois[..., :1], self.pooling_model.enlarge_roi(sample_rois[..., 1:])], -1)
+        pred_bbox_deltas, pred_scores = self.RCNN_model(pooled)
+        cls_prob = F.softmax(pred_scores, 1)
+        flat_rois = sample_rois.reshape(N * R, -1)
+        loss = 0.
+        if is_sample:
+            ks = [R] * N
+            loss = roi_head_loss(pred_scores, pred_bbox_deltas, labels.reshape(-1), flat_rois, gt_rois.reshape(N * R, -1))
+            gt_labels = labels
+        else:
+            if ks is None:
+                ks = counts.tolist()                  # the one synchronisation
+            gt_labels = [labels[i, :k] for i, k in enumerate(ks)]
+        out_boxes = roi_decode(pred_bbox_deltas, flat_rois).reshape(N, R, -1) if is_reg else sample_rois[..., 1:]
+        return [[out_boxes[i, :k] for i, k in enumerate(ks)], gt_labels], [cls_prob[i * R:i * R + k] for i, k in enumerate(ks)], loss

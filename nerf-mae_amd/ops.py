@@ -1799,3 +1799,107 @@ def rpn_post_nms(post, ncols, pre_boxes, pre_scores, pre_index, sorted_keys, ord
     lib().call("nmh_rpn_post_nms", plan.L, plan.dims, plan.N, ncols, post.top_n, pre_boxes, pre_scores, pre_index, sorted_keys, order, pre_counts, nms_thresh,
                int(post_nms_top_n), mask, keep, boxes, scores, levels, index, counts, _st())
     return boxes, scores, levels, index, counts
+
+
+# ---- RoI stage of the two-stage detector: proposal targets, pyramid RoI pooling, box-head losses, decode (csrc/roi_head.hip) -----------------------
+ROI_MAX_GRID = 1024            # points per axis of one oriented RoI's sampling grid; a larger grid is cut to this
+ROI_MAX_CELLS = 4096           # ow * oh * od
+ROI_MAX_CLASSES = 1024
+ROI_MAX_ROWS = 1 << 24         # proposals (cap) and sampled rows (R) per scene
+
+
+def roi_targets(boxes, levels, counts, gt, gt_labels, offsets, R, want_fg, fg, bg, is_sample, rng_state=None, keep=None, counts2=None):
+    """boxes [N,cap,6|7], levels [N,cap] int32, counts [N] int32, gt [G,6|7] with gt_labels [G] fp32 and host offsets [N+1] ->
+    (labels [N,R], rois [N,R,1+6|7], gt_rois [N,R,6|7], keep [N,R] int32, counts2 [N,2] int32 or None, max_iou [N,cap], arg [N,cap] int32).
+    Sampling takes rng_state (int64 [2]: seed, counter; the counter advances) or the caller's keep and counts2; evaluation has R = cap."""
+    _chk(boxes, levels, counts, gt, gt_labels, rng_state, keep, counts2)
+    N, cap, B = boxes.shape
+    dev = boxes.device
+    miou = torch.empty((N, cap), dtype=torch.float32, device=dev)
+    arg = torch.empty((N, cap), dtype=torch.int32, device=dev)
+    lists = None
+    if is_sample:
+        if rng_state is not None:
+            lists = torch.empty((N, 2, cap), dtype=torch.int32, device=dev)
+            keep = torch.empty((N, R), dtype=torch.int32, device=dev)
+            counts2 = torch.empty((N, 2), dtype=torch.int32, device=dev)
+        else:
+            keep, counts2 = keep.clone(), counts2.contiguous()
+    else:
+        keep, counts2 = torch.empty((N, R), dtype=torch.int32, device=dev), None
+    labels = torch.empty((N, R), dtype=torch.float32, device=dev)
+    rois = torch.empty((N, R, 1 + B), dtype=torch.float32, device=dev)
+    gt_rois = torch.empty((N, R, B), dtype=torch.float32, device=dev)
+    offs = (ctypes.c_int * (N + 1))(*offsets)
+    lib().call("nmh_roi_targets", N, cap, B, R, int(bool(is_sample)), boxes, levels, counts, gt if gt.numel() else None, gt_labels if gt_labels.numel() else None, offs, want_fg, fg, bg,
+               rng_state, miou, arg, lists, keep, counts2, labels, rois, gt_rois, _st())
+    return labels, rois, gt_rois, keep, counts2, miou, arg
+
+
+def roi_level_map(boxes, ncols, k_min, k_max, canonical_scale, canonical_level, eps):
+    """boxes [M, ncols | 1+ncols] fp32 (the box in the last ncols columns) -> levels [M] int32"""
+    _chk(boxes)
+    out = torch.empty((boxes.shape[0],), dtype=torch.int32, device=boxes.device)
+    if boxes.shape[0]:
+        lib().call("nmh_roi_level_map", boxes.shape[0], boxes, boxes.shape[1], ncols, k_min, k_max, canonical_scale, canonical_level, eps, out, _st())
+    return out
+
+
+class RoiPoolPlan:
+    """the host-side level table of the pooling entries: maps (N, C, W, H, D) per level, their scales, the output size and 1 + enlarge_scale"""
+
+    def __init__(self, maps, scales, output_size, enlarge, ncols):
+        self.L, self.N, self.C, self.ncols = len(maps), maps[0].shape[0], maps[0].shape[1], ncols
+        self.shapes = [tuple(m.shape) for m in maps]
+        self.dims = (ctypes.c_int * (3 * self.L))(*[int(v) for m in maps for v in m.shape[2:]])
+        self.scales = (ctypes.c_float * self.L)(*[float(s) for s in scales])
+        self.out = tuple(int(v) for v in output_size)
+        self.enlarge = float(enlarge)
+
+    def table(self, tensors):
+        return (ctypes.c_void_p * self.L)(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def roi_pool_fwd(plan, maps, rois, level_override):
+    """rois [N,R,1+6|7] -> (out [N*R,C,ow,oh,od], argmax int32 of the same shape)"""
+    _chk(*maps, rois, level_override)
+    R = rois.shape[1]
+    out = torch.empty((plan.N * R, plan.C, *plan.out), dtype=torch.float32, device=rois.device)
+    arg = torch.empty(out.shape, dtype=torch.int32, device=rois.device)
+    lib().call("nmh_roi_pool_fwd", plan.L, plan.dims, plan.scales, plan.N, plan.C, R, plan.ncols, *plan.out, plan.enlarge, plan.table(maps), rois, level_override, out, arg, _st())
+    return out, arg
+
+
+def roi_pool_bwd(plan, dout, arg, rois, level_override, need):
+    """-> per level the gradient of the map (zeroed here, then accumulated with fp32 atomics), None where need[k] is False"""
+    dmaps = [torch.zeros(s, dtype=torch.float32, device=dout.device) if n else None for s, n in zip(plan.shapes, need)]
+    lib().call("nmh_roi_pool_bwd", plan.L, plan.dims, plan.scales, plan.N, plan.C, rois.shape[1], plan.ncols, *plan.out, plan.enlarge, dout, arg, rois, level_override,
+               plan.table(dmaps), _st())
+    return dmaps
+
+
+def roi_loss_fwd(ncols, scores, deltas, labels, rois, gt_rois):
+    """-> (scalars [4] = (loss_objectness, loss_rpn_box_reg, valid rows, positive rows), targets [M,ncols])"""
+    _chk(scores, deltas, labels, rois, gt_rois)
+    M, dev = scores.shape[0], scores.device
+    nb = lib().cdll.nmh_roi_loss_blocks(M)
+    partials = torch.empty((4 * nb,), dtype=torch.float32, device=dev)
+    scalars = torch.empty((4,), dtype=torch.float32, device=dev)
+    targets = torch.empty((M, ncols), dtype=torch.float32, device=dev)
+    lib().call("nmh_roi_loss_fwd", M, scores.shape[1], ncols, scores, deltas, labels, rois, rois.shape[-1], gt_rois, targets, partials, scalars, _st())
+    return scalars, targets
+
+
+def roi_loss_bwd(ncols, scores, deltas, labels, targets, scalars, g_obj, g_reg):
+    dscores, ddeltas = torch.empty_like(scores), torch.empty_like(deltas)
+    lib().call("nmh_roi_loss_bwd", scores.shape[0], scores.shape[1], ncols, scores, deltas, labels, targets, scalars, g_obj, g_reg, dscores, ddeltas, _st())
+    return dscores, ddeltas
+
+
+def roi_decode(ncols, deltas, rois):
+    """deltas [M,ncols], rois [M, ncols | 1+ncols] -> boxes [M,ncols]"""
+    _chk(deltas, rois)
+    out = torch.empty_like(deltas)
+    if deltas.shape[0]:
+        lib().call("nmh_roi_decode", deltas.shape[0], ncols, deltas, rois, rois.shape[-1], out, _st())
+    return out
