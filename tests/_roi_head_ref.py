@@ -1,11 +1,14 @@
 """Float64 restatement of the RoI stage (nerf_mae_amd/detector.py over csrc/roi_head.hip), written from the semantics in that file's header, and the seeded
 inputs of its tests.  Checked against the recorded reference (tests/golden/g22_roi_head.npz, tools/gen_golden_roi_head.py) in tests/test_roi_head_ref_cpu.py.
 
-The sampler is not restated: every function takes the kept indices.  Next to its results each function returns the smallest margin of its discrete decisions,
+The matching, pooling and loss functions take the kept indices; the sampler that draws them is restated on its own, exactly, in Python integers (sample).
+Next to its results each function returns the smallest margin of its discrete decisions,
 so that a test can assert that fp32 arithmetic cannot flip one: IoU against the two thresholds ("iou_fg", "iou_bg"), top-two IoU gap per RoI ("iou_top2"),
 distance of every floored or ceiled quantity from an integer ("floor"; quantities that are integers exactly, such as the points of an integer-placed RoI with
 theta = 0, are exact in fp32 as well and do not count), top-two gap inside each pooling cell ("cell_gap", the padding zero included), the level mapper's floor
-("level").  "inside": every oriented sampling point lies in its map and every axis-aligned crop is unclamped."""
+("level").  "inside": every oriented sampling point lies in its map and every axis-aligned crop is unclamped.  At realistic sizes (thousands of proposals)
+no scene keeps 1e-3 on every row, so targets also returns the three IoU margins per row (margins["rows"]): a row is decided if all three are at least MARGIN, and
+targets(alt_arg / alt_label) gives the other outcome that a near-tie allows on the rows that are not."""
 import math
 
 import numpy as np
@@ -68,46 +71,135 @@ def make_scene(seed, rotated, N=2, K=24, G=4):
 
 
 # ---- proposal targets ------------------------------------------------------------------------------------------------------------------------
-def match(rois, gt):
-    """rois [K, 6|7], gt [G, 6|7] -> (max IoU [K], arg [K] with ties to the lowest index, top-two gap)"""
+def _ious(rois, gt):
+    if rois.shape[0] == 0 or gt.shape[0] == 0:
+        return torch.zeros((rois.shape[0], gt.shape[0]), dtype=F64)
     iou = pairwise(rois.to(F64), gt.to(F64))
-    iou = torch.where(iou > 0, iou, torch.zeros_like(iou))
+    return torch.where(iou > 0, iou, torch.zeros_like(iou))
+
+
+def _match(iou):
+    if iou.shape[1] == 0:                                   # a scene without boxes: IoU 0 with "box 0"
+        return torch.zeros(iou.shape[0], dtype=F64), torch.zeros(iou.shape[0], dtype=torch.int64), float("inf")
     best, arg = iou.max(1)
     arg = (iou == best[:, None]).to(torch.int64).argmax(1)
     gap = float("inf")
-    if iou.shape[1] > 1:
+    if iou.shape[1] > 1 and iou.shape[0] > 0:
         top = iou.topk(2, dim=1).values
         gap = float((top[:, 0] - top[:, 1])[top[:, 0] > 0].min()) if bool((top[:, 0] > 0).any()) else float("inf")
     return best, arg, gap
 
 
-def targets(all_rois, gt_boxes, gt_labels, fg=FG, bg=BG, keep=None, n_fg=None):
+def match(rois, gt):
+    """rois [K, 6|7], gt [G, 6|7] -> (max IoU [K], arg [K] with ties to the lowest index, top-two gap)"""
+    return _match(_ious(rois, gt))
+
+
+def row_margins(iou, fg=FG, bg=BG):
+    """iou [K, G] -> per row: best, arg, arg2 (the runner-up, ties to the lowest index; arg where there is none), d_fg, d_bg = |best - threshold|, gap = best -
+    runner-up (inf where best is 0, an exact tie that goes to box 0 in fp32 as well, or where G < 2), decided = all three >= MARGIN"""
+    K, G = iou.shape
+    best, arg, _ = _match(iou)
+    arg2, gap = arg.clone(), torch.full((K,), float("inf"), dtype=F64)
+    if G > 1 and K > 0:
+        rest = iou.clone()
+        rest[torch.arange(K), arg] = -1.0
+        second, _ = rest.max(1)
+        arg2 = (rest == second[:, None]).to(torch.int64).argmax(1)
+        gap = torch.where(best > 0, best - second, gap)
+    d_fg, d_bg = (best - fg).abs(), (best - bg).abs()
+    return dict(best=best, arg=arg, arg2=arg2, d_fg=d_fg, d_bg=d_bg, gap=gap, decided=(d_fg >= MARGIN) & (d_bg >= MARGIN) & (gap >= MARGIN))
+
+
+def targets(all_rois, gt_boxes, gt_labels, fg=FG, bg=BG, keep=None, n_fg=None, rows=None, alt_arg=False, alt_label=False):
     """all_rois per scene [K, 1+6|7]; keep: per scene the kept indices (foreground slots first, n_fg[i] of them; -1: none) or None for evaluation ->
-    (labels, rois, gt_rois: per scene, float64), margins"""
+    (labels, rois, gt_rois: per scene, float64), margins.  A scene may have no RoIs or no boxes (IoU 0, zero gt_rois, label 0).  rows: margins["rows"] of an
+    earlier call on the same inputs (the IoUs are not formed again).  alt_arg: rows whose top-two gap is below MARGIN take the runner-up box; alt_label
+    (evaluation): rows within MARGIN of fg take the other label."""
     m = dict(iou_fg=float("inf"), iou_bg=float("inf"), iou_top2=float("inf"))
-    L, Ro, Gr, cand = [], [], [], []
+    L, Ro, Gr, cand, per_row = [], [], [], [], []
     for i, (r, g, gl) in enumerate(zip(all_rois, gt_boxes, gt_labels)):
         r, g = r.to(F64), g.to(F64)
-        best, arg, gap = match(r[:, 1:], g)
-        m["iou_fg"] = min(m["iou_fg"], float((best - fg).abs().min()))
-        m["iou_bg"] = min(m["iou_bg"], float((best - bg).abs().min()))
-        m["iou_top2"] = min(m["iou_top2"], gap)
+        rm = row_margins(_ious(r[:, 1:], g), fg, bg) if rows is None else rows[i]
+        per_row.append(rm)
+        best, arg = rm["best"], rm["arg"]
+        if r.shape[0]:
+            m["iou_fg"] = min(m["iou_fg"], float(rm["d_fg"].min()))
+            m["iou_bg"] = min(m["iou_bg"], float(rm["d_bg"].min()))
+            m["iou_top2"] = min(m["iou_top2"], float(rm["gap"][best > 0].min()) if bool((best > 0).any()) else float("inf"))
+        if alt_arg:
+            arg = torch.where(rm["gap"] < MARGIN, rm["arg2"], arg)
         cand.append((torch.nonzero(best >= fg).view(-1), torch.nonzero((best < bg) & ~(best >= fg)).view(-1)))
+        gbox = g[arg] if g.shape[0] else torch.zeros((r.shape[0], r.shape[1] - 1), dtype=F64)
+        glab = gl.to(F64)[arg] if g.shape[0] else torch.zeros(r.shape[0], dtype=F64)
         if keep is None:
-            L.append((best >= fg).to(F64))
+            lab = best >= fg
+            L.append((lab ^ (rm["d_fg"] < MARGIN) if alt_label else lab).to(F64))
             Ro.append(r)
-            Gr.append(g[arg])
+            Gr.append(gbox)
             continue
         k = torch.as_tensor(keep[i], dtype=torch.int64)
         ok = k >= 0
         kk = k.clamp_min(0)
-        lab = gl.to(F64)[arg[kk]]
+        if r.shape[0] == 0:
+            L.append(torch.full((k.numel(),), -1.0, dtype=F64))
+            Ro.append(torch.zeros((k.numel(), r.shape[1]), dtype=F64))
+            Gr.append(torch.zeros((k.numel(), r.shape[1] - 1), dtype=F64))
+            continue
+        lab = glab[kk]
         lab[n_fg[i]:] = 0
         L.append(torch.where(ok, lab, torch.full_like(lab, -1.0)))
         Ro.append(r[kk] * ok[:, None])
-        Gr.append(g[arg[kk]] * ok[:, None])
+        Gr.append(gbox[kk] * ok[:, None])
     m["candidates"] = cand
+    m["rows"] = per_row
     return L, Ro, Gr, m
+
+
+# ---- the sampler, in Python integers (csrc/roi_head.hip's header, csrc/rpn_shared.hpp) ---------------------------------------------------------
+_M64 = (1 << 64) - 1
+_PHI, _STEP, _SECOND = 0x9E3779B97F4A7C15, 0xD1342543DE82EF95, 0x5851F42D4C957F2D
+
+
+def mix64(x):
+    """the splitmix64 finaliser on a 64-bit unsigned value"""
+    x ^= x >> 30
+    x = x * 0xBF58476D1CE4E5B9 & _M64
+    x ^= x >> 27
+    x = x * 0x94D049BB133111EB & _M64
+    return x ^ (x >> 31)
+
+
+def sample_stream(seed, counter, scene):
+    return mix64(mix64((seed + _PHI * (counter + 1)) & _M64) ^ (((scene + 1) << 40) & _M64))
+
+
+def sample_key(stream, idx):
+    """the complemented hash of one proposal: the largest keys are the smallest hashes"""
+    return ~(mix64((stream + idx * _STEP) & _M64) >> 32) & 0xFFFFFFFF
+
+
+def sample_draw(stream2, j, cnt):
+    """slot j's draw, uniform in 0 .. cnt-1: floor(h cnt / 2^32)"""
+    return ((mix64((stream2 + j * _STEP) & _M64) >> 32) * cnt) >> 32
+
+
+def sample(fg, bg, R, want_fg, seed, counter, scene):
+    """fg, bg: the scene's candidate indices in index order -> (keep [R], (foreground slots, background slots), positions: the list position of every draw
+    with replacement, per slot, None in the slots filled without replacement)"""
+    fg, bg = [int(v) for v in fg], [int(v) for v in bg]
+    stream = sample_stream(seed, counter, scene)
+    stream2 = mix64(stream ^ _SECOND)
+    if not fg and not bg:
+        return [-1] * R, (0, 0), [None] * R
+    if not fg or not bg:
+        lst = fg or bg
+        pos = [sample_draw(stream2, j, len(lst)) for j in range(R)]
+        return [lst[p] for p in pos], ((R, 0) if fg else (0, R)), pos
+    nf = min(max(want_fg, 0), len(fg), R)
+    chosen = sorted(sorted(fg, key=lambda q: (-sample_key(stream, q), q))[:nf])          # the nf largest keys, ties to the lower index, written in index order
+    pos = [sample_draw(stream2, j, len(bg)) for j in range(nf, R)]
+    return chosen + [bg[p] for p in pos], (nf, R - nf), [None] * nf + pos
 
 
 def level_map(boxes, k_min, k_max, s0, lvl0, eps=1e-6):
@@ -286,10 +378,168 @@ def input_sums(rois, gts, maps):
     return np.array([sum(t.double().sum().item() for t in ts) for ts in (rois, gts, maps)], dtype=np.float64)
 
 
+# ---- targets and sampling at real extents ------------------------------------------------------------------------------------------------------
+# Six scenes in one dense triple of cap 2500.  counts: a full cap, one past a 1024-lane chunk of the sampler, exactly a chunk, a single row, an empty scene,
+# one past two chunks.  G: across the 64-box stage of the matching twice (130), one past it, on it, none, one, just past it.  The scene without boxes has one
+# proposal, so that its IoU 0, box 0 and zero gt_rois are compared; the scene without proposals has one box.
+BIG = dict(cap=2500, counts=(2500, 1025, 1024, 1, 0, 2049), G=(130, 65, 64, 0, 1, 70), R=1500, max_undecided=0.03)
+BIG_SEED = {False: 0, True: 0}                                              # every scene's undecided share <= 3 %: tests/test_roi_head_ref_cpu.py
+
+
+def big_case(rotated, seed=None):
+    """-> dict(rois, gts, labs: per scene, rois [counts[i], 1+6|7]; boxes [N, cap, 6|7], levels [N, cap] int32: the dense form, rows past counts[i] hold
+    garbage (boxes 5 .. 6, level 7); counts).  Labels cycle through 1 .. 5 so that a wrong matched box shows in the label."""
+    seed = BIG_SEED[rotated] if seed is None else seed
+    B, cap = (7 if rotated else 6), BIG["cap"]
+    g = torch.Generator().manual_seed(4242 + seed)
+    rois, gts, labs = [], [], []
+    boxes, levels = 5 + torch.rand((len(BIG["counts"]), cap, B), generator=g, dtype=torch.float32), torch.full((len(BIG["counts"]), cap), 7, dtype=torch.int32)
+    for i, (k, ng) in enumerate(zip(BIG["counts"], BIG["G"])):
+        r, gt, _ = make_scene(100 * seed + i, rotated, N=1, K=max(k, 1), G=max(ng, 1))
+        rois.append(r[0][:k])
+        gts.append(gt[0][:ng])
+        labs.append((1 + torch.arange(ng) % 5).to(torch.float32))
+        boxes[i, :k], levels[i, :k] = rois[i][:, 1:], rois[i][:, 0].to(torch.int32)
+    return dict(rois=rois, gts=gts, labs=labs, boxes=boxes, levels=levels, counts=list(BIG["counts"]))
+
+
+def big_keep(candidates, R=None, seed=0):
+    """kept rows from the restatement's candidates: up to R / 2 foreground rows (a seeded subset in index order), background rows with replacement; one class
+    only: every slot from it; neither: -1 -> (keep [N, R] int64, n_fg)"""
+    R = BIG["R"] if R is None else R
+    g = torch.Generator().manual_seed(99 + seed)
+    keep, n_fg = [], []
+    for f, b in candidates:
+        draw = lambda lst, n: lst[torch.randint(lst.numel(), (n,), generator=g)]          # noqa: E731
+        if f.numel() and b.numel():
+            nf = min(R // 2, f.numel())
+            keep.append(torch.cat([f[torch.randperm(f.numel(), generator=g)[:nf]].sort().values, draw(b, R - nf)]))
+        elif f.numel() or b.numel():
+            nf = R if f.numel() else 0
+            keep.append(draw(f if f.numel() else b, R))
+        else:
+            nf = 0
+            keep.append(torch.full((R,), -1, dtype=torch.int64))
+        n_fg.append(nf)
+    return torch.stack(keep), n_fg
+
+
+# The sampling scenes: one box and proposals that are copies of it (IoU 1), disjoint (IoU 0) or half overlapping (IoU 1/3: neither class), so that every row
+# is decided by construction.  (foreground, background, neither) per scene: all three chunks of the sampler with a cut (want_fg below the foreground count)
+# and more than 1024 background candidates; foreground only; background only; neither; fewer foreground rows than wanted (no cut); no proposals at all.
+SAMPLER = dict(cap=2500, scenes=((900, 1300, 300), (1500, 0, 600), (0, 800, 230), (0, 0, 300), (20, 2000, 280), (0, 0, 0)), runs=((64, 32), (1500, 750)), seed=11, counters=(0, 5))
+
+
+def sampler_case():
+    """-> dict(boxes [N, cap, 6], levels, counts, gts, labs, kind: per scene [count] 0 / 1 / 2); rows past the counts are copies of the box (they would be
+    foreground if read) with level 7"""
+    cap, N = SAMPLER["cap"], len(SAMPLER["scenes"])
+    gt = torch.tensor([[0.0, 0, 0, 4, 4, 4]])
+    proto = torch.tensor([[0.0, 0, 0, 4, 4, 4], [10.0, 10, 10, 14, 14, 14], [2.0, 0, 0, 6, 4, 4]])
+    boxes, levels = proto[0].repeat(N, cap, 1), torch.full((N, cap), 7, dtype=torch.int32)
+    kinds, counts = [], []
+    for i, ns in enumerate(SAMPLER["scenes"]):
+        kind = torch.repeat_interleave(torch.arange(3), torch.tensor(ns))
+        kind = kind[torch.randperm(kind.numel(), generator=torch.Generator().manual_seed(50 + i))]
+        boxes[i, :kind.numel()], levels[i, :kind.numel()] = proto[kind], (torch.arange(kind.numel()) % 3).to(torch.int32)
+        kinds.append(kind)
+        counts.append(kind.numel())
+    return dict(boxes=boxes, levels=levels, counts=counts, gts=[gt] * N, labs=[torch.full((1,), 3.0)] * N, kind=kinds)
+
+
+def sampler_rois(case):
+    return [torch.cat([case["levels"][i, :k, None].float(), case["boxes"][i, :k]], 1) for i, k in enumerate(case["counts"])]
+
+
+# ---- the two stages joined ---------------------------------------------------------------------------------------------------------------------
+# The first stage's restatement (tests/_rpn_post_ref.py) on its recorded heads with two of the configurations of tests/test_rpn_post_gpu.py (pre 200, post 100,
+# NMS 0.3, N = 2), its four levels as the pyramid of the second stage (strides 4 / 8 / 16 / 32 of the 32^3 mesh, maps 8^3 .. 1^3), the tiny head of the
+# recorded runs (C = 4, output 2^3, 12 rows per batch).  empty: a third scene whose objectness lies 20 below, with score_thresh 0.5 so that it hands over no
+# proposal (the input of that suite's test_a_scene_where_every_box_is_dropped); the other two scenes lose their proposals below 0.5 as well.
+JOIN = dict(pre=200, post=100, nms=0.3, scales=(4, 8, 16, 32), batch=12, cap=517, shift={False: 0.05, True: 0.1}, map_seed={(False, False): 0, (False, True): 0, (True, False): 2, (True, True): 2})
+
+
+def joined_case(rotated, empty=False, map_seed=None, shift=None):
+    """-> dict(obj, reg, ori, score: the first stage's inputs; res, marg: its restatement; rois (float64, level in front), gts, labs: per scene; rows,
+    candidates: the float64 matching; keep [N, R], n_fg: kept rows chosen among the candidates that are decided rows and keep MARGIN on every floor of their
+    pooling grid, foreground first; maps; R)"""
+    from tests import _rpn_post_ref as P
+    from tests import _rpn_ref as RR
+    obj, reg = P.inputs(P.HEAD_SEED[rotated], rotated)
+    ori, score = list(RR.ORI), 0.0
+    if empty:
+        o3, r3 = P.inputs(5, rotated, N=1)
+        obj, reg = [torch.cat([a, b - 20.0]) for a, b in zip(obj, o3)], [torch.cat([a, b]) for a, b in zip(reg, r3)]
+        ori, score = ori + [RR.MESH], 0.5
+    N = len(ori)
+    res, marg = P.proposals(obj, reg, ori=ori, pre_nms_top_n=JOIN["pre"], post_nms_top_n=JOIN["post"], nms_thresh=JOIN["nms"], score_thresh=score, rotated=rotated)
+    rois = [torch.cat([r["level"].to(F64)[:, None], r["boxes"]], 1) for r in res]
+    gts, shift = [], (JOIN["shift"][rotated] if shift is None else shift)
+    for r in rois:                         # three of the scene's own proposals, 10 % larger (IoU 0.75 with their proposal) and moved a little
+        K = r.shape[0]
+        g = r[[1, K // 3, 2 * K // 3], 1:].clone() if K >= 3 else torch.tensor([[12.0, 12, 12, 8, 8, 8, 0.3]] if rotated else [[8.0, 8, 8, 16, 16, 16]], dtype=F64)
+        if K >= 3 and rotated:
+            g[:, 3:6] *= 1.1
+            g[:, :3] += shift
+        elif K >= 3:
+            c, h = (g[:, :3] + g[:, 3:]) / 2 + shift, (g[:, 3:] - g[:, :3]) / 2 * 1.1
+            g = torch.cat([c - h, c + h], 1)
+        gts.append(g.float())
+    labs = [torch.ones(g.shape[0], dtype=torch.float32) for g in gts]
+    m = targets(rois, gts, labs)[3]
+    dims = [tuple(int(v) for v in g) for g in RR.GRIDS]
+    R = JOIN["batch"] // N
+    keep, n_fg = [], []
+    for r, rm, (f, b) in zip(rois, m["rows"], m["candidates"]):
+        good = [bool(rm["decided"][q]) and _grid(r[q, 1:], rotated, float(JOIN["scales"][int(r[q, 0])]), dims[int(r[q, 0])], ENLARGE)[4] >= MARGIN for q in range(r.shape[0])]
+        f, b = [int(q) for q in f if good[q]], [int(q) for q in b if good[q]]
+        if not f or not b:
+            keep.append([-1] * R)
+            n_fg.append(0)
+            continue
+        nf = min(R // 2, len(f))
+        b = sorted(b, key=lambda q: (-int(r[q, 0]), q))                                  # the coarse levels first, so that the kept rows mix the levels
+        keep.append(f[:nf] + [b[j % len(b)] for j in range(R - nf)])
+        n_fg.append(nf)
+    seed = JOIN["map_seed"][(rotated, empty)] if map_seed is None else map_seed
+    return dict(obj=obj, reg=reg, ori=ori, score=score, res=res, marg=marg, rois=rois, gts=gts, labs=labs, rows=m["rows"], candidates=m["candidates"], keep=torch.tensor(keep), n_fg=n_fg,
+                maps=make_maps(seed, GOLD["C"], N, dims), R=R)
+
+
+def joined_chain(case, rotated):
+    """the second stage in float64 on the case's kept rows -> dict(L, Ro, Gr: [N, R, ..]; pooled; margins of the pooling; deltas, scores; loss (H.loss);
+    boxes, wrap: the decode and its margin; dmaps, dparams: the gradient of the sum of both losses)"""
+    N, R, B = len(case["rois"]), case["R"], 7 if rotated else 6
+    L, Ro, Gr, _ = targets(case["rois"], case["gts"], case["labs"], keep=case["keep"], n_fg=case["n_fg"], rows=case["rows"])
+    L, Ro, Gr = torch.stack(L), torch.stack(Ro), torch.stack(Gr)
+    pooled, pm, _ = pool(case["maps"], Ro, scales=JOIN["scales"], out=GOLD["out"], rotated=rotated)
+    hp = {k: v.double() for k, v in gold_head(rotated).items()}
+    x = pooled.reshape(N * R, -1)
+    deltas, scores = x @ hp["RCNN_bbox_pred_w"].T + hp["RCNN_bbox_pred_b"], x @ hp["RCNN_cls_score_w"].T + hp["RCNN_cls_score_b"]
+    ex = Ro.reshape(N * R, -1)[:, 1:].clone()
+    if rotated:                            # with remap off the model encodes and decodes against the enlarged RoIs
+        ex[:, 3:6] *= 1 + ENLARGE
+    lo = loss(scores, deltas, L.reshape(-1), ex, Gr.reshape(N * R, B), rotated)
+    boxes, wrap = decode(deltas, ex, rotated)
+    dx = lo["dscores"] @ hp["RCNN_cls_score_w"] + lo["ddeltas"] @ hp["RCNN_bbox_pred_w"]
+    _, _, dmaps = pool(case["maps"], Ro, scales=JOIN["scales"], out=GOLD["out"], rotated=rotated, dout=dx.reshape(pooled.shape))
+    dparams = dict(RCNN_bbox_pred_w=lo["ddeltas"].T @ x, RCNN_bbox_pred_b=lo["ddeltas"].sum(0), RCNN_cls_score_w=lo["dscores"].T @ x, RCNN_cls_score_b=lo["dscores"].sum(0))
+    return dict(L=L, Ro=Ro, Gr=Gr, ex=ex, pooled=pooled, pm=pm, deltas=deltas, scores=scores, loss=lo, boxes=boxes, wrap=wrap, dmaps=dmaps, dparams=dparams)
+
+
 # ---- the pooling cases of the GPU tests --------------------------------------------------------------------------------------------------------
 NONCUBIC = [(16, 12, 8), (8, 6, 4), (4, 3, 2)]                     # a 32 x 24 x 16 mesh
 # (rotated, non-cubic maps, C, output size) -> (scene seed, map seed), found with pool_case_search below: every margin >= MARGIN
 POOL_CASES = {(False, False, 8, (2, 2, 2)): (0, 0), (False, True, 5, (3, 2, 1)): (0, 0), (True, False, 5, (3, 2, 1)): (0, 1), (True, True, 8, (2, 2, 2)): (0, 0)}
+# Past one channel group and one workgroup per RoI, on the RoI sets above (the oriented geometry margins admit no larger set), map seeds found with
+# pool_map_search below.  C = 20, output (5, 4, 3): three channel groups of 8, the last with 4 channels, several points per cell (maxima).  C = 12, output
+# (7, 7, 7): 343 cells x 2 groups = 686 lanes = 3 workgroups per RoI, at most one point per cell (addressing).
+POOL_WIDE = {(False, False, 20, (5, 4, 3)): (0, 0), (False, True, 20, (5, 4, 3)): (0, 0), (True, False, 20, (5, 4, 3)): (0, 4), (True, True, 20, (5, 4, 3)): (0, 4),
+             (False, False, 12, (7, 7, 7)): (0, 0), (False, True, 12, (7, 7, 7)): (0, 0), (True, False, 12, (7, 7, 7)): (0, 0), (True, True, 12, (7, 7, 7)): (0, 0)}
+POOL_CASES.update(POOL_WIDE)
+# four levels (a 2^3 map at scale 16 behind the cubic three): rotated -> (scene seed, map seed), found with pool4_search below
+SCALES4 = SCALES + (16,)
+POOL4 = dict(C=12, out=(2, 2, 2), seeds={False: (0, 0), True: (5, 2)})
 
 
 def pool_rois(seed, rotated, N=2, K=None):
@@ -309,6 +559,46 @@ def pool_case(key):
     seed, map_seed = POOL_CASES[key]
     rois = pool_rois(seed, rotated)
     return rois, make_maps(map_seed, C, rois.shape[0], NONCUBIC if noncubic else None)
+
+
+def pool4_case(rotated, seed=None, map_seed=None):
+    """pool_rois with every third RoI moved to level 3 and maps of four levels -> (rois, maps)"""
+    seed, map_seed = (POOL4["seeds"][rotated][0] if seed is None else seed), (POOL4["seeds"][rotated][1] if map_seed is None else map_seed)
+    rois = pool_rois(seed, rotated)
+    rois[:, ::3, 0] = 3.0
+    return rois, make_maps(map_seed, POOL4["C"], rois.shape[0], [tuple(m // s for m in MESH) for s in SCALES4])
+
+
+def pool4_search(limit=200):
+    for rotated in (False, True):
+        for seed in range(limit):
+            rois, maps = pool4_case(rotated, seed, 0)
+            _, m, _ = pool(maps, rois, scales=SCALES4, out=POOL4["out"], rotated=rotated, want_values=False)
+            if m["floor"] < MARGIN:
+                continue
+            for map_seed in range(20):
+                rois, maps = pool4_case(rotated, seed, map_seed)
+                _, m, _ = pool(maps, rois, scales=SCALES4, out=POOL4["out"], rotated=rotated)
+                if m["cell_gap"] >= MARGIN:
+                    print("POOL4", rotated, (seed, map_seed), {k: m[k] for k in ("floor", "cell_gap", "padded_cells", "masked_points", "ragged")}, flush=True)
+                    break
+            else:
+                continue
+            break
+
+
+def pool_map_search(limit=16):
+    """the first map seed of every POOL_WIDE case that keeps every margin, on the recorded scene seed"""
+    for key, (seed, _) in POOL_WIDE.items():
+        rotated, noncubic, C, out = key
+        rois = pool_rois(seed, rotated)
+        for map_seed in range(limit):
+            _, m, _ = pool(make_maps(map_seed, C, rois.shape[0], NONCUBIC if noncubic else None), rois, out=out, rotated=rotated)
+            if min(m["floor"], m["cell_gap"]) >= MARGIN:
+                print(key, (seed, map_seed), {k: m[k] for k in ("floor", "cell_gap", "padded_cells", "masked_points", "ragged")}, flush=True)
+                break
+        else:
+            print(key, "no map seed below", limit, flush=True)
 
 
 # the oriented remap case of the GPU tests: (scene seed, map seed), found with remap_case_search below

@@ -4,8 +4,10 @@ recorded reference, tests/golden/g22_roi_head.npz, in tests/test_roi_head_ref_cp
 Tolerance: the project's contract for fp32, assert_close(rtol=1e-3).  Labels, kept rows, levels and exact zeros are compared exactly; that is defined because every
 input used here has a margin of at least 1e-3 on every discrete decision (asserted before each comparison; fp32 errs by about 1e-6 on an IoU or a grid position),
 or sits on integers, where fp32 is exact.  Geometry: a 32^3 mesh with maps 16^3 / 8^3 / 4^3 (scales 2 / 4 / 8) and a 32 x 24 x 16 mesh with non-cubic maps, two
-scenes, 23 axis-aligned or 15 oriented RoIs per scene (tests/_roi_head_ref.pool_rois), C = 8 and C = 5 (the channel tail of a lane's 8), output (2,2,2) and (3,2,1); remap with
-oriented boxes on 8 RoIs per scene that use all three levels (tests/_roi_head_ref.remap_case).  Measured on an MI355X (NMH_PRINT_ERR=1): DESIGN.md 3.13.
+scenes, 23 axis-aligned or 15 oriented RoIs per scene (tests/_roi_head_ref.pool_rois), C = 8 and C = 5 (the channel tail of a lane's 8), output (2,2,2) and (3,2,1); C = 20
+with output (5,4,3) (three channel groups, the last ragged) and C = 12 with output (7,7,7) (three workgroups per RoI); four levels; remap with
+oriented boxes on 8 RoIs per scene that use all three levels (tests/_roi_head_ref.remap_case).  Targets and the sampler are also run on 2500 proposals per scene
+(H.BIG, H.SAMPLER), where rows are compared by their own margins and the sampler against its restatement in integers.  Measured on an MI355X (NMH_PRINT_ERR=1): DESIGN.md 3.13.
 
 The built-in sampler is checked for its counts, classes, with-replacement draws, one-sided cases, determinism and uniformity: 64 identical scenes x 8 fixed counters =
 512 draws of 8 out of 40 foreground candidates, every candidate's count within 6 standard deviations of Binomial(512, 0.2) (about 102 +- 54); and 512 x 8
@@ -77,6 +79,72 @@ def test_targets_in_both_modes_with_the_recorded_keep(pre, rotated):
     counts[0] = 5
     labels, r, gr, kept, c2 = M.roi_targets_dense(boxes, levels, counts, [g.cuda() for g in gts], [l.cuda() for l in labs], 0, 0, H.FG, H.BG, None, False)
     assert c2 is None and (labels[0, 5:] == -1).all() and (r[0, 5:] == 0).all() and (gr[0, 5:] == 0).all() and (kept[0, 5:] == -1).all()
+
+
+# ---- 1b. matching and labels past one chunk of either kernel -------------------------------------------------------------------------------
+def _pad(per_scene, cap, fill):
+    """per-scene [k, ...] float64 -> [N, cap, ...] with `fill` in the rows past k"""
+    return torch.stack([torch.cat([t, torch.full((cap - t.shape[0], *t.shape[1:]), fill, dtype=t.dtype)]) for t in per_scene])
+
+
+def _same_rows(a, b):
+    return (a.double() == b).all(-1)
+
+
+@functools.lru_cache(maxsize=None)
+def big_ref(rotated):
+    """the six scenes of H.BIG, the float64 matching once, and from it both outcomes of every near-tie in evaluation mode and with a given keep"""
+    c = H.big_case(rotated)
+    args = (c["rois"], c["gts"], c["labs"])
+    ev = H.targets(*args)
+    rows = ev[3]["rows"]
+    keep, n_fg = H.big_keep(ev[3]["candidates"])
+    kw = dict(keep=keep, n_fg=n_fg, rows=rows)
+    return c, rows, keep, n_fg, ev, H.targets(*args, rows=rows, alt_arg=True), H.targets(*args, rows=rows, alt_label=True), H.targets(*args, **kw), H.targets(*args, alt_arg=True, **kw)
+
+
+@pytest.mark.parametrize("pre,rotated", FORMS)
+def test_targets_past_one_chunk_with_per_row_margins(pre, rotated):
+    """2500 proposals per scene (three 1024-lane chunks of the sampler's walk, ten workgroups of the matching) against up to 130 boxes (three 64-box stages),
+    counts on, one past and below the chunk sizes, a scene without proposals and one without boxes, garbage in the rows past the counts.  Rows that keep 1e-3
+    on all three IoU decisions (at least 97 % of every scene, tests/test_roi_head_ref_cpu.py) must agree exactly; a row that does not may take either outcome
+    of its near-tie.  counts above cap and below 0 are clamped."""
+    M = _m()
+    c, rows, keep, n_fg, ev, ev_arg, ev_lab, sm, sm_arg = big_ref(rotated)
+    cap, R, N = H.BIG["cap"], H.BIG["R"], len(c["counts"])
+    boxes, levels = c["boxes"].cuda(), c["levels"].cuda()
+    gts, labs = [g.cuda() for g in c["gts"]], [l.cuda() for l in c["labs"]]
+    exists = torch.arange(cap)[None] < torch.tensor(c["counts"])[:, None]
+    decided = torch.stack([torch.cat([rm["decided"], torch.zeros(cap - rm["decided"].numel(), dtype=torch.bool)]) for rm in rows])
+    assert decided.sum() >= 0.97 * exists.sum()
+    clamped = [c["counts"][0] + 7] + c["counts"][1:]
+    clamped[c["counts"].index(0)] = -3
+    kc = _i32([[nf, R - nf] if (keep[i] >= 0).any() else [0, 0] for i, nf in enumerate(n_fg)])
+    for counts in (c["counts"], clamped):
+        # evaluation: every proposal
+        labels, r, gr, kept, c2 = [None if t is None else t.cpu() for t in M.roi_targets_dense(boxes, levels, _i32(counts), gts, labs, 0, 0, H.FG, H.BG, None, False)]
+        assert c2 is None and labels.shape == (N, cap)
+        assert (labels[~exists] == -1).all() and not r[~exists].any() and not gr[~exists].any() and (kept[~exists] == -1).all(), "rows past the counts are not read"
+        assert torch.equal(kept[exists].long(), torch.arange(cap).repeat(N, 1)[exists])
+        assert torch.equal(r[exists][:, 1:], c["boxes"][exists]) and torch.equal(r[exists][:, 0], c["levels"][exists].float()), "rows are copies"
+        L, L2, G1, G2 = _pad(ev[0], cap, -1.0), _pad(ev_lab[0], cap, -1.0), _pad(ev[2], cap, 0.0), _pad(ev_arg[2], cap, 0.0)
+        assert torch.equal(labels.double()[decided], L[decided]) and torch.equal(gr.double()[decided], G1[decided]), "decided rows"
+        lab_alt, box_alt = (labels.double() != L) & exists, ~_same_rows(gr, G1) & exists
+        print(f"evaluation, {pre}: {int(lab_alt.sum())} labels and {int(box_alt.sum())} matched boxes of {int((exists & ~decided).sum())} undecided rows took the other outcome")
+        assert ((labels.double() == L) | (labels.double() == L2)).all() and (_same_rows(gr, G1) | _same_rows(gr, G2)).all(), "an undecided row takes one of its two outcomes"
+        i0 = H.BIG["G"].index(0)
+        assert labels[i0, 0] == 0 and not gr[i0].any(), "the scene without boxes: IoU 0, label 0, zero gt_rois"
+        # sampling with a given keep
+        labels, r, gr, kept, c2 = [t.cpu() for t in M.roi_targets_dense(boxes, levels, _i32(counts), gts, labs, R, R // 2, H.FG, H.BG, None, True, keep=_i32(keep), keep_counts=kc)]
+        assert torch.equal(kept.long(), keep) and torch.equal(c2, kc.cpu())
+        assert torch.equal(r.double(), torch.stack(sm[1])), "rows are copies, zero where keep is -1"
+        L, L2, G1, G2 = torch.stack(sm[0]), torch.stack(sm_arg[0]), torch.stack(sm[2]), torch.stack(sm_arg[2])
+        slot_decided = torch.stack([torch.cat([rm["decided"], torch.ones(1, dtype=torch.bool)])[keep[i]] for i, rm in enumerate(rows)])      # keep -1 -> the appended True
+        assert torch.equal(labels.double()[slot_decided], L[slot_decided]) and torch.equal(gr.double()[slot_decided], G1[slot_decided]), "decided rows"
+        first = (labels.double() == L) & _same_rows(gr, G1)
+        print(f"given keep, {pre}: {int((~first).sum())} of {int((~slot_decided).sum())} undecided slots took the other box")
+        assert (first | ((labels.double() == L2) & _same_rows(gr, G2))).all(), "label and box of an undecided row come from one of its top two boxes"
+        assert (L[~slot_decided] != L2[~slot_decided]).any(), "a near-tie between boxes of different labels is among the kept rows"
 
 
 # ---- 2. the sampler ----------------------------------------------------------------------------------------------------------------------
@@ -151,6 +219,39 @@ def test_sampler_is_uniform():
         assert dev <= 6 * sd, f"class {cls}: a count deviates by {dev:.0f} > 6 sigma = {6 * sd:.0f}"
 
 
+@functools.lru_cache(maxsize=None)
+def sampler_ref():
+    c = H.sampler_case()
+    rois = H.sampler_rois(c)
+    m = H.targets(rois, c["gts"], c["labs"])[3]
+    assert all(bool(rm["decided"].all()) for rm in m["rows"])
+    return c, rois, m
+
+
+def test_sampler_equals_its_restatement_across_chunks():
+    """keep and counts2 against the draw restated in Python integers (H.sample) on scenes of up to 2500 rows whose rows are all decided by construction: a
+    cut in all three chunks, more than 1024 background candidates, one-sided and empty scenes, garbage foreground rows past the counts, R below and above
+    1024.  The conditions on these inputs are asserted on the restatement in tests/test_roi_head_ref_cpu.py."""
+    M = _m()
+    c, rois, m = sampler_ref()
+    boxes, levels, counts = c["boxes"].cuda(), c["levels"].cuda(), _i32(c["counts"])
+    gts, labs = [g.cuda() for g in c["gts"]], [l.cuda() for l in c["labs"]]
+    seed = H.SAMPLER["seed"]
+    for R, want in H.SAMPLER["runs"]:
+        for counter in H.SAMPLER["counters"]:
+            st = _state(seed, counter)
+            labels, r, gr, keep, c2 = [t.cpu() for t in M.roi_targets_dense(boxes, levels, counts, gts, labs, R, want, H.FG, H.BG, st, True)]
+            ref = [H.sample(f, b, R, want, seed, counter, i) for i, (f, b) in enumerate(m["candidates"])]
+            rk, rc = torch.tensor([k for k, _, _ in ref]), torch.tensor([list(n) for _, n, _ in ref])
+            differ = int((keep.long() != rk).sum())
+            print(f"sampler R {R} want {want} counter {counter}: {differ} of {rk.numel()} slots differ")
+            assert torch.equal(c2.long(), rc), (c2.tolist(), rc.tolist())
+            assert differ == 0, [(i, int((keep[i].long() != rk[i]).sum())) for i in range(rk.shape[0])]
+            assert st.cpu().tolist() == [seed, counter + 1]
+            L, Ro, Gr, _ = H.targets(rois, c["gts"], c["labs"], keep=rk, n_fg=rc[:, 0].tolist(), rows=m["rows"])
+            assert torch.equal(labels.double(), torch.stack(L)) and torch.equal(r.double(), torch.stack(Ro)) and torch.equal(gr.double(), torch.stack(Gr))
+
+
 # ---- 3. pooling --------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def pool_ref(key):
@@ -186,6 +287,28 @@ def test_pooling_forward_and_backward(key):
     # the reference's per-scene lists give the same features
     lists = pool([[t[i].cuda() for t in maps] for i in range(rois.shape[0])], [r.cuda() for r in rois])
     assert torch.equal(torch.cat(lists), got.detach())
+
+
+@pytest.mark.parametrize("rotated", [False, True], ids=["aabb", "obb"])
+def test_pooling_over_four_levels(rotated):
+    """scales 2 / 4 / 8 / 16 with a 2^3 map behind the cubic three and every third RoI on level 3: the fourth slot of the kernels' level tables"""
+    M = _m()
+    rois, maps = H.pool4_case(rotated)
+    C, out = H.POOL4["C"], H.POOL4["out"]
+    dout = torch.randn((rois.shape[0] * rois.shape[1], C, *out), generator=torch.Generator().manual_seed(5), dtype=torch.float32)
+    res, m, dmaps = H.pool(maps, rois, scales=H.SCALES4, out=out, rotated=rotated, dout=dout)
+    assert m["floor"] >= H.MARGIN and m["cell_gap"] >= H.MARGIN and (rois[..., 0] == 3).sum() >= 10, m
+    at3 = (rois[..., 0] == 3).reshape(-1)
+    assert res[at3].abs().sum() > 0 and dmaps[3].abs().sum() > 0, "level 3 gives values and takes gradient"
+    pool = M.ROIPool(out, H.SCALES4, H.ENLARGE, rotated)
+    leaves = [t.cuda().requires_grad_(True) for t in maps]
+    got = pool(leaves, rois.cuda())
+    assert_close(got, res, 1e-3, "pooled, four levels")
+    assert torch.equal(got.detach().cpu() == 0, res == 0), "exact zeros where the padding or a masked point won"
+    got.backward(dout.cuda())
+    for k, (leaf, want) in enumerate(zip(leaves, dmaps)):
+        assert_close(leaf.grad, want, 1e-3, f"d map {k}, four levels")
+        assert (leaf.grad.cpu()[want == 0] == 0).all(), "exactly zero gradient where no cell's maximum came from"
 
 
 def test_pooling_with_remap_and_the_level_mapper():
