@@ -535,6 +535,20 @@ NMH_API int nmh_roi_loss_fwd(int64_t M, int n_classes, int ncols, const float* s
 NMH_API int nmh_roi_loss_bwd(int64_t M, int n_classes, int ncols, const float* scores, const float* deltas, const float* labels, const float* targets, const float* scalars, const float* g_obj, const float* g_reg, float* dscores, float* ddeltas, void* stream);
 /* RotatedCoder.decode_single (coder/rotated_coder.py:57-121) / AABBCoder.decode_single (coder/AABB_coder.py:86-137), detector.py:609-611. */
 NMH_API int nmh_roi_decode(int64_t M, int ncols, const float* deltas, const float* rois, int roi_stride, float* boxes, void* stream);
+/* ---- RPNHead's output stage (nerf_rpn/model/anchor.py:177-224; kernels, fragment maps and semantics: csrc/rpn_head.hip) ----
+ * level_vox: HOST int [nlevels] = W H D per level, 1 <= nlevels <= 4; N scenes; Cin a multiple of 8; 1 <= A <= 32 anchors per location; C 6 | 8, else -4.
+ * t: HOST table of per-level DEVICE activations (N, W, H, D, Cin) channels-last in dt; w_cls [A][Cin], w_box [A C][Cin] in dt (the head's column j is row j
+ * of w_cls below A and row j - A of w_box above); b_cls [A], b_box [A C] fp32.  relu != 0: t is rectified as it is read.
+ * -> objectness (N, A, W, H, D) and pred_bbox_deltas (N, A C, W, H, D) fp32 per level, channel a C + c.  One launch for all levels. */
+NMH_API int nmh_rpn_head_out_fwd(int dt, int nlevels, const int* level_vox, int N, int Cin, int A, int C, int relu, const void* const* t, const void* w_cls, const void* w_box, const float* b_cls, const float* b_box, float* const* objectness, float* const* regression, void* stream);
+/* Its backward.  g_obj, g_reg: per-level dense fp32 gradients of the two outputs.  -> dt_out per level = relu'(t) o (G Wcat) in dt, channels-last (relu'(0) = 0;
+ * no mask with relu == 0); dw_cls, dw_box, db_cls, db_box += Gt relu(t) and the column sums of G over all levels, by per-workgroup partials (DEVICE workspace of
+ * nmh_rpn_head_bwd_ws_floats() floats) summed in workgroup order: bit-identical between runs.  Three launches for all levels. */
+NMH_API int64_t nmh_rpn_head_bwd_ws_floats(int nlevels, const int* level_vox, int N, int Cin, int A, int C);
+NMH_API int nmh_rpn_head_out_bwd(int dt, int nlevels, const int* level_vox, int N, int Cin, int A, int C, int relu, const void* const* t, const void* w_cls, const void* w_box, const float* const* g_obj, const float* const* g_reg, void* const* dt_out, float* partials, float* dw_cls, float* dw_box, float* db_cls, float* db_box, void* stream);
+/* The ReLU between the head's convolutions, in place on a channels-last tensor of n elements (n % 8 == 0): x = max(x, 0); dy = 0 where y <= 0. */
+NMH_API int nmh_relu_(int dt, void* x, int64_t n, void* stream);
+NMH_API int nmh_relu_bwd_(int dt, void* dy, const void* y, int64_t n, void* stream);
 /* Per-step host parameters of the training step in ONE launch, passed as kernel arguments (no host-to-device copies):
  *  - block_bits (HOST, nb^3 bits, bit (a*nb+b)*nb+c = 1: the 4x4x4-token block (a,b,c) is removed; window_masking_3d's raster order,
  *    swin_mae3d.py:1366-1373) is expanded to the token mask tokmask[g^3] (device, uint8; tokens outside the nb^3 blocks stay 0);

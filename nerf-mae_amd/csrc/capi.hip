@@ -715,6 +715,32 @@ int nmh_rpn_post_nms(int nlevels, const int* level_dims, int N, int ncols, int p
   return k_rpn_post_nms(nlevels, level_dims, N, ncols, pre_nms_top_n, pre_boxes, pre_scores, pre_index, (const long*)sorted_keys, (const long*)order, pre_counts, nms_thresh,
                         post_nms_top_n, (unsigned long long*)mask, keep, boxes, scores, levels, index, counts, ST);
 }
+int nmh_rpn_head_out_fwd(int dt, int nlevels, const int* level_vox, int N, int Cin, int A, int C, int relu, const void* const* t, const void* w_cls, const void* w_box,
+                         const float* b_cls, const float* b_box, float* const* objectness, float* const* regression, void* stream) {
+  CLR();
+  REQ(level_vox, t, w_cls, w_box, b_cls, b_box, objectness, regression);
+  return k_rpn_head_out_fwd(dt, nlevels, level_vox, N, Cin, A, C, relu, t, w_cls, w_box, b_cls, b_box, objectness, regression, ST);
+}
+int64_t nmh_rpn_head_bwd_ws_floats(int nlevels, const int* level_vox, int N, int Cin, int A, int C) {
+  return level_vox ? k_rpn_head_bwd_ws_floats(nlevels, level_vox, N, Cin, A, C) : -1;
+}
+int nmh_rpn_head_out_bwd(int dt, int nlevels, const int* level_vox, int N, int Cin, int A, int C, int relu, const void* const* t, const void* w_cls, const void* w_box,
+                         const float* const* g_obj, const float* const* g_reg, void* const* dt_out, float* partials, float* dw_cls, float* dw_box, float* db_cls, float* db_box,
+                         void* stream) {
+  CLR();
+  REQ(level_vox, t, w_cls, w_box, g_obj, g_reg, dt_out, partials, dw_cls, dw_box, db_cls, db_box);
+  return k_rpn_head_out_bwd(dt, nlevels, level_vox, N, Cin, A, C, relu, t, w_cls, w_box, g_obj, g_reg, dt_out, partials, dw_cls, dw_box, db_cls, db_box, ST);
+}
+int nmh_relu_(int dt, void* x, int64_t n, void* stream) {
+  CLR();
+  REQ(x);
+  return k_relu_(dt, x, (long)n, ST);
+}
+int nmh_relu_bwd_(int dt, void* dy, const void* y, int64_t n, void* stream) {
+  CLR();
+  REQ(dy, y);
+  return k_relu_bwd_(dt, dy, y, (long)n, ST);
+}
 int nmh_step_params(const uint32_t* block_bits, int nb, int g, unsigned char* tokmask, const float* hyper, float* hyper_dev, const int* extents, int n_ext, int* extents_dev,
                     void* stream) {
   CLR();

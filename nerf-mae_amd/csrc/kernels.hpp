@@ -349,6 +349,16 @@ int k_roi_loss_fwd(long M, int n_classes, int ncols, const float* scores, const 
 int k_roi_loss_bwd(long M, int n_classes, int ncols, const float* scores, const float* deltas, const float* labels, const float* targets, const float* scalars, const float* g_obj,
                    const float* g_reg, float* dscores, float* ddeltas, hipStream_t st);
 int k_roi_decode(long M, int ncols, const float* deltas, const float* rois, int roi_stride, float* out, hipStream_t st);
+// ---- rpn_head.hip (RPNHead's output stage: cls_logits + bbox_pred from the channels-last activation to the NCDHW fp32 planes, and back; ReLU passes) ----
+// vox: HOST [nlevels] voxels per scene; t / obj / reg / g_* / dt_out: HOST tables of nlevels DEVICE pointers.  Layouts: rpn_head.hip.
+long k_rpn_head_bwd_ws_floats(int nlevels, const int* vox, int N, int Cin, int A, int C);
+int k_rpn_head_out_fwd(int dt, int nlevels, const int* vox, int N, int Cin, int A, int C, int relu, const void* const* t, const void* w_cls, const void* w_box, const float* b_cls,
+                       const float* b_box, float* const* obj, float* const* reg, hipStream_t st);
+int k_rpn_head_out_bwd(int dt, int nlevels, const int* vox, int N, int Cin, int A, int C, int relu, const void* const* t, const void* w_cls, const void* w_box,
+                       const float* const* g_obj, const float* const* g_reg, void* const* dt_out, float* partials, float* dw_cls, float* dw_box, float* db_cls, float* db_box,
+                       hipStream_t st);
+int k_relu_(int dt, void* x, long n, hipStream_t st);
+int k_relu_bwd_(int dt, void* dy, const void* y, long n, hipStream_t st);
 int k_step_params(const unsigned* bits, int nb, int g, unsigned char* tokmask, const float* hyper_host, float* hyper_dev, const int* ext_host, int n_ext, int* ext_dev, hipStream_t st);
 int k_grad_cast(int to_bf16, const void* src, void* dst, long n, float scale, hipStream_t st);
 

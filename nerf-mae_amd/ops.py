@@ -1801,6 +1801,80 @@ def rpn_post_nms(post, ncols, pre_boxes, pre_scores, pre_index, sorted_keys, ord
     return boxes, scores, levels, index, counts
 
 
+# ---- RPNHead's output stage and the ReLU between its convolutions (csrc/rpn_head.hip) -------------------------------------------------------
+def _head_args(name, ts, w_cls, w_box, C):
+    """per-level channels-last activations (N,W,H,D,Cin) + the two 1x1x1 weights [A,Cin], [A*C,Cin] -> (level table, N, Cin, A)"""
+    if not 1 <= len(ts) <= FCOS_MAX_LEVELS:
+        raise ValueError(f"{name} takes 1 to {FCOS_MAX_LEVELS} levels, got {len(ts)}")
+    if C not in (6, 8):
+        raise ValueError(f"{name}: 6 or 8 regression values per anchor, got {C}")
+    _chk(*ts, w_cls, w_box)
+    N, Cin = ts[0].shape[0], ts[0].shape[-1]
+    A = w_cls.numel() // Cin
+    if any(t.dim() != 5 or t.shape[0] != N or t.shape[-1] != Cin or t.dtype != ts[0].dtype for t in ts):
+        raise ValueError(f"{name}: every level must be (N, W, H, D, Cin) channels-last of one dtype")
+    if Cin % 8:
+        raise NotImplementedError(f"{name}: channel counts must be multiples of 8, got {Cin}")
+    if w_cls.dtype != ts[0].dtype or w_box.dtype != ts[0].dtype or w_cls.numel() != A * Cin or w_box.numel() != A * C * Cin:
+        raise ValueError(f"{name}: weights [A,{Cin}] and [A*{C},{Cin}] in the activations' dtype; got {w_cls.numel()} and {w_box.numel()} elements")
+    if not 1 <= A <= RPN_MAX_ANCHORS:
+        raise ValueError(f"{name} takes 1 to {RPN_MAX_ANCHORS} anchors per location, got {A}")
+    vox = (ctypes.c_int * len(ts))(*[t.shape[1] * t.shape[2] * t.shape[3] for t in ts])
+    return vox, N, Cin, A
+
+
+def _ptr_table(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def rpn_head_out_fwd(ts, w_cls, w_box, b_cls, b_box, C, relu):
+    """ts: per level the channels-last activation (N,W,H,D,Cin) in the compute dtype; w_cls [A,Cin], w_box [A*C,Cin] in that dtype; b_cls [A], b_box [A*C] fp32;
+    relu: rectify ts as it is read -> (objectness [(N,A,W,H,D)], pred_bbox_deltas [(N,A*C,W,H,D)]) fp32, all levels in one launch"""
+    vox, N, Cin, A = _head_args("rpn_head_out_fwd", ts, w_cls, w_box, C)
+    _chk(b_cls, b_box)
+    dev = ts[0].device
+    obj = [torch.empty((N, A, *t.shape[1:4]), dtype=torch.float32, device=dev) for t in ts]
+    reg = [torch.empty((N, A * C, *t.shape[1:4]), dtype=torch.float32, device=dev) for t in ts]
+    lib().call("nmh_rpn_head_out_fwd", dt_of(ts[0]), len(ts), vox, N, Cin, A, C, int(bool(relu)), _ptr_table(ts), w_cls, w_box, b_cls, b_box, _ptr_table(obj), _ptr_table(reg), _st())
+    return obj, reg
+
+
+def rpn_head_out_bwd(ts, w_cls, w_box, g_obj, g_reg, C, relu, dw_cls, dw_box, db_cls, db_box):
+    """the dense fp32 gradients of the two outputs -> per level dt = relu'(t) o (G Wcat), channels-last in the compute dtype; dw_cls, dw_box, db_cls, db_box
+    (fp32) += the weight and bias gradients summed over all levels in a fixed order"""
+    vox, N, Cin, A = _head_args("rpn_head_out_bwd", ts, w_cls, w_box, C)
+    _chk(*g_obj, *g_reg, dw_cls, dw_box, db_cls, db_box)
+    if len(g_obj) != len(ts) or len(g_reg) != len(ts):
+        raise ValueError("rpn_head_out_bwd: one gradient of each output per level")
+    for t, go, gr in zip(ts, g_obj, g_reg):
+        if go.dtype != torch.float32 or gr.dtype != torch.float32 or tuple(go.shape) != (N, A, *t.shape[1:4]) or tuple(gr.shape) != (N, A * C, *t.shape[1:4]):
+            raise ValueError(f"rpn_head_out_bwd: gradients (N,{A},W,H,D) and (N,{A * C},W,H,D) fp32; got {tuple(go.shape)}, {tuple(gr.shape)}")
+    if dw_cls.numel() != A * Cin or dw_box.numel() != A * C * Cin or db_cls.numel() != A or db_box.numel() != A * C or any(
+            g.dtype != torch.float32 for g in (dw_cls, dw_box, db_cls, db_box)):
+        raise ValueError("rpn_head_out_bwd: fp32 gradient buffers of the shapes of the weights and biases")
+    dts = [torch.empty_like(t) for t in ts]
+    ws = torch.empty((lib().cdll.nmh_rpn_head_bwd_ws_floats(len(ts), vox, N, Cin, A, C),), dtype=torch.float32, device=ts[0].device)
+    lib().call("nmh_rpn_head_out_bwd", dt_of(ts[0]), len(ts), vox, N, Cin, A, C, int(bool(relu)), _ptr_table(ts), w_cls, w_box, _ptr_table(g_obj), _ptr_table(g_reg), _ptr_table(dts), ws,
+               dw_cls, dw_box, db_cls, db_box, _st())
+    return dts
+
+
+def relu_(x):
+    """x = max(x, 0) in place (channels-last, a multiple of 8 elements)"""
+    _chk(x)
+    lib().call("nmh_relu_", dt_of(x), x, x.numel(), _st())
+    return x
+
+
+def relu_bwd_(dy, y):
+    """dy = 0 where y <= 0, in place"""
+    _chk(dy, y)
+    if dy.shape != y.shape or dy.dtype != y.dtype:
+        raise ValueError("relu_bwd_: dy and y of one shape and dtype")
+    lib().call("nmh_relu_bwd_", dt_of(dy), dy, y, dy.numel(), _st())
+    return dy
+
+
 # ---- RoI stage of the two-stage detector: proposal targets, pyramid RoI pooling, box-head losses, decode (csrc/roi_head.hip) -----------------------
 ROI_MAX_GRID = 1024            # points per axis of one oriented RoI's sampling grid; a larger grid is cut to this
 ROI_MAX_CELLS = 4096           # ow * oh * od

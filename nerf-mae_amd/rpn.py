@@ -9,6 +9,11 @@ the reference's names (the import swap is one line):
   rpn_decode_proposals         box_coder.decode_list (model/coder/base_bbox_coder.py:55-86) over AABBCoder / MidpointOffsetCoder.decode_single
   rpn_proposals_dense          _get_top_n_idx + filter_proposals (model/rpn.py:292-370) with fixed-size results and no host synchronisation, for HIP graphs
   RPNProposalFilter            the inference half of forward (model/rpn.py:507-512): per-scene lists (boxes, level_indexes, scores)
+  RPNHead                      model/anchor.py:177-213 on the channels-last convolutions and the output kernels of csrc/rpn_head.hip (same constructor, state_dict
+                               keys, shapes and initialisation; compute_dtype is an addition)
+  RegionProposalNetwork        model/rpn.py:167-549: head + RPNLossComputation (training) or RPNProposalFilter (evaluation); same constructor, state_dict keys
+                               head.* only; proposals_dense() is the capturable hand-over to the RoI stage
+  NeRFRegionProposalNetwork    model/nerf_rpn.py: backbone + RegionProposalNetwork, zero padding to the batch maximum, the degenerate-box check
 
 Head outputs are the per-level tensors as the head writes them, (N, A, W, H, D) objectness logits and (N, A*6|8, W, H, D) regression (channel
 a*C + c), fp32; they are read and differentiated in place (no permute, no cat).  Ground-truth boxes are one fp32 device tensor per scene, [k, 6]
@@ -47,13 +52,17 @@ from __future__ import annotations
 
 import itertools
 
+import numpy as np
 import torch
+import torch.nn.functional as F
 from torch import nn
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import ops
 from .fcos_loss import _boxes, _check
+from .fpn import _NCDHWToCL
+from .model import _gradbuf, _Packer
 
 MAX_LEVELS, MAX_SCENES, MAX_ANCHORS = ops.FCOS_MAX_LEVELS, ops.FCOS_MAX_SCENES, ops.RPN_MAX_ANCHORS
 NMS_MAX_BOXES = ops.OBB_NMS_MAX
@@ -361,3 +370,276 @@ class RPNProposalFilter(object):
                                                                self.pre_nms_top_n, self.post_nms_top_n, self.nms_thresh, self.score_thresh, self.min_size, self.rotate)
         counts = counts.tolist()                # the one synchronisation
         return ([boxes[i, :k] for i, k in enumerate(counts)], [levels[i, :k].long() for i, k in enumerate(counts)], [scores[i, :k] for i, k in enumerate(counts)])
+
+
+# ---- head and network ------------------------------------------------------------------------------------------------------------------------
+class _RPNHeadFn(Function):
+    """(head, *channels-last features) -> (*objectness levels, *regression levels): the 3x3x3 convs with ReLU on channels-last tensors, then the output
+    kernel that writes the fp32 NCDHW planes.  The parameters are not autograd inputs: their gradients are accumulated into .grad by the kernels (as in
+    fpn._FPNFn).  Saved per level: the input of every conv (rectified in place) and the last conv's output before its ReLU."""
+
+    @staticmethod
+    def forward(ctx, head, *feats):
+        pk, Cin, depth, C = head._pk, head.in_channels, head.conv_depth, head.num_delta_digits
+        acts = []
+        for f in feats:
+            xs = [f.contiguous()]
+            for k in range(depth):
+                conv, x = head.conv[2 * k], xs[-1]
+                if ops.use_conv64(x, Cin) and f"c{k}.w64" in pk.views:
+                    y = ops.conv3d_k3_c64(x, pk[f"c{k}.w64"], Cin, bias=conv.bias)
+                else:
+                    y = ops.conv3d_k3_bias(x, pk[f"c{k}.w"], conv.bias, Cin)
+                if k < depth - 1:               # the last conv's ReLU is fused into the output kernel's load
+                    ops.relu_(y)
+                xs.append(y)
+            acts.append(xs)
+        obj, reg = ops.rpn_head_out_fwd([xs[-1] for xs in acts], pk["cls.w"], pk["box.w"], head.cls_logits.bias, head.bbox_pred.bias, C, depth > 0)
+        ctx.head, ctx.saved = head, acts
+        return (*obj, *reg)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gs):
+        head, acts = ctx.head, ctx.saved
+        pk, Cin, depth, C, L = head._pk, head.in_channels, head.conv_depth, head.num_delta_digits, len(ctx.saved)
+        g_obj, g_reg = [g.contiguous() for g in gs[:L]], [g.contiguous() for g in gs[L:]]
+        cls, box = head.cls_logits, head.bbox_pred
+        dts = ops.rpn_head_out_bwd([xs[-1] for xs in acts], pk["cls.w"], pk["box.w"], g_obj, g_reg, C, depth > 0, _gradbuf(cls.weight), _gradbuf(box.weight),
+                                   _gradbuf(cls.bias), _gradbuf(box.bias))
+        dfeats, keep = [], []   # keep: tensors the forked side stream still reads -- referenced until the join
+        for i, (xs, dy) in enumerate(zip(acts, dts)):
+            for k in range(depth - 1, -1, -1):
+                conv, x = head.conv[2 * k], xs[k]
+                if k < depth - 1:
+                    ops.relu_bwd_(dy, xs[k + 1])
+                keep.append(dy)
+                with ops.side_stream():
+                    ops.conv3d_k3_wgrad(dy, x, _gradbuf(conv.weight))
+                    ops.bias_grad(dy.view(-1, Cin), _gradbuf(conv.bias), dy.numel() // Cin, Cin)
+                if k == 0 and not ctx.needs_input_grad[1 + i]:
+                    dy = None
+                elif ops.use_conv64(dy, Cin) and f"c{k}.w64d" in pk.views:
+                    dy = ops.conv3d_k3_c64(dy, pk[f"c{k}.w64d"], Cin)
+                else:
+                    dy = ops.conv3d_k3(dy, pk[f"c{k}.wd"], Cin)
+            dfeats.append(dy)
+        ops.join_side()
+        del keep
+        return (None, *dfeats)
+
+
+class RPNHead(nn.Module):
+    """model/anchor.py:177-213.  Parameters live in `nn.Conv3d` holders (`conv` = Sequential of Conv3d, ReLU pairs; `cls_logits`; `bbox_pred`) so that names,
+    shapes and the initialisation (normal 0.01, zero bias) equal the reference's; their forward is never used.  conv_depth 0 is legal (the features are then
+    not rectified).  Outputs per level: objectness (N, A, W, H, D) and pred_bbox_deltas (N, A*6|8, W, H, D), fp32."""
+
+    def __init__(self, in_channels, num_anchors, conv_depth=1, rotate=False, compute_dtype: torch.dtype = torch.bfloat16):
+        super().__init__()
+        if in_channels % 8:
+            raise NotImplementedError("channel counts must be multiples of 8")
+        if not 1 <= int(num_anchors) <= MAX_ANCHORS:
+            raise ValueError(f"RPNHead supports 1 to {MAX_ANCHORS} anchors per location, got {num_anchors}")
+        if compute_dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError(f"compute_dtype must be bfloat16 or float32, got {compute_dtype}")
+        self.in_channels, self.num_anchors, self.conv_depth = int(in_channels), int(num_anchors), int(conv_depth)
+        self.num_delta_digits = 8 if rotate else 6
+        self.compute_dtype = compute_dtype
+        convs = []
+        for _ in range(self.conv_depth):
+            convs.append(nn.Conv3d(in_channels, in_channels, kernel_size=3, padding=1))
+            convs.append(nn.ReLU(inplace=True))
+        self.conv = nn.Sequential(*convs)
+        self.cls_logits = nn.Conv3d(in_channels, num_anchors, kernel_size=1, stride=1)
+        self.bbox_pred = nn.Conv3d(in_channels, num_anchors * self.num_delta_digits, kernel_size=1, stride=1)
+        for layer in self.modules():
+            if isinstance(layer, nn.Conv3d):
+                torch.nn.init.normal_(layer.weight, std=0.01)
+                torch.nn.init.constant_(layer.bias, 0)
+        self._pk = None
+        self._pk_key = None
+
+    def _pack(self):
+        ps = list(self.parameters())
+        if not ps[0].is_cuda:
+            raise RuntimeError("RPNHead (HIP) needs its parameters on a HIP device: call .cuda() first (no CPU fallback)")
+        key = tuple(p.data_ptr() for p in ps)
+        if self._pk is None or self._pk_key != key:
+            P = _Packer()
+            for k in range(self.conv_depth):
+                w = self.conv[2 * k].weight
+                P.add(f"c{k}.w", w, P.CONV_F)
+                P.add(f"c{k}.wd", w, P.CONV_D)
+                if self.compute_dtype == torch.bfloat16 and self.in_channels % 64 == 0:
+                    P.add(f"c{k}.w64", w, P.C64_F)
+                    P.add(f"c{k}.w64d", w, P.C64_D)
+            P.add("cls.w", self.cls_logits.weight, P.CAST)
+            P.add("box.w", self.bbox_pred.weight, P.CAST)
+            P.build(self.compute_dtype, ps[0].device)
+            P.split = None
+            self._pk, self._pk_key = P, key
+        self._pk.run()
+
+    def forward_channels_last(self, feats):
+        """feats: per level a channels-last (N, W, H, D, C) tensor in the compute dtype -> (logits, bbox_reg), lists of fp32 NCDHW tensors"""
+        feats = list(feats)
+        if not 1 <= len(feats) <= MAX_LEVELS:
+            raise ValueError(f"RPNHead supports 1 to {MAX_LEVELS} levels, got {len(feats)}")
+        for f in feats:
+            if not f.is_cuda:
+                raise RuntimeError("RPNHead (HIP) needs HIP device tensors (no CPU fallback)")
+            if f.dim() != 5 or f.shape[-1] != self.in_channels or f.dtype != self.compute_dtype:
+                raise ValueError(f"RPNHead: channels-last (N, W, H, D, {self.in_channels}) features in {self.compute_dtype}, got {tuple(f.shape)} {f.dtype}")
+        self._pack()
+        out = _RPNHeadFn.apply(self, *feats)
+        return list(out[:len(feats)]), list(out[len(feats):])
+
+    def forward(self, x):
+        """reference signature: list of NCDHW tensors -> (logits, bbox_reg)"""
+        return self.forward_channels_last([_NCDHWToCL.apply(f, self.compute_dtype) for f in x])
+
+
+class RegionProposalNetwork(nn.Module):
+    """model/rpn.py:167-549 with the reference's constructor.  Training: the losses of RPNLossComputation, no proposals; evaluation: the lists of
+    RPNProposalFilter and {}.  The only registered submodules are anchor_generator (no parameters) and head, so the state_dict keys are head.*."""
+
+    def __init__(self, anchor_generator, head, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, pre_nms_top_n, post_nms_top_n, nms_thresh,
+                 score_thresh=0.0, iou_batch_size=16, rotated_bbox=False, reg_loss_type="smooth_l1"):
+        super().__init__()
+        self.anchor_generator = anchor_generator
+        self.head = head
+        self.rotate = bool(rotated_bbox)
+        self.num_bbox_digits = 7 if rotated_bbox else 6
+        self.num_delta_digits = 8 if rotated_bbox else 6
+        self.iou_batch_size = iou_batch_size        # kept for the signature: the assignment kernel needs no batching
+        self._pre_nms_top_n = pre_nms_top_n
+        self._post_nms_top_n = post_nms_top_n
+        self.nms_thresh = nms_thresh
+        self.score_thresh = score_thresh
+        self.reg_loss_type = reg_loss_type
+        self.min_size = 1e-3
+        self.loss = RPNLossComputation(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox, reg_loss_type)
+        self.filters = {mode: RPNProposalFilter(anchor_generator, pre_nms_top_n[mode], post_nms_top_n[mode], nms_thresh, score_thresh, rotated_bbox)
+                        for mode in ("training", "testing")}
+
+    def pre_nms_top_n(self):
+        return self._pre_nms_top_n["training" if self.training else "testing"]
+
+    def post_nms_top_n(self):
+        return self._post_nms_top_n["training" if self.training else "testing"]
+
+    def _filter(self):
+        return self.filters["training" if self.training else "testing"]
+
+    def forward(self, meshes, features, original_mesh_sizes, targets=None, objectness_output_paths=None, sampled=None):
+        """meshes (N, C, X, Y, Z): only its size is read; features: per level NCDHW; original_mesh_sizes: the scenes' sizes before padding, used only when N > 1;
+        sampled: uint8 flags [N, n] in place of the sampler (RPNLossComputation) -> (boxes, level_indexes, losses, scores)"""
+        objectness, pred_bbox_deltas = self.head(features)
+        if objectness_output_paths is not None:
+            self.output_objectness(objectness, original_mesh_sizes, objectness_output_paths)
+        mesh_size = tuple(int(v) for v in meshes.shape[-3:])
+        if self.training:
+            if targets is None:
+                raise ValueError("targets should not be None")
+            return None, None, self.loss(mesh_size, objectness, pred_bbox_deltas, targets, original_mesh_sizes, sampled=sampled), None
+        boxes, level_indexes, scores = self._filter()(mesh_size, objectness, pred_bbox_deltas, original_mesh_sizes)
+        return boxes, level_indexes, {}, scores
+
+    def proposals_dense(self, meshes, features, original_mesh_sizes=None):
+        """the proposals of the current mode's top-n as rpn_proposals_dense's fixed-size quintuple (boxes, scores, levels, anchor_index, counts): never waits
+        for the host, capturable (pass original_mesh_sizes as an int32 device tensor [N, 3] then)"""
+        objectness, pred_bbox_deltas = self.head(features)
+        f = self._filter()
+        N = objectness[0].shape[0]
+        return rpn_proposals_dense(self.anchor_generator, tuple(int(v) for v in meshes.shape[-3:]), objectness, pred_bbox_deltas, original_mesh_sizes if N > 1 else None,
+                                   f.pre_nms_top_n, f.post_nms_top_n, f.nms_thresh, f.score_thresh, f.min_size, f.rotate)
+
+    def output_objectness(self, objectness, ori_sizes, output_paths):
+        """model/rpn.py:538-549, in plain torch as the reference has it"""
+        for i in range(len(ori_sizes)):
+            all_levels = {}
+            for level in range(len(objectness)):
+                score = objectness[level][i].max(dim=0)[0]
+                w, l, h = np.ceil(np.array([int(v) for v in ori_sizes[i]]) / 2 ** (level + 2)).astype(int)
+                all_levels[str(level)] = score[:w, :l, :h].detach().cpu().numpy()
+            np.savez_compressed(output_paths[i], **all_levels)
+
+
+def _default_anchorgen():
+    anchor_sizes = ((8,), (16,), (32,), (64,),)
+    aspect_ratios = (((1., 1., 1.), (1., 1., 2.), (1., 2., 2.), (1., 1., 3.), (1., 3., 3.)),) * len(anchor_sizes)
+    return AnchorGenerator3D(anchor_sizes, aspect_ratios)
+
+
+class NeRFRegionProposalNetwork(nn.Module):
+    """model/nerf_rpn.py: backbone + RegionProposalNetwork over a list of (C, W, H, D) grids -> [features, proposals, level_index], losses, scores.
+    With rpn_head=None the head is RPNHead(out_channels, A, rotated_bbox) as in the reference, so the flag lands in conv_depth (depth 0 or 1, always 6 regression
+    columns).  check_targets = False skips the degenerate-box check, the one place that waits for the host in training (for graph capture)."""
+
+    def __init__(self, backbone, rpn_anchor_generator=None, rpn_head=None, rpn_pre_nms_top_n_train=2000, rpn_pre_nms_top_n_test=1000, rpn_post_nms_top_n_train=2000,
+                 rpn_post_nms_top_n_test=1000, rpn_nms_thresh=0.7, rpn_fg_iou_thresh=0.7, rpn_bg_iou_thresh=0.3, rpn_batch_size_per_image=256, rpn_positive_fraction=0.5,
+                 rpn_score_thresh=0.0, iou_batch_size=16, rotated_bbox=False, reg_loss_type="smooth_l1", **kwargs):
+        if not hasattr(backbone, "out_channels"):
+            raise ValueError("backbone should contain an attribute out_channels specifying the number of output channels (assumed to be the same for all the levels)")
+        if not isinstance(rpn_anchor_generator, (AnchorGenerator3D, type(None))):
+            raise TypeError(f"rpn_anchor_generator should be of type AnchorGenerator or None instead of {type(rpn_anchor_generator)}")
+        out_channels = backbone.out_channels
+        if rpn_anchor_generator is None:
+            rpn_anchor_generator = _default_anchorgen()
+        if rpn_head is None:
+            rpn_head = RPNHead(out_channels, rpn_anchor_generator.num_anchors_per_location()[0], rotated_bbox)      # the reference's quirk: the flag is conv_depth
+        rpn = RegionProposalNetwork(rpn_anchor_generator, rpn_head, rpn_fg_iou_thresh, rpn_bg_iou_thresh, rpn_batch_size_per_image, rpn_positive_fraction,
+                                    dict(training=rpn_pre_nms_top_n_train, testing=rpn_pre_nms_top_n_test),
+                                    dict(training=rpn_post_nms_top_n_train, testing=rpn_post_nms_top_n_test), rpn_nms_thresh, score_thresh=rpn_score_thresh,
+                                    iou_batch_size=iou_batch_size, rotated_bbox=rotated_bbox, reg_loss_type=reg_loss_type)
+        super().__init__()
+        self.backbone = backbone
+        self.rpn = rpn
+        self.check_targets = True
+        self._ori_cache = {}
+
+    def transform(self, meshes, targets=None):
+        """zero padding to the batch maximum (in place in the list, as the reference does)"""
+        if len(meshes) > 1:
+            target_shape = np.max([m.shape for m in meshes], axis=0)
+            for i, mesh in enumerate(meshes):
+                meshes[i] = F.pad(mesh, (0, int(target_shape[-1] - mesh.shape[-1]), 0, int(target_shape[-2] - mesh.shape[-2]), 0, int(target_shape[-3] - mesh.shape[-3])),
+                                  mode="constant", value=0)
+        return meshes, targets
+
+    def check_bbox_degeneration(self, targets):
+        if targets is not None:
+            for target_idx, boxes in enumerate(targets):
+                degenerate_boxes = boxes[:, 3:] <= boxes[:, :3] if boxes.shape[1] == 6 else boxes[:, 3:6] <= 0
+                if degenerate_boxes.any():
+                    bb_idx = torch.where(degenerate_boxes.any(dim=1))[0][0]
+                    torch._assert(False, "All bounding boxes should have positive height, width and depth."
+                                         f" Found invalid box {boxes[bb_idx].tolist()} for target at index {target_idx}.")
+
+    def forward(self, meshes, targets=None, objectness_output_paths=None):
+        if self.training:
+            if targets is None:
+                torch._assert(False, "targets should not be none when in training mode")
+            for boxes in targets:
+                if isinstance(boxes, torch.Tensor):
+                    torch._assert(len(boxes.shape) == 2 and boxes.shape[-1] in (6, 7), f"Expected target boxes to be a tensor of shape [N, 6], got {boxes.shape}.")
+                else:
+                    torch._assert(False, f"Expected target boxes to be of type Tensor, got {type(boxes)}.")
+        original_mesh_sizes = []
+        for mesh in meshes:
+            val = mesh.shape[-3:]
+            torch._assert(len(val) == 3, f"expecting the last three dimensions of the Tensor to be W, H and D instead got {mesh.shape[-3:]}")
+            original_mesh_sizes.append((val[0], val[1], val[2]))
+        meshes, targets = self.transform(meshes, targets)
+        if self.check_targets:
+            self.check_bbox_degeneration(targets)
+        mesh_tensors = torch.stack(meshes, dim=0)
+        features = list(self.backbone(mesh_tensors))
+        ori = original_mesh_sizes
+        if len(meshes) > 1 and objectness_output_paths is None:      # one host-to-device copy per distinct set of sizes, none afterwards (nothing waits for the host)
+            key = (tuple(tuple(int(v) for v in o) for o in ori), mesh_tensors.device)
+            if key not in self._ori_cache:
+                self._ori_cache[key] = torch.tensor(key[0], dtype=torch.int32, device=mesh_tensors.device)
+            ori = self._ori_cache[key]
+        proposals, level_index, proposal_losses, scores = self.rpn(mesh_tensors, features, ori, targets, objectness_output_paths)
+        return [features, proposals, level_index], proposal_losses, scores
