@@ -549,6 +549,36 @@ NMH_API int nmh_rpn_head_out_bwd(int dt, int nlevels, const int* level_vox, int 
 /* The ReLU between the head's convolutions, in place on a channels-last tensor of n elements (n % 8 == 0): x = max(x, 0); dy = 0 where y <= 0. */
 NMH_API int nmh_relu_(int dt, void* x, int64_t n, void* stream);
 NMH_API int nmh_relu_bwd_(int dt, void* dy, const void* y, int64_t n, void* stream);
+/* ---- FCOSHead (nerf_rpn/model/fcos/fcos.py:26-139) between its 3x3x3 tower convolutions; kernels, fragment maps and semantics: csrc/fcos_head.hip ----
+ * A job is one channels-last tensor (N, W, L, H, C) in dt of one (level, tower); njobs <= 10, C % 32 == 0, C <= 2048, C / G in {1, 2, 4} or a multiple of 8, else -4.
+ * vox: HOST int [njobs] = W L H; tower: HOST int [njobs] in {0, 1}; x, y, dy, dx: HOST tables of njobs DEVICE pointers; gamma, beta, dgamma, dbeta: HOST tables of
+ * two DEVICE pointers [C] fp32, one per tower (cls_tower, bbox_tower; an unused tower's entry may be NULL).  One launch covers every job.
+ * nmh_fcos_gn_stats: nn.GroupNorm(G, C)'s statistics (fcos.py:63,75; eps inside the root, biased variance) -> stats [njobs][N][G][2] = {mean, rstd} fp32, from fp64
+ * per-workgroup partial sums (ws: nmh_fcos_gn_ws_doubles() doubles) added in a fixed order.
+ * nmh_fcos_gn_apply: y = relu(gamma_c (x - mean) rstd + beta_c) in dt (GroupNorm + nn.ReLU, fcos.py:63-64, 75-76).
+ * nmh_fcos_gn_bwd: dx = rstd (dyh - mean_g(dyh) - xh mean_g(dyh xh)) in dt with dyh = dy [y > 0] gamma_c; dgamma[tower][c] += sum dy [y > 0] xh and
+ * dbeta[tower][c] += sum dy [y > 0] over every job of the tower; sums: [njobs][N][G][2] fp32 scratch (the two group means); ws as above. */
+NMH_API int64_t nmh_fcos_gn_ws_doubles(int njobs, const int* vox, int N, int C);
+NMH_API int nmh_fcos_gn_stats(int dt, int njobs, const int* vox, int N, int C, int G, float eps, const void* const* x, double* ws, float* stats, void* stream);
+NMH_API int nmh_fcos_gn_apply(int dt, int njobs, const int* vox, const int* tower, int N, int C, int G, const void* const* x, const float* stats, const float* const* gamma, const float* const* beta, void* const* y, void* stream);
+NMH_API int nmh_fcos_gn_bwd(int dt, int njobs, const int* vox, const int* tower, int N, int C, int G, const void* const* dy, const void* const* x, const void* const* y, const float* stats, const float* const* gamma, double* ws, float* sums, float* const* dgamma, float* const* dbeta, void* const* dx, void* stream);
+/* The output stage (fcos.py:80-87, 117-137): cls_logits, bbox_pred and centerness, nn.Conv3d(C, 1 | nreg | 1, 3, padding=1), nreg 6 | 8, of nlevels <= 5 levels in one
+ * launch.  dims: HOST int [3 nlevels] = W, L, H; strides: HOST float [nlevels] (fpn_strides); act: HOST table of 2 nlevels DEVICE activations, entry 2 l + t the input
+ * of tower t (0 cls, 1 bbox) at level l; w16: two packed weights [16][27][C] in dt, row j of tower 0 = cls_logits (j = 0), centerness (j = 1, unless ctr_on_reg), of
+ * tower 1 = bbox_pred (j < nreg), centerness (j = nreg, if ctr_on_reg), the other rows zero; scale: nlevels DEVICE pointers to the Scale parameters (fcos.py:17-23).
+ * mode 0: norm_reg_targets in training (ReLU on columns 0-5, fcos.py:126-130); 1: in evaluation (those columns times the stride, :132); 2: exp of every column (:136).
+ * -> cls (N, 1, W, L, H), reg (N, nreg, W, L, H), ctr (N, 1, W, L, H) fp32 and u (N, nreg, W, L, H): bbox_pred with its bias before the Scale, kept for the backward. */
+NMH_API int nmh_fcos_head_out_fwd(int dt, int nlevels, const int* dims, const float* strides, int N, int C, int nreg, int ctr_on_reg, int mode, const void* const* act, const void* const* w16, const float* b_cls, const float* b_box, const float* b_ctr, const float* const* scale, float* const* cls, float* const* reg, float* const* ctr, float* const* u, void* stream);
+/* Its backward, first half: the dense fp32 gradients through the epilogue (ReLU mask where the output is > 0, times the Scale, times the output in the exp branch)
+ * -> g16: per (level, tower) the 16-column gradient (N, W, L, H, 16) in dt, the dgrad operand of nmh_conv3d_k3; gt: the same as fp32 planes (N, 16, W, L, H), the
+ * operand of nmh_fcos_head_out_wgrad; db_cls, db_box, db_ctr += the bias gradients and *dscale[l] += sum g mask (conv + bias), from per-workgroup partials
+ * (nmh_fcos_head_pack_ws_floats() floats) summed in a fixed order. */
+NMH_API int64_t nmh_fcos_head_pack_ws_floats(int nlevels, const int* dims, int N);
+NMH_API int nmh_fcos_head_out_bwd_pack(int dt, int nlevels, const int* dims, const float* strides, int N, int nreg, int ctr_on_reg, int mode, const float* const* g_cls, const float* const* g_reg, const float* const* g_ctr, const float* const* u, const float* const* scale, void* const* g16, float* const* gt, float* partials, float* db_cls, float* db_box, float* db_ctr, float* const* dscale, void* stream);
+/* Second half: dw_cls [1][C][3][3][3], dw_box [nreg][C][3][3][3], dw_ctr [1][C][3][3][3] (fp32, nn.Conv3d layout) += the weight gradients over every level, from
+ * per-workgroup partials (nmh_fcos_head_wgrad_ws_floats() floats) summed in workgroup order; in bf16 the gradient enters the matrix cores as hi + lo. */
+NMH_API int64_t nmh_fcos_head_wgrad_ws_floats(int nlevels, const int* dims, int N, int C);
+NMH_API int nmh_fcos_head_out_wgrad(int dt, int nlevels, const int* dims, int N, int C, int nreg, int ctr_on_reg, const void* const* act, const float* const* gt, float* partials, float* dw_cls, float* dw_box, float* dw_ctr, void* stream);
 /* Per-step host parameters of the training step in ONE launch, passed as kernel arguments (no host-to-device copies):
  *  - block_bits (HOST, nb^3 bits, bit (a*nb+b)*nb+c = 1: the 4x4x4-token block (a,b,c) is removed; window_masking_3d's raster order,
  *    swin_mae3d.py:1366-1373) is expanded to the token mask tokmask[g^3] (device, uint8; tokens outside the nb^3 blocks stay 0);

@@ -741,6 +741,46 @@ int nmh_relu_bwd_(int dt, void* dy, const void* y, int64_t n, void* stream) {
   REQ(dy, y);
   return k_relu_bwd_(dt, dy, y, (long)n, ST);
 }
+int64_t nmh_fcos_gn_ws_doubles(int njobs, const int* vox, int N, int C) { return vox ? k_fcos_gn_ws_doubles(njobs, vox, N, C) : -1; }
+int nmh_fcos_gn_stats(int dt, int njobs, const int* vox, int N, int C, int G, float eps, const void* const* x, double* ws, float* stats, void* stream) {
+  CLR();
+  REQ(vox, x, ws, stats);
+  return k_fcos_gn_stats(dt, njobs, vox, N, C, G, eps, x, ws, stats, ST);
+}
+int nmh_fcos_gn_apply(int dt, int njobs, const int* vox, const int* tower, int N, int C, int G, const void* const* x, const float* stats, const float* const* gamma,
+                      const float* const* beta, void* const* y, void* stream) {
+  CLR();
+  REQ(vox, tower, x, stats, gamma, beta, y);
+  return k_fcos_gn_apply(dt, njobs, vox, tower, N, C, G, x, stats, gamma, beta, y, ST);
+}
+int nmh_fcos_gn_bwd(int dt, int njobs, const int* vox, const int* tower, int N, int C, int G, const void* const* dy, const void* const* x, const void* const* y, const float* stats,
+                    const float* const* gamma, double* ws, float* sums, float* const* dgamma, float* const* dbeta, void* const* dx, void* stream) {
+  CLR();
+  REQ(vox, tower, dy, x, y, stats, gamma, ws, sums, dgamma, dbeta, dx);
+  return k_fcos_gn_bwd(dt, njobs, vox, tower, N, C, G, dy, x, y, stats, gamma, ws, sums, dgamma, dbeta, dx, ST);
+}
+int nmh_fcos_head_out_fwd(int dt, int nlevels, const int* dims, const float* strides, int N, int C, int nreg, int ctr_on_reg, int mode, const void* const* act, const void* const* w16,
+                          const float* b_cls, const float* b_box, const float* b_ctr, const float* const* scale, float* const* cls, float* const* reg, float* const* ctr,
+                          float* const* u, void* stream) {
+  CLR();
+  REQ(dims, strides, act, w16, b_cls, b_box, b_ctr, scale, cls, reg, ctr, u);
+  return k_fcos_out_fwd(dt, nlevels, dims, strides, N, C, nreg, ctr_on_reg, mode, act, w16, b_cls, b_box, b_ctr, scale, cls, reg, ctr, u, ST);
+}
+int64_t nmh_fcos_head_pack_ws_floats(int nlevels, const int* dims, int N) { return dims ? k_fcos_out_pack_ws_floats(nlevels, dims, N) : -1; }
+int nmh_fcos_head_out_bwd_pack(int dt, int nlevels, const int* dims, const float* strides, int N, int nreg, int ctr_on_reg, int mode, const float* const* g_cls,
+                               const float* const* g_reg, const float* const* g_ctr, const float* const* u, const float* const* scale, void* const* g16, float* const* gt,
+                               float* partials, float* db_cls, float* db_box, float* db_ctr, float* const* dscale, void* stream) {
+  CLR();
+  REQ(dims, strides, g_cls, g_reg, g_ctr, u, scale, g16, gt, partials, db_cls, db_box, db_ctr, dscale);
+  return k_fcos_out_bwd_pack(dt, nlevels, dims, strides, N, nreg, ctr_on_reg, mode, g_cls, g_reg, g_ctr, u, scale, g16, gt, partials, db_cls, db_box, db_ctr, dscale, ST);
+}
+int64_t nmh_fcos_head_wgrad_ws_floats(int nlevels, const int* dims, int N, int C) { return dims ? k_fcos_out_wgrad_ws_floats(nlevels, dims, N, C) : -1; }
+int nmh_fcos_head_out_wgrad(int dt, int nlevels, const int* dims, int N, int C, int nreg, int ctr_on_reg, const void* const* act, const float* const* gt, float* partials,
+                            float* dw_cls, float* dw_box, float* dw_ctr, void* stream) {
+  CLR();
+  REQ(dims, act, gt, partials, dw_cls, dw_box, dw_ctr);
+  return k_fcos_out_wgrad(dt, nlevels, dims, N, C, nreg, ctr_on_reg, act, gt, partials, dw_cls, dw_box, dw_ctr, ST);
+}
 int nmh_step_params(const uint32_t* block_bits, int nb, int g, unsigned char* tokmask, const float* hyper, float* hyper_dev, const int* extents, int n_ext, int* extents_dev,
                     void* stream) {
   CLR();

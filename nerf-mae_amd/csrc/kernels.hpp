@@ -359,6 +359,24 @@ int k_rpn_head_out_bwd(int dt, int nlevels, const int* vox, int N, int Cin, int 
                        hipStream_t st);
 int k_relu_(int dt, void* x, long n, hipStream_t st);
 int k_relu_bwd_(int dt, void* dy, const void* y, long n, hipStream_t st);
+// ---- fcos_head.hip (FCOSHead between its tower convolutions: GroupNorm + ReLU forward and backward, the three 3x3x3 output convs with their epilogue, and back) ----
+// vox / tower: HOST [njobs]; dims: HOST [3 nlevels] = W, L, H; every const* const* / * const* argument is a HOST table of DEVICE pointers.  Layouts: fcos_head.hip.
+long k_fcos_gn_ws_doubles(int njobs, const int* vox, int N, int C);
+int k_fcos_gn_stats(int dt, int njobs, const int* vox, int N, int C, int G, float eps, const void* const* x, double* ws, float* stats, hipStream_t st);
+int k_fcos_gn_apply(int dt, int njobs, const int* vox, const int* tower, int N, int C, int G, const void* const* x, const float* stats, const float* const* gamma,
+                    const float* const* beta, void* const* y, hipStream_t st);
+int k_fcos_gn_bwd(int dt, int njobs, const int* vox, const int* tower, int N, int C, int G, const void* const* dy, const void* const* x, const void* const* y, const float* stats,
+                  const float* const* gamma, double* ws, float* sums, float* const* dgamma, float* const* dbeta, void* const* dx, hipStream_t st);
+int k_fcos_out_fwd(int dt, int nlevels, const int* dims, const float* strides, int N, int C, int nreg, int ctr_on_reg, int mode, const void* const* act, const void* const* w16,
+                   const float* b_cls, const float* b_box, const float* b_ctr, const float* const* scale, float* const* cls, float* const* reg, float* const* ctr,
+                   float* const* u, hipStream_t st);
+long k_fcos_out_pack_ws_floats(int nlevels, const int* dims, int N);
+int k_fcos_out_bwd_pack(int dt, int nlevels, const int* dims, const float* strides, int N, int nreg, int ctr_on_reg, int mode, const float* const* g_cls, const float* const* g_reg,
+                        const float* const* g_ctr, const float* const* u, const float* const* scale, void* const* g16, float* const* gt, float* partials, float* db_cls,
+                        float* db_box, float* db_ctr, float* const* dscale, hipStream_t st);
+long k_fcos_out_wgrad_ws_floats(int nlevels, const int* dims, int N, int C);
+int k_fcos_out_wgrad(int dt, int nlevels, const int* dims, int N, int C, int nreg, int ctr_on_reg, const void* const* act, const float* const* gt, float* partials, float* dw_cls,
+                     float* dw_box, float* dw_ctr, hipStream_t st);
 int k_step_params(const unsigned* bits, int nb, int g, unsigned char* tokmask, const float* hyper_host, float* hyper_dev, const int* ext_host, int n_ext, int* ext_dev, hipStream_t st);
 int k_grad_cast(int to_bf16, const void* src, void* dst, long n, float scale, hipStream_t st);
 

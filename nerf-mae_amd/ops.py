@@ -1977,3 +1977,165 @@ def roi_decode(ncols, deltas, rois):
     if deltas.shape[0]:
         lib().call("nmh_roi_decode", deltas.shape[0], ncols, deltas, rois, rois.shape[-1], out, _st())
     return out
+
+
+# ---- FCOSHead between its tower convolutions: GroupNorm + ReLU and the three 3x3x3 output convs (csrc/fcos_head.hip) ------------------------------
+FCOS_HEAD_MAX_LEVELS = 5           # the reference's FCOSHead has five Scale parameters
+FCOS_HEAD_MAX_JOBS = 2 * FCOS_HEAD_MAX_LEVELS
+FCOS_HEAD_MODES = {"train": 0, "eval": 1, "exp": 2}
+
+
+def _ptr_table_opt(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _gn_args(name, xs, towers, G, others=()):
+    """xs: the channels-last tensors (N,W,L,H,C) of up to 10 (level, tower) jobs; towers: 0 | 1 per job -> (vox, tower table, N, C)"""
+    if not 1 <= len(xs) <= FCOS_HEAD_MAX_JOBS:
+        raise ValueError(f"{name} takes 1 to {FCOS_HEAD_MAX_JOBS} tensors, got {len(xs)}")
+    _chk(*xs, *[t for o in others for t in o])
+    N, C = xs[0].shape[0], xs[0].shape[-1]
+    if any(t.dim() != 5 or t.shape[0] != N or t.shape[-1] != C or t.dtype != xs[0].dtype for t in xs):
+        raise ValueError(f"{name}: every tensor must be (N, W, L, H, C) channels-last of one dtype")
+    for o in others:
+        if len(o) != len(xs) or any(a.shape != b.shape or a.dtype != b.dtype for a, b in zip(o, xs)):
+            raise ValueError(f"{name}: the tensor lists must agree in shape and dtype")
+    if C % 32 or C > 2048:
+        raise NotImplementedError(f"{name}: channel counts must be multiples of 32 up to 2048, got {C}")
+    if G < 1 or C % G or not (C // G in (1, 2, 4) or (C // G) % 8 == 0):
+        raise NotImplementedError(f"{name}: {C} channels in {G} groups: channels per group must be 1, 2, 4 or a multiple of 8")
+    if towers is not None and (len(towers) != len(xs) or any(t not in (0, 1) for t in towers)):
+        raise ValueError(f"{name}: one tower index 0 | 1 per tensor")
+    vox = (ctypes.c_int * len(xs))(*[t.shape[1] * t.shape[2] * t.shape[3] for t in xs])
+    tw = None if towers is None else (ctypes.c_int * len(xs))(*[int(t) for t in towers])
+    return vox, tw, N, C
+
+
+def _gn_ws(vox, n, N, C, device):
+    return torch.empty((lib().cdll.nmh_fcos_gn_ws_doubles(n, vox, N, C),), dtype=torch.float64, device=device)
+
+
+def fcos_gn_stats(xs, G, eps=1e-5):
+    """nn.GroupNorm(G, C)'s statistics of every tensor in one launch -> stats [len(xs), N, G, 2] fp32 = {mean, rstd} (fp64 sums in a fixed order)"""
+    vox, _, N, C = _gn_args("fcos_gn_stats", xs, None, G)
+    stats = torch.empty((len(xs), N, G, 2), dtype=torch.float32, device=xs[0].device)
+    lib().call("nmh_fcos_gn_stats", dt_of(xs[0]), len(xs), vox, N, C, G, eps, _ptr_table(xs), _gn_ws(vox, len(xs), N, C, xs[0].device), stats, _st())
+    return stats
+
+
+def fcos_gn_apply(xs, towers, stats, gammas, betas, G):
+    """y = relu(gamma_c (x - mean) rstd + beta_c) of every tensor in one launch, in the tensors' dtype; gammas, betas: the (cls_tower, bbox_tower) fp32 pairs
+    (an unused tower's entry may be None)"""
+    vox, tw, N, C = _gn_args("fcos_gn_apply", xs, towers, G)
+    _chk(stats, *gammas, *betas)
+    if stats.dtype != torch.float32 or stats.numel() != len(xs) * N * G * 2 or len(gammas) != 2 or len(betas) != 2:
+        raise ValueError("fcos_gn_apply: stats [jobs, N, G, 2] fp32 and one (gamma, beta) per tower")
+    for t in set(towers):
+        if gammas[t] is None or betas[t] is None or gammas[t].dtype != torch.float32 or betas[t].dtype != torch.float32 or gammas[t].numel() != C or betas[t].numel() != C:
+            raise ValueError(f"fcos_gn_apply: tower {t} needs fp32 gamma and beta of {C} elements")
+    ys = [torch.empty_like(x) for x in xs]
+    lib().call("nmh_fcos_gn_apply", dt_of(xs[0]), len(xs), vox, tw, N, C, G, _ptr_table(xs), stats, _ptr_table_opt(gammas), _ptr_table_opt(betas), _ptr_table(ys), _st())
+    return ys
+
+
+def fcos_gn_bwd(dys, xs, ys, towers, stats, gammas, dgammas, dbetas, G):
+    """the backward of GroupNorm + ReLU for every tensor: -> dxs in the tensors' dtype; dgammas[t], dbetas[t] (fp32) += the parameter gradients over all the
+    tensors of tower t, in a fixed order"""
+    vox, tw, N, C = _gn_args("fcos_gn_bwd", xs, towers, G, (dys, ys))
+    _chk(stats, *gammas, *dgammas, *dbetas)
+    if stats.dtype != torch.float32 or stats.numel() != len(xs) * N * G * 2:
+        raise ValueError("fcos_gn_bwd: stats [jobs, N, G, 2] fp32")
+    for t in set(towers):
+        for p in (gammas[t], dgammas[t], dbetas[t]):
+            if p is None or p.dtype != torch.float32 or p.numel() != C:
+                raise ValueError(f"fcos_gn_bwd: tower {t} needs fp32 gamma, dgamma and dbeta of {C} elements")
+    dev = xs[0].device
+    sums = torch.empty((len(xs), N, G, 2), dtype=torch.float32, device=dev)
+    dxs = [torch.empty_like(x) for x in xs]
+    lib().call("nmh_fcos_gn_bwd", dt_of(xs[0]), len(xs), vox, tw, N, C, G, _ptr_table(dys), _ptr_table(xs), _ptr_table(ys), stats, _ptr_table_opt(gammas),
+               _gn_ws(vox, len(xs), N, C, dev), sums, _ptr_table_opt(dgammas), _ptr_table_opt(dbetas), _ptr_table(dxs), _st())
+    return dxs
+
+
+def _fcos_out_args(name, acts, nreg, mode):
+    """acts: per level the (cls tower, bbox tower) pair of channels-last activations -> (L, dims, N, C, flat job list)"""
+    L = len(acts)
+    if not 1 <= L <= FCOS_HEAD_MAX_LEVELS:
+        raise ValueError(f"{name} takes 1 to {FCOS_HEAD_MAX_LEVELS} levels, got {L}")
+    if nreg not in (6, 8):
+        raise ValueError(f"{name}: 6 or 8 regression columns, got {nreg}")
+    if mode not in FCOS_HEAD_MODES:
+        raise ValueError(f"{name}: mode is one of {sorted(FCOS_HEAD_MODES)}, got {mode!r}")
+    flat = [t for pair in acts for t in pair]
+    _chk(*flat)
+    N, C = flat[0].shape[0], flat[0].shape[-1]
+    if any(len(pair) != 2 or pair[0].shape != pair[1].shape for pair in acts) or any(t.dim() != 5 or t.shape[0] != N or t.shape[-1] != C or t.dtype != flat[0].dtype for t in flat):
+        raise ValueError(f"{name}: per level two (N, W, L, H, C) channels-last activations of one dtype")
+    if C % 32 or C > 2048:
+        raise NotImplementedError(f"{name}: channel counts must be multiples of 32 up to 2048, got {C}")
+    dims = (ctypes.c_int * (3 * L))(*[int(v) for pair in acts for v in pair[0].shape[1:4]])
+    return L, dims, N, C, flat
+
+
+def fcos_head_out_fwd(acts, w16, b_cls, b_box, b_ctr, scales, strides, nreg, ctr_on_reg, mode):
+    """acts: per level (cls tower, bbox tower) channels-last activations (N,W,L,H,C); w16: the two towers' packed weights [16][27][C] in the activations' dtype
+    (csrc/fcos_head.hip: tower columns); b_*: fp32 biases; scales: per level the fp32 Scale parameter [1]; mode "train" | "eval" | "exp" ->
+    (cls [(N,1,W,L,H)], reg [(N,nreg,W,L,H)], ctr [(N,1,W,L,H)], u [(N,nreg,W,L,H)]) fp32, u = bbox_pred + bias before the Scale; one launch"""
+    L, dims, N, C, flat = _fcos_out_args("fcos_head_out_fwd", acts, nreg, mode)
+    _chk(*w16, b_cls, b_box, b_ctr, *scales)
+    if len(w16) != 2 or any(w.dtype != flat[0].dtype or w.numel() != 16 * 27 * C for w in w16):
+        raise ValueError(f"fcos_head_out_fwd: two packed weights of 16 x 27 x {C} elements in the activations' dtype")
+    if len(scales) != L or len(strides) != L or any(s.dtype != torch.float32 or s.numel() != 1 for s in scales):
+        raise ValueError("fcos_head_out_fwd: one fp32 Scale parameter and one stride per level")
+    if any(b.dtype != torch.float32 for b in (b_cls, b_box, b_ctr)) or b_cls.numel() != 1 or b_box.numel() != nreg or b_ctr.numel() != 1:
+        raise ValueError(f"fcos_head_out_fwd: fp32 biases of 1, {nreg} and 1 elements")
+    dev = flat[0].device
+    shp = [tuple(pair[0].shape[1:4]) for pair in acts]
+    cls = [torch.empty((N, 1, *s), dtype=torch.float32, device=dev) for s in shp]
+    reg = [torch.empty((N, nreg, *s), dtype=torch.float32, device=dev) for s in shp]
+    ctr = [torch.empty((N, 1, *s), dtype=torch.float32, device=dev) for s in shp]
+    u = [torch.empty((N, nreg, *s), dtype=torch.float32, device=dev) for s in shp]
+    st = (ctypes.c_float * L)(*[float(s) for s in strides])
+    lib().call("nmh_fcos_head_out_fwd", dt_of(flat[0]), L, dims, st, N, C, nreg, int(bool(ctr_on_reg)), FCOS_HEAD_MODES[mode], _ptr_table(flat), _ptr_table(w16), b_cls, b_box, b_ctr,
+               _ptr_table(scales), _ptr_table(cls), _ptr_table(reg), _ptr_table(ctr), _ptr_table(u), _st())
+    return cls, reg, ctr, u
+
+
+def fcos_head_out_bwd(acts, g_cls, g_reg, g_ctr, u, scales, strides, nreg, ctr_on_reg, mode, db_cls, db_box, db_ctr, dscales):
+    """the dense fp32 gradients of the three outputs through the epilogue -> g16: per level the (cls tower, bbox tower) pair of 16-column gradients (N,W,L,H,16)
+    in the activations' dtype, the operand of the input-gradient convolution, and gt: the same as fp32 planes (N,16,W,L,H), the operand of
+    fcos_head_out_wgrad; db_* (fp32) and dscales[l] += the bias and Scale gradients over all levels in a fixed order -> (g16, gt)"""
+    L, dims, N, C, flat = _fcos_out_args("fcos_head_out_bwd", acts, nreg, mode)
+    _chk(*g_cls, *g_reg, *g_ctr, *u, *scales, db_cls, db_box, db_ctr, *dscales)
+    if any(len(t) != L for t in (g_cls, g_reg, g_ctr, u, scales, strides, dscales)):
+        raise ValueError("fcos_head_out_bwd: one gradient of each output, one saved u, one Scale and its gradient per level")
+    for pair, gc, gr, gk, uu in zip(acts, g_cls, g_reg, g_ctr, u):
+        s = tuple(pair[0].shape[1:4])
+        if any(t.dtype != torch.float32 for t in (gc, gr, gk, uu)) or tuple(gc.shape) != (N, 1, *s) or tuple(gk.shape) != (N, 1, *s) or tuple(gr.shape) != (N, nreg, *s) or uu.shape != gr.shape:
+            raise ValueError(f"fcos_head_out_bwd: fp32 gradients (N,1,W,L,H), (N,{nreg},W,L,H), (N,1,W,L,H) per level")
+    if any(t.dtype != torch.float32 for t in (db_cls, db_box, db_ctr, *scales, *dscales)) or db_cls.numel() != 1 or db_ctr.numel() != 1 or db_box.numel() != nreg or \
+            any(s.numel() != 1 for s in (*scales, *dscales)):
+        raise ValueError("fcos_head_out_bwd: fp32 gradient buffers of the shapes of the biases and the Scale parameters")
+    dev, dtype = flat[0].device, flat[0].dtype
+    g16 = [torch.empty((*t.shape[:4], 16), dtype=dtype, device=dev) for t in flat]
+    gt = [torch.empty((N, 16, *t.shape[1:4]), dtype=torch.float32, device=dev) for t in flat]
+    st = (ctypes.c_float * L)(*[float(s) for s in strides])
+    ws = torch.empty((lib().cdll.nmh_fcos_head_pack_ws_floats(L, dims, N),), dtype=torch.float32, device=dev)
+    lib().call("nmh_fcos_head_out_bwd_pack", dt_of(flat[0]), L, dims, st, N, nreg, int(bool(ctr_on_reg)), FCOS_HEAD_MODES[mode], _ptr_table(g_cls), _ptr_table(g_reg), _ptr_table(g_ctr),
+               _ptr_table(u), _ptr_table(scales), _ptr_table(g16), _ptr_table(gt), ws, db_cls, db_box, db_ctr, _ptr_table(dscales), _st())
+    return [(g16[2 * l], g16[2 * l + 1]) for l in range(L)], [(gt[2 * l], gt[2 * l + 1]) for l in range(L)]
+
+
+def fcos_head_out_wgrad(acts, gt, nreg, ctr_on_reg, dw_cls, dw_box, dw_ctr):
+    """gt: fcos_head_out_bwd's fp32 planes -> dw_cls [1,C,3,3,3], dw_box [nreg,C,3,3,3], dw_ctr [1,C,3,3,3] (fp32) += the weight gradients over all levels, per-workgroup
+    partials summed in a fixed order; returns the workspace, which the caller keeps alive when the call runs on a side stream"""
+    L, dims, N, C, flat = _fcos_out_args("fcos_head_out_wgrad", acts, nreg, "train")
+    gflat = [t for pair in gt for t in pair]
+    _chk(*gflat, dw_cls, dw_box, dw_ctr)
+    if len(gflat) != len(flat) or any(g.dtype != torch.float32 or tuple(g.shape) != (N, 16, *t.shape[1:4]) for g, t in zip(gflat, flat)):
+        raise ValueError("fcos_head_out_wgrad: per level two fp32 gradient planes (N, 16, W, L, H)")
+    if any(t.dtype != torch.float32 for t in (dw_cls, dw_box, dw_ctr)) or dw_cls.numel() != 27 * C or dw_ctr.numel() != 27 * C or dw_box.numel() != nreg * 27 * C:
+        raise ValueError("fcos_head_out_wgrad: fp32 gradient buffers of the shapes of the weights")
+    ws = torch.empty((lib().cdll.nmh_fcos_head_wgrad_ws_floats(L, dims, N, C),), dtype=torch.float32, device=flat[0].device)
+    lib().call("nmh_fcos_head_out_wgrad", dt_of(flat[0]), L, dims, N, C, nreg, int(bool(ctr_on_reg)), _ptr_table(flat), _ptr_table(gflat), ws, dw_cls, dw_box, dw_ctr, _st())
+    return ws

@@ -8,6 +8,7 @@
     convT_k_eq_s_fwd / _bwd                 ConvTranspose3d(kernel = stride) (unetr_block.py:151-158)
     conv3d_3x3x3_fwd / _dgrad / _wgrad      nn.Conv3d(k = 3, padding = 1, bias-free use) (unetr_block.py:35-44)
     instnorm_lrelu_add_fwd / _bwd           InstanceNorm3d (+ residual) -> LeakyReLU(0.01) (unetr_block.py:57-71)
+    groupnorm_relu_fwd / groupnorm_relu_bwd nn.GroupNorm(G, C) -> nn.ReLU of the FCOS head's towers (nerf_rpn/model/fcos/fcos.py:63-64, 75-76)
     mae_loss_fwd / mae_loss_bwd             UnetOutBlock 1x1 conv + forward_loss (swin_mae3d.py:1513-1549)
     adamw_clip_step                         clip_grad_norm_ + AdamW on flat buffers (run_swin_mae3d.py:665-669)
 
@@ -232,6 +233,24 @@ def instnorm_lrelu_add_bwd(dout: Tensor, saved):
     dr = torch.empty_like(xt) if has_r else None
     ops.instnorm_bwd_apply(d, out, xt, stats, sums, dx, B, V, C, rmode=rmode, dr=dr, slope=slope)
     return dx.view(dout.shape), (dr.view(dout.shape) if has_r else None)
+
+
+# ---- GroupNorm + ReLU --------------------------------------------------------------------------------------------------------------------
+def groupnorm_relu_fwd(x: Tensor, gamma: Tensor, beta: Tensor, groups: int = 32, eps: float = 1e-5):
+    """x (N, ..., C) channels-last, C % 32 == 0 -> (relu(GroupNorm(x)), saved)"""
+    xt = x.reshape(x.shape[0], -1, 1, 1, x.shape[-1]).contiguous()
+    g, b = _w(gamma, torch.float32), _w(beta, torch.float32)
+    stats = ops.fcos_gn_stats([xt], groups, eps)
+    y = ops.fcos_gn_apply([xt], [0], stats, [g, None], [b, None], groups)[0]
+    return y.view(x.shape), (xt, y, stats, g, groups)
+
+
+def groupnorm_relu_bwd(dy: Tensor, saved):
+    """-> (dx, dgamma, dbeta)"""
+    xt, y, stats, g, groups = saved
+    dg, db = torch.zeros_like(g), torch.zeros_like(g)
+    dx = ops.fcos_gn_bwd([dy.reshape(xt.shape).contiguous()], [xt], [y], [0], stats, [g, None], [dg, None], [db, None], groups)[0]
+    return dx.view(dy.shape), dg, db
 
 
 # ---- 1x1 head + masked MSE ---------------------------------------------------------------------------------------------------------------
