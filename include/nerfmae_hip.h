@@ -340,6 +340,20 @@ NMH_API int nmh_mae_tail_bwd(int dt, const void* d0, const void* r, const void* 
  * rotation [transpose axes 0,1 then flip axis 0], 2 = flip axis 0, 4 = flip axis 1, applied in that order), zero padding at the high
  * end of each axis.  The valid extents of the result are (rot ? L : W, rot ? W : L, H). */
 NMH_API int nmh_grid_prepare(int src_u8, const void* src, int W, int L, int H, float* dst, int R, int flags, void* stream);
+/* Detection input pipeline (nerf_rpn/datasets.py:173-244, 478-524).  nmh_grid_prepare_rs: nmh_grid_prepare followed, before the padding, by
+ * rotate_and_scale_scene's resample of the augmented grid (extents r0,r1,r2 = rot ? L : W, rot ? W : L, H; angle in radians): output voxel (i,j,k) inside
+ * the extents is the trilinear blend (align_corners=True, taps outside [0,r) contribute 0) of the augmented grid at
+ *   X = (2i/(r0-1) - 1) r0/2 (Y, Z alike);  qx = s (cos a X - sin a Y), qy = s (sin a X + cos a Y), qz = s Z;  a0 = (qx/(r0/2) + 1)/2 (r0-1) (a1, a2 alike)
+ * (datasets.py:481-512).  Taps are converted (/255, alpha) before blending.  Every extent must be >= 2 (-2 otherwise).  A scene without rot-scale goes
+ * through nmh_grid_prepare: angle 0, scale 1 here is still a resample (equal values up to fp32 blending with zero weights, not the same kernel).
+ * nmh_boxes_augment: the box side, z_up=True, one launch for a batch.  boxes/out: [total_rows, cols] fp32 on the device, cols 6 (xmin,ymin,zmin,xmax,ymax,
+ * zmax) or 7 (x,y,z,w,l,h,theta); itab [n_scenes][7] = first row, count, flags (1 rot, 2 flip 0, 4 flip 1), has_rs, e0, e1, e2 (the scene's extents after
+ * rot / flips) and ftab [n_scenes][2] = angle, scale are HOST arrays, copied into the launch arguments (no H2D copy, no synchronisation); n_scenes <= 64.
+ * 6 columns: rot swaps x/y and sets (xmin,xmax) = e0 - (xmax,xmin); a flip of axis a sets (min,max) = e_a - (max,min) (:208-211, 225-229).  7 columns: rot
+ * swaps x/y and w/l and sets x = e0 - x, theta unchanged; a flip mirrors the centre and negates theta (:215-217, 230-233); rot-scale (7 columns only):
+ * theta -= angle, dims /= scale, centre = (centre - e/2) @ (Rz(angle)/scale) + e/2, a row vector times the matrix (:514-522).  Rows of no scene are copied. */
+NMH_API int nmh_grid_prepare_rs(int src_u8, const void* src, int W, int L, int H, float* dst, int R, int flags, float angle, float scale, void* stream);
+NMH_API int nmh_boxes_augment(const float* boxes, float* out, int cols, int total_rows, int n_scenes, const int* itab, const float* ftab, void* stream);
 NMH_API int nmh_bias_grad(int dt, const void* dY, float* db, int64_t M, int N, const float* rowscale, int rows_per_scale, void* stream);
 NMH_API int nmh_add_inplace(int dt, void* a, const void* b, int64_t n, void* stream);
 /* out = a + b (out may alias a): the sum of the two gradients of an encoder feature map that feeds both the next stage and a decoder

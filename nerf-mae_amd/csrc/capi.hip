@@ -486,6 +486,17 @@ int nmh_grid_prepare(int src_u8, const void* src, int W, int L, int H, float* ds
   CLR();
   return k_grid_prepare(src_u8, src, W, L, H, dst, R, flags, ST);
 }
+int nmh_grid_prepare_rs(int src_u8, const void* src, int W, int L, int H, float* dst, int R, int flags, float angle, float scale, void* stream) {
+  CLR();
+  REQ(src, dst);
+  return k_grid_prepare_rs(src_u8, src, W, L, H, dst, R, flags, angle, scale, ST);
+}
+int nmh_boxes_augment(const float* boxes, float* out, int cols, int total_rows, int n_scenes, const int* itab, const float* ftab, void* stream) {
+  CLR();
+  if (total_rows <= 0) return total_rows < 0 ? -4 : 0;
+  REQ(boxes, out, itab, ftab);
+  return k_boxes_augment(boxes, out, cols, total_rows, n_scenes, itab, ftab, ST);
+}
 int nmh_bias_grad(int dt, const void* dY, float* db, int64_t M, int N, const float* rowscale, int rows_per_scale, void* stream) {
   CLR();
   if (M <= 0) return 0;

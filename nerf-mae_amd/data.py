@@ -43,6 +43,30 @@ def draw_augmentation(flip_prob: float, rotate_prob: float, rng=_random) -> int:
     return flags
 
 
+def draw_detection_augmentation(flip_prob: float, rotate_prob: float, rot_scale_prob: float, oriented: bool, rng=_random) -> Tuple[int, float, float]:
+    """(flags, angle, scale) of one scene of the detection path, drawn in the reference's order (datasets.py:181-244, z_up=True): rotation, flip 0,
+    flip 1; then, for oriented (7-column) boxes only, one draw against `rot_scale_prob` and, if it is taken, uniform(-pi/18, pi/18) and uniform(0.9, 1.1).
+    Axis-aligned boxes make exactly three draws.  (0.0, 1.0) means that rot-scale was not taken: the scene goes through `ops.grid_prepare`"""
+    if not (0.0 <= flip_prob <= 1.0):
+        raise ValueError("flip_prob must be between 0 and 1, but got {}".format(flip_prob))
+    if not (0.0 <= rotate_prob <= 1.0):
+        raise ValueError("rotate_prob must be between 0 and 1, but got {}".format(rotate_prob))
+    if not (0.0 <= rot_scale_prob <= 1.0):
+        raise ValueError(f"rotate_and_scale_prob must be between 0 and 1, but got {rot_scale_prob}")
+    flags = 0
+    if rng.random() < rotate_prob:
+        flags |= ops.GRID_ROT
+    if rng.random() < flip_prob:
+        flags |= ops.GRID_FLIP0
+    if rng.random() < flip_prob:
+        flags |= ops.GRID_FLIP1
+    angle, scale = 0.0, 1.0
+    if oriented and rng.random() < rot_scale_prob:
+        angle = rng.uniform(-np.pi / 18, np.pi / 18)
+        scale = rng.uniform(0.9, 1.1)
+    return flags, angle, scale
+
+
 def synthetic_scene(shape: Sequence[int] = (160, 160, 160), seed: int = 0, dtype=np.float32) -> np.ndarray:
     """A stored-format synthetic scene (W,L,H,4) following SURVEY 8(d): RGB ~ U[0,1); raw density sigma ~ N(0,3^2) inside the
     central 60 % box and -10 outside (float32), so that density->alpha gives a realistic occupied fraction; uint8: RGB and an
@@ -180,6 +204,82 @@ class GridBatcher:
             if k is not None:
                 self._slots[i].release_after(k, st)
         return xb, ext
+
+
+class DetectionBatcher(GridBatcher):
+    """Input of the detection stack: stored scenes and their boxes -> `(xb (B,4,R,R,R) fp32, extents, targets)`, targets being the per-scene fp32 device
+    tensors [G_i, 6|7] that FCOSOverNeRF, NeRFRegionProposalNetwork, fcos_targets and rpn_assign_targets take (views of one buffer).  What the reference's
+    BaseDataset.augment_rpn_inputs does per scene on the CPU (datasets.py:173-244, 478-524) is one scene kernel per scene -- `ops.grid_prepare`, or
+    `ops.grid_prepare_rs` for a scene that drew the small rotation + scaling -- and ONE box kernel per batch (`ops.boxes_augment`, its per-scene table passed
+    as kernel arguments).  Scenes go through GridBatcher's pinned rings, host boxes through one pinned buffer of their own; nothing synchronises."""
+
+    def __init__(self, resolution: int, device, normalize_density: bool = True, flip_prob: float = 0.0, rotate_prob: float = 0.0,
+                 rot_scale_prob: float = 0.0, depth: int = 3, z_up: bool = True):
+        if not z_up:
+            raise NotImplementedError("DetectionBatcher: only z-up scenes (the reference's z_up=False, Hypersim, is not built)")
+        super().__init__(resolution, device, normalize_density, flip_prob, rotate_prob, depth)
+        self.rot_scale_prob = rot_scale_prob
+        self._box_ring = _PinnedSlot(depth, self.device)
+
+    def __call__(self, scenes: List[Scene], boxes, params=None, out: Optional[torch.Tensor] = None, rng=_random):
+        xb, ext, targets = self.prepare(scenes, boxes, params, out, rng)
+        return xb, torch.tensor(ext, dtype=torch.int32).to(self.device, non_blocking=True), targets
+
+    def _stage_boxes(self, boxes, cols: int, counts: List[int]):
+        """-> (device tensor [sum G, cols] holding the untransformed boxes, ring index or None)"""
+        total = sum(counts)
+        if total == 0:
+            return torch.empty((0, cols), dtype=torch.float32, device=self.device), None
+        if all(isinstance(b, torch.Tensor) and b.is_cuda for b in boxes):
+            return torch.cat([b.to(torch.float32).reshape(-1, cols) for b in boxes]).contiguous(), None
+        k, pin, dev = self._box_ring.acquire(total * cols, torch.float32)
+        pin, dev = pin.view(total, cols), dev.view(total, cols)
+        first = 0
+        for b, n in zip(boxes, counts):
+            if n and not (isinstance(b, torch.Tensor) and b.is_cuda):
+                pin[first:first + n].copy_(torch.as_tensor(b).reshape(n, cols))
+            first += n
+        dev.copy_(pin, non_blocking=True)
+        first = 0
+        for b, n in zip(boxes, counts):
+            if n and isinstance(b, torch.Tensor) and b.is_cuda:
+                dev[first:first + n].copy_(b.reshape(n, cols))
+            first += n
+        return dev, k
+
+    def prepare(self, scenes: List[Scene], boxes, params=None, out: Optional[torch.Tensor] = None, rng=_random):
+        """boxes: one [G_i, 6|7] array per scene (numpy, host tensor or device tensor; the same column count in every scene); params: one
+        (flags, angle, scale) per scene as `draw_detection_augmentation` returns them, None: drawn here from `rng`, scene by scene"""
+        B, R = len(scenes), self.R
+        if len(boxes) != B:
+            raise ValueError("DetectionBatcher: one box array per scene")
+        cols = {int(b.shape[-1]) for b in boxes}
+        if len(cols) != 1 or not cols <= {6, 7} or any(b.ndim != 2 for b in boxes):
+            raise ValueError("DetectionBatcher: boxes must be [G, 6] in every scene or [G, 7] in every scene")
+        cols = cols.pop()
+        counts = [int(b.shape[0]) for b in boxes]
+        xb = out if out is not None else torch.empty((B, 4, R, R, R), dtype=torch.float32, device=self.device)
+        st = torch.cuda.current_stream()
+        staged = [self._stage_begin(i, sc) for i, sc in enumerate(scenes)]     # all host copies of the batch in flight at once
+        ext, table, first = [], [], 0
+        for i in range(B):
+            f, angle, scale = params[i] if params is not None else draw_detection_augmentation(self.flip_prob, self.rotate_prob, self.rot_scale_prob, cols == 7, rng)
+            has_rs = (angle, scale) != (0.0, 1.0)
+            if has_rs and cols != 7:
+                raise ValueError("DetectionBatcher: rot-scale needs oriented (7-column) boxes")
+            src, k = self._stage_end(*staged[i]), staged[i][1]
+            g = f | ops.GRID_DENSITY if self.normalize_density and src.dtype == torch.float32 else f
+            e = ops.grid_prepare_rs(src, xb[i], R, g, angle, scale) if has_rs else ops.grid_prepare(src, xb[i], R, g)
+            if k is not None:
+                self._slots[i].release_after(k, st)
+            ext.append(list(e))
+            table.append((first, counts[i], f, has_rs, e, angle, scale))
+            first += counts[i]
+        dev, k = self._stage_boxes(boxes, cols, counts)
+        outb = ops.boxes_augment(dev, table)
+        if k is not None:
+            self._box_ring.release_after(k, st)
+        return xb, ext, [outb[t[0]:t[0] + t[1]] for t in table]
 
 
 def pin_scene(scene: np.ndarray) -> torch.Tensor:

@@ -1160,6 +1160,51 @@ def grid_prepare(src, dst, R, flags=0):
     return (L, W, H) if flags & GRID_ROT else (W, L, H)
 
 
+def grid_prepare_rs(src, dst, R, flags=0, angle=0.0, scale=1.0):
+    """grid_prepare with rotate_and_scale_scene's trilinear resample (nerf_rpn/datasets.py:478-512) of the augmented grid before the padding; returns
+    the valid extents.  Always resamples: a scene that drew no rot-scale belongs in grid_prepare"""
+    _chk(src, dst)
+    if src.dim() != 4 or src.shape[3] != 4 or src.dtype not in (torch.float32, torch.uint8):
+        raise ValueError("grid_prepare_rs: src must be (W,L,H,4) float32 or uint8")
+    W, L, H, _ = src.shape
+    if dst.dtype != torch.float32 or dst.numel() != 4 * R ** 3:
+        raise ValueError("grid_prepare_rs: dst must be the (4,R,R,R) float32 slot")
+    lib().call("nmh_grid_prepare_rs", int(src.dtype == torch.uint8), src, W, L, H, dst, R, flags, angle, scale, _st())
+    return (L, W, H) if flags & GRID_ROT else (W, L, H)
+
+
+BOX_SCENES_PER_LAUNCH = 64   # csrc/det_input.hip: NMH_BOX_SCENES
+
+
+def boxes_augment(boxes, table, out=None):
+    """boxes: [sum G, 6|7] fp32 on the device, the scenes' boxes concatenated; table: per scene (first row, count, flags, has_rs, (e0,e1,e2), angle, scale),
+    e the scene's extents after rot / flips -> the boxes after augment_rpn_inputs' transforms (nerf_rpn/datasets.py:206-233, 514-522, z_up=True).  The table
+    travels as kernel arguments (as step_params' values do): one launch per 64 scenes, no copy, no synchronisation"""
+    _chk(boxes, out)
+    if boxes.dim() != 2 or boxes.shape[1] not in (6, 7) or boxes.dtype != torch.float32 or not boxes.is_contiguous():
+        raise ValueError("boxes_augment: boxes must be contiguous [N, 6|7] float32")
+    if out is None:
+        out = torch.empty_like(boxes)
+    elif out.shape != boxes.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("boxes_augment: out must match boxes")
+    rows, cols = boxes.shape
+    for first, count, flags, has_rs, ext, angle, scale in table:
+        if first < 0 or count < 0 or first + count > rows or (has_rs and cols != 7):
+            raise ValueError("boxes_augment: a scene's rows lie outside the boxes, or rot-scale on 6-column boxes")
+    if rows == 0:
+        return out
+    if not table:
+        out.copy_(boxes)
+        return out
+    for a in range(0, len(table), BOX_SCENES_PER_LAUNCH):
+        part = table[a:a + BOX_SCENES_PER_LAUNCH]
+        it = [int(v) for first, count, flags, has_rs, ext, angle, scale in part for v in (first, count, flags, bool(has_rs), ext[0], ext[1], ext[2])]
+        ft = [float(v) for first, count, flags, has_rs, ext, angle, scale in part for v in (angle, scale)]
+        # every launch writes all rows (rows of scenes outside its part are copied); later parts therefore transform in place
+        lib().call("nmh_boxes_augment", boxes if a == 0 else out, out, cols, rows, len(part), (ctypes.c_int * len(it))(*it), (ctypes.c_float * len(ft))(*ft), _st())
+    return out
+
+
 def bias_grad(dY, db, M, N, rowscale=None, rows_per_scale=1):
     _chk(dY, db, rowscale)
     lib().call("nmh_bias_grad", dt_of(dY), dY, db, M, N, rowscale, rows_per_scale, _st())
