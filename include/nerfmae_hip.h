@@ -549,6 +549,25 @@ NMH_API int nmh_roi_loss_fwd(int64_t M, int n_classes, int ncols, const float* s
 NMH_API int nmh_roi_loss_bwd(int64_t M, int n_classes, int ncols, const float* scores, const float* deltas, const float* labels, const float* targets, const float* scalars, const float* g_obj, const float* g_reg, float* dscores, float* ddeltas, void* stream);
 /* RotatedCoder.decode_single (coder/rotated_coder.py:57-121) / AABBCoder.decode_single (coder/AABB_coder.py:86-137), detector.py:609-611. */
 NMH_API int nmh_roi_decode(int64_t M, int ncols, const float* deltas, const float* rois, int roi_stride, float* boxes, void* stream);
+/* ---- detection evaluation (nerf_rpn/eval.py; kernels, tie rules and the two stated deviations: csrc/det_eval.hip) ----
+ * Common arguments.  N scenes; boxes [N][cap] rows of row_stride floats in DESCENDING score with the box in columns col_offset .. col_offset + ncols - 1 (ncols 6:
+ * x0,y0,z0,x1,y1,z1; 7: x,y,z,w,l,h,theta), read in place; counts [N]; gt [N][Gmax][ncols] padded, gt_counts [N].  cap <= 16384, Gmax <= 1024, at most 8 limits and
+ * 8 thresholds, col_offset + ncols <= row_stride, else -4; a NULL required pointer is -4.  N == 0 returns 0 without a launch.  Nothing waits on the host.
+ * nmh_det_eval_iou: box_iou_3d (model/utils.py:387-415) of every scene, as eval.py:36 and :357 call it -> iouT [N][Gmax][cap] (ground-truth-major; only entries
+ * below counts and gt_counts are written), best_iou, best_gt [N][cap] = overlaps.max(dim=1) of eval.py:358, ties to the lower gt; (0, -1) without ground truth or
+ * past counts. */
+NMH_API int nmh_det_eval_iou(int ncols, int N, int cap, int row_stride, int col_offset, const float* boxes, const int* counts, int Gmax, const float* gt, const int* gt_counts, float* iouT, float* best_iou, int* best_gt, void* stream);
+/* evaluate_box_proposals_recall's per-scene half (eval.py:22-59) for nlimits limits at once; limits HOST int [nlimits], negative: no cut -> gt_overlaps
+ * [N][nlimits][Gmax] (the recorded IoUs in the order they were taken, 0 up to gt_counts, -1 behind it and in every slot of a skipped scene), counted [N][nlimits] =
+ * the scene's contribution to num_pos (gt_counts, or 0 for a scene skipped by eval.py:28). */
+NMH_API int nmh_det_eval_match(int N, int cap, int Gmax, const int* counts, const int* gt_counts, const float* iouT, int nlimits, const int* limits, float* gt_overlaps, int* counted, void* stream);
+/* evaluate_box_proposals_ap's true-positive test (eval.py:331-366) per scene for nthresh IoU thresholds (HOST float [nthresh]) without the sequential walk;
+ * top_k <= 0: no cut -> tp_mask [N][cap] bytes (bit q: true positive at thresholds[q]), kept [N][cap] bytes (row < min(counts, top_k)). */
+NMH_API int nmh_det_eval_claims(int N, int cap, int Gmax, const int* counts, const float* best_iou, const int* best_gt, int nthresh, const float* thresholds, int top_k, unsigned char* tp_mask, unsigned char* kept, void* stream);
+/* eval.py:368-387 for nthresh thresholds: bits [M] = the tp_mask bytes in the global descending-score order with the kept detections first; n_det [1] their
+ * number, num_gt [1] (DEVICE ints) -> tp_cum, fp_cum [nthresh][M] int32, recalls, precisions [nthresh][M] fp32 (zeros from n_det on), ap [nthresh] fp64.
+ * M == 0 returns 0 without a launch and leaves ap untouched. */
+NMH_API int nmh_det_eval_pr(int64_t M, const unsigned char* bits, const int* n_det, const int* num_gt, int nthresh, int* tp_cum, int* fp_cum, float* recalls, float* precisions, double* ap, void* stream);
 /* ---- RPNHead's output stage (nerf_rpn/model/anchor.py:177-224; kernels, fragment maps and semantics: csrc/rpn_head.hip) ----
  * level_vox: HOST int [nlevels] = W H D per level, 1 <= nlevels <= 4; N scenes; Cin a multiple of 8; 1 <= A <= 32 anchors per location; C 6 | 8, else -4.
  * t: HOST table of per-level DEVICE activations (N, W, H, D, Cin) channels-last in dt; w_cls [A][Cin], w_box [A C][Cin] in dt (the head's column j is row j

@@ -5,3 +5,13 @@ Public surface mirrors the reference (nerf_mae/model/mae/swin_mae3d.py, run_swin
 contract and `state_dict()` keys.  All arithmetic runs in libnerfmae_hip.so (hand-written HIP); there is no CPU
 fallback and importing the model without the built library fails loudly."""
 __version__ = "0.1.0"
+
+_DET_EVAL = ("det_eval_dense", "DetectionEvaluator", "evaluate_box_proposals_recall", "evaluate_box_proposals_ap")
+
+
+def __getattr__(name):
+    # detection evaluation (det_eval.py), loaded on first use so that importing the package stays as light as before
+    if name in _DET_EVAL:
+        from . import det_eval
+        return getattr(det_eval, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -873,6 +873,42 @@ int nmh_roi_decode(int64_t M, int ncols, const float* deltas, const float* rois,
   REQ(deltas, rois, boxes);
   return k_roi_decode((long)M, ncols, deltas, rois, roi_stride, boxes, ST);
 }
+static bool det_eval_dims_ok(int N, int cap, int Gmax) { return N >= 0 && cap >= 0 && cap <= NMH_OBB_NMS_MAX && Gmax >= 0 && Gmax <= NMH_DET_EVAL_MAX_GT; }
+int nmh_det_eval_iou(int ncols, int N, int cap, int row_stride, int col_offset, const float* boxes, const int* counts, int Gmax, const float* gt, const int* gt_counts, float* iouT,
+                     float* best_iou, int* best_gt, void* stream) {
+  CLR();
+  if ((ncols != 6 && ncols != 7) || !det_eval_dims_ok(N, cap, Gmax) || col_offset < 0 || row_stride < col_offset + ncols) return -4;
+  if (N == 0 || cap == 0) return 0;
+  REQ(boxes, counts, gt_counts, best_iou, best_gt);
+  if (Gmax > 0) REQ(gt, iouT);
+  return k_det_eval_iou(ncols, N, cap, row_stride, col_offset, boxes, counts, Gmax, gt, gt_counts, iouT, best_iou, best_gt, ST);
+}
+int nmh_det_eval_match(int N, int cap, int Gmax, const int* counts, const int* gt_counts, const float* iouT, int nlimits, const int* limits, float* gt_overlaps, int* counted,
+                       void* stream) {
+  CLR();
+  if (!det_eval_dims_ok(N, cap, Gmax) || nlimits < 1 || nlimits > NMH_DET_EVAL_MAX_LIMITS) return -4;
+  if (N == 0) return 0;
+  REQ(counts, gt_counts, limits, counted);
+  if (Gmax > 0) REQ(gt_overlaps);
+  if (Gmax > 0 && cap > 0) REQ(iouT);
+  return k_det_eval_match(N, cap, Gmax, counts, gt_counts, iouT, nlimits, limits, gt_overlaps, counted, ST);
+}
+int nmh_det_eval_claims(int N, int cap, int Gmax, const int* counts, const float* best_iou, const int* best_gt, int nthresh, const float* thresholds, int top_k,
+                        unsigned char* tp_mask, unsigned char* kept, void* stream) {
+  CLR();
+  if (!det_eval_dims_ok(N, cap, Gmax) || nthresh < 1 || nthresh > NMH_DET_EVAL_MAX_THRESH) return -4;
+  if (N == 0 || cap == 0) return 0;
+  REQ(counts, best_iou, best_gt, thresholds, tp_mask, kept);
+  return k_det_eval_claims(N, cap, Gmax, counts, best_iou, best_gt, nthresh, thresholds, top_k, tp_mask, kept, ST);
+}
+int nmh_det_eval_pr(int64_t M, const unsigned char* bits, const int* n_det, const int* num_gt, int nthresh, int* tp_cum, int* fp_cum, float* recalls, float* precisions, double* ap,
+                    void* stream) {
+  CLR();
+  if (M < 0 || M > 0x7fffffffll || nthresh < 1 || nthresh > NMH_DET_EVAL_MAX_THRESH) return -4;
+  if (M == 0) return 0;
+  REQ(bits, n_det, num_gt, tp_cum, fp_cum, recalls, precisions, ap);
+  return k_det_eval_pr((long)M, bits, n_det, num_gt, nthresh, tp_cum, fp_cum, recalls, precisions, ap, ST);
+}
 int nmh_clip_coef(const double* acc, float max_norm, float* coef, float* norm_out, void* stream) {
   CLR(); return k_clip_coef(acc, max_norm, coef, norm_out, ST); }
 int nmh_adamw_step(float* p, float* g, float* m, float* v, int64_t n, const float* hyper, const float* coef, void* stream) {

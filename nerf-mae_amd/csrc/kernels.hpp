@@ -349,6 +349,19 @@ int k_roi_loss_fwd(long M, int n_classes, int ncols, const float* scores, const 
 int k_roi_loss_bwd(long M, int n_classes, int ncols, const float* scores, const float* deltas, const float* labels, const float* targets, const float* scalars, const float* g_obj,
                    const float* g_reg, float* dscores, float* ddeltas, hipStream_t st);
 int k_roi_decode(long M, int ncols, const float* deltas, const float* rois, int roi_stride, float* out, hipStream_t st);
+// ---- det_eval.hip (detection evaluation: IoU matrix and row best, greedy recall matching, AP claims, precision / recall scan) ----
+// limits, thresholds: HOST arrays; everything else DEVICE.  Layouts, tie rules and the deviations from eval.py: det_eval.hip.
+#define NMH_DET_EVAL_MAX_GT 1024
+#define NMH_DET_EVAL_MAX_LIMITS 8
+#define NMH_DET_EVAL_MAX_THRESH 8
+int k_det_eval_iou(int ncols, int N, int cap, int row_stride, int col_offset, const float* boxes, const int* counts, int Gmax, const float* gt, const int* gt_counts, float* iouT,
+                   float* best_iou, int* best_gt, hipStream_t st);
+int k_det_eval_match(int N, int cap, int Gmax, const int* counts, const int* gt_counts, const float* iouT, int nlimits, const int* limits, float* gt_overlaps, int* counted,
+                     hipStream_t st);
+int k_det_eval_claims(int N, int cap, int Gmax, const int* counts, const float* best_iou, const int* best_gt, int nthresh, const float* thresholds, int top_k, unsigned char* tp_mask,
+                      unsigned char* kept, hipStream_t st);
+int k_det_eval_pr(long M, const unsigned char* bits, const int* n_det, const int* num_gt, int nthresh, int* tp_cum, int* fp_cum, float* recalls, float* precisions, double* ap,
+                  hipStream_t st);
 // ---- rpn_head.hip (RPNHead's output stage: cls_logits + bbox_pred from the channels-last activation to the NCDHW fp32 planes, and back; ReLU passes) ----
 // vox: HOST [nlevels] voxels per scene; t / obj / reg / g_* / dt_out: HOST tables of nlevels DEVICE pointers.  Layouts: rpn_head.hip.
 long k_rpn_head_bwd_ws_floats(int nlevels, const int* vox, int N, int Cin, int A, int C);

@@ -2184,3 +2184,44 @@ def fcos_head_out_wgrad(acts, gt, nreg, ctr_on_reg, dw_cls, dw_box, dw_ctr):
     ws = torch.empty((lib().cdll.nmh_fcos_head_wgrad_ws_floats(L, dims, N, C),), dtype=torch.float32, device=flat[0].device)
     lib().call("nmh_fcos_head_out_wgrad", dt_of(flat[0]), L, dims, N, C, nreg, int(bool(ctr_on_reg)), _ptr_table(flat), _ptr_table(gflat), ws, dw_cls, dw_box, dw_ctr, _st())
     return ws
+
+
+# ---- detection evaluation: IoU and row best, greedy recall matching, AP claims, precision / recall scan (csrc/det_eval.hip) ----------------------
+DET_EVAL_MAX_GT, DET_EVAL_MAX_LIMITS, DET_EVAL_MAX_THRESH = 1024, 8, 8
+
+
+def det_eval_match(boxes, counts, gt, gt_counts, limits, thresholds, top_k, col_offset=0):
+    """boxes [N,cap,col_offset+6|7+..] rows in descending score, counts [N] int32, gt [N,Gmax,6|7] padded, gt_counts [N] int32; limits: ints (negative: no cut),
+    thresholds: floats, top_k <= 0: no cut -> (gt_overlaps [N,L,Gmax], counted [N,L] int32, best_iou [N,cap], best_gt [N,cap] int32, tp_mask [N,cap] uint8,
+    kept [N,cap] uint8).  Three launches, nothing but the outputs and the IoU workspace is allocated, and the host does not wait."""
+    _chk(boxes, counts, gt, gt_counts)
+    N, cap, stride = boxes.shape
+    Gmax, ncols = gt.shape[1], gt.shape[2]
+    if any(t.dtype != torch.float32 for t in (boxes, gt)) or any(t.dtype != torch.int32 for t in (counts, gt_counts)) or gt.shape[0] != N or counts.numel() != N or gt_counts.numel() != N:
+        raise RuntimeError("det_eval_match: fp32 boxes [N,cap,C] and gt [N,Gmax,6|7], int32 counts [N] and gt_counts [N]")
+    L, T, dev = len(limits), len(thresholds), boxes.device
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)   # noqa: E731
+    iouT = new((N, Gmax, cap), torch.float32)
+    gt_overlaps, counted = new((N, L, Gmax), torch.float32), new((N, L), torch.int32)
+    best_iou, best_gt = new((N, cap), torch.float32), new((N, cap), torch.int32)
+    tp_mask, kept = new((N, cap), torch.uint8), new((N, cap), torch.uint8)
+    lim = (ctypes.c_int * L)(*[int(v) for v in limits])
+    thr = (ctypes.c_float * T)(*[float(v) for v in thresholds])
+    lib().call("nmh_det_eval_iou", ncols, N, cap, stride, col_offset, boxes, counts, Gmax, gt, gt_counts, iouT, best_iou, best_gt, _st())
+    lib().call("nmh_det_eval_match", N, cap, Gmax, counts, gt_counts, iouT, L, lim, gt_overlaps, counted, _st())
+    lib().call("nmh_det_eval_claims", N, cap, Gmax, counts, best_iou, best_gt, T, thr, int(top_k), tp_mask, kept, _st())
+    return gt_overlaps, counted, best_iou, best_gt, tp_mask, kept
+
+
+def det_eval_pr(bits, n_det, num_gt, nthresh):
+    """bits [M] uint8 (the true-positive byte-masks in the global descending-score order, kept detections first), n_det, num_gt int32 [1] on the device ->
+    (tp_cum, fp_cum [T,M] int32, recalls, precisions [T,M] fp32, ap [T] fp64); ap is 0 for M == 0"""
+    _chk(bits, n_det, num_gt)
+    if bits.dtype != torch.uint8 or n_det.dtype != torch.int32 or num_gt.dtype != torch.int32:
+        raise RuntimeError("det_eval_pr: uint8 bits, int32 n_det and num_gt")
+    M, dev = bits.numel(), bits.device
+    tp_cum, fp_cum = (torch.empty((nthresh, M), dtype=torch.int32, device=dev) for _ in range(2))
+    recalls, precisions = (torch.empty((nthresh, M), dtype=torch.float32, device=dev) for _ in range(2))
+    ap = torch.zeros((nthresh,), dtype=torch.float64, device=dev)
+    lib().call("nmh_det_eval_pr", M, bits, n_det, num_gt, nthresh, tp_cum, fp_cum, recalls, precisions, ap, _st())
+    return tp_cum, fp_cum, recalls, precisions, ap
