@@ -31,11 +31,11 @@ from torch import nn
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import ops
+from . import conv_layer, ops
 from .fcos_inference import FCOSPostProcessor, fcos_postprocess_dense
 from .fcos_loss import FCOSLossComputation
-from .fpn import _NCDHWToCL
-from .model import _gradbuf, _Packer
+from .fpn import _NCDHWToCL, check_channels_last
+from .model import _gradbuf
 
 MAX_LEVELS = ops.FCOS_HEAD_MAX_LEVELS
 
@@ -55,7 +55,7 @@ class _FCOSHeadFn(Function):
 
     @staticmethod
     def forward(ctx, head, mode, *feats):
-        pk, C, depth, L = head._pk, head.in_channels, head.num_convs, len(feats)
+        pk, depth, L = head._pk, head.num_convs, len(feats)
         towers = [0, 1] * L
         cur = [f.contiguous() for f in feats for _ in (0, 1)]
         saved = []
@@ -63,11 +63,7 @@ class _FCOSHeadFn(Function):
             xs = []
             for j, a in enumerate(cur):
                 t = j & 1
-                conv = head._tower(t)[3 * k]
-                if ops.use_conv64(a, C) and f"t{t}c{k}.w64" in pk.views:
-                    xs.append(ops.conv3d_k3_c64(a, pk[f"t{t}c{k}.w64"], C, bias=conv.bias))
-                else:
-                    xs.append(ops.conv3d_k3_bias(a, pk[f"t{t}c{k}.w"], conv.bias, C))
+                xs.append(conv_layer.forward(pk, f"t{t}c{k}", head._tower(t)[3 * k], a))
             gn = [head._tower(t)[3 * k + 1] for t in (0, 1)]
             stats = ops.fcos_gn_stats(xs, gn[0].num_groups, gn[0].eps)
             ys = ops.fcos_gn_apply(xs, towers, stats, [g.weight for g in gn], [g.bias for g in gn], gn[0].num_groups)
@@ -102,16 +98,7 @@ class _FCOSHeadFn(Function):
             dcur = []
             for j, dx in enumerate(dxs):
                 t = j & 1
-                conv = head._tower(t)[3 * k]
-                with ops.side_stream():
-                    ops.conv3d_k3_wgrad(dx, inp[j], _gradbuf(conv.weight))
-                    ops.bias_grad(dx.view(-1, C), _gradbuf(conv.bias), dx.numel() // C, C)
-                if k == 0 and not ctx.needs_input_grad[2 + j // 2]:
-                    dcur.append(None)
-                elif ops.use_conv64(dx, C) and f"t{t}c{k}.w64d" in pk.views:
-                    dcur.append(ops.conv3d_k3_c64(dx, pk[f"t{t}c{k}.w64d"], C))
-                else:
-                    dcur.append(ops.conv3d_k3(dx, pk[f"t{t}c{k}.wd"], C))
+                dcur.append(conv_layer.backward(pk, f"t{t}c{k}", head._tower(t)[3 * k], dx, inp[j], need_dx=k > 0 or ctx.needs_input_grad[2 + j // 2]))
         dfeats = [None if dcur[2 * l] is None or not ctx.needs_input_grad[2 + l] else ops.add_inplace(dcur[2 * l], dcur[2 * l + 1]) for l in range(L)]
         ops.join_side()
         del keep
@@ -167,34 +154,26 @@ class FCOSHead(nn.Module):
 
     def _pack(self):
         ps = list(self.parameters())
-        if not ps[0].is_cuda:
-            raise RuntimeError("FCOSHead (HIP) needs its parameters on a HIP device: call .cuda() first (no CPU fallback)")
-        key = tuple(p.data_ptr() for p in ps)
-        if self._pk is None or self._pk_key != key:
+
+        def fill(P):
             # the output convs of one tower as one 16-row weight (csrc/fcos_head.hip: tower columns); the rows past the tower's columns stay zero
             self._w16 = [torch.zeros((16, self.in_channels, 3, 3, 3), dtype=torch.float32, device=ps[0].device) for _ in (0, 1)]
-            P = _Packer()
             for t in (0, 1):
                 for k in range(self.num_convs):
-                    w = self._tower(t)[3 * k].weight
-                    P.add(f"t{t}c{k}.w", w, P.CONV_F)
-                    P.add(f"t{t}c{k}.wd", w, P.CONV_D)
-                    if self.compute_dtype == torch.bfloat16 and self.in_channels % 64 == 0:
-                        P.add(f"t{t}c{k}.w64", w, P.C64_F)
-                        P.add(f"t{t}c{k}.w64d", w, P.C64_D)
+                    conv_layer.register(P, f"t{t}c{k}", self._tower(t)[3 * k], self.compute_dtype)
                 P.add(f"o{t}.w", self._w16[t], P.CONV_F)
                 P.add(f"o{t}.wd", self._w16[t], P.CONV_D)
-            P.build(self.compute_dtype, ps[0].device)
-            P.split = None
-            self._pk, self._pk_key = P, key
-        with torch.no_grad():
+
+        @torch.no_grad()
+        def refresh():
             self._w16[0][0].copy_(self.cls_logits.weight[0])
             self._w16[1][:self.num_reg].copy_(self.bbox_pred.weight)
             if self.centerness_on_reg:
                 self._w16[1][self.num_reg].copy_(self.centerness.weight[0])
             else:
                 self._w16[0][1].copy_(self.centerness.weight[0])
-        self._pk.run()
+
+        conv_layer.ensure_packed(self, ps, "FCOSHead (HIP) needs its parameters on a HIP device: call .cuda() first (no CPU fallback)", fill, refresh)
 
     def forward_channels_last(self, feats):
         """feats: per level a channels-last (N, W, L, H, C) tensor in the compute dtype -> (logits, bbox_reg, centerness), lists of fp32 NCDHW tensors"""
@@ -203,11 +182,7 @@ class FCOSHead(nn.Module):
             raise ValueError(f"FCOSHead supports 1 to {MAX_LEVELS} levels (the reference has {MAX_LEVELS} scales), got {len(feats)}")
         if len(feats) > len(self.fpn_strides):
             raise ValueError(f"FCOSHead: {len(feats)} levels but {len(self.fpn_strides)} fpn_strides")
-        for f in feats:
-            if not f.is_cuda:
-                raise RuntimeError("FCOSHead (HIP) needs HIP device tensors (no CPU fallback)")
-            if f.dim() != 5 or f.shape[-1] != self.in_channels or f.dtype != self.compute_dtype:
-                raise ValueError(f"FCOSHead: channels-last (N, W, L, H, {self.in_channels}) features in {self.compute_dtype}, got {tuple(f.shape)} {f.dtype}")
+        check_channels_last("FCOSHead", "W, L, H", feats, self.in_channels, self.compute_dtype)
         self._pack()
         mode = ("train" if self.training else "eval") if self.norm_reg_targets else "exp"
         out = _FCOSHeadFn.apply(self, mode, *feats)

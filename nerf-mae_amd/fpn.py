@@ -5,7 +5,7 @@ stage outputs, `forward(x (B,4,R,R,R)) -> tuple of 4 NCDHW maps`.  Same construc
 `fpn_neck`, `out_channels`) and state_dict keys as the reference, so detection heads and checkpoints are interchangeable.
 
 Everything between the input grid and the returned maps runs in the HIP library (channels-last, compute dtype): encoder kernels of
-model.py, 1x1 lateral convs = `gemm_nt` with bias, top-down `nearest_upsample_add`, 3x3x3 output convs = `conv3d_k3_bias`, and
+model.py, 1x1 lateral convs = `gemm_nt` with bias, top-down `nearest_upsample_add`, 3x3x3 output convs = `conv_layer`, and
 one transposing store to the NCDHW fp32 layout the heads consume.  Backward launches the matching dgrad / wgrad kernels.  No CPU
 fallback: the ops raise without the library or with CPU tensors."""
 from __future__ import annotations
@@ -16,7 +16,7 @@ from typing import List, Optional, Sequence
 import torch
 from torch import Tensor, nn
 
-from . import ops
+from . import conv_layer, ops
 from .model import SWIN_CONFIGS, SwinTransformer_MAE3D_New, _EmbedFn, _gradbuf, _Packer
 
 
@@ -37,11 +37,7 @@ class _FPNFn(torch.autograd.Function):
             ops.nearest_upsample_add(lats[i], lats[i - 1])
         outs = []
         for i, lat in enumerate(lats):
-            if ops.use_conv64(lat, Co) and f"f{i}.w64" in pk.views:   # LDS-halo kernel on 64-channel blocks (bias in its epilogue)
-                y = ops.conv3d_k3_c64(lat, pk[f"f{i}.w64"], Co, bias=fpn.fpn_convs[i].bias)
-            else:
-                y = ops.conv3d_k3_bias(lat, pk[f"f{i}.w"], fpn.fpn_convs[i].bias, Co)
-            outs.append(ops.ndhwc_to_ncdhw(y))
+            outs.append(ops.ndhwc_to_ncdhw(conv_layer.forward(pk, f"f{i}", fpn.fpn_convs[i], lat)))
         ctx.fpn, ctx.saved = fpn, (feats, lats)
         return tuple(outs)
 
@@ -52,20 +48,12 @@ class _FPNFn(torch.autograd.Function):
         pk, Co, n = fpn._pk, fpn.out_channels, len(feats)
         dlats, keep = [], []   # keep: tensors the forked side stream still reads -- referenced until the join (the caching allocator knows nothing of that stream)
         for i, (lat, g) in enumerate(zip(lats, douts)):
-            B, D, H, W, _ = lat.shape
             if g is None:
                 dlats.append(torch.zeros_like(lat))
                 continue
             dy = ops.ncdhw_to_ndhwc(g, lat.dtype)
             keep.append(dy)
-            conv = fpn.fpn_convs[i]
-            with ops.side_stream():
-                ops.conv3d_k3_wgrad(dy, lat, _gradbuf(conv.weight))
-                ops.bias_grad(dy.view(-1, Co), _gradbuf(conv.bias), B * D * H * W, Co)
-            if ops.use_conv64(dy, Co) and f"f{i}.w64d" in pk.views:
-                dlats.append(ops.conv3d_k3_c64(dy, pk[f"f{i}.w64d"], Co))
-            else:
-                dlats.append(ops.conv3d_k3(dy, pk[f"f{i}.wd"], Co))
+            dlats.append(conv_layer.backward(pk, f"f{i}", fpn.fpn_convs[i], dy, lat))
         for i in range(1, n):   # d lat_i += adjoint of the nearest upsample of d lat_{i-1} (which is final by then)
             ops.nearest_upsample_add_bwd(dlats[i - 1], dlats[i])
         dfeats = []
@@ -110,24 +98,13 @@ class FPN(nn.Module):
                 nn.init.constant_(m.bias, 0)
 
     def _pack(self):
-        ps = list(self.parameters())
-        if not ps[0].is_cuda:
-            raise RuntimeError("FPN (HIP) needs its parameters on a HIP device: call .cuda() first (no CPU fallback)")
-        key = tuple(p.data_ptr() for p in ps)
-        if self._pk is None or self._pk_key != key:
-            P = _Packer()
+        def fill(P):
             for i, (l, c) in enumerate(zip(self.lateral_convs, self.fpn_convs)):
                 P.add(f"l{i}.w", l.weight, P.CAST)
                 P.add(f"l{i}.wT", l.weight, P.TRANS)
-                P.add(f"f{i}.w", c.weight, P.CONV_F)
-                P.add(f"f{i}.wd", c.weight, P.CONV_D)
-                if self.compute_dtype == torch.bfloat16 and c.weight.shape[0] % 64 == 0 and c.weight.shape[1] % 64 == 0:
-                    P.add(f"f{i}.w64", c.weight, P.C64_F)
-                    P.add(f"f{i}.w64d", c.weight, P.C64_D)
-            P.build(self.compute_dtype, ps[0].device)
-            P.split = None
-            self._pk, self._pk_key = P, key
-        self._pk.run()
+                conv_layer.register(P, f"f{i}", c, self.compute_dtype)
+
+        conv_layer.ensure_packed(self, list(self.parameters()), "FPN (HIP) needs its parameters on a HIP device: call .cuda() first (no CPU fallback)", fill)
 
     def forward_channels_last(self, feats: List[Tensor]):
         """feats: channels-last (B,D,H,W,C_i) tensors in the compute dtype (what the encoder kernels produce)"""
@@ -149,6 +126,15 @@ class _NCDHWToCL(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return ops.ndhwc_to_ncdhw(g.contiguous()), None
+
+
+def check_channels_last(name: str, axes: str, feats, channels: int, dtype: torch.dtype):
+    """what a head's forward_channels_last asks of every level: a HIP device tensor (N, <axes>, channels) in the compute dtype"""
+    for f in feats:
+        if not f.is_cuda:
+            raise RuntimeError(f"{name} (HIP) needs HIP device tensors (no CPU fallback)")
+        if f.dim() != 5 or f.shape[-1] != channels or f.dtype != dtype:
+            raise ValueError(f"{name}: channels-last (N, {axes}, {channels}) features in {dtype}, got {tuple(f.shape)} {f.dtype}")
 
 
 class SwinTransformer_FPN_Pretrained_Skip(nn.Module):

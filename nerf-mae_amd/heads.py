@@ -13,8 +13,8 @@ from typing import List, Optional
 import torch
 from torch import Tensor, nn
 
-from . import ops
-from .model import SWIN_CONFIGS, OutBlock3D, ResBlock3D, SwinTransformer_MAE3D_New, UpBlock3D, _EmbedFn, _gradbuf, _Packer
+from . import conv_layer, ops
+from .model import SWIN_CONFIGS, OutBlock3D, ResBlock3D, SwinTransformer_MAE3D_New, UpBlock3D, _EmbedFn, _gradbuf
 
 
 class UnetrBasicBlock3D(nn.Module):
@@ -184,11 +184,8 @@ class _VoxelHeadBase(nn.Module):
 
     def _pack(self):
         ps = [p for n, p in self.named_parameters() if not n.startswith("base.")]
-        if not ps[0].is_cuda:
-            raise RuntimeError("the voxel heads (HIP) need their parameters on a HIP device: call .cuda() first (no CPU fallback)")
-        key = tuple(p.data_ptr() for p in ps)
-        if self._pk is None or self._pk_key != key:
-            P = _Packer()
+
+        def fill(P):
             e1, d, oc = self.encoder1.layer, self.decoder1, self._out_conv()
             P.add("e1.c1.w", e1.conv1.weight, P.PAD_CIN8)
             P.add("e1.c2.w", e1.conv2.weight, P.CONV_F)
@@ -209,12 +206,10 @@ class _VoxelHeadBase(nn.Module):
             P.add(k + "c3.wT", d.conv_block.conv3.weight, P.TRANS)
             P.add("out.w", oc.weight, P.PAD_ROWS)
             P.add("out.wT", oc.weight, P.PAD_ROWS_T)
-            P.build(self.compute_dtype, ps[0].device)
-            P.split = None
             d._pk = P
-            self._pk, self._pk_key = P, key
             self._bias_pad = torch.zeros((oc.weight.shape[0] + 7) // 8 * 8, device=ps[0].device)
-        self._pk.run()
+
+        conv_layer.ensure_packed(self, ps, "the voxel heads (HIP) need their parameters on a HIP device: call .cuda() first (no CPU fallback)", fill)
 
     def _dec0(self, x: List[Tensor]):
         """everything up to the last decoder level (feature_extractor.py:2199-2222 / 2797-2817), channels-last [B*R^3][E/2]"""

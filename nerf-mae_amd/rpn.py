@@ -59,10 +59,10 @@ from torch import nn
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import ops
+from . import conv_layer, ops
 from .fcos_loss import _boxes, _check
-from .fpn import _NCDHWToCL
-from .model import _gradbuf, _Packer
+from .fpn import _NCDHWToCL, check_channels_last
+from .model import _gradbuf
 
 MAX_LEVELS, MAX_SCENES, MAX_ANCHORS = ops.FCOS_MAX_LEVELS, ops.FCOS_MAX_SCENES, ops.RPN_MAX_ANCHORS
 NMS_MAX_BOXES = ops.OBB_NMS_MAX
@@ -380,16 +380,12 @@ class _RPNHeadFn(Function):
 
     @staticmethod
     def forward(ctx, head, *feats):
-        pk, Cin, depth, C = head._pk, head.in_channels, head.conv_depth, head.num_delta_digits
+        pk, depth, C = head._pk, head.conv_depth, head.num_delta_digits
         acts = []
         for f in feats:
             xs = [f.contiguous()]
             for k in range(depth):
-                conv, x = head.conv[2 * k], xs[-1]
-                if ops.use_conv64(x, Cin) and f"c{k}.w64" in pk.views:
-                    y = ops.conv3d_k3_c64(x, pk[f"c{k}.w64"], Cin, bias=conv.bias)
-                else:
-                    y = ops.conv3d_k3_bias(x, pk[f"c{k}.w"], conv.bias, Cin)
+                y = conv_layer.forward(pk, f"c{k}", head.conv[2 * k], xs[-1])
                 if k < depth - 1:               # the last conv's ReLU is fused into the output kernel's load
                     ops.relu_(y)
                 xs.append(y)
@@ -402,7 +398,7 @@ class _RPNHeadFn(Function):
     @once_differentiable
     def backward(ctx, *gs):
         head, acts = ctx.head, ctx.saved
-        pk, Cin, depth, C, L = head._pk, head.in_channels, head.conv_depth, head.num_delta_digits, len(ctx.saved)
+        pk, depth, C, L = head._pk, head.conv_depth, head.num_delta_digits, len(ctx.saved)
         g_obj, g_reg = [g.contiguous() for g in gs[:L]], [g.contiguous() for g in gs[L:]]
         cls, box = head.cls_logits, head.bbox_pred
         dts = ops.rpn_head_out_bwd([xs[-1] for xs in acts], pk["cls.w"], pk["box.w"], g_obj, g_reg, C, depth > 0, _gradbuf(cls.weight), _gradbuf(box.weight),
@@ -410,19 +406,10 @@ class _RPNHeadFn(Function):
         dfeats, keep = [], []   # keep: tensors the forked side stream still reads -- referenced until the join
         for i, (xs, dy) in enumerate(zip(acts, dts)):
             for k in range(depth - 1, -1, -1):
-                conv, x = head.conv[2 * k], xs[k]
                 if k < depth - 1:
                     ops.relu_bwd_(dy, xs[k + 1])
                 keep.append(dy)
-                with ops.side_stream():
-                    ops.conv3d_k3_wgrad(dy, x, _gradbuf(conv.weight))
-                    ops.bias_grad(dy.view(-1, Cin), _gradbuf(conv.bias), dy.numel() // Cin, Cin)
-                if k == 0 and not ctx.needs_input_grad[1 + i]:
-                    dy = None
-                elif ops.use_conv64(dy, Cin) and f"c{k}.w64d" in pk.views:
-                    dy = ops.conv3d_k3_c64(dy, pk[f"c{k}.w64d"], Cin)
-                else:
-                    dy = ops.conv3d_k3(dy, pk[f"c{k}.wd"], Cin)
+                dy = conv_layer.backward(pk, f"c{k}", head.conv[2 * k], dy, xs[k], need_dx=k > 0 or ctx.needs_input_grad[1 + i])
             dfeats.append(dy)
         ops.join_side()
         del keep
@@ -460,36 +447,20 @@ class RPNHead(nn.Module):
         self._pk_key = None
 
     def _pack(self):
-        ps = list(self.parameters())
-        if not ps[0].is_cuda:
-            raise RuntimeError("RPNHead (HIP) needs its parameters on a HIP device: call .cuda() first (no CPU fallback)")
-        key = tuple(p.data_ptr() for p in ps)
-        if self._pk is None or self._pk_key != key:
-            P = _Packer()
+        def fill(P):
             for k in range(self.conv_depth):
-                w = self.conv[2 * k].weight
-                P.add(f"c{k}.w", w, P.CONV_F)
-                P.add(f"c{k}.wd", w, P.CONV_D)
-                if self.compute_dtype == torch.bfloat16 and self.in_channels % 64 == 0:
-                    P.add(f"c{k}.w64", w, P.C64_F)
-                    P.add(f"c{k}.w64d", w, P.C64_D)
+                conv_layer.register(P, f"c{k}", self.conv[2 * k], self.compute_dtype)
             P.add("cls.w", self.cls_logits.weight, P.CAST)
             P.add("box.w", self.bbox_pred.weight, P.CAST)
-            P.build(self.compute_dtype, ps[0].device)
-            P.split = None
-            self._pk, self._pk_key = P, key
-        self._pk.run()
+
+        conv_layer.ensure_packed(self, list(self.parameters()), "RPNHead (HIP) needs its parameters on a HIP device: call .cuda() first (no CPU fallback)", fill)
 
     def forward_channels_last(self, feats):
         """feats: per level a channels-last (N, W, H, D, C) tensor in the compute dtype -> (logits, bbox_reg), lists of fp32 NCDHW tensors"""
         feats = list(feats)
         if not 1 <= len(feats) <= MAX_LEVELS:
             raise ValueError(f"RPNHead supports 1 to {MAX_LEVELS} levels, got {len(feats)}")
-        for f in feats:
-            if not f.is_cuda:
-                raise RuntimeError("RPNHead (HIP) needs HIP device tensors (no CPU fallback)")
-            if f.dim() != 5 or f.shape[-1] != self.in_channels or f.dtype != self.compute_dtype:
-                raise ValueError(f"RPNHead: channels-last (N, W, H, D, {self.in_channels}) features in {self.compute_dtype}, got {tuple(f.shape)} {f.dtype}")
+        check_channels_last("RPNHead", "W, H, D", feats, self.in_channels, self.compute_dtype)
         self._pack()
         out = _RPNHeadFn.apply(self, *feats)
         return list(out[:len(feats)]), list(out[len(feats):])

@@ -383,6 +383,16 @@ def test_module_bf16_within_twice_the_rounding_error(depth, obb):
     _bf16_check(fcos, mod_case(depth, obb), depth, obb, f"bf16 depth {depth} obb {obb}")
 
 
+def test_module_bf16_on_the_64_channel_block_convolution():
+    """64 channels and a 32^3 level: ops.use_conv64 holds, so both towers' LDS-halo conv with the bias epilogue and its dgrad run; the second level takes the
+    generic conv"""
+    ops, fcos = _m()
+    c = mod_case(1, False, C=64, N=1, grids=((32, 32, 32), (3, 2, 2)))
+    assert ops.use_conv64(torch.empty(1, 32, 32, 32, 64, dtype=torch.bfloat16), 64)
+    assert not ops.use_conv64(torch.empty(1, 3, 2, 2, 64, dtype=torch.bfloat16), 64)
+    _bf16_check(fcos, c, 1, False, "bf16 conv64 depth 1")
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_ncdhw_entry_equals_the_channels_last_entry_bit_for_bit(dtype):
     _, fcos = _m()

@@ -377,3 +377,25 @@ def test_decoder1_pack_record_names_its_buffers(monkeypatch):
     monkeypatch.setattr(ops, "CCONV_WGRAD", False)
     d = _Dec1Pack(blk, torch.device("cpu"))
     assert d.mean_table is None and d.dgrad is None and d.optional() == {"tail_residual"}
+
+
+@pytest.mark.parametrize("dtype,cin,cout,c64", [(torch.bfloat16, 64, 64, True), (torch.float32, 64, 64, False), (torch.bfloat16, 32, 32, False), (torch.bfloat16, 64, 96, False)],
+                         ids=["bf16-64-64", "fp32-64-64", "bf16-32-32", "bf16-64-96"])
+def test_conv_layer_registers_the_64_channel_block_layouts_only_where_the_kernel_can_run(dtype, cin, cout, c64):
+    """conv_layer.register on a bare _Packer (add only reads shapes): `.w` / `.wd` always, `.w64` / `.w64d` if and only if bf16 and both channel counts
+    are multiples of 64, decided from the weight's shape"""
+    from nerf_mae_amd import conv_layer, ops
+    from nerf_mae_amd.model import _Packer
+    P = _Packer()
+    conv = torch.nn.Conv3d(cin, cout, 3, padding=1)
+    conv_layer.register(P, "k", conv, dtype)
+    modes = {key: mode for key, _, mode, _, _ in P.items}
+    want = {"k.w": P.CONV_F, "k.wd": P.CONV_D}
+    if c64:
+        want.update({"k.w64": P.C64_F, "k.w64d": P.C64_D})
+    assert modes == want and [key for key, *_ in P.items] == list(want)
+    assert all(p is conv.weight for _, p, *_ in P.items)
+    numel = {key: n for key, *_, n in P.items}
+    assert numel["k.w"] == numel["k.wd"] == conv.weight.numel()
+    if c64:
+        assert numel["k.w64"] == numel["k.w64d"] == ops.conv64_pack_numel(cin, cout) > 0
