@@ -391,6 +391,17 @@ NMH_API int nmh_voxel_sr_loss_bwd(const float* pred, const float* target, int B,
  * (mIoULoss_new, metrics.py:194-245); out fp32[2] = {loss, mean soft IoU}.  _bwd: dlogits = gscale * d(loss)/d(logits).  K <= 32. */
 NMH_API int nmh_masked_ce_fwd(const float* logits, const float* labels, const float* class_weights, int B, int K, int64_t V, double* sums, double* iou_sums, float* out, void* stream);
 NMH_API int nmh_masked_ce_bwd(const float* logits, const float* labels, const float* class_weights, int B, int K, int64_t V, const double* sums, float gscale, float* dlogits, void* stream);
+/* VoxelSemantics evaluation (feature_extractor.py:2748-2806 output_metrics, metrics.py:491-518 intersectionAndUnionGPU), one read of the logits.  Inputs as
+ * nmh_masked_ce_fwd (2 <= K <= 32, else -2).  out fp32[2] = {loss, mean soft IoU} by the definitions of nmh_masked_ce_fwd; p(v) = arg-max of the RAW logits over
+ * all K classes, the lowest index on an exact tie; over the voxels with label > 0 and the whole batch, per class c = 1..K-1:  I = #(p == c and label == c),
+ * P = #(p == c), T = #(label == c), U = P + T - I;  counts int64 [4][K-1] = {I, U, T, P};  pred_vis / target_vis int64 (B,V) = p * (label > 0), label * (label > 0);
+ * totals (optional) int64 [3][K-1] += {I, U, T}.  A label >= K is a labelled voxel of no class: it can count in P, never in T or I, and weighs 0 in the loss.
+ * Workspaces (written, never read back by the caller): fpart fp64 [1024][2 + 2(K-1)], ipart int64 [1024][3(K-1)]; B <= 1024, else -2.
+ * Two launches, no atomics, no allocation, no host wait; every sum has a fixed order.
+ * nmh_sem_label_counts: the same counts from two label arrays of n elements (dt 0 fp32, 1 int32, 2 int64; `output` plays p, `target` the label); needs ipart only. */
+NMH_API int nmh_sem_eval(const float* logits, const float* labels, const float* class_weights, int B, int K, int64_t V, double* fpart, int64_t* ipart, float* out,
+                         int64_t* counts, int64_t* pred_vis, int64_t* target_vis, int64_t* totals, void* stream);
+NMH_API int nmh_sem_label_counts(int dt, const void* output, const void* target, int64_t n, int K, int64_t* ipart, int64_t* counts, void* stream);
 /* ---- the reference's two native (CUDA) ops, both on the downstream path that the pretrained encoder + FPN feeds ----
  * Rotated 3-D RoIAlign (nerf_rpn/model/rotated_align/src/cuda_3d/ROIAlignRotated3D_cuda.cu RoIAlignRotated3DForward / ...BackwardFeature, bound by
  * rotated_align/roi_align_rotate_3d.py:10-47, used by detector.py:192-193).  rois [N][8] fp32 = {batch index, centre (w,l,h), size (w,l,h), angle in

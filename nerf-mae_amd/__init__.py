@@ -7,6 +7,7 @@ fallback and importing the model without the built library fails loudly."""
 __version__ = "0.1.0"
 
 _DET_EVAL = ("det_eval_dense", "DetectionEvaluator", "evaluate_box_proposals_recall", "evaluate_box_proposals_ap")
+_SEM_EVAL = ("SemanticEvaluator", "sem_eval_dense", "intersection_and_union")
 
 
 def __getattr__(name):
@@ -14,4 +15,7 @@ def __getattr__(name):
     if name in _DET_EVAL:
         from . import det_eval
         return getattr(det_eval, name)
+    if name in _SEM_EVAL:      # voxel-semantics evaluation (sem_eval.py), likewise
+        from . import sem_eval
+        return getattr(sem_eval, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

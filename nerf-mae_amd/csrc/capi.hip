@@ -550,6 +550,19 @@ int nmh_masked_ce_bwd(const float* logits, const float* labels, const float* cla
   if (!logits || !labels || !sums || !dlogits) return -4;
   return k_masked_ce_bwd(logits, labels, class_weights, B, K, (long)V, sums, gscale, dlogits, ST);
 }
+int nmh_sem_eval(const float* logits, const float* labels, const float* class_weights, int B, int K, int64_t V, double* fpart, int64_t* ipart, float* out,
+                 int64_t* counts, int64_t* pred_vis, int64_t* target_vis, int64_t* totals, void* stream) {
+  CLR();
+  REQ(logits, labels, fpart, ipart, out, counts, pred_vis, target_vis);
+  return k_sem_eval(logits, labels, class_weights, B, K, (long)V, fpart, (long long*)ipart, out, (long long*)counts, (long long*)pred_vis, (long long*)target_vis,
+                    (long long*)totals, ST);
+}
+int nmh_sem_label_counts(int dt, const void* output, const void* target, int64_t n, int K, int64_t* ipart, int64_t* counts, void* stream) {
+  CLR();
+  REQ(ipart, counts);
+  if (n > 0) REQ(output, target);
+  return k_sem_label_counts(dt, output, target, (long)n, K, (long long*)ipart, (long long*)counts, ST);
+}
 int nmh_roi_align_rotated_3d_fwd(int layout, int dt, const void* input, const float* rois, void* out, int N, int B, int W, int L, int H, int C, int PW, int PL, int PH,
                                  float spatial_scale, int sampling_ratio, void* stream) {
   CLR();

@@ -264,3 +264,269 @@ int k_masked_ce_bwd(const float* logits, const float* labels, const float* cw, i
   NMH_CHECK_LAUNCH();
   return 0;
 }
+
+// ---- VoxelSemantics evaluation (feature_extractor.py:2748-2806 output_metrics + metrics.py:491-518 intersectionAndUnionGPU) ---------
+// One read of the logits gives the loss scalars of masked_ce_fwd (same definitions; for a labelled voxel the masked and the raw logits are
+// the same numbers, an unlabelled voxel contributes w[0] * log K and nothing else), the predicted label p(v) = arg-max of the RAW logits
+// over all K classes (strict >, from class 0 up: the lowest index wins an exact tie), the two int64 label volumes and, per class
+// c = 1..K-1 over the labelled voxels (label > 0), the exact counts  I[c] = #(p == c and label == c),  P[c] = #(p == c),
+// T[c] = #(label == c).  A label >= K is a labelled voxel of no class: it can add to P, never to T or I, and weighs 0 in the loss.
+// Counting: ballot + popcount, lane c of every wave owns class c (64-bit per-lane counters); floating sums: per-lane fp32, xor-tree over
+// the wave, the four waves added in fp64 in order.  Every workgroup writes ONE row of two slabs -- fpart [row][2 + 2(K-1)] fp64 =
+// {sum w nll, sum w, sum m p_k ..., sum_{label == k} p_k ...} and ipart [row][3(K-1)] int64 = {I.., P.., T..}, row = b * nb + block -- and one
+// workgroup adds the rows in a fixed order: no atomics, no clearing launch, two runs give the same bits.
+#define SEM_NF(K) (2 + 2 * ((K) - 1))
+#define SEM_NI(K) (3 * ((K) - 1))
+
+template <int KMAX>
+__device__ __forceinline__ void sem_wave_counts(int p, int t, bool lab, int K, int lane, unsigned long long& ci, unsigned long long& cp, unsigned long long& ct) {
+  // called by every lane of the wave (lanes past the end pass lab = false)
+#pragma unroll
+  for (int c = 1; c < KMAX; ++c)
+    if (c < K) {
+      const unsigned long long bt = __ballot(lab && t == c), bp = __ballot(lab && p == c);
+      if (lane == c) { ct += __popcll(bt); cp += __popcll(bp); ci += __popcll(bt & bp); }
+    }
+}
+// the wave's counters -> LDS [4 waves][3][32]; after a barrier thread i < 3(K-1) writes the workgroup's row
+__device__ __forceinline__ void sem_counts_to_row(unsigned long long (*wc)[3][32], int K, unsigned long long ci, unsigned long long cp, unsigned long long ct,
+                                                  long long* __restrict__ row) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane < 32) { wc[w][0][lane] = ci; wc[w][1][lane] = cp; wc[w][2][lane] = ct; }
+  __syncthreads();
+  if ((int)threadIdx.x < SEM_NI(K)) {
+    const int j = threadIdx.x / (K - 1), c = 1 + threadIdx.x % (K - 1);
+    row[threadIdx.x] = (long long)(wc[0][j][c] + wc[1][j][c] + wc[2][j][c] + wc[3][j][c]);
+  }
+}
+
+template <int KMAX, int VEC>
+__global__ __launch_bounds__(256) void sem_eval_kernel(const float* __restrict__ logits, const float* __restrict__ labels, const float* __restrict__ cw, int K, long V,
+                                                       double* __restrict__ fpart, long long* __restrict__ ipart, long long* __restrict__ pred_vis,
+                                                       long long* __restrict__ target_vis) {
+  __shared__ float cwsh[32];
+  __shared__ float fsh[4][SEM_NF(32)];
+  __shared__ unsigned long long wc[4][3][32];
+  const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (threadIdx.x < 32) cwsh[threadIdx.x] = (cw && (int)threadIdx.x < K) ? cw[threadIdx.x] : 1.f;
+  __syncthreads();
+  const float w0 = cwsh[0], logK = __logf((float)K);
+  float s_nll = 0.f, s_w = 0.f, sp[KMAX], si[KMAX];
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) { sp[k] = 0.f; si[k] = 0.f; }
+  unsigned long long ci = 0, cp = 0, ct = 0;
+  const float* lg = logits + (long)b * K * V;
+  const long step = (long)gridDim.x * 256 * VEC;
+  for (long vb = (long)blockIdx.x * 256 * VEC; vb < V; vb += step) {     // workgroup-uniform trip count: the ballots below see whole waves
+    const long v = vb + (long)threadIdx.x * VEC;
+    const bool in = v < V;                                                // VEC == 4 only with V % 4 == 0: v < V covers v + 3
+    float l[VEC][KMAX];
+    int t[VEC];
+    if (in) {
+      if (VEC == 4) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(labels + (long)b * V + v);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) t[j] = (int)q[j];
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+          if (k < K) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(lg + (long)k * V + v);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) l[j][k] = x[j];
+          }
+      } else {
+        t[0] = (int)labels[(long)b * V + v];
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+          if (k < K) l[0][k] = lg[(long)k * V + v];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        t[j] = 0;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) l[j][k] = 0.f;
+      }
+    }
+    long long pv[VEC], tv[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      const bool lab = t[j] > 0;
+      float mx = l[j][0], lt = 0.f;
+      int arg = 0;
+#pragma unroll
+      for (int k = 1; k < KMAX; ++k)
+        if (k < K && l[j][k] > mx) { mx = l[j][k]; arg = k; }
+      float se = 0.f;
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k)
+        if (k < K) {
+          if (k == t[j]) lt = l[j][k];
+          l[j][k] = __expf(l[j][k] - mx);
+          se += l[j][k];
+        }
+      const float wt = t[j] < K ? cwsh[t[j] & 31] : 0.f;
+      if (in) {
+        s_nll += lab ? wt * (mx + __logf(se) - lt) : w0 * logK;
+        s_w += lab ? wt : w0;
+      }
+      const float rs = 1.f / se;
+#pragma unroll
+      for (int k = 1; k < KMAX; ++k)
+        if (k < K) {
+          const float p = lab ? l[j][k] * rs : 0.f;      // (a select, not a product: an unlabelled voxel may hold anything)
+          sp[k] += p;
+          si[k] += k == t[j] ? p : 0.f;
+        }
+      sem_wave_counts<KMAX>(arg, t[j], lab, K, lane, ci, cp, ct);
+      pv[j] = lab ? arg : 0;
+      tv[j] = lab ? t[j] : 0;
+    }
+    if (in) {
+      long long* po = pred_vis + (long)b * V + v;
+      long long* to = target_vis + (long)b * V + v;
+      if (VEC == 4) {
+        typedef long long ll2 __attribute__((ext_vector_type(2)));
+        reinterpret_cast<ll2*>(po)[0] = ll2{pv[0], pv[1]}; reinterpret_cast<ll2*>(po)[1] = ll2{pv[2], pv[VEC - 1]};
+        reinterpret_cast<ll2*>(to)[0] = ll2{tv[0], tv[1]}; reinterpret_cast<ll2*>(to)[1] = ll2{tv[2], tv[VEC - 1]};
+      } else {
+        po[0] = pv[0]; to[0] = tv[0];
+      }
+    }
+  }
+  const int nf = SEM_NF(K);
+  s_nll = wave_sum(s_nll); s_w = wave_sum(s_w);
+  if (lane == 0) { fsh[wave][0] = s_nll; fsh[wave][1] = s_w; }
+#pragma unroll
+  for (int k = 1; k < KMAX; ++k)
+    if (k < K) {
+      const float a = wave_sum(sp[k]), c = wave_sum(si[k]);
+      if (lane == 0) { fsh[wave][2 + (k - 1)] = a; fsh[wave][2 + (K - 1) + (k - 1)] = c; }
+    }
+  const long row = (long)b * gridDim.x + blockIdx.x;
+  sem_counts_to_row(wc, K, ci, cp, ct, ipart + row * SEM_NI(K));           // (its barrier also orders fsh)
+  if ((int)threadIdx.x < nf) fpart[row * nf + threadIdx.x] = (double)fsh[0][threadIdx.x] + (double)fsh[1][threadIdx.x] + (double)fsh[2][threadIdx.x] + (double)fsh[3][threadIdx.x];
+}
+
+// labels only: T = float, int or long long label arrays of n elements; the same counting code, one ipart row per workgroup
+template <typename T>
+__global__ __launch_bounds__(256) void sem_label_count_kernel(const T* __restrict__ output, const T* __restrict__ target, int K, long n, long long* __restrict__ ipart) {
+  __shared__ unsigned long long wc[4][3][32];
+  unsigned long long ci = 0, cp = 0, ct = 0;
+  const int lane = threadIdx.x & 63;
+  for (long vb = (long)blockIdx.x * 256; vb < n; vb += (long)gridDim.x * 256) {
+    const long v = vb + threadIdx.x;
+    const bool in = v < n;
+    const long long t = in ? (long long)target[v] : 0, p = in ? (long long)output[v] : 0;
+    const bool lab = t > 0;
+    sem_wave_counts<32>((p > 0 && p < K) ? (int)p : 0, (t > 0 && t < K) ? (int)t : 0, lab, K, lane, ci, cp, ct);
+  }
+  sem_counts_to_row(wc, K, ci, cp, ct, ipart + (long)blockIdx.x * SEM_NI(K));
+}
+
+// one column of a slab over rows first, first + stride, ...: 8 independent loads in flight, added in row order (a one-load-per-trip loop waits out the memory
+// latency a thousand times over: 50-60 us measured for 1024 rows)
+template <typename T>
+__device__ __forceinline__ T sem_col_sum(const T* __restrict__ col, int ncols, int nrows, int first, int stride) {
+  T s = 0;
+  for (int r = first; r < nrows; r += 8 * stride) {
+    T v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = r + u * stride < nrows ? col[(long)(r + u * stride) * ncols] : T(0);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += v[u];
+  }
+  return s;
+}
+// one workgroup of 1024: rows b * nb .. b * nb + nb - 1 of each slab added in a fixed order (16 resp. 8 interleaved partial sums per column, then those in
+// order); out[0] = weighted CE, out[1] = mean over (sample, class >= 1) of inter / (sum m p + T - inter + 1e-8); counts int64 [4][K-1] = {I, U = P + T - I,
+// T, P} over the batch; totals (optional) int64 [3][K-1] += {I, U, T}.  fpart == nullptr (labels only): the counts alone.
+__global__ __launch_bounds__(1024) void sem_eval_finalize_kernel(const double* __restrict__ fpart, const long long* __restrict__ ipart, int B, int nb, int K,
+                                                                 float* __restrict__ out, long long* __restrict__ counts, long long* __restrict__ totals) {
+  __shared__ double fs[16][64];
+  __shared__ long long is[8][128];
+  __shared__ double fres[64];
+  __shared__ long long ires[128];
+  __shared__ double term[32];
+  const int nf = SEM_NF(K), ni = SEM_NI(K), tid = threadIdx.x;
+  const int fa = tid & 63, fp = tid >> 6, ia = tid & 127, ip = tid >> 7;
+  double f_tot = 0.0, iou_acc = 0.0;     // thread a < 2: the CE sums over the batch; thread k-1 < K-1: the soft-IoU terms of class k over the batch
+  long long i_tot = 0;                   // thread a < ni: the batch's count
+  for (int b = 0; b < B; ++b) {
+    if (fpart && fa < nf) {
+      fs[fp][fa] = sem_col_sum(fpart + (long)b * nb * nf + fa, nf, nb, fp, 16);
+    }
+    if (ia < ni) {
+      is[ip][ia] = sem_col_sum(ipart + (long)b * nb * ni + ia, ni, nb, ip, 8);
+    }
+    __syncthreads();
+    if (fpart && tid < nf) {
+      double s = 0.0;
+      for (int q = 0; q < 16; ++q) s += fs[q][tid];
+      fres[tid] = s;
+      if (tid < 2) f_tot += s;
+    }
+    if (tid < ni) {
+      long long s = 0;
+      for (int q = 0; q < 8; ++q) s += is[q][tid];
+      ires[tid] = s;
+      i_tot += s;
+    }
+    __syncthreads();
+    if (fpart && tid < K - 1) {
+      const double sp = fres[2 + tid], inter = fres[2 + (K - 1) + tid], cnt = (double)ires[2 * (K - 1) + tid];
+      iou_acc += inter / (sp + cnt - inter + 1e-8);
+    }
+    __syncthreads();
+  }
+  if (fpart) {
+    if (tid < 2) fres[tid] = f_tot;
+    if (tid < K - 1) term[tid] = iou_acc;
+  }
+  if (tid < ni) ires[tid] = i_tot;
+  __syncthreads();
+  if (fpart && tid == 0) {
+    out[0] = (float)(fres[0] / fres[1]);
+    double acc = 0.0;
+    for (int k = 0; k < K - 1; ++k) acc += term[k];
+    out[1] = (float)(acc / ((double)B * (K - 1)));
+  }
+  if (tid < K - 1) {
+    const long long I = ires[tid], P = ires[(K - 1) + tid], T = ires[2 * (K - 1) + tid], U = P + T - I;
+    counts[tid] = I; counts[(K - 1) + tid] = U; counts[2 * (K - 1) + tid] = T; counts[3 * (K - 1) + tid] = P;
+    if (totals) { totals[tid] += I; totals[(K - 1) + tid] += U; totals[2 * (K - 1) + tid] += T; }
+  }
+}
+
+template <int KMAX>
+static void sem_eval_launch(bool vec, unsigned nb, int B, const float* logits, const float* labels, const float* cw, int K, long V, double* fpart, long long* ipart,
+                            long long* pred_vis, long long* target_vis, hipStream_t st) {
+  if (vec) hipLaunchKernelGGL((sem_eval_kernel<KMAX, 4>), dim3(nb, B), dim3(256), 0, st, logits, labels, cw, K, V, fpart, ipart, pred_vis, target_vis);
+  else hipLaunchKernelGGL((sem_eval_kernel<KMAX, 1>), dim3(nb, B), dim3(256), 0, st, logits, labels, cw, K, V, fpart, ipart, pred_vis, target_vis);
+}
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+int k_sem_eval(const float* logits, const float* labels, const float* cw, int B, int K, long V, double* fpart, long long* ipart, float* out, long long* counts,
+               long long* pred_vis, long long* target_vis, long long* totals, hipStream_t st) {
+  if (K < 2 || K > 32 || B < 1 || B > NMH_SEM_EVAL_ROWS || V < 1) return -2;
+  // 16-byte loads and stores: every class plane of every sample starts at a multiple of 4 elements
+  const bool vec = (V % 4 == 0) && al16(logits) && al16(labels) && al16(pred_vis) && al16(target_vis);
+  const long per = 256L * (vec ? 4 : 1), cap = NMH_SEM_EVAL_ROWS / B;     // rows = B * nb <= NMH_SEM_EVAL_ROWS, the extent of the caller's slabs
+  long nbl = (V + per - 1) / per;
+  const unsigned nb = (unsigned)(nbl > cap ? cap : nbl);
+  if (K <= 20) sem_eval_launch<20>(vec, nb, B, logits, labels, cw, K, V, fpart, ipart, pred_vis, target_vis, st);
+  else sem_eval_launch<32>(vec, nb, B, logits, labels, cw, K, V, fpart, ipart, pred_vis, target_vis, st);
+  hipLaunchKernelGGL(sem_eval_finalize_kernel, dim3(1), dim3(1024), 0, st, (const double*)fpart, (const long long*)ipart, B, (int)nb, K, out, counts, totals);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
+int k_sem_label_counts(int dt, const void* output, const void* target, long n, int K, long long* ipart, long long* counts, hipStream_t st) {
+  if (K < 2 || K > 32 || n < 0 || dt < 0 || dt > 2) return -2;
+  long nbl = (n + 255) / 256;
+  const unsigned nb = (unsigned)(nbl > NMH_SEM_EVAL_ROWS ? NMH_SEM_EVAL_ROWS : (nbl < 1 ? 1 : nbl));
+  if (dt == 0) hipLaunchKernelGGL(sem_label_count_kernel<float>, dim3(nb), dim3(256), 0, st, (const float*)output, (const float*)target, K, n, ipart);
+  else if (dt == 1) hipLaunchKernelGGL(sem_label_count_kernel<int>, dim3(nb), dim3(256), 0, st, (const int*)output, (const int*)target, K, n, ipart);
+  else hipLaunchKernelGGL(sem_label_count_kernel<long long>, dim3(nb), dim3(256), 0, st, (const long long*)output, (const long long*)target, K, n, ipart);
+  hipLaunchKernelGGL(sem_eval_finalize_kernel, dim3(1), dim3(1024), 0, st, (const double*)nullptr, (const long long*)ipart, 1, (int)nb, K, (float*)nullptr, counts, (long long*)nullptr);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}

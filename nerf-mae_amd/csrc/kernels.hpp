@@ -268,6 +268,10 @@ int k_sr_loss_fwd(const float* pred, const float* tgt, int B, long V, double* su
 int k_sr_loss_bwd(const float* pred, const float* tgt, int B, long V, const double* sums, float gscale, float* dpred, hipStream_t st);
 int k_masked_ce_fwd(const float* logits, const float* labels, const float* cw, int B, int K, long V, double* sums, double* iou, float* out, hipStream_t st);
 int k_masked_ce_bwd(const float* logits, const float* labels, const float* cw, int B, int K, long V, const double* sums, float gscale, float* dlogits, hipStream_t st);
+#define NMH_SEM_EVAL_ROWS 1024   // rows of the caller's partial slabs: one per workgroup of the evaluation pass
+int k_sem_eval(const float* logits, const float* labels, const float* cw, int B, int K, long V, double* fpart, long long* ipart, float* out, long long* counts,
+               long long* pred_vis, long long* target_vis, long long* totals, hipStream_t st);
+int k_sem_label_counts(int dt, const void* output, const void* target, long n, int K, long long* ipart, long long* counts, hipStream_t st);
 // ---- rotated.hip (the reference's two native downstream ops: rotated 3-D RoIAlign, polygon vertex sort) ----
 // layout 0: channels-last (B,W,L,H,C) in dt -> [N,PW,PL,PH,C] in dt; layout 1: NCWLH fp32 -> [N,C,PW,PL,PH] fp32.  dx is fp32 in both and is added to.
 int k_roi_align_rotated_3d_fwd(int layout, int dt, const void* x, const float* rois, void* out, int N, int B, int W, int L, int H, int C, int PW, int PL, int PH,

@@ -280,7 +280,7 @@ class SwinTransformer_VoxelSR_Pretrained_Skip(_VoxelHeadBase):
 
 class SwinTransformer_VoxelSemantics_Pretrained_Skip(_VoxelHeadBase):
     """feature_extractor.py:2521-2848.  forward(list of (4,W,L,H) grids) -> class logits (B,K,res^3); loss_fn(list of (1,W,L,H) label grids,
-    pred) -> (loss, sem_ce_loss, mean soft IoU)."""
+    pred) -> (loss, sem_ce_loss, mean soft IoU); output_metrics(label grids, pred) -> the evaluation loop's per-batch counts (sem_eval.py)."""
 
     def __init__(self, expand_dim: bool = True, out_channels: int = 19, resolution=160, decoder_embed_dim: int = 768, checkpoint_path=None,
                  is_eval=False, patch_size=[4, 4, 4], class_weights: Optional[Tensor] = None, compute_dtype: torch.dtype = torch.bfloat16):
@@ -307,3 +307,14 @@ class SwinTransformer_VoxelSemantics_Pretrained_Skip(_VoxelHeadBase):
 
     def loss_fn(self, x, pred):
         return self.forward_loss(x, pred)
+
+    def output_metrics(self, x, pred):
+        """feature_extractor.py:2748-2806 in one pass over the logits (sem_eval.py): (sem_ce_loss_val, metrics, pred_labels_vis, target_vis) with
+        metrics = {intersection, union, target: int64 [K-1] over the labelled voxels of the batch; iou_val} as device tensors and the two label volumes
+        int64 (B,R,R,R).  Never waits for the host."""
+        from .sem_eval import sem_eval_dense
+        if not pred.is_cuda:
+            raise RuntimeError("the voxel heads (HIP) need their tensors on a HIP device (no CPU fallback)")
+        labels = self.transform(x, resolution=self.input_resolution)[:, 0]
+        with torch.no_grad():
+            return sem_eval_dense(pred, labels, self.class_weights)

@@ -1438,6 +1438,50 @@ def masked_ce_bwd(logits, labels, class_weights, sums, gscale, dlogits):
     lib().call("nmh_masked_ce_bwd", logits, labels, class_weights, B, K, logits[0, 0].numel(), sums, gscale, dlogits, _st())
 
 
+SEM_EVAL_ROWS = 1024   # rows of the partial slabs (NMH_SEM_EVAL_ROWS): one per workgroup of the evaluation pass
+
+
+def sem_eval(logits, labels, class_weights=None, totals=None):
+    """logits (B,K,*) fp32, labels (B,*) fp32 class ids (0 = unlabelled), class_weights [K] fp32 or None, totals int64 [3][K-1] or None (+= {I, U, T} on the device)
+    -> (out fp32[2] = {loss, mean soft IoU}, counts int64 [4][K-1] = {I, U, T, P}, pred_vis int64 (B,V), target_vis int64 (B,V)).  One read of the logits, two
+    launches; only the outputs and the two partial slabs are allocated, and the host does not wait."""
+    _chk(logits, labels, class_weights, totals)
+    if logits.dtype != torch.float32 or labels.dtype != torch.float32 or (class_weights is not None and class_weights.dtype != torch.float32):
+        raise RuntimeError("sem_eval: fp32 logits, labels and class weights")
+    B, K = logits.shape[:2]
+    V = logits[0, 0].numel()
+    if labels.numel() != B * V or (class_weights is not None and class_weights.numel() != K):
+        raise RuntimeError(f"sem_eval: labels (B,V) and class weights [K] for logits (B,K,V) = ({B},{K},{V}), got {tuple(labels.shape)}")
+    if totals is not None and (totals.dtype != torch.int64 or tuple(totals.shape) != (3, K - 1)):
+        raise RuntimeError(f"sem_eval: totals int64 [3][{K - 1}]")
+    dev = logits.device
+    n1 = max(K - 1, 1)
+    fpart = torch.empty((SEM_EVAL_ROWS, 2 + 2 * n1), dtype=torch.float64, device=dev)
+    ipart = torch.empty((SEM_EVAL_ROWS, 3 * n1), dtype=torch.int64, device=dev)
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    counts = torch.empty((4, n1), dtype=torch.int64, device=dev)
+    pred_vis = torch.empty((B, V), dtype=torch.int64, device=dev)
+    target_vis = torch.empty((B, V), dtype=torch.int64, device=dev)
+    lib().call("nmh_sem_eval", logits, labels, class_weights, B, K, V, fpart, ipart, out, counts, pred_vis, target_vis, totals, _st())
+    return out, counts, pred_vis, target_vis
+
+
+_LABEL_DT = {torch.float32: 0, torch.int32: 1, torch.int64: 2}
+
+
+def sem_label_counts(output, target, K):
+    """two label tensors of one shape and dtype (fp32, int32 or int64) -> counts int64 [4][K-1] = {I, U, T, P} over the elements with target > 0"""
+    _chk(output, target)
+    if output.dtype != target.dtype or output.dtype not in _LABEL_DT or output.shape != target.shape:
+        raise RuntimeError("sem_label_counts: output and target of one shape and one dtype out of fp32, int32, int64")
+    dev = output.device
+    n1 = max(int(K) - 1, 1)
+    ipart = torch.empty((SEM_EVAL_ROWS, 3 * n1), dtype=torch.int64, device=dev)
+    counts = torch.empty((4, n1), dtype=torch.int64, device=dev)
+    lib().call("nmh_sem_label_counts", _LABEL_DT[output.dtype], output, target, output.numel(), int(K), ipart, counts, _st())
+    return counts
+
+
 # ---- the reference's two native downstream ops (csrc/rotated.hip) ------------------------------------------------------------------
 ROI_CHANNELS_LAST, ROI_NCWLH = 0, 1
 
