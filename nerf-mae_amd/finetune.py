@@ -1,0 +1,210 @@
+"""Fine-tuning of the downstream models (the detectors, the voxel heads) with the fused optimizer of the MAE path.
+
+  FlatParameters   one flat fp32 parameter buffer and one flat gradient buffer over ANY module of this package: the trainable parameters of its
+                   SwinTransformer_MAE3D_New (`base` of the FPN backbone or of a voxel head) first, in base._trainable() order and filling the base's own flat
+                   buffers in place, then every other trainable parameter in named_parameters() order, each on an 8-element granule.  It has the attributes
+                   FusedAdamW, trainer.flat_layout and the checkpoint functions read (_flat, _flat_grad, _offsets, flatten_parameters, named_parameters,
+                   state_dict), so those work on it unchanged.
+  FinetuneStep     one eager step: check the views, forward, backward, clip + AdamW (three launches; the update clears the gradient buffer).
+  fcos_loss_fn, rpn_loss_fn, voxel_loss_fn, loss_fn_for   the loss functions FinetuneStep takes, for the four downstream models.
+
+No kernel of its own: forward and backward are the models', the optimizer is nmh_grad_sqnorm / nmh_clip_coef / nmh_adamw_step (trainer.FusedAdamW).
+
+Ordering of the gradient producers before the optimizer reads the buffer: every Function of this package that forks the side stream joins it
+before its backward returns, and the base's deferred weight gradients are issued and joined by _EmbedFn.backward and by the end-of-backward callback of its
+queue, so `loss.backward()` returns with every gradient launch ordered before whatever the calling stream is given next.  The step adds no join.
+
+Single process, eager.  dist.GradReducer's segments are those of the MAE layout and a graph capture of the detectors needs padded target lists first; both are
+left out."""
+from __future__ import annotations
+
+from typing import Callable, Dict, Optional
+
+import torch
+from torch import nn
+
+from .model import SwinTransformer_MAE3D_New
+
+__all__ = ["FlatParameters", "FinetuneStep", "fcos_loss_fn", "rpn_loss_fn", "voxel_loss_fn", "loss_fn_for"]
+
+
+def _round8(n: int) -> int:
+    return (n + 7) // 8 * 8
+
+
+def _same_device(a: torch.device, b: torch.device) -> bool:
+    if a.type != b.type:
+        return False
+    if a.type != "cuda":
+        return True
+    cur = torch.cuda.current_device() if (a.index is None or b.index is None) else 0
+    return (cur if a.index is None else a.index) == (cur if b.index is None else b.index)
+
+
+class FlatParameters:
+    """FlatParameters(module, device=None): re-homes every trainable parameter of `module` and its .grad as views of one flat fp32 buffer pair.
+
+    Layout: [base._trainable() on 8-element granules = base._flat | the other trainable parameters in named_parameters() order, 8-element granules]; a parameter
+    object registered under two names is placed once.  Frozen parameters (pos_embed) and buffers stay where they are.  The module must already be on the device
+    it trains on: `device` only states what the caller expects and is refused when the parameters live elsewhere (moving the parameters alone would leave the
+    frozen ones and the buffers behind).  Refused as well: more than one SwinTransformer_MAE3D_New, and one without a trainable parameter.
+
+    The modules outside model.py rebuild their packed weights when a parameter's storage moves (conv_layer.ensure_packed keys on data_ptr()), and the base's
+    _ensure_ready finds its parameters where its own _offsets say, so nothing re-flattens afterwards.  `check()` verifies exactly that before every step."""
+
+    def __init__(self, module: nn.Module, device=None):
+        self.module = module
+        self._flat = self._flat_grad = None
+        self._offsets: Dict[int, int] = {}
+        self._views = []
+        self.base: Optional[SwinTransformer_MAE3D_New] = None
+        self.flatten_parameters(device)
+
+    # ---- layout -----------------------------------------------------------------------------------------------------------------------------
+    def flatten_parameters(self, device=None):
+        module = self.module
+        bases = [m for m in module.modules() if isinstance(m, SwinTransformer_MAE3D_New)]
+        if len(bases) > 1:
+            raise ValueError(f"FlatParameters: the module holds {len(bases)} SwinTransformer_MAE3D_New; one flat buffer can lead with the parameters of one only")
+        base = bases[0] if bases else None
+        lead = base._trainable() if base is not None else []
+        if base is not None and not lead:
+            raise ValueError("FlatParameters: the module's SwinTransformer_MAE3D_New has no trainable parameter (a frozen encoder is not supported: it keeps no "
+                             "flat buffer of its own to run from)")
+        seen = {id(p) for p in lead}
+        rest = []
+        for name, p in module.named_parameters():
+            if p.requires_grad and id(p) not in seen:
+                seen.add(id(p))
+                rest.append(p)
+        if not lead and not rest:
+            raise ValueError("FlatParameters: the module has no trainable parameter")
+        everything = list(module.parameters()) + list(module.buffers())
+        where = (lead + rest)[0].device
+        stray = [t for t in everything if not _same_device(t.device, where)]
+        if stray:
+            raise RuntimeError(f"FlatParameters: the module's parameters and buffers are spread over {where} and {stray[0].device}; move the module first")
+        if device is not None and not _same_device(torch.device(device), where):
+            raise RuntimeError(f"FlatParameters: the parameters are on {where}, not on {torch.device(device)}: move the module first (.cuda() / .to()); the flat "
+                               "buffers are made where the parameters are")
+        if any(p.dtype != torch.float32 for p in lead + rest):
+            raise TypeError("FlatParameters: fp32 master parameters only")
+        nb = base.flat_numel() if base is not None else 0
+        n = nb + sum(_round8(p.numel()) for p in rest)
+        flat, fg = torch.zeros(n, device=where), torch.zeros(n, device=where)
+        offsets: Dict[int, int] = {}
+        if base is not None:
+            base.flatten_parameters(out=(flat[:nb], fg[:nb]))
+            offsets.update(base._offsets)
+        off = nb
+        with torch.no_grad():
+            for p in rest:
+                k = p.numel()
+                flat[off:off + k].copy_(p.data.reshape(-1))
+                p.data = flat[off:off + k].view(p.shape)
+                p.grad = fg[off:off + k].view(p.shape)
+                offsets[id(p)] = off
+                off += _round8(k)
+        self.base, self._flat, self._flat_grad, self._offsets = base, flat, fg, offsets
+        self._views = [(name, p, offsets[id(p)]) for name, p in module.named_parameters() if id(p) in offsets]
+        return flat, fg
+
+    # ---- what FusedAdamW, flat_layout and the checkpoint functions read ------------------------------------------------------------------------
+    def named_parameters(self, *args, **kwargs):
+        return self.module.named_parameters(*args, **kwargs)
+
+    def state_dict(self, *args, **kwargs):
+        return self.module.state_dict(*args, **kwargs)
+
+    def zero_grad(self):
+        self._flat_grad.zero_()
+
+    def check(self):
+        """every trainable parameter's .data and .grad must still be the view it was given (compared by pointer); raises RuntimeError naming the first that is
+        not.  What breaks it: nn.Module.zero_grad() with torch's default set_to_none=True (use zero_grad() of this object), .cuda() / .to() / .float() after
+        flattening, a base that re-flattened itself.  Without this the optimizer would update memory nothing reads."""
+        p0, g0 = self._flat.data_ptr(), self._flat_grad.data_ptr()
+        for name, p, off in self._views:
+            if p.data_ptr() != p0 + 4 * off:
+                raise RuntimeError(f"FlatParameters.check: parameter '{name}' no longer lives in the flat buffer (moved by .cuda() / .to(), its .data replaced, or "
+                                   "its SwinTransformer_MAE3D_New flattened itself again); build a new FlatParameters and optimizer")
+            g = p.grad
+            if g is None or g.data_ptr() != g0 + 4 * off:
+                raise RuntimeError(f"FlatParameters.check: the .grad of parameter '{name}' is no longer its view of the flat gradient buffer "
+                                   f"({'None: zero_grad(set_to_none=True)?' if g is None else 'replaced'}); clear gradients with FlatParameters.zero_grad()")
+        b = self.base
+        if b is not None and (b._flat is None or b._flat.data_ptr() != p0 or b._flat_grad.data_ptr() != g0):
+            raise RuntimeError("FlatParameters.check: the SwinTransformer_MAE3D_New flattened itself again; build a new FlatParameters and optimizer")
+
+
+# ---- loss functions of the four downstream models ----------------------------------------------------------------------------------------------
+def fcos_loss_fn(model) -> Callable:
+    """FCOSOverNeRF: (meshes, targets) -> {"loss_cls", "loss_reg", "loss_centerness"}"""
+    return lambda meshes, targets: model(list(meshes), targets)[1]
+
+
+def rpn_loss_fn(model) -> Callable:
+    """NeRFRegionProposalNetwork: (meshes, targets) -> {"loss_objectness", "loss_rpn_box_reg", "loss_rpn_box_reg_2d"}"""
+    return lambda meshes, targets: model(list(meshes), targets)[1]
+
+
+def voxel_loss_fn(model) -> Callable:
+    """the voxel heads: (grids, target grids) -> {"loss": model.loss_fn(targets, model(grids))} (the first entry where loss_fn returns a tuple)"""
+
+    def fn(x, t):
+        out = model.loss_fn(t, model(x))
+        return {"loss": out[0] if isinstance(out, (tuple, list)) else out}
+
+    return fn
+
+
+def loss_fn_for(model) -> Callable:
+    from .fcos import FCOSOverNeRF
+    from .heads import _VoxelHeadBase
+    from .rpn import NeRFRegionProposalNetwork
+    if isinstance(model, FCOSOverNeRF):
+        return fcos_loss_fn(model)
+    if isinstance(model, NeRFRegionProposalNetwork):
+        return rpn_loss_fn(model)
+    if isinstance(model, _VoxelHeadBase):
+        return voxel_loss_fn(model)
+    raise TypeError(f"loss_fn_for: no ready-made loss function for {type(model).__name__}; pass your own to FinetuneStep")
+
+
+class FinetuneStep:
+    """FinetuneStep(flat_params, opt, loss_fn, weights=None): one eager fine-tuning step.
+
+    loss_fn(*batch) -> a tensor or a dict of tensors; the total of a dict is sum(weights.get(k, 1.0) * losses[k]) (the reference's `losses["loss_reg"] *=
+    reg_loss_weight; loss = cls + reg + centerness`, run_fcos_pretrained.py:729-731, is weights={"loss_reg": w}).  __call__(*batch): check(), forward, backward,
+    the optimizer's three launches.  The AdamW kernel clears the gradient buffer (opt.zero_grads_after_step), so no step starts with a zero fill; the buffer is
+    cleared once here.  Returns the UNWEIGHTED losses as detached device tensors (a bare tensor under the key "loss"); nothing waits for the host.
+    Set the step's learning rate and beta1 with opt.set_hyper() before the call."""
+
+    def __init__(self, flat_params: FlatParameters, opt, loss_fn: Callable, weights: Optional[Dict[str, float]] = None):
+        if not flat_params._flat.is_cuda:
+            raise RuntimeError("FinetuneStep needs the parameters on a HIP device: call .cuda() on the module before FlatParameters (no CPU fallback)")
+        if opt.model is not flat_params:
+            raise ValueError("FinetuneStep: the optimizer must have been built over the same FlatParameters (FusedAdamW(flat_params, ...))")
+        self.flat, self.opt, self.loss_fn, self.weights = flat_params, opt, loss_fn, dict(weights or {})
+        opt.zero_grads_after_step = True
+        flat_params.zero_grad()
+
+    def forward(self, *batch):
+        """check() + forward -> (the loss dict as loss_fn returned it, the weighted total); __call__ without the backward and the update (tools/bench_finetune_step.py
+        times the three parts)"""
+        self.flat.check()
+        out = self.loss_fn(*batch)
+        losses = out if isinstance(out, dict) else {"loss": out}
+        total = None
+        for k, v in losses.items():
+            w = self.weights.get(k, 1.0)
+            t = v if w == 1.0 else v * w
+            total = t if total is None else total + t
+        return losses, total
+
+    def __call__(self, *batch):
+        losses, total = self.forward(*batch)
+        total.backward()
+        # every gradient launch is ordered before this point on the current stream (module docstring): no join here
+        self.opt.step()
+        return {k: v.detach() for k, v in losses.items()}

@@ -1162,13 +1162,26 @@ class SwinTransformer_MAE3D_New(nn.Module):
                 seen.add(id(p))
         return ps
 
-    def flatten_parameters(self, device=None):
-        """Re-home every trainable parameter (and its .grad) as a view of one flat fp32 buffer."""
+    def flat_numel(self) -> int:
+        """length of the flat buffer `flatten_parameters` fills: every trainable parameter rounded up to an 8-element granule"""
+        return sum((p.numel() + 7) // 8 * 8 for p in self._trainable())   # 8-element granules: every segment boundary is 16-byte aligned in fp32 AND in bf16 buckets
+
+    def flatten_parameters(self, device=None, out=None):
+        """Re-home every trainable parameter (and its .grad) as a view of one flat fp32 buffer.  out=(flat, grad): fill this storage (two contiguous fp32
+        vectors of flat_numel() elements, e.g. the leading slices of finetune.FlatParameters' buffers) instead of allocating; the granule gaps are cleared."""
         ps = self._trainable()
-        device = device or ps[0].device
-        n = sum((p.numel() + 7) // 8 * 8 for p in ps)   # 8-element granules: every segment boundary is 16-byte aligned in fp32 AND in bf16 buckets
-        flat = torch.zeros(n, device=device)
-        fg = torch.zeros(n, device=device)
+        n = self.flat_numel()
+        if out is None:
+            device = device or ps[0].device
+            flat = torch.zeros(n, device=device)
+            fg = torch.zeros(n, device=device)
+        else:
+            flat, fg = out
+            for t in (flat, fg):
+                if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+                    raise ValueError(f"flatten_parameters: out must be two contiguous fp32 vectors of flat_numel() = {n} elements")
+            device = flat.device
+            fg.zero_()
         off = 0
         self._offsets = {}
         for p in ps:
@@ -1177,6 +1190,8 @@ class SwinTransformer_MAE3D_New(nn.Module):
             p.data = flat[off:off + k].view(p.shape)
             p.grad = fg[off:off + k].view(p.shape)
             self._offsets[id(p)] = off
+            if out is not None and k % 8:
+                flat[off + k:off + (k + 7) // 8 * 8].zero_()
             off += (k + 7) // 8 * 8
         self._flat, self._flat_grad = flat, fg
         self._build_packer(device)

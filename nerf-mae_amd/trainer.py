@@ -425,16 +425,39 @@ def save_checkpoint(path: str, model, epoch: int, train_args: dict, opt: "FusedA
     cannot resume its optimizer): AdamW moments over the flat buffer, step count, beta powers, schedule position."""
     ck = {"epoch": epoch, "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "train_args": dict(train_args)}
     if opt is not None:
-        # the moments are flat buffers in the model's parameter order: the layout (name -> offset, numel) travels with them, so a file
-        # written under another flat layout (e.g. the 4-element granule of earlier builds) is remapped by name instead of misaligned
-        ck["resume"] = {"m": opt.m.detach().cpu(), "v": opt.v.detach().cpu(), "t": opt.t, "lr": opt.lr, "betas": opt.betas, "step": step,
-                        "layout": flat_layout(model)}
+        ck["resume"] = resume_section(model, opt, step)
     torch.save(ck, path)
 
 
 def flat_layout(model) -> dict:
     """{parameter name: [offset, numel]} of the model's flat fp32 parameter / gradient / moment buffers"""
     return {n: [int(model._offsets[id(p)]), int(p.numel())] for n, p in model.named_parameters() if id(p) in model._offsets}
+
+
+def resume_section(model, opt, step=None) -> dict:
+    """what a TRUE resume needs, as save_checkpoint and save_detection_checkpoint store it under "resume": the AdamW moments over the flat buffer, step count,
+    learning rate, betas, schedule position.  The moments are flat buffers in the model's parameter order: the layout (name -> offset, numel) travels with
+    them, so a file written under another flat layout (e.g. the 4-element granule of earlier builds) is remapped by name instead of misaligned"""
+    return {"m": opt.m.detach().cpu(), "v": opt.v.detach().cpu(), "t": opt.t, "lr": opt.lr, "betas": tuple(opt.betas), "step": step, "layout": flat_layout(model)}
+
+
+def restore_resume(r: dict, model, opt, who: str):
+    """the inverse of resume_section: the moments into opt.m / opt.v (remapped by parameter name when the file's flat layout is not this build's), then
+    t, lr and betas.  `model` is whatever flat_layout takes (an MAE model or a finetune.FlatParameters)."""
+    lay_now, lay_ck = flat_layout(model), r.get("layout")
+    if lay_ck is None or {k: list(v) for k, v in lay_ck.items()} == lay_now:
+        if r["m"].numel() != opt.m.numel():
+            raise RuntimeError(f"{who}: the optimizer state has {r['m'].numel()} elements, this build's flat layout {opt.m.numel()} "
+                               "(a file without a 'layout' section written under another parameter granule cannot be remapped)")
+        opt.m.copy_(r["m"]); opt.v.copy_(r["v"])
+    else:   # another flat layout: remap every parameter's moments by name
+        if set(lay_ck) != set(lay_now) or any(lay_ck[k][1] != lay_now[k][1] for k in lay_now):
+            raise RuntimeError(f"{who}: the optimizer state belongs to a different parameter set")
+        opt.m.zero_(); opt.v.zero_()
+        for k, (off, n) in lay_now.items():
+            o2 = lay_ck[k][0]
+            opt.m[off:off + n].copy_(r["m"][o2:o2 + n]); opt.v[off:off + n].copy_(r["v"][o2:o2 + n])
+    opt.t, opt.lr, opt.betas = r["t"], r["lr"], tuple(r["betas"])
 
 
 def load_checkpoint(path: str, model, opt: "FusedAdamW" = None, strict: bool = True) -> dict:
@@ -447,20 +470,7 @@ def load_checkpoint(path: str, model, opt: "FusedAdamW" = None, strict: bool = T
         r = ck["resume"]
         if model._flat is None or not model._flat.is_cuda:
             raise RuntimeError("load_checkpoint: move the model to the HIP device before restoring the optimizer")
-        lay_now, lay_ck = flat_layout(model), r.get("layout")
-        if lay_ck is None or {k: list(v) for k, v in lay_ck.items()} == lay_now:
-            if r["m"].numel() != opt.m.numel():
-                raise RuntimeError(f"load_checkpoint: the optimizer state has {r['m'].numel()} elements, this build's flat layout {opt.m.numel()} "
-                                   "(a file without a 'layout' section written under another parameter granule cannot be remapped)")
-            opt.m.copy_(r["m"]); opt.v.copy_(r["v"])
-        else:   # another flat layout: remap every parameter's moments by name
-            if set(lay_ck) != set(lay_now) or any(lay_ck[k][1] != lay_now[k][1] for k in lay_now):
-                raise RuntimeError("load_checkpoint: the optimizer state belongs to a different parameter set")
-            opt.m.zero_(); opt.v.zero_()
-            for k, (off, n) in lay_now.items():
-                o2 = lay_ck[k][0]
-                opt.m[off:off + n].copy_(r["m"][o2:o2 + n]); opt.v[off:off + n].copy_(r["v"][o2:o2 + n])
-        opt.t, opt.lr, opt.betas = r["t"], r["lr"], tuple(r["betas"])
+        restore_resume(r, model, opt, "load_checkpoint")
     return ck
 
 
@@ -564,4 +574,190 @@ class Trainer:
             self.history.append(rec)
             if self.rank == 0:
                 self.log(" ".join(f"{k}={v:.5g}" if isinstance(v, float) else f"{k}={v}" for k, v in rec.items()))
+        return self.history
+
+
+# --------------------------------------------------------------------------------------------------
+# Detection fine-tuning: the reference's checkpoint format and the epoch loop of run_fcos_pretrained.py
+# --------------------------------------------------------------------------------------------------
+def _plain(v):
+    """train_args as torch.load(weights_only=True) reads them back: numbers, strings, None and containers of those; anything else by its str()"""
+    if isinstance(v, (bool, int, float, str, type(None))):
+        return v
+    if isinstance(v, dict):
+        return {str(k): _plain(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_plain(x) for x in v]
+    return str(v)
+
+
+def save_detection_checkpoint(path: str, model, epoch: int, train_args: dict, opt: "FusedAdamW" = None, step: int = None):
+    """the reference's detection checkpoint (run_fcos_pretrained.py:477-497): {"epoch", "backbone_state_dict", "fcos_state_dict", "train_args"} of a
+    FCOSOverNeRF, keys and shapes the reference's, so nerf_rpn loads it unchanged.  With `opt` (a FusedAdamW over a finetune.FlatParameters of this model) the
+    file also carries the "resume" section of save_checkpoint: moments over the flat buffer, t, lr, betas, step and the name -> [offset, numel] layout."""
+    model = getattr(model, "module", model)
+    ck = {"epoch": epoch, "backbone_state_dict": {k: v.detach().cpu() for k, v in model.backbone.state_dict().items()},
+          "fcos_state_dict": {k: v.detach().cpu() for k, v in model.fcos_module.state_dict().items()}, "train_args": _plain(dict(train_args))}
+    if opt is not None:
+        ck["resume"] = resume_section(opt.model, opt, step)
+    torch.save(ck, path)
+
+
+def load_detection_checkpoint(path: str, model, opt: "FusedAdamW" = None) -> dict:
+    """loads a detection checkpoint (also one written by the reference) strictly into model.backbone and model.fcos_module; returns the checkpoint dict.  With
+    `opt` and a "resume" section the optimizer continues where it stopped; moments written under another flat layout are remapped by parameter name."""
+    model = getattr(model, "module", model)
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    model.backbone.load_state_dict(ck["backbone_state_dict"], strict=True)
+    model.fcos_module.load_state_dict(ck["fcos_state_dict"], strict=True)
+    if opt is not None and "resume" in ck:
+        restore_resume(ck["resume"], opt.model, opt, "load_detection_checkpoint")
+    return ck
+
+
+def delete_suboptimal_checkpoints(checkpoint_dir: str, metric_name: str = "ap50", max_to_keep: int = 6, min_to_keep: int = 1):
+    """run_fcos_pretrained.py:507-535: every *.pt of the directory is ranked by the number its name carries -- for "ap50" the second-to-last '_' field, which
+    is AP50 under both best-checkpoint name patterns; for "ap25" the last field -- and all but the max(max_to_keep, min_to_keep) highest are removed; ties keep
+    the directory order.  A *.pt whose name carries no such number ranks as 0.0 (the reference raises ValueError on it)."""
+    import glob
+    import os
+
+    def metric(filename):
+        parts = filename.split("_")
+        try:
+            if len(parts) >= 2:
+                return float(parts[-1].replace(".pt", "")) if metric_name == "ap25" else float(parts[-2])
+        except ValueError:
+            pass
+        return 0.0
+
+    files = glob.glob(os.path.join(checkpoint_dir, "*.pt"))
+    files.sort(key=metric)
+    keep = files[-min(max(max_to_keep, min_to_keep), len(files)):] if files else []
+    for f in files:
+        if f not in keep:
+            os.remove(f)
+
+
+class DetectionTrainer:
+    """Epoch loop of run_fcos_pretrained.py:537-815 without wandb, single GPU, for FCOSOverNeRF: input from data.DetectionBatcher, one optimizer group over
+    ALL parameters (the reference passes model.parameters(): weight decay applies to everything), clip + AdamW by FusedAdamW over finetune.FlatParameters,
+    loss = loss_cls + reg_loss_weight * loss_reg + loss_centerness, the OneCycle schedule stepped every iteration.
+
+    `schedule_epochs`: the reference sizes its schedule by a literal 1000 epochs whatever --num_epochs says (`total_steps=1000 * len(train_loader)`, :643-647);
+    that is the default here, so a run of num_epochs < 1000 stops part-way up or down the cycle exactly as the reference's does.  Pass num_epochs for a
+    schedule that ends with the run.
+
+    No drop_last: the ragged last batch of an epoch runs as a smaller batch.  The epoch's losses accumulate on the device and are read back once per epoch;
+    `train_loss` of the history is the weighted total, `loss_cls` / `loss_reg` / `loss_centerness` the unweighted parts (the reference logs loss_reg after its
+    in-place weighting).  Every `eval_interval` epochs and at the last one: model.eval(), detections through the reference forward, scored by
+    DetectionEvaluator with the limits [300, 1000, fpn_post_nms_top_n] that do not exceed fpn_post_nms_top_n (:875-877) -> recall at 0.25 / 0.5, AR, AP at
+    0.25 / 0.5 (train_args["ap_top_n"]: detections kept per scene for AP, default all).  Best checkpoints by AP50 and by AP25 under the reference's file names,
+    then the best 6 by AP50 are kept (delete_suboptimal_checkpoints).  The checkpoints carry the optimizer state (save_detection_checkpoint).
+
+    train_scenes / val_scenes: stored scenes ((W,L,H,4) arrays or paths); train_boxes / val_boxes: one [G, 6|7] array per scene."""
+
+    def __init__(self, model, train_scenes, train_boxes, val_scenes=None, val_boxes=None, batch_size: int = 2, num_epochs: int = 1, lr: float = 3e-4,
+                 weight_decay: float = 1e-3, clip_grad_norm: float = 0.1, reg_loss_weight: float = 1.0, eval_interval: int = 1, save_path: str = None,
+                 normalize_density: bool = True, flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = 1000,
+                 log=print, train_args: dict = None, seed: int = 0):
+        import random
+        from . import data
+        from .finetune import FinetuneStep, FlatParameters, fcos_loss_fn
+        if len(train_scenes) != len(train_boxes) or (val_scenes is not None and len(val_scenes) != len(val_boxes or [])):
+            raise ValueError("DetectionTrainer: one box array per scene")
+        if len(train_scenes) < 1:
+            raise ValueError("DetectionTrainer: no training scene")
+        resolution = getattr(model, "resoluton", None)          # (the reference's spelling, fcos.FCOSOverNeRF)
+        if resolution is None:
+            raise ValueError("DetectionTrainer: the model needs a fixed resolution (FCOSOverNeRF(..., resolution=R)): the batcher pads every scene to it")
+        self.model, self.train_scenes, self.train_boxes, self.val_scenes, self.val_boxes = model, train_scenes, train_boxes, val_scenes, val_boxes
+        self.batch, self.epochs, self.eval_interval, self.save_path, self.log, self.seed = batch_size, num_epochs, eval_interval, save_path, log, seed
+        self.reg_loss_weight = reg_loss_weight
+        self.args = _plain(dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, reg_loss_weight=reg_loss_weight,
+                                batch_size=batch_size, num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
+                                rot_scale_prob=rot_scale_prob))
+        dev = next(model.parameters()).device
+        self.batcher = data.DetectionBatcher(resolution, dev, normalize_density, flip_prob, rotate_prob, rot_scale_prob)
+        self.val_batcher = data.DetectionBatcher(resolution, dev, normalize_density)
+        self.flat = FlatParameters(model, dev)
+        self.opt = FusedAdamW(self.flat, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
+        self.steps_per_epoch = -(-len(train_scenes) // batch_size)          # len(train_loader) without drop_last
+        self.sched = OneCycle(lr, schedule_epochs * self.steps_per_epoch)
+        self.step_fn = FinetuneStep(self.flat, self.opt, fcos_loss_fn(model), weights={"loss_reg": reg_loss_weight})
+        self.top_n = int(model.args.fpn_post_nms_top_n)
+        self.limits = [l for l in (300, 1000, self.top_n) if l <= self.top_n]
+        self.ap_top_n = (train_args or {}).get("ap_top_n")
+        self._rng = random.Random(seed)
+        self.global_step, self.best_metric_ap50, self.best_metric_ap25, self.history = 0, None, None, []
+
+    @staticmethod
+    def _load(s):
+        from . import data
+        return data.load_scene(s) if isinstance(s, str) else s
+
+    @staticmethod
+    def _meshes(xb, ext):
+        """the batcher's padded batch as the list of grids in their own sizes that the reference forward takes (it pads them again and keeps the sizes)"""
+        return [xb[i, :, :e[0], :e[1], :e[2]] for i, e in enumerate(ext)]
+
+    def train_epoch(self, epoch: int):
+        from .dist import shard_indices
+        self.model.train()
+        idx = shard_indices(len(self.train_scenes), 0, 1, epoch, seed=self.seed)     # the DataLoader's shuffle
+        acc = None
+        for b in range(self.steps_per_epoch):
+            ids = idx[b * self.batch:(b + 1) * self.batch]
+            xb, ext, targets = self.batcher.prepare([self._load(self.train_scenes[i]) for i in ids], [self.train_boxes[i] for i in ids], rng=self._rng)
+            lr, b1 = self.sched.at(self.global_step)
+            self.opt.set_hyper(lr=lr, beta1=b1)
+            losses = self.step_fn(self._meshes(xb, ext), targets)
+            self.global_step += 1
+            parts = torch.stack([losses["loss_cls"], losses["loss_reg"], losses["loss_centerness"]])
+            acc = parts if acc is None else acc + parts
+        cls, reg, ctr = (acc / self.steps_per_epoch).tolist()         # the epoch's one read-back
+        return {"train_loss": cls + self.reg_loss_weight * reg + ctr, "loss_cls": cls, "loss_reg": reg, "loss_centerness": ctr}
+
+    @torch.no_grad()
+    def evaluate(self):
+        from .det_eval import DetectionEvaluator
+        self.model.eval()
+        ev = DetectionEvaluator(limits=self.limits, ap_thresholds=(0.25, 0.5), top_k=self.ap_top_n)
+        for b in range(0, len(self.val_scenes), self.batch):
+            scenes = [self._load(s) for s in self.val_scenes[b:b + self.batch]]
+            xb, ext, gt = self.val_batcher.prepare(scenes, list(self.val_boxes[b:b + self.batch]), params=[(0, 0.0, 1.0)] * len(scenes))
+            boxes, _, scores = self.model(self._meshes(xb, ext))
+            ev.update([p[:, 1:] for p in boxes], list(scores), list(gt))       # column 0 is the level index (the reference drops it too, :857-858)
+        self.model.train()
+        out = ev.compute()
+        rec = {}
+        for l in self.limits:
+            for key in ("25", "50", "ar"):
+                rec[f"recall_{key}_top_{l}"] = float(out[f"recall_{key}_top_{l}"]["ar"])
+        rec["ap_25"], rec["ap_50"] = float(out["ap_25"]["ap"]), float(out["ap_50"]["ap"])
+        return rec
+
+    def _save(self, name, epoch):
+        import os
+        save_detection_checkpoint(os.path.join(self.save_path, name), self.model, epoch, self.args, self.opt, self.global_step)
+
+    def fit(self):
+        import os
+        if self.save_path:
+            os.makedirs(self.save_path, exist_ok=True)
+        for epoch in range(1, self.epochs + 1):
+            rec = {"epoch": epoch, **self.train_epoch(epoch)}
+            if self.val_scenes and (epoch % self.eval_interval == 0 or epoch == self.epochs):
+                rec.update(self.evaluate())
+                ap50, ap25 = rec["ap_50"], rec["ap_25"]
+                if self.save_path:
+                    if self.best_metric_ap50 is None or ap50 > self.best_metric_ap50:
+                        self.best_metric_ap50 = ap50
+                        self._save(f"model_best_ap50_ap25_{ap50}_{ap25}.pt", epoch)
+                    if self.best_metric_ap25 is None or ap25 > self.best_metric_ap25:
+                        self.best_metric_ap25 = ap25
+                        self._save(f"model_best_ap25_ap50_{ap50}_{ap25}.pt", epoch)
+                    delete_suboptimal_checkpoints(self.save_path, "ap50", 6, 1)
+            self.history.append(rec)
+            self.log(" ".join(f"{k}={v:.5g}" if isinstance(v, float) else f"{k}={v}" for k, v in rec.items()))
         return self.history

@@ -1,0 +1,117 @@
+"""Times one FCOS fine-tuning step on the GPU: swin_s backbone + FPN(256) + FCOS head (4 tower layers, oriented boxes), 160^3, batch 2, bf16 compute.
+
+Two paths over models with the same weights and the same fixed batch, alternated step by step in one process:
+  fused   finetune.FinetuneStep: forward, backward, FusedAdamW over finetune.FlatParameters (three launches, the update clears the gradients)
+  stock   the same forward and backward, then torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW over the separate tensors and a zero_grad fill
+          (the only way to train the detector before finetune.py existed)
+HIP events around forward, backward and optimizer (the stock path's zero fill counts as optimizer time); 10 warm-up steps, --steps (default 50, at least 50)
+timed steps per path.  Prints the median and mean of each part in ms and one JSON line.  Nothing is asserted on the times."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import types
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def build(args):
+    from nerf_mae_amd.fcos import FCOSOverNeRF
+    from nerf_mae_amd.fpn import SwinTransformer_FPN_Pretrained_Skip
+    a = types.SimpleNamespace(num_convs=4, norm_reg_targets=True, centerness_on_reg=True, rotated_bbox=True, center_sampling_radius=1.5, iou_loss_type="iou",
+                              use_additional_l1_loss=True, proj2d_loss_weight=0.0, pre_nms_thresh=0.0, pre_nms_top_n=2500, nms_thresh=0.3, fpn_post_nms_top_n=2500,
+                              min_size=0.0, compute_dtype=torch.bfloat16)
+    torch.manual_seed(0)
+    bb = SwinTransformer_FPN_Pretrained_Skip(resolution=args.resolution, is_eval=True, backbone_type=args.backbone, out_channels=256, compute_dtype=torch.bfloat16)
+    return FCOSOverNeRF(a, bb, [4, 8, 16, 32], resolution=args.resolution)
+
+
+def batch(args):
+    from nerf_mae_amd import data
+    R = args.resolution
+    batcher = data.DetectionBatcher(R, torch.device("cuda"), normalize_density=True)
+    rng = np.random.default_rng(0)
+    boxes = []
+    for _ in range(args.batch):
+        c = rng.uniform(0.25 * R, 0.75 * R, (8, 3))
+        s = np.exp(rng.uniform(np.log(8.0), np.log(0.4 * R), (8, 3)))
+        boxes.append(np.concatenate([c, s, rng.uniform(-0.5, 0.5, (8, 1))], 1).astype(np.float32))
+    xb, ext, targets = batcher.prepare([data.synthetic_scene((R, R, R), i + 1) for i in range(args.batch)], boxes, params=[(0, 0.0, 1.0)] * args.batch)
+    return [xb[i] for i in range(args.batch)], targets
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--resolution", type=int, default=160)
+    ap.add_argument("--batch", type=int, default=2)
+    ap.add_argument("--backbone", default="swin_s")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_finetune_step needs an MI355X (no CPU fallback)")
+    from nerf_mae_amd.finetune import FinetuneStep, FlatParameters, fcos_loss_fn
+    from nerf_mae_amd.trainer import FusedAdamW
+    A = build(args)
+    B = build(args)
+    B.load_state_dict(A.state_dict(), strict=True)
+    A, B = A.cuda().train(), B.cuda().train()
+    meshes, targets = batch(args)
+    flat = FlatParameters(A)
+    fopt = FusedAdamW(flat, lr=1e-4, weight_decay=1e-2, max_grad_norm=0.1)
+    step = FinetuneStep(flat, fopt, fcos_loss_fn(A))
+    sopt = torch.optim.AdamW(B.parameters(), lr=1e-4, weight_decay=1e-2)
+
+    def ev():
+        return torch.cuda.Event(enable_timing=True)
+
+    def fused():
+        e = [ev() for _ in range(4)]
+        e[0].record()
+        losses, total = step.forward(meshes, targets)
+        e[1].record()
+        total.backward()
+        e[2].record()
+        fopt.step()
+        e[3].record()
+        return e
+
+    def stock():
+        e = [ev() for _ in range(4)]
+        e[0].record()
+        out = B(list(meshes), targets)[1]
+        total = out["loss_cls"] + out["loss_reg"] + out["loss_centerness"]
+        e[1].record()
+        total.backward()
+        e[2].record()
+        torch.nn.utils.clip_grad_norm_(B.parameters(), 0.1)
+        sopt.step()
+        sopt.zero_grad(set_to_none=False)
+        e[3].record()
+        return e
+
+    for _ in range(args.warmup):
+        fused()
+        stock()
+    torch.cuda.synchronize()
+    rec = {"fused": [], "stock": []}
+    for _ in range(max(args.steps, 1)):
+        rec["fused"].append(fused())
+        rec["stock"].append(stock())
+    torch.cuda.synchronize()
+    result = {"metric": "fcos_finetune_step_ms", "backbone": args.backbone, "resolution": args.resolution, "batch": args.batch, "dtype": "bf16", "steps": args.steps,
+              "warmup": args.warmup, "tensors": len([p for p in A.parameters() if p.requires_grad]), "elements": int(flat._flat.numel())}
+    for name, runs in rec.items():
+        parts = {"forward": [e[0].elapsed_time(e[1]) for e in runs], "backward": [e[1].elapsed_time(e[2]) for e in runs],
+                 "optimizer": [e[2].elapsed_time(e[3]) for e in runs], "step": [e[0].elapsed_time(e[3]) for e in runs]}
+        result[name] = {k: {"median": round(statistics.median(v), 3), "mean": round(statistics.fmean(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+                        for k, v in parts.items()}
+        print(f"{name:5s} " + "  ".join(f"{k} {result[name][k]['median']:.3f} ms (mean {result[name][k]['mean']:.3f})" for k in parts))
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
