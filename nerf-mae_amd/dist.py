@@ -6,7 +6,10 @@ all-reduces launched from inside backward as soon as a segment is complete -- de
 91 % of the FLOPs' worth of backward time behind it), then stage 3..0, then the embed tail -- on a side stream so they
 overlap the remaining backward kernels.  xGMI is point-to-point (7 links/GPU), so few large messages beat many small
 buckets.  AVG reduction = DDP's gradient averaging; no per-step barrier or scalar loss all-reduce (the reference's
-:676-686) -- losses are reduced only when logged."""
+:676-686) -- losses are reduced only when logged.
+
+Fine-tuning of the downstream models (finetune.FlatParameters: the base's flat buffer, then the neck, the heads, ...) uses the same exchange through
+FlatGradReducer, which differs in its segment bounds only."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -50,30 +53,29 @@ class GradReducer:
 
     def __init__(self, model, process_group=None, comm_dtype: Optional[torch.dtype] = None, stage_chunks: Optional[int] = None):
         import os
-        self.model, self.group = model, process_group
+        self.model, self.group = model, process_group    # `model`: whatever holds _flat_grad and _offsets (FlatGradReducer: a finetune.FlatParameters)
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         # NMH_DP_FORCE=1: run the whole exchange machinery also over a one-rank group (single-GPU measurements of its cost)
         self.active = self.world > 1 or os.environ.get("NMH_DP_FORCE") == "1"
-        if model._flat is None:
-            model.flatten_parameters()
+        enc = self._encoder()
         off = model._offsets
         first = lambda mod: min(off[id(p)] for p in mod.parameters() if p.requires_grad)  # noqa: E731
         n = model._flat_grad.numel()
         if stage_chunks is None:
             stage_chunks = int(os.environ.get("NMH_DP_STAGE2_CHUNKS", "3"))
-        self.chunk_stage = self.CHUNK_STAGE if len(model.stages) > self.CHUNK_STAGE else -1
-        self.chunk_groups = stage_chunk_groups(model, self.chunk_stage, stage_chunks) if self.chunk_stage >= 0 else []
+        nstages = len(enc.stages) if enc is not None else 0
+        self.chunk_stage = self.CHUNK_STAGE if nstages > self.CHUNK_STAGE else -1
+        self.chunk_groups = stage_chunk_groups(enc, self.chunk_stage, stage_chunks) if self.chunk_stage >= 0 else []
         nc = max(1, len(self.chunk_groups))
         self.nchunks = nc
-        # coarse forward-order boundaries: [embed | stage0 | stage1 | stage2 | stage3 | decoders+head]
-        sb = [0] + [first(st) for st in model.stages] + [first(model.decoder4), n]
+        sb = self._coarse_bounds(enc, first, n)   # [0, start of every stage, start of what follows the last stage, n]; [0, n] without an encoder
         self.stage_bounds = sb
         b = []
-        for si in range(len(model.stages) + 1):       # entry si = start of segment "stage si-1" (entry 0: embed)
+        for si in range(len(sb) - 2):       # entry si = start of segment "stage si-1" (entry 0: embed)
             b.append(sb[si])
             if si - 1 == self.chunk_stage and nc > 1:
                 b.extend(first(grp[0]) for grp in self.chunk_groups[1:])
-        b += sb[len(model.stages) + 1:]
+        b += sb[len(sb) - 2:]
         self.bounds = b
         self.nseg = len(b) - 1
         self.on_gpu = model._flat_grad.is_cuda
@@ -82,6 +84,17 @@ class GradReducer:
         self.timing = None            # timing_begin(): {"ranges": [(lo, hi, ev0, ev1)], "joins": [(ev_main, ev_comm_end)]} -- HIP events on the comm / main stream
         self.comm_dtype = comm_dtype
         self.staging = torch.empty(n, dtype=comm_dtype, device=model._flat_grad.device) if (comm_dtype and self.active) else None
+
+    # ---- the layout: what a subclass over another flat buffer overrides ------------------------------------------------------------------------
+    def _encoder(self):
+        """the module whose `stages` bound the segments (flattened if it was not); None: the whole buffer is one segment"""
+        if self.model._flat is None:
+            self.model.flatten_parameters()
+        return self.model
+
+    def _coarse_bounds(self, enc, first, n):
+        """coarse forward-order boundaries: [embed | stage0 | stage1 | stage2 | stage3 | decoders+head]"""
+        return [0] + [first(st) for st in enc.stages] + [first(enc.decoder4), n]
 
     def seg_stage(self, si: int, chunk: int = 0) -> int:
         """segment id of encoder stage si (of its block group `chunk` for the chunked stage)"""
@@ -170,6 +183,9 @@ class GradReducer:
         if not self.active:
             return
         lo, hi = self.bounds[seg], self.bounds[seg + 1]
+        if hi <= lo:         # an empty range (FlatGradReducer: nothing behind the last stage)
+            self.pending.append(seg)
+            return
         if not self.on_gpu:  # CPU/gloo (tests): synchronous
             self._exchange(lo, hi)
             self.pending.append(seg)
@@ -203,6 +219,33 @@ class GradReducer:
         self.pending = []
 
 
+class FlatGradReducer(GradReducer):
+    """GradReducer over a finetune.FlatParameters (the detectors, the voxel heads): same exchange, same streams, same switches; only the bounds differ.
+    Segments in forward order of the composite buffer:
+        0 embed | 1 stage 0 | 2 stage 1 | 3 .. 3+nc-1 the nc block groups of stage 2 | 3+nc stage 3 | 4+nc tail
+    The tail is [end of stage 3's parameters, n): whatever the base keeps behind stage 3 (decoder4..2 under a voxel head, nothing under the FPN backbone), then
+    the neck, the heads, encoder1 / decoder1 / the output convs and the Scales.  Every bound is a multiple of 8, the granule of both layouts.  A module without
+    a SwinTransformer_MAE3D_New is one segment, which is its tail.  model.forward_encoder places the stage triggers (it reads trigger, seg_stage, chunk_stage and
+    chunk_groups of base._reducer); fpn.SwinTransformer_FPN_Pretrained_Skip.forward places the tail's."""
+
+    def __init__(self, flat_params, process_group=None, comm_dtype: Optional[torch.dtype] = None, stage_chunks: Optional[int] = None):
+        self.flat = flat_params
+        super().__init__(flat_params, process_group, comm_dtype, stage_chunks)
+
+    def _encoder(self):
+        return self.flat.base
+
+    def _coarse_bounds(self, enc, first, n):
+        if enc is None:
+            return [0, n]
+        off = self.flat._offsets
+        tail = max((off[id(p)] + p.numel() + 7) // 8 * 8 for p in enc.stages[-1].parameters() if p.requires_grad)
+        return [0] + [first(st) for st in enc.stages] + [tail, n]
+
+    def seg_tail(self) -> int:
+        return self.nseg - 1
+
+
 def broadcast_parameters(model, src: int = 0, group=None):
     """DDP's initial parameter broadcast: one flat message."""
     if dist.is_initialized() and dist.get_world_size(group) > 1:
@@ -210,6 +253,20 @@ def broadcast_parameters(model, src: int = 0, group=None):
             model.flatten_parameters()
         dist.broadcast(model._flat, src=src, group=group)
         dist.broadcast(model.pos_embed.data, src=src, group=group)
+
+
+def broadcast_flat_parameters(flat, src: int = 0, group=None):
+    """broadcast_parameters for a finetune.FlatParameters: the flat buffer in one message, then every frozen parameter (pos_embed) and floating-point buffer
+    of the module, which live outside it"""
+    if dist.is_initialized() and dist.get_world_size(group) > 1:
+        dist.broadcast(flat._flat, src=src, group=group)
+        placed = flat._offsets
+        for p in flat.module.parameters():
+            if id(p) not in placed:
+                dist.broadcast(p.data, src=src, group=group)
+        for b in flat.module.buffers():
+            if b.is_floating_point():
+                dist.broadcast(b.data, src=src, group=group)
 
 
 def shard_indices(n: int, rank: int, world: int, epoch: int, shuffle: bool = True, seed: int = 0):

@@ -14,8 +14,8 @@ Ordering of the gradient producers before the optimizer reads the buffer (DESIGN
 before its backward returns, and the base's deferred weight gradients are issued and joined by _EmbedFn.backward and by the end-of-backward callback of its
 queue, so `loss.backward()` returns with every gradient launch ordered before whatever the calling stream is given next.  The step adds no join.
 
-Single process, eager.  dist.GradReducer's segments are those of the MAE layout and a graph capture of the detectors needs padded target lists first; both are
-left out."""
+Eager.  Data-parallel with a dist.FlatGradReducer (FinetuneStep(..., reducer=)): the gradient ranges are exchanged from autograd triggers and by finish().
+A graph capture of the detectors needs padded target lists first and is left out."""
 from __future__ import annotations
 
 from typing import Callable, Dict, Optional
@@ -172,20 +172,29 @@ def loss_fn_for(model) -> Callable:
 
 
 class FinetuneStep:
-    """FinetuneStep(flat_params, opt, loss_fn, weights=None): one eager fine-tuning step.
+    """FinetuneStep(flat_params, opt, loss_fn, weights=None, reducer=None): one eager fine-tuning step.
 
     loss_fn(*batch) -> a tensor or a dict of tensors; the total of a dict is sum(weights.get(k, 1.0) * losses[k]) (the reference's `losses["loss_reg"] *=
     reg_loss_weight; loss = cls + reg + centerness`, run_fcos_pretrained.py:729-731, is weights={"loss_reg": w}).  __call__(*batch): check(), forward, backward,
     the optimizer's three launches.  The AdamW kernel clears the gradient buffer (opt.zero_grads_after_step), so no step starts with a zero fill; the buffer is
     cleared once here.  Returns the UNWEIGHTED losses as detached device tensors (a bare tensor under the key "loss"); nothing waits for the host.
-    Set the step's learning rate and beta1 with opt.set_hyper() before the call."""
+    Set the step's learning rate and beta1 with opt.set_hyper() before the call.
 
-    def __init__(self, flat_params: FlatParameters, opt, loss_fn: Callable, weights: Optional[Dict[str, float]] = None):
+    reducer: a dist.FlatGradReducer over the same FlatParameters.  When it is active (more than one rank, or NMH_DP_FORCE=1) the base gets it as its _reducer,
+    so the forward places the segment triggers, and reducer.finish() runs between backward and the update: every rank then steps on the mean gradient.  With
+    None or an inactive reducer the step issues exactly the launches it issues without one."""
+
+    def __init__(self, flat_params: FlatParameters, opt, loss_fn: Callable, weights: Optional[Dict[str, float]] = None, reducer=None):
         if not flat_params._flat.is_cuda:
             raise RuntimeError("FinetuneStep needs the parameters on a HIP device: call .cuda() on the module before FlatParameters (no CPU fallback)")
         if opt.model is not flat_params:
             raise ValueError("FinetuneStep: the optimizer must have been built over the same FlatParameters (FusedAdamW(flat_params, ...))")
+        if reducer is not None and reducer.model is not flat_params:
+            raise ValueError("FinetuneStep: the reducer must have been built over the same FlatParameters (dist.FlatGradReducer(flat_params, ...))")
         self.flat, self.opt, self.loss_fn, self.weights = flat_params, opt, loss_fn, dict(weights or {})
+        self.reducer = reducer if (reducer is not None and reducer.active) else None
+        if self.reducer is not None and flat_params.base is not None:
+            flat_params.base._reducer = self.reducer
         opt.zero_grads_after_step = True
         flat_params.zero_grad()
 
@@ -206,5 +215,7 @@ class FinetuneStep:
         losses, total = self.forward(*batch)
         total.backward()
         # every gradient launch is ordered before this point on the current stream (module docstring): no join here
+        if self.reducer is not None:
+            self.reducer.finish()   # the ranges no trigger launched, then the join of the comm stream
         self.opt.step()
         return {k: v.detach() for k, v in losses.items()}

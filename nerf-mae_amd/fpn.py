@@ -172,4 +172,10 @@ class SwinTransformer_FPN_Pretrained_Skip(nn.Module):
         # patch_partition + pos_embed in one pass (feature_extractor.py:1179-1180), no masking
         tok = _EmbedFn.apply(b._anchor, b, x.float().contiguous(), None).view(B, g, g, g, b.embed_dim)
         feats = b.forward_encoder(tok)
+        red = b._reducer
+        if red is not None and hasattr(red, "seg_tail"):
+            # data-parallel fine-tuning (dist.FlatGradReducer): the tail range holds the neck and everything behind it.  The neck's backward is ONE node
+            # (_FPNFn) that needs every head's gradient first and joins the side stream before it returns, so the trigger on any one of its inputs fires
+            # behind every gradient launch of the range; the coarsest feature is the first input the encoder's backward consumes.
+            feats[-1] = red.trigger(feats[-1], red.seg_tail())
         return self.fpn_neck.forward_channels_last(feats)

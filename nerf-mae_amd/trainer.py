@@ -639,8 +639,21 @@ def delete_suboptimal_checkpoints(checkpoint_dir: str, metric_name: str = "ap50"
             os.remove(f)
 
 
+def dp_epoch_plan(n: int, batch: int, rank: int, world: int, epoch: int, seed: int = 0):
+    """the batches of one epoch for one rank, as lists of scene indices: rank's shard of dist.shard_indices (the epoch-seeded permutation, padded to a multiple
+    of `world`) cut into ceil(len / batch) slices, the last one ragged (no drop_last).  The shards have equal length, so every rank gets the same number of
+    steps with the same batch sizes.  Raises on an empty shard (n == 0) and on batch < 1."""
+    from .dist import shard_indices
+    if batch < 1 or world < 1 or not 0 <= rank < world:
+        raise ValueError(f"dp_epoch_plan: batch {batch}, rank {rank} of {world}")
+    idx = shard_indices(n, rank, world, epoch, seed=seed)
+    if not idx:
+        raise ValueError("dp_epoch_plan: empty training shard")
+    return [idx[b * batch:(b + 1) * batch] for b in range(-(-len(idx) // batch))]
+
+
 class DetectionTrainer:
-    """Epoch loop of run_fcos_pretrained.py:537-815 without wandb, single GPU, for FCOSOverNeRF: input from data.DetectionBatcher, one optimizer group over
+    """Epoch loop of run_fcos_pretrained.py:537-815 without wandb for FCOSOverNeRF, one process per GPU: input from data.DetectionBatcher, one optimizer group over
     ALL parameters (the reference passes model.parameters(): weight decay applies to everything), clip + AdamW by FusedAdamW over finetune.FlatParameters,
     loss = loss_cls + reg_loss_weight * loss_reg + loss_centerness, the OneCycle schedule stepped every iteration.
 
@@ -655,14 +668,25 @@ class DetectionTrainer:
     0.25 / 0.5 (train_args["ap_top_n"]: detections kept per scene for AP, default all).  Best checkpoints by AP50 and by AP25 under the reference's file names,
     then the best 6 by AP50 are kept (delete_suboptimal_checkpoints).  The checkpoints carry the optimizer state (save_detection_checkpoint).
 
-    train_scenes / val_scenes: stored scenes ((W,L,H,4) arrays or paths); train_boxes / val_boxes: one [G, 6|7] array per scene."""
+    train_scenes / val_scenes: stored scenes ((W,L,H,4) arrays or paths); train_boxes / val_boxes: one [G, 6|7] array per scene.
+
+    Data-parallel (rank, world, reducer; the conventions of Trainer; the reference wraps the model in DDP, run_fcos_pretrained.py:359-361): `batch_size` is per
+    rank and train_args["batch_size"] = batch_size * world (:614); every rank holds all scenes and trains on its shard (dp_epoch_plan).  INVARIANT: every rank
+    runs the same number of steps per epoch with the same batch sizes, the ragged last one included, because dist.shard_indices pads the shards to equal length
+    -- each step holds collectives (the loss normalisers, the gradient ranges), and a rank that ran one step fewer would hang the others.  The model must have
+    been built with world_size=world (its loss all-reduces the normalisers); the constructor broadcasts rank 0's parameters.  `reducer`: a
+    dist.FlatGradReducer over a finetune.FlatParameters of this model, which the trainer then adopts (that is how bf16 buckets are chosen); None with world > 1
+    builds one with fp32 buckets.  The augmentation draws of rank r come from random.Random(seed + 1000003 * r).  The three accumulated epoch losses are
+    averaged over the ranks in ONE all-reduce per epoch (the reference: a barrier and four all-reduces per step, :747-751).  Evaluation, checkpoints and
+    delete_suboptimal_checkpoints run on rank 0 only; the other ranks wait at one barrier per evaluated epoch and their `history` carries the training losses
+    only.  With world = 1 nothing of this is active."""
 
     def __init__(self, model, train_scenes, train_boxes, val_scenes=None, val_boxes=None, batch_size: int = 2, num_epochs: int = 1, lr: float = 3e-4,
                  weight_decay: float = 1e-3, clip_grad_norm: float = 0.1, reg_loss_weight: float = 1.0, eval_interval: int = 1, save_path: str = None,
                  normalize_density: bool = True, flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = 1000,
-                 log=print, train_args: dict = None, seed: int = 0):
+                 log=print, train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None):
         import random
-        from . import data
+        from . import data, dist as _dist
         from .finetune import FinetuneStep, FlatParameters, fcos_loss_fn
         if len(train_scenes) != len(train_boxes) or (val_scenes is not None and len(val_scenes) != len(val_boxes or [])):
             raise ValueError("DetectionTrainer: one box array per scene")
@@ -674,21 +698,35 @@ class DetectionTrainer:
         self.model, self.train_scenes, self.train_boxes, self.val_scenes, self.val_boxes = model, train_scenes, train_boxes, val_scenes, val_boxes
         self.batch, self.epochs, self.eval_interval, self.save_path, self.log, self.seed = batch_size, num_epochs, eval_interval, save_path, log, seed
         self.reg_loss_weight = reg_loss_weight
+        self.rank, self.world = rank, world
+        if world > 1 and getattr(model, "world_size", 1) != world:
+            raise ValueError(f"DetectionTrainer: world = {world}, but the model's loss was built with world_size = {getattr(model, 'world_size', 1)}: its two "
+                             "normalisers would be per-rank sums and the result silently another; build FCOSOverNeRF(..., world_size=world)")
         self.args = _plain(dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, reg_loss_weight=reg_loss_weight,
-                                batch_size=batch_size, num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
-                                rot_scale_prob=rot_scale_prob))
+                                batch_size=batch_size * world, num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob,
+                                rotate_prob=rotate_prob, rot_scale_prob=rot_scale_prob))
         dev = next(model.parameters()).device
         self.batcher = data.DetectionBatcher(resolution, dev, normalize_density, flip_prob, rotate_prob, rot_scale_prob)
         self.val_batcher = data.DetectionBatcher(resolution, dev, normalize_density)
-        self.flat = FlatParameters(model, dev)
+        if reducer is not None:
+            if getattr(reducer.model, "module", None) is not model:
+                raise ValueError("DetectionTrainer: the reducer must be a dist.FlatGradReducer over a finetune.FlatParameters of this model")
+            self.flat = reducer.model
+        else:
+            self.flat = FlatParameters(model, dev)
+            if world > 1:
+                reducer = _dist.FlatGradReducer(self.flat)
+        self.reducer = reducer
+        if world > 1:
+            _dist.broadcast_flat_parameters(self.flat)   # DDP's initial broadcast: every rank starts from rank 0's weights
         self.opt = FusedAdamW(self.flat, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
-        self.steps_per_epoch = -(-len(train_scenes) // batch_size)          # len(train_loader) without drop_last
+        self.steps_per_epoch = len(dp_epoch_plan(len(train_scenes), batch_size, rank, world, 0, seed))   # len(train_loader) without drop_last, the same on every rank
         self.sched = OneCycle(lr, schedule_epochs * self.steps_per_epoch)
-        self.step_fn = FinetuneStep(self.flat, self.opt, fcos_loss_fn(model), weights={"loss_reg": reg_loss_weight})
+        self.step_fn = FinetuneStep(self.flat, self.opt, fcos_loss_fn(model), weights={"loss_reg": reg_loss_weight}, reducer=reducer)
         self.top_n = int(model.args.fpn_post_nms_top_n)
         self.limits = [l for l in (300, 1000, self.top_n) if l <= self.top_n]
         self.ap_top_n = (train_args or {}).get("ap_top_n")
-        self._rng = random.Random(seed)
+        self._rng = random.Random(seed + 1000003 * rank)         # the augmentation draws: another sequence on every rank
         self.global_step, self.best_metric_ap50, self.best_metric_ap25, self.history = 0, None, None, []
 
     @staticmethod
@@ -702,12 +740,9 @@ class DetectionTrainer:
         return [xb[i, :, :e[0], :e[1], :e[2]] for i, e in enumerate(ext)]
 
     def train_epoch(self, epoch: int):
-        from .dist import shard_indices
         self.model.train()
-        idx = shard_indices(len(self.train_scenes), 0, 1, epoch, seed=self.seed)     # the DataLoader's shuffle
         acc = None
-        for b in range(self.steps_per_epoch):
-            ids = idx[b * self.batch:(b + 1) * self.batch]
+        for ids in dp_epoch_plan(len(self.train_scenes), self.batch, self.rank, self.world, epoch, self.seed):     # the DataLoader's shuffle, this rank's shard
             xb, ext, targets = self.batcher.prepare([self._load(self.train_scenes[i]) for i in ids], [self.train_boxes[i] for i in ids], rng=self._rng)
             lr, b1 = self.sched.at(self.global_step)
             self.opt.set_hyper(lr=lr, beta1=b1)
@@ -715,6 +750,10 @@ class DetectionTrainer:
             self.global_step += 1
             parts = torch.stack([losses["loss_cls"], losses["loss_reg"], losses["loss_centerness"]])
             acc = parts if acc is None else acc + parts
+        if self.world > 1:
+            import torch.distributed as tdist
+            tdist.all_reduce(acc, op=tdist.ReduceOp.SUM)              # the epoch's one exchange of the logged losses: their mean over the ranks
+            acc = acc / self.world
         cls, reg, ctr = (acc / self.steps_per_epoch).tolist()         # the epoch's one read-back
         return {"train_loss": cls + self.reg_loss_weight * reg + ctr, "loss_cls": cls, "loss_reg": reg, "loss_centerness": ctr}
 
@@ -743,11 +782,12 @@ class DetectionTrainer:
 
     def fit(self):
         import os
-        if self.save_path:
+        if self.save_path and self.rank == 0:
             os.makedirs(self.save_path, exist_ok=True)
         for epoch in range(1, self.epochs + 1):
             rec = {"epoch": epoch, **self.train_epoch(epoch)}
-            if self.val_scenes and (epoch % self.eval_interval == 0 or epoch == self.epochs):
+            evaluated = bool(self.val_scenes) and (epoch % self.eval_interval == 0 or epoch == self.epochs)    # the same decision on every rank
+            if evaluated and self.rank == 0:
                 rec.update(self.evaluate())
                 ap50, ap25 = rec["ap_50"], rec["ap_25"]
                 if self.save_path:
@@ -758,6 +798,10 @@ class DetectionTrainer:
                         self.best_metric_ap25 = ap25
                         self._save(f"model_best_ap25_ap50_{ap50}_{ap25}.pt", epoch)
                     delete_suboptimal_checkpoints(self.save_path, "ap50", 6, 1)
+            if evaluated and self.world > 1:
+                import torch.distributed as tdist
+                tdist.barrier()        # the other ranks wait here for rank 0's evaluation and files, once per evaluated epoch
             self.history.append(rec)
-            self.log(" ".join(f"{k}={v:.5g}" if isinstance(v, float) else f"{k}={v}" for k, v in rec.items()))
+            if self.rank == 0:
+                self.log(" ".join(f"{k}={v:.5g}" if isinstance(v, float) else f"{k}={v}" for k, v in rec.items()))
         return self.history
