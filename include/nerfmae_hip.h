@@ -560,6 +560,17 @@ NMH_API int nmh_roi_loss_fwd(int64_t M, int n_classes, int ncols, const float* s
 NMH_API int nmh_roi_loss_bwd(int64_t M, int n_classes, int ncols, const float* scores, const float* deltas, const float* labels, const float* targets, const float* scalars, const float* g_obj, const float* g_reg, float* dscores, float* ddeltas, void* stream);
 /* RotatedCoder.decode_single (coder/rotated_coder.py:57-121) / AABBCoder.decode_single (coder/AABB_coder.py:86-137), detector.py:609-611. */
 NMH_API int nmh_roi_decode(int64_t M, int ncols, const float* deltas, const float* rois, int roi_stride, float* boxes, void* stream);
+/* ---- RoI post-processing (Trainer.filter_proposals, nerf_rpn/run_rpn_detect.py:403-439; kernels, semantics, sort key and tie rules: csrc/roi_post.hip) ----
+ * 1 <= N <= 64 scenes of 1 <= R <= 16384 rows; 2 <= n_classes <= 1024; ncols 6 or 7; else -4.  Everything is DEVICE memory and fp32 unless stated.
+ * pred_scores [N R][n_classes] logits, pred_bbox_deltas [N R][ncols] (may be NULL without is_reg), rois [N R][1+ncols] (level, box), counts [N] (clamped to
+ * 0 .. R), mesh_sizes [N][3] int.  Per row: softmax, the decode of nmh_roi_decode (is_reg) or the RoI's own box, clip to the mesh (6 columns) or centre test
+ * (7), size filter, score threshold (threshold_mode 0: any class probability >= score_thresh, the reference's reading; 1: the object probability) ->
+ * cand_boxes [N R][ncols], cand_scores [N R] (the object probability), keys [N R] int (0: dropped or past counts, else the bits of the score plus 1). */
+NMH_API int nmh_roi_post_select(int N, int R, int n_classes, int ncols, const float* pred_scores, const float* pred_bbox_deltas, const float* rois, const int* counts, const int* mesh_sizes, float score_thresh, float min_size, int is_reg, int threshold_mode, float* cand_boxes, float* cand_scores, int* keys, void* stream);
+/* sorted_keys, order [N][R]: the stable descending sort of keys along R and its int64 indices.  mask: workspace of N R ceil(R / 64) words; keep: workspace
+ * [N][R].  NMS per scene (suppressed iff IoU with a kept box > nms_thresh) -> boxes [N][R][ncols], scores [N][R], index [N][R] (source row, -1 past the
+ * count), counts_out [N]; results in descending score, rows past the count zero. */
+NMH_API int nmh_roi_post_nms(int N, int R, int ncols, const float* cand_boxes, const float* cand_scores, const int* sorted_keys, const int64_t* order, float nms_thresh, uint64_t* mask, int* keep, float* boxes, float* scores, int* index, int* counts_out, void* stream);
 /* ---- detection evaluation (nerf_rpn/eval.py; kernels, tie rules and the two stated deviations: csrc/det_eval.hip) ----
  * Common arguments.  N scenes; boxes [N][cap] rows of row_stride floats in DESCENDING score with the box in columns col_offset .. col_offset + ncols - 1 (ncols 6:
  * x0,y0,z0,x1,y1,z1; 7: x,y,z,w,l,h,theta), read in place; counts [N]; gt [N][Gmax][ncols] padded, gt_counts [N].  cap <= 16384, Gmax <= 1024, at most 8 limits and

@@ -8,6 +8,7 @@ __version__ = "0.1.0"
 
 _DET_EVAL = ("det_eval_dense", "DetectionEvaluator", "evaluate_box_proposals_recall", "evaluate_box_proposals_ap")
 _SEM_EVAL = ("SemanticEvaluator", "sem_eval_dense", "intersection_and_union")
+_TWO_STAGE = ("TwoStageDetector", "roi_postprocess_dense", "filter_proposals")
 
 
 def __getattr__(name):
@@ -18,4 +19,7 @@ def __getattr__(name):
     if name in _SEM_EVAL:      # voxel-semantics evaluation (sem_eval.py), likewise
         from . import sem_eval
         return getattr(sem_eval, name)
+    if name in _TWO_STAGE:     # two-stage detector inference (detector.py), likewise
+        from . import detector
+        return getattr(detector, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -886,6 +886,20 @@ int nmh_roi_decode(int64_t M, int ncols, const float* deltas, const float* rois,
   REQ(deltas, rois, boxes);
   return k_roi_decode((long)M, ncols, deltas, rois, roi_stride, boxes, ST);
 }
+int nmh_roi_post_select(int N, int R, int n_classes, int ncols, const float* pred_scores, const float* pred_bbox_deltas, const float* rois, const int* counts, const int* mesh_sizes,
+                        float score_thresh, float min_size, int is_reg, int threshold_mode, float* cand_boxes, float* cand_scores, int* keys, void* stream) {
+  CLR();
+  REQ(pred_scores, rois, counts, mesh_sizes, cand_boxes, cand_scores, keys);
+  if (is_reg) REQ(pred_bbox_deltas);
+  return k_roi_post_select(N, R, n_classes, ncols, pred_scores, pred_bbox_deltas, rois, counts, mesh_sizes, score_thresh, min_size, is_reg ? 1 : 0, threshold_mode, cand_boxes, cand_scores,
+                           keys, ST);
+}
+int nmh_roi_post_nms(int N, int R, int ncols, const float* cand_boxes, const float* cand_scores, const int* sorted_keys, const int64_t* order, float nms_thresh, uint64_t* mask, int* keep,
+                     float* boxes, float* scores, int* index, int* counts_out, void* stream) {
+  CLR();
+  REQ(cand_boxes, cand_scores, sorted_keys, order, mask, keep, boxes, scores, index, counts_out);
+  return k_roi_post_nms(N, R, ncols, cand_boxes, cand_scores, sorted_keys, (const long*)order, nms_thresh, (unsigned long long*)mask, keep, boxes, scores, index, counts_out, ST);
+}
 static bool det_eval_dims_ok(int N, int cap, int Gmax) { return N >= 0 && cap >= 0 && cap <= NMH_OBB_NMS_MAX && Gmax >= 0 && Gmax <= NMH_DET_EVAL_MAX_GT; }
 int nmh_det_eval_iou(int ncols, int N, int cap, int row_stride, int col_offset, const float* boxes, const int* counts, int Gmax, const float* gt, const int* gt_counts, float* iouT,
                      float* best_iou, int* best_gt, void* stream) {

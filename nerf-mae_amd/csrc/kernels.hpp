@@ -353,6 +353,12 @@ int k_roi_loss_fwd(long M, int n_classes, int ncols, const float* scores, const 
 int k_roi_loss_bwd(long M, int n_classes, int ncols, const float* scores, const float* deltas, const float* labels, const float* targets, const float* scalars, const float* g_obj,
                    const float* g_reg, float* dscores, float* ddeltas, hipStream_t st);
 int k_roi_decode(long M, int ncols, const float* deltas, const float* rois, int roi_stride, float* out, hipStream_t st);
+// ---- roi_post.hip (RoI post-processing: softmax, decode, clip, size and score filters, NMS per scene) ----
+// Everything DEVICE.  N <= NMH_FCOS_MAX_SCENES, R <= NMH_OBB_NMS_MAX, 2 <= n_classes <= NMH_ROI_MAX_CLASSES.  Semantics, sort key and tie rules: roi_post.hip.
+int k_roi_post_select(int N, int R, int n_classes, int ncols, const float* pred_scores, const float* pred_bbox_deltas, const float* rois, const int* counts, const int* mesh_sizes,
+                      float score_thresh, float min_size, int is_reg, int threshold_mode, float* cand_boxes, float* cand_scores, int* keys, hipStream_t st);
+int k_roi_post_nms(int N, int R, int ncols, const float* cand_boxes, const float* cand_scores, const int* sorted_keys, const long* order, float nms_thresh, unsigned long long* mask,
+                   int* keep, float* boxes, float* scores, int* index, int* counts_out, hipStream_t st);
 // ---- det_eval.hip (detection evaluation: IoU matrix and row best, greedy recall matching, AP claims, precision / recall scan) ----
 // limits, thresholds: HOST arrays; everything else DEVICE.  Layouts, tie rules and the deviations from eval.py: det_eval.hip.
 #define NMH_DET_EVAL_MAX_GT 1024

@@ -455,3 +455,217 @@ class Classification_Model(nn.Module):
             gt_labels = [labels[i, :k] for i, k in enumerate(ks)]
         out_boxes = roi_decode(pred_bbox_deltas, flat_rois).reshape(N, R, -1) if is_reg else sample_rois[..., 1:]
         return [[out_boxes[i, :k] for i, k in enumerate(ks)], gt_labels], [cls_prob[i * R:i * R + k] for i, k in enumerate(ks)], loss
+
+    HEAD_BLOCK = 256
+
+    def _head_blocks(self, pooled):
+        """RCNN_model over blocks of exactly HEAD_BLOCK rows, the last one zero-padded.  The box head is torch (nn.Linear, nn.Conv3d), whose libraries choose their
+        kernel, and with it the order of a row's sums, by the shape of the whole call; with one fixed shape a row's logits and deltas do not depend on how many
+        rows share its call, so predict_dense gives the same bits for every chunk_rows.  -> (pred_bbox_deltas, pred_scores)
+        This rests on a property of the libraries' kernels that nothing guarantees: within a call of one shape, a row's result depends neither on its position
+        nor on the other rows.  It held for the two Linear layers (is_add_layer off, is_flatten on) on the rocBLAS this was written against; the conv layers of
+        is_add_layer and the mean-pooled head were not measured.  tests/test_two_stage_gpu.py::test_chunked_prediction_is_bit_identical is
+        the check, and the place to look after a library update.  The price is one head call per 256 rows, about 0.8 ms at 2 x 2000 rows."""
+        M, B = pooled.shape[0], self.HEAD_BLOCK
+        deltas, scores = [], []
+        for m0 in range(0, M, B):
+            blk = pooled[m0:m0 + B]
+            n = blk.shape[0]
+            if n < B:
+                blk = F.pad(blk, (0, 0) * (blk.dim() - 1) + (0, B - n))
+            d, s = self.RCNN_model(blk)
+            deltas.append(d[:n])
+            scores.append(s[:n])
+        return torch.cat(deltas), torch.cat(scores)
+
+    def predict_dense(self, boxes, levels, counts, features, chunk_rows=None):
+        """The evaluation forward without ground truth: pooling, then RCNN_model, for all N x R rows of the dense triple (boxes [N,R,6|7], levels [N,R] int32,
+        counts [N] int32) of rpn_proposals_dense -> (pred_scores [N*R, n_classes] logits, pred_bbox_deltas [N*R, 6|7], rois_used [N*R, 1+6|7]: the RoIs the
+        head's deltas refer to, enlarged for oriented boxes with remap off, as in forward).  Rows past counts are computed like any other (zero boxes pool to
+        zeros); roi_postprocess_dense ignores them.  chunk_rows: the rows of every scene go through pooling and head chunk_rows at a time, which bounds the
+        pooled tensor (the reference chunks by cls_batch_size); the loop is over fixed sizes and needs no host wait.  The head always runs in blocks of
+        HEAD_BLOCK rows (_head_blocks), so the results are the same bits for every chunk_rows.  No gradient."""
+        name = "Classification_Model.predict_dense"
+        _check(name, boxes)
+        if boxes.dim() != 3 or boxes.shape[2] != self.reg_dim:
+            raise ValueError(f"{name}: boxes must be [N, R, {self.reg_dim}], got {tuple(boxes.shape)}")
+        N, R, B = boxes.shape
+        levels = _int32(name, "levels", levels, (N, R))
+        _int32(name, "counts", counts, (N,))
+        step = R if chunk_rows is None else int(chunk_rows)
+        if step < 1:
+            raise ValueError(f"{name}: chunk_rows must be at least 1, got {chunk_rows}")
+        with torch.no_grad():
+            original_size = []
+            if self.feature_extractor is not None:
+                flat = self.transform([f[0] for f in features])
+                original_size = [f.shape[1:] for f in flat]
+                features = [f.to(torch.float32) for f in self.feature_extractor(torch.stack(flat, dim=0))]
+            rois = torch.cat([levels.to(torch.float32)[..., None], boxes.detach()], -1)
+            scores, deltas = [], []
+            for r0 in range(0, R, step):
+                part = rois[:, r0:r0 + step].contiguous()
+                d, s = self._head_blocks(self.pooling_model(features, part, original_size))
+                scores.append(s.reshape(N, part.shape[1], -1))
+                deltas.append(d.reshape(N, part.shape[1], -1))
+            if self.pooling_model.is_rotated_bbox and not self.pooling_model.remap:
+                rois = torch.cat([rois[..., :1], self.pooling_model.enlarge_roi(rois[..., 1:])], -1)
+            return torch.cat(scores, 1).reshape(N * R, -1), torch.cat(deltas, 1).reshape(N * R, B), rois.reshape(N * R, 1 + B).contiguous()
+
+
+# ---- post-processing of the second stage -------------------------------------------------------------------------------------------------------
+POST_MAX_ROWS, POST_MASK_BYTES_MAX = ops.ROI_POST_MAX_ROWS, ops.ROI_POST_MASK_BYTES_MAX
+
+
+def _mesh_sizes(name, mesh_sizes, N, dev):
+    """a triple, a list of N triples, or an int32 device tensor [N, 3] -> int32 device tensor [N, 3] (a host list costs one small copy)"""
+    if isinstance(mesh_sizes, torch.Tensor):
+        if mesh_sizes.dtype != torch.int32 or tuple(mesh_sizes.shape) != (N, 3) or not mesh_sizes.is_cuda:
+            raise ValueError(f"{name}: mesh_sizes must be a triple, a list of {N} triples or an int32 device tensor [{N}, 3]")
+        return mesh_sizes.contiguous()
+    rows = list(mesh_sizes)
+    if len(rows) == 3 and not isinstance(rows[0], (list, tuple, torch.Size, np.ndarray)):
+        rows = [rows] * N
+    if len(rows) != N or any(len(r) != 3 for r in rows):
+        raise ValueError(f"{name}: mesh_sizes must be a triple, a list of {N} triples or an int32 device tensor [{N}, 3]")
+    if any(float(v) != int(v) for r in rows for v in r):    # the reference passes shape * spatial_scale, floats: int() would cut a size down silently
+        raise ValueError(f"{name}: mesh_sizes must be whole numbers, got {rows}")
+    return torch.tensor([[int(v) for v in r] for r in rows], dtype=torch.int32).to(dev, non_blocking=True)
+
+
+def roi_postprocess_dense(pred_scores, pred_bbox_deltas, rois, counts, mesh_sizes, score_thresh=0.5, nms_thresh=0.1, min_size=1e-3, is_reg=True, threshold_mode="any"):
+    """Trainer.filter_proposals (run_rpn_detect.py:403-439) for all scenes at once, with the softmax and the decode of the evaluation forward in front of it.
+    pred_scores [N*R, K] logits, pred_bbox_deltas [N*R, 6|7] (None without is_reg), rois [N*R, 1+6|7] (or the three with [N, R, ..]), counts [N] int32 device
+    (clamped to 0 .. R), mesh_sizes: a triple, N triples or an int32 device tensor [N, 3] (use the tensor when capturing).
+    -> (boxes [N, R, 6|7], scores [N, R], index [N, R] int32, counts [N] int32): scene i's results are rows 0 .. counts[i]-1 in descending score (equal scores:
+    the lower row first), index the source row of each (gather gt_labels or anything else by it); rows past them are zero with index -1.
+    threshold_mode "any" (the reference's reading): a row passes iff any class probability >= score_thresh; "object": iff p[1] does.  Semantics: the header of
+    csrc/roi_post.hip.  Never waits for the host; capturable with torch.cuda.graph on one stream."""
+    name = "roi_postprocess_dense"
+    _check(name, pred_scores, rois)
+    if threshold_mode not in ops.ROI_POST_MODES:
+        raise ValueError(f"{name}: threshold_mode must be one of {sorted(ops.ROI_POST_MODES)}, got {threshold_mode!r}")
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.dim() != 1 or not counts.is_cuda:
+        raise ValueError(f"{name}: counts must be an int32 device tensor [N]")
+    N = counts.shape[0]
+    if not 1 <= N <= MAX_SCENES:
+        raise ValueError(f"{name} supports 1 to {MAX_SCENES} scenes, got {N}")
+    if rois.shape[-1] not in (7, 8):
+        raise ValueError(f"{name}: rois must be [N*R, 1+6|7] (level, box), got {tuple(rois.shape)}")
+    B, K = rois.shape[-1] - 1, pred_scores.shape[-1]
+    M = rois.numel() // (1 + B)
+    if M < N or M % N:
+        raise ValueError(f"{name}: {M} rows do not divide into {N} scenes of at least one row")
+    R = M // N
+    if R > POST_MAX_ROWS:
+        raise ValueError(f"{name} supports at most {POST_MAX_ROWS} rows per scene, got {R}")
+    if not 2 <= K <= MAX_CLASSES:
+        raise ValueError(f"{name} supports 2 to {MAX_CLASSES} classes, got {K}")
+    if N * R * ((R + 63) // 64) * 8 > POST_MASK_BYTES_MAX:
+        raise ValueError(f"{name}: the suppression workspace of {N} scenes x {R} rows exceeds {POST_MASK_BYTES_MAX} bytes; pass fewer scenes per call")
+    if pred_scores.numel() != M * K:
+        raise ValueError(f"{name}: pred_scores must have {M} rows, got {tuple(pred_scores.shape)}")
+    deltas = None
+    if is_reg:
+        _check(name, pred_bbox_deltas)
+        if pred_bbox_deltas.shape[-1] != B or pred_bbox_deltas.numel() != M * B:
+            raise ValueError(f"{name}: pred_bbox_deltas must be [{M}, {B}], got {tuple(pred_bbox_deltas.shape)}")
+        deltas = pred_bbox_deltas.detach().reshape(M, B).contiguous()
+    with torch.no_grad():
+        mesh = _mesh_sizes(name, mesh_sizes, N, rois.device)
+        cand_boxes, cand_scores, keys = ops.roi_post_select(N, R, B, pred_scores.detach().reshape(M, K).contiguous(), deltas, rois.detach().reshape(M, 1 + B).contiguous(),
+                                                            counts.contiguous(), mesh, float(score_thresh), float(min_size), bool(is_reg), ops.ROI_POST_MODES[threshold_mode])
+        sorted_keys, order = torch.sort(keys, dim=1, descending=True, stable=True)        # dropped rows (key 0) sort last
+        return ops.roi_post_nms(B, cand_boxes, cand_scores, sorted_keys, order, float(nms_thresh))
+
+
+def filter_proposals(proposals, objectness, gt_labels, mesh_sizes, score_threhold=0.8, nms_thresh=0.1, min_size=1e-3, threshold_mode="any"):
+    """Trainer.filter_proposals with the reference's name, argument order and spelling: per scene proposals [K, 6|7] (already decoded), objectness [K, n_classes]
+    class PROBABILITIES, gt_labels [K] (anything per row, passed through), mesh_sizes per scene -> (final_boxes, final_scores [k, n_classes], final_gt_labels)
+    per scene, in descending objectness[:, 1].  The kernel takes logits: log(objectness) is handed over with is_reg=False, and softmax(log p) = p for rows that
+    sum to 1, as a softmax's do (a probability of 0 becomes -inf and comes back as 0).  One host wait, for the N counts."""
+    name = "filter_proposals"
+    N = len(proposals)
+    if not (N == len(objectness) == len(gt_labels)) or N < 1:
+        raise ValueError(f"{name}: one proposal, objectness and label tensor per scene")
+    _check(name, *proposals, *objectness)
+    B = proposals[0].shape[-1]
+    boxes, levels, counts, ks = _pack(name, [F.pad(p.detach().reshape(-1, B), (1, 0)) for p in proposals], B)
+    R = boxes.shape[1]
+    logits = torch.stack([F.pad(torch.log(o.detach()), (0, 0, 0, R - k)) for o, k in zip(objectness, ks)])
+    rois = torch.cat([levels.to(torch.float32)[..., None], boxes], -1)
+    out_boxes, _, index, kept = roi_postprocess_dense(logits, None, rois, counts, mesh_sizes, score_threhold, nms_thresh, min_size, False, threshold_mode)
+    kept = kept.tolist()                  # the one synchronisation
+    rows = [index[i, :k].long() for i, k in enumerate(kept)]
+    return [out_boxes[i, :k] for i, k in enumerate(kept)], [o[r] for o, r in zip(objectness, rows)], [g[r.to(g.device)] for g, r in zip(gt_labels, rows)]
+
+
+# ---- the two stages joined ---------------------------------------------------------------------------------------------------------------------
+class TwoStageDetector(nn.Module):
+    """A NeRFRegionProposalNetwork and a Classification_Model(feature_extractor=None) on the same FPN features: the backbone runs once, rpn.proposals_dense
+    hands its dense triple to the second stage, and in evaluation roi_postprocess_dense turns the head's outputs into detections (the reference runs the two
+    stages as two programs, run_rpn.py and run_rpn_detect.py, with the proposals on disk between them).
+
+    Training, forward(meshes, targets): {"loss_objectness", "loss_rpn_box_reg"} of the sampled second stage (all ground-truth labels 1, as
+    run_rpn_detect.py:351); the first stage runs under no_grad unless train_rpn, in which case its three losses are added under "rpn_"-prefixed keys (its head
+    then runs twice, once for the losses and once for the proposals).  The features carry gradient to the backbone through the pooling either way.
+    keep / keep_counts replace the second stage's sampler (roi_targets_dense).
+    Evaluation: detections_dense(meshes) -> (boxes [N,R,6|7], scores [N,R], counts [N] int32), what DetectionEvaluator.update takes, without a host wait;
+    forward(meshes) -> (boxes, scores) as per-scene lists, with one host wait.  Boxes are clipped to, and oriented centres tested against, each scene's own
+    size before padding.  state_dict: the parts' keys under rpn_network. and roi_model.RCNN_model."""
+
+    def __init__(self, rpn_network, roi_model, score_thresh, nms_thresh, min_size=1e-3, is_reg=True, threshold_mode="any", train_rpn=False):
+        super().__init__()
+        if roi_model.feature_extractor is not None:
+            raise ValueError("TwoStageDetector: the second stage must be a Classification_Model(feature_extractor=None); it reads the first stage's features")
+        if threshold_mode not in ops.ROI_POST_MODES:
+            raise ValueError(f"TwoStageDetector: threshold_mode must be one of {sorted(ops.ROI_POST_MODES)}, got {threshold_mode!r}")
+        if bool(rpn_network.rpn.rotate) != bool(roi_model.is_rotated_bbox):
+            raise ValueError("TwoStageDetector: both stages must use the same box form")
+        self.rpn_network, self.roi_model = rpn_network, roi_model
+        self.score_thresh, self.nms_thresh, self.min_size = score_thresh, nms_thresh, min_size
+        self.is_reg, self.threshold_mode, self.train_rpn = is_reg, threshold_mode, train_rpn
+        self.chunk_rows = None
+        self._size_cache = {}
+        if not train_rpn:                                  # the first stage's head gets no gradient: it is frozen, so that an optimizer's weight decay leaves it alone
+            for p in rpn_network.rpn.parameters():
+                p.requires_grad_(False)
+
+    def _first_stage(self, meshes, targets=None):
+        """-> (features, (boxes, levels, counts), sizes int32 device [N,3], the first stage's losses or {})"""
+        net = self.rpn_network
+        sizes = tuple(tuple(int(v) for v in m.shape[-3:]) for m in meshes)
+        meshes, _ = net.transform(list(meshes))
+        x = torch.stack(meshes, dim=0)
+        key = (sizes, x.device)
+        if key not in self._size_cache:                    # one host-to-device copy per distinct set of sizes
+            self._size_cache[key] = torch.tensor(sizes, dtype=torch.int32, device=x.device)
+        ori = self._size_cache[key]
+        features = list(net.backbone(x))
+        losses = {}
+        if self.training and self.train_rpn:
+            losses = net.rpn(x, features, ori, targets)[2]
+        with torch.no_grad():
+            boxes, _, levels, _, counts = net.rpn.proposals_dense(x, features, ori)
+        return features, (boxes, levels, counts), ori, losses
+
+    def detections_dense(self, meshes):
+        with torch.no_grad():
+            features, (boxes, levels, counts), sizes, _ = self._first_stage(meshes)
+            pred_scores, pred_bbox_deltas, rois = self.roi_model.predict_dense(boxes, levels, counts, features, self.chunk_rows)
+            out_boxes, scores, _, kept = roi_postprocess_dense(pred_scores, pred_bbox_deltas, rois, counts, sizes, self.score_thresh, self.nms_thresh, self.min_size, self.is_reg,
+                                                               self.threshold_mode)
+        return out_boxes, scores, kept
+
+    def forward(self, meshes, targets=None, keep=None, keep_counts=None):
+        if not self.training:
+            boxes, scores, counts = self.detections_dense(meshes)
+            counts = counts.tolist()              # the one synchronisation
+            return [boxes[i, :k] for i, k in enumerate(counts)], [scores[i, :k] for i, k in enumerate(counts)]
+        if targets is None:
+            raise ValueError("TwoStageDetector: targets should not be None in training mode")
+        features, dense, _, rpn_losses = self._first_stage(meshes, targets)
+        gt_labels = [t.new_ones(t.shape[0]) for t in targets]
+        losses = dict(self.roi_model(dense, targets, gt_labels, features, is_sample=True, keep=keep, keep_counts=keep_counts)[2])
+        losses.update({"rpn_" + k: v for k, v in rpn_losses.items()})
+        return losses

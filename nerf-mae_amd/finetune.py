@@ -137,7 +137,7 @@ class FlatParameters:
             raise RuntimeError("FlatParameters.check: the SwinTransformer_MAE3D_New flattened itself again; build a new FlatParameters and optimizer")
 
 
-# ---- loss functions of the four downstream models ----------------------------------------------------------------------------------------------
+# ---- loss functions of the five downstream models ----------------------------------------------------------------------------------------------
 def fcos_loss_fn(model) -> Callable:
     """FCOSOverNeRF: (meshes, targets) -> {"loss_cls", "loss_reg", "loss_centerness"}"""
     return lambda meshes, targets: model(list(meshes), targets)[1]
@@ -146,6 +146,12 @@ def fcos_loss_fn(model) -> Callable:
 def rpn_loss_fn(model) -> Callable:
     """NeRFRegionProposalNetwork: (meshes, targets) -> {"loss_objectness", "loss_rpn_box_reg", "loss_rpn_box_reg_2d"}"""
     return lambda meshes, targets: model(list(meshes), targets)[1]
+
+
+def roi_loss_fn(model) -> Callable:
+    """detector.TwoStageDetector: (meshes, targets) -> {"loss_objectness", "loss_rpn_box_reg"} of the second stage (and the first stage's under "rpn_" keys with
+    train_rpn); weights={"loss_rpn_box_reg": reg_loss_weight} reproduces run_rpn_detect.py:359-363"""
+    return lambda meshes, targets, *sampler: model(list(meshes), targets, *sampler)
 
 
 def voxel_loss_fn(model) -> Callable:
@@ -159,6 +165,7 @@ def voxel_loss_fn(model) -> Callable:
 
 
 def loss_fn_for(model) -> Callable:
+    from .detector import TwoStageDetector
     from .fcos import FCOSOverNeRF
     from .heads import _VoxelHeadBase
     from .rpn import NeRFRegionProposalNetwork
@@ -166,6 +173,8 @@ def loss_fn_for(model) -> Callable:
         return fcos_loss_fn(model)
     if isinstance(model, NeRFRegionProposalNetwork):
         return rpn_loss_fn(model)
+    if isinstance(model, TwoStageDetector):
+        return roi_loss_fn(model)
     if isinstance(model, _VoxelHeadBase):
         return voxel_loss_fn(model)
     raise TypeError(f"loss_fn_for: no ready-made loss function for {type(model).__name__}; pass your own to FinetuneStep")

@@ -2068,6 +2068,39 @@ def roi_decode(ncols, deltas, rois):
     return out
 
 
+# ---- RoI post-processing: softmax, decode, clip, size and score filters, NMS per scene (csrc/roi_post.hip) ----------------------------------------
+ROI_POST_MAX_ROWS = OBB_NMS_MAX            # rows per scene: the walk's removed-set is 256 words of LDS
+ROI_POST_MASK_BYTES_MAX = 1 << 30         # the suppression workspace N R ceil(R / 64) 8 of one call
+ROI_POST_MODES = {"any": 0, "object": 1}
+
+
+def roi_post_select(N, R, ncols, pred_scores, pred_bbox_deltas, rois, counts, mesh_sizes, score_thresh, min_size, is_reg, threshold_mode):
+    """pred_scores [N*R,K] logits, pred_bbox_deltas [N*R,ncols] (None without is_reg), rois [N*R,1+ncols], counts [N] int32, mesh_sizes [N,3] int32 ->
+    (cand_boxes [N,R,ncols], cand_scores [N,R], keys [N,R] int32: 0 dropped, else the bits of the score plus 1)"""
+    _chk(pred_scores, pred_bbox_deltas, rois, counts, mesh_sizes)
+    dev = pred_scores.device
+    cand_boxes = torch.empty((N, R, ncols), dtype=torch.float32, device=dev)
+    cand_scores = torch.empty((N, R), dtype=torch.float32, device=dev)
+    keys = torch.empty((N, R), dtype=torch.int32, device=dev)
+    lib().call("nmh_roi_post_select", N, R, pred_scores.shape[1], ncols, pred_scores, pred_bbox_deltas, rois, counts, mesh_sizes, score_thresh, min_size, int(bool(is_reg)),
+               int(threshold_mode), cand_boxes, cand_scores, keys, _st())
+    return cand_boxes, cand_scores, keys
+
+
+def roi_post_nms(ncols, cand_boxes, cand_scores, sorted_keys, order, nms_thresh):
+    """the stable descending sort (sorted_keys int32, order int64) of the keys -> (boxes [N,R,ncols], scores [N,R], index [N,R] int32, counts [N] int32)"""
+    _chk(cand_boxes, cand_scores, sorted_keys, order)
+    N, R = cand_scores.shape
+    dev = cand_boxes.device
+    mask = torch.empty((N, R, (R + 63) // 64), dtype=torch.int64, device=dev)
+    keep = torch.empty((N, R), dtype=torch.int32, device=dev)
+    boxes, scores = torch.empty_like(cand_boxes), torch.empty_like(cand_scores)
+    index = torch.empty((N, R), dtype=torch.int32, device=dev)
+    counts = torch.empty((N,), dtype=torch.int32, device=dev)
+    lib().call("nmh_roi_post_nms", N, R, ncols, cand_boxes, cand_scores, sorted_keys, order, nms_thresh, mask, keep, boxes, scores, index, counts, _st())
+    return boxes, scores, index, counts
+
+
 # ---- FCOSHead between its tower convolutions: GroupNorm + ReLU and the three 3x3x3 output convs (csrc/fcos_head.hip) ------------------------------
 FCOS_HEAD_MAX_LEVELS = 5           # the reference's FCOSHead has five Scale parameters
 FCOS_HEAD_MAX_JOBS = 2 * FCOS_HEAD_MAX_LEVELS

@@ -615,6 +615,35 @@ def load_detection_checkpoint(path: str, model, opt: "FusedAdamW" = None) -> dic
     return ck
 
 
+def save_two_stage_checkpoint(path: str, model, epoch: int, train_args: dict, opt: "FusedAdamW" = None, step: int = None, fine_tune: bool = True):
+    """the reference's second-stage checkpoint (run_rpn_detect.py:261-269): {"epoch", "backbone_state_dict" (None unless fine_tune), "RCNN_dict", "train_args"} of a
+    detector.TwoStageDetector, keys and shapes the reference's, so its RCNN loads "RCNN_dict" unchanged.  The first stage's head, which the reference keeps in
+    run_rpn.py's own file, goes under "rpn_state_dict".  With `opt` (a FusedAdamW over a finetune.FlatParameters of this model) the file also carries the
+    "resume" section of save_checkpoint, in place of the reference's torch optimizer and scheduler state."""
+    model = getattr(model, "module", model)
+    cpu = lambda sd: {k: v.detach().cpu() for k, v in sd.items()}
+    ck = {"epoch": epoch, "backbone_state_dict": cpu(model.rpn_network.backbone.state_dict()) if fine_tune else None,
+          "RCNN_dict": cpu(model.roi_model.RCNN_model.state_dict()), "rpn_state_dict": cpu(model.rpn_network.rpn.state_dict()), "train_args": _plain(dict(train_args))}
+    if opt is not None:
+        ck["resume"] = resume_section(opt.model, opt, step)
+    torch.save(ck, path)
+
+
+def load_two_stage_checkpoint(path: str, model, opt: "FusedAdamW" = None) -> dict:
+    """loads a second-stage checkpoint (also one written by the reference) strictly into the parts it carries: "RCNN_dict" always, the backbone and the first
+    stage's head where present; returns the checkpoint dict.  With `opt` and a "resume" section the optimizer continues where it stopped."""
+    model = getattr(model, "module", model)
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    model.roi_model.RCNN_model.load_state_dict(ck["RCNN_dict"], strict=True)
+    if ck.get("backbone_state_dict") is not None:
+        model.rpn_network.backbone.load_state_dict(ck["backbone_state_dict"], strict=True)
+    if ck.get("rpn_state_dict") is not None:
+        model.rpn_network.rpn.load_state_dict(ck["rpn_state_dict"], strict=True)
+    if opt is not None and "resume" in ck:
+        restore_resume(ck["resume"], opt.model, opt, "load_two_stage_checkpoint")
+    return ck
+
+
 def delete_suboptimal_checkpoints(checkpoint_dir: str, metric_name: str = "ap50", max_to_keep: int = 6, min_to_keep: int = 1):
     """run_fcos_pretrained.py:507-535: every *.pt of the directory is ranked by the number its name carries -- for "ap50" the second-to-last '_' field, which
     is AP50 under both best-checkpoint name patterns; for "ap25" the last field -- and all but the max(max_to_keep, min_to_keep) highest are removed; ties keep
