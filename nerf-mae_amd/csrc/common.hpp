@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef unsigned short bf16_t;  // raw bfloat16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
@@ -175,6 +176,11 @@ __device__ __forceinline__ Frag<bf16_t> tr_frag(const TrFrag& f) {
 }
 
 // ---- misc ---------------------------------------------------------------------------------------
+// compile-time loop: f(std::integral_constant<int, I>{}) for I = first .. E-1, for indices that must be constants (fragment element setters)
+template <int I, int E> struct ForE {
+  template <typename F> static __device__ __forceinline__ void run(F&& f) { f(std::integral_constant<int, I>{}); ForE<I + 1, E>::run(f); }
+};
+template <int E> struct ForE<E, E> { template <typename F> static __device__ __forceinline__ void run(F&&) {} };
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -44,6 +44,7 @@
 #include "obb_geom.hpp"
 #include "fcos_decode.hpp"
 #include "levels4.hpp"
+#include "reduce_fixed.hpp"
 
 namespace {
 
@@ -61,48 +62,23 @@ struct FcosOffs { int off[NMH_FCOS_MAX_SCENES + 1]; };
 
 struct Where { int lvl, scene, loc, n; long p; bool active; };
 __device__ __forceinline__ Where fcos_where(const FcosGeom& G) {
+  const LevelItem at = level_item(G.blk0, G.bpl, G.L);
   Where q;
-  int b = blockIdx.x;
-  q.lvl = 0;
-#pragma unroll
-  for (int k = 1; k < 4; ++k) if (k < G.L && b >= G.blk0[k]) q.lvl = k;
-  b -= pick4(G.blk0, q.lvl);
-  const int bpl = pick4(G.bpl, q.lvl);
+  q.lvl = at.lvl; q.scene = at.scene; q.loc = at.i;
   q.n = pick4(G.n, q.lvl);
-  q.scene = b / bpl;
-  q.loc = (b - q.scene * bpl) * 256 + (int)threadIdx.x;
   q.active = q.loc < q.n;
   q.p = pick4(G.p0, q.lvl) + (long)q.scene * q.n + q.loc;
   return q;
-}
-
-// sums (a, b) over the workgroup in a fixed order -> out[0], out[1] (thread 0)
-__device__ __forceinline__ void block_sum2(float a, float b, float* __restrict__ out) {
-  __shared__ float red[2][4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o, 64); b += __shfl_down(b, o, 64); }
-  const int t = threadIdx.x;
-  if ((t & 63) == 0) { red[0][t >> 6] = a; red[1][t >> 6] = b; }
-  __syncthreads();
-  if (t == 0) { out[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]); out[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]); }
 }
 
 // one workgroup: fixed-order sum of the per-workgroup partials, then the normalisation
 enum { FIN_SCALARS = 0, FIN_CLS = 1, FIN_POS = 2 };
 __global__ __launch_bounds__(256) void fcos_final_kernel(const float* __restrict__ partials, int nblocks, int what, float world, float* __restrict__ scalars, float* __restrict__ out0,
                                                          float* __restrict__ out1) {
-  __shared__ float sa[256], sb[256];
-  const int t = threadIdx.x;
-  float a = 0.f, b = 0.f;
-  for (int i = t; i < nblocks; i += 256) { a += partials[2 * i]; b += partials[2 * i + 1]; }
-  sa[t] = a; sb[t] = b;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) { sa[t] += sa[t + o]; sb[t] += sb[t + o]; }
-    __syncthreads();
-  }
-  if (t != 0) return;
-  a = sa[0]; b = sb[0];
+  float sum[2];
+  final_sum_fixed(partials, nblocks, sum);
+  if (threadIdx.x != 0) return;
+  const float a = sum[0], b = sum[1];
   if (what == FIN_SCALARS) { scalars[0] = a; scalars[1] = b; return; }
   const float norm_pos = fmaxf(scalars[0] / world, 1.f), csum = scalars[1];
   if (what == FIN_CLS) { out0[0] = a / norm_pos; return; }
@@ -273,7 +249,8 @@ __global__ __launch_bounds__(256) void fcos_assign_kernel(FcosGeom G, FcosOffs S
     for (int k = 0; k < C; ++k) targets[q.p * C + k] = d[k];
     ok = v && bi >= 0;
   }
-  block_sum2(ok ? 1.f : 0.f, ok ? ct : 0.f, partials + 2 * (long)blockIdx.x);
+  float sum[2] = {ok ? 1.f : 0.f, ok ? ct : 0.f};
+  block_sum_fixed(sum, partials + 2 * (long)blockIdx.x);
 }
 
 // ---- focal loss ------------------------------------------------------------------------------------------------------------------------
@@ -294,7 +271,8 @@ __global__ __launch_bounds__(256) void fcos_focal_fwd_kernel(FcosGeom G, Ptr4<co
     fcos_sig(x, sp, p, q);
     v = labels[w.p] > 0.f ? 0.25f * (sp - x) * q * q : 0.75f * sp * p * p;
   }
-  block_sum2(v, 0.f, partials + 2 * (long)blockIdx.x);
+  float sum[2] = {v, 0.f};               // the second sum is not used
+  block_sum_fixed(sum, partials + 2 * (long)blockIdx.x);
 }
 __global__ __launch_bounds__(256) void fcos_focal_bwd_kernel(FcosGeom G, Ptr4<const float> cls, const float* __restrict__ labels, const unsigned char* __restrict__ valid,
                                                              const float* __restrict__ scalars, float world, const float* __restrict__ g_out, Ptr4<float> dcls) {
@@ -379,7 +357,7 @@ __global__ __launch_bounds__(256) void fcos_pos_fwd_kernel(FcosGeom G, Ptr4<cons
                                                            float* __restrict__ partials) {
   constexpr int C = KIND == FCOS_AABB ? 6 : 8;
   const Where w = fcos_where(G);
-  float vr = 0.f, vc = 0.f;
+  float v[2] = {0.f, 0.f};              // regression, centerness
   if (w.active && valid[w.p] && labels[w.p] > 0.f) {
     const float* rp = pick4(reg.p, w.lvl) + (long)w.scene * C * w.n + w.loc;
     float p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, t[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, gp[8];
@@ -388,11 +366,11 @@ __global__ __launch_bounds__(256) void fcos_pos_fwd_kernel(FcosGeom G, Ptr4<cons
     const float ct = ctr_t[w.p];
     float term = KIND == FCOS_AABB ? fcos_aabb_term<false>(p, t, loss_type, gp) : fcos_obb_term<KIND>(p, t, loss_type);
     if (KIND != FCOS_AABB && add_l1) term += smooth_l1(p[6] - t[6]) + smooth_l1(p[7] - t[7]);
-    vr = term * ct;
+    v[0] = term * ct;
     const float c = pick4(ctr.p, w.lvl)[(long)w.scene * w.n + w.loc];
-    vc = fmaxf(c, 0.f) - c * ct + log1pf(expf(-fabsf(c)));
+    v[1] = fmaxf(c, 0.f) - c * ct + log1pf(expf(-fabsf(c)));
   }
-  block_sum2(vr, vc, partials + 2 * (long)blockIdx.x);
+  block_sum_fixed(v, partials + 2 * (long)blockIdx.x);
 }
 
 template <int KIND>

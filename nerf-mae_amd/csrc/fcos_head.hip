@@ -26,7 +26,6 @@
 //              (bf16: split into hi + lo = bf16(G) + bf16(G - hi), two instructions, so that G keeps 16 mantissa bits), B = 8 strided elements of a.
 // Tower columns: cls tower j = 0 cls_logits, j = 1 centerness unless centerness_on_reg; bbox tower j = 0 .. nreg-1 bbox_pred, j = nreg centerness if
 // centerness_on_reg.  Rows of W16 past the tower's columns are zero.  Tap t = (a 3 + b) 3 + c reads voxel (w + a - 1, l + b - 1, h + c - 1): nn.Conv3d's order.
-#include <type_traits>
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -478,10 +477,6 @@ template <> struct WideFrag<float> {
 };
 template <int E> __device__ __forceinline__ void frag_set(Frag<bf16_t>& f, bf16_t x) { f.v[E] = (short)x; }
 template <int E> __device__ __forceinline__ void frag_set(Frag<float>& f, float x) { f.v[E] = x; }
-template <int I, int E> struct ForE {
-  template <typename F> static __device__ __forceinline__ void run(F&& f) { f(std::integral_constant<int, I>{}); ForE<I + 1, E>::run(f); }
-};
-template <int E> struct ForE<E, E> { template <typename F> static __device__ __forceinline__ void run(F&&) {} };
 
 // Workgroup (b, tower) sums the steps [b steps / nb, (b + 1) steps / nb) of every level into its partial image [16][27][C]; the (tap, 32-channel) output
 // tiles go round the 4 waves and every wave walks all the workgroup's steps for each of its tiles.

@@ -145,21 +145,12 @@ __global__ __launch_bounds__(256) void fcos_post_nms_mask_kernel(PostGeom G, con
                                                                  float thr, unsigned long long* __restrict__ mask) {
   constexpr int ROW = AABB ? 7 : 8;
   __shared__ BoxTile rows[64], cols[64];
-  const int t = threadIdx.x, scene = blockIdx.y, capw = (G.cap + 63) >> 6;
+  const int scene = blockIdx.y, capw = (G.cap + 63) >> 6;
   const int nb = scene_count(G, pre_counts, scene);
-  int by, j;
-  tri_block(blockIdx.x, capw, by, j);
-  const int r0 = by * 64, c0 = j * 64;
-  if (c0 >= nb) return;                                // uniform; r0 <= c0
   const long sb = (long)scene * G.cap;
-  if (t < 128) {
-    const int i = (t < 64 ? c0 : r0 - 64) + t;
-    BoxTile& dst = t < 64 ? cols[t] : rows[t - 64];
-    if (i < nb) stage_box<AABB>(pre_boxes + sb * ROW + 1, min(max(order[sb + i], 0L), (long)G.cap - 1), (long)G.cap, dst, ROW);      // + 1: past the level column
-    else zero_box(dst);
-  }
-  __syncthreads();
-  nms_mask_tile<AABB>(rows, cols, r0, c0, j, nb, thr, mask + sb * capw, capw, nullptr, nullptr);
+  NmsBlock at;                                         // col 1: past the level column
+  if (!nms_stage_sorted<AABB>(blockIdx.x, capw, pre_boxes + sb * ROW, ROW, 1, order + sb, 0L, (long)G.cap - 1, nb, rows, cols, at)) return;
+  nms_mask_tile<AABB>(rows, cols, at.r0, at.c0, at.j, nb, thr, mask + sb * capw, capw, nullptr, nullptr);
 }
 
 // one workgroup per scene; cap <= 16384 (256 words of removed-set)

@@ -1,8 +1,11 @@
-// Bit-matrix NMS over boxes in descending score, shared by rotated_iou.hip (obb_nms_*), fcos_post.hip (one matrix per scene) and rpn_post.hip (one per scene
-// and level).  Word (i, j) of a matrix of row_words 64-bit words per row has bit k set iff iou(i, 64 j + k) > threshold and 64 j + k > i.  Only the upper
-// triangle of 64 x 64 blocks is launched: one workgroup of 256 lanes per block, one wave per word (lane k takes column 64 j + k, the ballot is the word); words
-// strictly below the diagonal block are zero by definition, never read and never written.  The walk is one workgroup of 256 lanes: per block of 64 rows it
-// resolves the block's own dependencies from the 64 diagonal words, then ORs the rows of the kept boxes into the removed-set in LDS.
+// Bit-matrix NMS over boxes in descending score, shared by rotated_iou.hip (obb_nms_*), fcos_post.hip and roi_post.hip (one matrix per scene) and rpn_post.hip
+// (one per scene and level).  Word (i, j) of a matrix of row_words 64-bit words per row has bit k set iff iou(i, 64 j + k) > threshold and 64 j + k > i.  Only
+// the upper triangle of 64 x 64 blocks is launched: one workgroup of 256 lanes per block, one wave per word (lane k takes column 64 j + k, the ballot is the
+// word); words strictly below the diagonal block are zero by definition, never read and never written.  A mask workgroup finds its block (tri_block), stages
+// the block's row and column boxes in LDS and forms its words (nms_mask_tile); the three post-processing files, whose boxes are reached through the caller's
+// sort order, stage with nms_stage_sorted, and rotated_iou.hip, which has categories and no order, stages on its own.  The walk (nms_greedy_walk) is one
+// workgroup of 256 lanes: per block of 64 rows it resolves the block's own dependencies from the 64 diagonal words, then ORs the rows of the kept boxes into
+// the removed-set in LDS.
 #pragma once
 #include "obb_geom.hpp"             // BoxTile, stage_box, tile_iou
 
@@ -13,6 +16,28 @@ __device__ __forceinline__ void tri_block(int b, int nw, int& by, int& j) {
   by = 0; j = b;
   while (j >= nw - by) { j -= nw - by; ++by; }       // uniform, at most nw <= 256 steps
   j += by;
+}
+
+// Workgroup b of the upper triangle of nw x nw blocks over nb boxes: its position -> (r0, c0 = 64 j, j), and its row and column boxes -> rows, cols, ready
+// behind a barrier.  Sorted position i is row clamp(order[i], lo, hi) of boxes, rows of `stride` floats with the box at float `col`; positions past nb are
+// zero boxes.  Returns false, uniformly and before any staging, when the block's columns start beyond nb (r0 <= c0): it has no word to write.
+struct NmsBlock { int r0, c0, j; };
+template <bool AABB>
+__device__ __forceinline__ bool nms_stage_sorted(int b, int nw, const float* __restrict__ boxes, int stride, int col, const long* __restrict__ order, long lo, long hi, int nb,
+                                                 BoxTile* rows, BoxTile* cols, NmsBlock& at) {
+  int by;
+  tri_block(b, nw, by, at.j);
+  at.r0 = by * 64; at.c0 = at.j * 64;
+  if (at.c0 >= nb) return false;
+  const int t = threadIdx.x;
+  if (t < 128) {
+    const int i = (t < 64 ? at.c0 : at.r0 - 64) + t;
+    BoxTile& dst = t < 64 ? cols[t] : rows[t - 64];
+    if (i < nb) stage_box<AABB>(boxes + col, min(max(order[i], lo), hi), hi + 1, dst, stride);
+    else zero_box(dst);
+  }
+  __syncthreads();
+  return true;
 }
 
 // the words (r0 .. r0+63, j) of a matrix of nb boxes at m0, from the staged row and column boxes (c0 = 64 j); rcat / cat: the staged categories of the rows and

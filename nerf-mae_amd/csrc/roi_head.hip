@@ -38,6 +38,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "select_scan.hpp"
+#include "reduce_fixed.hpp"
 #include "levels4.hpp"
 #include "rpn_geom.hpp"
 #include "rpn_shared.hpp"
@@ -395,25 +396,6 @@ __device__ __forceinline__ void roi_encode_obb(const float* __restrict__ g, cons
   o[7] = 0.f;
 }
 
-// sums four values over the workgroup of 256 in a fixed order -> out[0 .. 3] (thread 0)
-__device__ __forceinline__ void roi_block_sum4(float (&v)[4], float* __restrict__ out) {
-  __shared__ float red[4][4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] += __shfl_down(v[k], o, 64);
-  }
-  const int t = threadIdx.x;
-  if ((t & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) red[k][t >> 6] = v[k];
-  }
-  __syncthreads();
-  if (t == 0) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-  }
-}
 __device__ __forceinline__ int roi_label(float lab, int ncls) { return lab >= 0.f && lab < (float)ncls ? (int)lab : -1; }
 
 template <bool ORIENTED>
@@ -428,10 +410,8 @@ __global__ __launch_bounds__(256) void roi_loss_fwd_kernel(long M, int ncls, con
     float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (li >= 0) {
       const float* __restrict__ s = scores + m * ncls;
-      float mx = s[0];
-      for (int c = 1; c < ncls; ++c) mx = fmaxf(mx, s[c]);
-      float sum = 0.f;
-      for (int c = 0; c < ncls; ++c) sum += expf(s[c] - mx);
+      float mx, sum;
+      row_softmax(s, ncls, mx, sum);
       v[0] = mx + logf(sum) - s[li];
       v[2] = 1.f;
       const float* __restrict__ e = rois + m * rstride + (rstride - B);
@@ -446,33 +426,18 @@ __global__ __launch_bounds__(256) void roi_loss_fwd_kernel(long M, int ncls, con
 #pragma unroll
     for (int k = 0; k < B; ++k) targets[m * B + k] = o[k];
   }
-  roi_block_sum4(v, partials + 4 * (long)blockIdx.x);
+  block_sum_fixed(v, partials + 4 * (long)blockIdx.x);
 }
 
 // one workgroup: fixed-order sum of the partials -> scalars = (objectness loss, box loss, valid rows, positive rows)
 __global__ __launch_bounds__(256) void roi_loss_final_kernel(const float* __restrict__ partials, int nblocks, float* __restrict__ scalars) {
-  __shared__ float s[4][256];
-  const int t = threadIdx.x;
-  float a[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int i = t; i < nblocks; i += 256) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) a[k] += partials[4 * i + k];
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) s[k][t] = a[k];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s[k][t] += s[k][t + o];
-    }
-    __syncthreads();
-  }
-  if (t != 0) return;
-  scalars[0] = s[2][0] > 0.f ? s[0][0] / s[2][0] : 0.f;
-  scalars[1] = s[3][0] > 0.f ? s[1][0] / s[3][0] : 0.f;
-  scalars[2] = s[2][0];
-  scalars[3] = s[3][0];
+  float sum[4];
+  final_sum_fixed(partials, nblocks, sum);
+  if (threadIdx.x != 0) return;
+  scalars[0] = sum[2] > 0.f ? sum[0] / sum[2] : 0.f;
+  scalars[1] = sum[3] > 0.f ? sum[1] / sum[3] : 0.f;
+  scalars[2] = sum[2];
+  scalars[3] = sum[3];
 }
 
 template <int B>
@@ -487,10 +452,8 @@ __global__ __launch_bounds__(256) void roi_loss_bwd_kernel(long M, int ncls, con
   float* __restrict__ ds = dscores + m * ncls;
   if (li >= 0 && nv > 0.f && g_obj) {
     const float sc = g_obj[0] / nv;
-    float mx = s[0];
-    for (int c = 1; c < ncls; ++c) mx = fmaxf(mx, s[c]);
-    float sum = 0.f;
-    for (int c = 0; c < ncls; ++c) sum += expf(s[c] - mx);
+    float mx, sum;
+    row_softmax(s, ncls, mx, sum);
     for (int c = 0; c < ncls; ++c) ds[c] = (expf(s[c] - mx) / sum - (c == li ? 1.f : 0.f)) * sc;
   } else {
     for (int c = 0; c < ncls; ++c) ds[c] = 0.f;

@@ -35,6 +35,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "nms_bits.hpp"
+#include "reduce_fixed.hpp"
 #include "roi_decode.hpp"
 
 namespace {
@@ -53,10 +54,8 @@ __global__ __launch_bounds__(256) void roi_post_select_kernel(int N, int R, int 
   bool ok = false;
   if (exists) {
     const float* __restrict__ x = logits + m * K;
-    float mx = x[0];
-    for (int c = 1; c < K; ++c) mx = fmaxf(mx, x[c]);
-    float sum = 0.f;
-    for (int c = 0; c < K; ++c) sum += expf(x[c] - mx);
+    float mx, sum;
+    row_softmax(x, K, mx, sum);
     s = expf(x[1] - mx) / sum;
     const float pmax = 1.f / sum;                      // exp(mx - mx) / sum
     const float* __restrict__ e = rois + m * (1 + B) + 1;
@@ -100,21 +99,12 @@ __global__ __launch_bounds__(256) void roi_post_nms_mask_kernel(int R, const flo
                                                                 unsigned long long* __restrict__ mask) {
   constexpr int B = AABB ? 6 : 7;
   __shared__ BoxTile rows[64], cols[64];
-  const int t = threadIdx.x, scene = blockIdx.y, rw = (R + 63) >> 6;
+  const int scene = blockIdx.y, rw = (R + 63) >> 6;
   const long sb = (long)scene * R;
   const int nb = surviving(sorted_keys + sb, R);
-  int by, j;
-  tri_block(blockIdx.x, rw, by, j);
-  const int r0 = by * 64, c0 = j * 64;
-  if (c0 >= nb) return;                                // uniform; r0 <= c0
-  if (t < 128) {
-    const int i = (t < 64 ? c0 : r0 - 64) + t;
-    BoxTile& dst = t < 64 ? cols[t] : rows[t - 64];
-    if (i < nb) stage_box<AABB>(cand_boxes + sb * B, source_row(order, sb, R, i), (long)R, dst);
-    else zero_box(dst);
-  }
-  __syncthreads();
-  nms_mask_tile<AABB>(rows, cols, r0, c0, j, nb, thr, mask + sb * rw, rw, nullptr, nullptr);
+  NmsBlock at;
+  if (!nms_stage_sorted<AABB>(blockIdx.x, rw, cand_boxes + sb * B, B, 0, order + sb, 0L, (long)R - 1, nb, rows, cols, at)) return;
+  nms_mask_tile<AABB>(rows, cols, at.r0, at.c0, at.j, nb, thr, mask + sb * rw, rw, nullptr, nullptr);
 }
 
 // one workgroup per scene; R <= 16384 (256 words of removed-set)

@@ -36,6 +36,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "select_scan.hpp"
+#include "reduce_fixed.hpp"
 #include "rpn_geom.hpp"
 #include "rpn_shared.hpp"
 
@@ -249,55 +250,34 @@ __device__ __forceinline__ RHead rpn_head_where(const RpnGeom& G) {
   r.p = (long)q.scene * G.ntot + pick4(G.off, q.lvl) + (long)r.loc * r.A + r.a;
   return r;
 }
-// sums (a, b, c) over the workgroup in a fixed order -> out[0 .. 2] (thread 0)
-__device__ __forceinline__ void block_sum3(float a, float b, float c, float* __restrict__ out) {
-  __shared__ float red[3][4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o, 64); b += __shfl_down(b, o, 64); c += __shfl_down(c, o, 64); }
-  const int t = threadIdx.x;
-  if ((t & 63) == 0) { red[0][t >> 6] = a; red[1][t >> 6] = b; red[2][t >> 6] = c; }
-  __syncthreads();
-  if (t == 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-  }
-}
 
 template <int C>
 __global__ __launch_bounds__(256) void rpn_loss_fwd_kernel(RpnGeom G, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
                                                            const float* __restrict__ targets, float* __restrict__ partials) {
   const RHead w = rpn_head_where(G);
-  float vo = 0.f, vr = 0.f, cnt = 0.f;
+  float v[3] = {0.f, 0.f, 0.f};         // objectness, box regression, sampled anchors
   const int f = w.active ? flags[w.p] : 0;
   if (f != 0) {
     const float x = pick4(obj.p, w.lvl)[(long)w.scene * w.A * w.nloc + w.j];
-    vo = fmaxf(x, 0.f) - (f == 1 ? x : 0.f) + log1pf(expf(-fabsf(x)));
-    cnt = 1.f;
+    v[0] = fmaxf(x, 0.f) - (f == 1 ? x : 0.f) + log1pf(expf(-fabsf(x)));
+    v[2] = 1.f;
     if (f == 1) {
       const float* __restrict__ rp = pick4(reg.p, w.lvl) + ((long)w.scene * w.A + w.a) * C * w.nloc + w.loc;
 #pragma unroll
-      for (int k = 0; k < C; ++k) vr += rpn_sl1(rp[(long)k * w.nloc] - targets[w.p * C + k]);
+      for (int k = 0; k < C; ++k) v[1] += rpn_sl1(rp[(long)k * w.nloc] - targets[w.p * C + k]);
     }
   }
-  block_sum3(vo, vr, cnt, partials + 3 * (long)blockIdx.x);
+  block_sum_fixed(v, partials + 3 * (long)blockIdx.x);
 }
 
 // one workgroup: fixed-order sum of the per-workgroup partials -> scalars = (objectness loss, box loss, number of sampled anchors)
 __global__ __launch_bounds__(256) void rpn_loss_final_kernel(const float* __restrict__ partials, int nblocks, float* __restrict__ scalars) {
-  __shared__ float s[3][256];
-  const int t = threadIdx.x;
-  float a = 0.f, b = 0.f, c = 0.f;
-  for (int i = t; i < nblocks; i += 256) { a += partials[3 * i]; b += partials[3 * i + 1]; c += partials[3 * i + 2]; }
-  s[0][t] = a; s[1][t] = b; s[2][t] = c;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) { s[0][t] += s[0][t + o]; s[1][t] += s[1][t + o]; s[2][t] += s[2][t + o]; }
-    __syncthreads();
-  }
-  if (t != 0) return;
-  const float cnt = s[2][0];
-  scalars[0] = cnt > 0.f ? s[0][0] / cnt : 0.f;
-  scalars[1] = cnt > 0.f ? s[1][0] / cnt : 0.f;
+  float sum[3];
+  final_sum_fixed(partials, nblocks, sum);
+  if (threadIdx.x != 0) return;
+  const float cnt = sum[2];
+  scalars[0] = cnt > 0.f ? sum[0] / cnt : 0.f;
+  scalars[1] = cnt > 0.f ? sum[1] / cnt : 0.f;
   scalars[2] = cnt;
 }
 

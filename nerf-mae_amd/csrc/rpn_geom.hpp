@@ -1,5 +1,6 @@
-// Level geometry of the RPN kernels (rpn.hip, rpn_post.hip): the by-value kernel arguments, the workgroup -> (level, scene, anchor) map, the anchor derived
-// from its index with the padding test, and the host-side builders of the arguments (the per-level pointer plumbing: levels4.hpp).  Layouts and semantics: the header of rpn.hip.
+// Level geometry of the RPN kernels (rpn.hip, rpn_post.hip): the by-value kernel arguments, the workgroup -> (level, scene, anchor) map (level_item of
+// levels4.hpp with the anchor's bound), the anchor derived from its index with the padding test, and the host-side builders of the arguments (the per-level
+// pointer plumbing: levels4.hpp).  Layouts and semantics: the header of rpn.hip.
 #pragma once
 #include "common.hpp"
 #include "kernels.hpp"
@@ -20,17 +21,8 @@ struct RpnBase { float h[4][RPN_MAX_A][3]; };       // kernel argument, by value
 
 struct RAt { int lvl, scene, i; bool active; };
 __device__ __forceinline__ RAt rpn_where(const RpnGeom& G) {
-  RAt q;
-  int b = blockIdx.x;
-  q.lvl = 0;
-#pragma unroll
-  for (int k = 1; k < 4; ++k) if (k < G.L && b >= G.blk0[k]) q.lvl = k;
-  b -= pick4(G.blk0, q.lvl);
-  const int bps = pick4(G.bps, q.lvl);
-  q.scene = b / bps;
-  q.i = (b - q.scene * bps) * 256 + (int)threadIdx.x;
-  q.active = q.i < pick4(G.n, q.lvl);
-  return q;
+  const LevelItem at = level_item(G.blk0, G.bps, G.L);
+  return RAt{at.lvl, at.scene, at.i, at.i < pick4(G.n, at.lvl)};
 }
 
 struct Box6 { float x0, y0, z0, x1, y1, z1, vol; };

@@ -20,7 +20,6 @@
 // bits), so that the loss gradient is not rounded to 8 bits before it is summed; everything accumulates in fp32.  No LDS, no scratch: operands are read
 // straight from memory (t is read once per 64 output columns: once for A <= 7; the weights and G stay in L1 / L2).
 // A wave owns a 32-voxel tile of one (level, scene); tiles are numbered level-major over all levels, start[k] = first tile of level k.
-#include <type_traits>
 #include "levels4.hpp"
 #include "kernels.hpp"
 
@@ -116,11 +115,6 @@ __device__ __forceinline__ f32x16 acc_zero() {
   for (int i = 0; i < 16; ++i) z[i] = 0.f;
   return z;
 }
-// compile-time element index for the fragment setters
-template <int I, int E> struct ForE {
-  template <typename F> static __device__ __forceinline__ void run(F&& f) { f(std::integral_constant<int, I>{}); ForE<I + 1, E>::run(f); }
-};
-template <int E> struct ForE<E, E> { template <typename F> static __device__ __forceinline__ void run(F&&) {} };
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------------------------
 template <typename T>

@@ -195,25 +195,13 @@ __global__ __launch_bounds__(256) void rpn_post_nms_mask_kernel(RpnGeom G, RpnPo
                                                                 const int* __restrict__ pre_counts, float thr, unsigned long long* __restrict__ mask) {
   constexpr int ROW = AABB ? 6 : 7;
   __shared__ BoxTile rows[64], cols[64];
-  const int t = threadIdx.x, scene = blockIdx.y;
-  int lvl = 0;
-#pragma unroll
-  for (int k = 1; k < 4; ++k) if (k < G.L && (int)blockIdx.x >= P.blk0[k]) lvl = k;
+  const int scene = blockIdx.y, lvl = level_of_block(P.blk0, G.L, blockIdx.x);
   const int tw = pick4(P.tw, lvl), top = pick4(P.top, lvl), off = pick4(P.off, lvl);
   const int nb = level_count(G, P, pre_counts, lvl, scene);
-  int by, j;
-  tri_block((int)blockIdx.x - pick4(P.blk0, lvl), tw, by, j);
-  const int r0 = by * 64, c0 = j * 64;
-  if (c0 >= nb) return;                                // uniform; r0 <= c0
   const long sb = (long)scene * P.cap;
-  if (t < 128) {
-    const int i = (t < 64 ? c0 : r0 - 64) + t;
-    BoxTile& dst = t < 64 ? cols[t] : rows[t - 64];
-    if (i < nb) stage_box<AABB>(pre_boxes + sb * ROW, sorted_slot(P, order, sb, off, top, i), (long)P.cap, dst);
-    else zero_box(dst);
-  }
-  __syncthreads();
-  nms_mask_tile<AABB>(rows, cols, r0, c0, j, nb, thr, mask + (long)scene * P.mtot + pick4(P.moff, lvl), tw, nullptr, nullptr);
+  NmsBlock at;                                         // the clamp keeps a position within the level's slots for any input
+  if (!nms_stage_sorted<AABB>((int)blockIdx.x - pick4(P.blk0, lvl), tw, pre_boxes + sb * ROW, ROW, 0, order + sb + off, (long)off, (long)off + top - 1, nb, rows, cols, at)) return;
+  nms_mask_tile<AABB>(rows, cols, at.r0, at.c0, at.j, nb, thr, mask + (long)scene * P.mtot + pick4(P.moff, lvl), tw, nullptr, nullptr);
 }
 
 // one workgroup per scene; t_k <= 16384 (256 words of removed-set)

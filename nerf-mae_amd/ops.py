@@ -1599,6 +1599,12 @@ FCOS_MAX_SCENES, FCOS_MAX_LEVELS = 64, 4
 FCOS_LOSS_TYPES = {"iou": 0, "linear_iou": 1, "giou": 2, "diou": 3}
 
 
+def _ptr_table(tensors, n=None):
+    """device tensors -> host array of their pointers (None -> NULL); n: the length the entry expects, a plan's level count"""
+    assert n is None or len(tensors) == n
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
 class FcosPlan:
     """feature sizes [(w,l,h)] and strides of 1..4 levels, N scenes -> the host-side level table of the fcos entries, the locations per level
     and in all (P = N sum n_k), and the size of the partial-sum workspace"""
@@ -1616,11 +1622,6 @@ class FcosPlan:
         self.nblocks = lib().cdll.nmh_fcos_num_blocks(self.L, self.dims, self.N)
         if self.nblocks <= 0:
             raise ValueError(f"FCOS ops: unsupported level table {feature_sizes} x {self.strides}")
-
-    def table(self, tensors):
-        """per-level device tensors -> host array of their pointers"""
-        assert len(tensors) == self.L
-        return (ctypes.c_void_p * self.L)(*[t.data_ptr() for t in tensors])
 
     def workspace(self, device):
         return torch.empty((2 * self.nblocks,), dtype=torch.float32, device=device)
@@ -1640,35 +1641,35 @@ def fcos_assign(plan, boxes, offsets, ncols, grid_sizes, masks, radius, norm_tar
     scalars = torch.empty((2,), dtype=torch.float32, device=dev)
     partials = plan.workspace(dev)
     offs = (ctypes.c_int * (plan.N + 1))(*offsets)
-    lib().call("nmh_fcos_assign", plan.L, plan.dims, plan.N, ncols, boxes if boxes.numel() else None, offs, grid_sizes, plan.table(masks) if masks else None, radius,
+    lib().call("nmh_fcos_assign", plan.L, plan.dims, plan.N, ncols, boxes if boxes.numel() else None, offs, grid_sizes, _ptr_table(masks, plan.L) if masks else None, radius,
                int(bool(norm_targets)), labels, targets, gt_index, ctr_t, valid, partials, scalars, _st())
     return labels, targets, gt_index, ctr_t, valid, scalars, partials
 
 
 def fcos_focal_fwd(plan, cls, labels, valid, scalars, world, partials):
     loss = torch.empty((), dtype=torch.float32, device=labels.device)
-    lib().call("nmh_fcos_focal_fwd", plan.L, plan.dims, plan.N, plan.table(cls), labels, valid, scalars, world, partials, loss, _st())
+    lib().call("nmh_fcos_focal_fwd", plan.L, plan.dims, plan.N, _ptr_table(cls, plan.L), labels, valid, scalars, world, partials, loss, _st())
     return loss
 
 
 def fcos_focal_bwd(plan, cls, labels, valid, scalars, world, g_loss):
     dcls = [torch.empty_like(t) for t in cls]
-    lib().call("nmh_fcos_focal_bwd", plan.L, plan.dims, plan.N, plan.table(cls), labels, valid, scalars, world, g_loss, plan.table(dcls), _st())
+    lib().call("nmh_fcos_focal_bwd", plan.L, plan.dims, plan.N, _ptr_table(cls, plan.L), labels, valid, scalars, world, g_loss, _ptr_table(dcls, plan.L), _st())
     return dcls
 
 
 def fcos_pos_fwd(plan, ncols, loss_type, add_l1, reg, ctr, labels, targets, ctr_t, valid, scalars, world, partials):
     reg_loss = torch.empty((), dtype=torch.float32, device=labels.device)
     ctr_loss = torch.empty((), dtype=torch.float32, device=labels.device)
-    lib().call("nmh_fcos_pos_fwd", plan.L, plan.dims, plan.N, ncols, loss_type, int(bool(add_l1)), plan.table(reg), plan.table(ctr), labels, targets, ctr_t, valid, scalars, world,
+    lib().call("nmh_fcos_pos_fwd", plan.L, plan.dims, plan.N, ncols, loss_type, int(bool(add_l1)), _ptr_table(reg, plan.L), _ptr_table(ctr, plan.L), labels, targets, ctr_t, valid, scalars, world,
                partials, reg_loss, ctr_loss, _st())
     return reg_loss, ctr_loss
 
 
 def fcos_pos_bwd(plan, ncols, loss_type, add_l1, reg, ctr, labels, targets, ctr_t, valid, scalars, world, g_reg, g_ctr):
     dreg, dctr = [torch.empty_like(t) for t in reg], [torch.empty_like(t) for t in ctr]
-    lib().call("nmh_fcos_pos_bwd", plan.L, plan.dims, plan.N, ncols, loss_type, int(bool(add_l1)), plan.table(reg), plan.table(ctr), labels, targets, ctr_t, valid, scalars, world,
-               g_reg, g_ctr, plan.table(dreg), plan.table(dctr), _st())
+    lib().call("nmh_fcos_pos_bwd", plan.L, plan.dims, plan.N, ncols, loss_type, int(bool(add_l1)), _ptr_table(reg, plan.L), _ptr_table(ctr, plan.L), labels, targets, ctr_t, valid, scalars, world,
+               g_reg, g_ctr, _ptr_table(dreg, plan.L), _ptr_table(dctr, plan.L), _st())
     return dreg, dctr
 
 
@@ -1719,10 +1720,6 @@ class FcosPostPlan:
         self.dims = (ctypes.c_int * self.L)(*self.n)
         assert lib().cdll.nmh_fcos_post_cap(self.L, self.dims, self.N, self.top_n) == self.cap
 
-    def table(self, tensors):
-        assert len(tensors) == self.L
-        return (ctypes.c_void_p * self.L)(*[t.data_ptr() for t in tensors])
-
 
 def fcos_post_select(plan, ncols, cls, reg, ctr, locations, masks, grid_sizes, pre_nms_thresh, min_size):
     """per-level head outputs, locations [n,3], optional per-level masks, grid_sizes int32 [N,3] (required for ncols 6) ->
@@ -1734,8 +1731,8 @@ def fcos_post_select(plan, ncols, cls, reg, ctr, locations, masks, grid_sizes, p
     pre_boxes = torch.empty((plan.N, plan.cap, row), dtype=torch.float32, device=dev)
     pre_scores = torch.empty((plan.N, plan.cap), dtype=torch.float32, device=dev)
     pre_counts = torch.empty((plan.L, plan.N), dtype=torch.int32, device=dev)
-    lib().call("nmh_fcos_post_select", plan.L, plan.dims, plan.N, ncols, plan.top_n, plan.table(cls), plan.table(reg), plan.table(ctr), plan.table(locations),
-               plan.table(masks) if masks else None, grid_sizes, pre_nms_thresh, min_size, keys, pre_boxes, pre_scores, pre_counts, _st())
+    lib().call("nmh_fcos_post_select", plan.L, plan.dims, plan.N, ncols, plan.top_n, _ptr_table(cls, plan.L), _ptr_table(reg, plan.L), _ptr_table(ctr, plan.L), _ptr_table(locations, plan.L),
+               _ptr_table(masks, plan.L) if masks else None, grid_sizes, pre_nms_thresh, min_size, keys, pre_boxes, pre_scores, pre_counts, _st())
     return pre_boxes, pre_scores, pre_counts
 
 
@@ -1782,11 +1779,6 @@ class RpnPlan:
         if self.nblocks <= 0 or min(flat) <= 0:
             raise ValueError(f"RPN ops: unsupported level table {grid_sizes} x {strides} x {self.A} anchors")
 
-    def table(self, tensors):
-        """per-level device tensors -> host array of their pointers"""
-        assert len(tensors) == self.L
-        return (ctypes.c_void_p * self.L)(*[t.data_ptr() for t in tensors])
-
 
 def rpn_assign(plan, boxes, offsets, ncols, ori_sizes, fg, bg):
     """boxes [G,6|7] fp32 (may be empty), offsets host ints [N+1], ori_sizes int32 [N,3] or None ->
@@ -1818,13 +1810,13 @@ def rpn_loss_fwd(plan, C, obj, reg, flags, targets):
     dev = flags.device
     partials = torch.empty((3 * plan.nblocks,), dtype=torch.float32, device=dev)
     scalars = torch.empty((3,), dtype=torch.float32, device=dev)
-    lib().call("nmh_rpn_loss_fwd", plan.L, plan.dims, plan.N, C, plan.table(obj), plan.table(reg), flags, targets, partials, scalars, _st())
+    lib().call("nmh_rpn_loss_fwd", plan.L, plan.dims, plan.N, C, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, targets, partials, scalars, _st())
     return scalars
 
 
 def rpn_loss_bwd(plan, C, obj, reg, flags, targets, scalars, g_obj, g_reg):
     dobj, dreg = [torch.empty_like(t) for t in obj], [torch.empty_like(t) for t in reg]
-    lib().call("nmh_rpn_loss_bwd", plan.L, plan.dims, plan.N, C, plan.table(obj), plan.table(reg), flags, targets, scalars, g_obj, g_reg, plan.table(dobj), plan.table(dreg), _st())
+    lib().call("nmh_rpn_loss_bwd", plan.L, plan.dims, plan.N, C, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, targets, scalars, g_obj, g_reg, _ptr_table(dobj, plan.L), _ptr_table(dreg, plan.L), _st())
     return dobj, dreg
 
 
@@ -1854,7 +1846,7 @@ def rpn_decode(plan, ncols, reg):
     """per-level regression (N, A*6|8, W, H, D) -> the unclipped decode of every anchor [N, n, 6|7], anchor order"""
     _chk(*reg)
     boxes = torch.empty((plan.N, plan.n, 6 if ncols == 6 else 7), dtype=torch.float32, device=reg[0].device)
-    lib().call("nmh_rpn_decode", plan.L, plan.dims, plan.base, plan.N, ncols, plan.table(reg), boxes, _st())
+    lib().call("nmh_rpn_decode", plan.L, plan.dims, plan.base, plan.N, ncols, _ptr_table(reg, plan.L), boxes, _st())
     return boxes
 
 
@@ -1869,7 +1861,7 @@ def rpn_post_select(post, ncols, obj, reg, ori_sizes, mesh_size, score_thresh, m
     pre_index = torch.empty((plan.N, post.cap), dtype=torch.int32, device=dev)
     pre_counts = torch.empty((plan.L, plan.N), dtype=torch.int32, device=dev)
     mesh = (ctypes.c_int * 3)(*[int(v) for v in mesh_size])
-    lib().call("nmh_rpn_post_select", plan.L, plan.dims, plan.base, plan.N, ncols, post.top_n, plan.table(obj), plan.table(reg), ori_sizes, mesh, score_thresh, min_size,
+    lib().call("nmh_rpn_post_select", plan.L, plan.dims, plan.base, plan.N, ncols, post.top_n, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), ori_sizes, mesh, score_thresh, min_size,
                pre_keys, pre_boxes, pre_scores, pre_index, pre_counts, _st())
     return pre_keys, pre_boxes, pre_scores, pre_index, pre_counts
 
@@ -1910,10 +1902,6 @@ def _head_args(name, ts, w_cls, w_box, C):
         raise ValueError(f"{name} takes 1 to {RPN_MAX_ANCHORS} anchors per location, got {A}")
     vox = (ctypes.c_int * len(ts))(*[t.shape[1] * t.shape[2] * t.shape[3] for t in ts])
     return vox, N, Cin, A
-
-
-def _ptr_table(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
 def rpn_head_out_fwd(ts, w_cls, w_box, b_cls, b_box, C, relu):
@@ -2019,9 +2007,6 @@ class RoiPoolPlan:
         self.out = tuple(int(v) for v in output_size)
         self.enlarge = float(enlarge)
 
-    def table(self, tensors):
-        return (ctypes.c_void_p * self.L)(*[None if t is None else t.data_ptr() for t in tensors])
-
 
 def roi_pool_fwd(plan, maps, rois, level_override):
     """rois [N,R,1+6|7] -> (out [N*R,C,ow,oh,od], argmax int32 of the same shape)"""
@@ -2029,7 +2014,7 @@ def roi_pool_fwd(plan, maps, rois, level_override):
     R = rois.shape[1]
     out = torch.empty((plan.N * R, plan.C, *plan.out), dtype=torch.float32, device=rois.device)
     arg = torch.empty(out.shape, dtype=torch.int32, device=rois.device)
-    lib().call("nmh_roi_pool_fwd", plan.L, plan.dims, plan.scales, plan.N, plan.C, R, plan.ncols, *plan.out, plan.enlarge, plan.table(maps), rois, level_override, out, arg, _st())
+    lib().call("nmh_roi_pool_fwd", plan.L, plan.dims, plan.scales, plan.N, plan.C, R, plan.ncols, *plan.out, plan.enlarge, _ptr_table(maps, plan.L), rois, level_override, out, arg, _st())
     return out, arg
 
 
@@ -2037,7 +2022,7 @@ def roi_pool_bwd(plan, dout, arg, rois, level_override, need):
     """-> per level the gradient of the map (zeroed here, then accumulated with fp32 atomics), None where need[k] is False"""
     dmaps = [torch.zeros(s, dtype=torch.float32, device=dout.device) if n else None for s, n in zip(plan.shapes, need)]
     lib().call("nmh_roi_pool_bwd", plan.L, plan.dims, plan.scales, plan.N, plan.C, rois.shape[1], plan.ncols, *plan.out, plan.enlarge, dout, arg, rois, level_override,
-               plan.table(dmaps), _st())
+               _ptr_table(dmaps, plan.L), _st())
     return dmaps
 
 
@@ -2107,10 +2092,6 @@ FCOS_HEAD_MAX_JOBS = 2 * FCOS_HEAD_MAX_LEVELS
 FCOS_HEAD_MODES = {"train": 0, "eval": 1, "exp": 2}
 
 
-def _ptr_table_opt(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
-
-
 def _gn_args(name, xs, towers, G, others=()):
     """xs: the channels-last tensors (N,W,L,H,C) of up to 10 (level, tower) jobs; towers: 0 | 1 per job -> (vox, tower table, N, C)"""
     if not 1 <= len(xs) <= FCOS_HEAD_MAX_JOBS:
@@ -2156,7 +2137,7 @@ def fcos_gn_apply(xs, towers, stats, gammas, betas, G):
         if gammas[t] is None or betas[t] is None or gammas[t].dtype != torch.float32 or betas[t].dtype != torch.float32 or gammas[t].numel() != C or betas[t].numel() != C:
             raise ValueError(f"fcos_gn_apply: tower {t} needs fp32 gamma and beta of {C} elements")
     ys = [torch.empty_like(x) for x in xs]
-    lib().call("nmh_fcos_gn_apply", dt_of(xs[0]), len(xs), vox, tw, N, C, G, _ptr_table(xs), stats, _ptr_table_opt(gammas), _ptr_table_opt(betas), _ptr_table(ys), _st())
+    lib().call("nmh_fcos_gn_apply", dt_of(xs[0]), len(xs), vox, tw, N, C, G, _ptr_table(xs), stats, _ptr_table(gammas), _ptr_table(betas), _ptr_table(ys), _st())
     return ys
 
 
@@ -2174,8 +2155,8 @@ def fcos_gn_bwd(dys, xs, ys, towers, stats, gammas, dgammas, dbetas, G):
     dev = xs[0].device
     sums = torch.empty((len(xs), N, G, 2), dtype=torch.float32, device=dev)
     dxs = [torch.empty_like(x) for x in xs]
-    lib().call("nmh_fcos_gn_bwd", dt_of(xs[0]), len(xs), vox, tw, N, C, G, _ptr_table(dys), _ptr_table(xs), _ptr_table(ys), stats, _ptr_table_opt(gammas),
-               _gn_ws(vox, len(xs), N, C, dev), sums, _ptr_table_opt(dgammas), _ptr_table_opt(dbetas), _ptr_table(dxs), _st())
+    lib().call("nmh_fcos_gn_bwd", dt_of(xs[0]), len(xs), vox, tw, N, C, G, _ptr_table(dys), _ptr_table(xs), _ptr_table(ys), stats, _ptr_table(gammas),
+               _gn_ws(vox, len(xs), N, C, dev), sums, _ptr_table(dgammas), _ptr_table(dbetas), _ptr_table(dxs), _st())
     return dxs
 
 

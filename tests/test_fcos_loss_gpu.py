@@ -23,7 +23,13 @@ from tests._metrics import assert_close  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 ONE = dict(sizes=((1, 1, 1),), strides=(4,))
-LOSS_CASES = [(False, t, False) for t in ("iou", "linear_iou", "giou")] + [(True, t, l1) for t in ("iou", "linear_iou", "giou", "diou") for l1 in (False, True)]
+# Two scenes of 42^3 + 3^3 locations are 2 x (290 + 1) = 582 workgroups of every loss kernel, more than the 256 partial sums that the final pass takes in its
+# first round, so its strided loop runs.  The scene seed is the first whose decisions all have their margin (asserted in ref_assign) and which has
+# positives in both scenes and on both levels.
+WIDE = dict(sizes=((42, 42, 42), (3, 3, 3)), strides=(4, 56), orig=((168, 168, 168), (150, 168, 121)), nbox=(12, 5), seed=1)
+LOSS_CASES = [(False, t, False, False) for t in ("iou", "linear_iou", "giou")] + [(True, t, l1, False) for t in ("iou", "linear_iou", "giou", "diou") for l1 in (False, True)]
+LOSS_CASES.append((True, "giou", True, True))
+LOSS_IDS = [f"{o}-{t}-{l1}" + ("-above-256-partials" if wide else "") for o, t, l1, wide in LOSS_CASES]
 
 
 def _m():
@@ -41,32 +47,50 @@ def scene(use_obb, small):
 
 
 @functools.lru_cache(maxsize=None)
+def wide_scene(use_obb):
+    return tuple(F.make_scene(WIDE["seed"], use_obb, nbox=WIDE["nbox"], extent=WIDE["orig"][0]))
+
+
+@functools.lru_cache(maxsize=None)
+def wide_assign(use_obb):
+    """center sampling 1.5, normalised targets"""
+    a = F.assign(list(wide_scene(use_obb)), 1.5, True, WIDE["sizes"], WIDE["strides"], WIDE["orig"])
+    n0, pos = 42 ** 3, a["valid"] & (a["labels"] > 0)
+    assert min(F.decision_margins(a).values()) >= 1e-3 and pos[:n0].any() and pos[n0:2 * n0].any() and pos[2 * n0:].any()
+    return a
+
+
+@functools.lru_cache(maxsize=None)
 def ref_assign(use_obb, radius, norm, small):
     if small:
         return F.assign(list(scene(use_obb, True)), radius, norm, **ONE)
     return F.assign(list(scene(use_obb, False)), radius, norm, orig=F.ORIG)
 
 
+def _heads(use_obb, norm, wide):
+    return F.make_heads(F.HEAD_SEED, use_obb, norm, len(WIDE["nbox"]), WIDE["sizes"], WIDE["strides"]) if wide else F.make_heads(F.HEAD_SEED, use_obb, norm)
+
+
 @functools.lru_cache(maxsize=None)
-def ref_losses(use_obb, loss_type, add_l1):
+def ref_losses(use_obb, loss_type, add_l1, wide=False):
     """float64 losses and the gradients of (1.0 cls + 0.7 reg + 1.3 ctr) in the dense layout; center sampling 1.5, normalised targets"""
-    a = ref_assign(use_obb, 1.5, True, False)
-    heads = [[t.double().requires_grad_(True) for t in ts] for ts in F.make_heads(F.HEAD_SEED, use_obb, True)]
+    a = wide_assign(use_obb) if wide else ref_assign(use_obb, 1.5, True, False)
+    heads = [[t.double().requires_grad_(True) for t in ts] for ts in _heads(use_obb, True, wide)]
     out = F.losses(*heads, a, loss_type, add_l1)
     (out[0] + 0.7 * out[1] + 1.3 * out[2]).backward()
     return [o.detach() for o in out], F.flatten_heads(*[[t.grad for t in ts] for ts in heads])
 
 
-def _sizes_dev():
-    return torch.tensor(F.ORIG, dtype=torch.int32).cuda()
+def _sizes_dev(wide=False):
+    return torch.tensor(WIDE["orig"] if wide else F.ORIG, dtype=torch.int32).cuda()
 
 
-def _gpu_heads(use_obb, norm=True):
-    return [[t.cuda().requires_grad_(True) for t in ts] for ts in F.make_heads(F.HEAD_SEED, use_obb, norm)]
+def _gpu_heads(use_obb, norm=True, wide=False):
+    return [[t.cuda().requires_grad_(True) for t in ts] for ts in _heads(use_obb, norm, wide)]
 
 
-def _run(M, use_obb, loss_type, add_l1, heads, boxes, weights=(1.0, 0.7, 1.3), **kw):
-    fn = M.FCOSLossComputation(list(F.STRIDES), 1.5, loss_type, True, 1, use_obb, add_l1)
+def _run(M, use_obb, loss_type, add_l1, heads, boxes, weights=(1.0, 0.7, 1.3), strides=F.STRIDES, **kw):
+    fn = M.FCOSLossComputation(list(strides), 1.5, loss_type, True, 1, use_obb, add_l1)
     out = fn(None, heads[0], heads[1], heads[2], boxes, None, **kw)
     sum(w * o for w, o in zip(weights, out)).backward()
     return out
@@ -125,14 +149,15 @@ def test_encode_decode():
 
 
 # ---- 2. losses and gradients -------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("use_obb,loss_type,add_l1", LOSS_CASES, ids=lambda v: str(v))
-def test_losses_and_gradients_against_float64(use_obb, loss_type, add_l1):
+@pytest.mark.parametrize("use_obb,loss_type,add_l1,wide", LOSS_CASES, ids=LOSS_IDS)
+def test_losses_and_gradients_against_float64(use_obb, loss_type, add_l1, wide):
     M = _m()
-    want, wgrads = ref_losses(use_obb, loss_type, add_l1)
-    a = ref_assign(use_obb, 1.5, True, False)
-    heads = _gpu_heads(use_obb)
-    out = _run(M, use_obb, loss_type, add_l1, heads, [b.cuda() for b in scene(use_obb, False)], grid_sizes=_sizes_dev())
-    tag = f"{'obb' if use_obb else 'aabb'} {loss_type}{' +l1' if add_l1 else ''}"
+    want, wgrads = ref_losses(use_obb, loss_type, add_l1, wide)
+    a = wide_assign(use_obb) if wide else ref_assign(use_obb, 1.5, True, False)
+    boxes = wide_scene(use_obb) if wide else scene(use_obb, False)
+    heads = _gpu_heads(use_obb, wide=wide)
+    out = _run(M, use_obb, loss_type, add_l1, heads, [b.cuda() for b in boxes], strides=WIDE["strides"] if wide else F.STRIDES, grid_sizes=_sizes_dev(wide))
+    tag = f"{'obb' if use_obb else 'aabb'} {loss_type}{' +l1' if add_l1 else ''}{' wide' if wide else ''}"
     assert_close(torch.stack([o.detach() for o in out]).cpu(), torch.stack(want), 1e-3, f"{tag} losses")
     grads = F.flatten_heads(*[[t.grad.cpu() for t in ts] for ts in heads])
     for name, g, wgt in zip(("d box_cls", "d box_regression", "d centerness"), grads, wgrads):

@@ -372,12 +372,23 @@ def test_oriented_remap_pooling_and_the_model_around_it():
 
 
 # ---- 4. losses and decode ------------------------------------------------------------------------------------------------------------------
-def _loss_case(rotated, labels=None):
+# 2 scenes of 35000 rows are 274 workgroups of the loss kernel, more than the 256 partial sums that the final pass takes in its first round, so its strided
+# loop runs; a third of the rows are positive and one in 97 is ignored
+WIDE_ROWS = (2, 35000)
+
+
+def _wide_labels():
+    lab = torch.tensor([0.0, 1, 0, 2, 0, 0])[torch.arange(WIDE_ROWS[0] * WIDE_ROWS[1]) % 6]
+    lab[::97] = -1.0
+    return lab
+
+
+def _loss_case(rotated, labels=None, N=1, K=300):
     B, g = (7 if rotated else 6), torch.Generator().manual_seed(11)
-    rois, gts, _ = H.make_scene(21, rotated, N=1, K=300, G=4)
-    ex, gt = rois[0], gts[0][torch.arange(300) % 4]
-    scores, deltas = torch.randn((300, 3), generator=g) * 2, torch.randn((300, B), generator=g) * 0.3
-    lab = torch.tensor([0.0, 1, 2, -1, 0, 1])[torch.arange(300) % 6] if labels is None else labels
+    rois, gts, _ = H.make_scene(21, rotated, N=N, K=K, G=4)
+    ex, gt = torch.cat(rois), torch.cat([b[torch.arange(K) % 4] for b in gts])
+    scores, deltas = torch.randn((N * K, 3), generator=g) * 2, torch.randn((N * K, B), generator=g) * 0.3
+    lab = torch.tensor([0.0, 1, 2, -1, 0, 1])[torch.arange(N * K) % 6] if labels is None else labels
     return scores, deltas, lab, ex, gt
 
 
@@ -389,10 +400,11 @@ def _run_loss(M, case, weights=(1.0, 1.0)):
     return loss["loss_objectness"].detach(), loss["loss_rpn_box_reg"].detach(), targets, s.grad, d.grad
 
 
-@pytest.mark.parametrize("rotated", [False, True])
-def test_loss_forward_and_backward(rotated):
+@pytest.mark.parametrize("rotated,wide", [(False, False), (True, False), (True, True)], ids=["False", "True", "True-above-256-partials"])
+def test_loss_forward_and_backward(rotated, wide):
     M = _m()
-    case = _loss_case(rotated)
+    N, K = WIDE_ROWS if wide else (1, 300)
+    case = _loss_case(rotated, _wide_labels() if wide else None, N, K)
     r = H.loss(case[0], case[1], case[2], case[3][:, 1:], case[4], rotated)
     obj, reg, targets, gs, gd = _run_loss(M, case, (1.0, 0.5))
     assert_close(obj.reshape(1), r["obj"].reshape(1), 1e-3, "loss_objectness")
@@ -405,9 +417,9 @@ def test_loss_forward_and_backward(rotated):
     again = _run_loss(M, case, (1.0, 0.5))
     assert all(torch.equal(a, b) for a, b in zip(again, (obj, reg, targets, gs, gd))), "bit-identical across two runs"
     # no positive row: the box loss is 0 with zero gradient; no valid row: both
-    nopos = _run_loss(M, _loss_case(rotated, torch.tensor([0.0, -1.0]).repeat(150)))
+    nopos = _run_loss(M, _loss_case(rotated, torch.tensor([0.0, -1.0]).repeat(N * K // 2), N, K))
     assert nopos[1].item() == 0 and (nopos[4] == 0).all() and nopos[0].item() > 0
-    none = _run_loss(M, _loss_case(rotated, torch.full((300,), -1.0)))
+    none = _run_loss(M, _loss_case(rotated, torch.full((N * K,), -1.0), N, K))
     assert none[0].item() == 0 and none[1].item() == 0 and (none[3] == 0).all() and (none[4] == 0).all()
 
 

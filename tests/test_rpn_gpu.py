@@ -172,40 +172,76 @@ def test_sampler_is_uniform():
 
 
 # ---- 3. losses ---------------------------------------------------------------------------------------------------------------------------
+# The wide case: two scenes of 42^3 + 3^3 anchors (one cube per location: side 16 at stride 2, side 32 at stride 28) are 2 x (290 + 1) = 582 workgroups of
+# the loss kernel, more than the 256 partial sums that the final pass takes in its first round, so its strided loop runs.  40000 anchors per scene are
+# sampled, so that most workgroups contribute.  Integer boxes; the seed is the first whose decisions all have their margin and which gives both scenes a
+# positive anchor on the second level.
+WIDE = dict(mesh=(84, 84, 84), grids=((42, 42, 42), (3, 3, 3)), ori=((84, 84, 84), (70, 84, 60)), sizes=((16,), (32,)), ratios=(((1., 1., 1.),),) * 2, nbox=(4, 3),
+            seed=262, batch=40000)
+
+
 @functools.lru_cache(maxsize=None)
-def ref_losses(rotated):
-    """float64 losses and the gradients of (1.0 objectness + 0.7 box) of the g20 case for its recorded sampled set"""
-    _, a = case("g20", rotated)
-    g = np.load(os.path.join(ROOT, "tests", "golden", "g20_rpn_targets.npz"))
-    flags = torch.from_numpy(g[("o_" if rotated else "a_") + "flags"])
-    heads = [[t.double().requires_grad_(True) for t in ts] for ts in R.make_heads(R.HEAD_SEED, len(R.NBOX), 8 if rotated else 6)]
+def wide_case():
+    rng = np.random.default_rng(WIDE["seed"])
+    boxes = []
+    for k, ori in zip(WIDE["nbox"], WIDE["ori"]):
+        size = rng.integers(10, 34, (k, 3))
+        lo = (rng.uniform(0, 1, (k, 3)) * (np.asarray(ori) - size + 1)).astype(np.int64)
+        boxes.append(torch.from_numpy(np.concatenate([lo, lo + size], 1).astype(np.float32)))
+    a = R.assign(boxes, mesh=WIDE["mesh"], grids=WIDE["grids"], ori=WIDE["ori"], base=R.base_anchors(WIDE["sizes"], WIDE["ratios"]))
+    for k, v in R.decision_margins(a).items():
+        assert v >= 1e-3, ("wide", k, v)
+    assert ((a["labels"][:, 42 ** 3:] == 1).sum(1) > 0).all()
+    return boxes, a
+
+
+def _heads(rotated, wide):
+    if wide:
+        return R.make_heads(R.HEAD_SEED, len(WIDE["nbox"]), 6, grids=WIDE["grids"], A=[1, 1])
+    return R.make_heads(R.HEAD_SEED, len(R.NBOX), 8 if rotated else 6)
+
+
+@functools.lru_cache(maxsize=None)
+def ref_losses(rotated, wide=False):
+    """float64 losses and the gradients of (1.0 objectness + 0.7 box): of the g20 case for its recorded sampled set, or of the wide case (6 columns)"""
+    if wide:
+        a = wide_case()[1]
+        flags = R.make_flags(3, a["labels"], batch=WIDE["batch"])
+    else:
+        a = case("g20", rotated)[1]
+        g = np.load(os.path.join(ROOT, "tests", "golden", "g20_rpn_targets.npz"))
+        flags = torch.from_numpy(g[("o_" if rotated else "a_") + "flags"])
+    heads = [[t.double().requires_grad_(True) for t in ts] for ts in _heads(rotated, wide)]
     out = R.losses(*heads, flags, a["targets"])
     (out[0] + 0.7 * out[1]).backward()
     return flags, [o.detach() for o in out], [[t.grad for t in ts] for ts in heads]
 
 
-def _run(rotated, flags, heads):
-    boxes, _ = case("g20", rotated)
-    fn = _m().RPNLossComputation(_gen(), R.FG, R.BG, R.BATCH, R.FRACTION, rotated_bbox=rotated)
-    out = fn(R.MESH, heads[0], heads[1], [b.cuda() for b in boxes], torch.tensor(R.ORI, dtype=torch.int32).cuda(), sampled=None if flags is None else flags.cuda())
+def _run(rotated, flags, heads, wide=False):
+    boxes = wide_case()[0] if wide else case("g20", rotated)[0]
+    gen = _m().AnchorGenerator3D(WIDE["sizes"], WIDE["ratios"]) if wide else _gen()
+    fn = _m().RPNLossComputation(gen, R.FG, R.BG, R.BATCH, R.FRACTION, rotated_bbox=rotated)
+    ori = torch.tensor(WIDE["ori"] if wide else R.ORI, dtype=torch.int32).cuda()
+    out = fn(WIDE["mesh"] if wide else R.MESH, heads[0], heads[1], [b.cuda() for b in boxes], ori, sampled=None if flags is None else flags.cuda())
     (out["loss_objectness"] + 0.7 * out["loss_rpn_box_reg"]).backward()
     return out
 
 
-def _gpu_heads(rotated):
-    return [[t.cuda().requires_grad_(True) for t in ts] for ts in R.make_heads(R.HEAD_SEED, len(R.NBOX), 8 if rotated else 6)]
+def _gpu_heads(rotated, wide=False):
+    return [[t.cuda().requires_grad_(True) for t in ts] for ts in _heads(rotated, wide)]
 
 
-@pytest.mark.parametrize("rotated", (False, True), ids=("aabb", "obb"))
-def test_losses_and_gradients_against_float64(rotated):
-    flags, want, wgrads = ref_losses(rotated)
+@pytest.mark.parametrize("rotated,wide", ((False, False), (True, False), (False, True)), ids=("aabb", "obb", "aabb-above-256-partials"))
+def test_losses_and_gradients_against_float64(rotated, wide):
+    flags, want, wgrads = ref_losses(rotated, wide)
     C = 8 if rotated else 6
-    heads = _gpu_heads(rotated)
-    out = _run(rotated, flags, heads)
-    tag = "obb" if rotated else "aabb"
+    heads = _gpu_heads(rotated, wide)
+    out = _run(rotated, flags, heads, wide)
+    tag = ("obb" if rotated else "aabb") + (" wide" if wide else "")
     assert_close(torch.stack([out["loss_objectness"], out["loss_rpn_box_reg"]]).detach().cpu(), torch.stack(want), 1e-3, f"{tag} losses")
-    g = np.load(os.path.join(ROOT, "tests", "golden", "g20_rpn_targets.npz"))
-    assert_close(torch.stack([out["loss_objectness"], out["loss_rpn_box_reg"]]).detach().cpu(), torch.from_numpy(g[("o_" if rotated else "a_") + "losses"]), 1e-3, f"g20 {tag} losses")
+    if not wide:
+        g = np.load(os.path.join(ROOT, "tests", "golden", "g20_rpn_targets.npz"))
+        assert_close(torch.stack([out["loss_objectness"], out["loss_rpn_box_reg"]]).detach().cpu(), torch.from_numpy(g[("o_" if rotated else "a_") + "losses"]), 1e-3, f"g20 {tag} losses")
     assert out["loss_rpn_box_reg_2d"].item() == 0 and not out["loss_rpn_box_reg_2d"].requires_grad
     for name, ts, ws in zip(("d objectness", "d pred_bbox_deltas"), heads, wgrads):
         for k, (t, w) in enumerate(zip(ts, ws)):
