@@ -340,6 +340,12 @@ NMH_API int nmh_mae_tail_bwd(int dt, const void* d0, const void* r, const void* 
  * rotation [transpose axes 0,1 then flip axis 0], 2 = flip axis 0, 4 = flip axis 1, applied in that order), zero padding at the high
  * end of each axis.  The valid extents of the result are (rot ? L : W, rot ? W : L, H). */
 NMH_API int nmh_grid_prepare(int src_u8, const void* src, int W, int L, int H, float* dst, int R, int flags, void* stream);
+/* Target side of the voxel-semantics input pipeline (nerf_rpn/datasets.py:150-167 hands the label volume to augment_rpn_inputs, whose two operations are
+ * :200-201 transpose + flip and :222 flip; padding torch_utils.py:56-90): one stored label volume (W,L,H) in device memory, dt 0 fp32, 1 int32, 2 int64, 3 uint8
+ * (the codes of nmh_sem_label_counts, plus uint8) -> the (R,R,R) fp32 slot of the (B,R,R,R) label batch that nmh_masked_ce_fwd and nmh_sem_eval read.
+ * Value = (float)label (negative ones as they are: the loss takes label <= 0 as unlabelled); flags 1 / 2 / 4 with the meaning and order of nmh_grid_prepare, bit 8
+ * ignored; zero (= unlabelled) padding at the high end of each axis.  -2: a non-positive extent, an extent of the result above R, an unknown dt. */
+NMH_API int nmh_labels_prepare(int dt, const void* src, int W, int L, int H, float* dst, int R, int flags, void* stream);
 /* Detection input pipeline (nerf_rpn/datasets.py:173-244, 478-524).  nmh_grid_prepare_rs: nmh_grid_prepare followed, before the padding, by
  * rotate_and_scale_scene's resample of the augmented grid (extents r0,r1,r2 = rot ? L : W, rot ? W : L, H; angle in radians): output voxel (i,j,k) inside
  * the extents is the trilinear blend (align_corners=True, taps outside [0,r) contribute 0) of the augmented grid at

@@ -7,7 +7,7 @@ fallback and importing the model without the built library fails loudly."""
 __version__ = "0.1.0"
 
 _DET_EVAL = ("det_eval_dense", "DetectionEvaluator", "evaluate_box_proposals_recall", "evaluate_box_proposals_ap")
-_SEM_EVAL = ("SemanticEvaluator", "sem_eval_dense", "intersection_and_union")
+_SEM_EVAL = ("SemanticEvaluator", "sem_eval_dense", "intersection_and_union", "label_class_counts", "class_weights_from_counts", "calculate_class_weights")
 _TWO_STAGE = ("TwoStageDetector", "roi_postprocess_dense", "filter_proposals")
 
 

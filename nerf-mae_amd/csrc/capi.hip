@@ -486,6 +486,11 @@ int nmh_grid_prepare(int src_u8, const void* src, int W, int L, int H, float* ds
   CLR();
   return k_grid_prepare(src_u8, src, W, L, H, dst, R, flags, ST);
 }
+int nmh_labels_prepare(int dt, const void* src, int W, int L, int H, float* dst, int R, int flags, void* stream) {
+  CLR();
+  REQ(src, dst);
+  return k_labels_prepare(dt, src, W, L, H, dst, R, flags, ST);
+}
 int nmh_grid_prepare_rs(int src_u8, const void* src, int W, int L, int H, float* dst, int R, int flags, float angle, float scale, void* stream) {
   CLR();
   REQ(src, dst);

@@ -411,6 +411,8 @@ int k_adamw(float* p, float* g, float* m, float* v, long n, const float* hyper /
 
 // raw scene (W,L,H,4) fp32|uint8 -> padded (4,R,R,R) fp32 network input; flags: 1 rotate (z-up 90 deg), 2 flip axis 0, 4 flip axis 1, 8 density->alpha
 int k_grid_prepare(int src_u8, const void* src, int W, int L, int H, float* dst, int R, int flags, hipStream_t st);
+// misc.hip: the label volume of the same scene, (W,L,H) fp32 / int32 / int64 / uint8 (dt 0..3) -> the (R,R,R) fp32 slot, rot / flips of k_grid_prepare
+int k_labels_prepare(int dt, const void* src, int W, int L, int H, float* dst, int R, int flags, hipStream_t st);
 // det_input.hip: k_grid_prepare with rotate_and_scale_scene's trilinear resample (angle in radians, scale) applied after rot / flips; extents >= 2
 int k_grid_prepare_rs(int src_u8, const void* src, int W, int L, int H, float* dst, int R, int flags, float angle, float scale, hipStream_t st);
 // boxes [total_rows, cols = 6 | 7] -> out; host tables itab [n_scenes][7] = first row, count, flags, has_rs, e0, e1, e2 and ftab [n_scenes][2] = angle, scale

@@ -760,22 +760,28 @@ int k_adamw(float* p, float* g, float* m, float* v, long n, const float* hyper, 
 //   zero padding at the high end of every axis up to R^3 (torch_utils.py:56-90).  dst: (4, R, R, R) fp32 slot of the batch tensor.
 // Output voxel (i, j, k) of the (A0, A1, A2 = H) result reads source voxel (w, l, h = k): the last axis is never permuted, so both
 // the 16-byte (4-byte for uint8) source reads and the four plane writes are coalesced along k.
+// source voxel index (w * L + l) * H + k of output voxel (i, j, k), or -1 in the padding; shared by the scene and the label kernel
+__device__ __forceinline__ long prepare_src_voxel(int i, int j, int k, int W, int L, int H, bool rot, bool f0, bool f1) {
+  const int A0 = rot ? L : W, A1 = rot ? W : L;
+  if (i >= A0 || j >= A1 || k >= H) return -1;
+  // undo the flips (applied last), then the rotation: rotated[i][j] = x[j][A0-1-i]
+  const int ii = f0 ? A0 - 1 - i : i, jj = f1 ? A1 - 1 - j : j;
+  int w, l;
+  if (rot) { w = jj; l = A0 - 1 - ii; } else { w = ii; l = jj; }
+  return ((long)w * L + l) * H + k;
+}
 template <typename S>
 __global__ __launch_bounds__(256) void grid_prepare_kernel(const S* __restrict__ src, int W, int L, int H, float* __restrict__ dst, int R, int flags) {
   const bool rot = flags & 1, f0 = flags & 2, f1 = flags & 4, dens = flags & 8;
-  const int A0 = rot ? L : W, A1 = rot ? W : L;
   const long R3 = (long)R * R * R;
   for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < R3; o += (long)gridDim.x * 256) {
     const int k = (int)(o % R);
     const long t = o / R;
     const int j = (int)(t % R), i = (int)(t / R);
     float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-    if (i < A0 && j < A1 && k < H) {
-      // undo the flips (applied last), then the rotation: rotated[i][j] = x[j][A0-1-i]
-      int ii = f0 ? A0 - 1 - i : i, jj = f1 ? A1 - 1 - j : j;
-      int w, l;
-      if (rot) { w = jj; l = A0 - 1 - ii; } else { w = ii; l = jj; }
-      const long si = (((long)w * L + l) * H + k) * 4;
+    const long sv = prepare_src_voxel(i, j, k, W, L, H, rot, f0, f1);
+    if (sv >= 0) {
+      const long si = sv * 4;
       if constexpr (sizeof(S) == 1) {
         const uchar4 u = *reinterpret_cast<const uchar4*>(src + si);
         v0 = u.x * (1.0f / 255.0f); v1 = u.y * (1.0f / 255.0f); v2 = u.z * (1.0f / 255.0f); v3 = u.w * (1.0f / 255.0f);
@@ -795,6 +801,33 @@ int k_grid_prepare(int src_u8, const void* src, int W, int L, int H, float* dst,
   const unsigned nb = (unsigned)((R3 + 255) / 256 < 8192 ? (R3 + 255) / 256 : 8192);
   if (src_u8) hipLaunchKernelGGL(grid_prepare_kernel<unsigned char>, dim3(nb), dim3(256), 0, st, (const unsigned char*)src, W, L, H, dst, R, flags);
   else hipLaunchKernelGGL(grid_prepare_kernel<float>, dim3(nb), dim3(256), 0, st, (const float*)src, W, L, H, dst, R, flags);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
+// label volume of a scene: (W, L, H) class ids, fp32 / int32 / int64 / uint8 -> the (R, R, R) fp32 slot of the label batch, value = (float)label, under
+// the rotation and flips of grid_prepare_kernel (bits 1 / 2 / 4 of flags; bit 8 means nothing here) and with zero = unlabelled padding.  A pure gather,
+// reads and writes coalesced along k.
+template <typename S>
+__global__ __launch_bounds__(256) void labels_prepare_kernel(const S* __restrict__ src, int W, int L, int H, float* __restrict__ dst, int R, int flags) {
+  const bool rot = flags & 1, f0 = flags & 2, f1 = flags & 4;
+  const long R3 = (long)R * R * R;
+  for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < R3; o += (long)gridDim.x * 256) {
+    const int k = (int)(o % R);
+    const long t = o / R;
+    const int j = (int)(t % R), i = (int)(t / R);
+    const long sv = prepare_src_voxel(i, j, k, W, L, H, rot, f0, f1);
+    dst[o] = sv >= 0 ? (float)src[sv] : 0.f;
+  }
+}
+int k_labels_prepare(int dt, const void* src, int W, int L, int H, float* dst, int R, int flags, hipStream_t st) {
+  const bool rot = flags & 1;
+  if ((rot ? L : W) > R || (rot ? W : L) > R || H > R || W <= 0 || L <= 0 || H <= 0 || dt < 0 || dt > 3) return -2;
+  const long R3 = (long)R * R * R;
+  const unsigned nb = (unsigned)((R3 + 255) / 256 < 8192 ? (R3 + 255) / 256 : 8192);
+  if (dt == 0) hipLaunchKernelGGL(labels_prepare_kernel<float>, dim3(nb), dim3(256), 0, st, (const float*)src, W, L, H, dst, R, flags);
+  else if (dt == 1) hipLaunchKernelGGL(labels_prepare_kernel<int>, dim3(nb), dim3(256), 0, st, (const int*)src, W, L, H, dst, R, flags);
+  else if (dt == 2) hipLaunchKernelGGL(labels_prepare_kernel<long long>, dim3(nb), dim3(256), 0, st, (const long long*)src, W, L, H, dst, R, flags);
+  else hipLaunchKernelGGL(labels_prepare_kernel<unsigned char>, dim3(nb), dim3(256), 0, st, (const unsigned char*)src, W, L, H, dst, R, flags);
   NMH_CHECK_LAUNCH();
   return 0;
 }

@@ -147,16 +147,17 @@ class GridBatcher:
             cls._pool = ThreadPoolExecutor(max_workers=int(os.environ.get("NMH_STAGE_THREADS", "8")), thread_name_prefix="nmh-stage")
         return cls._pool
 
-    def _stage_begin(self, slot: int, scene: Scene):
+    def _stage_begin(self, slot: int, scene: Scene, slots=None):
         """-> (host tensor, ring index, pinned buffer, device buffer, host-copy futures); a scene that is already on the device comes back as
         (scene, None, None, None, [])"""
         if isinstance(scene, torch.Tensor) and scene.is_cuda:
             return scene.contiguous(), None, None, None, []
         t = torch.from_numpy(scene) if isinstance(scene, np.ndarray) else scene
         t = t.contiguous()
-        sl = self._slots.get(slot)
+        slots = self._slots if slots is None else slots     # (a subclass stages a second tensor per sample through rings of its own)
+        sl = slots.get(slot)
         if sl is None:
-            sl = self._slots[slot] = _PinnedSlot(self.depth, self.device)
+            sl = slots[slot] = _PinnedSlot(self.depth, self.device)
         k, pin, dev = sl.acquire(t.numel(), t.dtype)
         futs = []
         if not t.is_pinned():
@@ -280,6 +281,94 @@ class DetectionBatcher(GridBatcher):
         if k is not None:
             self._box_ring.release_after(k, st)
         return xb, ext, [outb[t[0]:t[0] + t[1]] for t in table]
+
+
+_LABEL_DTYPES = (torch.uint8, torch.int32, torch.int64, torch.float32)
+
+
+class VoxelBatcher(GridBatcher):
+    """Input of the two voxel heads: stored scenes and their stored targets -> `(xb (B,4,R,R,R) fp32, extents, tb)` with ONE augmentation draw per scene applied
+    to both halves.  target="labels": a label volume (W,L,H) or (1,W,L,H) per scene, uint8 / int32 / int64 / float32, of the scene's own extents, through
+    `ops.labels_prepare` -> tb (B,R,R,R) fp32, what the semantics head's loss and `SemanticEvaluator` take.  target="grid": a stored high-resolution scene
+    (W',L',H',4) uint8 / float32 through `ops.grid_prepare` at `target_resolution` -> tb (B,4,Ro,Ro,Ro) fp32, the super-resolution head's target
+    (`normalize_density` applies to float targets as to float inputs).  Targets go through pinned rings of their own under the event discipline of the scenes';
+    pinned and device-resident targets are read in place.  Nothing synchronises.
+
+    NOT the reference's behaviour for flip_prob / rotate_prob > 0: there the target takes the place of `boxes` in augment_rpn_inputs (datasets.py:150-167), whose
+    assertion (:193-196) rejects it, so the reference's voxel runs work with all probabilities 0 only -- the default here.  With probabilities > 0 the draw
+    of `draw_augmentation` (the reference's draw order with boxes=None) is applied to input and target alike."""
+
+    def __init__(self, resolution: int, device, target: str = "labels", target_resolution: Optional[int] = None, normalize_density: bool = True,
+                 flip_prob: float = 0.0, rotate_prob: float = 0.0, depth: int = 3):
+        if target not in ("labels", "grid"):
+            raise ValueError(f"VoxelBatcher: target must be 'labels' or 'grid', got {target!r}")
+        super().__init__(resolution, device, normalize_density, flip_prob, rotate_prob, depth)
+        self.target = target
+        self.Ro = int(target_resolution) if (target == "grid" and target_resolution is not None) else resolution
+        self._target_slots = {}
+
+    def draw_flags(self, n: int, rng=_random) -> List[int]:
+        """the flags of n successive scenes: one `draw_augmentation` each, in scene order"""
+        return [draw_augmentation(self.flip_prob, self.rotate_prob, rng) for _ in range(n)]
+
+    def _target_tensor(self, tgt, scene):
+        t = torch.from_numpy(tgt) if isinstance(tgt, np.ndarray) else tgt
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("VoxelBatcher: a target must be a numpy array or a torch tensor")
+        if self.target == "grid":
+            if t.dim() != 4 or t.shape[3] != 4 or t.dtype not in (torch.uint8, torch.float32):
+                raise ValueError(f"VoxelBatcher: a grid target must be (W,L,H,4) uint8 or float32, got {tuple(t.shape)} {t.dtype}")
+            return t
+        if t.dtype not in _LABEL_DTYPES:
+            raise ValueError(f"VoxelBatcher: a label volume must be uint8, int32, int64 or float32, got {t.dtype}")
+        if t.dim() == 4 and t.shape[0] == 1:
+            t = t[0]
+        if t.dim() != 3 or tuple(t.shape) != tuple(scene.shape[:3]):
+            raise ValueError(f"VoxelBatcher: a label volume must have its scene's extents {tuple(scene.shape[:3])} (or 1 in front of them), got {tuple(tgt.shape)}")
+        return t
+
+    def __call__(self, scenes: List[Scene], targets, flags: Optional[List[int]] = None, out: Optional[torch.Tensor] = None,
+                 target_out: Optional[torch.Tensor] = None, rng=_random):
+        xb, ext, tb = self.prepare(scenes, targets, flags, out, target_out, rng)
+        return xb, torch.tensor(ext, dtype=torch.int32).to(self.device, non_blocking=True), tb
+
+    def prepare(self, scenes: List[Scene], targets, flags: Optional[List[int]] = None, out: Optional[torch.Tensor] = None,
+                target_out: Optional[torch.Tensor] = None, rng=_random):
+        """targets: one per scene (see the class); flags: one per scene, None: drawn here from `rng`, scene by scene -> (xb, extents as a host list, tb)"""
+        B, R, Ro = len(scenes), self.R, self.Ro
+        if len(targets) != B:
+            raise ValueError("VoxelBatcher: one target per scene")
+        if flags is None:
+            flags = self.draw_flags(B, rng)
+        tgts = [self._target_tensor(t, scenes[i]) for i, t in enumerate(targets)]
+        for i in range(B):                                   # (a rotation swaps two extents: the largest decides either way)
+            if max(scenes[i].shape[:3]) > R:
+                raise ValueError(f"VoxelBatcher: scene {i} of extents {tuple(scenes[i].shape[:3])} does not fit the resolution {R}")
+            if self.target == "grid" and max(tgts[i].shape[:3]) > Ro:
+                raise ValueError(f"VoxelBatcher: target {i} of extents {tuple(tgts[i].shape[:3])} does not fit the target resolution {Ro}")
+        tshape = (B, R, R, R) if self.target == "labels" else (B, 4, Ro, Ro, Ro)
+        xb = out if out is not None else torch.empty((B, 4, R, R, R), dtype=torch.float32, device=self.device)
+        tb = target_out if target_out is not None else torch.empty(tshape, dtype=torch.float32, device=self.device)
+        if tuple(tb.shape) != tshape or tb.dtype != torch.float32 or not tb.is_contiguous():
+            raise ValueError(f"VoxelBatcher: target_out must be a contiguous float32 {tshape}")
+        st = torch.cuda.current_stream()
+        staged = [self._stage_begin(i, sc) for i, sc in enumerate(scenes)]     # all host copies of the batch in flight at once, both halves
+        staged_t = [self._stage_begin(i, t, self._target_slots) for i, t in enumerate(tgts)]
+        ext = []
+        for i in range(B):
+            f = int(flags[i]) & (ops.GRID_ROT | ops.GRID_FLIP0 | ops.GRID_FLIP1)
+            src, k = self._stage_end(*staged[i]), staged[i][1]
+            ext.append(list(ops.grid_prepare(src, xb[i], R, f | ops.GRID_DENSITY if self.normalize_density and src.dtype == torch.float32 else f)))
+            if k is not None:
+                self._slots[i].release_after(k, st)
+            tsrc, k = self._stage_end(*staged_t[i]), staged_t[i][1]
+            if self.target == "labels":
+                ops.labels_prepare(tsrc, tb[i], R, f)
+            else:
+                ops.grid_prepare(tsrc, tb[i], Ro, f | ops.GRID_DENSITY if self.normalize_density and tsrc.dtype == torch.float32 else f)
+            if k is not None:
+                self._target_slots[i].release_after(k, st)
+        return xb, ext, tb
 
 
 def pin_scene(scene: np.ndarray) -> torch.Tensor:

@@ -231,6 +231,14 @@ class _VoxelHeadBase(nn.Module):
         dec0 = self.decoder1(d, enc1.view(B, R, R, R, -1))
         return dec0.reshape(B * R ** 3, -1), B
 
+    @staticmethod
+    def _dense_target(x, shape, device, what):
+        """a batcher's dense target (data.VoxelBatcher) is used as it is -- no transform, no zero fill, no copy -- after this check"""
+        if tuple(x.shape) != tuple(shape) or x.dtype != torch.float32 or x.device != device or not x.is_contiguous():
+            raise ValueError(f"{what}: a dense target must be a contiguous float32 tensor {tuple(shape)} on {device}, got {x.dtype} {tuple(x.shape)} on {x.device}"
+                             f"{'' if x.is_contiguous() else ', not contiguous'} (or pass the list of per-scene grids)")
+        return x
+
     def transform(self, x, resolution=160):
         """pad_tensor semantics (torch_utils.py:56-90): list of (C,W,L,H) -> (B,C,res,res,res) fp32 on the device, zero padded"""
         dev = self.base.pos_embed.device
@@ -243,7 +251,8 @@ class _VoxelHeadBase(nn.Module):
 
 class SwinTransformer_VoxelSR_Pretrained_Skip(_VoxelHeadBase):
     """feature_extractor.py:1898-2244.  forward(list of (4,W,L,H) grids) -> pred (B,4,out_res^3); loss_fn(list of grids at the output
-    resolution, pred) -> masked RGB MSE."""
+    resolution, pred) -> masked RGB MSE.  In place of the list, loss_fn / forward_loss / output_metrics take the dense (B,4,out_res^3) fp32 device tensor of
+    data.VoxelBatcher(target="grid") as it is."""
 
     def __init__(self, expand_dim: bool = True, out_channels: int = 256, resolution=160, out_resolution=256, decoder_embed_dim: int = 768,
                  checkpoint_path=None, is_eval=False, patch_size=[4, 4, 4], compute_dtype: torch.dtype = torch.bfloat16):
@@ -264,8 +273,14 @@ class SwinTransformer_VoxelSR_Pretrained_Skip(_VoxelHeadBase):
         inv = float(torch.tensor(1.0 / scale, dtype=torch.float32))
         return _HeadFn.apply(d0, self, self.voxel_out.conv, B, R, Ro, inv)
 
+    def _target(self, x, pred):
+        """x: the list of (4,W,L,H) grids at the output resolution, or the dense (B,4,Ro,Ro,Ro) fp32 device tensor of data.VoxelBatcher(target="grid")"""
+        if isinstance(x, Tensor):
+            return self._dense_target(x, pred.shape, pred.device, type(self).__name__)
+        return self.transform(x, resolution=pred.shape[2])
+
     def forward_loss(self, x, pred, is_eval=False):
-        return _SRLossFn.apply(pred, self.transform(x, resolution=pred.shape[2]))
+        return _SRLossFn.apply(pred, self._target(x, pred))
 
     def loss_fn(self, x, pred):
         return self.forward_loss(x, pred)
@@ -278,9 +293,40 @@ class SwinTransformer_VoxelSR_Pretrained_Skip(_VoxelHeadBase):
         return {"MSE": mse, "PSNR": -10.0 * math.log10(mse)}
 
 
+class SREvaluator:
+    """The super-resolution evaluation loop's bookkeeping (run_voxelSR.py:734-786) without a host wait per batch: `output_metrics` of the reference gives the
+    batch's MSE and PSNR, the loop averages the per-batch values.
+        ev = SREvaluator(head)
+        for target, pred in batches: ev.update(target, pred)      # target: the list of grids or the dense tensor that loss_fn takes
+        ev.compute() -> {"psnr_mean", "mse_mean"}                   (floats; the one synchronisation)"""
+
+    def __init__(self, head: "SwinTransformer_VoxelSR_Pretrained_Skip"):
+        self.head, self.mse, self.psnr = head, [], []
+
+    def update(self, target, pred):
+        """appends the batch's MSE (the loss kernel's value / 3: it divides by the voxel count, the MSE by the entry count) and PSNR = -10 log10(MSE) as device
+        scalars and returns them"""
+        with torch.no_grad():
+            mse = self.head.forward_loss(target, pred.detach()) / 3.0
+            psnr = -10.0 * torch.log10(mse)
+        self.mse.append(mse)
+        self.psnr.append(psnr)
+        return mse, psnr
+
+    def compute(self):
+        if not self.mse:
+            raise RuntimeError("SREvaluator.compute() before any update")
+        m, p = torch.stack([torch.stack(self.mse).mean(), torch.stack(self.psnr).mean()]).tolist()
+        return {"psnr_mean": p, "mse_mean": m}
+
+    def reset(self):
+        self.mse, self.psnr = [], []
+
+
 class SwinTransformer_VoxelSemantics_Pretrained_Skip(_VoxelHeadBase):
     """feature_extractor.py:2521-2848.  forward(list of (4,W,L,H) grids) -> class logits (B,K,res^3); loss_fn(list of (1,W,L,H) label grids,
-    pred) -> (loss, sem_ce_loss, mean soft IoU); output_metrics(label grids, pred) -> the evaluation loop's per-batch counts (sem_eval.py)."""
+    pred) -> (loss, sem_ce_loss, mean soft IoU); output_metrics(label grids, pred) -> the evaluation loop's per-batch counts (sem_eval.py).  In place of the list, all three take the dense
+    (B,res^3) fp32 device tensor of data.VoxelBatcher(target="labels") as it is."""
 
     def __init__(self, expand_dim: bool = True, out_channels: int = 19, resolution=160, decoder_embed_dim: int = 768, checkpoint_path=None,
                  is_eval=False, patch_size=[4, 4, 4], class_weights: Optional[Tensor] = None, compute_dtype: torch.dtype = torch.bfloat16):
@@ -299,8 +345,15 @@ class SwinTransformer_VoxelSemantics_Pretrained_Skip(_VoxelHeadBase):
         R = self.input_resolution
         return _HeadFn.apply(d0, self, self.sem_out.conv, B, R, R, 1.0)
 
+    def _labels(self, x, pred):
+        """x: the list of (1,W,L,H) label grids, or the dense (B,R,R,R) fp32 device tensor of data.VoxelBatcher(target="labels")"""
+        if isinstance(x, Tensor):
+            R = self.input_resolution
+            return self._dense_target(x, (pred.shape[0], R, R, R), pred.device, type(self).__name__)
+        return self.transform(x, resolution=self.input_resolution)[:, 0]
+
     def forward_loss(self, x, pred, is_eval=False):
-        labels = self.transform(x, resolution=self.input_resolution)[:, 0].contiguous()
+        labels = self._labels(x, pred).contiguous()
         cw = None if self.class_weights is None else self.class_weights.to(device=pred.device, dtype=torch.float32)
         loss, out = _CELossFn.apply(pred, labels, cw)
         return loss, loss, out[1]
@@ -315,6 +368,6 @@ class SwinTransformer_VoxelSemantics_Pretrained_Skip(_VoxelHeadBase):
         from .sem_eval import sem_eval_dense
         if not pred.is_cuda:
             raise RuntimeError("the voxel heads (HIP) need their tensors on a HIP device (no CPU fallback)")
-        labels = self.transform(x, resolution=self.input_resolution)[:, 0]
+        labels = self._labels(x, pred)
         with torch.no_grad():
             return sem_eval_dense(pred, labels, self.class_weights)

@@ -1160,6 +1160,25 @@ def grid_prepare(src, dst, R, flags=0):
     return (L, W, H) if flags & GRID_ROT else (W, L, H)
 
 
+LABEL_PREPARE_DT = {torch.float32: 0, torch.int32: 1, torch.int64: 2, torch.uint8: 3}
+
+
+def labels_prepare(src, dst, R, flags=0):
+    """src: one stored label volume (W,L,H) fp32|int32|int64|uint8 on the device; dst: the (R,R,R) fp32 slot of the label batch; rotation and flips as
+    grid_prepare (GRID_DENSITY means nothing here), zero = unlabelled padding; returns the valid extents"""
+    _chk(src, dst)
+    if src.dim() != 3 or src.dtype not in LABEL_PREPARE_DT:
+        raise ValueError(f"labels_prepare: src must be (W,L,H) uint8, int32, int64 or float32, got {tuple(src.shape)} {src.dtype}")
+    if dst.dtype != torch.float32 or dst.numel() != R ** 3:
+        raise ValueError("labels_prepare: dst must be the (R,R,R) float32 slot")
+    W, L, H = src.shape
+    ext = (L, W, H) if flags & GRID_ROT else (W, L, H)
+    if min(ext) < 1 or max(ext) > R:
+        raise ValueError(f"labels_prepare: the result's extents {ext} must lie in 1..{R}")
+    lib().call("nmh_labels_prepare", LABEL_PREPARE_DT[src.dtype], src, W, L, H, dst, R, flags, _st())
+    return ext
+
+
 def grid_prepare_rs(src, dst, R, flags=0, angle=0.0, scale=1.0):
     """grid_prepare with rotate_and_scale_scene's trilinear resample (nerf_rpn/datasets.py:478-512) of the augmented grid before the padding; returns
     the valid extents.  Always resamples: a scene that drew no rot-scale belongs in grid_prepare"""

@@ -31,7 +31,8 @@ import torch
 
 from . import ops
 
-__all__ = ["sem_eval_dense", "intersection_and_union", "pad_label_grids", "SemanticEvaluator"]
+__all__ = ["sem_eval_dense", "intersection_and_union", "pad_label_grids", "SemanticEvaluator", "label_class_counts", "class_weights_from_counts",
+           "calculate_class_weights"]
 
 
 def pad_label_grids(x, spatial, device):
@@ -119,3 +120,50 @@ class SemanticEvaluator:
     def reset(self):
         if self.totals is not None:
             self.totals.zero_()
+
+
+# ---- class weights of the training loss (nerf_rpn/model/metrics.py:383-426 calculate_class_weights) --------------------------------------------------------
+def label_class_counts(labels, num_classes: int):
+    """labels: a device tensor of class ids (any shape; fp32, int32, int64 or uint8) -> int64 [num_classes] on the device: entry c = #(label == c) for
+    c = 1..num_classes-1, entry 0 = 0 (unlabelled voxels are not counted, metrics.py:400, 414); a label >= num_classes enters no bin.  The target histogram of
+    nmh_sem_label_counts with output = target = labels: no atomics, fixed summation order, no host wait."""
+    if not labels.is_cuda:
+        raise RuntimeError("label_class_counts (HIP) needs a device tensor (no CPU fallback)")
+    if labels.dtype not in (torch.float32, torch.int32, torch.int64):
+        if labels.dtype != torch.uint8:
+            raise ValueError(f"label_class_counts: labels must be uint8, int32, int64 or float32, got {labels.dtype}")
+        labels = labels.to(torch.int32)
+    lab = labels.contiguous()
+    counts = torch.zeros(int(num_classes), dtype=torch.int64, device=labels.device)
+    counts[1:] = ops.sem_label_counts(lab, lab, num_classes)[2]
+    return counts
+
+
+def class_weights_from_counts(counts, c: float = 1.02) -> np.ndarray:
+    """w = 1 / log(c + counts / counts.sum()) with counts[0] taken as 0 and w[0] = 0 (metrics.py:414-426), float64 numpy; importable and usable without a GPU.
+    An all-zero histogram raises ValueError (the reference divides by zero)."""
+    n = np.array(counts, dtype=np.float64)
+    if n.ndim != 1 or n.size < 2:
+        raise ValueError("class_weights_from_counts: a histogram over at least two classes")
+    n[0] = 0
+    total = n.sum()
+    if not total > 0:
+        raise ValueError("class_weights_from_counts: no labelled voxel in the histogram")
+    w = 1 / np.log(c + n / total)
+    w[0] = 0
+    return w
+
+
+def calculate_class_weights(label_volumes, num_classes: int = 19, c: float = 1.02, device=None) -> np.ndarray:
+    """metrics.py:383-426 over an iterable of stored label volumes (numpy arrays or tensors, any shape): the histograms are taken on the device and summed
+    there, read back once -> float64 [num_classes] for `class_weights=` of the semantics head.  device: where host volumes are counted (default: the current one)"""
+    total = None
+    for v in label_volumes:
+        t = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v
+        if not t.is_cuda:
+            t = t.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
+        n = label_class_counts(t, num_classes)
+        total = n if total is None else total + n
+    if total is None:
+        raise ValueError("calculate_class_weights: no label volume")
+    return class_weights_from_counts(total.cpu().numpy(), c)

@@ -834,3 +834,180 @@ class DetectionTrainer:
             if self.rank == 0:
                 self.log(" ".join(f"{k}={v:.5g}" if isinstance(v, float) else f"{k}={v}" for k, v in rec.items()))
         return self.history
+
+
+# --------------------------------------------------------------------------------------------------
+# Voxel heads: the reference's checkpoint format and the epoch loops of run_voxelSR.py / run_voxel_semantics.py
+# --------------------------------------------------------------------------------------------------
+def save_voxel_checkpoint(path: str, model, epoch: int, train_args: dict, opt: "FusedAdamW" = None, step: int = None):
+    """the voxel runs' checkpoint (run_voxel_semantics.py:509-527, run_voxelSR.py:494-512): {"epoch", "state_dict", "train_args"} of a voxel head, keys and
+    shapes the reference's.  With `opt` (a FusedAdamW over a finetune.FlatParameters of this model) the file also carries the "resume" section of
+    save_checkpoint."""
+    model = getattr(model, "module", model)
+    ck = {"epoch": epoch, "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "train_args": _plain(dict(train_args))}
+    if opt is not None:
+        ck["resume"] = resume_section(opt.model, opt, step)
+    torch.save(ck, path)
+
+
+def load_voxel_checkpoint(path: str, model, opt: "FusedAdamW" = None) -> dict:
+    """loads a voxel-head checkpoint (also one written by the reference) strictly; returns the checkpoint dict.  With `opt` and a "resume" section the optimizer
+    continues where it stopped; a file without the section loads the weights only."""
+    model = getattr(model, "module", model)
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    model.load_state_dict(ck["state_dict"], strict=True)
+    if opt is not None and "resume" in ck:
+        restore_resume(ck["resume"], opt.model, opt, "load_voxel_checkpoint")
+    return ck
+
+
+class VoxelTrainer:
+    """Epoch loops of run_voxel_semantics.py:537-958 and run_voxelSR.py:600-790 without wandb, one process per GPU, for the two heads of heads.py: input from
+    data.VoxelBatcher (scene and target under one augmentation draw, the target never a host fp32 batch), AdamW over ALL parameters + clip by FusedAdamW over
+    finetune.FlatParameters, OneCycle sized by `num_epochs` (`schedule_epochs` overrides; the reference: total_steps = num_epochs * len(train_loader)) and stepped
+    every iteration, no drop_last.  The head decides the rest:
+
+      semantics   train_targets: one label volume per scene ((W,L,H) or (1,W,L,H), uint8 / int32 / int64 / float32).  History: train_loss, train_iou (the loss's
+                  mean soft IoU, its second output, outside the backward), and from SemanticEvaluator mIoU, mAcc, allAcc; best by mIoU.
+      SR          train_targets: one stored high-resolution scene (W',L',H',4) per scene, padded to int(R * final_upsample.scale_factor).  History: train_loss,
+                  and from heads.SREvaluator psnr, mse (the means of the per-batch values); best by psnr.
+
+    Evaluation every `eval_interval` epochs and at the last one, in model.eval() with flags 0; `model_best.pt` = {"epoch", "state_dict", "train_args"} plus the
+    resume section (save_voxel_checkpoint).  `resume(path)` continues a run from such a file.
+
+    Augmentation: flip_prob / rotate_prob > 0 apply ONE draw to scene and target, which the reference cannot do (see data.VoxelBatcher); rot_scale_prob is a
+    trilinear blend without meaning for labels and must be 0.
+
+    Data-parallel (rank, world, reducer) by the conventions of DetectionTrainer: `batch_size` per rank, dp_epoch_plan (equal step counts and batch sizes on
+    every rank), draws from random.Random(seed + 1000003 * rank), the epoch's logged losses in one all-reduce and one read-back, evaluation and files on rank 0
+    with one barrier per evaluated epoch; reducer None with world > 1 builds a dist.FlatGradReducer with fp32 buckets; rank 0's parameters are broadcast."""
+
+    def __init__(self, model, train_scenes, train_targets, val_scenes=None, val_targets=None, batch_size: int = 1, num_epochs: int = 1, lr: float = 5e-3,
+                 weight_decay: float = 0.01, clip_grad_norm: float = 0.1, eval_interval: int = 1, save_path: str = None, normalize_density: bool = True,
+                 flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = None, log=print,
+                 train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None):
+        import random
+        from . import data, dist as _dist
+        from .finetune import FinetuneStep, FlatParameters
+        from .heads import SwinTransformer_VoxelSemantics_Pretrained_Skip, SwinTransformer_VoxelSR_Pretrained_Skip
+        if isinstance(model, SwinTransformer_VoxelSemantics_Pretrained_Skip):
+            self.kind, self.best_key = "semantics", "mIoU"
+        elif isinstance(model, SwinTransformer_VoxelSR_Pretrained_Skip):
+            self.kind, self.best_key = "sr", "psnr"
+        else:
+            raise TypeError(f"VoxelTrainer: {type(model).__name__} is neither voxel head (SwinTransformer_VoxelSR_Pretrained_Skip, "
+                            "SwinTransformer_VoxelSemantics_Pretrained_Skip); the detectors train with DetectionTrainer")
+        if rot_scale_prob != 0:
+            raise ValueError("VoxelTrainer: rot_scale_prob must be 0: the small rotation + scaling is a trilinear blend, which has no meaning for a label volume")
+        if len(train_scenes) != len(train_targets) or (val_scenes is not None and len(val_scenes) != len(val_targets or [])):
+            raise ValueError("VoxelTrainer: one target per scene")
+        if len(train_scenes) < 1:
+            raise ValueError("VoxelTrainer: no training scene")
+        self.model, self.train_scenes, self.train_targets, self.val_scenes, self.val_targets = model, train_scenes, train_targets, val_scenes, val_targets
+        self.batch, self.epochs, self.eval_interval, self.save_path, self.log, self.seed = batch_size, num_epochs, eval_interval, save_path, log, seed
+        self.rank, self.world = rank, world
+        self.args = _plain(dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, batch_size=batch_size * world,
+                                num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
+                                rot_scale_prob=rot_scale_prob))
+        dev = next(model.parameters()).device
+        R = model.input_resolution
+        kw = dict(target="labels") if self.kind == "semantics" else dict(target="grid", target_resolution=int(R * float(model.final_upsample.scale_factor)))
+        self.batcher = data.VoxelBatcher(R, dev, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob, **kw)
+        self.val_batcher = data.VoxelBatcher(R, dev, normalize_density=normalize_density, **kw)
+        if reducer is not None:
+            if getattr(reducer.model, "module", None) is not model:
+                raise ValueError("VoxelTrainer: the reducer must be a dist.FlatGradReducer over a finetune.FlatParameters of this model")
+            self.flat = reducer.model
+        else:
+            self.flat = FlatParameters(model, dev)
+            if world > 1:
+                reducer = _dist.FlatGradReducer(self.flat)
+        self.reducer = reducer
+        if world > 1:
+            _dist.broadcast_flat_parameters(self.flat)   # DDP's initial broadcast: every rank starts from rank 0's weights
+        self.opt = FusedAdamW(self.flat, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
+        self.steps_per_epoch = len(dp_epoch_plan(len(train_scenes), batch_size, rank, world, 0, seed))   # len(train_loader) without drop_last, the same on every rank
+        self.sched = OneCycle(lr, (schedule_epochs or num_epochs) * self.steps_per_epoch)
+        self._aux = None                                     # the semantics loss's mean soft IoU of the step: logged, never part of the backward
+        self.step_fn = FinetuneStep(self.flat, self.opt, self._loss, reducer=reducer)
+        self._rng = random.Random(seed + 1000003 * rank)     # the augmentation draws: another sequence on every rank
+        self.global_step, self.start_epoch, self.best_metric, self.history = 0, 1, None, []
+
+    _load = staticmethod(DetectionTrainer._load)
+    _meshes = staticmethod(DetectionTrainer._meshes)
+
+    def _loss(self, meshes, tb):
+        out = self.model.loss_fn(tb, self.model(meshes))
+        if self.kind == "semantics":
+            self._aux = out[2].detach()
+            return {"loss": out[0]}
+        return {"loss": out}
+
+    def _target(self, t):
+        """a stored target by path: the scene file's `rgbsigma` for the SR head; label volumes are passed as arrays"""
+        return self._load(t) if self.kind == "sr" else t
+
+    def train_epoch(self, epoch: int):
+        self.model.train()
+        acc = None
+        for ids in dp_epoch_plan(len(self.train_scenes), self.batch, self.rank, self.world, epoch, self.seed):     # the DataLoader's shuffle, this rank's shard
+            xb, ext, tb = self.batcher.prepare([self._load(self.train_scenes[i]) for i in ids], [self._target(self.train_targets[i]) for i in ids], rng=self._rng)
+            lr, b1 = self.sched.at(self.global_step)
+            self.opt.set_hyper(lr=lr, beta1=b1)
+            losses = self.step_fn(self._meshes(xb, ext), tb)
+            self.global_step += 1
+            parts = torch.stack([losses["loss"], self._aux]) if self.kind == "semantics" else losses["loss"].reshape(1)
+            acc = parts if acc is None else acc + parts
+        if self.world > 1:
+            import torch.distributed as tdist
+            tdist.all_reduce(acc, op=tdist.ReduceOp.SUM)              # the epoch's one exchange of the logged losses: their mean over the ranks
+            acc = acc / self.world
+        vals = (acc / self.steps_per_epoch).tolist()                  # the epoch's one read-back
+        return dict(zip(("train_loss", "train_iou"), vals))
+
+    @torch.no_grad()
+    def evaluate(self):
+        from .heads import SREvaluator
+        from .sem_eval import SemanticEvaluator
+        self.model.eval()
+        ev = SemanticEvaluator(self.model.out_channels, self.model.class_weights) if self.kind == "semantics" else SREvaluator(self.model)
+        try:
+            for b in range(0, len(self.val_scenes), self.batch):
+                scenes = [self._load(s) for s in self.val_scenes[b:b + self.batch]]
+                xb, ext, tb = self.val_batcher.prepare(scenes, [self._target(t) for t in self.val_targets[b:b + self.batch]], flags=[0] * len(scenes))
+                ev.update(tb, self.model(self._meshes(xb, ext)))
+        finally:
+            self.model.train()
+        out = ev.compute()                                            # the evaluation's one synchronisation
+        if self.kind == "semantics":
+            return {k: float(out[k]) for k in ("mIoU", "mAcc", "allAcc")}
+        return {"psnr": float(out["psnr_mean"]), "mse": float(out["mse_mean"])}
+
+    def resume(self, path: str) -> dict:
+        """continue a run from a file of save_voxel_checkpoint: weights, optimizer state, schedule position; fit() then starts at the epoch after the file's"""
+        ck = load_voxel_checkpoint(path, self.model, self.opt)
+        self.flat.check()
+        self.start_epoch = int(ck["epoch"]) + 1
+        step = ck.get("resume", {}).get("step")
+        self.global_step = int(step) if step is not None else (self.start_epoch - 1) * self.steps_per_epoch
+        return ck
+
+    def fit(self):
+        import os
+        if self.save_path and self.rank == 0:
+            os.makedirs(self.save_path, exist_ok=True)
+        for epoch in range(self.start_epoch, self.epochs + 1):
+            rec = {"epoch": epoch, **self.train_epoch(epoch)}
+            evaluated = bool(self.val_scenes) and (epoch % self.eval_interval == 0 or epoch == self.epochs)    # the same decision on every rank
+            if evaluated and self.rank == 0:
+                rec.update(self.evaluate())
+                if self.save_path and (self.best_metric is None or rec[self.best_key] > self.best_metric):
+                    self.best_metric = rec[self.best_key]
+                    save_voxel_checkpoint(os.path.join(self.save_path, "model_best.pt"), self.model, epoch, self.args, self.opt, self.global_step)
+            if evaluated and self.world > 1:
+                import torch.distributed as tdist
+                tdist.barrier()        # the other ranks wait here for rank 0's evaluation and file, once per evaluated epoch
+            self.history.append(rec)
+            if self.rank == 0:
+                self.log(" ".join(f"{k}={v:.5g}" if isinstance(v, float) else f"{k}={v}" for k, v in rec.items()))
+        return self.history
