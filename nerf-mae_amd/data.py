@@ -26,13 +26,17 @@ def load_scene(path: str) -> np.ndarray:
         return np.ascontiguousarray(f["rgbsigma"])
 
 
-def draw_augmentation(flip_prob: float, rotate_prob: float, rng=_random) -> int:
-    """flags for `ops.grid_prepare`, drawn in the reference's order (datasets.py:198-233 with boxes=None, z_up=True):
-    one draw for the rotation, then one per flip axis"""
+def _check_probs(flip_prob: float, rotate_prob: float):
     if not (0.0 <= flip_prob <= 1.0):
         raise ValueError("flip_prob must be between 0 and 1, but got {}".format(flip_prob))
     if not (0.0 <= rotate_prob <= 1.0):
         raise ValueError("rotate_prob must be between 0 and 1, but got {}".format(rotate_prob))
+
+
+def draw_augmentation(flip_prob: float, rotate_prob: float, rng=_random) -> int:
+    """flags for `ops.grid_prepare`, drawn in the reference's order (datasets.py:198-233 with boxes=None, z_up=True):
+    one draw for the rotation, then one per flip axis"""
+    _check_probs(flip_prob, rotate_prob)
     flags = 0
     if rng.random() < rotate_prob:
         flags |= ops.GRID_ROT
@@ -47,19 +51,10 @@ def draw_detection_augmentation(flip_prob: float, rotate_prob: float, rot_scale_
     """(flags, angle, scale) of one scene of the detection path, drawn in the reference's order (datasets.py:181-244, z_up=True): rotation, flip 0,
     flip 1; then, for oriented (7-column) boxes only, one draw against `rot_scale_prob` and, if it is taken, uniform(-pi/18, pi/18) and uniform(0.9, 1.1).
     Axis-aligned boxes make exactly three draws.  (0.0, 1.0) means that rot-scale was not taken: the scene goes through `ops.grid_prepare`"""
-    if not (0.0 <= flip_prob <= 1.0):
-        raise ValueError("flip_prob must be between 0 and 1, but got {}".format(flip_prob))
-    if not (0.0 <= rotate_prob <= 1.0):
-        raise ValueError("rotate_prob must be between 0 and 1, but got {}".format(rotate_prob))
+    _check_probs(flip_prob, rotate_prob)
     if not (0.0 <= rot_scale_prob <= 1.0):
         raise ValueError(f"rotate_and_scale_prob must be between 0 and 1, but got {rot_scale_prob}")
-    flags = 0
-    if rng.random() < rotate_prob:
-        flags |= ops.GRID_ROT
-    if rng.random() < flip_prob:
-        flags |= ops.GRID_FLIP0
-    if rng.random() < flip_prob:
-        flags |= ops.GRID_FLIP1
+    flags = draw_augmentation(flip_prob, rotate_prob, rng)
     angle, scale = 0.0, 1.0
     if oriented and rng.random() < rot_scale_prob:
         angle = rng.uniform(-np.pi / 18, np.pi / 18)
@@ -184,6 +179,26 @@ class GridBatcher:
         st = self._stage_begin(slot, scene)
         return self._stage_end(*st), st[1]
 
+    def _batch_out(self, out: Optional[torch.Tensor], shape, name: str = "out") -> torch.Tensor:
+        """the output batch: a new one, or the caller's after a check of what the kernels rely on"""
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"{type(self).__name__}: {name} must be a contiguous float32 {tuple(shape)}")
+        return out
+
+    def _prepare_slot(self, i: int, staged, dst: torch.Tensor, R: int, flags: int, angle: float = 0.0, scale: float = 1.0, slots=None):
+        """the per-scene sequence for slot i of the batch: finish the staging that `_stage_begin` started (-> the H2D copy), the density flag for a float
+        scene under normalize_density, `ops.grid_prepare` -- `ops.grid_prepare_rs` for an (angle, scale) other than (0.0, 1.0) -- into `dst`, and the release
+        of the ring buffer behind that launch -> the valid extents"""
+        src, k = self._stage_end(*staged), staged[1]
+        if self.normalize_density and src.dtype == torch.float32:
+            flags |= ops.GRID_DENSITY
+        e = ops.grid_prepare(src, dst, R, flags) if (angle, scale) == (0.0, 1.0) else ops.grid_prepare_rs(src, dst, R, flags, angle, scale)
+        if k is not None:
+            (self._slots if slots is None else slots)[i].release_after(k, torch.cuda.current_stream())
+        return e
+
     def __call__(self, scenes: List[Scene], flags: Optional[List[int]] = None, out: Optional[torch.Tensor] = None,
                  rng=_random) -> Tuple[torch.Tensor, torch.Tensor]:
         xb, ext = self.prepare(scenes, flags, out, rng)
@@ -192,18 +207,12 @@ class GridBatcher:
     def prepare(self, scenes: List[Scene], flags: Optional[List[int]] = None, out: Optional[torch.Tensor] = None, rng=_random):
         """as __call__, but the extents come back as a host list (no device round trip)"""
         B, R = len(scenes), self.R
-        xb = out if out is not None else torch.empty((B, 4, R, R, R), dtype=torch.float32, device=self.device)
+        xb = self._batch_out(out, (B, 4, R, R, R))
         ext = []
-        st = torch.cuda.current_stream()
         staged = [self._stage_begin(i, sc) for i, sc in enumerate(scenes)]     # all host copies of the batch in flight at once
-        for i, sc in enumerate(scenes):
+        for i in range(B):
             f = flags[i] if flags is not None else draw_augmentation(self.flip_prob, self.rotate_prob, rng)
-            src, k = self._stage_end(*staged[i]), staged[i][1]
-            if self.normalize_density and src.dtype == torch.float32:
-                f |= ops.GRID_DENSITY
-            ext.append(list(ops.grid_prepare(src, xb[i], R, f)))
-            if k is not None:
-                self._slots[i].release_after(k, st)
+            ext.append(list(self._prepare_slot(i, staged[i], xb[i], R, f)))
         return xb, ext
 
 
@@ -259,8 +268,7 @@ class DetectionBatcher(GridBatcher):
             raise ValueError("DetectionBatcher: boxes must be [G, 6] in every scene or [G, 7] in every scene")
         cols = cols.pop()
         counts = [int(b.shape[0]) for b in boxes]
-        xb = out if out is not None else torch.empty((B, 4, R, R, R), dtype=torch.float32, device=self.device)
-        st = torch.cuda.current_stream()
+        xb = self._batch_out(out, (B, 4, R, R, R))
         staged = [self._stage_begin(i, sc) for i, sc in enumerate(scenes)]     # all host copies of the batch in flight at once
         ext, table, first = [], [], 0
         for i in range(B):
@@ -268,18 +276,14 @@ class DetectionBatcher(GridBatcher):
             has_rs = (angle, scale) != (0.0, 1.0)
             if has_rs and cols != 7:
                 raise ValueError("DetectionBatcher: rot-scale needs oriented (7-column) boxes")
-            src, k = self._stage_end(*staged[i]), staged[i][1]
-            g = f | ops.GRID_DENSITY if self.normalize_density and src.dtype == torch.float32 else f
-            e = ops.grid_prepare_rs(src, xb[i], R, g, angle, scale) if has_rs else ops.grid_prepare(src, xb[i], R, g)
-            if k is not None:
-                self._slots[i].release_after(k, st)
+            e = self._prepare_slot(i, staged[i], xb[i], R, f, angle, scale)
             ext.append(list(e))
             table.append((first, counts[i], f, has_rs, e, angle, scale))
             first += counts[i]
         dev, k = self._stage_boxes(boxes, cols, counts)
         outb = ops.boxes_augment(dev, table)
         if k is not None:
-            self._box_ring.release_after(k, st)
+            self._box_ring.release_after(k, torch.cuda.current_stream())
         return xb, ext, [outb[t[0]:t[0] + t[1]] for t in table]
 
 
@@ -347,27 +351,20 @@ class VoxelBatcher(GridBatcher):
             if self.target == "grid" and max(tgts[i].shape[:3]) > Ro:
                 raise ValueError(f"VoxelBatcher: target {i} of extents {tuple(tgts[i].shape[:3])} does not fit the target resolution {Ro}")
         tshape = (B, R, R, R) if self.target == "labels" else (B, 4, Ro, Ro, Ro)
-        xb = out if out is not None else torch.empty((B, 4, R, R, R), dtype=torch.float32, device=self.device)
-        tb = target_out if target_out is not None else torch.empty(tshape, dtype=torch.float32, device=self.device)
-        if tuple(tb.shape) != tshape or tb.dtype != torch.float32 or not tb.is_contiguous():
-            raise ValueError(f"VoxelBatcher: target_out must be a contiguous float32 {tshape}")
-        st = torch.cuda.current_stream()
+        xb, tb = self._batch_out(out, (B, 4, R, R, R)), self._batch_out(target_out, tshape, "target_out")
         staged = [self._stage_begin(i, sc) for i, sc in enumerate(scenes)]     # all host copies of the batch in flight at once, both halves
         staged_t = [self._stage_begin(i, t, self._target_slots) for i, t in enumerate(tgts)]
         ext = []
         for i in range(B):
             f = int(flags[i]) & (ops.GRID_ROT | ops.GRID_FLIP0 | ops.GRID_FLIP1)
-            src, k = self._stage_end(*staged[i]), staged[i][1]
-            ext.append(list(ops.grid_prepare(src, xb[i], R, f | ops.GRID_DENSITY if self.normalize_density and src.dtype == torch.float32 else f)))
-            if k is not None:
-                self._slots[i].release_after(k, st)
-            tsrc, k = self._stage_end(*staged_t[i]), staged_t[i][1]
-            if self.target == "labels":
-                ops.labels_prepare(tsrc, tb[i], R, f)
+            ext.append(list(self._prepare_slot(i, staged[i], xb[i], R, f)))
+            if self.target == "grid":
+                self._prepare_slot(i, staged_t[i], tb[i], Ro, f, slots=self._target_slots)
             else:
-                ops.grid_prepare(tsrc, tb[i], Ro, f | ops.GRID_DENSITY if self.normalize_density and tsrc.dtype == torch.float32 else f)
-            if k is not None:
-                self._target_slots[i].release_after(k, st)
+                tsrc, k = self._stage_end(*staged_t[i]), staged_t[i][1]
+                ops.labels_prepare(tsrc, tb[i], R, f)
+                if k is not None:
+                    self._target_slots[i].release_after(k, torch.cuda.current_stream())
         return xb, ext, tb
 
 

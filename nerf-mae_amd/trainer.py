@@ -144,7 +144,7 @@ class GraphedTrainStep:
         self._embed_cap = embed_capacity_rows(g, p_remove=model.masking_prob)
         self.losses = None
         self._ext_host = None
-        self._g1 = self._g2 = self._gb1 = self._gb2 = None
+        self._g1 = self._g2 = None
         self._gb, self._ranges = [], []
         self._warm = warmup
         self.overlap = True    # False: every collective on the main stream (A/B measurement of what the overlap hides)
@@ -207,7 +207,10 @@ class GraphedTrainStep:
             for _ in range(self._warm):
                 # warm-up touches no optimizer state (lazy kernel attributes / allocator pools only)
                 if split:
-                    self._split_a(zero=True); self._split_b1(); self._split_b2()
+                    self._split_a(zero=True)
+                    for j in range(len(self._pieces["back"])):
+                        self._split_back(j)
+                    self._pieces = None
                 else:
                     self._fwd_bwd()
                     if self.comm_captured:
@@ -248,7 +251,6 @@ class GraphedTrainStep:
         self._g2 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._g2, pool=pool, stream=s, capture_error_mode=_CAPTURE_MODE):
             self.opt.launch()
-        self._gb1 = self._gb[0]            # (kept for callers that test for the split mode)
         self._pieces = None
 
     # ---- the step in autograd pieces (data-parallel graph mode) ----------------------------------------------------------------------
@@ -326,16 +328,6 @@ class GraphedTrainStep:
             e1 = P["e1"]
             ops.add_inplace(e1.grad, d[1].grad)     # stage 1's output feeds stage 2 and decoder3's skip connection
             torch.autograd.backward([f1, f0], [e1.grad, d[0].grad])
-
-    # (compatibility with the three-piece step of round 2: the two encoder pieces by name)
-    def _split_b1(self):
-        for j, pc in enumerate(self._pieces["back"]):
-            if pc["kind"] == "s2":
-                self._split_back(j)
-
-    def _split_b2(self):
-        self._split_back(len(self._pieces["back"]) - 1)
-        self._pieces = None
 
     def __call__(self, grids=None, block_mask=None):
         """grids: optional list of (4,a0,a1,a2) tensors (copied into the static batch); block_mask: uint8 (g,g,g) host tensor"""
@@ -419,14 +411,42 @@ def eval_metrics(eval_out) -> tuple:
     return psnr(pred[..., :3], target[..., :3], m), mse(pred[..., :3], target[..., :3], m)
 
 
+def _unwrapped(model):
+    """the model inside a DDP-style wrapper, or the model itself"""
+    return getattr(model, "module", model)
+
+
+def _write_checkpoint(path: str, sections: dict, epoch: int, train_args: dict, opt=None, step: int = None, flat=None):
+    """the one writer behind the four save_*_checkpoint: {"epoch", one entry per section in the order given (a state dict copied to the host, or None),
+    "train_args" (stored as passed)} and, with `opt`, the "resume" section (resume_section) over `flat`, the owner of the flat buffers: opt.model unless given."""
+    ck = {"epoch": epoch}
+    for name, sd in sections.items():
+        ck[name] = None if sd is None else {k: v.detach().cpu() for k, v in sd.items()}
+    ck["train_args"] = train_args
+    if opt is not None:
+        ck["resume"] = resume_section(opt.model if flat is None else flat, opt, step)
+    torch.save(ck, path)
+
+
+def _read_checkpoint(path: str, parts, opt=None, who: str = "", strict: bool = True) -> dict:
+    """the one reader behind the four load_*_checkpoint.  parts: (section, module, required) triples, loaded in that order; a section that is not required is
+    skipped where the file has none (or None).  With `opt` and a "resume" section the optimizer continues where it stopped (restore_resume over opt.model).
+    Returns the checkpoint dict."""
+    # tensors, numbers, strings, dicts/lists/tuples only: nothing in any checkpoint format needs unpickling of arbitrary objects
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    for section, module, required in parts:
+        if required or ck.get(section) is not None:
+            module.load_state_dict(ck[section], strict=strict)
+    if opt is not None and "resume" in ck:
+        restore_resume(ck["resume"], opt.model, opt, who)
+    return ck
+
+
 def save_checkpoint(path: str, model, epoch: int, train_args: dict, opt: "FusedAdamW" = None, step: int = None):
     """the reference's checkpoint (run_swin_mae3d.py:471-489): {"epoch", "state_dict", "train_args"}; state_dict keys/shapes are the
     reference's, so nerf_rpn loads it unchanged.  With `opt` the file additionally carries what a TRUE resume needs (the reference
     cannot resume its optimizer): AdamW moments over the flat buffer, step count, beta powers, schedule position."""
-    ck = {"epoch": epoch, "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "train_args": dict(train_args)}
-    if opt is not None:
-        ck["resume"] = resume_section(model, opt, step)
-    torch.save(ck, path)
+    _write_checkpoint(path, {"state_dict": model.state_dict()}, epoch, dict(train_args), opt, step, flat=model)
 
 
 def flat_layout(model) -> dict:
@@ -463,15 +483,22 @@ def restore_resume(r: dict, model, opt, who: str):
 def load_checkpoint(path: str, model, opt: "FusedAdamW" = None, strict: bool = True) -> dict:
     """loads a reference-format checkpoint (also one written by the reference itself); returns the checkpoint dict.  With `opt` and
     a "resume" section the optimizer continues where it stopped."""
-    # tensors, numbers, strings, dicts/lists/tuples only: nothing in either checkpoint format needs unpickling of arbitrary objects
-    ck = torch.load(path, map_location="cpu", weights_only=True)
-    model.load_state_dict(ck["state_dict"], strict=strict)
-    if opt is not None and "resume" in ck:
-        r = ck["resume"]
+    ck = _read_checkpoint(path, [("state_dict", model, True)], strict=strict)
+    if opt is not None and "resume" in ck:      # (its own tail: the moments lie over the model itself, which must be on the device by now)
         if model._flat is None or not model._flat.is_cuda:
             raise RuntimeError("load_checkpoint: move the model to the HIP device before restoring the optimizer")
-        restore_resume(r, model, opt, "load_checkpoint")
+        restore_resume(ck["resume"], model, opt, "load_checkpoint")
     return ck
+
+
+def _eval_epoch(val_scenes, epoch: int, eval_interval: int, epochs: int) -> bool:
+    """is `epoch` evaluated: there are validation scenes, and it is a multiple of eval_interval or the last one (from arguments alone: the same on every rank)"""
+    return bool(val_scenes) and (epoch % eval_interval == 0 or epoch == epochs)
+
+
+def _format_record(rec: dict) -> str:
+    """one history record as the log line"""
+    return " ".join(f"{k}={v:.5g}" if isinstance(v, float) else f"{k}={v}" for k, v in rec.items())
 
 
 class Trainer:
@@ -564,7 +591,7 @@ class Trainer:
         for epoch in range(1, self.epochs + 1):
             loss = self.train_epoch(epoch)
             rec = {"epoch": epoch, "train_loss": loss}
-            if self.rank == 0 and self.val_scenes and (epoch % self.eval_interval == 0 or epoch == self.epochs):
+            if self.rank == 0 and _eval_epoch(self.val_scenes, epoch, self.eval_interval, self.epochs):
                 rec["psnr"], rec["mse"] = self.evaluate()
                 if self.save_path:
                     if self.best_metric is None or rec["psnr"] > self.best_metric:
@@ -573,7 +600,7 @@ class Trainer:
                     save_checkpoint(os.path.join(self.save_path, f"epoch_{epoch}.pt"), self.model, epoch, self.args, self.opt, self.global_step)
             self.history.append(rec)
             if self.rank == 0:
-                self.log(" ".join(f"{k}={v:.5g}" if isinstance(v, float) else f"{k}={v}" for k, v in rec.items()))
+                self.log(_format_record(rec))
         return self.history
 
 
@@ -581,7 +608,7 @@ class Trainer:
 # Detection fine-tuning: the reference's checkpoint format and the epoch loop of run_fcos_pretrained.py
 # --------------------------------------------------------------------------------------------------
 def _plain(v):
-    """train_args as torch.load(weights_only=True) reads them back: numbers, strings, None and containers of those; anything else by its str()"""
+    """train_args as the weights-only torch.load of _read_checkpoint reads them back: numbers, strings, None and containers of those; anything else by its str()"""
     if isinstance(v, (bool, int, float, str, type(None))):
         return v
     if isinstance(v, dict):
@@ -595,24 +622,16 @@ def save_detection_checkpoint(path: str, model, epoch: int, train_args: dict, op
     """the reference's detection checkpoint (run_fcos_pretrained.py:477-497): {"epoch", "backbone_state_dict", "fcos_state_dict", "train_args"} of a
     FCOSOverNeRF, keys and shapes the reference's, so nerf_rpn loads it unchanged.  With `opt` (a FusedAdamW over a finetune.FlatParameters of this model) the
     file also carries the "resume" section of save_checkpoint: moments over the flat buffer, t, lr, betas, step and the name -> [offset, numel] layout."""
-    model = getattr(model, "module", model)
-    ck = {"epoch": epoch, "backbone_state_dict": {k: v.detach().cpu() for k, v in model.backbone.state_dict().items()},
-          "fcos_state_dict": {k: v.detach().cpu() for k, v in model.fcos_module.state_dict().items()}, "train_args": _plain(dict(train_args))}
-    if opt is not None:
-        ck["resume"] = resume_section(opt.model, opt, step)
-    torch.save(ck, path)
+    model = _unwrapped(model)
+    _write_checkpoint(path, {"backbone_state_dict": model.backbone.state_dict(), "fcos_state_dict": model.fcos_module.state_dict()}, epoch,
+                      _plain(dict(train_args)), opt, step)
 
 
 def load_detection_checkpoint(path: str, model, opt: "FusedAdamW" = None) -> dict:
     """loads a detection checkpoint (also one written by the reference) strictly into model.backbone and model.fcos_module; returns the checkpoint dict.  With
     `opt` and a "resume" section the optimizer continues where it stopped; moments written under another flat layout are remapped by parameter name."""
-    model = getattr(model, "module", model)
-    ck = torch.load(path, map_location="cpu", weights_only=True)
-    model.backbone.load_state_dict(ck["backbone_state_dict"], strict=True)
-    model.fcos_module.load_state_dict(ck["fcos_state_dict"], strict=True)
-    if opt is not None and "resume" in ck:
-        restore_resume(ck["resume"], opt.model, opt, "load_detection_checkpoint")
-    return ck
+    model = _unwrapped(model)
+    return _read_checkpoint(path, [("backbone_state_dict", model.backbone, True), ("fcos_state_dict", model.fcos_module, True)], opt, "load_detection_checkpoint")
 
 
 def save_two_stage_checkpoint(path: str, model, epoch: int, train_args: dict, opt: "FusedAdamW" = None, step: int = None, fine_tune: bool = True):
@@ -620,28 +639,18 @@ def save_two_stage_checkpoint(path: str, model, epoch: int, train_args: dict, op
     detector.TwoStageDetector, keys and shapes the reference's, so its RCNN loads "RCNN_dict" unchanged.  The first stage's head, which the reference keeps in
     run_rpn.py's own file, goes under "rpn_state_dict".  With `opt` (a FusedAdamW over a finetune.FlatParameters of this model) the file also carries the
     "resume" section of save_checkpoint, in place of the reference's torch optimizer and scheduler state."""
-    model = getattr(model, "module", model)
-    cpu = lambda sd: {k: v.detach().cpu() for k, v in sd.items()}
-    ck = {"epoch": epoch, "backbone_state_dict": cpu(model.rpn_network.backbone.state_dict()) if fine_tune else None,
-          "RCNN_dict": cpu(model.roi_model.RCNN_model.state_dict()), "rpn_state_dict": cpu(model.rpn_network.rpn.state_dict()), "train_args": _plain(dict(train_args))}
-    if opt is not None:
-        ck["resume"] = resume_section(opt.model, opt, step)
-    torch.save(ck, path)
+    model = _unwrapped(model)
+    _write_checkpoint(path, {"backbone_state_dict": model.rpn_network.backbone.state_dict() if fine_tune else None,
+                             "RCNN_dict": model.roi_model.RCNN_model.state_dict(), "rpn_state_dict": model.rpn_network.rpn.state_dict()}, epoch,
+                      _plain(dict(train_args)), opt, step)
 
 
 def load_two_stage_checkpoint(path: str, model, opt: "FusedAdamW" = None) -> dict:
     """loads a second-stage checkpoint (also one written by the reference) strictly into the parts it carries: "RCNN_dict" always, the backbone and the first
     stage's head where present; returns the checkpoint dict.  With `opt` and a "resume" section the optimizer continues where it stopped."""
-    model = getattr(model, "module", model)
-    ck = torch.load(path, map_location="cpu", weights_only=True)
-    model.roi_model.RCNN_model.load_state_dict(ck["RCNN_dict"], strict=True)
-    if ck.get("backbone_state_dict") is not None:
-        model.rpn_network.backbone.load_state_dict(ck["backbone_state_dict"], strict=True)
-    if ck.get("rpn_state_dict") is not None:
-        model.rpn_network.rpn.load_state_dict(ck["rpn_state_dict"], strict=True)
-    if opt is not None and "resume" in ck:
-        restore_resume(ck["resume"], opt.model, opt, "load_two_stage_checkpoint")
-    return ck
+    model = _unwrapped(model)
+    return _read_checkpoint(path, [("RCNN_dict", model.roi_model.RCNN_model, True), ("backbone_state_dict", model.rpn_network.backbone, False),
+                                   ("rpn_state_dict", model.rpn_network.rpn, False)], opt, "load_two_stage_checkpoint")
 
 
 def delete_suboptimal_checkpoints(checkpoint_dir: str, metric_name: str = "ap50", max_to_keep: int = 6, min_to_keep: int = 1):
@@ -681,68 +690,51 @@ def dp_epoch_plan(n: int, batch: int, rank: int, world: int, epoch: int, seed: i
     return [idx[b * batch:(b + 1) * batch] for b in range(-(-len(idx) // batch))]
 
 
-class DetectionTrainer:
-    """Epoch loop of run_fcos_pretrained.py:537-815 without wandb for FCOSOverNeRF, one process per GPU: input from data.DetectionBatcher, one optimizer group over
-    ALL parameters (the reference passes model.parameters(): weight decay applies to everything), clip + AdamW by FusedAdamW over finetune.FlatParameters,
-    loss = loss_cls + reg_loss_weight * loss_reg + loss_centerness, the OneCycle schedule stepped every iteration.
+class _FinetuneTrainer:
+    """What DetectionTrainer and VoxelTrainer share: the epoch loop of the reference's fine-tuning scripts without wandb, one process per GPU.
 
-    `schedule_epochs`: the reference sizes its schedule by a literal 1000 epochs whatever --num_epochs says (`total_steps=1000 * len(train_loader)`, :643-647);
-    that is the default here, so a run of num_epochs < 1000 stops part-way up or down the cycle exactly as the reference's does.  Pass num_epochs for a
-    schedule that ends with the run.
+    One optimizer group over ALL parameters (the reference passes model.parameters(): weight decay applies to everything), clip + AdamW by FusedAdamW over
+    finetune.FlatParameters, the OneCycle schedule over schedule_epochs * steps_per_epoch steps, stepped every iteration.  No drop_last: the ragged last batch
+    of an epoch runs as a smaller batch.  The epoch's logged losses accumulate on the device and are read back once per epoch.  Every `eval_interval` epochs and
+    at the last one: evaluate(), in model.eval(); with `save_path` the subclass then keeps its best checkpoints (_keep_best), which carry the optimizer state.
+    `resume(path)` continues a run from such a file.
 
-    No drop_last: the ragged last batch of an epoch runs as a smaller batch.  The epoch's losses accumulate on the device and are read back once per epoch;
-    `train_loss` of the history is the weighted total, `loss_cls` / `loss_reg` / `loss_centerness` the unweighted parts (the reference logs loss_reg after its
-    in-place weighting).  Every `eval_interval` epochs and at the last one: model.eval(), detections through the reference forward, scored by
-    DetectionEvaluator with the limits [300, 1000, fpn_post_nms_top_n] that do not exceed fpn_post_nms_top_n (:875-877) -> recall at 0.25 / 0.5, AR, AP at
-    0.25 / 0.5 (train_args["ap_top_n"]: detections kept per scene for AP, default all).  Best checkpoints by AP50 and by AP25 under the reference's file names,
-    then the best 6 by AP50 are kept (delete_suboptimal_checkpoints).  The checkpoints carry the optimizer state (save_detection_checkpoint).
-
-    train_scenes / val_scenes: stored scenes ((W,L,H,4) arrays or paths); train_boxes / val_boxes: one [G, 6|7] array per scene.
+    train_scenes / val_scenes: stored scenes ((W,L,H,4) arrays or paths); train_targets / val_targets: one target per scene, as the subclass's batcher takes it.
 
     Data-parallel (rank, world, reducer; the conventions of Trainer; the reference wraps the model in DDP, run_fcos_pretrained.py:359-361): `batch_size` is per
     rank and train_args["batch_size"] = batch_size * world (:614); every rank holds all scenes and trains on its shard (dp_epoch_plan).  INVARIANT: every rank
     runs the same number of steps per epoch with the same batch sizes, the ragged last one included, because dist.shard_indices pads the shards to equal length
-    -- each step holds collectives (the loss normalisers, the gradient ranges), and a rank that ran one step fewer would hang the others.  The model must have
-    been built with world_size=world (its loss all-reduces the normalisers); the constructor broadcasts rank 0's parameters.  `reducer`: a
-    dist.FlatGradReducer over a finetune.FlatParameters of this model, which the trainer then adopts (that is how bf16 buckets are chosen); None with world > 1
-    builds one with fp32 buckets.  The augmentation draws of rank r come from random.Random(seed + 1000003 * r).  The three accumulated epoch losses are
-    averaged over the ranks in ONE all-reduce per epoch (the reference: a barrier and four all-reduces per step, :747-751).  Evaluation, checkpoints and
-    delete_suboptimal_checkpoints run on rank 0 only; the other ranks wait at one barrier per evaluated epoch and their `history` carries the training losses
-    only.  With world = 1 nothing of this is active."""
+    -- each step holds collectives (the loss normalisers, the gradient ranges), and a rank that ran one step fewer would hang the others.  The constructor
+    broadcasts rank 0's parameters.  `reducer`: a dist.FlatGradReducer over a finetune.FlatParameters of this model, which the trainer then adopts (that is how
+    bf16 buckets are chosen); None with world > 1 builds one with fp32 buckets.  The augmentation draws of rank r come from random.Random(seed + 1000003 * r),
+    scene by scene, batch by batch, and nothing else uses that generator.  The accumulated epoch losses are averaged over the ranks in ONE all-reduce per epoch
+    (the reference: a barrier and four all-reduces per step, :747-751).  Evaluation and files are rank 0's; the other ranks wait at one barrier per evaluated
+    epoch and their `history` carries the training losses only.  With world = 1 nothing of this is active.
 
-    def __init__(self, model, train_scenes, train_boxes, val_scenes=None, val_boxes=None, batch_size: int = 2, num_epochs: int = 1, lr: float = 3e-4,
-                 weight_decay: float = 1e-3, clip_grad_norm: float = 0.1, reg_loss_weight: float = 1.0, eval_interval: int = 1, save_path: str = None,
-                 normalize_density: bool = True, flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = 1000,
-                 log=print, train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None):
+    A subclass supplies its checkpoint pair (_save_checkpoint, _load_checkpoint) and
+      _logged(losses)         the step's detached losses -> the 1-D tensor that the epoch accumulates
+      _record(vals)           the epoch's means of _logged, read back as a list -> the training part of the history record
+      evaluate()              -> the evaluation part of the record
+      _keep_best(epoch, rec)  rank 0 has evaluated `epoch` with record `rec` and there is a save_path: the best-checkpoint policy
+    and may override _target(t), a stored target as the batcher takes it."""
+
+    def __init__(self, model, train_scenes, train_targets, val_scenes, val_targets, batcher, val_batcher, loss_fn, weights, args: dict, batch_size: int,
+                 num_epochs: int, schedule_epochs: int, lr: float, weight_decay: float, clip_grad_norm: float, eval_interval: int, save_path: str, log, seed: int,
+                 rank: int, world: int, reducer):
         import random
-        from . import data, dist as _dist
-        from .finetune import FinetuneStep, FlatParameters, fcos_loss_fn
-        if len(train_scenes) != len(train_boxes) or (val_scenes is not None and len(val_scenes) != len(val_boxes or [])):
-            raise ValueError("DetectionTrainer: one box array per scene")
-        if len(train_scenes) < 1:
-            raise ValueError("DetectionTrainer: no training scene")
-        resolution = getattr(model, "resoluton", None)          # (the reference's spelling, fcos.FCOSOverNeRF)
-        if resolution is None:
-            raise ValueError("DetectionTrainer: the model needs a fixed resolution (FCOSOverNeRF(..., resolution=R)): the batcher pads every scene to it")
-        self.model, self.train_scenes, self.train_boxes, self.val_scenes, self.val_boxes = model, train_scenes, train_boxes, val_scenes, val_boxes
+        from . import dist as _dist
+        from .finetune import FinetuneStep, FlatParameters
+        self.model, self.train_scenes, self.train_targets, self.val_scenes, self.val_targets = model, train_scenes, train_targets, val_scenes, val_targets
         self.batch, self.epochs, self.eval_interval, self.save_path, self.log, self.seed = batch_size, num_epochs, eval_interval, save_path, log, seed
-        self.reg_loss_weight = reg_loss_weight
         self.rank, self.world = rank, world
-        if world > 1 and getattr(model, "world_size", 1) != world:
-            raise ValueError(f"DetectionTrainer: world = {world}, but the model's loss was built with world_size = {getattr(model, 'world_size', 1)}: its two "
-                             "normalisers would be per-rank sums and the result silently another; build FCOSOverNeRF(..., world_size=world)")
-        self.args = _plain(dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, reg_loss_weight=reg_loss_weight,
-                                batch_size=batch_size * world, num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob,
-                                rotate_prob=rotate_prob, rot_scale_prob=rot_scale_prob))
-        dev = next(model.parameters()).device
-        self.batcher = data.DetectionBatcher(resolution, dev, normalize_density, flip_prob, rotate_prob, rot_scale_prob)
-        self.val_batcher = data.DetectionBatcher(resolution, dev, normalize_density)
+        self.args = _plain(args)
+        self.batcher, self.val_batcher = batcher, val_batcher
         if reducer is not None:
             if getattr(reducer.model, "module", None) is not model:
-                raise ValueError("DetectionTrainer: the reducer must be a dist.FlatGradReducer over a finetune.FlatParameters of this model")
+                raise ValueError(f"{type(self).__name__}: the reducer must be a dist.FlatGradReducer over a finetune.FlatParameters of this model")
             self.flat = reducer.model
         else:
-            self.flat = FlatParameters(model, dev)
+            self.flat = FlatParameters(model, next(model.parameters()).device)
             if world > 1:
                 reducer = _dist.FlatGradReducer(self.flat)
         self.reducer = reducer
@@ -751,12 +743,9 @@ class DetectionTrainer:
         self.opt = FusedAdamW(self.flat, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
         self.steps_per_epoch = len(dp_epoch_plan(len(train_scenes), batch_size, rank, world, 0, seed))   # len(train_loader) without drop_last, the same on every rank
         self.sched = OneCycle(lr, schedule_epochs * self.steps_per_epoch)
-        self.step_fn = FinetuneStep(self.flat, self.opt, fcos_loss_fn(model), weights={"loss_reg": reg_loss_weight}, reducer=reducer)
-        self.top_n = int(model.args.fpn_post_nms_top_n)
-        self.limits = [l for l in (300, 1000, self.top_n) if l <= self.top_n]
-        self.ap_top_n = (train_args or {}).get("ap_top_n")
+        self.step_fn = FinetuneStep(self.flat, self.opt, loss_fn, weights=weights, reducer=reducer)
         self._rng = random.Random(seed + 1000003 * rank)         # the augmentation draws: another sequence on every rank
-        self.global_step, self.best_metric_ap50, self.best_metric_ap25, self.history = 0, None, None, []
+        self.global_step, self.start_epoch, self.history = 0, 1, []
 
     @staticmethod
     def _load(s):
@@ -768,22 +757,118 @@ class DetectionTrainer:
         """the batcher's padded batch as the list of grids in their own sizes that the reference forward takes (it pads them again and keeps the sizes)"""
         return [xb[i, :, :e[0], :e[1], :e[2]] for i, e in enumerate(ext)]
 
+    def _target(self, t):
+        return t
+
+    def _batch(self, ids):
+        """the scenes `ids` -> (meshes, targets) of one step, the augmentation drawn from this rank's generator"""
+        xb, ext, targets = self.batcher.prepare([self._load(self.train_scenes[i]) for i in ids], [self._target(self.train_targets[i]) for i in ids], rng=self._rng)
+        return self._meshes(xb, ext), targets
+
     def train_epoch(self, epoch: int):
         self.model.train()
         acc = None
         for ids in dp_epoch_plan(len(self.train_scenes), self.batch, self.rank, self.world, epoch, self.seed):     # the DataLoader's shuffle, this rank's shard
-            xb, ext, targets = self.batcher.prepare([self._load(self.train_scenes[i]) for i in ids], [self.train_boxes[i] for i in ids], rng=self._rng)
+            meshes, targets = self._batch(ids)
             lr, b1 = self.sched.at(self.global_step)
             self.opt.set_hyper(lr=lr, beta1=b1)
-            losses = self.step_fn(self._meshes(xb, ext), targets)
+            parts = self._logged(self.step_fn(meshes, targets))
             self.global_step += 1
-            parts = torch.stack([losses["loss_cls"], losses["loss_reg"], losses["loss_centerness"]])
             acc = parts if acc is None else acc + parts
         if self.world > 1:
             import torch.distributed as tdist
             tdist.all_reduce(acc, op=tdist.ReduceOp.SUM)              # the epoch's one exchange of the logged losses: their mean over the ranks
             acc = acc / self.world
-        cls, reg, ctr = (acc / self.steps_per_epoch).tolist()         # the epoch's one read-back
+        return self._record((acc / self.steps_per_epoch).tolist())   # the epoch's one read-back
+
+    def _save(self, name: str, epoch: int):
+        import os
+        self._save_checkpoint(os.path.join(self.save_path, name), self.model, epoch, self.args, self.opt, self.global_step)
+
+    def resume(self, path: str) -> dict:
+        """continue a run from a file of this trainer's checkpoint writer: weights, optimizer state, schedule position; fit() then starts at the epoch after the
+        file's"""
+        ck = self._load_checkpoint(path, self.model, self.opt)
+        self.flat.check()
+        self.start_epoch = int(ck["epoch"]) + 1
+        step = ck.get("resume", {}).get("step")
+        self.global_step = int(step) if step is not None else (self.start_epoch - 1) * self.steps_per_epoch
+        return ck
+
+    def fit(self):
+        import os
+        if self.save_path and self.rank == 0:
+            os.makedirs(self.save_path, exist_ok=True)
+        for epoch in range(self.start_epoch, self.epochs + 1):
+            rec = {"epoch": epoch, **self.train_epoch(epoch)}
+            evaluated = _eval_epoch(self.val_scenes, epoch, self.eval_interval, self.epochs)    # the same decision on every rank
+            if evaluated and self.rank == 0:
+                rec.update(self.evaluate())
+                if self.save_path:
+                    self._keep_best(epoch, rec)
+            if evaluated and self.world > 1:
+                import torch.distributed as tdist
+                tdist.barrier()        # the other ranks wait here for rank 0's evaluation and files, once per evaluated epoch
+            self.history.append(rec)
+            if self.rank == 0:
+                self.log(_format_record(rec))
+        return self.history
+
+
+class DetectionTrainer(_FinetuneTrainer):
+    """Epoch loop of run_fcos_pretrained.py:537-815 for FCOSOverNeRF (the conventions of _FinetuneTrainer): input from data.DetectionBatcher,
+    loss = loss_cls + reg_loss_weight * loss_reg + loss_centerness.
+
+    `schedule_epochs`: the reference sizes its schedule by a literal 1000 epochs whatever --num_epochs says (`total_steps=1000 * len(train_loader)`, :643-647);
+    that is the default here, so a run of num_epochs < 1000 stops part-way up or down the cycle exactly as the reference's does.  Pass num_epochs for a
+    schedule that ends with the run.
+
+    `train_loss` of the history is the weighted total, `loss_cls` / `loss_reg` / `loss_centerness` the unweighted parts (the reference logs loss_reg after its
+    in-place weighting).  Evaluation: detections through the reference forward, scored by DetectionEvaluator with the limits [300, 1000, fpn_post_nms_top_n]
+    that do not exceed fpn_post_nms_top_n (:875-877) -> recall at 0.25 / 0.5, AR, AP at 0.25 / 0.5 (train_args["ap_top_n"]: detections kept per scene for AP,
+    default all).  Best checkpoints by AP50 and by AP25 under the reference's file names (save_detection_checkpoint), then the best 6 by AP50 are kept
+    (delete_suboptimal_checkpoints).
+
+    train_boxes / val_boxes: one [G, 6|7] array per scene.  Data-parallel: the model must have been built with world_size=world (its loss all-reduces the
+    normalisers)."""
+
+    _save_checkpoint, _load_checkpoint = staticmethod(save_detection_checkpoint), staticmethod(load_detection_checkpoint)
+
+    def __init__(self, model, train_scenes, train_boxes, val_scenes=None, val_boxes=None, batch_size: int = 2, num_epochs: int = 1, lr: float = 3e-4,
+                 weight_decay: float = 1e-3, clip_grad_norm: float = 0.1, reg_loss_weight: float = 1.0, eval_interval: int = 1, save_path: str = None,
+                 normalize_density: bool = True, flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = 1000,
+                 log=print, train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None):
+        from . import data
+        from .finetune import fcos_loss_fn
+        if len(train_scenes) != len(train_boxes) or (val_scenes is not None and len(val_scenes) != len(val_boxes or [])):
+            raise ValueError("DetectionTrainer: one box array per scene")
+        if len(train_scenes) < 1:
+            raise ValueError("DetectionTrainer: no training scene")
+        resolution = getattr(model, "resoluton", None)          # (the reference's spelling, fcos.FCOSOverNeRF)
+        if resolution is None:
+            raise ValueError("DetectionTrainer: the model needs a fixed resolution (FCOSOverNeRF(..., resolution=R)): the batcher pads every scene to it")
+        if world > 1 and getattr(model, "world_size", 1) != world:
+            raise ValueError(f"DetectionTrainer: world = {world}, but the model's loss was built with world_size = {getattr(model, 'world_size', 1)}: its two "
+                             "normalisers would be per-rank sums and the result silently another; build FCOSOverNeRF(..., world_size=world)")
+        self.train_boxes, self.val_boxes, self.reg_loss_weight = train_boxes, val_boxes, reg_loss_weight
+        dev = next(model.parameters()).device
+        super().__init__(model, train_scenes, train_boxes, val_scenes, val_boxes,
+                         data.DetectionBatcher(resolution, dev, normalize_density, flip_prob, rotate_prob, rot_scale_prob),
+                         data.DetectionBatcher(resolution, dev, normalize_density), fcos_loss_fn(model), {"loss_reg": reg_loss_weight},
+                         dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, reg_loss_weight=reg_loss_weight,
+                              batch_size=batch_size * world, num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob,
+                              rotate_prob=rotate_prob, rot_scale_prob=rot_scale_prob),
+                         batch_size, num_epochs, schedule_epochs, lr, weight_decay, clip_grad_norm, eval_interval, save_path, log, seed, rank, world, reducer)
+        self.top_n = int(model.args.fpn_post_nms_top_n)
+        self.limits = [l for l in (300, 1000, self.top_n) if l <= self.top_n]
+        self.ap_top_n = (train_args or {}).get("ap_top_n")
+        self.best_metric_ap50 = self.best_metric_ap25 = None
+
+    def _logged(self, losses):
+        return torch.stack([losses["loss_cls"], losses["loss_reg"], losses["loss_centerness"]])
+
+    def _record(self, vals):
+        cls, reg, ctr = vals
         return {"train_loss": cls + self.reg_loss_weight * reg + ctr, "loss_cls": cls, "loss_reg": reg, "loss_centerness": ctr}
 
     @torch.no_grad()
@@ -805,35 +890,15 @@ class DetectionTrainer:
         rec["ap_25"], rec["ap_50"] = float(out["ap_25"]["ap"]), float(out["ap_50"]["ap"])
         return rec
 
-    def _save(self, name, epoch):
-        import os
-        save_detection_checkpoint(os.path.join(self.save_path, name), self.model, epoch, self.args, self.opt, self.global_step)
-
-    def fit(self):
-        import os
-        if self.save_path and self.rank == 0:
-            os.makedirs(self.save_path, exist_ok=True)
-        for epoch in range(1, self.epochs + 1):
-            rec = {"epoch": epoch, **self.train_epoch(epoch)}
-            evaluated = bool(self.val_scenes) and (epoch % self.eval_interval == 0 or epoch == self.epochs)    # the same decision on every rank
-            if evaluated and self.rank == 0:
-                rec.update(self.evaluate())
-                ap50, ap25 = rec["ap_50"], rec["ap_25"]
-                if self.save_path:
-                    if self.best_metric_ap50 is None or ap50 > self.best_metric_ap50:
-                        self.best_metric_ap50 = ap50
-                        self._save(f"model_best_ap50_ap25_{ap50}_{ap25}.pt", epoch)
-                    if self.best_metric_ap25 is None or ap25 > self.best_metric_ap25:
-                        self.best_metric_ap25 = ap25
-                        self._save(f"model_best_ap25_ap50_{ap50}_{ap25}.pt", epoch)
-                    delete_suboptimal_checkpoints(self.save_path, "ap50", 6, 1)
-            if evaluated and self.world > 1:
-                import torch.distributed as tdist
-                tdist.barrier()        # the other ranks wait here for rank 0's evaluation and files, once per evaluated epoch
-            self.history.append(rec)
-            if self.rank == 0:
-                self.log(" ".join(f"{k}={v:.5g}" if isinstance(v, float) else f"{k}={v}" for k, v in rec.items()))
-        return self.history
+    def _keep_best(self, epoch: int, rec: dict):
+        ap50, ap25 = rec["ap_50"], rec["ap_25"]
+        if self.best_metric_ap50 is None or ap50 > self.best_metric_ap50:
+            self.best_metric_ap50 = ap50
+            self._save(f"model_best_ap50_ap25_{ap50}_{ap25}.pt", epoch)
+        if self.best_metric_ap25 is None or ap25 > self.best_metric_ap25:
+            self.best_metric_ap25 = ap25
+            self._save(f"model_best_ap25_ap50_{ap50}_{ap25}.pt", epoch)
+        delete_suboptimal_checkpoints(self.save_path, "ap50", 6, 1)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -843,52 +908,37 @@ def save_voxel_checkpoint(path: str, model, epoch: int, train_args: dict, opt: "
     """the voxel runs' checkpoint (run_voxel_semantics.py:509-527, run_voxelSR.py:494-512): {"epoch", "state_dict", "train_args"} of a voxel head, keys and
     shapes the reference's.  With `opt` (a FusedAdamW over a finetune.FlatParameters of this model) the file also carries the "resume" section of
     save_checkpoint."""
-    model = getattr(model, "module", model)
-    ck = {"epoch": epoch, "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "train_args": _plain(dict(train_args))}
-    if opt is not None:
-        ck["resume"] = resume_section(opt.model, opt, step)
-    torch.save(ck, path)
+    _write_checkpoint(path, {"state_dict": _unwrapped(model).state_dict()}, epoch, _plain(dict(train_args)), opt, step)
 
 
 def load_voxel_checkpoint(path: str, model, opt: "FusedAdamW" = None) -> dict:
     """loads a voxel-head checkpoint (also one written by the reference) strictly; returns the checkpoint dict.  With `opt` and a "resume" section the optimizer
     continues where it stopped; a file without the section loads the weights only."""
-    model = getattr(model, "module", model)
-    ck = torch.load(path, map_location="cpu", weights_only=True)
-    model.load_state_dict(ck["state_dict"], strict=True)
-    if opt is not None and "resume" in ck:
-        restore_resume(ck["resume"], opt.model, opt, "load_voxel_checkpoint")
-    return ck
+    return _read_checkpoint(path, [("state_dict", _unwrapped(model), True)], opt, "load_voxel_checkpoint")
 
 
-class VoxelTrainer:
-    """Epoch loops of run_voxel_semantics.py:537-958 and run_voxelSR.py:600-790 without wandb, one process per GPU, for the two heads of heads.py: input from
-    data.VoxelBatcher (scene and target under one augmentation draw, the target never a host fp32 batch), AdamW over ALL parameters + clip by FusedAdamW over
-    finetune.FlatParameters, OneCycle sized by `num_epochs` (`schedule_epochs` overrides; the reference: total_steps = num_epochs * len(train_loader)) and stepped
-    every iteration, no drop_last.  The head decides the rest:
+class VoxelTrainer(_FinetuneTrainer):
+    """Epoch loops of run_voxel_semantics.py:537-958 and run_voxelSR.py:600-790 for the two heads of heads.py (the conventions of _FinetuneTrainer): input from
+    data.VoxelBatcher (scene and target under one augmentation draw, the target never a host fp32 batch), OneCycle sized by `num_epochs` (`schedule_epochs`
+    overrides; the reference: total_steps = num_epochs * len(train_loader)).  The head decides the rest:
 
       semantics   train_targets: one label volume per scene ((W,L,H) or (1,W,L,H), uint8 / int32 / int64 / float32).  History: train_loss, train_iou (the loss's
                   mean soft IoU, its second output, outside the backward), and from SemanticEvaluator mIoU, mAcc, allAcc; best by mIoU.
       SR          train_targets: one stored high-resolution scene (W',L',H',4) per scene, padded to int(R * final_upsample.scale_factor).  History: train_loss,
                   and from heads.SREvaluator psnr, mse (the means of the per-batch values); best by psnr.
 
-    Evaluation every `eval_interval` epochs and at the last one, in model.eval() with flags 0; `model_best.pt` = {"epoch", "state_dict", "train_args"} plus the
-    resume section (save_voxel_checkpoint).  `resume(path)` continues a run from such a file.
+    Evaluation with flags 0; `model_best.pt` = {"epoch", "state_dict", "train_args"} plus the resume section (save_voxel_checkpoint).
 
     Augmentation: flip_prob / rotate_prob > 0 apply ONE draw to scene and target, which the reference cannot do (see data.VoxelBatcher); rot_scale_prob is a
-    trilinear blend without meaning for labels and must be 0.
+    trilinear blend without meaning for labels and must be 0."""
 
-    Data-parallel (rank, world, reducer) by the conventions of DetectionTrainer: `batch_size` per rank, dp_epoch_plan (equal step counts and batch sizes on
-    every rank), draws from random.Random(seed + 1000003 * rank), the epoch's logged losses in one all-reduce and one read-back, evaluation and files on rank 0
-    with one barrier per evaluated epoch; reducer None with world > 1 builds a dist.FlatGradReducer with fp32 buckets; rank 0's parameters are broadcast."""
+    _save_checkpoint, _load_checkpoint = staticmethod(save_voxel_checkpoint), staticmethod(load_voxel_checkpoint)
 
     def __init__(self, model, train_scenes, train_targets, val_scenes=None, val_targets=None, batch_size: int = 1, num_epochs: int = 1, lr: float = 5e-3,
                  weight_decay: float = 0.01, clip_grad_norm: float = 0.1, eval_interval: int = 1, save_path: str = None, normalize_density: bool = True,
                  flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = None, log=print,
                  train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None):
-        import random
-        from . import data, dist as _dist
-        from .finetune import FinetuneStep, FlatParameters
+        from . import data
         from .heads import SwinTransformer_VoxelSemantics_Pretrained_Skip, SwinTransformer_VoxelSR_Pretrained_Skip
         if isinstance(model, SwinTransformer_VoxelSemantics_Pretrained_Skip):
             self.kind, self.best_key = "semantics", "mIoU"
@@ -903,38 +953,19 @@ class VoxelTrainer:
             raise ValueError("VoxelTrainer: one target per scene")
         if len(train_scenes) < 1:
             raise ValueError("VoxelTrainer: no training scene")
-        self.model, self.train_scenes, self.train_targets, self.val_scenes, self.val_targets = model, train_scenes, train_targets, val_scenes, val_targets
-        self.batch, self.epochs, self.eval_interval, self.save_path, self.log, self.seed = batch_size, num_epochs, eval_interval, save_path, log, seed
-        self.rank, self.world = rank, world
-        self.args = _plain(dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, batch_size=batch_size * world,
-                                num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
-                                rot_scale_prob=rot_scale_prob))
         dev = next(model.parameters()).device
         R = model.input_resolution
         kw = dict(target="labels") if self.kind == "semantics" else dict(target="grid", target_resolution=int(R * float(model.final_upsample.scale_factor)))
-        self.batcher = data.VoxelBatcher(R, dev, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob, **kw)
-        self.val_batcher = data.VoxelBatcher(R, dev, normalize_density=normalize_density, **kw)
-        if reducer is not None:
-            if getattr(reducer.model, "module", None) is not model:
-                raise ValueError("VoxelTrainer: the reducer must be a dist.FlatGradReducer over a finetune.FlatParameters of this model")
-            self.flat = reducer.model
-        else:
-            self.flat = FlatParameters(model, dev)
-            if world > 1:
-                reducer = _dist.FlatGradReducer(self.flat)
-        self.reducer = reducer
-        if world > 1:
-            _dist.broadcast_flat_parameters(self.flat)   # DDP's initial broadcast: every rank starts from rank 0's weights
-        self.opt = FusedAdamW(self.flat, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
-        self.steps_per_epoch = len(dp_epoch_plan(len(train_scenes), batch_size, rank, world, 0, seed))   # len(train_loader) without drop_last, the same on every rank
-        self.sched = OneCycle(lr, (schedule_epochs or num_epochs) * self.steps_per_epoch)
         self._aux = None                                     # the semantics loss's mean soft IoU of the step: logged, never part of the backward
-        self.step_fn = FinetuneStep(self.flat, self.opt, self._loss, reducer=reducer)
-        self._rng = random.Random(seed + 1000003 * rank)     # the augmentation draws: another sequence on every rank
-        self.global_step, self.start_epoch, self.best_metric, self.history = 0, 1, None, []
-
-    _load = staticmethod(DetectionTrainer._load)
-    _meshes = staticmethod(DetectionTrainer._meshes)
+        super().__init__(model, train_scenes, train_targets, val_scenes, val_targets,
+                         data.VoxelBatcher(R, dev, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob, **kw),
+                         data.VoxelBatcher(R, dev, normalize_density=normalize_density, **kw), self._loss, None,
+                         dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, batch_size=batch_size * world,
+                              num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
+                              rot_scale_prob=rot_scale_prob),
+                         batch_size, num_epochs, schedule_epochs or num_epochs, lr, weight_decay, clip_grad_norm, eval_interval, save_path, log, seed, rank, world,
+                         reducer)
+        self.best_metric = None
 
     def _loss(self, meshes, tb):
         out = self.model.loss_fn(tb, self.model(meshes))
@@ -947,22 +978,10 @@ class VoxelTrainer:
         """a stored target by path: the scene file's `rgbsigma` for the SR head; label volumes are passed as arrays"""
         return self._load(t) if self.kind == "sr" else t
 
-    def train_epoch(self, epoch: int):
-        self.model.train()
-        acc = None
-        for ids in dp_epoch_plan(len(self.train_scenes), self.batch, self.rank, self.world, epoch, self.seed):     # the DataLoader's shuffle, this rank's shard
-            xb, ext, tb = self.batcher.prepare([self._load(self.train_scenes[i]) for i in ids], [self._target(self.train_targets[i]) for i in ids], rng=self._rng)
-            lr, b1 = self.sched.at(self.global_step)
-            self.opt.set_hyper(lr=lr, beta1=b1)
-            losses = self.step_fn(self._meshes(xb, ext), tb)
-            self.global_step += 1
-            parts = torch.stack([losses["loss"], self._aux]) if self.kind == "semantics" else losses["loss"].reshape(1)
-            acc = parts if acc is None else acc + parts
-        if self.world > 1:
-            import torch.distributed as tdist
-            tdist.all_reduce(acc, op=tdist.ReduceOp.SUM)              # the epoch's one exchange of the logged losses: their mean over the ranks
-            acc = acc / self.world
-        vals = (acc / self.steps_per_epoch).tolist()                  # the epoch's one read-back
+    def _logged(self, losses):
+        return torch.stack([losses["loss"], self._aux]) if self.kind == "semantics" else losses["loss"].reshape(1)
+
+    def _record(self, vals):
         return dict(zip(("train_loss", "train_iou"), vals))
 
     @torch.no_grad()
@@ -983,31 +1002,7 @@ class VoxelTrainer:
             return {k: float(out[k]) for k in ("mIoU", "mAcc", "allAcc")}
         return {"psnr": float(out["psnr_mean"]), "mse": float(out["mse_mean"])}
 
-    def resume(self, path: str) -> dict:
-        """continue a run from a file of save_voxel_checkpoint: weights, optimizer state, schedule position; fit() then starts at the epoch after the file's"""
-        ck = load_voxel_checkpoint(path, self.model, self.opt)
-        self.flat.check()
-        self.start_epoch = int(ck["epoch"]) + 1
-        step = ck.get("resume", {}).get("step")
-        self.global_step = int(step) if step is not None else (self.start_epoch - 1) * self.steps_per_epoch
-        return ck
-
-    def fit(self):
-        import os
-        if self.save_path and self.rank == 0:
-            os.makedirs(self.save_path, exist_ok=True)
-        for epoch in range(self.start_epoch, self.epochs + 1):
-            rec = {"epoch": epoch, **self.train_epoch(epoch)}
-            evaluated = bool(self.val_scenes) and (epoch % self.eval_interval == 0 or epoch == self.epochs)    # the same decision on every rank
-            if evaluated and self.rank == 0:
-                rec.update(self.evaluate())
-                if self.save_path and (self.best_metric is None or rec[self.best_key] > self.best_metric):
-                    self.best_metric = rec[self.best_key]
-                    save_voxel_checkpoint(os.path.join(self.save_path, "model_best.pt"), self.model, epoch, self.args, self.opt, self.global_step)
-            if evaluated and self.world > 1:
-                import torch.distributed as tdist
-                tdist.barrier()        # the other ranks wait here for rank 0's evaluation and file, once per evaluated epoch
-            self.history.append(rec)
-            if self.rank == 0:
-                self.log(" ".join(f"{k}={v:.5g}" if isinstance(v, float) else f"{k}={v}" for k, v in rec.items()))
-        return self.history
+    def _keep_best(self, epoch: int, rec: dict):
+        if self.best_metric is None or rec[self.best_key] > self.best_metric:
+            self.best_metric = rec[self.best_key]
+            self._save("model_best.pt", epoch)

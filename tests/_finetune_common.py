@@ -77,3 +77,14 @@ def trainable(module):
 
 def round8(n):
     return (n + 7) // 8 * 8
+
+
+def record_batches(tr, scenes):
+    """wraps tr.batcher.prepare -> the list that fills with the batches it receives, each as the indices into `scenes` of the arrays handed over"""
+    seen, prepare = [], tr.batcher.prepare
+
+    def recording(batch, *a, **k):
+        seen.append([next(i for i, s in enumerate(scenes) if s is b) for b in batch])
+        return prepare(batch, *a, **k)
+    tr.batcher.prepare = recording
+    return seen

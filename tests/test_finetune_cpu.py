@@ -1,5 +1,6 @@
 """finetune.FlatParameters and the detection checkpoint on the host (flatten_parameters(device=cpu) is supported, so the layout logic needs no GPU): the common
-small models of tests/_finetune_common.py.  The step itself, the optimizer arithmetic and DetectionTrainer are tests/test_finetune_gpu.py."""
+small models of tests/_finetune_common.py; the four checkpoint formats (key order, train_args, resume section, weights-only files, missing sections) on stand-in
+modules.  The step itself, the optimizer arithmetic and DetectionTrainer are tests/test_finetune_gpu.py."""
 import copy
 import os
 import sys
@@ -222,3 +223,115 @@ def test_delete_suboptimal_checkpoints_keeps_the_best_six_by_ap50(tmp_path):
     delete_suboptimal_checkpoints(str(tmp_path), "ap50", 6, 1)
     left = sorted(float(f.split("_")[-2]) for f in os.listdir(tmp_path))
     assert left == sorted(ap50)[-6:]
+
+
+# ---- the four checkpoint formats: key order, train_args, resume section, weights-only files, missing sections ---------------------------------------------
+class _Flat(torch.nn.Module):
+    """stand-in for a flattened model (and for finetune.FlatParameters): what flat_layout reads"""
+
+    def __init__(self, module):
+        super().__init__()
+        self.module = module
+        self._offsets, off = {}, 0
+        for p in module.parameters():
+            self._offsets[id(p)] = off
+            off += C.round8(p.numel())
+        self._flat = torch.zeros(off)
+
+    def named_parameters(self, *a, **k):
+        return self.module.named_parameters(*a, **k)
+
+
+def _lin(seed):
+    torch.manual_seed(seed)
+    return torch.nn.Linear(3, 2)
+
+
+def _stand_in(which, seed):
+    """a module with the attribute names the writer of `which` reads, and the {section: module} it stores"""
+    if which in ("mae", "voxel"):
+        m = _lin(seed)
+        return m, {"state_dict": m}
+    m = torch.nn.Module()
+    if which == "detection":
+        m.backbone, m.fcos_module = _lin(seed), _lin(seed + 1)
+        return m, {"backbone_state_dict": m.backbone, "fcos_state_dict": m.fcos_module}
+    m.rpn_network, m.roi_model = torch.nn.Module(), torch.nn.Module()
+    m.rpn_network.backbone, m.rpn_network.rpn, m.roi_model.RCNN_model = _lin(seed), _lin(seed + 1), _lin(seed + 2)
+    return m, {"backbone_state_dict": m.rpn_network.backbone, "RCNN_dict": m.roi_model.RCNN_model, "rpn_state_dict": m.rpn_network.rpn}
+
+
+CHECKPOINT_KEYS = {"mae": ["epoch", "state_dict", "train_args"],
+                   "detection": ["epoch", "backbone_state_dict", "fcos_state_dict", "train_args"],
+                   "two_stage": ["epoch", "backbone_state_dict", "RCNN_dict", "rpn_state_dict", "train_args"],
+                   "voxel": ["epoch", "state_dict", "train_args"]}
+REQUIRED = {"mae": "state_dict", "detection": "fcos_state_dict", "two_stage": "RCNN_dict", "voxel": "state_dict"}
+
+
+@pytest.mark.parametrize("which", list(CHECKPOINT_KEYS))
+def test_checkpoint_writers_key_order_resume_and_required_sections(tmp_path, which):
+    from nerf_mae_amd import trainer as T
+    save, load = {"mae": (T.save_checkpoint, T.load_checkpoint), "detection": (T.save_detection_checkpoint, T.load_detection_checkpoint),
+                  "two_stage": (T.save_two_stage_checkpoint, T.load_two_stage_checkpoint), "voxel": (T.save_voxel_checkpoint, T.load_voxel_checkpoint)}[which]
+    m, parts = _stand_in(which, 0)
+    # save_checkpoint stores train_args as passed, the fine-tuning formats through _plain
+    args = {"lr": 1e-3, "sizes": [1, 2]} if which == "mae" else {"lr": 1e-3, "sizes": (1, 2), "device": CPU, 5: None}
+    plain = {"lr": 1e-3, "sizes": [1, 2]} if which == "mae" else {"lr": 1e-3, "sizes": [1, 2], "device": "cpu", "5": None}
+    path = str(tmp_path / "a.pt")
+
+    def equal(a, b):
+        a, b = a.state_dict(), b.state_dict()
+        return list(a) == list(b) and all(torch.equal(a[k], b[k]) for k in a)
+
+    # without an optimizer: the format's keys in their order, no resume section; the file loads the weights only, also with an optimizer at hand
+    save(path, m if which == "mae" else types.SimpleNamespace(module=m), 3, args)          # (the fine-tuning formats store a wrapper's .module)
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    assert list(ck) == CHECKPOINT_KEYS[which] and ck["epoch"] == 3
+    assert ck["train_args"] == plain and (which == "mae" or T._plain(args) == plain)
+    for section, mod in parts.items():
+        assert list(ck[section]) == list(mod.state_dict()) and all(torch.equal(ck[section][k], v) for k, v in mod.state_dict().items())
+    fresh, fresh_parts = _stand_in(which, 10)
+    flat2 = fresh if which == "mae" else _Flat(fresh)
+    if which == "mae":
+        fresh._offsets, fresh._flat = _Flat(fresh)._offsets, None
+    opt2 = _Opt(_Flat(fresh), 0.0)
+    opt2.model = flat2
+    m0, v0 = opt2.m.clone(), opt2.v.clone()
+    assert "resume" not in load(path, fresh, opt2)
+    assert all(equal(parts[s], fresh_parts[s]) for s in parts) and torch.equal(opt2.m, m0) and torch.equal(opt2.v, v0) and opt2.t == 7
+
+    # with an optimizer: "resume" is the last key, its layout is flat_layout's
+    flat = m if which == "mae" else _Flat(m)
+    if which == "mae":
+        m._offsets = _Flat(m)._offsets
+    opt = _Opt(_Flat(m), 1.0)
+    opt.model = flat
+    save(path, m, 4, args, opt, step=11)
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    assert list(ck) == CHECKPOINT_KEYS[which] + ["resume"] and list(ck["resume"]) == ["m", "v", "t", "lr", "betas", "step", "layout"]
+    assert ck["resume"]["layout"] == T.flat_layout(flat) and ck["resume"]["step"] == 11 and torch.equal(ck["resume"]["m"], opt.m)
+    if which == "mae":          # the moments lie over the model itself, which must be on the device by then
+        with pytest.raises(RuntimeError, match="move the model to the HIP device"):
+            load(path, fresh, opt2)
+    else:
+        opt2.t = 0
+        load(path, fresh, opt2)
+        assert torch.equal(opt2.m, opt.m) and torch.equal(opt2.v, opt.v) and (opt2.t, opt2.lr, opt2.betas) == (7, 3e-4, (0.87, 0.999))
+
+    # a missing required section raises; the two-stage format's optional ones may be None or absent
+    del ck[REQUIRED[which]]
+    torch.save(ck, path)
+    with pytest.raises(KeyError, match=REQUIRED[which]):
+        load(path, fresh)
+    if which == "two_stage":
+        save(path, m, 5, args, fine_tune=False)
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+        assert list(ck) == CHECKPOINT_KEYS[which] and ck["backbone_state_dict"] is None
+        other, other_parts = _stand_in(which, 20)
+        before = {k: v.clone() for k, v in other.rpn_network.backbone.state_dict().items()}
+        load(path, other)
+        assert equal(other_parts["RCNN_dict"], parts["RCNN_dict"]) and equal(other_parts["rpn_state_dict"], parts["rpn_state_dict"])
+        assert all(torch.equal(v, before[k]) for k, v in other.rpn_network.backbone.state_dict().items())
+        del ck["rpn_state_dict"], ck["backbone_state_dict"]
+        torch.save(ck, path)
+        load(path, _stand_in(which, 21)[0])

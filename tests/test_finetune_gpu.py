@@ -8,6 +8,9 @@ swin_t, 64 FPN channels, fp32 compute; FCOS with num_convs=2 and oriented boxes)
   generality             eight steps lower the loss of FCOSOverNeRF, NeRFRegionProposalNetwork and the voxel-semantics head
   resume                 two steps, checkpoint, fresh model and optimizer, third step == three uninterrupted steps within the bound above
   DetectionTrainer.fit   two epochs over three scenes with evaluation and the reference's checkpoint names
+  the epoch loop         the batcher receives dp_epoch_plan's batches, and the trainer's generator is drawn from once per scene in that order and by nothing else
+  DetectionTrainer.resume  one epoch + checkpoint + fresh trainer + one epoch against two uninterrupted epochs: relerr <= 3 * 1e-5 + 4 relerr(U, U'), the
+                         construction of tests/test_voxel_trainer_gpu.py::test_true_resume_continues_where_it_stopped (stochastic depth off, AdamW's eps 1)
 
 relerr over a set of tensors is the LARGEST of the per-tensor tests/_metrics.relerr (max |a - b| / max |b|), so a small tensor is not hidden behind a large one."""
 import functools
@@ -268,3 +271,66 @@ def test_detection_trainer_fit(tmp_path):
         assert sorted(ck) == ["backbone_state_dict", "epoch", "fcos_state_dict", "resume", "train_args"] and ck["train_args"]["batch_size"] == 2
         float(os.path.basename(path)[:-3].split("_")[-1]), float(os.path.basename(path).split("_")[-2])
     tr.flat.check()
+
+
+def test_train_epoch_follows_the_plan_and_draws_scene_by_scene():
+    """the shared epoch loop hands the batcher exactly the batches of dp_epoch_plan, and the trainer's generator ends where a fresh one ends after one
+    draw_detection_augmentation per scene in that order: drawn scene by scene, batch by batch, and nothing else uses the generator"""
+    import random
+    from nerf_mae_amd.data import draw_detection_augmentation
+    from nerf_mae_amd.trainer import DetectionTrainer, dp_epoch_plan
+    seed, scenes = 4, [C.scene(s) for s in (11, 12, 13)]
+    tr = DetectionTrainer(fcos_on_gpu(), scenes, [C.obb_boxes(s) for s in (11, 12, 13)], batch_size=2, num_epochs=1, lr=1e-4, flip_prob=0.5, rotate_prob=0.5,
+                          rot_scale_prob=0.5, log=lambda s: None, seed=seed)
+    seen = C.record_batches(tr, scenes)
+    tr.train_epoch(1)
+    plan = dp_epoch_plan(3, 2, 0, 1, 1, seed)
+    assert seen == plan and [len(ids) for ids in plan] == [2, 1]
+    rng = random.Random(seed + 1000003 * 0)
+    for ids in plan:
+        for _ in ids:
+            draw_detection_augmentation(0.5, 0.5, 0.5, True, rng)
+    assert rng.getstate() == tr._rng.getstate()
+
+
+# ---- DetectionTrainer.resume: the twin of tests/test_voxel_trainer_gpu.py::test_true_resume_continues_where_it_stopped ------------------------------------
+def _resume_trainer(seed=0):
+    from nerf_mae_amd.trainer import DetectionTrainer
+    from tests._voxel_common import no_stochastic_depth
+    m = no_stochastic_depth(C.fcos_model(seed)).cuda().train()
+    tr = DetectionTrainer(m, [C.scene(s) for s in (11, 12)], [C.obb_boxes(s) for s in (11, 12)], batch_size=1, num_epochs=2, lr=LR, weight_decay=WD,
+                          log=lambda s: None)
+    tr.opt.eps = EPS          # 1, as in the step tests: the order noise of fp32 atomics is not blown up to +-lr
+    return tr
+
+
+@functools.lru_cache(maxsize=None)
+def _uninterrupted():
+    """U, U': two epochs without a stop, twice.  Computed once, left unchanged."""
+    runs = []
+    for _ in range(2):
+        tr = _resume_trainer()
+        tr.fit()
+        torch.cuda.synchronize()
+        runs.append(tr.flat._flat.detach().cpu().clone())
+    return runs
+
+
+def test_detection_trainer_resume_continues_where_it_stopped(tmp_path):
+    """one epoch + checkpoint + fresh trainer + resume() + one epoch against two uninterrupted epochs: relerr <= 3 * 1e-5 + 4 relerr(U, U')"""
+    from nerf_mae_amd.trainer import save_detection_checkpoint
+    u, u2 = _uninterrupted()
+    a = _resume_trainer()
+    a.train_epoch(1)
+    path = str(tmp_path / "epoch_1.pt")
+    save_detection_checkpoint(path, a.model, 1, a.args, a.opt, a.global_step)
+    b = _resume_trainer(seed=9)          # other weights: everything must come from the file
+    ck = b.resume(path)
+    assert ck["resume"]["step"] == 2 and b.global_step == 2 and b.start_epoch == 2 and b.opt.t == 2
+    assert torch.equal(b.opt.m, a.opt.m) and torch.equal(b.opt.v, a.opt.v) and torch.equal(b.flat._flat, a.flat._flat)
+    hist = b.fit()
+    torch.cuda.synchronize()
+    assert [h["epoch"] for h in hist] == [2] and b.global_step == 4
+    err, spread = relerr(b.flat._flat, u), relerr(u2, u)
+    _print(f"  [detection resume] relerr(resumed, uninterrupted) {err:.2e}  relerr(U, U') {spread:.2e}  bound {3 * STEP_BOUND + 4 * spread:.2e}")
+    assert err <= 3 * STEP_BOUND + 4 * spread, (err, spread)

@@ -9,6 +9,7 @@ swin_s base) with stochastic depth off; the SR head has out_resolution=256, so i
   true resume       one epoch + checkpoint + fresh trainer + one epoch against two uninterrupted epochs: relerr <= 3 * 1e-5 + 4 relerr(U, U'), the construction and
                     constants of tests/test_finetune_gpu.py::test_true_resume_continues_where_it_stopped with the uninterrupted run's own spread in the place of
                     the stock path's (there is no stock voxel trainer); AdamW's eps is 1 as there, so the order noise of fp32 atomics is not blown up to +-lr
+  the epoch loop    the batcher receives dp_epoch_plan's batches; the trainer's generator is drawn from once per scene in that order and by nothing else
   augmentation on   runs and gives a finite loss (the reference cannot run this configuration: nothing to compare with)
   two ranks         on one GPU over gloo: bit-equal parameters, files and evaluation on rank 0 only
 
@@ -274,3 +275,22 @@ def test_voxel_trainer_fit_on_two_ranks(tmp_path):
         assert all(h0[k] == h1[k] for k in SEM_KEYS[:3]), (h0, h1)
     assert os.listdir(tmp_path / "rank0") == ["model_best.pt"]
     assert not os.path.exists(tmp_path / "rank1") or not os.listdir(tmp_path / "rank1")
+
+
+def test_train_epoch_follows_the_plan_and_draws_scene_by_scene():
+    """the voxel twin of tests/test_finetune_gpu.py's test of the same name: the batches are dp_epoch_plan's, one draw_augmentation per scene in that order"""
+    import random
+    from nerf_mae_amd.data import draw_augmentation
+    from nerf_mae_amd.trainer import VoxelTrainer, dp_epoch_plan
+    seed, scenes = 4, [C.scene(s) for s in (11, 12, 13)]
+    tr = VoxelTrainer(V.semantics_model(), scenes, [V.label_volume(s) for s in (11, 12, 13)], batch_size=2, num_epochs=1, lr=1e-3, flip_prob=0.5,
+                      rotate_prob=0.5, log=lambda s: None, seed=seed)
+    seen = C.record_batches(tr, scenes)
+    tr.train_epoch(1)
+    plan = dp_epoch_plan(3, 2, 0, 1, 1, seed)
+    assert seen == plan and [len(ids) for ids in plan] == [2, 1]
+    rng = random.Random(seed + 1000003 * 0)
+    for ids in plan:
+        for _ in ids:
+            draw_augmentation(0.5, 0.5, rng)
+    assert rng.getstate() == tr._rng.getstate()
