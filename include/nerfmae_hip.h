@@ -521,6 +521,16 @@ NMH_API int nmh_rpn_sample(int N, int64_t n, const float* labels, int batch, int
  * written, exactly 0 where flag == 0; NULL g = zero. */
 NMH_API int nmh_rpn_loss_fwd(int nlevels, const int* level_dims, int N, int ncols, const float* const* objectness, const float* const* regression, const unsigned char* flags, const float* targets, float* partials, float* scalars, void* stream);
 NMH_API int nmh_rpn_loss_bwd(int nlevels, const int* level_dims, int N, int ncols, const float* const* objectness, const float* const* regression, const unsigned char* flags, const float* targets, const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj, float* const* dreg, void* stream);
+/* The IoU-type box regression losses of the oriented RPN: RotatedIOULoss over the decoded proposals (nerf_rpn/model/rpn.py:133-164, 400-417) with
+ * MidpointOffsetCoder.decode_single / delta_sp2bbox (coder/midpoint_offset_coder.py:160-223) and rectpoly2obb / regular_obb (coder/misc.py:5-43), differentiated
+ * by hand.  ncols must be 8; loss_type 0 iou, 1 linear_iou, 2 giou, 3 diou; else -4.  boxes DEVICE [box_offsets[N]][7] (may be NULL without boxes), box_offsets
+ * HOST int [N+1], ori_sizes DEVICE int [N][3] or NULL and matched_idxs DEVICE int [N][n] as in nmh_rpn_assign; partials as in nmh_rpn_loss_fwd.  Only the lanes
+ * with flag == 1 decode: box term (A = the decode of the anchor's 8 deltas, B = box row max(matched, 0) of the scene) -log((inter3d + 1) / (u3d + 1)),
+ * 1 - that ratio, or the GIoU / DIoU loss over the smallest enclosing rectangle.  -> scalars [3] = (the objectness loss of nmh_rpn_loss_fwd, same bits;
+ * sum of the box terms / #(flags != 0); #(flags != 0)).  A flagged positive in a scene without boxes or in the padding contributes 0.  _bwd: as
+ * nmh_rpn_loss_bwd; dreg is exactly 0 where flag != 1. */
+NMH_API int nmh_rpn_iou_loss_fwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int loss_type, const float* const* objectness, const float* const* regression, const unsigned char* flags, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, float* partials, float* scalars, void* stream);
+NMH_API int nmh_rpn_iou_loss_bwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int loss_type, const float* const* objectness, const float* const* regression, const unsigned char* flags, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj, float* const* dreg, void* stream);
 /* ---- RPN proposals (csrc/rpn_post.hip; semantics, the stated tie, order and NaN rules and the slot layout are in that file's header) ----
  * The inference half of RegionProposalNetwork.forward (nerf_rpn/model/rpn.py:292-370, 507-512): box_coder.decode_list, _get_top_n_idx and filter_proposals over
  * clip_boxes_to_mesh, remove_small_boxes and batched_nms (model/utils.py).  level_dims, base_half and the level tables as for the entries above.  pre_nms_top_n >= 1;

@@ -721,6 +721,21 @@ int nmh_rpn_loss_bwd(int nlevels, const int* level_dims, int N, int ncols, const
   REQ(level_dims, objectness, regression, flags, targets, scalars, dobj, dreg);
   return k_rpn_loss_bwd(nlevels, level_dims, N, ncols, objectness, regression, flags, targets, scalars, g_obj, g_reg, dobj, dreg, ST);
 }
+int nmh_rpn_iou_loss_fwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int loss_type, const float* const* objectness, const float* const* regression,
+                         const unsigned char* flags, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, float* partials, float* scalars,
+                         void* stream) {
+  CLR();
+  REQ(level_dims, base_half, objectness, regression, flags, box_offsets, matched_idxs, partials, scalars);
+  return k_rpn_iou_loss_fwd(nlevels, level_dims, base_half, N, ncols, loss_type, objectness, regression, flags, boxes, box_offsets, ori_sizes, matched_idxs, partials, scalars, ST);
+}
+int nmh_rpn_iou_loss_bwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int loss_type, const float* const* objectness, const float* const* regression,
+                         const unsigned char* flags, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* scalars, const float* g_obj,
+                         const float* g_reg, float* const* dobj, float* const* dreg, void* stream) {
+  CLR();
+  REQ(level_dims, base_half, objectness, regression, flags, box_offsets, matched_idxs, scalars, dobj, dreg);
+  return k_rpn_iou_loss_bwd(nlevels, level_dims, base_half, N, ncols, loss_type, objectness, regression, flags, boxes, box_offsets, ori_sizes, matched_idxs, scalars, g_obj, g_reg, dobj,
+                            dreg, ST);
+}
 int64_t nmh_rpn_post_cap(int nlevels, const int* level_dims, int N, int pre_nms_top_n) { return level_dims ? k_rpn_post_cap(nlevels, level_dims, N, pre_nms_top_n) : -1; }
 int64_t nmh_rpn_post_mask_words(int nlevels, const int* level_dims, int N, int pre_nms_top_n) { return level_dims ? k_rpn_post_mask_words(nlevels, level_dims, N, pre_nms_top_n) : -1; }
 int nmh_rpn_decode(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, const float* const* regression, float* boxes, void* stream) {

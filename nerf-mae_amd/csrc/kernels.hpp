@@ -324,6 +324,12 @@ int k_rpn_loss_fwd(int nlevels, const int* dims, int N, int ncols, const float* 
                    float* scalars, hipStream_t st);
 int k_rpn_loss_bwd(int nlevels, const int* dims, int N, int ncols, const float* const* obj, const float* const* reg, const unsigned char* flags, const float* targets,
                    const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj, float* const* dreg, hipStream_t st);
+// the IoU-type box losses over the decoded proposals (ncols 8 only; loss_type 0 iou, 1 linear_iou, 2 giou, 3 diou); boxes: DEVICE [offs[N]][7]; midx: DEVICE [N][n]
+int k_rpn_iou_loss_fwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
+                       const float* boxes, const int* offs, const int* ori, const int* midx, float* partials, float* scalars, hipStream_t st);
+int k_rpn_iou_loss_bwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
+                       const float* boxes, const int* offs, const int* ori, const int* midx, const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj,
+                       float* const* dreg, hipStream_t st);
 // ---- rpn_post.hip (RPN proposals: decode, exact top-k per level on the raw logits, per-level NMS, post-NMS cut) ----
 // mesh: HOST [3]; ori: DEVICE [N][3] or NULL.  Slot layout, sort key and tie rules: rpn_post.hip.
 long k_rpn_post_cap(int nlevels, const int* dims, int N, int pre_top_n);

@@ -33,12 +33,21 @@
 //   objectness = sum over flags != 0 of bce_with_logits(x, flag == 1) / s;  box_reg = sum over flags == 1 and c of smooth_l1(pred - target; 1/9) / s;
 //   both 0 when s == 0 (the reference gives NaN there).  Forward: per-workgroup partial sums, then a fixed-order pass of one workgroup.  Backward: one
 //   pass that writes every element of both gradients, exactly 0 where flag == 0.
+// IoU-type box losses (rpn_iou_loss: RotatedIOULoss over the decoded proposals, rpn.py:133-164, 214-217, 400-417, 518-520; 8 columns only).  The same
+//   lane map, sums and objectness; the box term of a lane with flag == 1 is taken between A = rpn_decode_obb(its 8 deltas, its anchor) and B = the scene's
+//   box row max(matched_idxs, 0), both (x, y, z, w, l, h, theta):  iou -log((inter3d + 1) / (u3d + 1)), linear_iou 1 - that ratio, giou / diou
+//   obb_pair_loss<OBB_GIOU_SMALLEST | OBB_DIOU_SMALLEST> (obb_geom.hpp), summed and divided by s.  Only flagged positives decode (the reference decodes
+//   every anchor and reads the sampled ones): a wave without one skips the geometry.  A flagged positive whose scene has no box row for it, or that
+//   lies in the padding (either is possible only with flags that the sampler did not draw), contributes 0 and has zero box gradient.  Backward:
+//   g_reg / s through obb_pair_grad (box A only) and rpn_decode_obb_bwd (rpn_decode.hpp); every element of both gradients is written, dreg exactly 0
+//   where flag != 1.
 #include "common.hpp"
 #include "kernels.hpp"
 #include "select_scan.hpp"
 #include "reduce_fixed.hpp"
 #include "rpn_geom.hpp"
 #include "rpn_shared.hpp"
+#include "rpn_decode.hpp"
 
 namespace {
 
@@ -309,6 +318,116 @@ __global__ __launch_bounds__(256) void rpn_loss_bwd_kernel(RpnGeom G, Ptr4<const
   for (int k = 0; k < C; ++k) dp[(long)k * w.nloc] = gr[k];
 }
 
+// ---- IoU-type box losses (oriented only) ---------------------------------------------------------------------------------------------------
+// the box term of one flagged positive and its gradient over the 8 deltas: A = the decode of the anchor's deltas, B = the matched box row
+template <int MODE>
+__device__ __forceinline__ float rpn_iou_term(const float (&r)[8], const Box6& a, const float* __restrict__ b, int linear) {
+  float o[7];
+  rpn_decode_obb(r, a, o);
+  const Obb A = obb_load(o), B = obb_load(b);
+  const PairOut p = obb_pair(A, B);
+  if (MODE == OBB_IOU) {
+    const float q = (p.inter3d + 1.f) / (p.u3d + 1.f);
+    return linear ? 1.f - q : -logf(q);
+  }
+  float X[8], Y[8];
+  obb_corners(A, X, Y, 0);
+  obb_corners(B, X, Y, 4);
+  Encl E;
+  return obb_pair_loss<MODE>(A, B, p, X, Y, E);
+}
+template <int MODE>
+__device__ __forceinline__ void rpn_iou_term_grad(const float (&r)[8], const Box6& a, const float* __restrict__ b, int linear, float (&gr)[8]) {
+  float o[7];
+  rpn_decode_obb(r, a, o);
+  const Obb A = obb_load(o), B = obb_load(b);
+  BoxGrad ga, gb;
+  if (MODE == OBB_IOU) {
+    const PairOut p = obb_pair(A, B);
+    const float u1 = p.u3d + 1.f, q = (p.inter3d + 1.f) / u1, gq = linear ? -1.f : -1.f / q;
+    obb_pair_grad<OBB_IOU>(A, B, gq * p.u3d / u1, gq * (p.iou - 1.f) / (u1 * u1), 0.f, false, ga, gb);
+  } else {
+    obb_pair_grad<MODE>(A, B, 0.f, 0.f, 1.f, false, ga, gb);
+  }
+  rpn_decode_obb_bwd(r, a, ga, gr);
+}
+
+// what a flagged positive needs beyond its head values: its anchor, and its box row (NULL: it contributes nothing)
+__device__ __forceinline__ const float* rpn_iou_pair(const RpnGeom& G, const float* __restrict__ sh_base, const RpnOffs& S, const RHead& w, const float* __restrict__ boxes,
+                                                     const int* __restrict__ ori, const int* __restrict__ midx, Box6& a) {
+  bool valid;
+  a = rpn_anchor(G, sh_base, ori, RAt{w.lvl, w.scene, w.loc * w.A + w.a, true}, valid);
+  const int g0 = S.off[w.scene], g1 = S.off[w.scene + 1], row = g0 + max(midx[w.p], 0);
+  return valid && row < g1 ? boxes + (long)row * 7 : nullptr;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void rpn_iou_loss_fwd_kernel(RpnGeom G, RpnBase B, RpnOffs S, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
+                                                               const float* __restrict__ boxes, const int* __restrict__ ori, const int* __restrict__ midx, int linear,
+                                                               float* __restrict__ partials) {
+  __shared__ float sh_base[RPN_MAX_A * 3];
+  const RHead w = rpn_head_where(G);
+  rpn_stage_base(B, w.lvl, w.A, sh_base);
+  __syncthreads();
+  float v[3] = {0.f, 0.f, 0.f};         // objectness, box regression, sampled anchors
+  const int f = w.active ? flags[w.p] : 0;
+  if (f != 0) {
+    const float x = pick4(obj.p, w.lvl)[(long)w.scene * w.A * w.nloc + w.j];
+    v[0] = fmaxf(x, 0.f) - (f == 1 ? x : 0.f) + log1pf(expf(-fabsf(x)));
+    v[2] = 1.f;
+    if (f == 1) {                       // a wave without a flagged positive skips this
+      Box6 a;
+      const float* __restrict__ b = rpn_iou_pair(G, sh_base, S, w, boxes, ori, midx, a);
+      if (b) {
+        const float* __restrict__ rp = pick4(reg.p, w.lvl) + ((long)w.scene * w.A + w.a) * 8 * w.nloc + w.loc;
+        float r[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) r[k] = rp[(long)k * w.nloc];
+        v[1] = rpn_iou_term<MODE>(r, a, b, linear);
+      }
+    }
+  }
+  block_sum_fixed(v, partials + 3 * (long)blockIdx.x);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void rpn_iou_loss_bwd_kernel(RpnGeom G, RpnBase B, RpnOffs S, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
+                                                               const float* __restrict__ boxes, const int* __restrict__ ori, const int* __restrict__ midx, int linear,
+                                                               const float* __restrict__ scalars, const float* __restrict__ g_obj, const float* __restrict__ g_reg,
+                                                               Ptr4<float> dobj, Ptr4<float> dreg) {
+  __shared__ float sh_base[RPN_MAX_A * 3];
+  const RHead w = rpn_head_where(G);
+  rpn_stage_base(B, w.lvl, w.A, sh_base);
+  __syncthreads();
+  if (!w.active) return;
+  const long at = (long)w.scene * w.A * w.nloc + w.j, rat = ((long)w.scene * w.A + w.a) * 8 * w.nloc + w.loc;
+  const int f = flags[w.p];
+  const float cnt = scalars[2];
+  float go = 0.f, gr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (f != 0 && cnt > 0.f) {
+    const float x = pick4(obj.p, w.lvl)[at];
+    go = (sigmoid_stable(x) - (f == 1 ? 1.f : 0.f)) * (g_obj ? g_obj[0] : 0.f) / cnt;
+    if (f == 1) {                       // a wave without a flagged positive skips this
+      Box6 a;
+      const float* __restrict__ b = rpn_iou_pair(G, sh_base, S, w, boxes, ori, midx, a);
+      if (b) {
+        const float* __restrict__ rp = pick4(reg.p, w.lvl) + rat;
+        const float sc = (g_reg ? g_reg[0] : 0.f) / cnt;
+        float r[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) r[k] = rp[(long)k * w.nloc];
+        rpn_iou_term_grad<MODE>(r, a, b, linear, gr);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) gr[k] *= sc;
+      }
+    }
+  }
+  pick4(dobj.p, w.lvl)[at] = go;
+  float* __restrict__ dp = pick4(dreg.p, w.lvl) + rat;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) dp[(long)k * w.nloc] = gr[k];
+}
+
 }  // namespace
 
 long k_rpn_num_blocks(int nlevels, const int* dims, int N) {
@@ -369,6 +488,52 @@ int k_rpn_loss_bwd(int nlevels, const int* dims, int N, int ncols, const float* 
   const Ptr4<float> DO = make_ptrs<float>(nlevels, dobj), DR = make_ptrs<float>(nlevels, dreg);
   if (ncols == 8) hipLaunchKernelGGL(rpn_loss_bwd_kernel<8>, dim3(G.nblocks), dim3(256), 0, st, G, O, R, flags, targets, scalars, g_obj, g_reg, DO, DR);
   else hipLaunchKernelGGL(rpn_loss_bwd_kernel<6>, dim3(G.nblocks), dim3(256), 0, st, G, O, R, flags, targets, scalars, g_obj, g_reg, DO, DR);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
+
+namespace {
+// the arguments the two IoU-loss entries share; loss_type: 0 iou, 1 linear_iou, 2 giou, 3 diou
+int make_iou_args(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* boxes, const int* offs, const int* midx, RpnGeom& G, RpnBase& B,
+                  RpnOffs& S) {
+  if (make_geom(nlevels, dims, N, G) || make_base(nlevels, dims, base, B) || ncols != 8 || loss_type < 0 || loss_type > 3 || !offs || offs[0] != 0 || !midx) return -4;
+  for (int b = 0; b < N; ++b) if (offs[b + 1] < offs[b]) return -4;
+  for (int b = 0; b <= NMH_FCOS_MAX_SCENES; ++b) S.off[b] = offs[b < N ? b : N];
+  return offs[N] > 0 && !boxes ? -4 : 0;
+}
+}  // namespace
+
+int k_rpn_iou_loss_fwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
+                       const float* boxes, const int* offs, const int* ori, const int* midx, float* partials, float* scalars, hipStream_t st) {
+  RpnGeom G;
+  RpnBase B;
+  RpnOffs S;
+  if (make_iou_args(nlevels, dims, base, N, ncols, loss_type, boxes, offs, midx, G, B, S) || !all_set(nlevels, obj) || !all_set(nlevels, reg)) return -4;
+  const Ptr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
+  const int linear = loss_type == 1;
+  if (loss_type <= 1) hipLaunchKernelGGL(rpn_iou_loss_fwd_kernel<OBB_IOU>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, partials);
+  else if (loss_type == 2) hipLaunchKernelGGL(rpn_iou_loss_fwd_kernel<OBB_GIOU_SMALLEST>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, partials);
+  else hipLaunchKernelGGL(rpn_iou_loss_fwd_kernel<OBB_DIOU_SMALLEST>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, partials);
+  NMH_CHECK_LAUNCH();
+  hipLaunchKernelGGL(rpn_loss_final_kernel, dim3(1), dim3(256), 0, st, partials, G.nblocks, scalars);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
+
+int k_rpn_iou_loss_bwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
+                       const float* boxes, const int* offs, const int* ori, const int* midx, const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj,
+                       float* const* dreg, hipStream_t st) {
+  RpnGeom G;
+  RpnBase B;
+  RpnOffs S;
+  if (make_iou_args(nlevels, dims, base, N, ncols, loss_type, boxes, offs, midx, G, B, S) || !all_set(nlevels, obj) || !all_set(nlevels, reg) || !all_set(nlevels, dobj) ||
+      !all_set(nlevels, dreg)) return -4;
+  const Ptr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
+  const Ptr4<float> DO = make_ptrs<float>(nlevels, dobj), DR = make_ptrs<float>(nlevels, dreg);
+  const int linear = loss_type == 1;
+  if (loss_type <= 1) hipLaunchKernelGGL(rpn_iou_loss_bwd_kernel<OBB_IOU>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, scalars, g_obj, g_reg, DO, DR);
+  else if (loss_type == 2) hipLaunchKernelGGL(rpn_iou_loss_bwd_kernel<OBB_GIOU_SMALLEST>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, scalars, g_obj, g_reg, DO, DR);
+  else hipLaunchKernelGGL(rpn_iou_loss_bwd_kernel<OBB_DIOU_SMALLEST>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, scalars, g_obj, g_reg, DO, DR);
   NMH_CHECK_LAUNCH();
   return 0;
 }

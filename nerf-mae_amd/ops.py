@@ -1839,6 +1839,35 @@ def rpn_loss_bwd(plan, C, obj, reg, flags, targets, scalars, g_obj, g_reg):
     return dobj, dreg
 
 
+def _rpn_iou_args(plan, loss_type, boxes, offsets, ori_sizes, midx):
+    if loss_type not in FCOS_LOSS_TYPES:
+        raise ValueError(f"RPN IoU loss: reg_loss_type must be one of {sorted(FCOS_LOSS_TYPES)}, got {loss_type!r}")
+    _chk(boxes, ori_sizes, midx)
+    offs = (ctypes.c_int * (plan.N + 1))(*offsets)
+    return FCOS_LOSS_TYPES[loss_type], boxes if boxes.numel() else None, offs
+
+
+def rpn_iou_loss_fwd(plan, loss_type, obj, reg, flags, boxes, offsets, ori_sizes, midx):
+    """the IoU-type box loss of the oriented RPN over the decoded proposals; loss_type: a key of FCOS_LOSS_TYPES; boxes [G,7], offsets host ints [N+1],
+    ori_sizes int32 [N,3] or None, midx [N,n] int32 as rpn_assign takes and returns them -> scalars [3] = (objectness loss, box loss, number of sampled anchors)"""
+    lt, boxes, offs = _rpn_iou_args(plan, loss_type, boxes, offsets, ori_sizes, midx)
+    dev = flags.device
+    partials = torch.empty((3 * plan.nblocks,), dtype=torch.float32, device=dev)
+    scalars = torch.empty((3,), dtype=torch.float32, device=dev)
+    lib().call("nmh_rpn_iou_loss_fwd", plan.L, plan.dims, plan.base, plan.N, 8, lt, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, boxes, offs, ori_sizes, midx, partials,
+               scalars, _st())
+    return scalars
+
+
+def rpn_iou_loss_bwd(plan, loss_type, obj, reg, flags, boxes, offsets, ori_sizes, midx, scalars, g_obj, g_reg, out=None):
+    """-> (dobj, dreg) per level; out: the pair of per-level lists to write instead of fresh tensors (every element is written)"""
+    lt, boxes, offs = _rpn_iou_args(plan, loss_type, boxes, offsets, ori_sizes, midx)
+    dobj, dreg = out if out is not None else ([torch.empty_like(t) for t in obj], [torch.empty_like(t) for t in reg])
+    lib().call("nmh_rpn_iou_loss_bwd", plan.L, plan.dims, plan.base, plan.N, 8, lt, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, boxes, offs, ori_sizes, midx, scalars,
+               g_obj, g_reg, _ptr_table(dobj, plan.L), _ptr_table(dreg, plan.L), _st())
+    return dobj, dreg
+
+
 # ---- RPN proposals: decode, top-k per level, per-level NMS, post-NMS cut (csrc/rpn_post.hip) --------------------------------------------------
 class RpnPostPlan:
     """RpnPlan + pre_nms_top_n -> what the selection adds to the level table: t_k = min(pre_nms_top_n, n_k) kept per level, the level's first slot,

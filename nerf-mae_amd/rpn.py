@@ -5,7 +5,9 @@ the reference's names (the import swap is one line):
   rpn_assign_targets           RegionProposalNetwork.assign_targets_to_anchors + box_coder.encode (model/rpn.py:240-290, 524) over Matcher
                                (model/utils.py:98-211) and AABBCoder / MidpointOffsetCoder.encode_single (model/coder/)
   rpn_sample                   BalancedPositiveNegativeSampler (model/utils.py:35-95)
-  RPNLossComputation           RegionProposalNetwork.compute_loss and the training half of forward (model/rpn.py:372-419, 514-534)
+  RPNLossComputation           RegionProposalNetwork.compute_loss and the training half of forward (model/rpn.py:372-419, 514-534), reg_loss_type "smooth_l1"
+  RPNIoULossComputation        the same with reg_loss_type "iou" | "linear_iou" | "giou" | "diou": RotatedIOULoss over the decoded proposals of the sampled
+                               positives (model/rpn.py:133-164, 214-217, 400-417, 518-520), oriented boxes only
   rpn_decode_proposals         box_coder.decode_list (model/coder/base_bbox_coder.py:55-86) over AABBCoder / MidpointOffsetCoder.decode_single
   rpn_proposals_dense          _get_top_n_idx + filter_proposals (model/rpn.py:292-370) with fixed-size results and no host synchronisation, for HIP graphs
   RPNProposalFilter            the inference half of forward (model/rpn.py:507-512): per-scene lists (boxes, level_indexes, scores)
@@ -33,7 +35,12 @@ Stated deviations from the reference, training path:
   - equal IoU of one anchor with several boxes goes to the lowest box index (torch.max leaves it open);
   - loss_rpn_box_reg_2d is returned as a constant zero without gradient: the reference weights it by --reg_loss_weight_2d, whose default is
     0.0 and which no launcher sets, so the total loss and every gradient are the reference's under its defaults;
-  - reg_loss_type other than "smooth_l1" raises NotImplementedError (the IoU-type losses need the differentiable decode of the proposals);
+  - the IoU-type losses are a class of their own, RPNIoULossComputation, which RegionProposalNetwork builds for rotated_bbox=True and a reg_loss_type other
+    than "smooth_l1"; RPNLossComputation itself raises NotImplementedError for them, and so does either network with rotated_bbox=False (the reference
+    fails there too: its rotated_iou_loss is None).  An unknown reg_loss_type raises ValueError with rotated_bbox=True;
+  - only the sampled positives are decoded for the IoU-type losses (the reference decodes every anchor and reads those); the backward of the decode is
+    written by hand, with the conventions stated at rpn_decode_obb_bwd (csrc/rpn_decode.hpp); a sampled positive in a scene without boxes or in the padding,
+    which only `sampled=` can produce, contributes nothing;
   - a scene without boxes has labels 0 (-1 in the padding) and all-zero targets (the reference takes log(0) there; nothing reads them);
   - without any sampled anchor both losses are 0 with zero gradients (the reference gives NaN);
   - other dtypes than fp32 raise TypeError, CPU tensors RuntimeError, more than 4 levels, 64 scenes or 32 anchors per location ValueError.
@@ -232,17 +239,40 @@ class _RpnLoss(Function):
         return (None, None, None, None, *dobj, *dreg)
 
 
-class RPNLossComputation(object):
-    """The training half of the reference's RegionProposalNetwork.forward on the fused kernels: assignment, sampling and the two losses.
+class _RpnIoULoss(Function):
+    """(plan, loss_type, flags, boxes, offsets, ori, matched_idxs, *objectness levels, *regression levels) -> (loss_objectness, loss_rpn_box_reg)"""
+
+    @staticmethod
+    def forward(ctx, plan, loss_type, flags, boxes, offsets, ori, midx, *heads):
+        heads = [h.contiguous() for h in heads]
+        scalars = ops.rpn_iou_loss_fwd(plan, loss_type, heads[:plan.L], heads[plan.L:], flags, boxes, offsets, ori, midx)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(flags, boxes, midx, scalars, *heads)
+        ctx.cfg = (plan, loss_type, offsets, ori)
+        return scalars[0], scalars[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_obj, g_reg):
+        plan, loss_type, offsets, ori = ctx.cfg
+        flags, boxes, midx, scalars, *heads = ctx.saved_tensors
+        if (g_obj is None and g_reg is None) or not any(ctx.needs_input_grad[7:]):
+            return (None,) * (7 + 2 * plan.L)
+        gs = [g if g is None else g.contiguous() for g in (g_obj, g_reg)]
+        dobj, dreg = ops.rpn_iou_loss_bwd(plan, loss_type, heads[:plan.L], heads[plan.L:], flags, boxes, offsets, ori, midx, scalars, gs[0], gs[1])
+        return (None,) * 7 + (*dobj, *dreg)
+
+
+class _RPNLossBase(object):
+    """What the two loss classes share: the checks, assignment and sampling (one seed draws the same sample in either), and the result's three keys.
     rng_state (int64 device tensor [2] = (seed, counter)) is created on the first call; copy into it to replay a draw."""
 
-    def __init__(self, anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox=False, reg_loss_type="smooth_l1", seed=0):
-        if reg_loss_type != "smooth_l1":
-            raise NotImplementedError(f'reg_loss_type {reg_loss_type!r} is not built; use "smooth_l1" (the IoU-type losses need the differentiable decode of the proposals)')
+    def __init__(self, anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox, reg_loss_type, seed):
+        self.name = type(self).__name__
         if len(anchor_generator.sizes) > MAX_LEVELS:
-            raise ValueError(f"RPNLossComputation supports at most {MAX_LEVELS} levels, got {len(anchor_generator.sizes)}")
+            raise ValueError(f"{self.name} supports at most {MAX_LEVELS} levels, got {len(anchor_generator.sizes)}")
         if bg_iou_thresh > fg_iou_thresh:
-            raise ValueError("RPNLossComputation: bg_iou_thresh must not exceed fg_iou_thresh")
+            raise ValueError(f"{self.name}: bg_iou_thresh must not exceed fg_iou_thresh")
         self.anchor_generator = anchor_generator
         self.fg_iou_thresh, self.bg_iou_thresh = float(fg_iou_thresh), float(bg_iou_thresh)
         self.batch_size_per_mesh, self.positive_fraction = int(batch_size_per_mesh), float(positive_fraction)
@@ -251,11 +281,15 @@ class RPNLossComputation(object):
         self.seed = int(seed)
         self.rng_state = None
 
+    def _losses(self, plan, C, flags, boxes, offsets, ori, matched_idxs, reg_targets, heads):
+        """-> (loss_objectness, loss_rpn_box_reg)"""
+        raise NotImplementedError
+
     def __call__(self, mesh_size, objectness, pred_bbox_deltas, targets, original_mesh_sizes=None, sampled=None):
         """mesh_size (X, Y, Z) of the padded batch; objectness, pred_bbox_deltas: the head's per-level lists; targets: list of N box tensors;
         original_mesh_sizes: the scenes' sizes before padding, used as the reference does, only when N > 1; sampled: flags [N, n] uint8 in place of the
         sampler -> {"loss_objectness", "loss_rpn_box_reg", "loss_rpn_box_reg_2d"}, 0-dim fp32 device tensors"""
-        name = "RPNLossComputation"
+        name = self.name
         L = len(objectness)
         if L > MAX_LEVELS:
             raise ValueError(f"{name} supports at most {MAX_LEVELS} levels, got {L}")
@@ -275,7 +309,7 @@ class RPNLossComputation(object):
                 raise ValueError(f"{name}: per level objectness (N,{A},W,H,D) and pred_bbox_deltas (N,{A * C},W,H,D); got {tuple(o.shape)}, {tuple(r.shape)}")
         boxes, offsets = _boxes(name, targets, ncols)
         ori = _ori(name, original_mesh_sizes if N > 1 else None, N, boxes.device)
-        labels, _, reg_targets = ops.rpn_assign(plan, boxes, offsets, ncols, ori, self.fg_iou_thresh, self.bg_iou_thresh)
+        labels, matched_idxs, reg_targets = ops.rpn_assign(plan, boxes, offsets, ncols, ori, self.fg_iou_thresh, self.bg_iou_thresh)
         if sampled is None:
             if self.rng_state is None:
                 self.rng_state = torch.tensor([self.seed, 0], dtype=torch.int64, device=boxes.device)
@@ -284,8 +318,36 @@ class RPNLossComputation(object):
             if not isinstance(sampled, torch.Tensor) or sampled.dtype != torch.uint8 or tuple(sampled.shape) != (N, plan.n) or not sampled.is_cuda:
                 raise ValueError(f"{name}: sampled must be a uint8 device tensor [N, n] = {(N, plan.n)}")
             flags = sampled.contiguous()
-        loss_obj, loss_reg = _RpnLoss.apply(plan, C, flags, reg_targets, *objectness, *pred_bbox_deltas)
+        loss_obj, loss_reg = self._losses(plan, C, flags, boxes, offsets, ori, matched_idxs, reg_targets, (*objectness, *pred_bbox_deltas))
         return {"loss_objectness": loss_obj, "loss_rpn_box_reg": loss_reg, "loss_rpn_box_reg_2d": torch.zeros((), dtype=torch.float32, device=boxes.device)}
+
+
+class RPNLossComputation(_RPNLossBase):
+    """The training half of the reference's RegionProposalNetwork.forward on the fused kernels: assignment, sampling, the objectness loss and the
+    smooth-L1 box loss on the encoded targets."""
+
+    def __init__(self, anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox=False, reg_loss_type="smooth_l1", seed=0):
+        if reg_loss_type != "smooth_l1":
+            raise NotImplementedError(f'RPNLossComputation computes reg_loss_type "smooth_l1" only, got {reg_loss_type!r}; the IoU-type losses of oriented boxes '
+                                      "are RPNIoULossComputation")
+        super().__init__(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox, reg_loss_type, seed)
+
+    def _losses(self, plan, C, flags, boxes, offsets, ori, matched_idxs, reg_targets, heads):
+        return _RpnLoss.apply(plan, C, flags, reg_targets, *heads)
+
+
+class RPNIoULossComputation(_RPNLossBase):
+    """The same training half with the reference's IoU-type box losses (run_rpn.py --rotated_bbox --reg_loss_type iou | linear_iou | giou | diou): the box
+    term is RotatedIOULoss between the decoded proposal of every sampled positive and its matched box, differentiated through the decode (csrc/rpn.hip, IoU-type
+    box losses).  Always oriented: 8 regression columns, [k, 7] boxes.  Same call, same keys, same sampler as RPNLossComputation."""
+
+    def __init__(self, anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, reg_loss_type="iou", seed=0):
+        if reg_loss_type not in ops.FCOS_LOSS_TYPES:
+            raise ValueError(f"RPNIoULossComputation: reg_loss_type must be one of {sorted(ops.FCOS_LOSS_TYPES)}, got {reg_loss_type!r}")
+        super().__init__(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, True, reg_loss_type, seed)
+
+    def _losses(self, plan, C, flags, boxes, offsets, ori, matched_idxs, reg_targets, heads):
+        return _RpnIoULoss.apply(plan, self.reg_loss_type, flags, boxes, offsets, ori, matched_idxs, *heads)
 
 
 # ---- inference path --------------------------------------------------------------------------------------------------------------------------
@@ -489,7 +551,10 @@ class RegionProposalNetwork(nn.Module):
         self.score_thresh = score_thresh
         self.reg_loss_type = reg_loss_type
         self.min_size = 1e-3
-        self.loss = RPNLossComputation(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox, reg_loss_type)
+        if rotated_bbox and reg_loss_type != "smooth_l1":
+            self.loss = RPNIoULossComputation(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, reg_loss_type)
+        else:           # an IoU type without rotated_bbox raises NotImplementedError here: the reference has no such loss either (its rotated_iou_loss is None)
+            self.loss = RPNLossComputation(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox, reg_loss_type)
         self.filters = {mode: RPNProposalFilter(anchor_generator, pre_nms_top_n[mode], post_nms_top_n[mode], nms_thresh, score_thresh, rotated_bbox)
                         for mode in ("training", "testing")}
 

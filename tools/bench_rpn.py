@@ -8,7 +8,12 @@ Timed with HIP events, median and minimum of `reps` >= 20 calls after 5 warm-up 
   composition  the steps of the semantics (csrc/rpn.hip) from framework ops, as the reference composes them: head tensors permuted and concatenated,
                the box x anchor IoU matrix in slices of 16 boxes, two maxima, the equality scan for the restore, boolean-mask writes, the encode, randperm
                sampling, gathered losses, autograd backward.  Written here from the semantics; it lives in this tool, not in the product.
-The composition and the fused op are also compared: the same labels, and, for the fused op's sampled set, losses that agree to 1e-4."""
+The composition and the fused op are also compared: the same labels, and, for the fused op's sampled set, losses that agree to 1e-4.
+
+    python tools/bench_rpn.py iou [reps]      (these rows alone; without "iou" they follow the lines above)
+The IoU-type box losses of the oriented RPN, loss forward + backward alone on a given sampled set: each of iou, linear_iou, giou, diou through the fused
+kernels, the smooth-L1 path on the same inputs, and a composition of each IoU type from framework ops (nonzero of the flags, gather, the decode in
+autograd, nerf_mae_amd.rotated_iou.cal_*_3d, backward), whose losses must agree with the fused ones to 1e-4."""
 import os
 import statistics
 import sys
@@ -161,5 +166,92 @@ def main(reps=20):
             print(f"  {name} run {run}: " + " | ".join(f"{k} median {m:9.1f} us  min {b:9.1f} us" for k, (m, b) in t.items()))
 
 
+def decode_obb(d, anc):
+    """MidpointOffsetCoder.decode_single from framework ops (the semantics of csrc/rpn_decode.hpp), differentiable: d [P, 8], anc [P, 6] -> [P, 7]"""
+    clip, pi = abs(float(np.log(16 / 1000))), 3.141592
+    p, e = (anc[:, :3] + anc[:, 3:]) * 0.5, anc[:, 3:] - anc[:, :3]
+    g, c = e * torch.exp(d[:, 3:6].clamp(-clip, clip)), p + e * d[:, :3]
+    gx, gy, gw, gh = c[:, 0], c[:, 1], g[:, 0], g[:, 1]
+    da, db = d[:, 6].clamp(-0.5, 0.5), d[:, 7].clamp(-0.5, 0.5)
+    X = torch.stack([da * gw, gw * 0.5, -da * gw, -gw * 0.5], 1)
+    Y = torch.stack([-gh * 0.5, db * gh, gh * 0.5, -db * gh], 1)
+    ln = torch.sqrt(X * X + Y * Y)
+    s = ln.max(1, keepdim=True).values / ln
+    X, Y = X * s + gx[:, None], Y * s + gy[:, None]
+    th = torch.atan2(-(Y[:, 1] - Y[:, 0]), X[:, 1] - X[:, 0] + 1e-7)
+    cs, sn = torch.cos(th), torch.sin(th)
+    x, y = X.sum(1) / 4, Y.sum(1) / 4
+    ux, uy = X - x[:, None], Y - y[:, None]
+    rx, ry = ux * cs[:, None] - uy * sn[:, None], ux * sn[:, None] + uy * cs[:, None]
+    w, h = rx.max(1).values - rx.min(1).values, ry.max(1).values - ry.min(1).values
+    keep = w > h
+    t = torch.where(keep, th, th + pi / 2) + pi / 2
+    return torch.stack([x, y, c[:, 2], torch.where(keep, w, h), torch.where(keep, h, w), g[:, 2], torch.remainder(t, pi) - pi / 2], 1)
+
+
+def iou_composition(anchors, boxes, offsets, midx, obj, reg, flags, loss_type):
+    """the IoU-type box loss from framework ops and the project's paired-box op: nonzero of the flags (one wait for the host), gather, the decode in
+    autograd, rotated_iou.cal_*_3d, the objectness loss, backward -> (loss_objectness, loss_rpn_box_reg)"""
+    from nerf_mae_amd import rotated_iou
+    N, n = flags.shape
+    o = torch.cat([t.permute(0, 2, 3, 4, 1).reshape(N, -1) for t in obj], 1).reshape(-1)
+    r = torch.cat([t.view(N, -1, 8, *t.shape[2:]).permute(0, 3, 4, 5, 1, 2).reshape(N, -1, 8) for t in reg], 1).reshape(-1, 8)
+    f = flags.reshape(-1)
+    pos, sampled = torch.nonzero(f == 1)[:, 0], torch.nonzero(f != 0)[:, 0]
+    rows = offsets[pos // n] + midx.reshape(-1)[pos].clamp(min=0).long()
+    A, B = decode_obb(r[pos], anchors[pos % n])[None], boxes[rows][None]
+    if loss_type in ("iou", "linear_iou"):
+        iou, _, _, _, u = rotated_iou.cal_iou_3d(A, B, verbose=True)
+        q = (iou * u + 1.0) / (u + 1.0)
+        terms = -torch.log(q) if loss_type == "iou" else 1.0 - q
+    elif loss_type == "giou":
+        terms = rotated_iou.cal_giou_3d(A, B)[0]
+    else:
+        terms = rotated_iou.cal_diou_3d(A, B)[0]
+    loss_reg = terms.sum() / sampled.numel()
+    loss_obj = F.binary_cross_entropy_with_logits(o[sampled], (f[sampled] == 1).float())
+    torch.autograd.grad(loss_obj + loss_reg, list(obj) + list(reg))
+    return loss_obj.detach(), loss_reg.detach()
+
+
+def iou_rows(reps):
+    """the loss forward + backward alone (assignment and sampling are done once, outside the timed region) on the oriented inputs: the four IoU types, the
+    smooth-L1 path on the same inputs, and the framework composition of each IoU type"""
+    from nerf_mae_amd import ops
+    gen = rpn.AnchorGenerator3D(SIZES, RATIOS)
+    anchors = gen(torch.zeros((1, 1, *MESH)), [torch.zeros((1, 1, *g)) for g in GRIDS])[0][0].cuda()
+    boxes, obj, reg = make_inputs(True)
+    plan = rpn._plan(gen, MESH, GRIDS, SCENES, "bench_rpn")
+    bx, offsets = rpn._boxes("bench_rpn", boxes, 7)
+    labels, midx, targets = ops.rpn_assign(plan, bx, offsets, 7, None, FG, BG)
+    flags, counts = rpn.rpn_sample(labels, BATCH, FRACTION, torch.tensor([1, 0], dtype=torch.int64).cuda())
+    heads = [t.requires_grad_(True) for t in obj] + [t.requires_grad_(True) for t in reg]
+    offs_dev = torch.tensor(offsets[:-1], dtype=torch.int64).cuda()
+
+    def fused(loss_type):
+        if loss_type == "smooth_l1":
+            out = rpn._RpnLoss.apply(plan, 8, flags, targets, *heads)
+        else:
+            out = rpn._RpnIoULoss.apply(plan, loss_type, flags, bx, offsets, None, midx, *heads)
+        torch.autograd.grad(out[0] + out[1], heads)
+        return out
+
+    print(f"IoU-type box losses, forward + backward on given flags: {SCENES} scenes x {anchors.shape[0]} anchors, sampled {counts.tolist()}; {reps} reps, two runs per line")
+    for t in ("smooth_l1",) + tuple(ops.FCOS_LOSS_TYPES):
+        line = {}
+        if t != "smooth_l1":
+            got, want = fused(t), iou_composition(anchors, bx, offs_dev, midx, obj, reg, flags, t)
+            line["agree to 1e-4"] = all(abs(a.item() - b.item()) <= 1e-4 * abs(b.item()) for a, b in zip(got, want))
+        for run in (1, 2):
+            res = {"fused": timed(lambda: fused(t), reps)}
+            if t != "smooth_l1":
+                res["composition"] = timed(lambda: iou_composition(anchors, bx, offs_dev, midx, obj, reg, flags, t), max(5, reps // 4), warm=1)
+            print(f"  {t:10s} run {run}: " + " | ".join(f"{k} median {m:9.1f} us  min {b:9.1f} us" for k, (m, b) in res.items()) + (f" | {line}" if line and run == 1 else ""))
+
+
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 20)
+    if len(sys.argv) > 1 and sys.argv[1] == "iou":
+        iou_rows(max(20, int(sys.argv[2]) if len(sys.argv) > 2 else 20))
+    else:
+        main(int(sys.argv[1]) if len(sys.argv) > 1 else 20)
+        iou_rows(max(20, int(sys.argv[1]) if len(sys.argv) > 1 else 20))
