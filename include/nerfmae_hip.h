@@ -476,6 +476,12 @@ NMH_API int nmh_fcos_focal_bwd(int nlevels, const int* level_dims, int N, const 
  * through the pair geometry and the decode; every element written, exactly 0 where label == 0 or invalid; NULL g = zero. */
 NMH_API int nmh_fcos_pos_fwd(int nlevels, const int* level_dims, int N, int ncols, int loss_type, int add_l1, const float* const* reg, const float* const* ctr, const float* labels, const float* targets, const float* ctr_targets, const unsigned char* valid, const float* scalars, float world, float* partials, float* reg_loss, float* ctr_loss, void* stream);
 NMH_API int nmh_fcos_pos_bwd(int nlevels, const int* level_dims, int N, int ncols, int loss_type, int add_l1, const float* const* reg, const float* const* ctr, const float* labels, const float* targets, const float* ctr_targets, const unsigned char* valid, const float* scalars, float world, const float* g_reg, const float* g_ctr, float* const* dreg, float* const* dctr, void* stream);
+/* The same two losses with the 2-D projection term of compute_2d_projection_loss (fcos/loss.py:447-475, 579-585; csrc/proj2d.hpp): ncols must be 8 and
+ * proj2d_weight >= 0, else -4.  Every valid positive's term gains proj2d_weight T / 160 / 16 before the centerness weight, T between the decodes of its prediction
+ * and of its target at location zero under the four cameras of get_w2cs(160) (the reference's literal, whatever the scene size).  Everything else, the
+ * centerness loss's bits included, as nmh_fcos_pos_fwd / _bwd. */
+NMH_API int nmh_fcos_pos2d_fwd(int nlevels, const int* level_dims, int N, int ncols, int loss_type, int add_l1, float proj2d_weight, const float* const* reg, const float* const* ctr, const float* labels, const float* targets, const float* ctr_targets, const unsigned char* valid, const float* scalars, float world, float* partials, float* reg_loss, float* ctr_loss, void* stream);
+NMH_API int nmh_fcos_pos2d_bwd(int nlevels, const int* level_dims, int N, int ncols, int loss_type, int add_l1, float proj2d_weight, const float* const* reg, const float* const* ctr, const float* labels, const float* targets, const float* ctr_targets, const unsigned char* valid, const float* scalars, float world, const float* g_reg, const float* g_ctr, float* const* dreg, float* const* dctr, void* stream);
 /* encode_fcos_obb / decode_fcos_obb (fcos/utils.py:64-105, 12-61) on their own: locations [n][3], boxes [n][7] -> out [n][8]; locations [n][3],
  * regression [n][8] -> boxes [n][7] (theta by atan2); _bwd: gbox [n][7] -> dregression [n][8] (the locations' gradient is gbox[:, :3]).  n == 0: no launch. */
 NMH_API int nmh_fcos_obb_encode(const float* locations, const float* boxes, int64_t n, float* out, void* stream);
@@ -531,6 +537,25 @@ NMH_API int nmh_rpn_loss_bwd(int nlevels, const int* level_dims, int N, int ncol
  * nmh_rpn_loss_bwd; dreg is exactly 0 where flag != 1. */
 NMH_API int nmh_rpn_iou_loss_fwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int loss_type, const float* const* objectness, const float* const* regression, const unsigned char* flags, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, float* partials, float* scalars, void* stream);
 NMH_API int nmh_rpn_iou_loss_bwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int loss_type, const float* const* objectness, const float* const* regression, const unsigned char* flags, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj, float* const* dreg, void* stream);
+/* The two kinds of loss above with the 2-D projection term, the third return of compute_loss (rpn.py:421-453; csrc/proj2d.hpp).  nmh_rpn_loss2d_*: the
+ * smooth-L1 box loss, ncols 6 (boxes [.][6]) or 8 (boxes [.][7]); nmh_rpn_iou_loss2d_*: the IoU types, ncols 8.  Arguments as in the entries above, and
+ * cams: HOST float [48] = the four cameras as fused 3x4 matrices K [R|t], row-major (nmh_proj2d_cameras(res) gives the reference's); res > 0: the divisor,
+ * max(mesh_size).  partials: DEVICE float workspace [5 nmh_rpn_num_blocks()].  -> scalars DEVICE float [5] = (objectness loss, box loss, #(flags != 0): the
+ * bits of the entries above; sum over flags == 1 of T / P / res, 0 if P == 0; P = #(flags == 1)), T between the unclipped decode of the anchor's deltas and its
+ * box row max(matched, 0).  A flagged positive in a scene without boxes or in the padding counts in P and contributes 0.  _bwd: dobj, dreg =
+ * g_obj[0] d scalars[0] + g_reg[0] d scalars[1] + g_2d[0] d scalars[3], every element written exactly once; NULL g = zero. */
+NMH_API int nmh_rpn_loss2d_fwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, const float* const* objectness, const float* const* regression, const unsigned char* flags, const float* targets, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* cams, float res, float* partials, float* scalars, void* stream);
+NMH_API int nmh_rpn_loss2d_bwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, const float* const* objectness, const float* const* regression, const unsigned char* flags, const float* targets, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* cams, float res, const float* scalars, const float* g_obj, const float* g_reg, const float* g_2d, float* const* dobj, float* const* dreg, void* stream);
+NMH_API int nmh_rpn_iou_loss2d_fwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int loss_type, const float* const* objectness, const float* const* regression, const unsigned char* flags, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* cams, float res, float* partials, float* scalars, void* stream);
+NMH_API int nmh_rpn_iou_loss2d_bwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int loss_type, const float* const* objectness, const float* const* regression, const unsigned char* flags, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* cams, float res, const float* scalars, const float* g_obj, const float* g_reg, const float* g_2d, float* const* dobj, float* const* dreg, void* stream);
+/* ---- The 2-D projection regression term on rows of boxes (csrc/proj2d.hip, csrc/proj2d.hpp) ----
+ * compute_2d_projection_loss of the reference's two detectors (rpn.py:421-453, fcos/loss.py:447-475) before weighting and normalisation.  pred, target DEVICE
+ * [n][ncols], ncols 6 (x0,y0,z0,x1,y1,z1) or 7 (x,y,z,w,l,h,theta), else -4; cams HOST float [48] as above.  -> terms [n]: the sum over four cameras, two
+ * opposite corners and two pixel coordinates of smooth-L1(beta 1/9)(uv_pred - uv_target).  _bwd: dpred [n][ncols] = g_terms[row] d terms[row] / d pred.
+ * n == 0: no launch.  nmh_proj2d_cameras: HOST only, cams [48] = the cameras of get_w2cs(res) (rpn.py:58-85) times K = [[600,0,320],[0,600,240],[0,0,1]]. */
+NMH_API int nmh_proj2d_cameras(float res, float* cams);
+NMH_API int nmh_proj2d_fwd(const float* pred, const float* target, int64_t n, int ncols, const float* cams, float* terms, void* stream);
+NMH_API int nmh_proj2d_bwd(const float* pred, const float* target, const float* g_terms, int64_t n, int ncols, const float* cams, float* dpred, void* stream);
 /* ---- RPN proposals (csrc/rpn_post.hip; semantics, the stated tie, order and NaN rules and the slot layout are in that file's header) ----
  * The inference half of RegionProposalNetwork.forward (nerf_rpn/model/rpn.py:292-370, 507-512): box_coder.decode_list, _get_top_n_idx and filter_proposals over
  * clip_boxes_to_mesh, remove_small_boxes and batched_nms (model/utils.py).  level_dims, base_half and the level tables as for the entries above.  pre_nms_top_n >= 1;

@@ -8,6 +8,7 @@ __version__ = "0.1.0"
 
 _DET_EVAL = ("det_eval_dense", "DetectionEvaluator", "evaluate_box_proposals_recall", "evaluate_box_proposals_ap")
 _SEM_EVAL = ("SemanticEvaluator", "sem_eval_dense", "intersection_and_union", "label_class_counts", "class_weights_from_counts", "calculate_class_weights")
+_PROJ2D = ("proj2d_cameras", "proj2d_points", "proj2d_terms")
 _TWO_STAGE = ("TwoStageDetector", "roi_postprocess_dense", "filter_proposals")
 
 
@@ -22,4 +23,7 @@ def __getattr__(name):
     if name in _TWO_STAGE:     # two-stage detector inference (detector.py), likewise
         from . import detector
         return getattr(detector, name)
+    if name in _PROJ2D:        # the 2-D projection term on rows of boxes (proj2d.py), likewise
+        from . import proj2d
+        return getattr(proj2d, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

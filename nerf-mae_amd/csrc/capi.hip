@@ -660,6 +660,22 @@ int nmh_fcos_pos_bwd(int nlevels, const int* level_dims, int N, int ncols, int l
   REQ(level_dims, reg, ctr, labels, targets, ctr_targets, valid, scalars, dreg, dctr);
   return k_fcos_pos_bwd(nlevels, level_dims, N, ncols, loss_type, add_l1, reg, ctr, labels, targets, ctr_targets, valid, scalars, world, g_reg, g_ctr, dreg, dctr, ST);
 }
+int nmh_fcos_pos2d_fwd(int nlevels, const int* level_dims, int N, int ncols, int loss_type, int add_l1, float proj2d_weight, const float* const* reg, const float* const* ctr,
+                       const float* labels, const float* targets, const float* ctr_targets, const unsigned char* valid, const float* scalars, float world, float* partials,
+                       float* reg_loss, float* ctr_loss, void* stream) {
+  CLR();
+  REQ(level_dims, reg, ctr, labels, targets, ctr_targets, valid, scalars, partials, reg_loss, ctr_loss);
+  if (!(proj2d_weight >= 0.f) || ncols != 8) return -4;
+  return k_fcos_pos2d_fwd(nlevels, level_dims, N, ncols, loss_type, add_l1, proj2d_weight, reg, ctr, labels, targets, ctr_targets, valid, scalars, world, partials, reg_loss, ctr_loss, ST);
+}
+int nmh_fcos_pos2d_bwd(int nlevels, const int* level_dims, int N, int ncols, int loss_type, int add_l1, float proj2d_weight, const float* const* reg, const float* const* ctr,
+                       const float* labels, const float* targets, const float* ctr_targets, const unsigned char* valid, const float* scalars, float world, const float* g_reg,
+                       const float* g_ctr, float* const* dreg, float* const* dctr, void* stream) {
+  CLR();
+  REQ(level_dims, reg, ctr, labels, targets, ctr_targets, valid, scalars, dreg, dctr);
+  if (!(proj2d_weight >= 0.f) || ncols != 8) return -4;
+  return k_fcos_pos2d_bwd(nlevels, level_dims, N, ncols, loss_type, add_l1, proj2d_weight, reg, ctr, labels, targets, ctr_targets, valid, scalars, world, g_reg, g_ctr, dreg, dctr, ST);
+}
 int nmh_fcos_obb_encode(const float* locations, const float* boxes, int64_t n, float* out, void* stream) {
   CLR();
   if (n < 0) return -4;
@@ -735,6 +751,62 @@ int nmh_rpn_iou_loss_bwd(int nlevels, const int* level_dims, const float* base_h
   REQ(level_dims, base_half, objectness, regression, flags, box_offsets, matched_idxs, scalars, dobj, dreg);
   return k_rpn_iou_loss_bwd(nlevels, level_dims, base_half, N, ncols, loss_type, objectness, regression, flags, boxes, box_offsets, ori_sizes, matched_idxs, scalars, g_obj, g_reg, dobj,
                             dreg, ST);
+}
+int nmh_rpn_loss2d_fwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, const float* const* objectness, const float* const* regression,
+                       const unsigned char* flags, const float* targets, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* cams,
+                       float res, float* partials, float* scalars, void* stream) {
+  CLR();
+  REQ(level_dims, base_half, objectness, regression, flags, targets, box_offsets, matched_idxs, cams, partials, scalars);
+  return k_rpn_loss2d_fwd(nlevels, level_dims, base_half, N, ncols, -1, objectness, regression, flags, targets, boxes, box_offsets, ori_sizes, matched_idxs, cams, res, partials, scalars, ST);
+}
+int nmh_rpn_loss2d_bwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, const float* const* objectness, const float* const* regression,
+                       const unsigned char* flags, const float* targets, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* cams,
+                       float res, const float* scalars, const float* g_obj, const float* g_reg, const float* g_2d, float* const* dobj, float* const* dreg, void* stream) {
+  CLR();
+  REQ(level_dims, base_half, objectness, regression, flags, targets, box_offsets, matched_idxs, cams, scalars, dobj, dreg);
+  return k_rpn_loss2d_bwd(nlevels, level_dims, base_half, N, ncols, -1, objectness, regression, flags, targets, boxes, box_offsets, ori_sizes, matched_idxs, cams, res, scalars, g_obj,
+                          g_reg, g_2d, dobj, dreg, ST);
+}
+int nmh_rpn_iou_loss2d_fwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int loss_type, const float* const* objectness, const float* const* regression,
+                           const unsigned char* flags, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* cams, float res,
+                           float* partials, float* scalars, void* stream) {
+  CLR();
+  REQ(level_dims, base_half, objectness, regression, flags, box_offsets, matched_idxs, cams, partials, scalars);
+  if (loss_type < 0) return -4;
+  return k_rpn_loss2d_fwd(nlevels, level_dims, base_half, N, ncols, loss_type, objectness, regression, flags, nullptr, boxes, box_offsets, ori_sizes, matched_idxs, cams, res, partials,
+                          scalars, ST);
+}
+int nmh_rpn_iou_loss2d_bwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int loss_type, const float* const* objectness, const float* const* regression,
+                           const unsigned char* flags, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* cams, float res,
+                           const float* scalars, const float* g_obj, const float* g_reg, const float* g_2d, float* const* dobj, float* const* dreg, void* stream) {
+  CLR();
+  REQ(level_dims, base_half, objectness, regression, flags, box_offsets, matched_idxs, cams, scalars, dobj, dreg);
+  if (loss_type < 0) return -4;
+  return k_rpn_loss2d_bwd(nlevels, level_dims, base_half, N, ncols, loss_type, objectness, regression, flags, nullptr, boxes, box_offsets, ori_sizes, matched_idxs, cams, res, scalars,
+                          g_obj, g_reg, g_2d, dobj, dreg, ST);
+}
+int nmh_proj2d_cameras(float res, float* cams) {
+  CLR();
+  REQ(cams);
+  if (!(res > 0.f)) return -4;
+  k_proj2d_cameras(res, cams);
+  return 0;
+}
+int nmh_proj2d_fwd(const float* pred, const float* target, int64_t n, int ncols, const float* cams, float* terms, void* stream) {
+  CLR();
+  if (n < 0 || (ncols != 6 && ncols != 7)) return -4;
+  REQ(cams);
+  if (n == 0) return 0;
+  REQ(pred, target, terms);
+  return k_proj2d_fwd(pred, target, (long)n, ncols, cams, terms, ST);
+}
+int nmh_proj2d_bwd(const float* pred, const float* target, const float* g_terms, int64_t n, int ncols, const float* cams, float* dpred, void* stream) {
+  CLR();
+  if (n < 0 || (ncols != 6 && ncols != 7)) return -4;
+  REQ(cams);
+  if (n == 0) return 0;
+  REQ(pred, target, g_terms, dpred);
+  return k_proj2d_bwd(pred, target, g_terms, (long)n, ncols, cams, dpred, ST);
 }
 int64_t nmh_rpn_post_cap(int nlevels, const int* level_dims, int N, int pre_nms_top_n) { return level_dims ? k_rpn_post_cap(nlevels, level_dims, N, pre_nms_top_n) : -1; }
 int64_t nmh_rpn_post_mask_words(int nlevels, const int* level_dims, int N, int pre_nms_top_n) { return level_dims ? k_rpn_post_mask_words(nlevels, level_dims, N, pre_nms_top_n) : -1; }

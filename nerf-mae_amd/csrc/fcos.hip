@@ -38,6 +38,9 @@
 //     giou / diou: the "smallest" enclosing forms of obb_geom.hpp.  decode keeps the clamp of vx, vy to the AABB, the 1e-7 in the
 //     normalisation and mid (0,0) -> (1e-7, 0); cos / sin of theta are taken from mid directly.  The gradient goes by hand through the pair
 //     geometry and the decode; clamp passes to the bound it hits, max(d0, d1) splits a tie evenly.  l1 = SmoothL1(beta 1) on columns 6:8.
+//   fcos_pos2d (8 columns only, opt-in): term += proj2d_weight T(A, B) / 160 / 16 with T the 2-D projection term of proj2d.hpp between the same two decoded
+//     boxes under the cameras of get_w2cs(160), whatever the scene size (compute_2d_projection_loss, loss.py:447-475, 579-585: the reference's literal);
+//     its gradient goes through fcos_decode_bwd with the pair geometry's.
 // Backward kernels recompute everything from the inputs and write every element of the gradients: exactly 0 where label == 0 or !valid.
 #include "common.hpp"
 #include "kernels.hpp"
@@ -45,6 +48,7 @@
 #include "fcos_decode.hpp"
 #include "levels4.hpp"
 #include "reduce_fixed.hpp"
+#include "proj2d.hpp"
 
 namespace {
 
@@ -351,9 +355,12 @@ __device__ __forceinline__ void fcos_obb_term_grad(const float (&p)[8], const fl
   fcos_decode_bwd(A, ga, gp);
 }
 
-template <int KIND>
+constexpr float FCOS_2D_RES = 160.f;      // the reference's literal: the cameras and the divisor, whatever the scene size
+struct Fcos2d { Proj2dCams cams; float weight; };        // read only by the kernels with P2D
+
+template <int KIND, bool P2D>
 __global__ __launch_bounds__(256) void fcos_pos_fwd_kernel(FcosGeom G, Ptr4<const float> reg, Ptr4<const float> ctr, const float* __restrict__ labels, const float* __restrict__ targets,
-                                                           const float* __restrict__ ctr_t, const unsigned char* __restrict__ valid, int loss_type, int add_l1,
+                                                           const float* __restrict__ ctr_t, const unsigned char* __restrict__ valid, int loss_type, int add_l1, Fcos2d p2d,
                                                            float* __restrict__ partials) {
   constexpr int C = KIND == FCOS_AABB ? 6 : 8;
   const Where w = fcos_where(G);
@@ -366,6 +373,7 @@ __global__ __launch_bounds__(256) void fcos_pos_fwd_kernel(FcosGeom G, Ptr4<cons
     const float ct = ctr_t[w.p];
     float term = KIND == FCOS_AABB ? fcos_aabb_term<false>(p, t, loss_type, gp) : fcos_obb_term<KIND>(p, t, loss_type);
     if (KIND != FCOS_AABB && add_l1) term += smooth_l1(p[6] - t[6]) + smooth_l1(p[7] - t[7]);
+    if constexpr (P2D) term += p2d.weight * (proj2d_term(fcos_decode(p).o, fcos_decode(t).o, p2d.cams) / FCOS_2D_RES / 16.f);
     v[0] = term * ct;
     const float c = pick4(ctr.p, w.lvl)[(long)w.scene * w.n + w.loc];
     v[1] = fmaxf(c, 0.f) - c * ct + log1pf(expf(-fabsf(c)));
@@ -373,9 +381,9 @@ __global__ __launch_bounds__(256) void fcos_pos_fwd_kernel(FcosGeom G, Ptr4<cons
   block_sum_fixed(v, partials + 2 * (long)blockIdx.x);
 }
 
-template <int KIND>
+template <int KIND, bool P2D>
 __global__ __launch_bounds__(256) void fcos_pos_bwd_kernel(FcosGeom G, Ptr4<const float> reg, Ptr4<const float> ctr, const float* __restrict__ labels, const float* __restrict__ targets,
-                                                           const float* __restrict__ ctr_t, const unsigned char* __restrict__ valid, int loss_type, int add_l1,
+                                                           const float* __restrict__ ctr_t, const unsigned char* __restrict__ valid, int loss_type, int add_l1, Fcos2d p2d,
                                                            const float* __restrict__ scalars, float world, const float* __restrict__ g_reg, const float* __restrict__ g_ctr,
                                                            Ptr4<float> dreg, Ptr4<float> dctr) {
   constexpr int C = KIND == FCOS_AABB ? 6 : 8;
@@ -393,6 +401,16 @@ __global__ __launch_bounds__(256) void fcos_pos_bwd_kernel(FcosGeom G, Ptr4<cons
     if (KIND == FCOS_AABB) fcos_aabb_term<true>(p, t, loss_type, gp);
     else fcos_obb_term_grad<KIND>(p, t, loss_type, gp);
     if (KIND != FCOS_AABB && add_l1) { gp[6] += smooth_l1_grad(p[6] - t[6]); gp[7] += smooth_l1_grad(p[7] - t[7]); }
+    if constexpr (P2D) {
+      const Dec A = fcos_decode(p);
+      BoxGrad g;
+      float g2[8];
+      proj2d_term_grad(A.o, fcos_decode(t).o, p2d.cams, g);
+      fcos_decode_bwd(A, g, g2);
+      const float s2 = p2d.weight / FCOS_2D_RES / 16.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) gp[k] += s2 * g2[k];
+    }
 #pragma unroll
     for (int k = 0; k < 8; ++k) gp[k] *= sr;
     const float c = pick4(ctr.p, w.lvl)[at];
@@ -479,19 +497,30 @@ static int pos_kind(int ncols, int loss_type) {
   return loss_type == 0 || loss_type == 1 ? FCOS_OBB_IOU : (loss_type == 2 ? FCOS_OBB_GIOU : (loss_type == 3 ? FCOS_OBB_DIOU : -1));
 }
 
+// proj2d_weight < 0: the entries without the 2-D term
 int k_fcos_pos_fwd(int nlevels, const int* dims, int N, int ncols, int loss_type, int add_l1, const float* const* reg, const float* const* ctr, const float* labels, const float* targets,
                    const float* ctr_t, const unsigned char* valid, const float* scalars, float world, float* partials, float* reg_loss, float* ctr_loss, hipStream_t st) {
+  return k_fcos_pos2d_fwd(nlevels, dims, N, ncols, loss_type, add_l1, -1.f, reg, ctr, labels, targets, ctr_t, valid, scalars, world, partials, reg_loss, ctr_loss, st);
+}
+int k_fcos_pos2d_fwd(int nlevels, const int* dims, int N, int ncols, int loss_type, int add_l1, float proj2d_weight, const float* const* reg, const float* const* ctr, const float* labels,
+                     const float* targets, const float* ctr_t, const unsigned char* valid, const float* scalars, float world, float* partials, float* reg_loss, float* ctr_loss,
+                     hipStream_t st) {
   FcosGeom G;
   const int kind = pos_kind(ncols, loss_type);
-  if (make_geom(nlevels, dims, N, G) || kind < 0 || !all_set(nlevels, reg) || !all_set(nlevels, ctr) || !(world >= 1.f)) return -4;
+  const bool with2d = proj2d_weight >= 0.f;
+  if (make_geom(nlevels, dims, N, G) || kind < 0 || !all_set(nlevels, reg) || !all_set(nlevels, ctr) || !(world >= 1.f) || (with2d && ncols != 8)) return -4;
   const Ptr4<const float> R = make_ptrs<const float>(nlevels, reg), Cn = make_ptrs<const float>(nlevels, ctr);
-#define FCOS_FWD(K) hipLaunchKernelGGL(fcos_pos_fwd_kernel<K>, dim3(G.nblocks), dim3(256), 0, st, G, R, Cn, labels, targets, ctr_t, valid, loss_type, add_l1, partials)
+  Fcos2d W = {};
+  if (with2d) { proj2d_make_cams(FCOS_2D_RES, W.cams); W.weight = proj2d_weight; }
+#define FCOS_FWD(K, P) hipLaunchKernelGGL((fcos_pos_fwd_kernel<K, P>), dim3(G.nblocks), dim3(256), 0, st, G, R, Cn, labels, targets, ctr_t, valid, loss_type, add_l1, W, partials)
+#define FCOS_FWD2(K) if (with2d) FCOS_FWD(K, true); else FCOS_FWD(K, false)
   switch (kind) {
-    case FCOS_AABB: FCOS_FWD(FCOS_AABB); break;
-    case FCOS_OBB_IOU: FCOS_FWD(FCOS_OBB_IOU); break;
-    case FCOS_OBB_GIOU: FCOS_FWD(FCOS_OBB_GIOU); break;
-    default: FCOS_FWD(FCOS_OBB_DIOU); break;
+    case FCOS_AABB: FCOS_FWD(FCOS_AABB, false); break;
+    case FCOS_OBB_IOU: FCOS_FWD2(FCOS_OBB_IOU); break;
+    case FCOS_OBB_GIOU: FCOS_FWD2(FCOS_OBB_GIOU); break;
+    default: FCOS_FWD2(FCOS_OBB_DIOU); break;
   }
+#undef FCOS_FWD2
 #undef FCOS_FWD
   NMH_CHECK_LAUNCH();
   launch_final(partials, G.nblocks, FIN_POS, world, const_cast<float*>(scalars), reg_loss, ctr_loss, st);
@@ -502,18 +531,29 @@ int k_fcos_pos_fwd(int nlevels, const int* dims, int N, int ncols, int loss_type
 int k_fcos_pos_bwd(int nlevels, const int* dims, int N, int ncols, int loss_type, int add_l1, const float* const* reg, const float* const* ctr, const float* labels, const float* targets,
                    const float* ctr_t, const unsigned char* valid, const float* scalars, float world, const float* g_reg, const float* g_ctr, float* const* dreg, float* const* dctr,
                    hipStream_t st) {
+  return k_fcos_pos2d_bwd(nlevels, dims, N, ncols, loss_type, add_l1, -1.f, reg, ctr, labels, targets, ctr_t, valid, scalars, world, g_reg, g_ctr, dreg, dctr, st);
+}
+int k_fcos_pos2d_bwd(int nlevels, const int* dims, int N, int ncols, int loss_type, int add_l1, float proj2d_weight, const float* const* reg, const float* const* ctr, const float* labels,
+                     const float* targets, const float* ctr_t, const unsigned char* valid, const float* scalars, float world, const float* g_reg, const float* g_ctr, float* const* dreg,
+                     float* const* dctr, hipStream_t st) {
   FcosGeom G;
   const int kind = pos_kind(ncols, loss_type);
-  if (make_geom(nlevels, dims, N, G) || kind < 0 || !all_set(nlevels, reg) || !all_set(nlevels, ctr) || !all_set(nlevels, dreg) || !all_set(nlevels, dctr) || !(world >= 1.f)) return -4;
+  const bool with2d = proj2d_weight >= 0.f;
+  if (make_geom(nlevels, dims, N, G) || kind < 0 || !all_set(nlevels, reg) || !all_set(nlevels, ctr) || !all_set(nlevels, dreg) || !all_set(nlevels, dctr) || !(world >= 1.f) ||
+      (with2d && ncols != 8)) return -4;
   const Ptr4<const float> R = make_ptrs<const float>(nlevels, reg), Cn = make_ptrs<const float>(nlevels, ctr);
   const Ptr4<float> DR = make_ptrs<float>(nlevels, dreg), DC = make_ptrs<float>(nlevels, dctr);
-#define FCOS_BWD(K) hipLaunchKernelGGL(fcos_pos_bwd_kernel<K>, dim3(G.nblocks), dim3(256), 0, st, G, R, Cn, labels, targets, ctr_t, valid, loss_type, add_l1, scalars, world, g_reg, g_ctr, DR, DC)
+  Fcos2d W = {};
+  if (with2d) { proj2d_make_cams(FCOS_2D_RES, W.cams); W.weight = proj2d_weight; }
+#define FCOS_BWD(K, P) hipLaunchKernelGGL((fcos_pos_bwd_kernel<K, P>), dim3(G.nblocks), dim3(256), 0, st, G, R, Cn, labels, targets, ctr_t, valid, loss_type, add_l1, W, scalars, world, g_reg, g_ctr, DR, DC)
+#define FCOS_BWD2(K) if (with2d) FCOS_BWD(K, true); else FCOS_BWD(K, false)
   switch (kind) {
-    case FCOS_AABB: FCOS_BWD(FCOS_AABB); break;
-    case FCOS_OBB_IOU: FCOS_BWD(FCOS_OBB_IOU); break;
-    case FCOS_OBB_GIOU: FCOS_BWD(FCOS_OBB_GIOU); break;
-    default: FCOS_BWD(FCOS_OBB_DIOU); break;
+    case FCOS_AABB: FCOS_BWD(FCOS_AABB, false); break;
+    case FCOS_OBB_IOU: FCOS_BWD2(FCOS_OBB_IOU); break;
+    case FCOS_OBB_GIOU: FCOS_BWD2(FCOS_OBB_GIOU); break;
+    default: FCOS_BWD2(FCOS_OBB_DIOU); break;
   }
+#undef FCOS_BWD2
 #undef FCOS_BWD
   NMH_CHECK_LAUNCH();
   return 0;

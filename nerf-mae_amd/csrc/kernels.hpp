@@ -302,6 +302,13 @@ int k_fcos_pos_fwd(int nlevels, const int* dims, int N, int ncols, int loss_type
 int k_fcos_pos_bwd(int nlevels, const int* dims, int N, int ncols, int loss_type, int add_l1, const float* const* reg, const float* const* ctr, const float* labels, const float* targets,
                    const float* ctr_t, const unsigned char* valid, const float* scalars, float world, const float* g_reg, const float* g_ctr, float* const* dreg, float* const* dctr,
                    hipStream_t st);
+// the same with the 2-D projection term (ncols 8 only): term += proj2d_weight T / 160 / 16 under the cameras of get_w2cs(160); proj2d_weight < 0: without it
+int k_fcos_pos2d_fwd(int nlevels, const int* dims, int N, int ncols, int loss_type, int add_l1, float proj2d_weight, const float* const* reg, const float* const* ctr, const float* labels,
+                     const float* targets, const float* ctr_t, const unsigned char* valid, const float* scalars, float world, float* partials, float* reg_loss, float* ctr_loss,
+                     hipStream_t st);
+int k_fcos_pos2d_bwd(int nlevels, const int* dims, int N, int ncols, int loss_type, int add_l1, float proj2d_weight, const float* const* reg, const float* const* ctr, const float* labels,
+                     const float* targets, const float* ctr_t, const unsigned char* valid, const float* scalars, float world, const float* g_reg, const float* g_ctr, float* const* dreg,
+                     float* const* dctr, hipStream_t st);
 int k_fcos_obb_encode(const float* loc, const float* boxes, long n, float* out, hipStream_t st);
 int k_fcos_obb_decode_fwd(const float* loc, const float* reg, long n, float* out, hipStream_t st);
 int k_fcos_obb_decode_bwd(const float* reg, const float* gbox, long n, float* dreg, hipStream_t st);
@@ -330,6 +337,18 @@ int k_rpn_iou_loss_fwd(int nlevels, const int* dims, const float* base, int N, i
 int k_rpn_iou_loss_bwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
                        const float* boxes, const int* offs, const int* ori, const int* midx, const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj,
                        float* const* dreg, hipStream_t st);
+// the losses with the 2-D projection term: loss_type < 0 smooth-L1 (ncols 6 | 8, targets required), else the IoU types (ncols 8); boxes DEVICE [offs[N]][6|7];
+// cams: HOST [48]; partials DEVICE [5 nblocks]; scalars DEVICE [5] = (objectness, box, sampled anchors, 2-D, sampled positives)
+int k_rpn_loss2d_fwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
+                     const float* targets, const float* boxes, const int* offs, const int* ori, const int* midx, const float* cams, float res, float* partials, float* scalars,
+                     hipStream_t st);
+int k_rpn_loss2d_bwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
+                     const float* targets, const float* boxes, const int* offs, const int* ori, const int* midx, const float* cams, float res, const float* scalars,
+                     const float* g_obj, const float* g_reg, const float* g_2d, float* const* dobj, float* const* dreg, hipStream_t st);
+// ---- proj2d.hip (the 2-D projection term on rows of boxes; cams: HOST [48] = the fused K [R|t] of four cameras, row-major 3x4) ----
+int k_proj2d_fwd(const float* pred, const float* target, long n, int ncols, const float* cams, float* terms, hipStream_t st);
+int k_proj2d_bwd(const float* pred, const float* target, const float* g_terms, long n, int ncols, const float* cams, float* dpred, hipStream_t st);
+void k_proj2d_cameras(float res, float* cams);           // HOST -> HOST: the cameras of get_w2cs(res)
 // ---- rpn_post.hip (RPN proposals: decode, exact top-k per level on the raw logits, per-level NMS, post-NMS cut) ----
 // mesh: HOST [3]; ori: DEVICE [N][3] or NULL.  Slot layout, sort key and tie rules: rpn_post.hip.
 long k_rpn_post_cap(int nlevels, const int* dims, int N, int pre_top_n);

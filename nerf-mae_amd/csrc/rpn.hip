@@ -41,6 +41,12 @@
 //   lies in the padding (either is possible only with flags that the sampler did not draw), contributes 0 and has zero box gradient.  Backward:
 //   g_reg / s through obb_pair_grad (box A only) and rpn_decode_obb_bwd (rpn_decode.hpp); every element of both gradients is written, dreg exactly 0
 //   where flag != 1.
+// 2-D projection term (rpn_loss2d, rpn_iou_loss2d: the third return of compute_loss, rpn.py:421-453), opt-in, for every box loss above and both box kinds.
+//   The same lane map and the same first two sums; a lane with flag == 1 adds T (proj2d.hpp) between the UNCLIPPED decode of its deltas (rpn_decode_aabb /
+//   rpn_decode_obb) and its matched box row, under the cameras of res = max(mesh_size).  P = number of flags == 1;  loss_2d = sum T / P / res, 0 when P == 0
+//   (the reference gives NaN).  A flagged positive without a box row or in the padding counts in P and contributes 0 (as for the IoU types).  scalars =
+//   (objectness, box, sampled anchors, 2-D, P).  Backward: one pass, g_2d / P / res through proj2d_term_grad and the decode's backward, added to the box
+//   term's gradient in registers, so that every element of both gradients is still written exactly once.
 #include "common.hpp"
 #include "kernels.hpp"
 #include "select_scan.hpp"
@@ -48,6 +54,7 @@
 #include "rpn_geom.hpp"
 #include "rpn_shared.hpp"
 #include "rpn_decode.hpp"
+#include "proj2d.hpp"
 
 namespace {
 
@@ -428,6 +435,155 @@ __global__ __launch_bounds__(256) void rpn_iou_loss_bwd_kernel(RpnGeom G, RpnBas
   for (int k = 0; k < 8; ++k) dp[(long)k * w.nloc] = gr[k];
 }
 
+// ---- the losses with the 2-D projection term -------------------------------------------------------------------------------------------------
+// TERM: what the box loss is; the 2-D term is the same for all of them
+enum { RPN2D_SL1_AABB = 0, RPN2D_SL1_OBB = 1, RPN2D_IOU = 2, RPN2D_GIOU = 3, RPN2D_DIOU = 4 };
+template <int TERM> struct Rpn2d {
+  static constexpr bool ORIENTED = TERM != RPN2D_SL1_AABB, SL1 = TERM <= RPN2D_SL1_OBB;
+  static constexpr int C = ORIENTED ? 8 : 6, NC = ORIENTED ? 7 : 6;
+  static constexpr int MODE = TERM == RPN2D_GIOU ? OBB_GIOU_SMALLEST : (TERM == RPN2D_DIOU ? OBB_DIOU_SMALLEST : OBB_IOU);
+};
+
+// as rpn_iou_pair, for box rows of NC columns
+template <int NC>
+__device__ __forceinline__ const float* rpn_2d_pair(const RpnGeom& G, const float* __restrict__ sh_base, const RpnOffs& S, const RHead& w, const float* __restrict__ boxes,
+                                                    const int* __restrict__ ori, const int* __restrict__ midx, Box6& a) {
+  bool valid;
+  a = rpn_anchor(G, sh_base, ori, RAt{w.lvl, w.scene, w.loc * w.A + w.a, true}, valid);
+  const int g0 = S.off[w.scene], g1 = S.off[w.scene + 1], row = g0 + max(midx[w.p], 0);
+  return valid && row < g1 ? boxes + (long)row * NC : nullptr;
+}
+
+// T between the unclipped decode of the deltas and the box row b, and its gradient over the deltas
+template <bool ORIENTED>
+__device__ __forceinline__ float rpn_2d_term(const float (&r)[8], const Box6& a, const float* __restrict__ b, const Proj2dCams& cams) {
+  float o[7];
+  if (ORIENTED) {
+    rpn_decode_obb(r, a, o);
+    return proj2d_term(obb_load(o), obb_load(b), cams);
+  }
+  rpn_decode_aabb(r, a, o);
+  const float p[6] = {o[0], o[1], o[2], o[3], o[4], o[5]}, t[6] = {b[0], b[1], b[2], b[3], b[4], b[5]};
+  return proj2d_term(p, t, cams);
+}
+template <bool ORIENTED>
+__device__ __forceinline__ void rpn_2d_term_grad(const float (&r)[8], const Box6& a, const float* __restrict__ b, const Proj2dCams& cams, float (&gr)[8]) {
+  float o[7];
+  if (ORIENTED) {
+    rpn_decode_obb(r, a, o);
+    BoxGrad g;
+    proj2d_term_grad(obb_load(o), obb_load(b), cams, g);
+    rpn_decode_obb_bwd(r, a, g, gr);
+  } else {
+    rpn_decode_aabb(r, a, o);
+    const float p[6] = {o[0], o[1], o[2], o[3], o[4], o[5]}, t[6] = {b[0], b[1], b[2], b[3], b[4], b[5]};
+    float g[6];
+    proj2d_term_grad(p, t, cams, g);
+    rpn_decode_aabb_bwd(r, a, g, gr);
+  }
+}
+
+template <int TERM>
+__global__ __launch_bounds__(256) void rpn_loss2d_fwd_kernel(RpnGeom G, RpnBase B, RpnOffs S, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
+                                                             const float* __restrict__ targets, const float* __restrict__ boxes, const int* __restrict__ ori,
+                                                             const int* __restrict__ midx, int linear, Proj2dCams cams, float* __restrict__ partials) {
+  using K = Rpn2d<TERM>;
+  constexpr int C = K::C;
+  __shared__ float sh_base[RPN_MAX_A * 3];
+  const RHead w = rpn_head_where(G);
+  rpn_stage_base(B, w.lvl, w.A, sh_base);
+  __syncthreads();
+  float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};   // objectness, box regression, sampled anchors, 2-D projection, sampled positives
+  const int f = w.active ? flags[w.p] : 0;
+  if (f != 0) {
+    const float x = pick4(obj.p, w.lvl)[(long)w.scene * w.A * w.nloc + w.j];
+    v[0] = fmaxf(x, 0.f) - (f == 1 ? x : 0.f) + log1pf(expf(-fabsf(x)));
+    v[2] = 1.f;
+    if (f == 1) {                       // a wave without a flagged positive skips this
+      v[4] = 1.f;
+      const float* __restrict__ rp = pick4(reg.p, w.lvl) + ((long)w.scene * w.A + w.a) * C * w.nloc + w.loc;
+      float r[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < C; ++k) r[k] = rp[(long)k * w.nloc];
+      if constexpr (K::SL1) {
+#pragma unroll
+        for (int k = 0; k < C; ++k) v[1] += rpn_sl1(r[k] - targets[w.p * C + k]);
+      }
+      Box6 a;
+      const float* __restrict__ b = rpn_2d_pair<K::NC>(G, sh_base, S, w, boxes, ori, midx, a);
+      if (b) {
+        if constexpr (!K::SL1) v[1] = rpn_iou_term<K::MODE>(r, a, b, linear);
+        v[3] = rpn_2d_term<K::ORIENTED>(r, a, b, cams);
+      }
+    }
+  }
+  block_sum_fixed(v, partials + 5 * (long)blockIdx.x);
+}
+
+// one workgroup: scalars = (objectness loss, box loss, number of sampled anchors, 2-D loss, number of sampled positives)
+__global__ __launch_bounds__(256) void rpn_loss2d_final_kernel(const float* __restrict__ partials, int nblocks, float res, float* __restrict__ scalars) {
+  float sum[5];
+  final_sum_fixed(partials, nblocks, sum);
+  if (threadIdx.x != 0) return;
+  const float cnt = sum[2], pos = sum[4];
+  scalars[0] = cnt > 0.f ? sum[0] / cnt : 0.f;
+  scalars[1] = cnt > 0.f ? sum[1] / cnt : 0.f;
+  scalars[2] = cnt;
+  scalars[3] = pos > 0.f ? sum[3] / pos / res : 0.f;
+  scalars[4] = pos;
+}
+
+template <int TERM>
+__global__ __launch_bounds__(256) void rpn_loss2d_bwd_kernel(RpnGeom G, RpnBase B, RpnOffs S, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
+                                                             const float* __restrict__ targets, const float* __restrict__ boxes, const int* __restrict__ ori,
+                                                             const int* __restrict__ midx, int linear, Proj2dCams cams, float res, const float* __restrict__ scalars,
+                                                             const float* __restrict__ g_obj, const float* __restrict__ g_reg, const float* __restrict__ g_2d, Ptr4<float> dobj,
+                                                             Ptr4<float> dreg) {
+  using K = Rpn2d<TERM>;
+  constexpr int C = K::C;
+  __shared__ float sh_base[RPN_MAX_A * 3];
+  const RHead w = rpn_head_where(G);
+  rpn_stage_base(B, w.lvl, w.A, sh_base);
+  __syncthreads();
+  if (!w.active) return;
+  const long at = (long)w.scene * w.A * w.nloc + w.j, rat = ((long)w.scene * w.A + w.a) * C * w.nloc + w.loc;
+  const int f = flags[w.p];
+  const float cnt = scalars[2], pos = scalars[4];
+  float go = 0.f, gr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (f != 0 && cnt > 0.f) {
+    const float x = pick4(obj.p, w.lvl)[at];
+    go = (sigmoid_stable(x) - (f == 1 ? 1.f : 0.f)) * (g_obj ? g_obj[0] : 0.f) / cnt;
+    if (f == 1) {                       // a wave without a flagged positive skips this
+      const float* __restrict__ rp = pick4(reg.p, w.lvl) + rat;
+      const float sc = (g_reg ? g_reg[0] : 0.f) / cnt, sc2 = (g_2d ? g_2d[0] : 0.f) / pos / res;
+      float r[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < C; ++k) r[k] = rp[(long)k * w.nloc];
+      if constexpr (K::SL1) {
+#pragma unroll
+        for (int k = 0; k < C; ++k) gr[k] = rpn_sl1_grad(r[k] - targets[w.p * C + k]) * sc;
+      }
+      Box6 a;
+      const float* __restrict__ b = rpn_2d_pair<K::NC>(G, sh_base, S, w, boxes, ori, midx, a);
+      if (b) {
+        float g2[8];
+        if constexpr (!K::SL1) {
+          rpn_iou_term_grad<K::MODE>(r, a, b, linear, g2);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) gr[k] = g2[k] * sc;
+        }
+        rpn_2d_term_grad<K::ORIENTED>(r, a, b, cams, g2);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) gr[k] += g2[k] * sc2;
+      }
+    }
+  }
+  pick4(dobj.p, w.lvl)[at] = go;
+  float* __restrict__ dp = pick4(dreg.p, w.lvl) + rat;
+#pragma unroll
+  for (int k = 0; k < C; ++k) dp[(long)k * w.nloc] = gr[k];
+}
+
 }  // namespace
 
 long k_rpn_num_blocks(int nlevels, const int* dims, int N) {
@@ -534,6 +690,73 @@ int k_rpn_iou_loss_bwd(int nlevels, const int* dims, const float* base, int N, i
   if (loss_type <= 1) hipLaunchKernelGGL(rpn_iou_loss_bwd_kernel<OBB_IOU>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, scalars, g_obj, g_reg, DO, DR);
   else if (loss_type == 2) hipLaunchKernelGGL(rpn_iou_loss_bwd_kernel<OBB_GIOU_SMALLEST>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, scalars, g_obj, g_reg, DO, DR);
   else hipLaunchKernelGGL(rpn_iou_loss_bwd_kernel<OBB_DIOU_SMALLEST>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, scalars, g_obj, g_reg, DO, DR);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
+
+namespace {
+// the arguments the four entries with the 2-D term share; term: a value of the RPN2D_ enum
+int make_2d_args(int nlevels, const int* dims, const float* base, int N, int term, const float* targets, const float* boxes, const int* offs, const int* midx, const float* cams,
+                 float res, RpnGeom& G, RpnBase& B, RpnOffs& S, Proj2dCams& C) {
+  if (make_geom(nlevels, dims, N, G) || make_base(nlevels, dims, base, B) || term < 0 || !offs || offs[0] != 0 || !midx || !cams || !(res > 0.f)) return -4;
+  if (term <= RPN2D_SL1_OBB && !targets) return -4;
+  for (int b = 0; b < N; ++b) if (offs[b + 1] < offs[b]) return -4;
+  for (int b = 0; b <= NMH_FCOS_MAX_SCENES; ++b) S.off[b] = offs[b < N ? b : N];
+  for (int k = 0; k < 48; ++k) C.m[k / 12][k % 12] = cams[k];
+  return offs[N] > 0 && !boxes ? -4 : 0;
+}
+int term_of(int ncols, int loss_type) {          // loss_type < 0: smooth-L1
+  if (loss_type < 0) return ncols == 6 ? RPN2D_SL1_AABB : (ncols == 8 ? RPN2D_SL1_OBB : -1);
+  return ncols != 8 || loss_type > 3 ? -1 : (loss_type <= 1 ? RPN2D_IOU : (loss_type == 2 ? RPN2D_GIOU : RPN2D_DIOU));
+}
+}  // namespace
+
+int k_rpn_loss2d_fwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
+                     const float* targets, const float* boxes, const int* offs, const int* ori, const int* midx, const float* cams, float res, float* partials, float* scalars,
+                     hipStream_t st) {
+  RpnGeom G;
+  RpnBase B;
+  RpnOffs S;
+  Proj2dCams C;
+  const int term = term_of(ncols, loss_type), linear = loss_type == 1;
+  if (make_2d_args(nlevels, dims, base, N, term, targets, boxes, offs, midx, cams, res, G, B, S, C) || !all_set(nlevels, obj) || !all_set(nlevels, reg)) return -4;
+  const Ptr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
+#define RPN2D_FWD(T) hipLaunchKernelGGL(rpn_loss2d_fwd_kernel<T>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, targets, boxes, ori, midx, linear, C, partials)
+  switch (term) {
+    case RPN2D_SL1_AABB: RPN2D_FWD(RPN2D_SL1_AABB); break;
+    case RPN2D_SL1_OBB: RPN2D_FWD(RPN2D_SL1_OBB); break;
+    case RPN2D_IOU: RPN2D_FWD(RPN2D_IOU); break;
+    case RPN2D_GIOU: RPN2D_FWD(RPN2D_GIOU); break;
+    default: RPN2D_FWD(RPN2D_DIOU); break;
+  }
+#undef RPN2D_FWD
+  NMH_CHECK_LAUNCH();
+  hipLaunchKernelGGL(rpn_loss2d_final_kernel, dim3(1), dim3(256), 0, st, partials, G.nblocks, res, scalars);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
+
+int k_rpn_loss2d_bwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
+                     const float* targets, const float* boxes, const int* offs, const int* ori, const int* midx, const float* cams, float res, const float* scalars,
+                     const float* g_obj, const float* g_reg, const float* g_2d, float* const* dobj, float* const* dreg, hipStream_t st) {
+  RpnGeom G;
+  RpnBase B;
+  RpnOffs S;
+  Proj2dCams C;
+  const int term = term_of(ncols, loss_type), linear = loss_type == 1;
+  if (make_2d_args(nlevels, dims, base, N, term, targets, boxes, offs, midx, cams, res, G, B, S, C) || !all_set(nlevels, obj) || !all_set(nlevels, reg) || !all_set(nlevels, dobj) ||
+      !all_set(nlevels, dreg)) return -4;
+  const Ptr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
+  const Ptr4<float> DO = make_ptrs<float>(nlevels, dobj), DR = make_ptrs<float>(nlevels, dreg);
+#define RPN2D_BWD(T) hipLaunchKernelGGL(rpn_loss2d_bwd_kernel<T>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, targets, boxes, ori, midx, linear, C, res, scalars, g_obj, g_reg, g_2d, DO, DR)
+  switch (term) {
+    case RPN2D_SL1_AABB: RPN2D_BWD(RPN2D_SL1_AABB); break;
+    case RPN2D_SL1_OBB: RPN2D_BWD(RPN2D_SL1_OBB); break;
+    case RPN2D_IOU: RPN2D_BWD(RPN2D_IOU); break;
+    case RPN2D_GIOU: RPN2D_BWD(RPN2D_GIOU); break;
+    default: RPN2D_BWD(RPN2D_DIOU); break;
+  }
+#undef RPN2D_BWD
   NMH_CHECK_LAUNCH();
   return 0;
 }

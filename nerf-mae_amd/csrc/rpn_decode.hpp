@@ -3,7 +3,8 @@
 //   rpn_decode_aabb     AABBCoder.decode_single (coder/AABB_coder.py:86-137): C = 6 -> (x0, y0, z0, x1, y1, z1), not clipped;
 //   rpn_decode_obb      MidpointOffsetCoder.decode_single = delta_sp2bbox (coder/midpoint_offset_coder.py:160-223, wh_ratio_clip 16/1000) with rectpoly2obb
 //                       and regular_obb (coder/misc.py:5-43): C = 8 -> (x, y, z, w, h, d, theta), not clipped;
-//   rpn_decode_obb_bwd  its hand-written backward (what autograd does for the reference): conventions at the function.
+//   rpn_decode_obb_bwd  its hand-written backward (what autograd does for the reference): conventions at the function;
+//   rpn_decode_aabb_bwd the backward of rpn_decode_aabb, for the 2-D projection term of the axis-aligned RPN.
 // fp32; the forwards keep the reference's order of operations, no contraction (a multiply and an add stay two roundings, as in the reference's tensor
 // arithmetic).  Non-finite deltas give unspecified values; nothing but the caller's registers is written.
 #pragma once
@@ -68,6 +69,18 @@ __device__ __forceinline__ void rpn_decode_obb(const float (&r)[8], const Box6& 
 
 // 1 where a clamp to [lo, hi] passes the gradient (lo <= v <= hi, as torch.clamp), else 0
 __device__ __forceinline__ float rpn_clamp_pass(float v, float lo, float hi) { return v >= lo && v <= hi ? 1.f : 0.f; }
+
+// Backward of rpn_decode_aabb: the gradient g over (x0, y0, z0, x1, y1, z1) -> gr, the gradient over the 6 deltas (gr[6], gr[7] = 0).  The clip of the size
+// deltas to log(2000) passes the gradient where v <= log(2000), as torch.clamp(max=) does.
+__device__ __forceinline__ void rpn_decode_aabb_bwd(const float (&r)[8], const Box6& a, const float (&g)[6], float (&gr)[8]) {
+  const float e[3] = {a.x1 - a.x0, a.y1 - a.y0, a.z1 - a.z0};
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    gr[k] = (g[k] + g[3 + k]) * e[k];
+    gr[3 + k] = (g[3 + k] - g[k]) * 0.5f * expf(fminf(r[3 + k], RPN_XFORM_CLIP)) * e[k] * rpn_clamp_pass(r[3 + k], -INFINITY, RPN_XFORM_CLIP);
+  }
+  gr[6] = gr[7] = 0.f;
+}
 
 // Backward of rpn_decode_obb: the gradient g over (x, y, z, w, h, d, theta) of the decoded box -> gr, the gradient over the 8 deltas.  The forward is
 // recomputed about the centre (gx, gy), in fp32 and free to contract: only the forward is bound to the reference's rounding.

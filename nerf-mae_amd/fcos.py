@@ -33,7 +33,7 @@ from torch.autograd.function import once_differentiable
 
 from . import conv_layer, ops
 from .fcos_inference import FCOSPostProcessor, fcos_postprocess_dense
-from .fcos_loss import FCOSLossComputation
+from .fcos_loss import FCOSLossComputation, FCOSProj2dLossComputation
 from .fpn import _NCDHWToCL, check_channels_last
 from .model import _gradbuf
 
@@ -209,9 +209,14 @@ class FCOSModule(nn.Module):
                              use_obb=args.rotated_bbox, compute_dtype=getattr(args, "compute_dtype", torch.bfloat16))
         self.box_selector_test = FCOSPostProcessor(args.pre_nms_thresh, args.pre_nms_top_n, args.nms_thresh, args.fpn_post_nms_top_n, args.min_size, 1,
                                                    use_obb=args.rotated_bbox)
-        self.loss_evaluator = FCOSLossComputation(fpn_strides, args.center_sampling_radius, args.iou_loss_type, args.norm_reg_targets, world_size=world_size,
-                                                  use_obb=args.rotated_bbox, use_additional_l1_loss=args.use_additional_l1_loss,
-                                                  proj2d_loss_weight=getattr(args, "proj2d_loss_weight", 0.0))
+        proj2d_loss_weight = getattr(args, "proj2d_loss_weight", 0.0)
+        if args.rotated_bbox and proj2d_loss_weight > 0:
+            self.loss_evaluator = FCOSProj2dLossComputation(fpn_strides, args.center_sampling_radius, args.iou_loss_type, args.norm_reg_targets, world_size,
+                                                            args.use_additional_l1_loss, proj2d_loss_weight)
+        else:       # a positive weight with axis-aligned boxes raises NotImplementedError here
+            self.loss_evaluator = FCOSLossComputation(fpn_strides, args.center_sampling_radius, args.iou_loss_type, args.norm_reg_targets, world_size=world_size,
+                                                      use_obb=args.rotated_bbox, use_additional_l1_loss=args.use_additional_l1_loss,
+                                                      proj2d_loss_weight=proj2d_loss_weight)
         self.resolution = resolution
         self.fpn_strides = fpn_strides
         self.world_size = world_size

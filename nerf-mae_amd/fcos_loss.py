@@ -2,6 +2,7 @@
 names, argument order and return tuple (the import swap is one line):
 
   FCOSLossComputation                  nerf_rpn/model/fcos/loss.py:174-591
+  FCOSProj2dLossComputation            the same for oriented boxes with the 2-D projection term, proj2d_loss_weight > 0 (loss.py:447-475, 579-585)
   encode_fcos_obb, decode_fcos_obb     nerf_rpn/model/fcos/utils.py:12-105
   fcos_targets                         the assignment on its own (prepare_targets), for inspection
 
@@ -18,7 +19,11 @@ workspace (8 bytes per 256 locations), so forward + backward can be captured wit
 DESIGN.md 3.8, Capture).  With world_size > 1 the two scalars are all-reduced as one 2-float tensor.
 
 Stated deviations from the reference:
-  - iou_loss_type="smooth_l1" and proj2d_loss_weight > 0 raise NotImplementedError;
+  - iou_loss_type="smooth_l1" raises NotImplementedError;
+  - the 2-D projection term is opt-in through a class of its own, FCOSProj2dLossComputation (oriented boxes only, as in the reference), which FCOSModule builds
+    for rotated_bbox=True and proj2d_loss_weight > 0: every positive's regression term gains proj2d_loss_weight T / 160 / 16 before the centerness weight, in the
+    same fused forward and backward (csrc/fcos.hip, fcos_pos2d).  FCOSLossComputation itself keeps raising NotImplementedError for proj2d_loss_weight > 0, so that
+    the default path runs the kernels without the term, unchanged; with axis-aligned boxes the reference ignores the weight, and a positive weight raises here;
   - the "unweighted sum if the weights sum to 0" branch of the IoU losses is not reproduced: positives always have positive centerness
     targets, because the in-box tests are strict;
   - with no positives reg_loss and centerness_loss are exact zeros with zero gradients (as in the reference);
@@ -96,7 +101,7 @@ class _FcosLoss(Function):
 
     @staticmethod
     def forward(ctx, cfg, boxes, offsets, grid_sizes, masks, *heads):
-        plan, ncols, loss_type, add_l1, radius, norm, world = cfg
+        plan, ncols, loss_type, add_l1, radius, norm, world, w2d = cfg        # w2d: the 2-D projection weight, None without the term
         L = plan.L
         heads = [h.contiguous() for h in heads]
         cls, reg, ctr = heads[:L], heads[L:2 * L], heads[2 * L:]
@@ -105,7 +110,10 @@ class _FcosLoss(Function):
             import torch.distributed as dist
             dist.all_reduce(scalars, op=dist.ReduceOp.SUM)
         cls_loss = ops.fcos_focal_fwd(plan, cls, labels, valid, scalars, float(world), partials)
-        reg_loss, ctr_loss = ops.fcos_pos_fwd(plan, 6 if ncols == 6 else 8, loss_type, add_l1, reg, ctr, labels, targets, ctr_t, valid, scalars, float(world), partials)
+        if w2d is None:
+            reg_loss, ctr_loss = ops.fcos_pos_fwd(plan, 6 if ncols == 6 else 8, loss_type, add_l1, reg, ctr, labels, targets, ctr_t, valid, scalars, float(world), partials)
+        else:
+            reg_loss, ctr_loss = ops.fcos_pos2d_fwd(plan, loss_type, add_l1, w2d, reg, ctr, labels, targets, ctr_t, valid, scalars, float(world), partials)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(labels, targets, ctr_t, valid, scalars, *heads)
         ctx.cfg = cfg
@@ -114,7 +122,7 @@ class _FcosLoss(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_cls, g_reg, g_ctr):
-        plan, ncols, loss_type, add_l1, _, _, world = ctx.cfg
+        plan, ncols, loss_type, add_l1, _, _, world, w2d = ctx.cfg
         L = plan.L
         labels, targets, ctr_t, valid, scalars, *heads = ctx.saved_tensors
         cls, reg, ctr = heads[:L], heads[L:2 * L], heads[2 * L:]
@@ -122,7 +130,10 @@ class _FcosLoss(Function):
         none = [None] * L
         dcls = ops.fcos_focal_bwd(plan, cls, labels, valid, scalars, float(world), gs[0]) if gs[0] is not None and any(ctx.needs_input_grad[5:5 + L]) else none
         if (gs[1] is not None or gs[2] is not None) and any(ctx.needs_input_grad[5 + L:]):
-            dreg, dctr = ops.fcos_pos_bwd(plan, 6 if ncols == 6 else 8, loss_type, add_l1, reg, ctr, labels, targets, ctr_t, valid, scalars, float(world), gs[1], gs[2])
+            if w2d is None:
+                dreg, dctr = ops.fcos_pos_bwd(plan, 6 if ncols == 6 else 8, loss_type, add_l1, reg, ctr, labels, targets, ctr_t, valid, scalars, float(world), gs[1], gs[2])
+            else:
+                dreg, dctr = ops.fcos_pos2d_bwd(plan, loss_type, add_l1, w2d, reg, ctr, labels, targets, ctr_t, valid, scalars, float(world), gs[1], gs[2])
         else:
             dreg, dctr = none, none
         return (None, None, None, None, None, *dcls, *dreg, *dctr)
@@ -137,7 +148,7 @@ class FCOSLossComputation(object):
         if iou_loss_type == "smooth_l1":
             raise NotImplementedError('iou_loss_type "smooth_l1" is not built; use "iou", "linear_iou", "giou"' + (' or "diou"' if use_obb else ""))
         if proj2d_loss_weight > 0:
-            raise NotImplementedError("the 2-D projection loss (proj2d_loss_weight > 0) is not built")
+            raise NotImplementedError("FCOSLossComputation runs without the 2-D projection loss; proj2d_loss_weight > 0 is FCOSProj2dLossComputation (oriented boxes only)")
         if iou_loss_type not in ops.FCOS_LOSS_TYPES or (iou_loss_type == "diou" and not use_obb):
             raise NotImplementedError(f"iou_loss_type {iou_loss_type!r} is not defined for use_obb={bool(use_obb)}")
         self.fpn_strides = [int(s) for s in fpn_strides]
@@ -148,11 +159,12 @@ class FCOSLossComputation(object):
         self.use_obb = bool(use_obb)
         self.use_additional_l1_loss = bool(use_additional_l1_loss)
         self.proj2d_loss_weight = proj2d_loss_weight
+        self._w2d = None                # set by FCOSProj2dLossComputation
 
     def __call__(self, locations, box_cls, box_regression, centerness, targets, padding_masks=None, grid_sizes=None):
         """box_cls, box_regression, centerness: lists of per-level tensors (N,1,w,l,h), (N,6|8,w,l,h), (N,1,w,l,h); targets: list of N box tensors
         -> (cls_loss, reg_loss, centerness_loss), 0-dim fp32 device tensors"""
-        name = "FCOSLossComputation"
+        name = type(self).__name__
         L = len(box_cls)
         if L > MAX_LEVELS:
             raise ValueError(f"{name} supports at most {MAX_LEVELS} levels, got {L}")
@@ -171,8 +183,21 @@ class FCOSLossComputation(object):
         plan = ops.FcosPlan(sizes, self.fpn_strides, N)
         grid_sizes, masks = _validity(name, plan, grid_sizes, padding_masks, boxes.device)
         cfg = (plan, ncols, ops.FCOS_LOSS_TYPES[self.iou_loss_type], self.use_obb and self.use_additional_l1_loss, self.center_sampling_radius, self.norm_reg_targets,
-               self.world_size)
+               self.world_size, self._w2d)
         return _FcosLoss.apply(cfg, boxes, offsets, grid_sizes, masks, *box_cls, *box_regression, *centerness)
+
+
+class FCOSProj2dLossComputation(FCOSLossComputation):
+    """FCOSLossComputation for oriented boxes with the reference's 2-D projection term (--proj2d_loss_weight of the FCOS launchers): same call, same three losses;
+    cls_loss and centerness_loss have the bits of FCOSLossComputation's, reg_loss gains proj2d_loss_weight sum_p ct_p T_p / 160 / 16 / (sum ct / world_size) with T
+    (proj2d.py) between decode_fcos_obb(0, box_regression) and decode_fcos_obb(0, reg_targets) under the cameras of get_w2cs(160), for every iou_loss_type and next
+    to the additional L1 term."""
+
+    def __init__(self, fpn_strides, center_sampling_radius, iou_loss_type, norm_reg_targets, world_size, use_additional_l1_loss, proj2d_loss_weight):
+        if not proj2d_loss_weight > 0:
+            raise ValueError(f"FCOSProj2dLossComputation: proj2d_loss_weight > 0, got {proj2d_loss_weight!r}; without the term use FCOSLossComputation")
+        super().__init__(fpn_strides, center_sampling_radius, iou_loss_type, norm_reg_targets, world_size, True, use_additional_l1_loss)
+        self.proj2d_loss_weight = self._w2d = float(proj2d_loss_weight)
 
 
 def encode_fcos_obb(locations, boxes):

@@ -1692,6 +1692,22 @@ def fcos_pos_bwd(plan, ncols, loss_type, add_l1, reg, ctr, labels, targets, ctr_
     return dreg, dctr
 
 
+def fcos_pos2d_fwd(plan, loss_type, add_l1, proj2d_weight, reg, ctr, labels, targets, ctr_t, valid, scalars, world, partials):
+    """fcos_pos_fwd with the 2-D projection term (8 regression columns only)"""
+    reg_loss = torch.empty((), dtype=torch.float32, device=labels.device)
+    ctr_loss = torch.empty((), dtype=torch.float32, device=labels.device)
+    lib().call("nmh_fcos_pos2d_fwd", plan.L, plan.dims, plan.N, 8, loss_type, int(bool(add_l1)), proj2d_weight, _ptr_table(reg, plan.L), _ptr_table(ctr, plan.L), labels, targets, ctr_t, valid,
+               scalars, world, partials, reg_loss, ctr_loss, _st())
+    return reg_loss, ctr_loss
+
+
+def fcos_pos2d_bwd(plan, loss_type, add_l1, proj2d_weight, reg, ctr, labels, targets, ctr_t, valid, scalars, world, g_reg, g_ctr):
+    dreg, dctr = [torch.empty_like(t) for t in reg], [torch.empty_like(t) for t in ctr]
+    lib().call("nmh_fcos_pos2d_bwd", plan.L, plan.dims, plan.N, 8, loss_type, int(bool(add_l1)), proj2d_weight, _ptr_table(reg, plan.L), _ptr_table(ctr, plan.L), labels, targets, ctr_t, valid,
+               scalars, world, g_reg, g_ctr, _ptr_table(dreg, plan.L), _ptr_table(dctr, plan.L), _st())
+    return dreg, dctr
+
+
 def fcos_obb_encode(locations, boxes):
     _chk(locations, boxes)
     out = torch.empty((boxes.shape[0], 8), dtype=torch.float32, device=boxes.device)
@@ -1866,6 +1882,61 @@ def rpn_iou_loss_bwd(plan, loss_type, obj, reg, flags, boxes, offsets, ori_sizes
     lib().call("nmh_rpn_iou_loss_bwd", plan.L, plan.dims, plan.base, plan.N, 8, lt, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, boxes, offs, ori_sizes, midx, scalars,
                g_obj, g_reg, _ptr_table(dobj, plan.L), _ptr_table(dreg, plan.L), _st())
     return dobj, dreg
+
+
+def _cams48(cams):
+    """fp32 host tensor [4, 3, 4] -> the host array the entries take"""
+    if not isinstance(cams, torch.Tensor) or cams.dtype != torch.float32 or cams.is_cuda or tuple(cams.shape) != (4, 3, 4):
+        raise ValueError("cameras must be an fp32 host tensor [4, 3, 4]")
+    return (ctypes.c_float * 48)(*cams.reshape(-1).tolist())
+
+
+def rpn_loss2d_fwd(plan, C, loss_type, obj, reg, flags, targets, boxes, offsets, ori_sizes, midx, cams, res):
+    """the losses of rpn_loss_fwd (loss_type None: smooth-L1, C 6 | 8, targets [N,n,C]) or rpn_iou_loss_fwd (a key of FCOS_LOSS_TYPES, C 8) with the 2-D projection
+    term; cams: the host array of _cams48, res = max(mesh_size) -> scalars [5] = (objectness loss, box loss, sampled anchors, 2-D loss, sampled positives)"""
+    _chk(boxes, ori_sizes, midx, targets)
+    dev = flags.device
+    offs = (ctypes.c_int * (plan.N + 1))(*offsets)
+    boxes = boxes if boxes.numel() else None
+    partials = torch.empty((5 * plan.nblocks,), dtype=torch.float32, device=dev)
+    scalars = torch.empty((5,), dtype=torch.float32, device=dev)
+    if loss_type is None:
+        lib().call("nmh_rpn_loss2d_fwd", plan.L, plan.dims, plan.base, plan.N, C, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, targets, boxes, offs, ori_sizes, midx, cams, res,
+                   partials, scalars, _st())
+    else:
+        lib().call("nmh_rpn_iou_loss2d_fwd", plan.L, plan.dims, plan.base, plan.N, C, FCOS_LOSS_TYPES[loss_type], _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, boxes, offs,
+                   ori_sizes, midx, cams, res, partials, scalars, _st())
+    return scalars
+
+
+def rpn_loss2d_bwd(plan, C, loss_type, obj, reg, flags, targets, boxes, offsets, ori_sizes, midx, cams, res, scalars, g_obj, g_reg, g_2d, out=None):
+    """-> (dobj, dreg) per level; out: the pair of per-level lists to write instead of fresh tensors (every element is written exactly once)"""
+    offs = (ctypes.c_int * (plan.N + 1))(*offsets)
+    boxes = boxes if boxes.numel() else None
+    dobj, dreg = out if out is not None else ([torch.empty_like(t) for t in obj], [torch.empty_like(t) for t in reg])
+    if loss_type is None:
+        lib().call("nmh_rpn_loss2d_bwd", plan.L, plan.dims, plan.base, plan.N, C, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, targets, boxes, offs, ori_sizes, midx, cams, res,
+                   scalars, g_obj, g_reg, g_2d, _ptr_table(dobj, plan.L), _ptr_table(dreg, plan.L), _st())
+    else:
+        lib().call("nmh_rpn_iou_loss2d_bwd", plan.L, plan.dims, plan.base, plan.N, C, FCOS_LOSS_TYPES[loss_type], _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, boxes, offs,
+                   ori_sizes, midx, cams, res, scalars, g_obj, g_reg, g_2d, _ptr_table(dobj, plan.L), _ptr_table(dreg, plan.L), _st())
+    return dobj, dreg
+
+
+# ---- the 2-D projection term on rows of boxes (csrc/proj2d.hip) ------------------------------------------------------------------------------
+def proj2d_fwd(pred, target, cams):
+    """pred, target [n, 6|7] fp32, cams: the host array of _cams48 -> terms [n]"""
+    _chk(pred, target)
+    terms = torch.empty((pred.shape[0],), dtype=torch.float32, device=pred.device)
+    lib().call("nmh_proj2d_fwd", pred, target, pred.shape[0], pred.shape[1], cams, terms, _st())
+    return terms
+
+
+def proj2d_bwd(pred, target, g_terms, cams):
+    _chk(pred, target, g_terms)
+    dpred = torch.empty_like(pred)
+    lib().call("nmh_proj2d_bwd", pred, target, g_terms, pred.shape[0], pred.shape[1], cams, dpred, _st())
+    return dpred
 
 
 # ---- RPN proposals: decode, top-k per level, per-level NMS, post-NMS cut (csrc/rpn_post.hip) --------------------------------------------------

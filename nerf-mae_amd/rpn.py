@@ -33,8 +33,12 @@ Stated deviations from the reference, training path:
   - the sampler does not reproduce torch.randperm's stream: a candidate's key is a hash of (seed, counter, scene, anchor index) and the num_pos /
     num_neg smallest keys are taken (uniform without replacement; equal keys at the cut go to the lower anchor index);
   - equal IoU of one anchor with several boxes goes to the lowest box index (torch.max leaves it open);
-  - loss_rpn_box_reg_2d is returned as a constant zero without gradient: the reference weights it by --reg_loss_weight_2d, whose default is
-    0.0 and which no launcher sets, so the total loss and every gradient are the reference's under its defaults;
+  - loss_rpn_box_reg_2d, the 2-D projection loss (model/rpn.py:421-453), is opt-in: with the trailing keyword reg_loss_2d=True of the two loss classes and
+    the two networks it is the reference's value, with its gradient, from the same fused forward and the same single backward launch (csrc/rpn.hip, 2-D
+    projection term; csrc/proj2d.hpp).  By default it stays a constant zero without gradient and the kernels without the term run: the reference weights
+    it by --reg_loss_weight_2d, whose default is 0.0 and which no launcher sets, so the default costs nothing and gives the reference's total loss and
+    gradients.  The weighting stays in the step, as in run_rpn.py:386-387: FinetuneStep(weights={"loss_rpn_box_reg_2d": w2d}).  Without a sampled positive
+    it is 0 (the reference gives NaN); a sampled positive without a box row or in the padding (only `sampled=` can produce one) contributes nothing;
   - the IoU-type losses are a class of their own, RPNIoULossComputation, which RegionProposalNetwork builds for rotated_bbox=True and a reg_loss_type other
     than "smooth_l1"; RPNLossComputation itself raises NotImplementedError for them, and so does either network with rotated_bbox=False (the reference
     fails there too: its rotated_iou_loss is None).  An unknown reg_loss_type raises ValueError with rotated_bbox=True;
@@ -66,7 +70,7 @@ from torch import nn
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import conv_layer, ops
+from . import conv_layer, ops, proj2d
 from .fcos_loss import _boxes, _check
 from .fpn import _NCDHWToCL, check_channels_last
 from .model import _gradbuf
@@ -263,12 +267,38 @@ class _RpnIoULoss(Function):
         return (None,) * 7 + (*dobj, *dreg)
 
 
+class _RpnLoss2d(Function):
+    """(plan, C, loss_type or None (smooth-L1), cams, res, flags, targets, boxes, offsets, ori, matched_idxs, *objectness levels, *regression levels) ->
+    (loss_objectness, loss_rpn_box_reg, loss_rpn_box_reg_2d): either box loss with the 2-D projection term, one forward and one backward launch"""
+
+    @staticmethod
+    def forward(ctx, plan, C, loss_type, cams, res, flags, targets, boxes, offsets, ori, midx, *heads):
+        heads = [h.contiguous() for h in heads]
+        scalars = ops.rpn_loss2d_fwd(plan, C, loss_type, heads[:plan.L], heads[plan.L:], flags, targets, boxes, offsets, ori, midx, cams, res)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(flags, targets, boxes, midx, scalars, *heads)
+        ctx.cfg = (plan, C, loss_type, cams, res, offsets, ori)
+        return scalars[0], scalars[1], scalars[3]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_obj, g_reg, g_2d):
+        plan, C, loss_type, cams, res, offsets, ori = ctx.cfg
+        flags, targets, boxes, midx, scalars, *heads = ctx.saved_tensors
+        if (g_obj is None and g_reg is None and g_2d is None) or not any(ctx.needs_input_grad[11:]):
+            return (None,) * (11 + 2 * plan.L)
+        gs = [g if g is None else g.contiguous() for g in (g_obj, g_reg, g_2d)]
+        dobj, dreg = ops.rpn_loss2d_bwd(plan, C, loss_type, heads[:plan.L], heads[plan.L:], flags, targets, boxes, offsets, ori, midx, cams, res, scalars, *gs)
+        return (None,) * 11 + (*dobj, *dreg)
+
+
 class _RPNLossBase(object):
     """What the two loss classes share: the checks, assignment and sampling (one seed draws the same sample in either), and the result's three keys.
     rng_state (int64 device tensor [2] = (seed, counter)) is created on the first call; copy into it to replay a draw."""
 
-    def __init__(self, anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox, reg_loss_type, seed):
+    def __init__(self, anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox, reg_loss_type, seed, reg_loss_2d=False):
         self.name = type(self).__name__
+        self.reg_loss_2d = bool(reg_loss_2d)
         if len(anchor_generator.sizes) > MAX_LEVELS:
             raise ValueError(f"{self.name} supports at most {MAX_LEVELS} levels, got {len(anchor_generator.sizes)}")
         if bg_iou_thresh > fg_iou_thresh:
@@ -285,10 +315,16 @@ class _RPNLossBase(object):
         """-> (loss_objectness, loss_rpn_box_reg)"""
         raise NotImplementedError
 
+    def _losses_2d(self, plan, C, mesh_size, flags, boxes, offsets, ori, matched_idxs, reg_targets, heads):
+        """-> (loss_objectness, loss_rpn_box_reg, loss_rpn_box_reg_2d); the cameras stand around a scene of max(mesh_size), which is also the divisor"""
+        res = float(max(int(m) for m in mesh_size[-3:]))
+        loss_type = None if self.reg_loss_type == "smooth_l1" else self.reg_loss_type
+        return _RpnLoss2d.apply(plan, C, loss_type, proj2d._cams(res), res, flags, reg_targets, boxes, offsets, ori, matched_idxs, *heads)
+
     def __call__(self, mesh_size, objectness, pred_bbox_deltas, targets, original_mesh_sizes=None, sampled=None):
         """mesh_size (X, Y, Z) of the padded batch; objectness, pred_bbox_deltas: the head's per-level lists; targets: list of N box tensors;
         original_mesh_sizes: the scenes' sizes before padding, used as the reference does, only when N > 1; sampled: flags [N, n] uint8 in place of the
-        sampler -> {"loss_objectness", "loss_rpn_box_reg", "loss_rpn_box_reg_2d"}, 0-dim fp32 device tensors"""
+        sampler -> {"loss_objectness", "loss_rpn_box_reg", "loss_rpn_box_reg_2d"}, 0-dim fp32 device tensors (the last a constant zero unless reg_loss_2d)"""
         name = self.name
         L = len(objectness)
         if L > MAX_LEVELS:
@@ -318,19 +354,25 @@ class _RPNLossBase(object):
             if not isinstance(sampled, torch.Tensor) or sampled.dtype != torch.uint8 or tuple(sampled.shape) != (N, plan.n) or not sampled.is_cuda:
                 raise ValueError(f"{name}: sampled must be a uint8 device tensor [N, n] = {(N, plan.n)}")
             flags = sampled.contiguous()
-        loss_obj, loss_reg = self._losses(plan, C, flags, boxes, offsets, ori, matched_idxs, reg_targets, (*objectness, *pred_bbox_deltas))
-        return {"loss_objectness": loss_obj, "loss_rpn_box_reg": loss_reg, "loss_rpn_box_reg_2d": torch.zeros((), dtype=torch.float32, device=boxes.device)}
+        heads = (*objectness, *pred_bbox_deltas)
+        if self.reg_loss_2d:
+            loss_obj, loss_reg, loss_2d = self._losses_2d(plan, C, mesh_size, flags, boxes, offsets, ori, matched_idxs, reg_targets, heads)
+        else:
+            loss_obj, loss_reg = self._losses(plan, C, flags, boxes, offsets, ori, matched_idxs, reg_targets, heads)
+            loss_2d = torch.zeros((), dtype=torch.float32, device=boxes.device)
+        return {"loss_objectness": loss_obj, "loss_rpn_box_reg": loss_reg, "loss_rpn_box_reg_2d": loss_2d}
 
 
 class RPNLossComputation(_RPNLossBase):
     """The training half of the reference's RegionProposalNetwork.forward on the fused kernels: assignment, sampling, the objectness loss and the
     smooth-L1 box loss on the encoded targets."""
 
-    def __init__(self, anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox=False, reg_loss_type="smooth_l1", seed=0):
+    def __init__(self, anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox=False, reg_loss_type="smooth_l1", seed=0,
+                 reg_loss_2d=False):
         if reg_loss_type != "smooth_l1":
             raise NotImplementedError(f'RPNLossComputation computes reg_loss_type "smooth_l1" only, got {reg_loss_type!r}; the IoU-type losses of oriented boxes '
                                       "are RPNIoULossComputation")
-        super().__init__(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox, reg_loss_type, seed)
+        super().__init__(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox, reg_loss_type, seed, reg_loss_2d)
 
     def _losses(self, plan, C, flags, boxes, offsets, ori, matched_idxs, reg_targets, heads):
         return _RpnLoss.apply(plan, C, flags, reg_targets, *heads)
@@ -341,10 +383,10 @@ class RPNIoULossComputation(_RPNLossBase):
     term is RotatedIOULoss between the decoded proposal of every sampled positive and its matched box, differentiated through the decode (csrc/rpn.hip, IoU-type
     box losses).  Always oriented: 8 regression columns, [k, 7] boxes.  Same call, same keys, same sampler as RPNLossComputation."""
 
-    def __init__(self, anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, reg_loss_type="iou", seed=0):
+    def __init__(self, anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, reg_loss_type="iou", seed=0, reg_loss_2d=False):
         if reg_loss_type not in ops.FCOS_LOSS_TYPES:
             raise ValueError(f"RPNIoULossComputation: reg_loss_type must be one of {sorted(ops.FCOS_LOSS_TYPES)}, got {reg_loss_type!r}")
-        super().__init__(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, True, reg_loss_type, seed)
+        super().__init__(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, True, reg_loss_type, seed, reg_loss_2d)
 
     def _losses(self, plan, C, flags, boxes, offsets, ori, matched_idxs, reg_targets, heads):
         return _RpnIoULoss.apply(plan, self.reg_loss_type, flags, boxes, offsets, ori, matched_idxs, *heads)
@@ -537,7 +579,7 @@ class RegionProposalNetwork(nn.Module):
     RPNProposalFilter and {}.  The only registered submodules are anchor_generator (no parameters) and head, so the state_dict keys are head.*."""
 
     def __init__(self, anchor_generator, head, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, pre_nms_top_n, post_nms_top_n, nms_thresh,
-                 score_thresh=0.0, iou_batch_size=16, rotated_bbox=False, reg_loss_type="smooth_l1"):
+                 score_thresh=0.0, iou_batch_size=16, rotated_bbox=False, reg_loss_type="smooth_l1", reg_loss_2d=False):
         super().__init__()
         self.anchor_generator = anchor_generator
         self.head = head
@@ -552,9 +594,10 @@ class RegionProposalNetwork(nn.Module):
         self.reg_loss_type = reg_loss_type
         self.min_size = 1e-3
         if rotated_bbox and reg_loss_type != "smooth_l1":
-            self.loss = RPNIoULossComputation(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, reg_loss_type)
+            self.loss = RPNIoULossComputation(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, reg_loss_type, reg_loss_2d=reg_loss_2d)
         else:           # an IoU type without rotated_bbox raises NotImplementedError here: the reference has no such loss either (its rotated_iou_loss is None)
-            self.loss = RPNLossComputation(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox, reg_loss_type)
+            self.loss = RPNLossComputation(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox, reg_loss_type,
+                                           reg_loss_2d=reg_loss_2d)
         self.filters = {mode: RPNProposalFilter(anchor_generator, pre_nms_top_n[mode], post_nms_top_n[mode], nms_thresh, score_thresh, rotated_bbox)
                         for mode in ("training", "testing")}
 
@@ -614,7 +657,7 @@ class NeRFRegionProposalNetwork(nn.Module):
 
     def __init__(self, backbone, rpn_anchor_generator=None, rpn_head=None, rpn_pre_nms_top_n_train=2000, rpn_pre_nms_top_n_test=1000, rpn_post_nms_top_n_train=2000,
                  rpn_post_nms_top_n_test=1000, rpn_nms_thresh=0.7, rpn_fg_iou_thresh=0.7, rpn_bg_iou_thresh=0.3, rpn_batch_size_per_image=256, rpn_positive_fraction=0.5,
-                 rpn_score_thresh=0.0, iou_batch_size=16, rotated_bbox=False, reg_loss_type="smooth_l1", **kwargs):
+                 rpn_score_thresh=0.0, iou_batch_size=16, rotated_bbox=False, reg_loss_type="smooth_l1", reg_loss_2d=False, **kwargs):
         if not hasattr(backbone, "out_channels"):
             raise ValueError("backbone should contain an attribute out_channels specifying the number of output channels (assumed to be the same for all the levels)")
         if not isinstance(rpn_anchor_generator, (AnchorGenerator3D, type(None))):
@@ -627,7 +670,7 @@ class NeRFRegionProposalNetwork(nn.Module):
         rpn = RegionProposalNetwork(rpn_anchor_generator, rpn_head, rpn_fg_iou_thresh, rpn_bg_iou_thresh, rpn_batch_size_per_image, rpn_positive_fraction,
                                     dict(training=rpn_pre_nms_top_n_train, testing=rpn_pre_nms_top_n_test),
                                     dict(training=rpn_post_nms_top_n_train, testing=rpn_post_nms_top_n_test), rpn_nms_thresh, score_thresh=rpn_score_thresh,
-                                    iou_batch_size=iou_batch_size, rotated_bbox=rotated_bbox, reg_loss_type=reg_loss_type)
+                                    iou_batch_size=iou_batch_size, rotated_bbox=rotated_bbox, reg_loss_type=reg_loss_type, reg_loss_2d=reg_loss_2d)
         super().__init__()
         self.backbone = backbone
         self.rpn = rpn

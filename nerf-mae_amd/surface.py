@@ -11,6 +11,7 @@
     groupnorm_relu_fwd / groupnorm_relu_bwd nn.GroupNorm(G, C) -> nn.ReLU of the FCOS head's towers (nerf_rpn/model/fcos/fcos.py:63-64, 75-76)
     mae_loss_fwd / mae_loss_bwd             UnetOutBlock 1x1 conv + forward_loss (swin_mae3d.py:1513-1549)
     adamw_clip_step                         clip_grad_norm_ + AdamW on flat buffers (run_swin_mae3d.py:665-669)
+    proj2d_fwd / proj2d_bwd                 the 2-D projection term of the detectors' box losses on rows of boxes (nerf_rpn/model/rpn.py:421-453, fcos/loss.py:447-475)
 
 Every function is a composition of the C-ABI entry points of include/nerfmae_hip.h through `ops` (the model's autograd Functions in
 model.py fuse further: LayerNorm with the window gather, the window reverse with the proj GEMM's store, deferred grouped weight
@@ -274,6 +275,21 @@ def mae_loss_bwd(saved):
     dW, db = torch.zeros(4, Cd, device=d0t.device), torch.zeros(4, device=d0t.device)
     ops.mae_loss_bwd(d0t, wo, b_out, target, extents, tokmask, B, R, Cd, sums, dd0, torch.empty((d0t.shape[0], 8), dtype=d0t.dtype, device=d0t.device), dW, db)
     return dd0.view(B, R, R, R, Cd), dW, db
+
+
+# ---- 2-D projection term of the box losses --------------------------------------------------------------------------------------------------
+def proj2d_fwd(pred: Tensor, target: Tensor, res: float):
+    """pred, target fp32 [n, 6] (x0,y0,z0,x1,y1,z1) or [n, 7] (x,y,z,w,l,h,theta), res: the cameras' scene size -> (terms [n], saved)"""
+    from . import proj2d
+    proj2d._rows("proj2d_fwd", pred, target)
+    pred, target, cams = pred.detach().contiguous(), target.detach().contiguous(), proj2d._cams(res)
+    return ops.proj2d_fwd(pred, target, cams), (pred, target, cams)
+
+
+def proj2d_bwd(g_terms: Tensor, saved) -> Tensor:
+    """-> dpred [n, 6|7] (the target has no gradient)"""
+    pred, target, cams = saved
+    return ops.proj2d_bwd(pred, target, g_terms.contiguous(), cams)
 
 
 # ---- clip + AdamW ------------------------------------------------------------------------------------------------------------------------
