@@ -591,6 +591,13 @@ NMH_API int nmh_roi_level_map(int64_t M, const float* boxes, int stride, int nco
 NMH_API int nmh_roi_pool_fwd(int nlevels, const int* level_dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* const* maps, const float* rois, const int* level_override, float* out, int* argmax, void* stream);
 /* Its adjoint with respect to the maps (autograd through the same lines): fp32 atomic adds into dmaps, which the caller zeroed; a NULL level is skipped. */
 NMH_API int nmh_roi_pool_bwd(int nlevels, const int* level_dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* dout, const int* argmax, const float* rois, const int* level_override, float* const* dmaps, void* stream);
+/* ROIPool.rotated_forward (detector.py:264-404) with 'interpolation', ncols 7 only (else -4): the rotated 8-corner grid of nmh_roi_pool_fwd, resampled to
+ * (ow, oh, od) as F.interpolate(mode="trilinear", align_corners=True) does, all scenes and levels in one launch.  Arguments as nmh_roi_pool_fwd without
+ * the argmax -> out [N R][C][ow][oh][od]; a level outside 0 .. nlevels-1 gives zeros. */
+NMH_API int nmh_roi_interp_fwd(int nlevels, const int* level_dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* const* maps, const float* rois, const int* level_override, float* out, void* stream);
+/* Its adjoint with respect to the maps (autograd through detector.py:264-404), the geometry formed again from the RoIs: fp32 atomic adds into dmaps, which the
+ * caller zeroed; a NULL level is skipped. */
+NMH_API int nmh_roi_interp_bwd(int nlevels, const int* level_dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* dout, const float* rois, const int* level_override, float* const* dmaps, void* stream);
 /* Classification_Model.compute_loss (detector.py:536-559) with the targets of box_coder.encode_single (detector.py:616; coder/rotated_coder.py:19-55,
  * coder/AABB_coder.py:7-56): cross-entropy over rows with 0 <= label < n_classes, smooth-L1 (beta 1/9) over rows with label > 0, in fixed order.
  * rois [M][roi_stride], the box in the last ncols columns.  -> targets [M][ncols], scalars [4] = (loss_objectness, loss_rpn_box_reg, valid rows,

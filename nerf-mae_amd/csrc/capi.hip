@@ -960,6 +960,18 @@ int nmh_roi_pool_bwd(int nlevels, const int* level_dims, const float* scales, in
   REQ(level_dims, scales, dout, argmax, rois, dmaps);
   return k_roi_pool_bwd(nlevels, level_dims, scales, N, C, R, ncols, ow, oh, od, enlarge, dout, argmax, rois, level_override, dmaps, ST);
 }
+int nmh_roi_interp_fwd(int nlevels, const int* level_dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* const* maps,
+                       const float* rois, const int* level_override, float* out, void* stream) {
+  CLR();
+  REQ(level_dims, scales, maps, rois, out);
+  return k_roi_interp_fwd(nlevels, level_dims, scales, N, C, R, ncols, ow, oh, od, enlarge, maps, rois, level_override, out, ST);
+}
+int nmh_roi_interp_bwd(int nlevels, const int* level_dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* dout, const float* rois,
+                       const int* level_override, float* const* dmaps, void* stream) {
+  CLR();
+  REQ(level_dims, scales, dout, rois, dmaps);
+  return k_roi_interp_bwd(nlevels, level_dims, scales, N, C, R, ncols, ow, oh, od, enlarge, dout, rois, level_override, dmaps, ST);
+}
 int64_t nmh_roi_loss_blocks(int64_t M) { return k_roi_loss_blocks((long)M); }
 int nmh_roi_loss_fwd(int64_t M, int n_classes, int ncols, const float* scores, const float* deltas, const float* labels, const float* rois, int roi_stride, const float* gt_rois,
                      float* targets, float* partials, float* scalars, void* stream) {

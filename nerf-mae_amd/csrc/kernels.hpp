@@ -372,6 +372,10 @@ int k_roi_pool_fwd(int nlevels, const int* dims, const float* scales, int N, int
                    const int* lvl_override, float* out, int* argout, hipStream_t st);
 int k_roi_pool_bwd(int nlevels, const int* dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* dout, const int* argout,
                    const float* rois, const int* lvl_override, float* const* dmaps, hipStream_t st);
+int k_roi_interp_fwd(int nlevels, const int* dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* const* maps, const float* rois,
+                     const int* lvl_override, float* out, hipStream_t st);
+int k_roi_interp_bwd(int nlevels, const int* dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* dout, const float* rois,
+                     const int* lvl_override, float* const* dmaps, hipStream_t st);
 long k_roi_loss_blocks(long M);
 int k_roi_loss_fwd(long M, int n_classes, int ncols, const float* scores, const float* deltas, const float* labels, const float* rois, int roi_stride, const float* gt_rois,
                    float* targets, float* partials, float* scalars, hipStream_t st);

@@ -2,6 +2,7 @@
 //   roi_match / roi_sample / roi_gather   ProposalTargetLayer._sample_rois_pytorch (detector.py:60-167) over batched_box_iou (model/utils.py:371-458)
 //   roi_level_map                         LevelMapper.__call__ (level_mapper.py:47-59), the remap=True branch of ROIPool.forward (detector.py:222-236)
 //   roi_pool fwd / bwd                    ROIPool.normal_forward (detector.py:407-438) and ROIPool.rotated_forward (detector.py:264-404), 'pooling'
+//   roi_interp fwd / bwd                  ROIPool.rotated_forward (detector.py:264-404), 'interpolation'
 //   roi_loss fwd / bwd                    Classification_Model.compute_loss (detector.py:536-559) over RotatedCoder / AABBCoder.encode_single
 //   roi_decode                            RotatedCoder.decode_single (coder/rotated_coder.py:57-121), AABBCoder.decode_single (coder/AABB_coder.py:86-137)
 // fp32 throughout; every kernel writes only its own outputs for any input and clamps every index it forms;
@@ -31,6 +32,14 @@
 //   A value wins over a zero of the padding or of a masked point when equal; among values the first in (x, y, z) order wins; arg = -1 where a zero won.
 //   backward: one lane per output element; arg >= 0: the gradient goes to the voxel (axis-aligned) or through the point's eight corner weights (oriented),
 //           with fp32 atomic adds into a gradient the caller zeroed.  RoIs get no gradient.
+// Interpolation (oriented only; ROIPool.rotated_forward with 'interpolation', detector.py:264-404).  The oriented sampling grid above (sizes, points, the 8-corner
+//   value, 0 at a point outside the map), resampled to (ow, oh, od) as F.interpolate(mode="trilinear", align_corners=True) does.  Per axis, g points and O outputs:
+//   s = (g - 1) / (O - 1) if O > 1 else 0, src = s o, i0 = min((int)src, g - 1), i1 = i0 + (i0 < g - 1), l1 = clamp(src - i0, 0, 1), l0 = 1 - l1; out = sum
+//   over the 8 grid points (i0 | i1)^3 of their values times the products of l0 / l1: at most 64 map reads per channel.  O == 1 takes grid point 0 (the grid's
+//   corner, not its centre) and g == 1 the single point: the reference's behaviour.  No arg-max and no padding; points of weight 0 are not read.  Lanes as in
+//   the pooling forward.
+//   backward: one lane per output element; the geometry is formed again from the RoI (nothing but the RoIs and the level override is saved) and the gradient
+//           goes through the resampling weights and each point's eight corner weights with fp32 atomic adds into a gradient the caller zeroed.
 // Loss.  One lane per row m.  valid: 0 <= label < n_classes; positive: valid and label > 0.  objectness = sum over valid of (logsumexp(scores) -
 //   scores[label]) / #valid; box = sum over positive and columns of smooth_l1(delta - encode(gt_roi, roi); 1/9) / #positive; each 0 when its count is 0.
 //   Forward: per-workgroup partial sums in a fixed order, then a fixed-order pass of one workgroup; it also writes the targets [M][B] (0 in rows that are
@@ -384,6 +393,91 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_kernel(RoiPoolGeom G, long t
   for (int j = 0; j < 8; ++j) atomicAdd(d + vox[j], w[j] * g);
 }
 
+// ---- interpolation (oriented) ------------------------------------------------------------------------------------------------------------------
+struct RoiLerp { int i0, i1; float l0, l1; };          // one axis of F.interpolate(trilinear, align_corners=True): grid points i0 <= i1 < g and their weights
+__device__ __forceinline__ RoiLerp roi_lerp(int g, int O, int o) {
+  const float s = O > 1 ? (float)(g - 1) / (float)(O - 1) : 0.f, src = s * (float)o;
+  RoiLerp r;
+  r.i0 = min((int)src, g - 1);
+  r.i1 = r.i0 + (r.i0 < g - 1 ? 1 : 0);
+  r.l1 = fminf(fmaxf(src - (float)r.i0, 0.f), 1.f);
+  r.l0 = 1.f - r.l1;
+  return r;
+}
+// the up to 8 grid points of one output cell: fn(weight of the point, its eight corner voxels, their weights); points of weight 0 and masked points are left out
+template <class F>
+__device__ __forceinline__ void roi_interp_points(const RoiPoolGeom& G, const float* __restrict__ box, int lvl, int cell, F&& fn) {
+  const int W = pick4(G.W, lvl), H = pick4(G.H, lvl), D = pick4(G.D, lvl);
+  RoiAxis ax[3];
+  RoiPose P;
+  roi_axes_obb(G, box, lvl, ax, P);
+  const int oz = cell % G.od, oy = (cell / G.od) % G.oh, ox = cell / (G.od * G.oh);
+  const RoiLerp lx = roi_lerp(ax[0].s, G.ow, ox), ly = roi_lerp(ax[1].s, G.oh, oy), lz = roi_lerp(ax[2].s, G.od, oz);
+  for (int j = 0; j < 8; ++j) {
+    const bool a = j & 4, b = j & 2, c = j & 1;
+    const float wt = (a ? lx.l1 : lx.l0) * (b ? ly.l1 : ly.l0) * (c ? lz.l1 : lz.l0);
+    if (wt == 0.f) continue;
+    int vox[8];
+    float w[8];
+    if (!roi_point(P, a ? lx.i1 : lx.i0, b ? ly.i1 : ly.i0, c ? lz.i1 : lz.i0, W, H, D, vox, w)) continue;
+    fn(wt, vox, w);
+  }
+}
+
+__global__ __launch_bounds__(256) void roi_interp_fwd_kernel(RoiPoolGeom G, Ptr4<const float> maps, const float* __restrict__ rois, const int* __restrict__ lvl_override,
+                                                             float* __restrict__ out) {
+  const long m = blockIdx.x / G.bpr;
+  const int wi = (blockIdx.x - (int)(m * G.bpr)) * 256 + (int)threadIdx.x;
+  const int nchunk = (G.C + ROI_CPL - 1) / ROI_CPL;
+  if (m >= G.M || wi >= G.ncell * nchunk) return;
+  const int cell = wi % G.ncell, c0 = (wi / G.ncell) * ROI_CPL;
+  const int scene = (int)(m / G.R);
+  const float* __restrict__ roi = rois + m * 8;
+  const int lvl = roi_level(G, roi, lvl_override, m);
+  float acc[ROI_CPL];
+#pragma unroll
+  for (int c = 0; c < ROI_CPL; ++c) acc[c] = 0.f;
+  if (lvl >= 0) {
+    const long vol = (long)pick4(G.W, lvl) * pick4(G.H, lvl) * pick4(G.D, lvl);
+    const float* __restrict__ f = pick4(maps.p, lvl) + ((long)scene * G.C + c0) * vol;
+    roi_interp_points(G, roi + 1, lvl, cell, [&](float wt, const int (&vox)[8], const float (&w)[8]) {
+#pragma unroll
+      for (int c = 0; c < ROI_CPL; ++c) {
+        if (c0 + c < G.C) {
+          float v = 0.f;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v += f[c * vol + vox[j]] * w[j];
+          acc[c] += wt * v;
+        }
+      }
+    });
+  }
+#pragma unroll
+  for (int c = 0; c < ROI_CPL; ++c)
+    if (c0 + c < G.C) out[(m * G.C + c0 + c) * G.ncell + cell] = acc[c];
+}
+
+// one lane per output element, as the pooling backward; the geometry is formed again from the RoI
+__global__ __launch_bounds__(256) void roi_interp_bwd_kernel(RoiPoolGeom G, long total, const float* __restrict__ dout, const float* __restrict__ rois,
+                                                             const int* __restrict__ lvl_override, Ptr4<float> dmaps) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const long mc = e / G.ncell, m = mc / G.C;
+  const int cell = (int)(e - mc * G.ncell), c = (int)(mc - m * G.C);
+  const float* __restrict__ roi = rois + m * 8;
+  const int lvl = roi_level(G, roi, lvl_override, m);
+  if (lvl < 0) return;
+  float* __restrict__ d = pick4(dmaps.p, lvl);
+  if (!d) return;
+  const long vol = (long)pick4(G.W, lvl) * pick4(G.H, lvl) * pick4(G.D, lvl);
+  d += ((m / G.R) * G.C + c) * vol;
+  const float g = dout[e];
+  roi_interp_points(G, roi + 1, lvl, cell, [&](float wt, const int (&vox)[8], const float (&w)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) atomicAdd(d + vox[j], w[j] * (wt * g));
+  });
+}
+
 // ---- losses ----------------------------------------------------------------------------------------------------------------------------------
 // RotatedCoder.encode_single
 __device__ __forceinline__ void roi_encode_obb(const float* __restrict__ g, const float* __restrict__ e, float (&o)[8]) {
@@ -554,6 +648,28 @@ int k_roi_pool_bwd(int nlevels, const int* dims, const float* scales, int N, int
   if ((total + 255) / 256 >= (1L << 31) - 1) return -4;
   if (ncols == 7) hipLaunchKernelGGL(roi_pool_bwd_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, G, total, dout, argout, rois, lvl_override, P);
   else hipLaunchKernelGGL(roi_pool_bwd_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, G, total, dout, argout, rois, lvl_override, P);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
+
+int k_roi_interp_fwd(int nlevels, const int* dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* const* maps, const float* rois,
+                     const int* lvl_override, float* out, hipStream_t st) {
+  RoiPoolGeom G;
+  if (roi_pool_geom(nlevels, dims, scales, N, C, R, ow, oh, od, enlarge, G) || ncols != 7 || !all_set(nlevels, maps)) return -4;
+  hipLaunchKernelGGL(roi_interp_fwd_kernel, dim3((unsigned)(G.M * G.bpr)), dim3(256), 0, st, G, make_ptrs<const float>(nlevels, maps), rois, lvl_override, out);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
+
+int k_roi_interp_bwd(int nlevels, const int* dims, const float* scales, int N, int C, int R, int ncols, int ow, int oh, int od, float enlarge, const float* dout, const float* rois,
+                     const int* lvl_override, float* const* dmaps, hipStream_t st) {
+  RoiPoolGeom G;
+  if (roi_pool_geom(nlevels, dims, scales, N, C, R, ow, oh, od, enlarge, G) || ncols != 7 || !dmaps) return -4;
+  Ptr4<float> P;
+  for (int k = 0; k < 4; ++k) P.p[k] = k < nlevels ? dmaps[k] : nullptr;       // a null level takes no gradient
+  const long total = G.M * C * G.ncell;
+  if ((total + 255) / 256 >= (1L << 31) - 1) return -4;
+  hipLaunchKernelGGL(roi_interp_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, G, total, dout, rois, lvl_override, P);
   NMH_CHECK_LAUNCH();
   return 0;
 }

@@ -3,7 +3,8 @@ is one line):
 
   roi_targets_dense / ProposalTargetLayer   nerf_rpn/model/detector.py:12-167 over batched_box_iou (model/utils.py:371-458)
   LevelMapper                               model/level_mapper.py:21-77 (with _setup_scales)
-  ROIPool                                   detector.py:170-438: normal_forward and rotated_forward with feature_extracting_type="pooling", remap
+  ROIPool                                   detector.py:170-438: normal_forward and rotated_forward with feature_extracting_type "pooling" or (oriented
+                                            boxes) "interpolation", remap
   RCNN                                      detector.py:441-496, a torch module with the reference's state_dict keys (two small convs and two Linear layers: no hot path)
   roi_head_loss / roi_decode / RotatedCoder  detector.py:536-559 with coder/rotated_coder.py and coder/AABB_coder.py
   Classification_Model                      detector.py:499-627
@@ -34,8 +35,12 @@ Stated deviations from the reference:
   - roi_decode has no gradient (the reference's decode only feeds outputs); RoIs get no gradient from the pooling;
   - both losses are 0 with zero gradient when no row counts (the reference: NaN objectness without valid rows); labels outside [0, n_classes) are ignored rows
     (F.cross_entropy raises);
-  - feature_extracting_type="interpolation" and use_cuda=True raise NotImplementedError: the launcher (run_rpn_detect.py) never sets them, and the use_cuda
-    path returns features in level order rather than RoI order;
+  - feature_extracting_type="interpolation" with axis-aligned boxes raises NotImplementedError: there the reference silently max-pools and ignores the
+    switch (only rotated_forward reads it); any other string raises ValueError at construction (the reference: NameError on the first oriented forward);
+  - in an oriented RoI's interpolation an output size of 1 on an axis takes grid point 0 of that axis (the grid's corner, not its centre), as F.interpolate
+    with align_corners=True does: the reference's behaviour, kept;
+  - use_cuda=True raises NotImplementedError: that path returns features in level order rather than RoI order.  (The launcher, run_rpn_detect.py, hands
+    --feature_extracting_type to ROIPool (:103, :166-169); it parses --use_cuda and --remap (:97-100) but hands neither over);
   - other dtypes than fp32 raise TypeError, CPU tensors RuntimeError; more than MAX_LEVELS levels, MAX_SCENES scenes, MAX_ROWS rows per scene, MAX_CELLS
     output cells or MAX_CLASSES classes raise ValueError."""
 from __future__ import annotations
@@ -204,6 +209,24 @@ class _RoiPool(Function):
         return (None, None, None, *dmaps)
 
 
+class _RoiInterp(Function):
+    """(plan, oriented rois [N,R,8], level override or None, *maps) -> [N*R, C, ow, oh, od]; the backward forms the geometry again from the RoIs"""
+
+    @staticmethod
+    def forward(ctx, plan, rois, override, *maps):
+        out = ops.roi_interp_fwd(plan, maps, rois, override)
+        ctx.save_for_backward(rois, *([] if override is None else [override]))
+        ctx.plan = plan
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        rois, *rest = ctx.saved_tensors
+        dmaps = ops.roi_interp_bwd(ctx.plan, dout.contiguous(), rois, rest[0] if rest else None, ctx.needs_input_grad[3:])
+        return (None, None, None, *dmaps)
+
+
 class ROIPool(nn.Module):
     """The reference's constructor.  forward(feature, rois, original_size=None): feature = one (N, C, W, H, D) fp32 map per level (or the reference's list
     of per-scene lists of (C, W, H, D) maps); rois = [N, R, 1+6|7], or a list of per-scene [K, 1+6|7] ->  [N*R, C, ow, oh, od] in RoI order for a tensor,
@@ -213,10 +236,13 @@ class ROIPool(nn.Module):
                  remap=False, use_cuda=False):
         super().__init__()
         if use_cuda:
-            raise NotImplementedError("ROIPool(use_cuda=True) is not built: the launcher never sets it and that path returns features in level order, not RoI order; "
+            raise NotImplementedError("ROIPool(use_cuda=True) is not built: that path returns features in level order, not RoI order; "
                                       "rotated.ROIAlignRotated3D is available on its own")
-        if feature_extracting_type != "pooling":
-            raise NotImplementedError(f'ROIPool(feature_extracting_type={feature_extracting_type!r}) is not built; the launcher uses "pooling"')
+        if feature_extracting_type not in ("pooling", "interpolation"):
+            raise ValueError(f'ROIPool: feature_extracting_type must be "pooling" or "interpolation", got {feature_extracting_type!r}')
+        if feature_extracting_type == "interpolation" and not is_rotated_bbox:
+            raise NotImplementedError('ROIPool(feature_extracting_type="interpolation") exists for oriented boxes (is_rotated_bbox=True) only: with axis-aligned '
+                                      "boxes the reference max-pools whatever the type, and this module does not label that as interpolation")
         if not 1 <= len(spatial_scale) <= MAX_LEVELS:
             raise ValueError(f"ROIPool supports 1 to {MAX_LEVELS} levels, got {len(spatial_scale)}")
         self.output_size = tuple(int(v) for v in output_size)
@@ -271,7 +297,7 @@ class ROIPool(nn.Module):
         rois = rois.detach().contiguous()
         override = self.map_levels.levels32(rois[..., 1:]).reshape(-1).contiguous() if self.remap else None
         plan = ops.RoiPoolPlan(maps, self.spatial_scale, self.output_size, 1 + self.enlarge_scale, B)
-        out = _RoiPool.apply(plan, rois, override, *maps)
+        out = (_RoiInterp if self.feature_extracting_type == "interpolation" else _RoiPool).apply(plan, rois, override, *maps)
         if ks is None:
             return out
         R = rois.shape[1]

@@ -2145,6 +2145,23 @@ def roi_pool_bwd(plan, dout, arg, rois, level_override, need):
     return dmaps
 
 
+def roi_interp_fwd(plan, maps, rois, level_override):
+    """oriented rois [N,R,8] -> out [N*R,C,ow,oh,od]: the RoI's sampling grid resampled as F.interpolate(trilinear, align_corners=True)"""
+    _chk(*maps, rois, level_override)
+    R = rois.shape[1]
+    out = torch.empty((plan.N * R, plan.C, *plan.out), dtype=torch.float32, device=rois.device)
+    lib().call("nmh_roi_interp_fwd", plan.L, plan.dims, plan.scales, plan.N, plan.C, R, plan.ncols, *plan.out, plan.enlarge, _ptr_table(maps, plan.L), rois, level_override, out, _st())
+    return out
+
+
+def roi_interp_bwd(plan, dout, rois, level_override, need):
+    """-> per level the gradient of the map (zeroed here, then accumulated with fp32 atomics), None where need[k] is False"""
+    dmaps = [torch.zeros(s, dtype=torch.float32, device=dout.device) if n else None for s, n in zip(plan.shapes, need)]
+    lib().call("nmh_roi_interp_bwd", plan.L, plan.dims, plan.scales, plan.N, plan.C, rois.shape[1], plan.ncols, *plan.out, plan.enlarge, dout, rois, level_override,
+               _ptr_table(dmaps, plan.L), _st())
+    return dmaps
+
+
 def roi_loss_fwd(ncols, scores, deltas, labels, rois, gt_rois):
     """-> (scalars [4] = (loss_objectness, loss_rpn_box_reg, valid rows, positive rows), targets [M,ncols])"""
     _chk(scores, deltas, labels, rois, gt_rois)

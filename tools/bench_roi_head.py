@@ -2,13 +2,15 @@
 output 5^3, 2000 proposals and 32 boxes per scene, 256 sampled RoIs per scene, axis-aligned and oriented.
     python tools/bench_roi_head.py [reps]
 
-Timed with HIP events, median and minimum of `reps` >= 10 calls after 3 warm-up calls:
+Timed with HIP events, median and minimum (the interpolation rows: and maximum) of `reps` >= 10 calls after 3 warm-up calls:
   targets      detector.roi_targets_dense: matching + sampling + gather (no host synchronisation)
   pool fwd     detector.ROIPool forward;  pool bwd: its backward to the four maps (the zeroing of the gradients included)
   loss fwd+bwd detector.roi_head_loss and the gradients to both head outputs
 Next to each, a plain-torch composition of the same semantics (detector.py's header), written here from the semantics: the IoU matrix with torch.nonzero
 sampling per scene; a Python loop over the RoIs with a crop (or an 8-corner gather), F.pad and max_pool3d each, reading the sizes back from the device;
-cross_entropy and smooth_l1_loss over gathered rows, with autograd for the backward.  The composition's pooled features are compared with the kernel's."""
+cross_entropy and smooth_l1_loss over gathered rows, with autograd for the backward.  The composition's pooled features are compared with the kernel's.
+The oriented run adds the "interpolation" feature type on the same maps and RoIs: interp fwd, interp bwd and interp fwd+bwd next to the pooling rows of the
+same run and to a composition that loops over the RoIs with F.interpolate(trilinear, align_corners=True), as the reference does; median [min .. max]."""
 import math
 import os
 import statistics
@@ -36,7 +38,7 @@ def timed(fn, reps, warm=3):
         b.record()
     torch.cuda.synchronize()
     us = [a.elapsed_time(b) * 1e3 for a, b in ev]
-    return statistics.median(us), min(us)
+    return statistics.median(us), min(us), max(us)
 
 
 def make_inputs(rotated, seed=5):
@@ -81,8 +83,8 @@ def comp_targets(dense, levels, gt):
     return out
 
 
-def comp_pool(maps, rois, rotated):
-    """per-RoI loop, sizes read back from the device"""
+def comp_pool(maps, rois, rotated, interp=False):
+    """per-RoI loop, sizes read back from the device; interp (oriented): F.interpolate on the RoI's grid in place of the padded max-pool, as the reference does"""
     feats = []
     N, Rr = rois.shape[:2]
     host = rois.cpu()
@@ -111,6 +113,9 @@ def comp_pool(maps, rois, rotated):
                             v = f[:, a.clamp(0, W - 1).long(), bb.clamp(0, W - 1).long(), c.clamp(0, W - 1).long()]
                             crop = crop + v * (1 - (X - a).abs() * (Y - bb).abs() * (Z - c).abs())
                 crop = crop * mask / 8
+            if interp:
+                feats.append(F.interpolate(crop[None], size=OUT, mode="trilinear", align_corners=True)[0])
+                continue
             s = crop.shape[1:]
             if min(s) == 0:
                 feats.append(torch.zeros((C, *OUT), device=f.device))
@@ -126,6 +131,24 @@ def comp_loss(scores, deltas, labels, targets):
     pos = torch.nonzero(labels > 0).view(-1)
     reg = F.smooth_l1_loss(deltas[pos], targets[pos], beta=1 / 9, reduction="sum") / max(pos.numel(), 1)
     torch.autograd.grad(obj + reg, (scores, deltas))
+
+
+def interp_rows(maps, leaves, rois, dout, pool_t, pool_c, reps):
+    """feature_extracting_type="interpolation" on the same maps and RoIs, next to the pooling rows of this run and to the per-RoI F.interpolate composition"""
+    interp = detector.ROIPool(OUT, SCALES, ENLARGE, True, "interpolation")
+    feat = interp(leaves, rois)
+    with torch.no_grad():
+        ref = comp_pool([m.detach() for m in maps], rois, True, interp=True)
+    err = ((ref - feat.detach()).abs().max() / ref.abs().max()).item()
+    t = {"interp fwd": timed(lambda: interp(maps, rois), reps), "interp bwd": timed(lambda: torch.autograd.grad(feat, leaves, dout, retain_graph=True), reps),
+         "interp fwd+bwd": timed(lambda: torch.autograd.grad(interp(leaves, rois), leaves, dout), reps)}
+    c = {"interp fwd": timed(lambda: comp_pool([m.detach() for m in maps], rois, True, interp=True), 3, warm=1),
+         "interp fwd+bwd": timed(lambda: torch.autograd.grad(comp_pool(leaves, rois, True, interp=True), leaves, dout), 3, warm=1)}
+    row = lambda d: " | ".join(f"{k} median {v[0]:10.1f} us [{v[1]:.1f} .. {v[2]:.1f}]" for k, v in d.items())          # noqa: E731
+    print(f"  oriented interpolation: composition's features differ by {err:.2e} of the largest")
+    print("  oriented interpolation kernels:     " + row(t))
+    print("  oriented interpolation composition: " + row(c))
+    print("  oriented pooling, same run:         " + row({k: pool_t[k] for k in ("pool fwd", "pool bwd")}) + " | composition " + row({k: pool_c[k] for k in ("pool fwd", "pool fwd+bwd")}))
 
 
 def main(reps=10):
@@ -161,8 +184,10 @@ def main(reps=10):
         if not rotated:
             c["targets"] = timed(lambda: comp_targets(dense, levels, gt), reps)
         print(f"  {name}: sampled (fg, bg) {c2.tolist()}; composition's pooled features differ by {err:.2e} of the largest")
-        print(f"  {name} kernels:     " + " | ".join(f"{k} median {m:10.1f} us  min {b:10.1f} us" for k, (m, b) in t.items()))
-        print(f"  {name} composition: " + " | ".join(f"{k} median {m:10.1f} us  min {b:10.1f} us" for k, (m, b) in c.items()))
+        print(f"  {name} kernels:     " + " | ".join(f"{k} median {m:10.1f} us  min {b:10.1f} us" for k, (m, b, _) in t.items()))
+        print(f"  {name} composition: " + " | ".join(f"{k} median {m:10.1f} us  min {b:10.1f} us" for k, (m, b, _) in c.items()))
+        if rotated:
+            interp_rows(maps, leaves, rois, dout, t, c, reps)
 
 
 if __name__ == "__main__":
