@@ -4,7 +4,8 @@ adjoint, the NCDHW <-> channels-last transposes, add_inplace).
 
 Conventions: inputs are rounded to the storage dtype first (`q`), the reference is float64 (tests/_conv_layer_ref.py), the check is tests/_metrics.assert_close
 (max-norm, relative L2 and elementwise) at the project's tolerances TOL -- except the pure moves and single additions of sections 6 and 7, which have one
-correctly rounded result and are held to torch.equal.  Every conv, weight-gradient and GEMM case names the dispatch line it reaches (`dispatch_nt` of
+correctly rounded result and are held to torch.equal, and sections 2b and 2c, which hold single kernels on bf16-rounded operands to a measured rounding bound
+far below TOL (one lost voxel or tap must fail).  Every conv, weight-gradient and GEMM case names the dispatch line it reaches (`dispatch_nt` of
 csrc/gemm.hip, the branch of ops.conv3d_k3_wgrad, ops.use_conv64); where the rule is visible from Python the test asserts it, and the C entry point that
 ran is read off a spy on the library's call()."""
 import pytest
@@ -130,6 +131,7 @@ WGRAD_CASES = [
     (BF16, 1, 16, 16, 16,  72,  40, IGEMM),    # 4096 voxels, channel counts divisible by neither 48 nor 64: the fall-through
     (F32,  1, 16, 16, 16,  72,  40, IGEMM),
     (BF16, 1, 16, 16, 16,  96, 192, HALO48),   # 48-block kernel (2 x 4 block pairs)
+    (BF16, 2, 18, 18, 18, 192,  96, HALO48),   # 48-block kernel, 8 sub-problems of 16 workgroups on 2 x 50 tiles, ragged on every axis (section 2b holds it to HALO_EPS)
 ]
 
 
@@ -164,6 +166,123 @@ def test_bias_gradient_added_onto_a_nonzero_buffer(M, N, dt):
     db = torch.full((N,), -0.75, device="cuda")
     ops.bias_grad(dev(dy, dt), db, M, N)
     check(db, dy.double().sum(0) - 0.75, dt, f"bias_grad {M}x{N}")
+
+
+# ---- 2b. the 48-block halo weight gradient in channel sub-problem mode, held to a rounding bound ----------------------------------------------------
+# launch_wgrad_halo (csrc/conv48.hip) with nsub = (Cin / 48) (Cout / 48) > 1: gridDim.y = nsub, nb = 128 / nsub workgroups per sub-problem (floored at 1,
+# clamped to the number of 4x4x16 tiles), workgroup j of a sub-problem walks tiles j, j + nb, ... of the B * tz * ty * tx tile sequence (samples back to back),
+# its partial goes to workspace slot sub * nb + j and the reduce kernel sums the nb slots of a sub-problem onto dW.
+#
+# The bound.  dW is fp32 and the operands hold bf16 values, so every product is exact in fp32 and the result differs from float64 by the accumulation order
+# only: |a - b| <= HALO_EPS * rms(b) for EVERY entry.  One voxel dropped from (or counted twice in) the contraction moves entries by about |x dy| / sqrt(L) of
+# rms (L = B D H W terms of unit variance), so HALO_EPS must stay below 0.1 / sqrt(L) of the case at hand -- asserted -- for a single lost voxel to fail; TOL[bf16]
+# = 3e-2 would let it through at every L >= 10 or so.  HALO_EPS is 4 x the worst value measured over the cases below on an MI355X (the measured figures are at
+# HALO_MEASURED; float32 F.conv3d on the host sits at 6e-6 ... 1.6e-5).
+HALO_SUB_CASES = [
+    # B   D   H   W  Cin Cout   nsub  nb  tiles
+    (1,  5,  6, 20,  96,  96),  #  4  32 -> 8   8: ragged on every axis; nb clamped to the tile count
+    (2,  6, 10, 20, 192,  96),  #  8  16       24: uneven shares (workgroups 0..7 two tiles, 8..15 one), and the stride of 16 takes workgroup j from sample 0 (tile j) into sample 1 (tile j + 16)
+    (3,  3,  5, 40,  96, 192),  #  8  16       18: D below one tile, x = 2.5 tiles (the 40^3 level's), three samples
+    (1,  9,  9, 17, 384, 192),  # 32   4       18: four or five tiles per workgroup through the prefetch loop
+    (1,  4,  4, 16, 576, 576),  # 144  1        1: the nb = 1 floor, 144 of the 256 workspace slots
+    (1,  2,  3,  5,  48,  96),  #  2  64 -> 1   1: the volume inside one tile on every axis
+]
+# max|a - b| / rms(b) on an MI355X, in the order of HALO_SUB_CASES: 8.6e-7, 7.1e-7, 6.2e-7, 1.66e-6, 1.23e-6, 3.8e-7; the dispatcher's 18^3 case 1.44e-6;
+# against caps of 4.1e-3, 2.0e-3, 2.4e-3, 2.7e-3, 6.3e-3, 1.8e-2 and 9.3e-4
+HALO_MEASURED = 1.66e-6        # the worst of them
+HALO_EPS = 4 * HALO_MEASURED
+
+
+def _halo_cap(B, D, H, W):
+    return 0.1 / (B * D * H * W) ** 0.5
+
+
+def _assert_rounding_bound(a, b, eps, cap, name, ulp=0.0):
+    """|a - b| <= ulp * |b| + eps * rms(b) for every entry, with eps <= cap (the caller's derivation of what one lost term would move)"""
+    assert eps <= cap, f"{name}: eps {eps:.2e} is no sharper than the cap {cap:.2e}"
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    assert a.shape == b.shape
+    rms = b.pow(2).mean().sqrt().item()
+    diff = (a - b).abs()
+    need = ((diff - ulp * b.abs()).clamp_min(0).max() / rms).item()
+    print(f"  [{name}] max|a-b| / rms {diff.max().item() / rms:.2e}  eps needed {need:.2e}  (eps {eps:.2e}, cap {cap:.2e})")
+    assert need <= eps, f"{name}: |a-b| exceeds {ulp:g} |b| + eps rms(b): needs eps {need:.3e} > {eps:.3e}"
+
+
+def _wgrad_halo_direct(ops, c, ws):
+    """nmh_conv3d_k3_wgrad_halo on the case's bf16 operands, added onto a dW filled with 0.5"""
+    B, Cin, D, H, W = c["x"].shape
+    Cout = c["dy"].shape[1]
+    dW = torch.full((Cout, Cin, 3, 3, 3), 0.5, device="cuda")
+    ops.lib().call("nmh_conv3d_k3_wgrad_halo", dev(cl(c["dy"]), BF16), dev(cl(c["x"]), BF16), dW, ws, B, D, H, W, Cin, Cout, torch.cuda.current_stream().cuda_stream)
+    return dW
+
+
+def _halo_ws(ops):
+    """a workspace of the documented size, NaN in every slot: a slot the reduce reads and the launch did not write shows"""
+    return torch.full((ops.lib().call("nmh_conv3d_k3_c48_wgrad_ws_floats"),), float("nan"), device="cuda")
+
+
+@pytest.mark.parametrize("case", HALO_SUB_CASES, ids=lambda c: _conv_id((BF16,) + c))
+def test_halo_weight_gradient_sub_problem_mode(case):
+    ops = _ops()
+    B, D, H, W, Cin, Cout = case
+    assert (Cin // 48) * (Cout // 48) > 1 and Cin % 48 == 0 and Cout % 48 == 0 and (Cin // 48) * (Cout // 48) <= 256
+    c = R.conv_case(BF16, *case)
+    dW = _wgrad_halo_direct(ops, c, _halo_ws(ops))
+    _assert_rounding_bound(dW, c["dw"] + 0.5, HALO_EPS, _halo_cap(B, D, H, W), f"wgrad_halo {_conv_id((BF16,) + case)}")
+
+
+def test_halo_weight_gradient_ignores_stale_partials():
+    """the fourth case (32 sub-problems x 4 workgroups: 128 slots) and then the first (4 x 8: 32 slots) on the SAME workspace, nothing cleared in between:
+    the second launch's reduce must sum its own 8 slots per sub-problem and none of the larger launch's"""
+    ops = _ops()
+    ws = _halo_ws(ops)
+    big, small = HALO_SUB_CASES[3], HALO_SUB_CASES[0]
+    cb, cs = R.conv_case(BF16, *big), R.conv_case(BF16, *small)
+    dWb = _wgrad_halo_direct(ops, cb, ws)
+    dWs = _wgrad_halo_direct(ops, cs, ws)
+    _assert_rounding_bound(dWb, cb["dw"] + 0.5, HALO_EPS, _halo_cap(*big[:4]), "wgrad_halo, first on the workspace")
+    _assert_rounding_bound(dWs, cs["dw"] + 0.5, HALO_EPS, _halo_cap(*small[:4]), "wgrad_halo, second on the same workspace")
+
+
+def test_halo_weight_gradient_through_the_dispatcher_at_the_rounding_bound(entries):
+    """WGRAD_CASES' 18^3 case once more, through ops.conv3d_k3_wgrad and its own workspace, held to HALO_EPS instead of TOL"""
+    ops = _ops()
+    case = (2, 18, 18, 18, 192, 96)
+    c = R.conv_case(BF16, *case)
+    dW = torch.full((96, 192, 3, 3, 3), 0.5, device="cuda")
+    ops.conv3d_k3_wgrad(dev(cl(c["dy"]), BF16), dev(cl(c["x"]), BF16), dW)
+    assert entries[-1] == HALO48
+    _assert_rounding_bound(dW, c["dw"] + 0.5, HALO_EPS, _halo_cap(*case[:4]), "wgrad_halo 18^3 through the dispatcher")
+
+
+# ---- 2c. the 48-block conv (ops.conv3d_k3_c48mb), forward and input gradient, held to a rounding bound ------------------------------------------------
+# bf16 outputs of an fp32 accumulation over 27 * C exact products: |a - b| <= 2^-8 |b| + C48MB_EPS * rms(b), half a bf16 ulp (the ulp of a value in
+# [2^e, 2^(e+1)) is 2^(e-7) <= 2^-7 |b|) plus accumulation noise.  One dropped tap moves an output by about 1 / sqrt(27 C) of rms; C48MB_EPS must stay below a
+# tenth of that -- asserted with the larger of the two channel counts, C = 192, for both directions.  C48MB_EPS is 4 x the worst value measured on an MI355X.
+C48MB_SHARP_CASES = [(2, 6, 10, 20, 192, 96), (1, 12, 9, 40, 96, 192)]
+# eps needed on an MI355X (max of (|a - b| - 2^-8 |b|) / rms(b)): forward 4.9e-7 and 6.6e-7, input gradient 2.5e-7 and 6.2e-7; the cap is 1.39e-3
+C48MB_MEASURED = 6.6e-7        # the worst of them
+C48MB_EPS = 4 * C48MB_MEASURED
+
+
+@pytest.mark.parametrize("case", C48MB_SHARP_CASES, ids=lambda c: _conv_id((BF16,) + c))
+def test_conv48_multiblock_at_the_rounding_bound(case, entries):
+    ops = _ops()
+    B, D, H, W, Cin, Cout = case
+    c = R.conv_case(BF16, *case)
+    w = nn.Parameter(c["w"].cuda())
+    P = _pack([("wkm", w, "C48_F"), ("wkmd", w, "C48_D")], BF16)
+    cap = 0.1 / (27 * max(Cin, Cout)) ** 0.5
+    y = ops.conv3d_k3_c48mb(dev(cl(c["x"]), BF16), P["wkm"], Cout)
+    yref = c["y"] - c["b"].double()[None, :, None, None, None]
+    check(ncdhw(y), yref, BF16, "conv48mb forward")
+    _assert_rounding_bound(ncdhw(y), yref, C48MB_EPS, cap, f"conv48mb forward {_conv_id((BF16,) + case)}", ulp=2.0 ** -8)
+    dx = ops.conv3d_k3_c48mb(dev(cl(c["dy"]), BF16), P["wkmd"], Cin)
+    check(ncdhw(dx), c["dx"], BF16, "conv48mb input gradient")
+    _assert_rounding_bound(ncdhw(dx), c["dx"], C48MB_EPS, cap, f"conv48mb input gradient {_conv_id((BF16,) + case)}", ulp=2.0 ** -8)
+    assert [e for e in entries if "conv3d" in e] == ["nmh_conv3d_k3_c48mb"] * 2
 
 
 # ---- 3. the 64-channel-block conv with the bias epilogue --------------------------------------------------------------------------------------------
