@@ -729,43 +729,47 @@ int nmh_rpn_loss_fwd(int nlevels, const int* level_dims, int N, int ncols, const
                      const float* targets, float* partials, float* scalars, void* stream) {
   CLR();
   REQ(level_dims, objectness, regression, flags, targets, partials, scalars);
-  return k_rpn_loss_fwd(nlevels, level_dims, N, ncols, objectness, regression, flags, targets, partials, scalars, ST);
+  return k_rpn_loss_fwd(nlevels, level_dims, nullptr, N, ncols, -1, objectness, regression, flags, targets, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, partials, scalars, ST);
 }
 int nmh_rpn_loss_bwd(int nlevels, const int* level_dims, int N, int ncols, const float* const* objectness, const float* const* regression, const unsigned char* flags,
                      const float* targets, const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj, float* const* dreg, void* stream) {
   CLR();
   REQ(level_dims, objectness, regression, flags, targets, scalars, dobj, dreg);
-  return k_rpn_loss_bwd(nlevels, level_dims, N, ncols, objectness, regression, flags, targets, scalars, g_obj, g_reg, dobj, dreg, ST);
+  return k_rpn_loss_bwd(nlevels, level_dims, nullptr, N, ncols, -1, objectness, regression, flags, targets, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, scalars, g_obj, g_reg, nullptr,
+                        dobj, dreg, ST);
 }
 int nmh_rpn_iou_loss_fwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int loss_type, const float* const* objectness, const float* const* regression,
                          const unsigned char* flags, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, float* partials, float* scalars,
                          void* stream) {
   CLR();
   REQ(level_dims, base_half, objectness, regression, flags, box_offsets, matched_idxs, partials, scalars);
-  return k_rpn_iou_loss_fwd(nlevels, level_dims, base_half, N, ncols, loss_type, objectness, regression, flags, boxes, box_offsets, ori_sizes, matched_idxs, partials, scalars, ST);
+  if (loss_type < 0) return -4;
+  return k_rpn_loss_fwd(nlevels, level_dims, base_half, N, ncols, loss_type, objectness, regression, flags, nullptr, boxes, box_offsets, ori_sizes, matched_idxs, nullptr, 0.f, partials,
+                        scalars, ST);
 }
 int nmh_rpn_iou_loss_bwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int loss_type, const float* const* objectness, const float* const* regression,
                          const unsigned char* flags, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* scalars, const float* g_obj,
                          const float* g_reg, float* const* dobj, float* const* dreg, void* stream) {
   CLR();
   REQ(level_dims, base_half, objectness, regression, flags, box_offsets, matched_idxs, scalars, dobj, dreg);
-  return k_rpn_iou_loss_bwd(nlevels, level_dims, base_half, N, ncols, loss_type, objectness, regression, flags, boxes, box_offsets, ori_sizes, matched_idxs, scalars, g_obj, g_reg, dobj,
-                            dreg, ST);
+  if (loss_type < 0) return -4;
+  return k_rpn_loss_bwd(nlevels, level_dims, base_half, N, ncols, loss_type, objectness, regression, flags, nullptr, boxes, box_offsets, ori_sizes, matched_idxs, nullptr, 0.f, scalars,
+                        g_obj, g_reg, nullptr, dobj, dreg, ST);
 }
 int nmh_rpn_loss2d_fwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, const float* const* objectness, const float* const* regression,
                        const unsigned char* flags, const float* targets, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* cams,
                        float res, float* partials, float* scalars, void* stream) {
   CLR();
   REQ(level_dims, base_half, objectness, regression, flags, targets, box_offsets, matched_idxs, cams, partials, scalars);
-  return k_rpn_loss2d_fwd(nlevels, level_dims, base_half, N, ncols, -1, objectness, regression, flags, targets, boxes, box_offsets, ori_sizes, matched_idxs, cams, res, partials, scalars, ST);
+  return k_rpn_loss_fwd(nlevels, level_dims, base_half, N, ncols, -1, objectness, regression, flags, targets, boxes, box_offsets, ori_sizes, matched_idxs, cams, res, partials, scalars, ST);
 }
 int nmh_rpn_loss2d_bwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, const float* const* objectness, const float* const* regression,
                        const unsigned char* flags, const float* targets, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* cams,
                        float res, const float* scalars, const float* g_obj, const float* g_reg, const float* g_2d, float* const* dobj, float* const* dreg, void* stream) {
   CLR();
   REQ(level_dims, base_half, objectness, regression, flags, targets, box_offsets, matched_idxs, cams, scalars, dobj, dreg);
-  return k_rpn_loss2d_bwd(nlevels, level_dims, base_half, N, ncols, -1, objectness, regression, flags, targets, boxes, box_offsets, ori_sizes, matched_idxs, cams, res, scalars, g_obj,
-                          g_reg, g_2d, dobj, dreg, ST);
+  return k_rpn_loss_bwd(nlevels, level_dims, base_half, N, ncols, -1, objectness, regression, flags, targets, boxes, box_offsets, ori_sizes, matched_idxs, cams, res, scalars, g_obj,
+                        g_reg, g_2d, dobj, dreg, ST);
 }
 int nmh_rpn_iou_loss2d_fwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int loss_type, const float* const* objectness, const float* const* regression,
                            const unsigned char* flags, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* cams, float res,
@@ -773,8 +777,8 @@ int nmh_rpn_iou_loss2d_fwd(int nlevels, const int* level_dims, const float* base
   CLR();
   REQ(level_dims, base_half, objectness, regression, flags, box_offsets, matched_idxs, cams, partials, scalars);
   if (loss_type < 0) return -4;
-  return k_rpn_loss2d_fwd(nlevels, level_dims, base_half, N, ncols, loss_type, objectness, regression, flags, nullptr, boxes, box_offsets, ori_sizes, matched_idxs, cams, res, partials,
-                          scalars, ST);
+  return k_rpn_loss_fwd(nlevels, level_dims, base_half, N, ncols, loss_type, objectness, regression, flags, nullptr, boxes, box_offsets, ori_sizes, matched_idxs, cams, res, partials,
+                        scalars, ST);
 }
 int nmh_rpn_iou_loss2d_bwd(int nlevels, const int* level_dims, const float* base_half, int N, int ncols, int loss_type, const float* const* objectness, const float* const* regression,
                            const unsigned char* flags, const float* boxes, const int* box_offsets, const int* ori_sizes, const int* matched_idxs, const float* cams, float res,
@@ -782,8 +786,8 @@ int nmh_rpn_iou_loss2d_bwd(int nlevels, const int* level_dims, const float* base
   CLR();
   REQ(level_dims, base_half, objectness, regression, flags, box_offsets, matched_idxs, cams, scalars, dobj, dreg);
   if (loss_type < 0) return -4;
-  return k_rpn_loss2d_bwd(nlevels, level_dims, base_half, N, ncols, loss_type, objectness, regression, flags, nullptr, boxes, box_offsets, ori_sizes, matched_idxs, cams, res, scalars,
-                          g_obj, g_reg, g_2d, dobj, dreg, ST);
+  return k_rpn_loss_bwd(nlevels, level_dims, base_half, N, ncols, loss_type, objectness, regression, flags, nullptr, boxes, box_offsets, ori_sizes, matched_idxs, cams, res, scalars,
+                        g_obj, g_reg, g_2d, dobj, dreg, ST);
 }
 int nmh_proj2d_cameras(float res, float* cams) {
   CLR();

@@ -327,24 +327,16 @@ long k_rpn_num_blocks(int nlevels, const int* dims, int N);
 int k_rpn_assign(int nlevels, const int* dims, const float* base, int N, int ncols, const float* boxes, const int* offs, const int* ori, float fg, float bg, unsigned* gtmax,
                  float* labels, int* midx, float* targets, hipStream_t st);
 int k_rpn_sample(int N, long n, const float* labels, int batch, int want_pos, long* rng, unsigned char* flags, int* counts, hipStream_t st);
-int k_rpn_loss_fwd(int nlevels, const int* dims, int N, int ncols, const float* const* obj, const float* const* reg, const unsigned char* flags, const float* targets, float* partials,
-                   float* scalars, hipStream_t st);
-int k_rpn_loss_bwd(int nlevels, const int* dims, int N, int ncols, const float* const* obj, const float* const* reg, const unsigned char* flags, const float* targets,
-                   const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj, float* const* dreg, hipStream_t st);
-// the IoU-type box losses over the decoded proposals (ncols 8 only; loss_type 0 iou, 1 linear_iou, 2 giou, 3 diou); boxes: DEVICE [offs[N]][7]; midx: DEVICE [N][n]
-int k_rpn_iou_loss_fwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
-                       const float* boxes, const int* offs, const int* ori, const int* midx, float* partials, float* scalars, hipStream_t st);
-int k_rpn_iou_loss_bwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
-                       const float* boxes, const int* offs, const int* ori, const int* midx, const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj,
-                       float* const* dreg, hipStream_t st);
-// the losses with the 2-D projection term: loss_type < 0 smooth-L1 (ncols 6 | 8, targets required), else the IoU types (ncols 8); boxes DEVICE [offs[N]][6|7];
-// cams: HOST [48]; partials DEVICE [5 nblocks]; scalars DEVICE [5] = (objectness, box, sampled anchors, 2-D, sampled positives)
-int k_rpn_loss2d_fwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
-                     const float* targets, const float* boxes, const int* offs, const int* ori, const int* midx, const float* cams, float res, float* partials, float* scalars,
-                     hipStream_t st);
-int k_rpn_loss2d_bwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
-                     const float* targets, const float* boxes, const int* offs, const int* ori, const int* midx, const float* cams, float res, const float* scalars,
-                     const float* g_obj, const float* g_reg, const float* g_2d, float* const* dobj, float* const* dreg, hipStream_t st);
+// the losses.  loss_type < 0: smooth-L1 on targets (ncols 6 | 8); else 0 iou, 1 linear_iou, 2 giou, 3 diou over the decoded proposals (ncols 8 only; targets unused).
+// base, boxes DEVICE [offs[N]][6|7], offs, midx DEVICE [N][n]: read by the IoU types and by the 2-D term, else unused.  cams: HOST [48], or NULL for the losses without the
+// 2-D projection term: partials DEVICE [3 nblocks], scalars DEVICE [3] = (objectness, box, sampled anchors); with it: res > 0, partials [5 nblocks], scalars [5] =
+// (objectness, box, sampled anchors, 2-D, sampled positives), and g_2d
+int k_rpn_loss_fwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
+                   const float* targets, const float* boxes, const int* offs, const int* ori, const int* midx, const float* cams, float res, float* partials, float* scalars,
+                   hipStream_t st);
+int k_rpn_loss_bwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
+                   const float* targets, const float* boxes, const int* offs, const int* ori, const int* midx, const float* cams, float res, const float* scalars,
+                   const float* g_obj, const float* g_reg, const float* g_2d, float* const* dobj, float* const* dreg, hipStream_t st);
 // ---- proj2d.hip (the 2-D projection term on rows of boxes; cams: HOST [48] = the fused K [R|t] of four cameras, row-major 3x4) ----
 int k_proj2d_fwd(const float* pred, const float* target, long n, int ncols, const float* cams, float* terms, hipStream_t st);
 int k_proj2d_bwd(const float* pred, const float* target, const float* g_terms, long n, int ncols, const float* cams, float* dpred, hipStream_t st);

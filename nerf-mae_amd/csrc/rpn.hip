@@ -33,7 +33,11 @@
 //   objectness = sum over flags != 0 of bce_with_logits(x, flag == 1) / s;  box_reg = sum over flags == 1 and c of smooth_l1(pred - target; 1/9) / s;
 //   both 0 when s == 0 (the reference gives NaN there).  Forward: per-workgroup partial sums, then a fixed-order pass of one workgroup.  Backward: one
 //   pass that writes every element of both gradients, exactly 0 where flag == 0.
-// IoU-type box losses (rpn_iou_loss: RotatedIOULoss over the decoded proposals, rpn.py:133-164, 214-217, 400-417, 518-520; 8 columns only).  The same
+//   One forward and one backward kernel template, rpn_loss_fwd_kernel / rpn_loss_bwd_kernel<TERM, P2D>, over the five box terms (smooth-L1 with 6 or 8 columns,
+//   iou / linear_iou, giou, diou) and the 2-D projection term as a compile-time flag, and one final kernel over 3 or 5 sums.  What the variants do not share is
+//   under `if constexpr`: the instantiations without the flag are the kernels without the term (smooth-L1: no base table in LDS, no barrier, three sums), and the
+//   eight nmh_rpn_*loss* entries of the C ABI forward to one launcher pair.
+// IoU-type box losses (nmh_rpn_iou_loss: RotatedIOULoss over the decoded proposals, rpn.py:133-164, 214-217, 400-417, 518-520; 8 columns only).  The same
 //   lane map, sums and objectness; the box term of a lane with flag == 1 is taken between A = rpn_decode_obb(its 8 deltas, its anchor) and B = the scene's
 //   box row max(matched_idxs, 0), both (x, y, z, w, l, h, theta):  iou -log((inter3d + 1) / (u3d + 1)), linear_iou 1 - that ratio, giou / diou
 //   obb_pair_loss<OBB_GIOU_SMALLEST | OBB_DIOU_SMALLEST> (obb_geom.hpp), summed and divided by s.  Only flagged positives decode (the reference decodes
@@ -41,10 +45,11 @@
 //   lies in the padding (either is possible only with flags that the sampler did not draw), contributes 0 and has zero box gradient.  Backward:
 //   g_reg / s through obb_pair_grad (box A only) and rpn_decode_obb_bwd (rpn_decode.hpp); every element of both gradients is written, dreg exactly 0
 //   where flag != 1.
-// 2-D projection term (rpn_loss2d, rpn_iou_loss2d: the third return of compute_loss, rpn.py:421-453), opt-in, for every box loss above and both box kinds.
+// 2-D projection term (nmh_rpn_loss2d, nmh_rpn_iou_loss2d: the third return of compute_loss, rpn.py:421-453), opt-in, for every box loss above and both box kinds.
 //   The same lane map and the same first two sums; a lane with flag == 1 adds T (proj2d.hpp) between the UNCLIPPED decode of its deltas (rpn_decode_aabb /
 //   rpn_decode_obb) and its matched box row, under the cameras of res = max(mesh_size).  P = number of flags == 1;  loss_2d = sum T / P / res, 0 when P == 0
-//   (the reference gives NaN).  A flagged positive without a box row or in the padding counts in P and contributes 0 (as for the IoU types).  scalars =
+//   (the reference gives NaN).  A flagged positive without a box row or in the padding counts in P and contributes 0 to the 2-D sum and, under the IoU types,
+//   to the box sum; under smooth-L1 it still adds its smooth-L1 term, which needs no box row.  scalars =
 //   (objectness, box, sampled anchors, 2-D, P).  Backward: one pass, g_2d / P / res through proj2d_term_grad and the decode's backward, added to the box
 //   term's gradient in registers, so that every element of both gradients is still written exactly once.
 #include "common.hpp"
@@ -55,11 +60,19 @@
 #include "rpn_shared.hpp"
 #include "rpn_decode.hpp"
 #include "proj2d.hpp"
+#include <type_traits>
 
 namespace {
 
 constexpr int RPN_CHUNK = 64;
-struct RpnOffs { int off[NMH_FCOS_MAX_SCENES + 1]; };
+struct RpnOffs { int off[NMH_FCOS_MAX_SCENES + 1]; };   // kernel argument, by value: scene b owns box rows off[b] .. off[b+1]-1; the entries past N repeat off[N]
+// offs: HOST [N+1], starting at 0 and not descending (else -4)
+int make_offs(int N, const int* offs, RpnOffs& S) {
+  if (!offs || offs[0] != 0) return -4;
+  for (int b = 0; b < N; ++b) if (offs[b + 1] < offs[b]) return -4;
+  for (int b = 0; b <= NMH_FCOS_MAX_SCENES; ++b) S.off[b] = offs[b < N ? b : N];
+  return 0;
+}
 
 template <bool ORIENTED>
 __device__ __forceinline__ Box6 rpn_gt(const float* __restrict__ b) {
@@ -267,66 +280,15 @@ __device__ __forceinline__ RHead rpn_head_where(const RpnGeom& G) {
   return r;
 }
 
-template <int C>
-__global__ __launch_bounds__(256) void rpn_loss_fwd_kernel(RpnGeom G, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
-                                                           const float* __restrict__ targets, float* __restrict__ partials) {
-  const RHead w = rpn_head_where(G);
-  float v[3] = {0.f, 0.f, 0.f};         // objectness, box regression, sampled anchors
-  const int f = w.active ? flags[w.p] : 0;
-  if (f != 0) {
-    const float x = pick4(obj.p, w.lvl)[(long)w.scene * w.A * w.nloc + w.j];
-    v[0] = fmaxf(x, 0.f) - (f == 1 ? x : 0.f) + log1pf(expf(-fabsf(x)));
-    v[2] = 1.f;
-    if (f == 1) {
-      const float* __restrict__ rp = pick4(reg.p, w.lvl) + ((long)w.scene * w.A + w.a) * C * w.nloc + w.loc;
-#pragma unroll
-      for (int k = 0; k < C; ++k) v[1] += rpn_sl1(rp[(long)k * w.nloc] - targets[w.p * C + k]);
-    }
-  }
-  block_sum_fixed(v, partials + 3 * (long)blockIdx.x);
-}
+// TERM: what the box loss is.  Smooth-L1 on the encoded targets (6 or 8 columns), or an IoU type between the decoded proposal and the matched box row (8 columns).
+enum { RPN_BOX_SL1_AABB = 0, RPN_BOX_SL1_OBB = 1, RPN_BOX_IOU = 2, RPN_BOX_GIOU = 3, RPN_BOX_DIOU = 4 };
+template <int TERM> struct Rpn2d {
+  static constexpr bool ORIENTED = TERM != RPN_BOX_SL1_AABB, SL1 = TERM <= RPN_BOX_SL1_OBB;
+  static constexpr int C = ORIENTED ? 8 : 6, NC = ORIENTED ? 7 : 6;
+  static constexpr int MODE = TERM == RPN_BOX_GIOU ? OBB_GIOU_SMALLEST : (TERM == RPN_BOX_DIOU ? OBB_DIOU_SMALLEST : OBB_IOU);
+};
 
-// one workgroup: fixed-order sum of the per-workgroup partials -> scalars = (objectness loss, box loss, number of sampled anchors)
-__global__ __launch_bounds__(256) void rpn_loss_final_kernel(const float* __restrict__ partials, int nblocks, float* __restrict__ scalars) {
-  float sum[3];
-  final_sum_fixed(partials, nblocks, sum);
-  if (threadIdx.x != 0) return;
-  const float cnt = sum[2];
-  scalars[0] = cnt > 0.f ? sum[0] / cnt : 0.f;
-  scalars[1] = cnt > 0.f ? sum[1] / cnt : 0.f;
-  scalars[2] = cnt;
-}
-
-template <int C>
-__global__ __launch_bounds__(256) void rpn_loss_bwd_kernel(RpnGeom G, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
-                                                           const float* __restrict__ targets, const float* __restrict__ scalars, const float* __restrict__ g_obj,
-                                                           const float* __restrict__ g_reg, Ptr4<float> dobj, Ptr4<float> dreg) {
-  const RHead w = rpn_head_where(G);
-  if (!w.active) return;
-  const long at = (long)w.scene * w.A * w.nloc + w.j, rat = ((long)w.scene * w.A + w.a) * C * w.nloc + w.loc;
-  const int f = flags[w.p];
-  const float cnt = scalars[2];
-  float go = 0.f, gr[C];
-#pragma unroll
-  for (int k = 0; k < C; ++k) gr[k] = 0.f;
-  if (f != 0 && cnt > 0.f) {
-    const float x = pick4(obj.p, w.lvl)[at];
-    go = (sigmoid_stable(x) - (f == 1 ? 1.f : 0.f)) * (g_obj ? g_obj[0] : 0.f) / cnt;
-    if (f == 1) {
-      const float* __restrict__ rp = pick4(reg.p, w.lvl) + rat;
-      const float sc = (g_reg ? g_reg[0] : 0.f) / cnt;
-#pragma unroll
-      for (int k = 0; k < C; ++k) gr[k] = rpn_sl1_grad(rp[(long)k * w.nloc] - targets[w.p * C + k]) * sc;
-    }
-  }
-  pick4(dobj.p, w.lvl)[at] = go;
-  float* __restrict__ dp = pick4(dreg.p, w.lvl) + rat;
-#pragma unroll
-  for (int k = 0; k < C; ++k) dp[(long)k * w.nloc] = gr[k];
-}
-
-// ---- IoU-type box losses (oriented only) ---------------------------------------------------------------------------------------------------
-// the box term of one flagged positive and its gradient over the 8 deltas: A = the decode of the anchor's deltas, B = the matched box row
+// the IoU-type box term of one flagged positive and its gradient over the 8 deltas: A = the decode of the anchor's deltas, B = the matched box row
 template <int MODE>
 __device__ __forceinline__ float rpn_iou_term(const float (&r)[8], const Box6& a, const float* __restrict__ b, int linear) {
   float o[7];
@@ -359,95 +321,10 @@ __device__ __forceinline__ void rpn_iou_term_grad(const float (&r)[8], const Box
   rpn_decode_obb_bwd(r, a, ga, gr);
 }
 
-// what a flagged positive needs beyond its head values: its anchor, and its box row (NULL: it contributes nothing)
-__device__ __forceinline__ const float* rpn_iou_pair(const RpnGeom& G, const float* __restrict__ sh_base, const RpnOffs& S, const RHead& w, const float* __restrict__ boxes,
-                                                     const int* __restrict__ ori, const int* __restrict__ midx, Box6& a) {
-  bool valid;
-  a = rpn_anchor(G, sh_base, ori, RAt{w.lvl, w.scene, w.loc * w.A + w.a, true}, valid);
-  const int g0 = S.off[w.scene], g1 = S.off[w.scene + 1], row = g0 + max(midx[w.p], 0);
-  return valid && row < g1 ? boxes + (long)row * 7 : nullptr;
-}
-
-template <int MODE>
-__global__ __launch_bounds__(256) void rpn_iou_loss_fwd_kernel(RpnGeom G, RpnBase B, RpnOffs S, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
-                                                               const float* __restrict__ boxes, const int* __restrict__ ori, const int* __restrict__ midx, int linear,
-                                                               float* __restrict__ partials) {
-  __shared__ float sh_base[RPN_MAX_A * 3];
-  const RHead w = rpn_head_where(G);
-  rpn_stage_base(B, w.lvl, w.A, sh_base);
-  __syncthreads();
-  float v[3] = {0.f, 0.f, 0.f};         // objectness, box regression, sampled anchors
-  const int f = w.active ? flags[w.p] : 0;
-  if (f != 0) {
-    const float x = pick4(obj.p, w.lvl)[(long)w.scene * w.A * w.nloc + w.j];
-    v[0] = fmaxf(x, 0.f) - (f == 1 ? x : 0.f) + log1pf(expf(-fabsf(x)));
-    v[2] = 1.f;
-    if (f == 1) {                       // a wave without a flagged positive skips this
-      Box6 a;
-      const float* __restrict__ b = rpn_iou_pair(G, sh_base, S, w, boxes, ori, midx, a);
-      if (b) {
-        const float* __restrict__ rp = pick4(reg.p, w.lvl) + ((long)w.scene * w.A + w.a) * 8 * w.nloc + w.loc;
-        float r[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] = rp[(long)k * w.nloc];
-        v[1] = rpn_iou_term<MODE>(r, a, b, linear);
-      }
-    }
-  }
-  block_sum_fixed(v, partials + 3 * (long)blockIdx.x);
-}
-
-template <int MODE>
-__global__ __launch_bounds__(256) void rpn_iou_loss_bwd_kernel(RpnGeom G, RpnBase B, RpnOffs S, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
-                                                               const float* __restrict__ boxes, const int* __restrict__ ori, const int* __restrict__ midx, int linear,
-                                                               const float* __restrict__ scalars, const float* __restrict__ g_obj, const float* __restrict__ g_reg,
-                                                               Ptr4<float> dobj, Ptr4<float> dreg) {
-  __shared__ float sh_base[RPN_MAX_A * 3];
-  const RHead w = rpn_head_where(G);
-  rpn_stage_base(B, w.lvl, w.A, sh_base);
-  __syncthreads();
-  if (!w.active) return;
-  const long at = (long)w.scene * w.A * w.nloc + w.j, rat = ((long)w.scene * w.A + w.a) * 8 * w.nloc + w.loc;
-  const int f = flags[w.p];
-  const float cnt = scalars[2];
-  float go = 0.f, gr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (f != 0 && cnt > 0.f) {
-    const float x = pick4(obj.p, w.lvl)[at];
-    go = (sigmoid_stable(x) - (f == 1 ? 1.f : 0.f)) * (g_obj ? g_obj[0] : 0.f) / cnt;
-    if (f == 1) {                       // a wave without a flagged positive skips this
-      Box6 a;
-      const float* __restrict__ b = rpn_iou_pair(G, sh_base, S, w, boxes, ori, midx, a);
-      if (b) {
-        const float* __restrict__ rp = pick4(reg.p, w.lvl) + rat;
-        const float sc = (g_reg ? g_reg[0] : 0.f) / cnt;
-        float r[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] = rp[(long)k * w.nloc];
-        rpn_iou_term_grad<MODE>(r, a, b, linear, gr);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) gr[k] *= sc;
-      }
-    }
-  }
-  pick4(dobj.p, w.lvl)[at] = go;
-  float* __restrict__ dp = pick4(dreg.p, w.lvl) + rat;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) dp[(long)k * w.nloc] = gr[k];
-}
-
-// ---- the losses with the 2-D projection term -------------------------------------------------------------------------------------------------
-// TERM: what the box loss is; the 2-D term is the same for all of them
-enum { RPN2D_SL1_AABB = 0, RPN2D_SL1_OBB = 1, RPN2D_IOU = 2, RPN2D_GIOU = 3, RPN2D_DIOU = 4 };
-template <int TERM> struct Rpn2d {
-  static constexpr bool ORIENTED = TERM != RPN2D_SL1_AABB, SL1 = TERM <= RPN2D_SL1_OBB;
-  static constexpr int C = ORIENTED ? 8 : 6, NC = ORIENTED ? 7 : 6;
-  static constexpr int MODE = TERM == RPN2D_GIOU ? OBB_GIOU_SMALLEST : (TERM == RPN2D_DIOU ? OBB_DIOU_SMALLEST : OBB_IOU);
-};
-
-// as rpn_iou_pair, for box rows of NC columns
+// what a flagged positive needs beyond its head values: its anchor, and its box row of NC columns (NULL: it contributes nothing)
 template <int NC>
-__device__ __forceinline__ const float* rpn_2d_pair(const RpnGeom& G, const float* __restrict__ sh_base, const RpnOffs& S, const RHead& w, const float* __restrict__ boxes,
-                                                    const int* __restrict__ ori, const int* __restrict__ midx, Box6& a) {
+__device__ __forceinline__ const float* rpn_pair(const RpnGeom& G, const float* __restrict__ sh_base, const RpnOffs& S, const RHead& w, const float* __restrict__ boxes,
+                                                 const int* __restrict__ ori, const int* __restrict__ midx, Box6& a) {
   bool valid;
   a = rpn_anchor(G, sh_base, ori, RAt{w.lvl, w.scene, w.loc * w.A + w.a, true}, valid);
   const int g0 = S.off[w.scene], g1 = S.off[w.scene + 1], row = g0 + max(midx[w.p], 0);
@@ -483,98 +360,138 @@ __device__ __forceinline__ void rpn_2d_term_grad(const float (&r)[8], const Box6
   }
 }
 
-template <int TERM>
-__global__ __launch_bounds__(256) void rpn_loss2d_fwd_kernel(RpnGeom G, RpnBase B, RpnOffs S, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
-                                                             const float* __restrict__ targets, const float* __restrict__ boxes, const int* __restrict__ ori,
-                                                             const int* __restrict__ midx, int linear, Proj2dCams cams, float* __restrict__ partials) {
+// One forward and one backward kernel over (box term, with or without the 2-D term).  PAIR: a flagged positive looks up its anchor and its box row, which
+// smooth-L1 without the 2-D term never does: that instantiation stages no base table and has no barrier before the loss.  Every instantiation takes the same
+// arguments; what a variant does not read (B, S, boxes, midx, linear without PAIR; targets of the IoU types; cams, res, g_2d without the term) rides along unread.
+// LATE: the IoU types without the term read their deltas (the backward also its scale) only once the lane has a box row; every other variant reads them before the
+// lookup.  That is not an optimisation: it keeps every instantiation on the bits it has always produced.  The backward of the decode and of the pair geometry is
+// free to contract, and where the compiler forms the fused multiply-adds moves with the position of these reads (with one position for all variants the IoU types'
+// box gradients changed in their last bits).
+template <int TERM, bool P2D>
+__global__ __launch_bounds__(256) void rpn_loss_fwd_kernel(RpnGeom G, RpnBase B, RpnOffs S, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
+                                                           const float* __restrict__ targets, const float* __restrict__ boxes, const int* __restrict__ ori,
+                                                           const int* __restrict__ midx, int linear, Proj2dCams cams, float* __restrict__ partials) {
   using K = Rpn2d<TERM>;
-  constexpr int C = K::C;
+  constexpr int C = K::C, NS = P2D ? 5 : 3;
+  constexpr bool PAIR = P2D || !K::SL1, LATE = !P2D && !K::SL1;
   __shared__ float sh_base[RPN_MAX_A * 3];
   const RHead w = rpn_head_where(G);
-  rpn_stage_base(B, w.lvl, w.A, sh_base);
-  __syncthreads();
-  float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};   // objectness, box regression, sampled anchors, 2-D projection, sampled positives
+  if constexpr (PAIR) {
+    rpn_stage_base(B, w.lvl, w.A, sh_base);
+    __syncthreads();
+  }
+  float v[NS] = {};                     // objectness, box regression, sampled anchors; with the term: 2-D projection, sampled positives
   const int f = w.active ? flags[w.p] : 0;
   if (f != 0) {
     const float x = pick4(obj.p, w.lvl)[(long)w.scene * w.A * w.nloc + w.j];
     v[0] = fmaxf(x, 0.f) - (f == 1 ? x : 0.f) + log1pf(expf(-fabsf(x)));
     v[2] = 1.f;
     if (f == 1) {                       // a wave without a flagged positive skips this
-      v[4] = 1.f;
-      const float* __restrict__ rp = pick4(reg.p, w.lvl) + ((long)w.scene * w.A + w.a) * C * w.nloc + w.loc;
+      if constexpr (P2D) v[4] = 1.f;
       float r[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      if constexpr (!LATE) {
+        const float* __restrict__ rp = pick4(reg.p, w.lvl) + ((long)w.scene * w.A + w.a) * C * w.nloc + w.loc;
 #pragma unroll
-      for (int k = 0; k < C; ++k) r[k] = rp[(long)k * w.nloc];
+        for (int k = 0; k < C; ++k) r[k] = rp[(long)k * w.nloc];
+      }
       if constexpr (K::SL1) {
 #pragma unroll
         for (int k = 0; k < C; ++k) v[1] += rpn_sl1(r[k] - targets[w.p * C + k]);
       }
-      Box6 a;
-      const float* __restrict__ b = rpn_2d_pair<K::NC>(G, sh_base, S, w, boxes, ori, midx, a);
-      if (b) {
-        if constexpr (!K::SL1) v[1] = rpn_iou_term<K::MODE>(r, a, b, linear);
-        v[3] = rpn_2d_term<K::ORIENTED>(r, a, b, cams);
+      if constexpr (PAIR) {
+        Box6 a;
+        const float* __restrict__ b = rpn_pair<K::NC>(G, sh_base, S, w, boxes, ori, midx, a);
+        if (b) {
+          if constexpr (LATE) {
+            const float* __restrict__ rp = pick4(reg.p, w.lvl) + ((long)w.scene * w.A + w.a) * C * w.nloc + w.loc;
+#pragma unroll
+            for (int k = 0; k < C; ++k) r[k] = rp[(long)k * w.nloc];
+          }
+          if constexpr (!K::SL1) v[1] = rpn_iou_term<K::MODE>(r, a, b, linear);
+          if constexpr (P2D) v[3] = rpn_2d_term<K::ORIENTED>(r, a, b, cams);
+        }
       }
     }
   }
-  block_sum_fixed(v, partials + 5 * (long)blockIdx.x);
+  block_sum_fixed(v, partials + NS * (long)blockIdx.x);
 }
 
-// one workgroup: scalars = (objectness loss, box loss, number of sampled anchors, 2-D loss, number of sampled positives)
-__global__ __launch_bounds__(256) void rpn_loss2d_final_kernel(const float* __restrict__ partials, int nblocks, float res, float* __restrict__ scalars) {
-  float sum[5];
+// one workgroup: fixed-order sum of the per-workgroup partials -> scalars = (objectness loss, box loss, number of sampled anchors); NS 5, with the 2-D term:
+// also (2-D loss, number of sampled positives)
+template <int NS>
+__global__ __launch_bounds__(256) void rpn_loss_final_kernel(const float* __restrict__ partials, int nblocks, float res, float* __restrict__ scalars) {
+  float sum[NS];
   final_sum_fixed(partials, nblocks, sum);
   if (threadIdx.x != 0) return;
-  const float cnt = sum[2], pos = sum[4];
+  const float cnt = sum[2];
   scalars[0] = cnt > 0.f ? sum[0] / cnt : 0.f;
   scalars[1] = cnt > 0.f ? sum[1] / cnt : 0.f;
   scalars[2] = cnt;
-  scalars[3] = pos > 0.f ? sum[3] / pos / res : 0.f;
-  scalars[4] = pos;
+  if constexpr (NS == 5) {
+    const float pos = sum[4];
+    scalars[3] = pos > 0.f ? sum[3] / pos / res : 0.f;
+    scalars[4] = pos;
+  }
 }
 
-template <int TERM>
-__global__ __launch_bounds__(256) void rpn_loss2d_bwd_kernel(RpnGeom G, RpnBase B, RpnOffs S, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
-                                                             const float* __restrict__ targets, const float* __restrict__ boxes, const int* __restrict__ ori,
-                                                             const int* __restrict__ midx, int linear, Proj2dCams cams, float res, const float* __restrict__ scalars,
-                                                             const float* __restrict__ g_obj, const float* __restrict__ g_reg, const float* __restrict__ g_2d, Ptr4<float> dobj,
-                                                             Ptr4<float> dreg) {
+template <int TERM, bool P2D>
+__global__ __launch_bounds__(256) void rpn_loss_bwd_kernel(RpnGeom G, RpnBase B, RpnOffs S, Ptr4<const float> obj, Ptr4<const float> reg, const unsigned char* __restrict__ flags,
+                                                           const float* __restrict__ targets, const float* __restrict__ boxes, const int* __restrict__ ori,
+                                                           const int* __restrict__ midx, int linear, Proj2dCams cams, float res, const float* __restrict__ scalars,
+                                                           const float* __restrict__ g_obj, const float* __restrict__ g_reg, const float* __restrict__ g_2d, Ptr4<float> dobj,
+                                                           Ptr4<float> dreg) {
   using K = Rpn2d<TERM>;
   constexpr int C = K::C;
+  constexpr bool PAIR = P2D || !K::SL1, LATE = !P2D && !K::SL1;
   __shared__ float sh_base[RPN_MAX_A * 3];
   const RHead w = rpn_head_where(G);
-  rpn_stage_base(B, w.lvl, w.A, sh_base);
-  __syncthreads();
+  if constexpr (PAIR) {
+    rpn_stage_base(B, w.lvl, w.A, sh_base);
+    __syncthreads();
+  }
   if (!w.active) return;
   const long at = (long)w.scene * w.A * w.nloc + w.j, rat = ((long)w.scene * w.A + w.a) * C * w.nloc + w.loc;
   const int f = flags[w.p];
-  const float cnt = scalars[2], pos = scalars[4];
+  const float cnt = scalars[2], pos = P2D ? scalars[4] : 0.f;
   float go = 0.f, gr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (f != 0 && cnt > 0.f) {
     const float x = pick4(obj.p, w.lvl)[at];
     go = (sigmoid_stable(x) - (f == 1 ? 1.f : 0.f)) * (g_obj ? g_obj[0] : 0.f) / cnt;
     if (f == 1) {                       // a wave without a flagged positive skips this
-      const float* __restrict__ rp = pick4(reg.p, w.lvl) + rat;
-      const float sc = (g_reg ? g_reg[0] : 0.f) / cnt, sc2 = (g_2d ? g_2d[0] : 0.f) / pos / res;
-      float r[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      float sc = 0.f, sc2 = 0.f, r[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      if constexpr (!LATE) {
+        const float* __restrict__ rp = pick4(reg.p, w.lvl) + rat;
+        sc = (g_reg ? g_reg[0] : 0.f) / cnt;
+        if constexpr (P2D) sc2 = (g_2d ? g_2d[0] : 0.f) / pos / res;
 #pragma unroll
-      for (int k = 0; k < C; ++k) r[k] = rp[(long)k * w.nloc];
+        for (int k = 0; k < C; ++k) r[k] = rp[(long)k * w.nloc];
+      }
       if constexpr (K::SL1) {
 #pragma unroll
         for (int k = 0; k < C; ++k) gr[k] = rpn_sl1_grad(r[k] - targets[w.p * C + k]) * sc;
       }
-      Box6 a;
-      const float* __restrict__ b = rpn_2d_pair<K::NC>(G, sh_base, S, w, boxes, ori, midx, a);
-      if (b) {
-        float g2[8];
-        if constexpr (!K::SL1) {
-          rpn_iou_term_grad<K::MODE>(r, a, b, linear, g2);
+      if constexpr (PAIR) {
+        Box6 a;
+        const float* __restrict__ b = rpn_pair<K::NC>(G, sh_base, S, w, boxes, ori, midx, a);
+        if (b) {
+          float g2[8];
+          if constexpr (LATE) {
+            const float* __restrict__ rp = pick4(reg.p, w.lvl) + rat;
+            sc = (g_reg ? g_reg[0] : 0.f) / cnt;
 #pragma unroll
-          for (int k = 0; k < 8; ++k) gr[k] = g2[k] * sc;
+            for (int k = 0; k < C; ++k) r[k] = rp[(long)k * w.nloc];
+          }
+          if constexpr (!K::SL1) {
+            rpn_iou_term_grad<K::MODE>(r, a, b, linear, g2);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) gr[k] = g2[k] * sc;
+          }
+          if constexpr (P2D) {
+            rpn_2d_term_grad<K::ORIENTED>(r, a, b, cams, g2);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) gr[k] += g2[k] * sc2;
+          }
         }
-        rpn_2d_term_grad<K::ORIENTED>(r, a, b, cams, g2);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) gr[k] += g2[k] * sc2;
       }
     }
   }
@@ -595,10 +512,8 @@ int k_rpn_assign(int nlevels, const int* dims, const float* base, int N, int nco
                  float* labels, int* midx, float* targets, hipStream_t st) {
   RpnGeom G;
   RpnBase B;
-  if (make_geom(nlevels, dims, N, G) || make_base(nlevels, dims, base, B) || (ncols != 6 && ncols != 7) || !offs || offs[0] != 0 || !(bg <= fg)) return -4;
   RpnOffs S;
-  for (int b = 0; b <= NMH_FCOS_MAX_SCENES; ++b) S.off[b] = offs[b < N ? b : N];
-  for (int b = 0; b < N; ++b) if (offs[b + 1] < offs[b]) return -4;
+  if (make_geom(nlevels, dims, N, G) || make_base(nlevels, dims, base, B) || (ncols != 6 && ncols != 7) || make_offs(N, offs, S) || !(bg <= fg)) return -4;
   const int total = offs[N];
   if (total > 0 && (!boxes || !gtmax)) return -4;
   if (total > 0) {
@@ -623,140 +538,84 @@ int k_rpn_sample(int N, long n, const float* labels, int batch, int want_pos, lo
   return 0;
 }
 
-int k_rpn_loss_fwd(int nlevels, const int* dims, int N, int ncols, const float* const* obj, const float* const* reg, const unsigned char* flags, const float* targets, float* partials,
-                   float* scalars, hipStream_t st) {
-  RpnGeom G;
-  if (make_geom(nlevels, dims, N, G) || (ncols != 6 && ncols != 8) || !all_set(nlevels, obj) || !all_set(nlevels, reg)) return -4;
-  const Ptr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
-  if (ncols == 8) hipLaunchKernelGGL(rpn_loss_fwd_kernel<8>, dim3(G.nblocks), dim3(256), 0, st, G, O, R, flags, targets, partials);
-  else hipLaunchKernelGGL(rpn_loss_fwd_kernel<6>, dim3(G.nblocks), dim3(256), 0, st, G, O, R, flags, targets, partials);
-  NMH_CHECK_LAUNCH();
-  hipLaunchKernelGGL(rpn_loss_final_kernel, dim3(1), dim3(256), 0, st, partials, G.nblocks, scalars);
-  NMH_CHECK_LAUNCH();
-  return 0;
-}
-
-int k_rpn_loss_bwd(int nlevels, const int* dims, int N, int ncols, const float* const* obj, const float* const* reg, const unsigned char* flags, const float* targets,
-                   const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj, float* const* dreg, hipStream_t st) {
-  RpnGeom G;
-  if (make_geom(nlevels, dims, N, G) || (ncols != 6 && ncols != 8) || !all_set(nlevels, obj) || !all_set(nlevels, reg) || !all_set(nlevels, dobj) || !all_set(nlevels, dreg)) return -4;
-  const Ptr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
-  const Ptr4<float> DO = make_ptrs<float>(nlevels, dobj), DR = make_ptrs<float>(nlevels, dreg);
-  if (ncols == 8) hipLaunchKernelGGL(rpn_loss_bwd_kernel<8>, dim3(G.nblocks), dim3(256), 0, st, G, O, R, flags, targets, scalars, g_obj, g_reg, DO, DR);
-  else hipLaunchKernelGGL(rpn_loss_bwd_kernel<6>, dim3(G.nblocks), dim3(256), 0, st, G, O, R, flags, targets, scalars, g_obj, g_reg, DO, DR);
-  NMH_CHECK_LAUNCH();
-  return 0;
-}
-
 namespace {
-// the arguments the two IoU-loss entries share; loss_type: 0 iou, 1 linear_iou, 2 giou, 3 diou
-int make_iou_args(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* boxes, const int* offs, const int* midx, RpnGeom& G, RpnBase& B,
-                  RpnOffs& S) {
-  if (make_geom(nlevels, dims, N, G) || make_base(nlevels, dims, base, B) || ncols != 8 || loss_type < 0 || loss_type > 3 || !offs || offs[0] != 0 || !midx) return -4;
-  for (int b = 0; b < N; ++b) if (offs[b + 1] < offs[b]) return -4;
-  for (int b = 0; b <= NMH_FCOS_MAX_SCENES; ++b) S.off[b] = offs[b < N ? b : N];
-  return offs[N] > 0 && !boxes ? -4 : 0;
+struct RpnLossArgs {             // the by-value arguments of the loss kernels
+  RpnGeom G;
+  RpnBase B;
+  RpnOffs S;
+  Ptr4<const float> obj, reg;
+  Proj2dCams cams;
+};
+// loss_type < 0: smooth-L1 on the encoded targets (ncols 6 | 8); else 0 iou, 1 linear_iou, 2 giou, 3 diou (ncols 8 only)
+int term_of(int ncols, int loss_type) {
+  if (loss_type < 0) return ncols == 6 ? RPN_BOX_SL1_AABB : (ncols == 8 ? RPN_BOX_SL1_OBB : -1);
+  return ncols != 8 || loss_type > 3 ? -1 : (loss_type <= 1 ? RPN_BOX_IOU : (loss_type == 2 ? RPN_BOX_GIOU : RPN_BOX_DIOU));
+}
+
+// the by-value arguments of both loss kernels and the box term; cams NULL: without the 2-D term.  Smooth-L1 needs targets; the IoU types and the 2-D term need
+// what the box-row lookup reads (base, offs, midx, and boxes if there is a row); the 2-D term needs res > 0.
+int make_loss_args(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const float* targets,
+                   const float* boxes, const int* offs, const int* midx, const float* cams, float res, RpnLossArgs& q, int& term) {
+  term = term_of(ncols, loss_type);
+  if (term < 0 || make_geom(nlevels, dims, N, q.G) || !all_set(nlevels, obj) || !all_set(nlevels, reg)) return -4;
+  const bool sl1 = term <= RPN_BOX_SL1_OBB;
+  if (sl1 && !targets) return -4;
+  if ((!sl1 || cams) && (make_base(nlevels, dims, base, q.B) || make_offs(N, offs, q.S) || !midx || (offs[N] > 0 && !boxes))) return -4;
+  if (cams) {
+    if (!(res > 0.f)) return -4;
+    for (int k = 0; k < 48; ++k) q.cams.m[k / 12][k % 12] = cams[k];
+  }
+  q.obj = make_ptrs<const float>(nlevels, obj); q.reg = make_ptrs<const float>(nlevels, reg);
+  return 0;
+}
+
+// (term, with the 2-D term or not) -> launch(the two as compile-time constants)
+template <typename F> void loss_dispatch(int term, bool p2d, F&& launch) {
+  auto both = [&](auto T) {
+    if (p2d) launch(T, std::true_type{});
+    else launch(T, std::false_type{});
+  };
+  switch (term) {
+    case RPN_BOX_SL1_AABB: both(std::integral_constant<int, RPN_BOX_SL1_AABB>{}); break;
+    case RPN_BOX_SL1_OBB: both(std::integral_constant<int, RPN_BOX_SL1_OBB>{}); break;
+    case RPN_BOX_IOU: both(std::integral_constant<int, RPN_BOX_IOU>{}); break;
+    case RPN_BOX_GIOU: both(std::integral_constant<int, RPN_BOX_GIOU>{}); break;
+    default: both(std::integral_constant<int, RPN_BOX_DIOU>{}); break;
+  }
 }
 }  // namespace
 
-int k_rpn_iou_loss_fwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
-                       const float* boxes, const int* offs, const int* ori, const int* midx, float* partials, float* scalars, hipStream_t st) {
-  RpnGeom G;
-  RpnBase B;
-  RpnOffs S;
-  if (make_iou_args(nlevels, dims, base, N, ncols, loss_type, boxes, offs, midx, G, B, S) || !all_set(nlevels, obj) || !all_set(nlevels, reg)) return -4;
-  const Ptr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
+int k_rpn_loss_fwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
+                   const float* targets, const float* boxes, const int* offs, const int* ori, const int* midx, const float* cams, float res, float* partials, float* scalars,
+                   hipStream_t st) {
+  RpnLossArgs q{};
+  int term;
   const int linear = loss_type == 1;
-  if (loss_type <= 1) hipLaunchKernelGGL(rpn_iou_loss_fwd_kernel<OBB_IOU>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, partials);
-  else if (loss_type == 2) hipLaunchKernelGGL(rpn_iou_loss_fwd_kernel<OBB_GIOU_SMALLEST>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, partials);
-  else hipLaunchKernelGGL(rpn_iou_loss_fwd_kernel<OBB_DIOU_SMALLEST>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, partials);
+  if (make_loss_args(nlevels, dims, base, N, ncols, loss_type, obj, reg, targets, boxes, offs, midx, cams, res, q, term)) return -4;
+  loss_dispatch(term, cams != nullptr, [&](auto T, auto P) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(rpn_loss_fwd_kernel<decltype(T)::value, decltype(P)::value>), dim3(q.G.nblocks), dim3(256), 0, st, q.G, q.B, q.S, q.obj, q.reg, flags, targets, boxes, ori, midx,
+                       linear, q.cams, partials);
+  });
   NMH_CHECK_LAUNCH();
-  hipLaunchKernelGGL(rpn_loss_final_kernel, dim3(1), dim3(256), 0, st, partials, G.nblocks, scalars);
+  if (cams) hipLaunchKernelGGL(rpn_loss_final_kernel<5>, dim3(1), dim3(256), 0, st, partials, q.G.nblocks, res, scalars);
+  else hipLaunchKernelGGL(rpn_loss_final_kernel<3>, dim3(1), dim3(256), 0, st, partials, q.G.nblocks, res, scalars);
   NMH_CHECK_LAUNCH();
   return 0;
 }
 
-int k_rpn_iou_loss_bwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
-                       const float* boxes, const int* offs, const int* ori, const int* midx, const float* scalars, const float* g_obj, const float* g_reg, float* const* dobj,
-                       float* const* dreg, hipStream_t st) {
-  RpnGeom G;
-  RpnBase B;
-  RpnOffs S;
-  if (make_iou_args(nlevels, dims, base, N, ncols, loss_type, boxes, offs, midx, G, B, S) || !all_set(nlevels, obj) || !all_set(nlevels, reg) || !all_set(nlevels, dobj) ||
-      !all_set(nlevels, dreg)) return -4;
-  const Ptr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
-  const Ptr4<float> DO = make_ptrs<float>(nlevels, dobj), DR = make_ptrs<float>(nlevels, dreg);
+int k_rpn_loss_bwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
+                   const float* targets, const float* boxes, const int* offs, const int* ori, const int* midx, const float* cams, float res, const float* scalars,
+                   const float* g_obj, const float* g_reg, const float* g_2d, float* const* dobj, float* const* dreg, hipStream_t st) {
+  RpnLossArgs q{};
+  int term;
   const int linear = loss_type == 1;
-  if (loss_type <= 1) hipLaunchKernelGGL(rpn_iou_loss_bwd_kernel<OBB_IOU>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, scalars, g_obj, g_reg, DO, DR);
-  else if (loss_type == 2) hipLaunchKernelGGL(rpn_iou_loss_bwd_kernel<OBB_GIOU_SMALLEST>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, scalars, g_obj, g_reg, DO, DR);
-  else hipLaunchKernelGGL(rpn_iou_loss_bwd_kernel<OBB_DIOU_SMALLEST>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, boxes, ori, midx, linear, scalars, g_obj, g_reg, DO, DR);
-  NMH_CHECK_LAUNCH();
-  return 0;
-}
-
-namespace {
-// the arguments the four entries with the 2-D term share; term: a value of the RPN2D_ enum
-int make_2d_args(int nlevels, const int* dims, const float* base, int N, int term, const float* targets, const float* boxes, const int* offs, const int* midx, const float* cams,
-                 float res, RpnGeom& G, RpnBase& B, RpnOffs& S, Proj2dCams& C) {
-  if (make_geom(nlevels, dims, N, G) || make_base(nlevels, dims, base, B) || term < 0 || !offs || offs[0] != 0 || !midx || !cams || !(res > 0.f)) return -4;
-  if (term <= RPN2D_SL1_OBB && !targets) return -4;
-  for (int b = 0; b < N; ++b) if (offs[b + 1] < offs[b]) return -4;
-  for (int b = 0; b <= NMH_FCOS_MAX_SCENES; ++b) S.off[b] = offs[b < N ? b : N];
-  for (int k = 0; k < 48; ++k) C.m[k / 12][k % 12] = cams[k];
-  return offs[N] > 0 && !boxes ? -4 : 0;
-}
-int term_of(int ncols, int loss_type) {          // loss_type < 0: smooth-L1
-  if (loss_type < 0) return ncols == 6 ? RPN2D_SL1_AABB : (ncols == 8 ? RPN2D_SL1_OBB : -1);
-  return ncols != 8 || loss_type > 3 ? -1 : (loss_type <= 1 ? RPN2D_IOU : (loss_type == 2 ? RPN2D_GIOU : RPN2D_DIOU));
-}
-}  // namespace
-
-int k_rpn_loss2d_fwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
-                     const float* targets, const float* boxes, const int* offs, const int* ori, const int* midx, const float* cams, float res, float* partials, float* scalars,
-                     hipStream_t st) {
-  RpnGeom G;
-  RpnBase B;
-  RpnOffs S;
-  Proj2dCams C;
-  const int term = term_of(ncols, loss_type), linear = loss_type == 1;
-  if (make_2d_args(nlevels, dims, base, N, term, targets, boxes, offs, midx, cams, res, G, B, S, C) || !all_set(nlevels, obj) || !all_set(nlevels, reg)) return -4;
-  const Ptr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
-#define RPN2D_FWD(T) hipLaunchKernelGGL(rpn_loss2d_fwd_kernel<T>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, targets, boxes, ori, midx, linear, C, partials)
-  switch (term) {
-    case RPN2D_SL1_AABB: RPN2D_FWD(RPN2D_SL1_AABB); break;
-    case RPN2D_SL1_OBB: RPN2D_FWD(RPN2D_SL1_OBB); break;
-    case RPN2D_IOU: RPN2D_FWD(RPN2D_IOU); break;
-    case RPN2D_GIOU: RPN2D_FWD(RPN2D_GIOU); break;
-    default: RPN2D_FWD(RPN2D_DIOU); break;
-  }
-#undef RPN2D_FWD
-  NMH_CHECK_LAUNCH();
-  hipLaunchKernelGGL(rpn_loss2d_final_kernel, dim3(1), dim3(256), 0, st, partials, G.nblocks, res, scalars);
-  NMH_CHECK_LAUNCH();
-  return 0;
-}
-
-int k_rpn_loss2d_bwd(int nlevels, const int* dims, const float* base, int N, int ncols, int loss_type, const float* const* obj, const float* const* reg, const unsigned char* flags,
-                     const float* targets, const float* boxes, const int* offs, const int* ori, const int* midx, const float* cams, float res, const float* scalars,
-                     const float* g_obj, const float* g_reg, const float* g_2d, float* const* dobj, float* const* dreg, hipStream_t st) {
-  RpnGeom G;
-  RpnBase B;
-  RpnOffs S;
-  Proj2dCams C;
-  const int term = term_of(ncols, loss_type), linear = loss_type == 1;
-  if (make_2d_args(nlevels, dims, base, N, term, targets, boxes, offs, midx, cams, res, G, B, S, C) || !all_set(nlevels, obj) || !all_set(nlevels, reg) || !all_set(nlevels, dobj) ||
+  if (make_loss_args(nlevels, dims, base, N, ncols, loss_type, obj, reg, targets, boxes, offs, midx, cams, res, q, term) || !all_set(nlevels, dobj) ||
       !all_set(nlevels, dreg)) return -4;
-  const Ptr4<const float> O = make_ptrs<const float>(nlevels, obj), R = make_ptrs<const float>(nlevels, reg);
   const Ptr4<float> DO = make_ptrs<float>(nlevels, dobj), DR = make_ptrs<float>(nlevels, dreg);
-#define RPN2D_BWD(T) hipLaunchKernelGGL(rpn_loss2d_bwd_kernel<T>, dim3(G.nblocks), dim3(256), 0, st, G, B, S, O, R, flags, targets, boxes, ori, midx, linear, C, res, scalars, g_obj, g_reg, g_2d, DO, DR)
-  switch (term) {
-    case RPN2D_SL1_AABB: RPN2D_BWD(RPN2D_SL1_AABB); break;
-    case RPN2D_SL1_OBB: RPN2D_BWD(RPN2D_SL1_OBB); break;
-    case RPN2D_IOU: RPN2D_BWD(RPN2D_IOU); break;
-    case RPN2D_GIOU: RPN2D_BWD(RPN2D_GIOU); break;
-    default: RPN2D_BWD(RPN2D_DIOU); break;
-  }
-#undef RPN2D_BWD
+  loss_dispatch(term, cams != nullptr, [&](auto T, auto P) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(rpn_loss_bwd_kernel<decltype(T)::value, decltype(P)::value>), dim3(q.G.nblocks), dim3(256), 0, st, q.G, q.B, q.S, q.obj, q.reg, flags, targets, boxes, ori, midx,
+                       linear, q.cams, res, scalars, g_obj, g_reg, g_2d, DO, DR);
+  });
   NMH_CHECK_LAUNCH();
   return 0;
 }

@@ -1840,50 +1840,6 @@ def rpn_sample(labels, batch, want_pos, rng_state):
     return flags, counts
 
 
-def rpn_loss_fwd(plan, C, obj, reg, flags, targets):
-    """-> scalars [3] = (objectness loss, box loss, number of sampled anchors)"""
-    dev = flags.device
-    partials = torch.empty((3 * plan.nblocks,), dtype=torch.float32, device=dev)
-    scalars = torch.empty((3,), dtype=torch.float32, device=dev)
-    lib().call("nmh_rpn_loss_fwd", plan.L, plan.dims, plan.N, C, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, targets, partials, scalars, _st())
-    return scalars
-
-
-def rpn_loss_bwd(plan, C, obj, reg, flags, targets, scalars, g_obj, g_reg):
-    dobj, dreg = [torch.empty_like(t) for t in obj], [torch.empty_like(t) for t in reg]
-    lib().call("nmh_rpn_loss_bwd", plan.L, plan.dims, plan.N, C, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, targets, scalars, g_obj, g_reg, _ptr_table(dobj, plan.L), _ptr_table(dreg, plan.L), _st())
-    return dobj, dreg
-
-
-def _rpn_iou_args(plan, loss_type, boxes, offsets, ori_sizes, midx):
-    if loss_type not in FCOS_LOSS_TYPES:
-        raise ValueError(f"RPN IoU loss: reg_loss_type must be one of {sorted(FCOS_LOSS_TYPES)}, got {loss_type!r}")
-    _chk(boxes, ori_sizes, midx)
-    offs = (ctypes.c_int * (plan.N + 1))(*offsets)
-    return FCOS_LOSS_TYPES[loss_type], boxes if boxes.numel() else None, offs
-
-
-def rpn_iou_loss_fwd(plan, loss_type, obj, reg, flags, boxes, offsets, ori_sizes, midx):
-    """the IoU-type box loss of the oriented RPN over the decoded proposals; loss_type: a key of FCOS_LOSS_TYPES; boxes [G,7], offsets host ints [N+1],
-    ori_sizes int32 [N,3] or None, midx [N,n] int32 as rpn_assign takes and returns them -> scalars [3] = (objectness loss, box loss, number of sampled anchors)"""
-    lt, boxes, offs = _rpn_iou_args(plan, loss_type, boxes, offsets, ori_sizes, midx)
-    dev = flags.device
-    partials = torch.empty((3 * plan.nblocks,), dtype=torch.float32, device=dev)
-    scalars = torch.empty((3,), dtype=torch.float32, device=dev)
-    lib().call("nmh_rpn_iou_loss_fwd", plan.L, plan.dims, plan.base, plan.N, 8, lt, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, boxes, offs, ori_sizes, midx, partials,
-               scalars, _st())
-    return scalars
-
-
-def rpn_iou_loss_bwd(plan, loss_type, obj, reg, flags, boxes, offsets, ori_sizes, midx, scalars, g_obj, g_reg, out=None):
-    """-> (dobj, dreg) per level; out: the pair of per-level lists to write instead of fresh tensors (every element is written)"""
-    lt, boxes, offs = _rpn_iou_args(plan, loss_type, boxes, offsets, ori_sizes, midx)
-    dobj, dreg = out if out is not None else ([torch.empty_like(t) for t in obj], [torch.empty_like(t) for t in reg])
-    lib().call("nmh_rpn_iou_loss_bwd", plan.L, plan.dims, plan.base, plan.N, 8, lt, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, boxes, offs, ori_sizes, midx, scalars,
-               g_obj, g_reg, _ptr_table(dobj, plan.L), _ptr_table(dreg, plan.L), _st())
-    return dobj, dreg
-
-
 def _cams48(cams):
     """fp32 host tensor [4, 3, 4] -> the host array the entries take"""
     if not isinstance(cams, torch.Tensor) or cams.dtype != torch.float32 or cams.is_cuda or tuple(cams.shape) != (4, 3, 4):
@@ -1891,35 +1847,41 @@ def _cams48(cams):
     return (ctypes.c_float * 48)(*cams.reshape(-1).tolist())
 
 
-def rpn_loss2d_fwd(plan, C, loss_type, obj, reg, flags, targets, boxes, offsets, ori_sizes, midx, cams, res):
-    """the losses of rpn_loss_fwd (loss_type None: smooth-L1, C 6 | 8, targets [N,n,C]) or rpn_iou_loss_fwd (a key of FCOS_LOSS_TYPES, C 8) with the 2-D projection
-    term; cams: the host array of _cams48, res = max(mesh_size) -> scalars [5] = (objectness loss, box loss, sampled anchors, 2-D loss, sampled positives)"""
+def _rpn_loss_entry(plan, C, loss_type, targets, boxes, offsets, ori_sizes, midx, cams, res):
+    """-> (the ABI entry's stem, its arguments from base_half up to flags, its arguments between flags and the outputs); of the eight entries the smooth-L1 pair
+    without the 2-D term takes neither the base table nor the box rows, and only the IoU types take a loss type"""
+    if loss_type is not None and loss_type not in FCOS_LOSS_TYPES:
+        raise ValueError(f"RPN IoU loss: reg_loss_type must be one of {sorted(FCOS_LOSS_TYPES)}, got {loss_type!r}")
     _chk(boxes, ori_sizes, midx, targets)
-    dev = flags.device
+    if loss_type is None and cams is None:
+        return "nmh_rpn_loss", (plan.N, C), (targets,)
     offs = (ctypes.c_int * (plan.N + 1))(*offsets)
-    boxes = boxes if boxes.numel() else None
-    partials = torch.empty((5 * plan.nblocks,), dtype=torch.float32, device=dev)
-    scalars = torch.empty((5,), dtype=torch.float32, device=dev)
+    rows = (boxes if boxes.numel() else None, offs, ori_sizes, midx) + (() if cams is None else (cams, res))
     if loss_type is None:
-        lib().call("nmh_rpn_loss2d_fwd", plan.L, plan.dims, plan.base, plan.N, C, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, targets, boxes, offs, ori_sizes, midx, cams, res,
-                   partials, scalars, _st())
-    else:
-        lib().call("nmh_rpn_iou_loss2d_fwd", plan.L, plan.dims, plan.base, plan.N, C, FCOS_LOSS_TYPES[loss_type], _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, boxes, offs,
-                   ori_sizes, midx, cams, res, partials, scalars, _st())
+        return "nmh_rpn_loss2d", (plan.base, plan.N, C), (targets, *rows)
+    return "nmh_rpn_iou_loss" + ("" if cams is None else "2d"), (plan.base, plan.N, C, FCOS_LOSS_TYPES[loss_type]), rows
+
+
+def rpn_loss_fwd(plan, C, loss_type, obj, reg, flags, targets, boxes, offsets, ori_sizes, midx, cams=None, res=None):
+    """loss_type None: the smooth-L1 box loss on targets [N,n,C], C 6 | 8; a key of FCOS_LOSS_TYPES: the IoU-type box loss of the oriented RPN over the decoded proposals,
+    C 8.  boxes [G,6|7], offsets host ints [N+1], ori_sizes int32 [N,3] or None, midx [N,n] int32 as rpn_assign takes and returns them (smooth-L1 without the 2-D term
+    reads none of them).  cams None -> scalars [3] = (objectness loss, box loss, number of sampled anchors); cams the host array of _cams48 and res = max(mesh_size):
+    with the 2-D projection term -> scalars [5] = (objectness loss, box loss, sampled anchors, 2-D loss, sampled positives)"""
+    name, head, tail = _rpn_loss_entry(plan, C, loss_type, targets, boxes, offsets, ori_sizes, midx, cams, res)
+    ns = 3 if cams is None else 5
+    partials = torch.empty((ns * plan.nblocks,), dtype=torch.float32, device=flags.device)
+    scalars = torch.empty((ns,), dtype=torch.float32, device=flags.device)
+    lib().call(name + "_fwd", plan.L, plan.dims, *head, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, *tail, partials, scalars, _st())
     return scalars
 
 
-def rpn_loss2d_bwd(plan, C, loss_type, obj, reg, flags, targets, boxes, offsets, ori_sizes, midx, cams, res, scalars, g_obj, g_reg, g_2d, out=None):
+def rpn_loss_bwd(plan, C, loss_type, obj, reg, flags, targets, boxes, offsets, ori_sizes, midx, cams, res, scalars, g_obj, g_reg, g_2d=None, out=None):
     """-> (dobj, dreg) per level; out: the pair of per-level lists to write instead of fresh tensors (every element is written exactly once)"""
-    offs = (ctypes.c_int * (plan.N + 1))(*offsets)
-    boxes = boxes if boxes.numel() else None
+    name, head, tail = _rpn_loss_entry(plan, C, loss_type, targets, boxes, offsets, ori_sizes, midx, cams, res)
     dobj, dreg = out if out is not None else ([torch.empty_like(t) for t in obj], [torch.empty_like(t) for t in reg])
-    if loss_type is None:
-        lib().call("nmh_rpn_loss2d_bwd", plan.L, plan.dims, plan.base, plan.N, C, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, targets, boxes, offs, ori_sizes, midx, cams, res,
-                   scalars, g_obj, g_reg, g_2d, _ptr_table(dobj, plan.L), _ptr_table(dreg, plan.L), _st())
-    else:
-        lib().call("nmh_rpn_iou_loss2d_bwd", plan.L, plan.dims, plan.base, plan.N, C, FCOS_LOSS_TYPES[loss_type], _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, boxes, offs,
-                   ori_sizes, midx, cams, res, scalars, g_obj, g_reg, g_2d, _ptr_table(dobj, plan.L), _ptr_table(dreg, plan.L), _st())
+    gs = (g_obj, g_reg) if cams is None else (g_obj, g_reg, g_2d)
+    lib().call(name + "_bwd", plan.L, plan.dims, *head, _ptr_table(obj, plan.L), _ptr_table(reg, plan.L), flags, *tail, scalars, *gs, _ptr_table(dobj, plan.L), _ptr_table(dreg, plan.L),
+               _st())
     return dobj, dreg
 
 

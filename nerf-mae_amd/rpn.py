@@ -219,76 +219,29 @@ def rpn_sample(labels, batch_size_per_mesh, positive_fraction, rng_state):
 
 
 class _RpnLoss(Function):
-    """(plan, C, flags, targets, *objectness levels, *regression levels) -> (loss_objectness, loss_rpn_box_reg)"""
-
-    @staticmethod
-    def forward(ctx, plan, C, flags, targets, *heads):
-        heads = [h.contiguous() for h in heads]
-        obj, reg = heads[:plan.L], heads[plan.L:]
-        scalars = ops.rpn_loss_fwd(plan, C, obj, reg, flags, targets)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(flags, targets, scalars, *heads)
-        ctx.cfg = (plan, C)
-        return scalars[0], scalars[1]
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_obj, g_reg):
-        plan, C = ctx.cfg
-        flags, targets, scalars, *heads = ctx.saved_tensors
-        if (g_obj is None and g_reg is None) or not any(ctx.needs_input_grad[4:]):
-            return (None,) * (4 + 2 * plan.L)
-        gs = [g if g is None else g.contiguous() for g in (g_obj, g_reg)]
-        dobj, dreg = ops.rpn_loss_bwd(plan, C, heads[:plan.L], heads[plan.L:], flags, targets, scalars, gs[0], gs[1])
-        return (None, None, None, None, *dobj, *dreg)
-
-
-class _RpnIoULoss(Function):
-    """(plan, loss_type, flags, boxes, offsets, ori, matched_idxs, *objectness levels, *regression levels) -> (loss_objectness, loss_rpn_box_reg)"""
-
-    @staticmethod
-    def forward(ctx, plan, loss_type, flags, boxes, offsets, ori, midx, *heads):
-        heads = [h.contiguous() for h in heads]
-        scalars = ops.rpn_iou_loss_fwd(plan, loss_type, heads[:plan.L], heads[plan.L:], flags, boxes, offsets, ori, midx)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(flags, boxes, midx, scalars, *heads)
-        ctx.cfg = (plan, loss_type, offsets, ori)
-        return scalars[0], scalars[1]
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_obj, g_reg):
-        plan, loss_type, offsets, ori = ctx.cfg
-        flags, boxes, midx, scalars, *heads = ctx.saved_tensors
-        if (g_obj is None and g_reg is None) or not any(ctx.needs_input_grad[7:]):
-            return (None,) * (7 + 2 * plan.L)
-        gs = [g if g is None else g.contiguous() for g in (g_obj, g_reg)]
-        dobj, dreg = ops.rpn_iou_loss_bwd(plan, loss_type, heads[:plan.L], heads[plan.L:], flags, boxes, offsets, ori, midx, scalars, gs[0], gs[1])
-        return (None,) * 7 + (*dobj, *dreg)
-
-
-class _RpnLoss2d(Function):
-    """(plan, C, loss_type or None (smooth-L1), cams, res, flags, targets, boxes, offsets, ori, matched_idxs, *objectness levels, *regression levels) ->
-    (loss_objectness, loss_rpn_box_reg, loss_rpn_box_reg_2d): either box loss with the 2-D projection term, one forward and one backward launch"""
+    """(plan, C, loss_type or None (smooth-L1), cams or None (without the 2-D projection term), res, flags, targets, boxes, offsets, ori, matched_idxs, *objectness levels,
+    *regression levels) -> (loss_objectness, loss_rpn_box_reg) and, with cams, loss_rpn_box_reg_2d: one forward and one backward launch for either box loss"""
 
     @staticmethod
     def forward(ctx, plan, C, loss_type, cams, res, flags, targets, boxes, offsets, ori, midx, *heads):
         heads = [h.contiguous() for h in heads]
-        scalars = ops.rpn_loss2d_fwd(plan, C, loss_type, heads[:plan.L], heads[plan.L:], flags, targets, boxes, offsets, ori, midx, cams, res)
+        scalars = ops.rpn_loss_fwd(plan, C, loss_type, heads[:plan.L], heads[plan.L:], flags, targets, boxes, offsets, ori, midx, cams, res)
         ctx.set_materialize_grads(False)
+        if cams is None:                         # kept alive until the backward: only what this variant's kernel reads
+            targets, boxes, midx = (targets, None, None) if loss_type is None else (None, boxes, midx)
         ctx.save_for_backward(flags, targets, boxes, midx, scalars, *heads)
         ctx.cfg = (plan, C, loss_type, cams, res, offsets, ori)
-        return scalars[0], scalars[1], scalars[3]
+        return (scalars[0], scalars[1]) if cams is None else (scalars[0], scalars[1], scalars[3])
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_obj, g_reg, g_2d):
+    def backward(ctx, *gs):
         plan, C, loss_type, cams, res, offsets, ori = ctx.cfg
         flags, targets, boxes, midx, scalars, *heads = ctx.saved_tensors
-        if (g_obj is None and g_reg is None and g_2d is None) or not any(ctx.needs_input_grad[11:]):
+        if all(g is None for g in gs) or not any(ctx.needs_input_grad[11:]):
             return (None,) * (11 + 2 * plan.L)
-        gs = [g if g is None else g.contiguous() for g in (g_obj, g_reg, g_2d)]
-        dobj, dreg = ops.rpn_loss2d_bwd(plan, C, loss_type, heads[:plan.L], heads[plan.L:], flags, targets, boxes, offsets, ori, midx, cams, res, scalars, *gs)
+        gs = [g if g is None else g.contiguous() for g in gs]
+        dobj, dreg = ops.rpn_loss_bwd(plan, C, loss_type, heads[:plan.L], heads[plan.L:], flags, targets, boxes, offsets, ori, midx, cams, res, scalars, *gs)
         return (None,) * 11 + (*dobj, *dreg)
 
 
@@ -310,16 +263,6 @@ class _RPNLossBase(object):
         self.reg_loss_type = reg_loss_type
         self.seed = int(seed)
         self.rng_state = None
-
-    def _losses(self, plan, C, flags, boxes, offsets, ori, matched_idxs, reg_targets, heads):
-        """-> (loss_objectness, loss_rpn_box_reg)"""
-        raise NotImplementedError
-
-    def _losses_2d(self, plan, C, mesh_size, flags, boxes, offsets, ori, matched_idxs, reg_targets, heads):
-        """-> (loss_objectness, loss_rpn_box_reg, loss_rpn_box_reg_2d); the cameras stand around a scene of max(mesh_size), which is also the divisor"""
-        res = float(max(int(m) for m in mesh_size[-3:]))
-        loss_type = None if self.reg_loss_type == "smooth_l1" else self.reg_loss_type
-        return _RpnLoss2d.apply(plan, C, loss_type, proj2d._cams(res), res, flags, reg_targets, boxes, offsets, ori, matched_idxs, *heads)
 
     def __call__(self, mesh_size, objectness, pred_bbox_deltas, targets, original_mesh_sizes=None, sampled=None):
         """mesh_size (X, Y, Z) of the padded batch; objectness, pred_bbox_deltas: the head's per-level lists; targets: list of N box tensors;
@@ -355,10 +298,12 @@ class _RPNLossBase(object):
                 raise ValueError(f"{name}: sampled must be a uint8 device tensor [N, n] = {(N, plan.n)}")
             flags = sampled.contiguous()
         heads = (*objectness, *pred_bbox_deltas)
-        if self.reg_loss_2d:
-            loss_obj, loss_reg, loss_2d = self._losses_2d(plan, C, mesh_size, flags, boxes, offsets, ori, matched_idxs, reg_targets, heads)
+        loss_type = None if self.reg_loss_type == "smooth_l1" else self.reg_loss_type
+        if self.reg_loss_2d:                     # the cameras stand around a scene of max(mesh_size), which is also the divisor
+            res = float(max(int(m) for m in mesh_size[-3:]))
+            loss_obj, loss_reg, loss_2d = _RpnLoss.apply(plan, C, loss_type, proj2d._cams(res), res, flags, reg_targets, boxes, offsets, ori, matched_idxs, *heads)
         else:
-            loss_obj, loss_reg = self._losses(plan, C, flags, boxes, offsets, ori, matched_idxs, reg_targets, heads)
+            loss_obj, loss_reg = _RpnLoss.apply(plan, C, loss_type, None, None, flags, reg_targets, boxes, offsets, ori, matched_idxs, *heads)
             loss_2d = torch.zeros((), dtype=torch.float32, device=boxes.device)
         return {"loss_objectness": loss_obj, "loss_rpn_box_reg": loss_reg, "loss_rpn_box_reg_2d": loss_2d}
 
@@ -374,9 +319,6 @@ class RPNLossComputation(_RPNLossBase):
                                       "are RPNIoULossComputation")
         super().__init__(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, rotated_bbox, reg_loss_type, seed, reg_loss_2d)
 
-    def _losses(self, plan, C, flags, boxes, offsets, ori, matched_idxs, reg_targets, heads):
-        return _RpnLoss.apply(plan, C, flags, reg_targets, *heads)
-
 
 class RPNIoULossComputation(_RPNLossBase):
     """The same training half with the reference's IoU-type box losses (run_rpn.py --rotated_bbox --reg_loss_type iou | linear_iou | giou | diou): the box
@@ -387,9 +329,6 @@ class RPNIoULossComputation(_RPNLossBase):
         if reg_loss_type not in ops.FCOS_LOSS_TYPES:
             raise ValueError(f"RPNIoULossComputation: reg_loss_type must be one of {sorted(ops.FCOS_LOSS_TYPES)}, got {reg_loss_type!r}")
         super().__init__(anchor_generator, fg_iou_thresh, bg_iou_thresh, batch_size_per_mesh, positive_fraction, True, reg_loss_type, seed, reg_loss_2d)
-
-    def _losses(self, plan, C, flags, boxes, offsets, ori, matched_idxs, reg_targets, heads):
-        return _RpnIoULoss.apply(plan, self.reg_loss_type, flags, boxes, offsets, ori, matched_idxs, *heads)
 
 
 # ---- inference path --------------------------------------------------------------------------------------------------------------------------

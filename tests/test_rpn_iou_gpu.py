@@ -142,10 +142,10 @@ def _ops_call(loss_type, obj, reg, flags, boxes, ori=None, g=(1.0, 1.0)):
     plan = M._plan(_gen(), R.MESH, R.GRIDS, flags.shape[0], "test")
     bx, offs = M._boxes("test", boxes, 7)
     _, midx, _ = ops.rpn_assign(plan, bx, offs, 7, ori, R.FG, R.BG)
-    scalars = ops.rpn_iou_loss_fwd(plan, loss_type, obj, reg, flags, bx, offs, ori, midx)
+    scalars = ops.rpn_loss_fwd(plan, 8, loss_type, obj, reg, flags, None, bx, offs, ori, midx)
     outs = ([torch.full_like(t, float("nan")) for t in obj], [torch.full_like(t, float("nan")) for t in reg])
     go, gr = [torch.tensor([v], dtype=torch.float32).cuda() for v in g]
-    ops.rpn_iou_loss_bwd(plan, loss_type, obj, reg, flags, bx, offs, ori, midx, scalars, go, gr, out=outs)
+    ops.rpn_loss_bwd(plan, 8, loss_type, obj, reg, flags, None, bx, offs, ori, midx, None, None, scalars, go, gr, out=outs)
     return scalars, outs[0], outs[1]
 
 

@@ -158,10 +158,10 @@ def _ops_call(c, obj, reg, flags, boxes, g=(1.0, 1.0, 1.0)):
     _, midx, targets = ops.rpn_assign(plan, bx, offs, ncols, _ori(), R.FG, R.BG)
     lt = None if c["loss_type"] == "smooth_l1" else c["loss_type"]
     args = (plan, C, lt, obj, reg, flags, targets, bx, offs, _ori(), midx, proj2d._cams(32.0), 32.0)
-    scalars = ops.rpn_loss2d_fwd(*args)
+    scalars = ops.rpn_loss_fwd(*args)
     outs = ([torch.full_like(t, float("nan")) for t in obj], [torch.full_like(t, float("nan")) for t in reg])
     gs = [None if v is None else torch.tensor([v], dtype=torch.float32).cuda() for v in g]
-    ops.rpn_loss2d_bwd(*args, scalars, *gs, out=outs)
+    ops.rpn_loss_bwd(*args, scalars, *gs, out=outs)
     return scalars.cpu(), outs[0], outs[1]
 
 

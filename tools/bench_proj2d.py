@@ -56,21 +56,17 @@ def main(reps=30):
         cams = proj2d._cams(res)
 
         def off():
-            if lt is None:
-                s = ops.rpn_loss_fwd(plan, C, obj, reg, flags, targets)
-                ops.rpn_loss_bwd(plan, C, obj, reg, flags, targets, s, one, one)
-            else:
-                s = ops.rpn_iou_loss_fwd(plan, lt, obj, reg, flags, bx, offs, None, midx)
-                ops.rpn_iou_loss_bwd(plan, lt, obj, reg, flags, bx, offs, None, midx, s, one, one)
+            s = ops.rpn_loss_fwd(plan, C, lt, obj, reg, flags, targets, bx, offs, None, midx)
+            ops.rpn_loss_bwd(plan, C, lt, obj, reg, flags, targets, bx, offs, None, midx, None, None, s, one, one)
 
         def on_():
-            s = ops.rpn_loss2d_fwd(plan, C, lt, obj, reg, flags, targets, bx, offs, None, midx, cams, res)
-            ops.rpn_loss2d_bwd(plan, C, lt, obj, reg, flags, targets, bx, offs, None, midx, cams, res, s, one, one, one)
+            s = ops.rpn_loss_fwd(plan, C, lt, obj, reg, flags, targets, bx, offs, None, midx, cams, res)
+            ops.rpn_loss_bwd(plan, C, lt, obj, reg, flags, targets, bx, offs, None, midx, cams, res, s, one, one, one)
 
         t0, t1 = B.timed(off, reps), B.timed(on_, reps)
         print(f"{name:16s} loss fwd + bwd  off {t0[0]:8.1f} us (min {t0[1]:8.1f})   on {t1[0]:8.1f} us (min {t1[1]:8.1f})   positives {int((flags == 1).sum())}")
         if not rotated:
-            fused = ops.rpn_loss2d_fwd(plan, C, lt, obj, reg, flags, targets, bx, offs, None, midx, cams, res)[3].item()
+            fused = ops.rpn_loss_fwd(plan, C, lt, obj, reg, flags, targets, bx, offs, None, midx, cams, res)[3].item()
             anchors = torch.cat(gen(torch.zeros((1, 1, *B.MESH)), obj)[0][:1]).cuda()
             n = anchors.shape[0]
 

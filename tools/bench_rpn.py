@@ -229,10 +229,7 @@ def iou_rows(reps):
     offs_dev = torch.tensor(offsets[:-1], dtype=torch.int64).cuda()
 
     def fused(loss_type):
-        if loss_type == "smooth_l1":
-            out = rpn._RpnLoss.apply(plan, 8, flags, targets, *heads)
-        else:
-            out = rpn._RpnIoULoss.apply(plan, loss_type, flags, bx, offsets, None, midx, *heads)
+        out = rpn._RpnLoss.apply(plan, 8, None if loss_type == "smooth_l1" else loss_type, None, None, flags, targets, bx, offsets, None, midx, *heads)
         torch.autograd.grad(out[0] + out[1], heads)
         return out
 
