@@ -41,6 +41,21 @@ NMH_API int nmh_gemm_nt_window_scatter(int dt, const void* A, int64_t lda, const
  * ws (optional, ws_floats fp32): scratch for the partial tiles of a split contraction; with it the splits are summed by a second
  * launch instead of fp32 global atomics (one scratch per stream: concurrent calls must not share it). */
 NMH_API int nmh_gemm_tn(int dt, const void* A, int64_t lda, const void* B, int64_t ldb, float* dW, int64_t M, int N, int K, const float* rowscale, int rows_per_scale, int omode, int64_t ldo, int p0, int p1, float* dbias, float* ws, int64_t ws_floats, void* stream);
+/* Which kernel nmh_gemm_nt / nmh_gemm_tn would launch for these arguments: the launch path decides through the same function.
+ * Pure host queries: nothing is launched and no device is touched (they work on a machine without a GPU).  Status 0, -2 for a shape
+ * the GEMM itself rejects, -4 for a bad argument.
+ * nmh_gemm_nt_plan: plan[6] = {family, MT, NT, ring stages, contraction splits, narrow}; family 0: register-prefetch kernel, tile
+ *   (64 MT) x (16 NT); 1: LDS-DMA ring, same tile; 2: two-k-tile kernel (K <= 128), 64 x (16 NT); 3: 2 x 2-wave kernel, tile
+ *   (32 MT) x (32 NT).  narrow = 1 when the narrow-tile rule picked the tile.  win_on / up_k / ksplit: the epilogue fields the decision
+ *   reads (window scatter, transpose-conv store, split contraction: 0 / 0 / 1 for nmh_gemm_nt); batch = grid.z samples (1).
+ * nmh_gemm_nt_plan_table: every {dt, family, MT, NT, stages} the launcher can launch for plain row-major operands; rows[5 * capacity]
+ *   (may be NULL), *count = number of rows.
+ * nmh_gemm_tn_plan: plan[6] = {NTW, KTW, ring stages, rows per split, splits, partials}; output tile (32 NTW) x (32 KTW); stages 0 = the
+ *   plain kernel; partials 1 = the splits go through the workspace and a reduce launch, 0 = they add into dW (fp32 atomics when
+ *   splits > 1).  ws_floats: the workspace nmh_gemm_tn would be given (0: none). */
+NMH_API int nmh_gemm_nt_plan(int dt, int64_t lda, int64_t ldw, int M, int N, int K, int win_on, int up_k, int ksplit, int batch, int* plan);
+NMH_API int nmh_gemm_nt_plan_table(int* rows, int capacity, int* count);
+NMH_API int nmh_gemm_tn_plan(int dt, int64_t lda, int64_t M, int N, int K, int has_rowscale, int rows_per_scale, int64_t ws_floats, int* plan);
 /* Grouped form of nmh_gemm_tn for bf16 operands (dt must be 1): `probs` is a HOST array of nprob descriptors; every problem is
  * dW[N,K] += sum_m rowscale[m / rows_per_sample] * A[m,N]^T . B[m,K] (+ dbias[N] += column sums of A), M a multiple of rows_per_sample.
  * The four Linear weight gradients of every Swin block of a stage (swin_mae3d.py:366-369 backward: attn.qkv, attn.proj, mlp.0, mlp.3)

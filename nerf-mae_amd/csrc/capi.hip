@@ -31,6 +31,10 @@ int nmh_gemm_nt(int dt, const void* A, int64_t lda, const void* W, int64_t ldw, 
   CLR();
   REQ(A, W, C);
   if (M <= 0) return 0;
+  // every operand and output access of the kernels is a 16-byte vector: a row stride that is not a whole number of them would put rows
+  // off that alignment, which none of the loaders (ADirect::load, Vec8) is written for
+  const int64_t e16 = dt == NMH_DT_BF16_C ? 8 : 4;
+  if (lda % e16 || ldw % e16 || ldc % e16) return -2;
   EpiParams ep{C, ldc, bias, act, C2, resid, rowscale, rows_per_scale > 0 ? rows_per_scale : 1, accumulate};
   return k_gemm_nt(dt, A, lda, W, ldw, M, N, K, ep, ST);
 }
@@ -52,6 +56,21 @@ int nmh_gemm_tn(int dt, const void* A, int64_t lda, const void* B, int64_t ldb, 
   gm.omode = omode; gm.ldo = ldo; gm.dbias = dbias; gm.ws = ws; gm.ws_floats = ws ? (long)ws_floats : 0;
   if (omode == 2) { gm.Cin = p0; gm.V = (unsigned)p1; gm.dC = make_fdiv(p0); }
   return k_gemm_tn(dt, A, lda, B, ldb, dW, M, N, K, rowscale, rows_per_scale > 0 ? rows_per_scale : 1, gm, ST);
+}
+int nmh_gemm_nt_plan(int dt, int64_t lda, int64_t ldw, int M, int N, int K, int win_on, int up_k, int ksplit, int batch, int* plan) {
+  REQ(plan);
+  if ((dt != 0 && dt != NMH_DT_BF16_C) || M <= 0 || N <= 0 || K <= 0 || batch <= 0) return -4;
+  return k_gemm_nt_plan(dt, (long)lda, (long)ldw, M, N, K, batch, win_on, up_k, ksplit, plan);
+}
+int nmh_gemm_nt_plan_table(int* rows, int capacity, int* count) {
+  REQ(count);
+  *count = k_gemm_nt_plan_table(rows, rows ? capacity : 0);
+  return 0;
+}
+int nmh_gemm_tn_plan(int dt, int64_t lda, int64_t M, int N, int K, int has_rowscale, int rows_per_scale, int64_t ws_floats, int* plan) {
+  REQ(plan);
+  if ((dt != 0 && dt != NMH_DT_BF16_C) || M <= 0 || N <= 0 || K <= 0) return -4;
+  return k_gemm_tn_plan(dt, (long)lda, (long)M, N, K, has_rowscale, rows_per_scale, (long)ws_floats, plan);
 }
 int nmh_gemm_tn_grouped(int dt, const nmh_tn_problem* probs, int nprob, float* ws, int64_t ws_floats, void* stream) {
   CLR();

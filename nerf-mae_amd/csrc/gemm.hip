@@ -14,7 +14,7 @@
 #include "kernels.hpp"
 #include <cstdlib>
 #include <type_traits>
-static inline bool lda_ok(long lda, long ldb) { return lda % 8 == 0 && ldb % 8 == 0; }
+#include "gemm_plan.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // fast unsigned division by a runtime constant (n < 2^31), host-built
@@ -637,43 +637,19 @@ static int launch_nt_w22(const bf16_t* A, long lda, const void* Bw, long ldb, in
 // cfg = MT * 100 + NT * 10 + ST
 static int launch_nt_w22_cfg(int cfg, const bf16_t* A, long lda, const void* Bw, long ldb, int M, int N, int K, const EpiParams& ep, hipStream_t st) {
   switch (cfg) {
-#define W22(mt, nt, s) case mt * 100 + nt * 10 + s: return launch_nt_w22<mt, nt, s>(A, lda, Bw, ldb, M, N, K, ep, st)
-    W22(4, 4, 2); W22(4, 4, 3); W22(4, 3, 2); W22(4, 3, 3); W22(2, 4, 2); W22(2, 4, 3); W22(2, 4, 4); W22(2, 3, 3); W22(2, 3, 4); W22(2, 2, 4); W22(4, 2, 3); W22(4, 2, 4);
+#define W22(mt, nt, s) case mt * 100 + nt * 10 + s: return launch_nt_w22<mt, nt, s>(A, lda, Bw, ldb, M, N, K, ep, st);
+    NMH_NT_W22_CFGS(W22)
 #undef W22
   }
   return -2;
 }
 
-// The pipelined kernel pays off where few workgroups exist to hide a global-load latency per k-tile (measured, M <= 8192:
-// fc2 4000x384x1536 21.9 -> 15.2 us, 500x768x3072 34.6 -> 24.5 us; with K = 384 the 4-deep ring holds most of the contraction at once:
-// whole step at 1 grid/GPU 13.75 -> 13.35 ms with the threshold lowered from K >= 1024 to K >= 384); with >= 1000 workgroups the
-// register-prefetch kernel's smaller LDS footprint (more co-resident workgroups) wins.  NMH_GEMM_DMA=0 disables, =3/4 forces it.
-template <typename T, int MT, int NT, class AL>
-static bool try_dma(const AL& al, const void* Bw, long ldb, int M, int N, int K, int batch, const EpiParams& ep, hipStream_t st, int* rc) {
-  if constexpr (std::is_same<AL, ADirect<bf16_t>>::value && MT == 1) {
-    static const int dma_st = [] { const char* e = getenv("NMH_GEMM_DMA"); return e ? atoi(e) : -1; }();
-    if (dma_st == 0 || !lda_ok(al.lda, ldb)) return false;
-    static const int min_k = [] { const char* e = getenv("NMH_GEMM_DMA_MINK"); return e ? atoi(e) : 384; }();
-    static const long max_m = [] { const char* e = getenv("NMH_GEMM_DMA_MAXM"); return e ? atol(e) : 8192L; }();
-    // (K < 1024: only while the launch has <= 640 workgroups -- 4000x1536x384 = 1008 workgroups measured 17.2 us with the register-prefetch kernel against 20.9, 8000x1536x384 = 2000 workgroups 37 us with the register-prefetch
-    //  kernel, 50 us with this one)
-    const long wgs = ((long)M + 64 * MT - 1) / (64 * MT) * ((N + 16 * NT - 1) / (16 * NT)) * batch;
-    const bool auto_on = dma_st < 0 && (long)M * batch <= max_m && (K >= 1024 || (K >= min_k && wgs <= 640));
-    if (dma_st == 3) { *rc = launch_nt_dma<MT, NT, 3>(al, Bw, ldb, M, N, K, batch, ep, st); return true; }
-    if (dma_st == 4 || auto_on) { *rc = launch_nt_dma<MT, NT, 4>(al, Bw, ldb, M, N, K, batch, ep, st); return true; }
-  }
-  return false;
-}
-
+// register-prefetch kernel at one (64 MT) x (16 NT) tile
 template <typename T, int MT, int NT, class AL>
 static int launch_nt(const AL& al, const void* Bw, long ldb, int M, int N, int K, int batch, const EpiParams& ep, hipStream_t st) {
   constexpr int BM = 64 * MT, BN = 16 * NT;
   constexpr int lds_main = 2 * (BM + BN) * 128, lds_epi = 4 * 16 * (BN + 4) * 4;
   constexpr int lds = lds_main > lds_epi ? lds_main : lds_epi;
-  {
-    int rc = 0;
-    if (try_dma<T, MT, NT, AL>(al, Bw, ldb, M, N, K, batch, ep, st, &rc)) return rc;
-  }
   dim3 grid((M + BM - 1) / BM, (N + BN - 1) / BN, batch * (ep.ksplit > 1 ? ep.ksplit : 1));
   static NmhPerDeviceOnce attr_set;  // > 64 KiB of dynamic LDS must be opted into once per kernel
   if (attr_set.need()) {
@@ -686,91 +662,77 @@ static int launch_nt(const AL& al, const void* Bw, long ldb, int M, int N, int K
   return 0;
 }
 
-// which launches take the 2 x 2-wave kernel, and with which tile (0: none).  NMH_GEMM_W22=<cfg> forces one tile everywhere it applies (tools/bench_nt_w22.py),
-// NMH_GEMM_W22=0 disables.
-static int w22_config(int M, int N, int K, const EpiParams& ep) {
-  const char* e = getenv("NMH_GEMM_W22");   // (read per dispatch: the tile sweep changes it inside one process)
-  const int forced = e ? atoi(e) : -1;
-  if (forced >= 0) return (K >= 64 && N >= 64) ? forced : 0;
-  // measured (tools/bench_nt_w22.py, graph replay, 8 grids; default dispatch -> this kernel): stage-2 Linears on 8000 rows 384 x 1536: 21.4 -> 17.3 us,
-  // 384 x 1152: 17.1 -> 14.2, 384 x 384: 10.0 -> 9.2 (64 x 96 tiles, ring of 3: 60 KB), 1536 x 384 + GELU' epilogue: 31.1 -> 24.9 (64 x 128, ring of 2: 48 KB);
-  // stage-1 Linears on 64000 rows 192 x 768: 49.7 -> 40.4, 192 x 576: 37.8 -> 34.0 (128 x 128, ring of 2).  4000 rows: 15.0 -> 13.9; 1000 rows lose (8.1 -> 12).
-  if (ep.win_on) return 0;
-  if (M >= 2048 && M <= 16384 && K >= 384) {
-    if (N % 96 == 0 && N <= 768) return 233;
-    if (N % 128 == 0) return 242;
+// launches what nt_plan (gemm_plan.hpp) decided: the one switch over the compiled kernels
+template <typename T, class AL>
+static int launch_nt_plan(const NtPlan& p, const AL& al, const void* Bw, long ldb, int M, int N, int K, int batch, const EpiParams& ep, hipStream_t st) {
+  if constexpr (std::is_same<AL, ADirect<bf16_t>>::value) {
+    if (p.family == NT_W22) return launch_nt_w22_cfg(p.w22cfg, al.A, al.lda, Bw, ldb, M, N, K, ep, st);
+    if (p.family == NT_K128) {
+      switch (p.nt) {
+#define K128(nt) case nt: return launch_nt_k128<nt>(al.A, al.lda, Bw, ldb, M, N, K, ep, st);
+        NMH_NT_K128_TILES(K128)
+#undef K128
+      }
+      return -2;
+    }
+    if (p.family == NT_DMA) {
+      switch (p.nt * 10 + p.stages) {
+#define DMA(nt) case nt * 10 + 3: return launch_nt_dma<1, nt, 3>(al, Bw, ldb, M, N, K, batch, ep, st); \
+                case nt * 10 + 4: return launch_nt_dma<1, nt, 4>(al, Bw, ldb, M, N, K, batch, ep, st);
+        NMH_NT_DMA_TILES(DMA)
+#undef DMA
+      }
+      return -2;
+    }
   }
-  if (M >= 32768 && N == 192 && K >= 576) return 442;
-  return 0;
+  if (p.family != NT_REG) return -2;
+  switch (p.mt * 100 + p.nt) {
+#define REG(mt, nt) case mt * 100 + nt: return launch_nt<T, mt, nt, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
+    NMH_NT_REG_TILES(REG)
+#undef REG
+  }
+  return -2;
 }
 
 template <typename T, class AL>
 static int dispatch_nt(const AL& al, const void* Bw, long ldb, int M, int N, int K, int batch, const EpiParams& ep, hipStream_t st) {
-  if (N % 8 != 0 || K % 8 != 0) return -2;
-  const int t16 = (N + 15) / 16;
-  if constexpr (std::is_same<AL, ADirect<bf16_t>>::value) {
-    if (batch == 1 && ep.ksplit <= 1 && !ep.up_k && lda_ok(al.lda, ldb)) {
-      const int cfg = w22_config(M, N, K, ep);
-      if (cfg > 0) return launch_nt_w22_cfg(cfg, al.A, al.lda, Bw, ldb, M, N, K, ep, st);
-    }
-  }
-  if (const char* ov = getenv("NMH_GEMM_CFG")) {  // tuning override "MT,NT"
-    int mt = ov[0] - '0', nt = atoi(ov + 2);
-    if (mt == 1 && nt == 2) return launch_nt<T, 1, 2, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-    if (mt == 1 && nt == 3) return launch_nt<T, 1, 3, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-    if (mt == 1 && nt == 4) return launch_nt<T, 1, 4, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-    if (mt == 1 && nt == 6) return launch_nt<T, 1, 6, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-    if (mt == 1 && nt == 8) return launch_nt<T, 1, 8, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-    if (mt == 2 && nt == 6) return launch_nt<T, 2, 6, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-    if (mt == 2 && nt == 8) return launch_nt<T, 2, 8, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-    if (mt == 4 && nt == 6) return launch_nt<T, 4, 6, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-    if (mt == 4 && nt == 8) return launch_nt<T, 4, 8, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-  }
-  // 64-row tiles (32-45 KB of LDS -> 3-5 workgroups per CU) for (a) small problems (stage 2/3 tokens, 10^3..20^3 decoder volumes), so
-  // that more than a few dozen CUs get work, and (b) short contractions (every Linear of the encoder, the transpose convs): those
-  // are HBM-bound with a latency-bound prologue/epilogue per workgroup, and co-resident workgroups are what hides it
-  // (measured on 256000x288x96: 145 us with 256x128 tiles, 67 us with 64x96)
-  if (((long)M * batch <= 8192 || K <= 1024) && t16 >= 4) {
-    // wide outputs of the 40^3-token Linears (fc1 / fc2-dgrad: N = 384, K = 96, >= 256 k rows) are write-bound: 128-column tiles store
-    // 256-byte-aligned row segments (96-column tiles split every second 128-byte line between two workgroups): 393 -> 312 us at 512 k rows
-    if constexpr (std::is_same<AL, ADirect<bf16_t>>::value) {
-      static const int k128_on = getenv("NMH_GEMM_K128") ? atoi(getenv("NMH_GEMM_K128")) : 1;
-      static const long k128_min = getenv("NMH_GEMM_K128_MINM") ? atol(getenv("NMH_GEMM_K128_MINM")) : 16384;
-      if (k128_on && batch == 1 && ep.ksplit <= 1 && K <= 128 && M >= k128_min && lda_ok(al.lda, ldb)) {
-        static const long nt8_min = getenv("NMH_GEMM_K128_NT8_MINM") ? atol(getenv("NMH_GEMM_K128_NT8_MINM")) : 16384;   // (1 grid: 64000 rows -- 12.48 -> 12.43 ms with 128-column tiles there too)
-        if (t16 % 8 == 0 && (long)M >= nt8_min) return launch_nt_k128<8>(al.A, al.lda, Bw, ldb, M, N, K, ep, st);
-        if (t16 % 6 == 0) return launch_nt_k128<6>(al.A, al.lda, Bw, ldb, M, N, K, ep, st);
-        if (t16 % 4 == 0) return launch_nt_k128<4>(al.A, al.lda, Bw, ldb, M, N, K, ep, st);
-      }
-    }
-    // launches of a few dozen workgroups with a long contraction (stage 3 / 4 Linears at 1-2 grids per GPU): one workgroup per CU is
-    // bound by its own LDS fragment reads (a wave reads the whole B tile: 56 KB per 64-deep k-tile with 96 columns, 24 KB with 32), so the
-    // narrowest tile that still gives at most 1.5 workgroups per CU wins (measured, graph replay: 1000x384x1536 13.3 -> 8.0 us,
-    // 125x768x3072 22.7 -> 12.9, 512x768x1536 13.3 -> 8.0, 216x768x768 8.1 -> 5.0; 4000x384x1536 stays at 96 columns: 15.1 vs 17.9 / 23.7)
-    if constexpr (std::is_same<AL, ADirect<bf16_t>>::value) {
-      static const int narrow_on = getenv("NMH_GEMM_NARROW") ? atoi(getenv("NMH_GEMM_NARROW")) : 1;
-      if (narrow_on && K >= 384 && ep.ksplit <= 1 && lda_ok(al.lda, ldb)) {   // (aligned rows: these launches take the LDS-DMA kernel)
-        const long rt = ((long)M + 63) / 64 * batch;
-        auto fits = [&](int nt) { return t16 % nt == 0 && rt * (t16 / nt) <= 384; };
-        if (rt * ((t16 + 5) / 6) <= 192) {   // (252 workgroups of 96 columns -- 4000x384x1536 -- are already one per CU)
-          if (fits(2)) return launch_nt<T, 1, 2, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-          if (fits(3)) return launch_nt<T, 1, 3, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-          if (fits(4)) return launch_nt<T, 1, 4, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-        }
-      }
-    }
-    if (t16 % 8 == 0 && K <= 128 && (long)M * batch >= 100000) return launch_nt<T, 1, 8, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-    if (t16 % 6 == 0) return launch_nt<T, 1, 6, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-    if (t16 % 4 == 0) return launch_nt<T, 1, 4, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-    if (t16 % 3 == 0) return launch_nt<T, 1, 3, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-    return launch_nt<T, 1, 4, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-  }
-  if (t16 <= 3) return launch_nt<T, 4, 3, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-  if (t16 == 4) return launch_nt<T, 4, 4, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-  // long contractions on big M (implicit-GEMM convs at 20^3..40^3, transpose-conv dgrad): 128-row tiles (2 workgroups per CU)
-  // measured 10-30 % faster than 256-row tiles (1 per CU) on every decoder shape
-  if (t16 % 6 == 0) return launch_nt<T, 2, 6, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
-  return launch_nt<T, 2, 8, AL>(al, Bw, ldb, M, N, K, batch, ep, st);
+  long lda = 0;
+  if constexpr (std::is_same<AL, ADirect<T>>::value) lda = al.lda;
+  const NtShape s{std::is_same<AL, ADirect<bf16_t>>::value, lda, ldb, M, N, K, batch, ep.win_on, ep.up_k, ep.ksplit};
+  NtPlan p;
+  if (int rc = nt_plan(s, &p)) return rc;
+  return launch_nt_plan<T, AL>(p, al, Bw, ldb, M, N, K, batch, ep, st);
+}
+
+// the plan of a plain row-major (ADirect) launch as {family, MT, NT, stages, ksplit, narrow}; 0 or -2
+int k_gemm_nt_plan(int dt, long lda, long ldb, int M, int N, int K, int batch, int win_on, int up_k, int ksplit, int* plan) {
+  const NtShape s{dt == NMH_DT_BF16, lda, ldb, M, N, K, batch, win_on, up_k, ksplit};
+  NtPlan p;
+  if (int rc = nt_plan(s, &p)) return rc;
+  plan[0] = p.family; plan[1] = p.mt; plan[2] = p.nt; plan[3] = p.stages; plan[4] = p.ksplit; plan[5] = p.narrow;
+  return 0;
+}
+// every plan launch_nt_plan's switch holds for ADirect operands: bf16 (dt 1) all families, fp32 (dt 0) the register-prefetch tiles;
+// rows of {dt, family, MT, NT, stages}; returns the row count (rows beyond `cap` are not written)
+int k_gemm_nt_plan_table(int* rows, int cap) {
+  int n = 0;
+  auto add = [&](int dt, int fam, int mt, int nt, int stg) {
+    if (rows && n < cap) { int* r = rows + 5 * n; r[0] = dt; r[1] = fam; r[2] = mt; r[3] = nt; r[4] = stg; }
+    ++n;
+  };
+#define REG(mt, nt) add(NMH_DT_BF16, NT_REG, mt, nt, 0); add(NMH_DT_F32, NT_REG, mt, nt, 0);
+  NMH_NT_REG_TILES(REG)
+#undef REG
+#define DMA(nt) add(NMH_DT_BF16, NT_DMA, 1, nt, 3); add(NMH_DT_BF16, NT_DMA, 1, nt, 4);
+  NMH_NT_DMA_TILES(DMA)
+#undef DMA
+#define K128(nt) add(NMH_DT_BF16, NT_K128, 1, nt, 0);
+  NMH_NT_K128_TILES(K128)
+#undef K128
+#define W22(mt, nt, s) add(NMH_DT_BF16, NT_W22, mt, nt, s);
+  NMH_NT_W22_CFGS(W22)
+#undef W22
+  return n;
 }
 
 int k_gemm_nt(int dt, const void* A, long lda, const void* Bw, long ldb, int M, int N, int K, const EpiParams& ep, hipStream_t st) {
@@ -1238,9 +1200,6 @@ __global__ __launch_bounds__(256) void tn_reduce_kernel(const float* __restrict_
     else gm.dbias[n] += s;
   }
 }
-// many splits of a small output (the 256000-row stage-0 gradients: 125-250 splits) would write more partial bytes than the operands
-// hold; those keep the atomics
-static int tn_ws_max_splits() { static const int v = getenv("NMH_TN_WS_SPLITS") ? atoi(getenv("NMH_TN_WS_SPLITS")) : 16; return v; }
 // plain row-major output, K % 4 == 0: four output elements per thread (16-byte partial loads and one 16-byte read-modify-write)
 __global__ __launch_bounds__(256) void tn_reduce4_kernel(const float* __restrict__ part, int gz, int N, int K, float* __restrict__ Out, TnGeom gm) {
   const long i4 = (long)blockIdx.x * 256 + threadIdx.x, NK = (long)N * K, NK4 = NK >> 2;
@@ -1277,67 +1236,58 @@ static int launch_tn_reduce(const TnGeom& gm, int gz, int N, int K, float* Out, 
 }
 
 template <class BL, int ST>
-static int launch_tn_dma(const void* A, long lda, const void* Bm, const BL& bl, float* Out, long Mtot, int N, int K, long mps, const float* rs, int rps, const TnGeom& gm0, hipStream_t st) {
+static int launch_tn_dma(const TnPlan& p, const void* A, long lda, const void* Bm, const BL& bl, float* Out, long Mtot, int N, int K, const float* rs, int rps, const TnGeom& gm0, hipStream_t st) {
   constexpr int lds = ST * 2 * 64 * 192;
-  int gx = (N + 95) / 96, gy = (K + 95) / 96, gz = (int)((Mtot + mps - 1) / mps);
+  int gx = (N + 95) / 96, gy = (K + 95) / 96, gz = p.splits;
   TnGeom gm = gm0;
-  gm.part = (gm.ws && gz > 1 && gz <= tn_ws_max_splits() && (long)gz * N * (K + 1) <= gm.ws_floats) ? gm.ws : nullptr;
+  gm.part = p.part ? gm.ws : nullptr;
   static NmhPerDeviceOnce attr_set;
   if (attr_set.need()) {
     hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_dma_kernel<BL, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;
     attr_set.set();
   }
-  hipLaunchKernelGGL((gemm_tn_dma_kernel<BL, ST>), dim3(gx, gy, gz), dim3(256), lds, st, (const bf16_t*)A, lda, (const bf16_t*)Bm, bl, Out, Mtot, N, K, (int)mps, rs, rps, gm);
+  hipLaunchKernelGGL((gemm_tn_dma_kernel<BL, ST>), dim3(gx, gy, gz), dim3(256), lds, st, (const bf16_t*)A, lda, (const bf16_t*)Bm, bl, Out, Mtot, N, K, (int)p.mps, rs, rps, gm);
   NMH_CHECK_LAUNCH();
   if (gm.part) return launch_tn_reduce(gm, gz, N, K, Out, st);
   return 0;
 }
 
 template <typename T, int NTW, int KTW, class BL>
-static int launch_tn(const void* A, long lda, const void* Bm, const BL& bl, float* Out, long Mtot, int N, int K, const float* rs, int rps, const TnGeom& gm, hipStream_t st) {
+static int launch_tn(const TnPlan& p, const void* A, long lda, const void* Bm, const BL& bl, float* Out, long Mtot, int N, int K, const float* rs, int rps, const TnGeom& gm, hipStream_t st) {
   constexpr int BNW = 32 * NTW, BKW = 32 * KTW;
   int gx = (N + BNW - 1) / BNW, gy = (K + BKW - 1) / BKW;
-  // the load->LDS->MFMA chain of one workgroup is not software-pipelined: latency is hidden by co-resident workgroups, so a
-  // long contraction (conv wgrad over 4M voxels) wants ~4 workgroups per CU; short ones are bounded by the atomics instead
-  long want = (Mtot >= (1L << 20) ? 1024 : 512) / ((long)gx * gy);  // aim for ~512 workgroups; many output tiles => no split (and no atomics)
-  if (want < 1) want = 1;
-  long mps = (Mtot + want - 1) / want;
-  mps = (mps + 63) / 64 * 64;
-  long mps_min = 1024;                 // every split ends in BNW*BKW atomics: give it >= 16 chunks of MFMA work first
-  if (const char* e = getenv("NMH_TN_MPS")) mps_min = atol(e);
-  if (const char* e = getenv("NMH_TN_WANT")) { want = atol(e) / ((long)gx * gy); if (want < 1) want = 1; mps = ((Mtot + want - 1) / want + 63) / 64 * 64; }
-  if (mps < mps_min) mps = mps_min;
   if constexpr (std::is_same<T, bf16_t>::value && NTW == 3 && KTW == 3) {
-    // measured: 8-12 % on the implicit-GEMM conv weight gradients (their gather loader is the longer dependency chain), within
-    // noise on the plain ones (which are bound by L2 -> LDS bandwidth of the 96x96 tiles, not by latency): default on for convs only
-    static const int dma_st = [] { const char* e = getenv("NMH_TN_DMA"); return e ? atoi(e) : (std::is_same<BL, BConv3TN>::value ? 3 : 0); }();
-    if (dma_st && lda % 8 == 0) {
-      long m2 = mps;
-      if (rs) {   // row scales are applied per split: every split must lie inside one sample
-        long j = (rps + m2 - 1) / m2;
-        while (j > 1 && rps % j) --j;
-        m2 = rps / j;
-      }
-      if (dma_st == 2) return launch_tn_dma<BL, 2>(A, lda, Bm, bl, Out, Mtot, N, K, m2, rs, rps, gm, st);
-      if (dma_st == 4) return launch_tn_dma<BL, 4>(A, lda, Bm, bl, Out, Mtot, N, K, m2, rs, rps, gm, st);
-      return launch_tn_dma<BL, 3>(A, lda, Bm, bl, Out, Mtot, N, K, m2, rs, rps, gm, st);
-    }
+    if (p.stages == 2) return launch_tn_dma<BL, 2>(p, A, lda, Bm, bl, Out, Mtot, N, K, rs, rps, gm, st);
+    if (p.stages == 4) return launch_tn_dma<BL, 4>(p, A, lda, Bm, bl, Out, Mtot, N, K, rs, rps, gm, st);
+    if (p.stages) return launch_tn_dma<BL, 3>(p, A, lda, Bm, bl, Out, Mtot, N, K, rs, rps, gm, st);
   }
-  int gz = (int)((Mtot + mps - 1) / mps);
+  int gz = p.splits;
   TnGeom gp = gm;
-  gp.part = (gp.ws && gz > 1 && gz <= tn_ws_max_splits() && (long)gz * N * (K + 1) <= gp.ws_floats) ? gp.ws : nullptr;
-  hipLaunchKernelGGL((gemm_tn_kernel<T, NTW, KTW, BL>), dim3(gx, gy, gz), dim3(256), 0, st, (const T*)A, lda, (const T*)Bm, bl, Out, Mtot, N, K, (int)mps, rs, rps, gp);
+  gp.part = p.part ? gp.ws : nullptr;
+  hipLaunchKernelGGL((gemm_tn_kernel<T, NTW, KTW, BL>), dim3(gx, gy, gz), dim3(256), 0, st, (const T*)A, lda, (const T*)Bm, bl, Out, Mtot, N, K, (int)p.mps, rs, rps, gp);
   NMH_CHECK_LAUNCH();
   if (gp.part) return launch_tn_reduce(gp, gz, N, K, Out, st);
   return 0;
 }
 
+// launches what tn_plan (gemm_plan.hpp) decided
 template <typename T, class BL>
 static int dispatch_tn(const void* A, long lda, const void* Bm, const BL& bl, float* Out, long Mtot, int N, int K, const float* rs, int rps, const TnGeom& gm, hipStream_t st) {
-  if (K % 8 != 0 || lda % 8 != 0) return -2;  // N may be ragged: A rows are padded to lda, output guarded by n < N
-  if (N <= 48) return launch_tn<T, 2, 3, BL>(A, lda, Bm, bl, Out, Mtot, N, K, rs, rps, gm, st);   // 64 x 96 tile (N padded)
-  return launch_tn<T, 3, 3, BL>(A, lda, Bm, bl, Out, Mtot, N, K, rs, rps, gm, st);                  // 96 x 96 tile
+  const TnShape s{std::is_same<T, bf16_t>::value, std::is_same<BL, BConv3TN>::value, lda, Mtot, N, K, rs != nullptr, rps, gm.ws != nullptr, gm.ws_floats};
+  TnPlan p;
+  if (int rc = tn_plan(s, &p)) return rc;
+  if (p.ntw == 2) return launch_tn<T, 2, 3, BL>(p, A, lda, Bm, bl, Out, Mtot, N, K, rs, rps, gm, st);   // 64 x 96 tile (N padded)
+  return launch_tn<T, 3, 3, BL>(p, A, lda, Bm, bl, Out, Mtot, N, K, rs, rps, gm, st);                    // 96 x 96 tile
+}
+
+// the plan of a plain row-major (BDirectTN) launch as {ntw, ktw, stages, rows per split, splits, part}; 0 or -2
+int k_gemm_tn_plan(int dt, long lda, long M, int N, int K, int has_rowscale, int rows_per_scale, long ws_floats, int* plan) {
+  const TnShape s{dt == NMH_DT_BF16, false, lda, M, N, K, has_rowscale != 0, rows_per_scale > 0 ? rows_per_scale : 1, ws_floats > 0, ws_floats};
+  TnPlan p;
+  if (int rc = tn_plan(s, &p)) return rc;
+  plan[0] = p.ntw; plan[1] = p.ktw; plan[2] = p.stages; plan[3] = (int)p.mps; plan[4] = p.splits; plan[5] = p.part;
+  return 0;
 }
 
 int k_gemm_tn(int dt, const void* A, long lda, const void* Bm, long ldb, float* Out, long M, int N, int K, const float* rowscale, int rows_per_scale, const TnGeom& gm, hipStream_t st) {

@@ -88,6 +88,10 @@ __device__ __forceinline__ long tok_to_win(const WinMap& w, long tok) {
 
 #endif
 int k_gemm_nt(int dt, const void* A, long lda, const void* Bw, long ldb, int M, int N, int K, const EpiParams& ep, hipStream_t st);
+// the kernel plans the two GEMM dispatches decide on (gemm_plan.hpp), as int rows for the C ABI: pure host functions, no launch
+int k_gemm_nt_plan(int dt, long lda, long ldb, int M, int N, int K, int batch, int win_on, int up_k, int ksplit, int* plan);
+int k_gemm_nt_plan_table(int* rows, int cap);
+int k_gemm_tn_plan(int dt, long lda, long M, int N, int K, int has_rowscale, int rows_per_scale, long ws_floats, int* plan);
 // ConvTranspose3d (kernel = stride = k) as GEMMs with the pixel shuffle folded into addressing (unetr_block.py:151-158):
 //   fwd:   cat[fine][0:Cout] = x[coarse] . Wt^T + bias   (Wt packed [(tap,co)][ci])
 //   dgrad: dx[coarse][ci] = sum_(tap,co) dcat[fine][co] Wd[ci][(tap,co)]

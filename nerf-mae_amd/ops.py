@@ -114,15 +114,52 @@ class WinGeom:
 def gemm_nt(A, W, bias=None, act=0, C2=None, resid=None, rowscale=None, rows_per_scale=1, out=None, accumulate=False,
             M=None, N=None, K=None):
     """out[M,N] = epi(A[M,K] @ W[N,K]^T)."""
-    _chk(A, W, bias, C2, resid, rowscale, out)
     M = A.shape[0] if M is None else M
     K = A.shape[-1] if K is None else K
     N = W.shape[0] if N is None else N
+    ldc = N if out is None else out.stride(0)
+    for name, t in (("C2", C2), ("resid", resid)):   # the epilogue indexes both with the output's row stride
+        ld = None if t is None else (t.stride(-2) if t.dim() > 1 else N)
+        if ld is not None and ld != ldc:
+            raise ValueError(f"gemm_nt: {name} has row stride {ld}, out has {ldc}: they must agree")
+    _chk(A, W, bias, C2, resid, rowscale, out)
     if out is None:
         out = torch.empty((M, N), dtype=A.dtype, device=A.device)
-    lib().call("nmh_gemm_nt", dt_of(A), A, A.stride(0) if A.dim() > 1 else K, W, W.stride(0), M, N, K, out, out.stride(0), bias, act, C2,
+    lib().call("nmh_gemm_nt", dt_of(A), A, A.stride(0) if A.dim() > 1 else K, W, W.stride(0), M, N, K, out, ldc, bias, act, C2,
                resid, rowscale, rows_per_scale, int(accumulate), _st())
     return out
+
+
+NT_FAMILIES = ("reg", "dma", "k128", "w22")   # include/nerfmae_hip.h: nmh_gemm_nt_plan
+
+
+def gemm_nt_plan(dtype, M, N, K, lda=None, ldw=None, win_on=False, up_k=0, ksplit=1, batch=1):
+    """The kernel gemm_nt would launch for these arguments, as (family, MT, NT, ring stages, contraction splits, narrow); asked of the
+    library's own dispatch (a host query: no launch, no device)."""
+    plan = (ctypes.c_int * 6)()
+    lib().call("nmh_gemm_nt_plan", BF16 if dtype == torch.bfloat16 else F32, K if lda is None else lda, K if ldw is None else ldw, M, N, K,
+               int(win_on), up_k, ksplit, batch, plan)
+    return (NT_FAMILIES[plan[0]],) + tuple(plan[1:6])
+
+
+def gemm_nt_plan_table():
+    """Every (dtype, family, MT, NT, ring stages) the gemm_nt launcher holds for plain row-major operands."""
+    cnt = (ctypes.c_int * 1)()
+    lib().call("nmh_gemm_nt_plan_table", None, 0, cnt)
+    n = cnt[0]
+    rows = (ctypes.c_int * (5 * n))()
+    lib().call("nmh_gemm_nt_plan_table", rows, n, cnt)
+    return [(torch.bfloat16 if rows[5 * i] == BF16 else torch.float32, NT_FAMILIES[rows[5 * i + 1]]) + tuple(rows[5 * i + 2:5 * i + 5]) for i in range(n)]
+
+
+def gemm_tn_plan(dtype, M, N, K, lda=None, rowscale=False, rows_per_scale=1, ws_floats=None):
+    """The kernel gemm_tn would launch, as (NTW, KTW, ring stages, rows per split, splits, partials): tile (32 NTW) x (32 KTW); partials 1 =
+    workspace partial sums + a reduce launch, 0 = the splits add into dW (fp32 atomics when there are several).  ws_floats defaults to
+    the workspace gemm_tn passes."""
+    plan = (ctypes.c_int * 6)()
+    lib().call("nmh_gemm_tn_plan", BF16 if dtype == torch.bfloat16 else F32, N if lda is None else lda, M, N, K, int(bool(rowscale)), rows_per_scale,
+               max(TN_WS_FLOATS, 0) if ws_floats is None else ws_floats, plan)
+    return tuple(plan)
 
 
 _TN_WS = {}

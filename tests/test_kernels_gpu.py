@@ -54,7 +54,7 @@ def test_gemm_nt_plain_bias(dt, M, N, K):
 
 @pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("M,N,K,rps", [(640, 384, 96, 320), (33130, 384, 96, 16565), (32800, 288, 128, 16400), (640, 384, 768, 320), (3200, 288, 512, 1600), (2500, 288, 512, 1250)],
-                         ids=["small", "33k_rows_k96", "33k_rows_k128", "narrow_tiles_32col", "narrow_tiles_48col", "narrow_tiles_32col_ragged"])
+                         ids=["small", "33k_rows_k96", "33k_rows_k128", "narrow_tiles_32col", "w22_233_3200_rows", "w22_233_2500_rows"])
 def test_gemm_nt_epilogues(dt, M, N, K, rps):
     """fused epilogues of nmh_gemm_nt; the two large cases are short contractions on many rows (the 40^3-token Linears) with a ragged last
     row tile"""
