@@ -664,19 +664,23 @@ int k_in_bwd_reduce(int dt, const void* dout, const void* out, const void* x, co
 // blocks.  In the replayed step (same box, three alternating runs each): 8 grids 49.22 ms against 49.66 without (49.45 with short blocks but temporal
 // accesses), 2 grids 16.71 against 16.97, 1 grid 11.06 against 11.18.  tools/probes/hbm_stream_probe.hip: a 2-read + 1-write pass over 3.1-GB tensors runs at 5.3 TB/s from 2048-4096 looping blocks, 6.0-6.25
 // from blocks that touch 16-64 bytes per thread and tensor with non-temporal accesses.  NMH_IN_STREAM=0 disables, NMH_IN_STREAM_VPB sets the voxels per block.
+// (the four NMH_IN_STREAM* variables are read per call: the tests switch them to reach the streaming forms at small shapes)
 static inline bool in_apply_streaming(long V, int B, int C, int dt) {
-  static const int on = getenv("NMH_IN_STREAM") ? atoi(getenv("NMH_IN_STREAM")) : 1;
-  static const double min_bytes = 1.0e6 * (getenv("NMH_IN_STREAM_MIN_MB") ? atof(getenv("NMH_IN_STREAM_MIN_MB")) : 300.0);
+  const char* e_on = getenv("NMH_IN_STREAM");
+  const char* e_mb = getenv("NMH_IN_STREAM_MIN_MB");
+  const int on = e_on ? atoi(e_on) : 1;
+  const double min_bytes = 1.0e6 * (e_mb ? atof(e_mb) : 300.0);
   return on && dt == NMH_DT_BF16 && C <= IN_STREAM_MAX_C && (double)V * B * C * 2 >= min_bytes;
 }
 // voxels per thread of a streaming block (mult x 256 / (C/8) voxels per block).  Measured at 8 x 160^3 x 48 (tools/bench_inbwd.py, tools/bench_tail.py):
 // forward apply 1.23 ms looping -> 1.04 / 1.03 / 1.12 / 1.14 with 2 / 4 / 8 / 16; backward apply 1.78 -> 1.80 / 1.60 / 1.58 / 1.67; tail backward
 // 2.14 -> 2.45 / 2.18 / 2.09 / 2.06 with 4 / 8 / 16 / 32 (its table is 8 arrays and two fp64 divisions per block)
-static inline bool in_stream_nt() { static const int v = getenv("NMH_IN_STREAM_NT") ? atoi(getenv("NMH_IN_STREAM_NT")) : 1; return v != 0; }
+static inline bool in_stream_nt() { const char* e = getenv("NMH_IN_STREAM_NT"); return (e ? atoi(e) : 1) != 0; }
 static inline long in_apply_vpb(long V, int B, int C, bool streaming = false, int mult = 8) {
   const int NV = 256 / (C >> 3);
   if (streaming) {
-    static const int sv = getenv("NMH_IN_STREAM_VPB") ? atoi(getenv("NMH_IN_STREAM_VPB")) : 0;
+    const char* e = getenv("NMH_IN_STREAM_VPB");
+    const int sv = e ? atoi(e) : 0;
     return sv > 0 ? sv : (long)mult * NV;
   }
   long vpb = (V * B + 1023) / 1024;
@@ -840,6 +844,7 @@ __global__ __launch_bounds__(256) void in_bwd_apply_kernel(const T* dout, const 
 int k_in_bwd_apply(int dt, const void* dout, const void* out, const void* x, const float* stats, const double* sums, const void* r, const float* stats_r,
                    const double* sums_r, int rmode, void* dx, void* dr, int dr_accumulate, int B, long V, int C, float slope, hipStream_t st) {
   if (C % 8 || C / 8 > 256 || (!out && rmode != 0)) return -2;
+  if (dr_accumulate && rmode != 1) return -2;   // only dr = g (rmode 1) adds into an existing dr: anything else would drop the flag silently
   const bool nt = in_apply_streaming(V, B, C, dt);
   const long vpb = in_apply_vpb(V, B, C, nt);
   dim3 grid((unsigned)((V + vpb - 1) / vpb), B);
