@@ -668,6 +668,31 @@ NMH_API int nmh_rpn_head_out_bwd(int dt, int nlevels, const int* level_vox, int 
 /* The ReLU between the head's convolutions, in place on a channels-last tensor of n elements (n % 8 == 0): x = max(x, 0); dy = 0 where y <= 0. */
 NMH_API int nmh_relu_(int dt, void* x, int64_t n, void* stream);
 NMH_API int nmh_relu_bwd_(int dt, void* dy, const void* y, int64_t n, void* stream);
+/* ---- RCNN, the box head of the two-stage detector (nerf_rpn/model/detector.py:441-496; kernels, layouts and the order of every sum: csrc/box_head.hip) ----
+ * x: the head's activation, channels-last per RoI in dt, [M][S][C]: M RoIs (1 .. 65535), S = ow oh od cells (1 .. 512), C channels (a multiple of 8, <= 2048).
+ * reg_dim 6 | 7, n_classes >= 1, reg_dim + n_classes <= 32; anything else returns -4.  flatten != 0: the Linear layers read the flattened volume (K = S C);
+ * 0: its mean over the cells (K = C).  relu != 0: x is rectified as it is read (the last conv's ReLU).
+ * nmh_box_head_pack: w_box [reg_dim][C S], w_cls [n_classes][C S] fp32 in nn.Linear's NCDHW flatten order (column c S + s) -> wcat [reg_dim + n_classes][S C] in
+ * dt with column s C + c, box rows first.  The mean form takes wcat in fp32 with S = 1 (dt = 0) whatever the activations' dtype.
+ * nmh_box_head_out_fwd -> pred_bbox_delta [M][reg_dim], pred_scores [M][n_classes] fp32 with the biases added; xmean [M][C] fp32 (mean form only, else NULL)
+ * receives the fp32 mean of relu?(x) over the cells and is an input of the backward.  A row's sums have one order for every M and every row position. */
+NMH_API int nmh_box_head_pack(int dt, int reg_dim, int n_classes, int C, int S, const float* w_box, const float* w_cls, void* wcat, void* stream);
+NMH_API int nmh_box_head_out_fwd(int dt, int M, int S, int C, int reg_dim, int n_classes, int flatten, int relu, const void* x, const void* wcat, const float* b_box, const float* b_cls, float* xmean, float* pred_bbox_delta, float* pred_scores, void* stream);
+/* Its backward.  g_box [M][reg_dim], g_cls [M][n_classes]: fp32 gradients of the two outputs; either may be NULL (read as zeros; that output's dw / db are then
+ * not touched and may be NULL).  -> dx [M][S][C] in dt = relu'(x) o (G wcat) (mean form: / S, through dxmean [M][C] fp32 scratch); dw_box, dw_cls (fp32, nn.Linear's
+ * layout) and db_box, db_cls += the weight and bias gradients, by per-workgroup partials (nmh_box_head_bwd_ws_floats() floats) summed in workgroup order:
+ * bit-identical between runs. */
+NMH_API int64_t nmh_box_head_bwd_ws_floats(int M, int S, int C, int reg_dim, int n_classes, int flatten);
+NMH_API int nmh_box_head_out_bwd(int dt, int M, int S, int C, int reg_dim, int n_classes, int flatten, int relu, const void* x, const void* wcat, const float* xmean, const float* g_box, const float* g_cls, void* dx, float* dxmean, float* partials, float* dw_box, float* dw_cls, float* db_box, float* db_cls, void* stream);
+/* db [C] fp32 += the column sums of dy [rows][C] in dt (the bias gradient of a channels-last conv), per-workgroup partials (nmh_box_head_colsum_ws_floats()
+ * floats) summed in workgroup order.  C a multiple of 8, <= 2048. */
+NMH_API int64_t nmh_box_head_colsum_ws_floats(int64_t rows, int C);
+NMH_API int nmh_box_head_colsum(int dt, const void* dy, int64_t rows, int C, float* partials, float* db, void* stream);
+/* nmh_conv3d_k3_wgrad with a fixed order of additions: the contraction splits leave partial tiles in ws and a second launch adds them in split order.
+ * nmh_conv3d_k3_wgrad_fixed_ws_floats(dt, rows = B D H W, Cin, Cout): the floats ws must hold (0: one split, ws may be NULL), or -2 when so many rows would
+ * need atomics: pass fewer per call (16384 rows always fit).  The call returns -2 in that case and when ws is too small. */
+NMH_API int64_t nmh_conv3d_k3_wgrad_fixed_ws_floats(int dt, int64_t rows, int Cin, int Cout);
+NMH_API int nmh_conv3d_k3_wgrad_fixed(int dt, const void* dY, const void* X, float* dW, float* ws, int64_t ws_floats, int B, int D, int H, int W, int Cin, int Cout, void* stream);
 /* ---- FCOSHead (nerf_rpn/model/fcos/fcos.py:26-139) between its 3x3x3 tower convolutions; kernels, fragment maps and semantics: csrc/fcos_head.hip ----
  * A job is one channels-last tensor (N, W, L, H, C) in dt of one (level, tower); njobs <= 10, C % 32 == 0, C <= 2048, C / G in {1, 2, 4} or a multiple of 8, else -4.
  * vox: HOST int [njobs] = W L H; tower: HOST int [njobs] in {0, 1}; x, y, dy, dx: HOST tables of njobs DEVICE pointers; gamma, beta, dgamma, dbeta: HOST tables of

@@ -880,6 +880,36 @@ int nmh_relu_bwd_(int dt, void* dy, const void* y, int64_t n, void* stream) {
   REQ(dy, y);
   return k_relu_bwd_(dt, dy, y, (long)n, ST);
 }
+int nmh_box_head_pack(int dt, int reg_dim, int n_classes, int C, int S, const float* w_box, const float* w_cls, void* wcat, void* stream) {
+  CLR();
+  return k_box_head_pack(dt, reg_dim, n_classes, C, S, w_box, w_cls, wcat, ST);
+}
+int nmh_box_head_out_fwd(int dt, int M, int S, int C, int reg_dim, int n_classes, int flatten, int relu, const void* x, const void* wcat, const float* b_box, const float* b_cls,
+                         float* xmean, float* pred_bbox_delta, float* pred_scores, void* stream) {
+  CLR();
+  return k_box_head_out_fwd(dt, M, S, C, reg_dim, n_classes, flatten, relu, x, wcat, b_box, b_cls, xmean, pred_bbox_delta, pred_scores, ST);
+}
+int64_t nmh_box_head_bwd_ws_floats(int M, int S, int C, int reg_dim, int n_classes, int flatten) { return k_box_head_bwd_ws_floats(M, S, C, reg_dim, n_classes, flatten); }
+int nmh_box_head_out_bwd(int dt, int M, int S, int C, int reg_dim, int n_classes, int flatten, int relu, const void* x, const void* wcat, const float* xmean, const float* g_box,
+                         const float* g_cls, void* dx, float* dxmean, float* partials, float* dw_box, float* dw_cls, float* db_box, float* db_cls, void* stream) {
+  CLR();
+  if ((g_box && (!dw_box || !db_box)) || (g_cls && (!dw_cls || !db_cls))) return -4;
+  return k_box_head_out_bwd(dt, M, S, C, reg_dim, n_classes, flatten, relu, x, wcat, xmean, g_box, g_cls, dx, dxmean, partials, g_box ? dw_box : nullptr, g_cls ? dw_cls : nullptr,
+                            g_box ? db_box : nullptr, g_cls ? db_cls : nullptr, ST);
+}
+int64_t nmh_box_head_colsum_ws_floats(int64_t rows, int C) { return k_box_head_colsum_ws_floats((long)rows, C); }
+int nmh_box_head_colsum(int dt, const void* dy, int64_t rows, int C, float* partials, float* db, void* stream) {
+  CLR();
+  return k_box_head_colsum(dt, dy, (long)rows, C, partials, db, ST);
+}
+int64_t nmh_conv3d_k3_wgrad_fixed_ws_floats(int dt, int64_t rows, int Cin, int Cout) { return k_conv3_tn_fixed_ws_floats(dt, (long)rows, Cin, Cout); }
+int nmh_conv3d_k3_wgrad_fixed(int dt, const void* dY, const void* X, float* dW, float* ws, int64_t ws_floats, int B, int D, int H, int W, int Cin, int Cout, void* stream) {
+  CLR();
+  REQ(dY, X, dW);
+  if (B < 1 || D < 1 || H < 1 || W < 1 || Cin < 8 || Cin % 8 || Cout < 8 || Cout % 8) return -4;
+  static float dummy_ws;       // a single split needs no workspace, but the fixed-order path is selected by a non-null one
+  return k_conv3_tn(dt, dY, X, dW, B, D, H, W, Cin, Cout, ST, ws ? ws : &dummy_ws, ws ? (long)ws_floats : 0);
+}
 int64_t nmh_fcos_gn_ws_doubles(int njobs, const int* vox, int N, int C) { return vox ? k_fcos_gn_ws_doubles(njobs, vox, N, C) : -1; }
 int nmh_fcos_gn_stats(int dt, int njobs, const int* vox, int N, int C, int G, float eps, const void* const* x, double* ws, float* stats, void* stream) {
   CLR();

@@ -1296,12 +1296,30 @@ int k_gemm_tn(int dt, const void* A, long lda, const void* Bm, long ldb, float* 
   return dispatch_tn<float>(A, lda, Bm, bl, Out, M, N, K, rowscale, rows_per_scale, gm, st);
 }
 
-int k_conv3_tn(int dt, const void* dY, const void* X, float* dW, int B, int D, int H, int W, int Cin, int Cout, hipStream_t st) {
+// the plan of a conv weight gradient over `rows` voxels when a workspace is given: the floats it needs for plain partial tiles (0: a single split, which adds
+// each output element once), or -2 when the plan would fall back to fp32 atomics (more splits than tn_ws_max_splits(): pass fewer rows per call)
+long k_conv3_tn_fixed_ws_floats(int dt, long rows, int Cin, int Cout) {
+  if (rows < 1 || Cin < 8 || Cout < 1) return -2;
+  const TnShape s{dt == NMH_DT_BF16, true, Cout, rows, Cout, 27 * Cin, false, 1, true, 1L << 40};
+  TnPlan p;
+  if (tn_plan(s, &p)) return -2;
+  if (p.splits <= 1) return 0;
+  return p.part ? (long)p.splits * Cout * (27L * Cin + 1) : -2;
+}
+
+// ws (optional): the contraction splits store partial tiles there and a reduce launch adds them in split order (bit-identical between runs); with ws the
+// call refuses (-2) a shape whose plan would add atomically (k_conv3_tn_fixed_ws_floats)
+int k_conv3_tn(int dt, const void* dY, const void* X, float* dW, int B, int D, int H, int W, int Cin, int Cout, hipStream_t st, float* ws, long ws_floats) {
   TnGeom gm{};
   gm.omode = 1; gm.Cin = Cin; gm.D = D; gm.H = H; gm.W = W; gm.V = (unsigned)(D * H * W);
   gm.dC = make_fdiv(Cin); gm.dW = make_fdiv(W); gm.dH = make_fdiv(H); gm.dV = make_fdiv(gm.V);
   BConv3TN bl;
   long M = (long)B * D * H * W;
+  if (ws) {
+    const long need = k_conv3_tn_fixed_ws_floats(dt, M, Cin, Cout);
+    if (need < 0 || need > ws_floats) return -2;
+    gm.ws = ws; gm.ws_floats = ws_floats;
+  }
   if (dt == NMH_DT_BF16) return dispatch_tn<bf16_t>(dY, Cout, X, bl, dW, M, Cout, 27 * Cin, nullptr, 1, gm, st);
   return dispatch_tn<float>(dY, Cout, X, bl, dW, M, Cout, 27 * Cin, nullptr, 1, gm, st);
 }

@@ -128,7 +128,8 @@ int k_in_finalize(int dt, const double* acc, float* stats, int B, long V, int C,
 int k_conv48_wgrad(const void* dY, const void* X, float* dW, float* ws, int B, int D, int H, int W, hipStream_t st, const float* scale_stats = nullptr);
 long k_conv48_wgrad_ws_floats();
 int k_conv3_wgrad_halo(const void* dY, const void* X, float* dW, float* ws, int B, int D, int H, int W, int Cin, int Cout, hipStream_t st);
-int k_conv3_tn(int dt, const void* dY, const void* X, float* dW, int B, int D, int H, int W, int Cin, int Cout, hipStream_t st);
+int k_conv3_tn(int dt, const void* dY, const void* X, float* dW, int B, int D, int H, int W, int Cin, int Cout, hipStream_t st, float* ws = nullptr, long ws_floats = 0);
+long k_conv3_tn_fixed_ws_floats(int dt, long rows, int Cin, int Cout);
 int k_nearest_up_add(int dt, const void* coarse, void* fine, int B, int Dc, int Hc, int Wc, int Df, int Hf, int Wf, int C, int bwd, hipStream_t st);
 int k_vc_transpose(int dt, const void* src, void* dst, int B, long V, int C, int dir, hipStream_t st);
 int k_copy_cols(int dt, const void* src, long lds, void* dst, long ldd, long M, int C, hipStream_t st);
@@ -407,6 +408,16 @@ int k_rpn_head_out_bwd(int dt, int nlevels, const int* vox, int N, int Cin, int 
                        hipStream_t st);
 int k_relu_(int dt, void* x, long n, hipStream_t st);
 int k_relu_bwd_(int dt, void* dy, const void* y, long n, hipStream_t st);
+// ---- box_head.hip (RCNN, the box head of the two-stage detector: both Linear layers from the channels-last activation [M][S][C] to the fp32 outputs, and back) ----
+// Layouts, limits and the order of every sum: box_head.hip.
+int k_box_head_pack(int dt, int reg, int ncls, int C, int S, const float* w_box, const float* w_cls, void* wcat, hipStream_t st);
+int k_box_head_out_fwd(int dt, int M, int S, int C, int reg, int ncls, int flatten, int relu, const void* x, const void* wcat, const float* b_box, const float* b_cls, float* xmean,
+                       float* out_box, float* out_cls, hipStream_t st);
+long k_box_head_bwd_ws_floats(int M, int S, int C, int reg, int ncls, int flatten);
+int k_box_head_out_bwd(int dt, int M, int S, int C, int reg, int ncls, int flatten, int relu, const void* x, const void* wcat, const float* xmean, const float* g_box,
+                       const float* g_cls, void* dx, float* dxmean, float* partials, float* dw_box, float* dw_cls, float* db_box, float* db_cls, hipStream_t st);
+long k_box_head_colsum_ws_floats(long R, int C);
+int k_box_head_colsum(int dt, const void* dy, long R, int C, float* partials, float* db, hipStream_t st);
 // ---- fcos_head.hip (FCOSHead between its tower convolutions: GroupNorm + ReLU forward and backward, the three 3x3x3 output convs with their epilogue, and back) ----
 // vox / tower: HOST [njobs]; dims: HOST [3 nlevels] = W, L, H; every const* const* / * const* argument is a HOST table of DEVICE pointers.  Layouts: fcos_head.hip.
 long k_fcos_gn_ws_doubles(int njobs, const int* vox, int N, int C);

@@ -21,11 +21,11 @@
 // straight from memory (t is read once per 64 output columns: once for A <= 7; the weights and G stay in L1 / L2).
 // A wave owns a 32-voxel tile of one (level, scene); tiles are numbered level-major over all levels, start[k] = first tile of level k.
 #include "levels4.hpp"
+#include "mfma32.hpp"         // MM<T> (the operand fragments of one contraction step), acc_row, acc_zero, Out4<T>
 #include "kernels.hpp"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 constexpr int HEAD_MAX_A = 32;
 constexpr int HEAD_DW_MAX_BLOCKS = 1024;
 constexpr long HEAD_DW_WS_FLOATS = 16L << 20;          // partial sums of the weight-gradient pass: at most 64 MiB
@@ -60,60 +60,6 @@ __device__ __forceinline__ TileAt head_tile(const HeadGeom& g, int wt) {
   const int rem = wt - pick4(g.start, q.k), tl = pick4(g.tiles, q.k);
   q.n = rem / tl; q.v0 = (rem - q.n * tl) * 32; q.V = pick4(g.V, q.k);
   return q;
-}
-__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
-// ---- operand fragments of one contraction step ------------------------------------------------------------------------------------------------
-// Exact: values of the compute dtype.  Wide: fp32 values (the loss gradient); bf16 carries them as hi + lo.
-template <typename T> struct MM;
-template <> struct MM<bf16_t> {
-  static constexpr int E = 8;                           // contraction elements per lane and step
-  struct Exact { bf16x8 v; };
-  struct Wide { bf16x8 hi, lo; };
-  static __device__ __forceinline__ Exact load16(const bf16_t* p) { Exact f; f.v = *reinterpret_cast<const bf16x8*>(p); return f; }
-  static __device__ __forceinline__ Exact zero() { Exact f; f.v = bf16x8{0, 0, 0, 0, 0, 0, 0, 0}; return f; }
-  static __device__ __forceinline__ Wide wzero() { Wide f; f.hi = f.lo = bf16x8{0, 0, 0, 0, 0, 0, 0, 0}; return f; }
-  static __device__ __forceinline__ void relu(Exact& f) { f.v = f.v & ~(f.v < 0); }      // the sign bit set: negative (or -0) -> +0
-  template <int I> static __device__ __forceinline__ void set(Exact& f, bf16_t x, bool relu_on) { f.v[I] = (relu_on && (short)x < 0) ? (short)0 : (short)x; }
-  template <int I> static __device__ __forceinline__ void setw(Wide& f, float x) {
-    const bf16_t hi = f2bf(x);
-    f.hi[I] = (short)hi; f.lo[I] = (short)f2bf(x - bf2f(hi));
-  }
-  static __device__ __forceinline__ void mma(f32x16& acc, const Exact& a, const Exact& b) { acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, b.v, acc, 0, 0, 0); }
-  static __device__ __forceinline__ void mma_wa(f32x16& acc, const Wide& a, const Exact& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi, b.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.lo, b.v, acc, 0, 0, 0);
-  }
-  static __device__ __forceinline__ void mma_wb(f32x16& acc, const Exact& a, const Wide& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, b.hi, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, b.lo, acc, 0, 0, 0);
-  }
-};
-template <> struct MM<float> {
-  static constexpr int E = 4;
-  struct Exact { float v[4]; };
-  typedef Exact Wide;
-  static __device__ __forceinline__ Exact load16(const float* p) { const float4 a = *reinterpret_cast<const float4*>(p); return Exact{{a.x, a.y, a.z, a.w}}; }
-  static __device__ __forceinline__ Exact zero() { return Exact{{0.f, 0.f, 0.f, 0.f}}; }
-  static __device__ __forceinline__ Wide wzero() { return zero(); }
-  static __device__ __forceinline__ void relu(Exact& f) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) f.v[e] = f.v[e] < 0.f ? 0.f : f.v[e];
-  }
-  template <int I> static __device__ __forceinline__ void set(Exact& f, float x, bool relu_on) { f.v[I] = (relu_on && x < 0.f) ? 0.f : x; }
-  template <int I> static __device__ __forceinline__ void setw(Wide& f, float x) { f.v[I] = x; }
-  static __device__ __forceinline__ void mma(f32x16& acc, const Exact& a, const Exact& b) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[e], b.v[e], acc, 0, 0, 0);
-  }
-  static __device__ __forceinline__ void mma_wa(f32x16& acc, const Wide& a, const Exact& b) { mma(acc, a, b); }
-  static __device__ __forceinline__ void mma_wb(f32x16& acc, const Exact& a, const Wide& b) { mma(acc, a, b); }
-};
-__device__ __forceinline__ f32x16 acc_zero() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
 }
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------------------------
@@ -172,27 +118,6 @@ __global__ __launch_bounds__(256) void head_out_fwd_kernel(HeadGeom g, Ptr4<cons
 }
 
 // ---- backward: dt -----------------------------------------------------------------------------------------------------------------------------
-template <typename T> struct Out4;
-template <> struct Out4<bf16_t> {
-  static __device__ __forceinline__ void mask_store(bf16_t* d, const bf16_t* t, bool relu_on, float a, float b, float c, float e) {
-    if (relu_on) {
-      const uint2 m = *reinterpret_cast<const uint2*>(t);                       // > 0: sign clear and not zero
-      const short t0 = (short)(m.x & 0xffff), t1 = (short)(m.x >> 16), t2 = (short)(m.y & 0xffff), t3 = (short)(m.y >> 16);
-      a = t0 > 0 ? a : 0.f; b = t1 > 0 ? b : 0.f; c = t2 > 0 ? c : 0.f; e = t3 > 0 ? e : 0.f;
-    }
-    *reinterpret_cast<uint2*>(d) = make_uint2(pk_bf16(a, b), pk_bf16(c, e));
-  }
-};
-template <> struct Out4<float> {
-  static __device__ __forceinline__ void mask_store(float* d, const float* t, bool relu_on, float a, float b, float c, float e) {
-    if (relu_on) {
-      const float4 m = *reinterpret_cast<const float4*>(t);
-      a = m.x > 0.f ? a : 0.f; b = m.y > 0.f ? b : 0.f; c = m.z > 0.f ? c : 0.f; e = m.w > 0.f ? e : 0.f;
-    }
-    *reinterpret_cast<float4*>(d) = make_float4(a, b, c, e);
-  }
-};
-
 template <typename T>
 __global__ __launch_bounds__(256) void head_out_dt_kernel(HeadGeom g, Ptr4<const T> t, const T* __restrict__ wc, const T* __restrict__ wb, Ptr4<const float> gobj,
                                                           Ptr4<const float> greg, Ptr4<T> dt) {

@@ -5,7 +5,10 @@ is one line):
   LevelMapper                               model/level_mapper.py:21-77 (with _setup_scales)
   ROIPool                                   detector.py:170-438: normal_forward and rotated_forward with feature_extracting_type "pooling" or (oriented
                                             boxes) "interpolation", remap
-  RCNN                                      detector.py:441-496, a torch module with the reference's state_dict keys (two small convs and two Linear layers: no hot path)
+  RCNN                                      detector.py:441-496, a torch module with the reference's state_dict keys (two small convs and two Linear layers), on
+                                            stock nn.Conv3d / nn.Linear: the default
+  FusedRCNN                                 the same head, parameters and state_dict on the channels-last 3x3x3 conv layer and the output kernels of
+                                            csrc/box_head.hip (compute_dtype is an addition); chosen by constructing it
   roi_head_loss / roi_decode / RotatedCoder  detector.py:536-559 with coder/rotated_coder.py and coder/AABB_coder.py
   Classification_Model                      detector.py:499-627
 
@@ -54,8 +57,9 @@ from torch import nn
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import ops
+from . import conv_layer, ops
 from .fcos_loss import _boxes, _check
+from .model import _gradbuf
 from .rpn import MAX_LEVELS, MAX_SCENES
 
 MAX_ROWS, MAX_CELLS, MAX_CLASSES, MAX_GRID = ops.ROI_MAX_ROWS, ops.ROI_MAX_CELLS, ops.ROI_MAX_CLASSES, ops.ROI_MAX_GRID
@@ -331,6 +335,117 @@ class RCNN(nn.Module):
         return self.RCNN_bbox_pred(x), self.RCNN_cls_score(x)
 
 
+class _FusedRCNNFn(Function):
+    """(anchor, head, pooled fp32 (M, C, ow, oh, od)) -> (pred_bbox_delta [M, 6|7], pred_scores [M, n_classes]) fp32: the layout pass to channels-last per RoI,
+    the two 3x3x3 convs with the RoI as the batch index (is_add_layer), then the output kernel.  The parameters are not autograd inputs: the kernels add their
+    gradients into .grad (as in rpn._RPNHeadFn), every one of them in a fixed order.  anchor is the head's one-element leaf that requires a gradient (as
+    model._EmbedFn's): with it the outputs carry a graph, and the backward runs, also when the pooled tensor needs no gradient (a head trained on stored
+    features); it receives none.  Saved: the input of every conv (rectified in place) and the last conv's output before its ReLU, which the output kernel applies
+    as it reads."""
+
+    @staticmethod
+    def forward(ctx, anchor, head, pooled):
+        M, C = pooled.shape[:2]
+        xs = [ops.ncdhw_to_ndhwc(pooled, head.compute_dtype)]
+        if head.layer is not None:
+            for k in range(2):
+                y = conv_layer.forward(head._pk, f"c{k}", head.layer[2 * k], xs[-1])
+                if k == 0:                      # the last conv's ReLU is fused into the output kernel's load
+                    ops.relu_(y)
+                xs.append(y)
+        box, cls, xmean = ops.box_head_out_fwd(xs[-1].view(M, -1, C), head._wcat, head.RCNN_bbox_pred.bias, head.RCNN_cls_score.bias, head.is_flatten, head.layer is not None)
+        ctx.set_materialize_grads(False)
+        ctx.head, ctx.saved = head, (xs, xmean)
+        return box, cls
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_box, g_cls):
+        head, (xs, xmean) = ctx.head, ctx.saved
+        if g_box is None and g_cls is None:
+            return None, None, None
+        need_dx = ctx.needs_input_grad[2]
+        M, C = xs[-1].shape[0], xs[-1].shape[-1]
+        box, cls = head.RCNN_bbox_pred, head.RCNN_cls_score
+        grads = [None if g is None else g.contiguous() for g in (g_box, g_cls)]
+        bufs = [(None, None) if g is None else (_gradbuf(lin.weight), _gradbuf(lin.bias)) for g, lin in zip(grads, (box, cls))]
+        dy = ops.box_head_out_bwd(xs[-1].view(M, -1, C), head._wcat, xmean, grads[0], grads[1], head.reg_dim, head.n_classes, head.is_flatten, head.layer is not None,
+                                  bufs[0][0], bufs[1][0], bufs[0][1], bufs[1][1]).view(xs[-1].shape)
+        keep = []   # tensors the forked side stream still reads -- referenced until the join
+        if head.layer is not None:
+            for k in (1, 0):
+                conv = head.layer[2 * k]
+                if k == 0:
+                    ops.relu_bwd_(dy, xs[1])
+                keep.append(dy)
+                with ops.side_stream():         # conv_layer.backward's two sums add atomically; these add in a fixed order
+                    ops.conv3d_k3_wgrad_fixed(dy, xs[k], _gradbuf(conv.weight))
+                    ops.colsum_fixed(dy, _gradbuf(conv.bias))
+                if k > 0 or need_dx:
+                    dy = ops.conv3d_k3(dy, head._pk[f"c{k}.wd"], C)
+            ops.join_side()
+        del keep
+        return None, None, (ops.ndhwc_to_ncdhw(dy) if need_dx else None)
+
+
+class FusedRCNN(RCNN):
+    """RCNN on the project's kernels: the reference's constructor plus compute_dtype (bfloat16 or float32); the same parameter holders, names, shapes and default
+    initialisation, so a state dict moves between the two classes under strict=True; the holders' own forward is never used.
+    forward(pooling_feature): the fp32 (M, C, ow, oh, od) tensor of ROIPool -> (pred_bbox_delta [M, 6|7], pred_scores [M, n_classes]) fp32, differentiable with
+    respect to pooling_feature; the parameters' gradients are added into .grad by the kernels, every sum in a fixed order (two runs give the same bits).
+    A row's outputs do not depend on how many rows share the call or where the row stands: the output kernel's contraction order is fixed by S and C alone, and the
+    shared conv layer sums an output element's taps and channels in one order whatever the batch (tests/test_box_head_gpu.py holds both to torch.equal).
+    The fp32 masters are repacked into the compute dtype on every call: the convs through conv_layer.ensure_packed, the two Linear weights by csrc/box_head.hip's
+    own pack, which also permutes nn.Linear's NCDHW flatten order (c S + s) to the activations' (s C + c).  The mean-pooled form (is_flatten=False) averages the
+    cells in fp32 and multiplies in fp32 for either compute dtype.
+    Limits: input_dim a multiple of 8 (NotImplementedError) and at most MAX_CHANNELS; reg_dim + n_classes <= MAX_COLS (n_classes up to 25); at most MAX_HEAD_CELLS
+    cells per RoI (7^3 fits); M >= 1 (more than MAX_HEAD_ROWS rows go through the kernels in slices of that many); fp32 device input of the constructor's
+    channel count and, when flattening, its input_size (ValueError / TypeError); parameters on the host raise RuntimeError."""
+
+    MAX_COLS, MAX_HEAD_CELLS, MAX_CHANNELS, MAX_HEAD_ROWS = ops.BOX_HEAD_MAX_COLS, ops.BOX_HEAD_MAX_CELLS, ops.BOX_HEAD_MAX_CHANNELS, ops.BOX_HEAD_MAX_ROWS
+
+    def __init__(self, input_dim, block, n_classes, input_size, is_add_layer=False, is_rotated_bbox=False, is_flatten=True, compute_dtype: torch.dtype = torch.bfloat16):
+        if compute_dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError(f"compute_dtype must be bfloat16 or float32, got {compute_dtype}")
+        size = tuple(int(v) for v in input_size)
+        if len(size) != 3 or min(size) < 1:
+            raise ValueError(f"FusedRCNN: input_size must be three sizes >= 1, got {input_size}")
+        ops.box_head_limits("FusedRCNN", None, size[0] * size[1] * size[2], int(input_dim), 7 if is_rotated_bbox else 6, int(n_classes))
+        super().__init__(input_dim, block, n_classes, input_size, is_add_layer, is_rotated_bbox, is_flatten)
+        self.compute_dtype, self.input_size = compute_dtype, size
+        self._pk = self._pk_key = self._wcat = self._anchor = None
+
+    def _pack(self):
+        if self.layer is not None:
+            conv_layer.ensure_packed(self, list(self.parameters()), "FusedRCNN (HIP) needs its parameters on a HIP device: call .cuda() first (no CPU fallback)",
+                                     lambda P: [conv_layer.register(P, f"c{k}", self.layer[2 * k], self.compute_dtype) for k in range(2)])
+        S = self.flatten_size if self.is_flatten else 1
+        dtype = self.compute_dtype if self.is_flatten else torch.float32
+        w = self.RCNN_bbox_pred.weight
+        if self._wcat is None or self._wcat.device != w.device:
+            self._wcat = torch.empty((self.reg_dim + self.n_classes, S * self.in_planes), dtype=dtype, device=w.device)
+            self._anchor = torch.zeros(1, device=w.device, requires_grad=True)
+        ops.box_head_pack(w.detach(), self.RCNN_cls_score.weight.detach(), self.in_planes, S, dtype, out=self._wcat)
+
+    def forward(self, pooling_feature):
+        x = pooling_feature
+        if not self.RCNN_bbox_pred.weight.is_cuda:
+            raise RuntimeError("FusedRCNN (HIP) needs its parameters on a HIP device: call .cuda() first (no CPU fallback)")
+        _check("FusedRCNN", x)
+        if x.dim() != 5 or x.shape[0] < 1 or x.shape[1] != self.in_planes or (self.is_flatten and tuple(x.shape[2:]) != self.input_size):
+            raise ValueError(f"FusedRCNN: pooling_feature must be (M >= 1, {self.in_planes}, {'ow, oh, od' if not self.is_flatten else ', '.join(map(str, self.input_size))}), "
+                             f"got {tuple(x.shape)}")
+        if x.shape[2] * x.shape[3] * x.shape[4] > self.MAX_HEAD_CELLS:
+            raise ValueError(f"FusedRCNN supports at most {self.MAX_HEAD_CELLS} cells per RoI, got {tuple(x.shape[2:])}")
+        self._pack()
+        x = x.contiguous()
+        M, step = x.shape[0], self.MAX_HEAD_ROWS
+        if M <= step:
+            return _FusedRCNNFn.apply(self._anchor, self, x)
+        parts = [_FusedRCNNFn.apply(self._anchor, self, x[m0:m0 + step]) for m0 in range(0, M, step)]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+
 # ---- losses and decode -----------------------------------------------------------------------------------------------------------------------
 class _RoiHeadLoss(Function):
     @staticmethod
@@ -491,7 +606,10 @@ class Classification_Model(nn.Module):
         This rests on a property of the libraries' kernels that nothing guarantees: within a call of one shape, a row's result depends neither on its position
         nor on the other rows.  It held for the two Linear layers (is_add_layer off, is_flatten on) on the rocBLAS this was written against; the conv layers of
         is_add_layer and the mean-pooled head were not measured.  tests/test_two_stage_gpu.py::test_chunked_prediction_is_bit_identical is
-        the check, and the place to look after a library update.  The price is one head call per 256 rows, about 0.8 ms at 2 x 2000 rows."""
+        the check, and the place to look after a library update.  The price is one head call per 256 rows, about 0.8 ms at 2 x 2000 rows.
+        A FusedRCNN needs none of this: a row's bits do not depend on the other rows of its call by construction, so it takes all rows at once."""
+        if isinstance(self.RCNN_model, FusedRCNN):
+            return self.RCNN_model(pooled)
         M, B = pooled.shape[0], self.HEAD_BLOCK
         deltas, scores = [], []
         for m0 in range(0, M, B):

@@ -2070,6 +2070,125 @@ def relu_bwd_(dy, y):
     return dy
 
 
+# ---- RCNN, the box head of the two-stage detector: its two Linear layers on the channels-last activation (csrc/box_head.hip) ---------------------------
+BOX_HEAD_MAX_COLS = 32         # reg_dim + n_classes
+BOX_HEAD_MAX_CELLS = 512       # ow * oh * od
+BOX_HEAD_MAX_CHANNELS = 2048
+BOX_HEAD_MAX_ROWS = 65535      # RoIs per call
+WGRAD_FIXED_ROWS = 16384       # voxels per nmh_conv3d_k3_wgrad_fixed call: its plan never has more splits than the workspace mode takes
+
+
+def box_head_limits(name, M, S, C, reg, ncls):
+    """raises what the C entries would answer with -4"""
+    if C % 8 or C < 8:
+        raise NotImplementedError(f"{name}: channel counts must be multiples of 8, got {C}")
+    if reg not in (6, 7) or ncls < 1 or reg + ncls > BOX_HEAD_MAX_COLS:
+        raise ValueError(f"{name}: reg_dim 6 or 7 and reg_dim + n_classes <= {BOX_HEAD_MAX_COLS}, got {reg} + {ncls}")
+    if not 1 <= S <= BOX_HEAD_MAX_CELLS:
+        raise ValueError(f"{name} supports 1 to {BOX_HEAD_MAX_CELLS} cells per RoI, got {S}")
+    if C > BOX_HEAD_MAX_CHANNELS:
+        raise ValueError(f"{name} supports at most {BOX_HEAD_MAX_CHANNELS} channels, got {C}")
+    if M is not None and not 1 <= M <= BOX_HEAD_MAX_ROWS:
+        raise ValueError(f"{name} supports 1 to {BOX_HEAD_MAX_ROWS} RoIs per call, got {M}")
+
+
+def box_head_pack(w_box, w_cls, C, S, dtype, out=None):
+    """w_box [reg, C*S], w_cls [ncls, C*S]: nn.Linear's fp32 weights over the NCDHW-flattened volume (column c*S + s) -> wcat [reg + ncls, S*C] in `dtype`,
+    column s*C + c, box rows first: the order of the channels-last activation.  The mean form: S = 1 and dtype float32."""
+    _chk(w_box, w_cls, out)
+    reg, ncls = w_box.shape[0], w_cls.shape[0]
+    box_head_limits("box_head_pack", None, S, C, reg, ncls)
+    if w_box.dtype != torch.float32 or w_cls.dtype != torch.float32 or w_box.numel() != reg * C * S or w_cls.numel() != ncls * C * S:
+        raise ValueError(f"box_head_pack: fp32 weights [reg, {C * S}] and [n_classes, {C * S}]; got {tuple(w_box.shape)}, {tuple(w_cls.shape)}")
+    if out is None:
+        out = torch.empty((reg + ncls, S * C), dtype=dtype, device=w_box.device)
+    elif out.dtype != dtype or out.numel() != (reg + ncls) * S * C:
+        raise ValueError("box_head_pack: out must hold (reg + n_classes) * S * C elements of dtype")
+    lib().call("nmh_box_head_pack", dt_of(out), reg, ncls, C, S, w_box, w_cls, out, _st())
+    return out
+
+
+def _box_head_args(name, x, wcat, reg, ncls, flatten):
+    _chk(x, wcat)
+    if x.dim() != 3:
+        raise ValueError(f"{name}: x must be [M, S, C] channels-last per RoI, got {tuple(x.shape)}")
+    M, S, C = x.shape
+    box_head_limits(name, M, S, C, reg, ncls)
+    want = x.dtype if flatten else torch.float32
+    if wcat.dtype != want or wcat.numel() != (reg + ncls) * (S * C if flatten else C):
+        raise ValueError(f"{name}: wcat must be box_head_pack's [{reg + ncls}, {S * C if flatten else C}] in {want}")
+    return M, S, C
+
+
+def box_head_out_fwd(x, wcat, b_box, b_cls, flatten, relu):
+    """x [M, S, C] in the compute dtype; wcat: box_head_pack's matrix; b_box [reg], b_cls [ncls] fp32; relu: rectify x as it is read ->
+    (pred_bbox_delta [M, reg], pred_scores [M, ncls]) fp32 and, in the mean form, the fp32 mean [M, C] the backward takes (else None)"""
+    reg, ncls = b_box.numel(), b_cls.numel()
+    M, S, C = _box_head_args("box_head_out_fwd", x, wcat, reg, ncls, flatten)
+    _chk(b_box, b_cls)
+    out_box = torch.empty((M, reg), dtype=torch.float32, device=x.device)
+    out_cls = torch.empty((M, ncls), dtype=torch.float32, device=x.device)
+    xmean = None if flatten else torch.empty((M, C), dtype=torch.float32, device=x.device)
+    lib().call("nmh_box_head_out_fwd", dt_of(x), M, S, C, reg, ncls, int(bool(flatten)), int(bool(relu)), x, wcat, b_box, b_cls, xmean, out_box, out_cls, _st())
+    return out_box, out_cls, xmean
+
+
+def box_head_out_bwd(x, wcat, xmean, g_box, g_cls, reg, ncls, flatten, relu, dw_box, dw_cls, db_box, db_cls):
+    """g_box [M, reg], g_cls [M, ncls]: the fp32 gradients of the two outputs, either may be None (zeros; its dw / db are then not touched and may be None) ->
+    dx [M, S, C] in x's dtype; dw_box, dw_cls (nn.Linear's layout), db_box, db_cls (fp32) += the weight and bias gradients in a fixed order"""
+    M, S, C = _box_head_args("box_head_out_bwd", x, wcat, reg, ncls, flatten)
+    for g, n, dw, db in ((g_box, reg, dw_box, db_box), (g_cls, ncls, dw_cls, db_cls)):
+        if g is None:
+            continue
+        _chk(g, dw, db)
+        if g.dtype != torch.float32 or tuple(g.shape) != (M, n):
+            raise ValueError(f"box_head_out_bwd: gradients [M, {reg}] and [M, {ncls}] fp32, got {tuple(g.shape)} {g.dtype}")
+        if dw is None or db is None or dw.dtype != torch.float32 or db.dtype != torch.float32 or dw.numel() != n * (S * C if flatten else C) or db.numel() != n:
+            raise ValueError("box_head_out_bwd: fp32 gradient buffers of the shapes of the weights and biases")
+    if not flatten and (xmean is None or xmean.dtype != torch.float32 or tuple(xmean.shape) != (M, C)):
+        raise ValueError("box_head_out_bwd: the mean form takes box_head_out_fwd's xmean [M, C]")
+    dx = torch.empty_like(x)
+    dxmean = None if flatten else torch.empty((M, C), dtype=torch.float32, device=x.device)
+    ws = torch.empty((lib().cdll.nmh_box_head_bwd_ws_floats(M, S, C, reg, ncls, int(bool(flatten))),), dtype=torch.float32, device=x.device)
+    lib().call("nmh_box_head_out_bwd", dt_of(x), M, S, C, reg, ncls, int(bool(flatten)), int(bool(relu)), x, wcat, xmean, g_box, g_cls, dx, dxmean, ws,
+               dw_box if g_box is not None else None, dw_cls if g_cls is not None else None, db_box if g_box is not None else None, db_cls if g_cls is not None else None, _st())
+    return dx
+
+
+def colsum_fixed(dy, db):
+    """db [C] fp32 += the column sums of the channels-last dy (.., C), per-workgroup partials added in workgroup order: a conv's bias gradient whose bits do
+    not change between runs (bias_grad adds atomically)"""
+    _chk(dy, db)
+    C = dy.shape[-1]
+    R = dy.numel() // C
+    if C % 8 or C > BOX_HEAD_MAX_CHANNELS or db.dtype != torch.float32 or db.numel() != C:
+        raise ValueError(f"colsum_fixed: C a multiple of 8, at most {BOX_HEAD_MAX_CHANNELS}, and an fp32 db [C]")
+    ws = torch.empty((lib().cdll.nmh_box_head_colsum_ws_floats(R, C),), dtype=torch.float32, device=dy.device)
+    lib().call("nmh_box_head_colsum", dt_of(dy), dy, R, C, ws, db, _st())
+    return db
+
+
+def conv3d_k3_wgrad_fixed(dY, X, dW):
+    """dW[Cout][Cin][3][3][3] += the weight gradient of the generic kernel with a fixed order of additions: the contraction splits leave partial tiles in a
+    workspace and a second launch adds them in split order (conv3d_k3_wgrad adds them atomically).  Batches of more than WGRAD_FIXED_ROWS voxels go in slices of
+    the batch index, one call after the other on the stream: still one order."""
+    _chk(dY, X, dW)
+    B, D, H, W, Cin = X.shape
+    Cout = dY.shape[-1]
+    V = D * H * W
+    if V > WGRAD_FIXED_ROWS:
+        raise ValueError(f"conv3d_k3_wgrad_fixed takes volumes of at most {WGRAD_FIXED_ROWS} voxels, got {V}")
+    step = max(1, WGRAD_FIXED_ROWS // V)
+    for b0 in range(0, B, step):
+        n = min(step, B - b0)
+        need = lib().cdll.nmh_conv3d_k3_wgrad_fixed_ws_floats(dt_of(X), n * V, Cin, Cout)
+        if need < 0:
+            raise RuntimeError(f"conv3d_k3_wgrad_fixed: no fixed-order plan for {n * V} voxels, {Cin} -> {Cout} channels")
+        ws = torch.empty((need,), dtype=torch.float32, device=X.device) if need else None
+        lib().call("nmh_conv3d_k3_wgrad_fixed", dt_of(X), dY[b0:b0 + n], X[b0:b0 + n], dW, ws, need, n, D, H, W, Cin, Cout, _st())
+    return dW
+
+
 # ---- RoI stage of the two-stage detector: proposal targets, pyramid RoI pooling, box-head losses, decode (csrc/roi_head.hip) -----------------------
 ROI_MAX_GRID = 1024            # points per axis of one oriented RoI's sampling grid; a larger grid is cut to this
 ROI_MAX_CELLS = 4096           # ow * oh * od
