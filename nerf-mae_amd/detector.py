@@ -756,7 +756,12 @@ class TwoStageDetector(nn.Module):
     keep / keep_counts replace the second stage's sampler (roi_targets_dense).
     Evaluation: detections_dense(meshes) -> (boxes [N,R,6|7], scores [N,R], counts [N] int32), what DetectionEvaluator.update takes, without a host wait;
     forward(meshes) -> (boxes, scores) as per-scene lists, with one host wait.  Boxes are clipped to, and oriented centres tested against, each scene's own
-    size before padding.  state_dict: the parts' keys under rpn_network. and roi_model.RCNN_model."""
+    size before padding.  state_dict: the parts' keys under rpn_network. and roi_model.RCNN_model.
+    first_stage_no_grad = True (an attribute): the backbone runs under torch.no_grad() and its features are handed on detached, so the pooling sends nothing
+    into it and the box head trains on fixed features (the reference's second stage without --fine_tune); without train_rpn the whole first stage then runs
+    without a graph, with train_rpn the first stage's head still trains, on the detached features (trainer.TwoStageTrainer chooses)."""
+
+    first_stage_no_grad = False
 
     def __init__(self, rpn_network, roi_model, score_thresh, nms_thresh, min_size=1e-3, is_reg=True, threshold_mode="any", train_rpn=False):
         super().__init__()
@@ -785,7 +790,11 @@ class TwoStageDetector(nn.Module):
         if key not in self._size_cache:                    # one host-to-device copy per distinct set of sizes
             self._size_cache[key] = torch.tensor(sizes, dtype=torch.int32, device=x.device)
         ori = self._size_cache[key]
-        features = list(net.backbone(x))
+        if self.first_stage_no_grad:
+            with torch.no_grad():
+                features = [f.detach() for f in net.backbone(x)]
+        else:
+            features = list(net.backbone(x))
         losses = {}
         if self.training and self.train_rpn:
             losses = net.rpn(x, features, ori, targets)[2]

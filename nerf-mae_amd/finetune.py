@@ -4,7 +4,7 @@
                    SwinTransformer_MAE3D_New (`base` of the FPN backbone or of a voxel head) first, in base._trainable() order and filling the base's own flat
                    buffers in place, then every other trainable parameter in named_parameters() order, each on an 8-element granule.  It has the attributes
                    FusedAdamW, trainer.flat_layout and the checkpoint functions read (_flat, _flat_grad, _offsets, flatten_parameters, named_parameters,
-                   state_dict), so those work on it unchanged.
+                   state_dict), so those work on it unchanged.  exclude=(sub-modules) leaves a frozen part out of the buffers altogether.
   FinetuneStep     one eager step: check the views, forward, backward, clip + AdamW (three launches; the update clears the gradient buffer).
   fcos_loss_fn, rpn_loss_fn, voxel_loss_fn, loss_fn_for   the loss functions FinetuneStep takes, for the four downstream models.
 
@@ -42,18 +42,25 @@ def _same_device(a: torch.device, b: torch.device) -> bool:
 
 
 class FlatParameters:
-    """FlatParameters(module, device=None): re-homes every trainable parameter of `module` and its .grad as views of one flat fp32 buffer pair.
+    """FlatParameters(module, device=None, exclude=()): re-homes every trainable parameter of `module` and its .grad as views of one flat fp32 buffer pair.
 
     Layout: [base._trainable() on 8-element granules = base._flat | the other trainable parameters in named_parameters() order, 8-element granules]; a parameter
     object registered under two names is placed once.  Frozen parameters (pos_embed) and buffers stay where they are.  The module must already be on the device
     it trains on: `device` only states what the caller expects and is refused when the parameters live elsewhere (moving the parameters alone would leave the
     frozen ones and the buffers behind).  Refused as well: more than one SwinTransformer_MAE3D_New, and one without a trainable parameter.
 
+    exclude: sub-modules of `module` that are left out (a frozen first stage).  Their parameters stay where they are: no view, no gradient
+    view, no offset, so neither the optimizer nor a reducer over this object touches them, and they are not searched for a SwinTransformer_MAE3D_New -- an
+    excluded encoder runs from the flat buffer it makes for itself (model._ensure_ready), as it does without a FlatParameters.  Names stay those of
+    module.named_parameters().  With exclude=() the layout is the one described above.  Refused: an entry that is not a sub-module of `module`, and an
+    exclusion that leaves no trainable parameter.
+
     The modules outside model.py rebuild their packed weights when a parameter's storage moves (conv_layer.ensure_packed keys on data_ptr()), and the base's
     _ensure_ready finds its parameters where its own _offsets say, so nothing re-flattens afterwards.  `check()` verifies exactly that before every step."""
 
-    def __init__(self, module: nn.Module, device=None):
+    def __init__(self, module: nn.Module, device=None, exclude=()):
         self.module = module
+        self.exclude = tuple(exclude)
         self._flat = self._flat_grad = None
         self._offsets: Dict[int, int] = {}
         self._views = []
@@ -63,7 +70,13 @@ class FlatParameters:
     # ---- layout -----------------------------------------------------------------------------------------------------------------------------
     def flatten_parameters(self, device=None):
         module = self.module
-        bases = [m for m in module.modules() if isinstance(m, SwinTransformer_MAE3D_New)]
+        inside = {id(m) for m in module.modules()}
+        for e in self.exclude:
+            if not isinstance(e, nn.Module) or id(e) not in inside:
+                raise ValueError(f"FlatParameters: exclude takes sub-modules of the module; {type(e).__name__} is not one of {type(module).__name__}'s")
+        out_mods = {id(m) for e in self.exclude for m in e.modules()}
+        out_params = {id(p) for e in self.exclude for p in e.parameters()}
+        bases = [m for m in module.modules() if isinstance(m, SwinTransformer_MAE3D_New) and id(m) not in out_mods]
         if len(bases) > 1:
             raise ValueError(f"FlatParameters: the module holds {len(bases)} SwinTransformer_MAE3D_New; one flat buffer can lead with the parameters of one only")
         base = bases[0] if bases else None
@@ -71,14 +84,17 @@ class FlatParameters:
         if base is not None and not lead:
             raise ValueError("FlatParameters: the module's SwinTransformer_MAE3D_New has no trainable parameter (a frozen encoder is not supported: it keeps no "
                              "flat buffer of its own to run from)")
-        seen = {id(p) for p in lead}
+        if any(id(p) in out_params for p in lead):
+            raise ValueError("FlatParameters: exclude the SwinTransformer_MAE3D_New as a whole (or a module around it), not a part of it: its flat buffer is "
+                             "one piece")
+        seen = {id(p) for p in lead} | out_params
         rest = []
         for name, p in module.named_parameters():
             if p.requires_grad and id(p) not in seen:
                 seen.add(id(p))
                 rest.append(p)
         if not lead and not rest:
-            raise ValueError("FlatParameters: the module has no trainable parameter")
+            raise ValueError("FlatParameters: the exclusion leaves no trainable parameter" if self.exclude else "FlatParameters: the module has no trainable parameter")
         everything = list(module.parameters()) + list(module.buffers())
         where = (lead + rest)[0].device
         stray = [t for t in everything if not _same_device(t.device, where)]

@@ -417,12 +417,14 @@ class RPNProposalFilter(object):
 
 # ---- head and network ------------------------------------------------------------------------------------------------------------------------
 class _RPNHeadFn(Function):
-    """(head, *channels-last features) -> (*objectness levels, *regression levels): the 3x3x3 convs with ReLU on channels-last tensors, then the output
+    """(anchor, head, *channels-last features) -> (*objectness levels, *regression levels): the 3x3x3 convs with ReLU on channels-last tensors, then the output
     kernel that writes the fp32 NCDHW planes.  The parameters are not autograd inputs: their gradients are accumulated into .grad by the kernels (as in
-    fpn._FPNFn).  Saved per level: the input of every conv (rectified in place) and the last conv's output before its ReLU."""
+    fpn._FPNFn).  anchor is the head's one-element leaf that requires a gradient (as detector._FusedRCNNFn's): with it the outputs carry a graph, and the
+    backward runs, also when no feature needs a gradient (a head trained on a frozen backbone's detached features); it receives none, and the first conv's
+    input gradient is then not formed.  Saved per level: the input of every conv (rectified in place) and the last conv's output before its ReLU."""
 
     @staticmethod
-    def forward(ctx, head, *feats):
+    def forward(ctx, anchor, head, *feats):
         pk, depth, C = head._pk, head.conv_depth, head.num_delta_digits
         acts = []
         for f in feats:
@@ -452,11 +454,11 @@ class _RPNHeadFn(Function):
                 if k < depth - 1:
                     ops.relu_bwd_(dy, xs[k + 1])
                 keep.append(dy)
-                dy = conv_layer.backward(pk, f"c{k}", head.conv[2 * k], dy, xs[k], need_dx=k > 0 or ctx.needs_input_grad[1 + i])
+                dy = conv_layer.backward(pk, f"c{k}", head.conv[2 * k], dy, xs[k], need_dx=k > 0 or ctx.needs_input_grad[2 + i])
             dfeats.append(dy)
         ops.join_side()
         del keep
-        return (None, *dfeats)
+        return (None, None, *dfeats)
 
 
 class RPNHead(nn.Module):
@@ -488,6 +490,7 @@ class RPNHead(nn.Module):
                 torch.nn.init.constant_(layer.bias, 0)
         self._pk = None
         self._pk_key = None
+        self._anchor = None
 
     def _pack(self):
         def fill(P):
@@ -497,6 +500,9 @@ class RPNHead(nn.Module):
             P.add("box.w", self.bbox_pred.weight, P.CAST)
 
         conv_layer.ensure_packed(self, list(self.parameters()), "RPNHead (HIP) needs its parameters on a HIP device: call .cuda() first (no CPU fallback)", fill)
+        dev = self.cls_logits.weight.device
+        if self._anchor is None or self._anchor.device != dev:
+            self._anchor = torch.zeros(1, device=dev, requires_grad=True)
 
     def forward_channels_last(self, feats):
         """feats: per level a channels-last (N, W, H, D, C) tensor in the compute dtype -> (logits, bbox_reg), lists of fp32 NCDHW tensors"""
@@ -505,7 +511,7 @@ class RPNHead(nn.Module):
             raise ValueError(f"RPNHead supports 1 to {MAX_LEVELS} levels, got {len(feats)}")
         check_channels_last("RPNHead", "W, H, D", feats, self.in_channels, self.compute_dtype)
         self._pack()
-        out = _RPNHeadFn.apply(self, *feats)
+        out = _RPNHeadFn.apply(self._anchor, self, *feats)
         return list(out[:len(feats)]), list(out[len(feats):])
 
     def forward(self, x):
@@ -592,7 +598,12 @@ def _default_anchorgen():
 class NeRFRegionProposalNetwork(nn.Module):
     """model/nerf_rpn.py: backbone + RegionProposalNetwork over a list of (C, W, H, D) grids -> [features, proposals, level_index], losses, scores.
     With rpn_head=None the head is RPNHead(out_channels, A, rotated_bbox) as in the reference, so the flag lands in conv_depth (depth 0 or 1, always 6 regression
-    columns).  check_targets = False skips the degenerate-box check, the one place that waits for the host in training (for graph capture)."""
+    columns).  check_targets = False skips the degenerate-box check, the one place that waits for the host in training (for graph capture).
+    backbone_no_grad = True (an attribute, the constructor is the reference's): the backbone runs under torch.no_grad() and its features are handed on
+    detached, so nothing of it is kept for a backward and the head skips the gradient of its input: a frozen backbone (run_rpn.py --freeze_backbone,
+    trainer.RPNTrainer(freeze_backbone=True))."""
+
+    backbone_no_grad = False
 
     def __init__(self, backbone, rpn_anchor_generator=None, rpn_head=None, rpn_pre_nms_top_n_train=2000, rpn_pre_nms_top_n_test=1000, rpn_post_nms_top_n_train=2000,
                  rpn_post_nms_top_n_test=1000, rpn_nms_thresh=0.7, rpn_fg_iou_thresh=0.7, rpn_bg_iou_thresh=0.3, rpn_batch_size_per_image=256, rpn_positive_fraction=0.5,
@@ -652,12 +663,32 @@ class NeRFRegionProposalNetwork(nn.Module):
         if self.check_targets:
             self.check_bbox_degeneration(targets)
         mesh_tensors = torch.stack(meshes, dim=0)
-        features = list(self.backbone(mesh_tensors))
+        features = self._features(mesh_tensors)
         ori = original_mesh_sizes
         if len(meshes) > 1 and objectness_output_paths is None:      # one host-to-device copy per distinct set of sizes, none afterwards (nothing waits for the host)
-            key = (tuple(tuple(int(v) for v in o) for o in ori), mesh_tensors.device)
-            if key not in self._ori_cache:
-                self._ori_cache[key] = torch.tensor(key[0], dtype=torch.int32, device=mesh_tensors.device)
-            ori = self._ori_cache[key]
+            ori = self._ori_tensor(ori, mesh_tensors.device)
         proposals, level_index, proposal_losses, scores = self.rpn(mesh_tensors, features, ori, targets, objectness_output_paths)
         return [features, proposals, level_index], proposal_losses, scores
+
+    def _features(self, mesh_tensors):
+        if not self.backbone_no_grad:
+            return list(self.backbone(mesh_tensors))
+        with torch.no_grad():
+            return [f.detach() for f in self.backbone(mesh_tensors)]
+
+    def _ori_tensor(self, ori, device):
+        key = (tuple(tuple(int(v) for v in o) for o in ori), device)
+        if key not in self._ori_cache:
+            self._ori_cache[key] = torch.tensor(key[0], dtype=torch.int32, device=device)
+        return self._ori_cache[key]
+
+    def proposals_dense(self, meshes):
+        """the list of (C, W, H, D) grids -> rpn.proposals_dense's fixed-size quintuple (boxes, scores, levels, anchor_index, counts) of the current mode's
+        top-n: padding, backbone and head as in forward, no gradient, no host wait once the sizes' tensor exists (what DetectionEvaluator.update takes in its
+        dense form)"""
+        with torch.no_grad():
+            meshes = list(meshes)
+            ori = [tuple(int(v) for v in m.shape[-3:]) for m in meshes]
+            meshes, _ = self.transform(meshes)
+            x = torch.stack(meshes, dim=0)
+            return self.rpn.proposals_dense(x, list(self.backbone(x)), self._ori_tensor(ori, x.device) if len(meshes) > 1 else None)

@@ -711,6 +711,9 @@ class _FinetuneTrainer:
     (the reference: a barrier and four all-reduces per step, :747-751).  Evaluation and files are rank 0's; the other ranks wait at one barrier per evaluated
     epoch and their `history` carries the training losses only.  With world = 1 nothing of this is active.
 
+    exclude: sub-modules that are frozen as a whole.  They are handed to FlatParameters(exclude=), so the optimizer neither steps nor decays them and a reducer
+    does not exchange them (the initial broadcast still sends them once), and they are put back into eval() after every model.train() of the loop.
+
     A subclass supplies its checkpoint pair (_save_checkpoint, _load_checkpoint) and
       _logged(losses)         the step's detached losses -> the 1-D tensor that the epoch accumulates
       _record(vals)           the epoch's means of _logged, read back as a list -> the training part of the history record
@@ -720,7 +723,7 @@ class _FinetuneTrainer:
 
     def __init__(self, model, train_scenes, train_targets, val_scenes, val_targets, batcher, val_batcher, loss_fn, weights, args: dict, batch_size: int,
                  num_epochs: int, schedule_epochs: int, lr: float, weight_decay: float, clip_grad_norm: float, eval_interval: int, save_path: str, log, seed: int,
-                 rank: int, world: int, reducer):
+                 rank: int, world: int, reducer, exclude=()):
         import random
         from . import dist as _dist
         from .finetune import FinetuneStep, FlatParameters
@@ -729,12 +732,15 @@ class _FinetuneTrainer:
         self.rank, self.world = rank, world
         self.args = _plain(args)
         self.batcher, self.val_batcher = batcher, val_batcher
+        self.exclude = tuple(exclude)                            # the frozen part: outside the flat buffers, kept in eval()
         if reducer is not None:
             if getattr(reducer.model, "module", None) is not model:
                 raise ValueError(f"{type(self).__name__}: the reducer must be a dist.FlatGradReducer over a finetune.FlatParameters of this model")
+            if [id(m) for m in getattr(reducer.model, "exclude", ())] != [id(m) for m in self.exclude]:
+                raise ValueError(f"{type(self).__name__}: the reducer's FlatParameters must leave out exactly what this trainer freezes (exclude=)")
             self.flat = reducer.model
         else:
-            self.flat = FlatParameters(model, next(model.parameters()).device)
+            self.flat = FlatParameters(model, next(model.parameters()).device, exclude=self.exclude)
             if world > 1:
                 reducer = _dist.FlatGradReducer(self.flat)
         self.reducer = reducer
@@ -765,8 +771,15 @@ class _FinetuneTrainer:
         xb, ext, targets = self.batcher.prepare([self._load(self.train_scenes[i]) for i in ids], [self._target(self.train_targets[i]) for i in ids], rng=self._rng)
         return self._meshes(xb, ext), targets
 
-    def train_epoch(self, epoch: int):
+    def _train_mode(self):
+        """model.train(), the frozen part back in eval(): its features are deterministic (the reference leaves a frozen backbone in train mode, with stochastic
+        depth drawing; a stated deviation)"""
         self.model.train()
+        for m in self.exclude:
+            m.eval()
+
+    def train_epoch(self, epoch: int):
+        self._train_mode()
         acc = None
         for ids in dp_epoch_plan(len(self.train_scenes), self.batch, self.rank, self.world, epoch, self.seed):     # the DataLoader's shuffle, this rank's shard
             meshes, targets = self._batch(ids)
@@ -899,6 +912,295 @@ class DetectionTrainer(_FinetuneTrainer):
             self.best_metric_ap25 = ap25
             self._save(f"model_best_ap25_ap50_{ap50}_{ap25}.pt", epoch)
         delete_suboptimal_checkpoints(self.save_path, "ap50", 6, 1)
+
+
+# --------------------------------------------------------------------------------------------------
+# The RPN and the two-stage detector: the epoch loops of run_rpn.py and run_rpn_detect.py
+# --------------------------------------------------------------------------------------------------
+def save_rpn_checkpoint(path: str, model, epoch: int, train_args: dict, opt: "FusedAdamW" = None, step: int = None):
+    """the reference's RPN checkpoint (run_rpn.py:294-300): {"epoch", "backbone_state_dict", "rpn_head_state_dict" (= model.rpn.head.state_dict()), "train_args"}
+    of a NeRFRegionProposalNetwork, keys and shapes the reference's.  The backbone is written whether it trained or not, as the reference does.  With `opt` (a
+    FusedAdamW over a finetune.FlatParameters of this model) the file also carries the "resume" section of save_checkpoint."""
+    model = _unwrapped(model)
+    _write_checkpoint(path, {"backbone_state_dict": model.backbone.state_dict(), "rpn_head_state_dict": model.rpn.head.state_dict()}, epoch,
+                      _plain(dict(train_args)), opt, step)
+
+
+def load_rpn_checkpoint(path: str, model, opt: "FusedAdamW" = None, backbone_only: bool = False) -> dict:
+    """loads an RPN checkpoint (also one written by the reference) strictly into model.backbone and model.rpn.head; returns the checkpoint dict.
+    backbone_only: the backbone alone, the reference's --load_backbone_only (run_rpn.py:189-191); the optimizer is then left as it is.  Otherwise, with `opt`
+    and a "resume" section, the optimizer continues where it stopped."""
+    model = _unwrapped(model)
+    parts = [("backbone_state_dict", model.backbone, True)] + ([] if backbone_only else [("rpn_head_state_dict", model.rpn.head, True)])
+    return _read_checkpoint(path, parts, None if backbone_only else opt, "load_rpn_checkpoint")
+
+
+def keep_latest_checkpoints(checkpoint_dir: str, keep_latest: int = 5):
+    """delete_old_checkpoints of run_rpn.py:302-308 and run_rpn_detect.py:271-277: of the directory's epoch_*.pt the `keep_latest` newest by modification time
+    stay (equal times: the higher epoch is the newer), the others are removed; the model_best* files are not touched.  keep_latest < 1 raises ValueError (the
+    reference's slice keeps everything there)."""
+    import glob
+    import os
+    import re
+    if int(keep_latest) < 1:
+        raise ValueError(f"keep_latest_checkpoints: keep_latest >= 1, got {keep_latest}")
+
+    def age(f):
+        m = re.search(r"epoch_(\d+)\.pt$", f)
+        return os.path.getmtime(f), int(m.group(1)) if m else -1
+
+    files = sorted(glob.glob(os.path.join(checkpoint_dir, "epoch_*.pt")), key=age)
+    for f in files[:max(len(files) - int(keep_latest), 0)]:
+        os.remove(f)
+
+
+def proposal_limits(top_n: int):
+    """the proposal limits of the reference's evaluations: those of [300, 1000, top_n] that do not exceed top_n (run_rpn.py:533-535)"""
+    return [l for l in (300, 1000, int(top_n)) if l <= int(top_n)]
+
+
+def _loss_record(keys, vals, weights: dict) -> dict:
+    """the epoch means of the unweighted losses -> {"train_loss": sum(weights.get(k, 1) * v), then every loss under its key}: FinetuneStep's total"""
+    rec = {"train_loss": sum(float(weights.get(k, 1.0)) * v for k, v in zip(keys, vals))}
+    rec.update(zip(keys, vals))
+    return rec
+
+
+def _backbone_resolution(backbone):
+    for owner in (backbone, getattr(backbone, "base", None)):
+        r = getattr(owner, "resolution", None)
+        if isinstance(r, int):
+            return r
+    return None
+
+
+def _dense_targets(gt, device):
+    """per-scene box tensors -> (gt_boxes [N, Gmax, 6|7] zero-padded, gt_counts [N] int32), what DetectionEvaluator.update takes in its dense form; no host wait"""
+    import torch.nn.functional as F
+    gmax = max(max(int(g.shape[0]) for g in gt), 1)
+    dense = torch.stack([F.pad(g.to(device=device, dtype=torch.float32), (0, 0, 0, gmax - int(g.shape[0]))) for g in gt])
+    return dense, torch.tensor([int(g.shape[0]) for g in gt], dtype=torch.int32).to(device, non_blocking=True)
+
+
+class _BoxTrainer(_FinetuneTrainer):
+    """What RPNTrainer and TwoStageTrainer share: the argument checks, the two DetectionBatchers, the loss bookkeeping by key, the validation loop in the
+    evaluator's dense form and the reference's keep-the-newest policy."""
+
+    def _setup(self, model, backbone, train_scenes, train_boxes, val_scenes, val_boxes, resolution, loss_fn, weights, keys, common: dict, exclude):
+        from . import data
+        who = type(self).__name__
+        if len(train_scenes) != len(train_boxes) or (val_scenes is not None and len(val_scenes) != len(val_boxes or [])):
+            raise ValueError(f"{who}: one box array per scene")
+        if len(train_scenes) < 1:
+            raise ValueError(f"{who}: no training scene")
+        if resolution is None:
+            resolution = _backbone_resolution(backbone)
+        if resolution is None:
+            raise ValueError(f"{who}: the backbone exposes no resolution; pass resolution=R (the batcher pads every scene to it)")
+        if int(common["keep_checkpoints"]) < 1:
+            raise ValueError(f"{who}: keep_checkpoints >= 1")
+        self.train_boxes, self.val_boxes, self.weights, self.keys = train_boxes, val_boxes, dict(weights), tuple(keys)
+        self.keep_checkpoints, self.top_k = int(common["keep_checkpoints"]), common["top_k"]
+        c = common
+        dev = next(model.parameters()).device
+        _FinetuneTrainer.__init__(self, model, train_scenes, train_boxes, val_scenes, val_boxes,
+                                  data.DetectionBatcher(resolution, dev, c["normalize_density"], c["flip_prob"], c["rotate_prob"], c["rot_scale_prob"]),
+                                  data.DetectionBatcher(resolution, dev, c["normalize_density"]), loss_fn, weights, c["args"], c["batch_size"], c["num_epochs"],
+                                  c["schedule_epochs"] or c["num_epochs"], c["lr"], c["weight_decay"], c["clip_grad_norm"], c["eval_interval"], c["save_path"],
+                                  c["log"], c["seed"], c["rank"], c["world"], c["reducer"], exclude=exclude)
+
+    def _logged(self, losses):
+        return torch.stack([losses[k] for k in self.keys])
+
+    def _record(self, vals):
+        return _loss_record(self.keys, vals, self.weights)
+
+    def _val_batches(self):
+        """the validation scenes in order, `batch` at a time, without augmentation -> (meshes, gt_boxes [N, Gmax, 6|7], gt_counts [N])"""
+        for b in range(0, len(self.val_scenes), self.batch):
+            scenes = [self._load(s) for s in self.val_scenes[b:b + self.batch]]
+            xb, ext, gt = self.val_batcher.prepare(scenes, list(self.val_boxes[b:b + self.batch]), params=[(0, 0.0, 1.0)] * len(scenes))
+            yield (self._meshes(xb, ext), *_dense_targets(gt, xb.device))
+
+    def resume(self, path: str) -> dict:
+        """_FinetuneTrainer.resume, and the samplers' counters: each draws once per step (rpn_sample, roi_targets: "the counter advances by one"), so the
+        run continues with the draws an uninterrupted one would make when the counters are set to the file's step"""
+        ck = super().resume(path)
+        for s in self._samplers():
+            s.rng_state = torch.tensor([s.seed, self.global_step], dtype=torch.int64, device=self.flat._flat.device)
+        return ck
+
+    def _newest(self, epoch: int):
+        self._save(f"epoch_{epoch}.pt", epoch)
+        keep_latest_checkpoints(self.save_path, self.keep_checkpoints)
+
+
+class RPNTrainer(_BoxTrainer):
+    """Epoch loop of run_rpn.py:310-431, 455-591 for NeRFRegionProposalNetwork (the conventions of _FinetuneTrainer): input from data.DetectionBatcher
+    (`resolution` from the backbone where it exposes one), loss = loss_objectness + reg_loss_weight * loss_rpn_box_reg + reg_loss_weight_2d *
+    loss_rpn_box_reg_2d (:385-387), OneCycle over (schedule_epochs or num_epochs) * steps_per_epoch steps (the reference sizes it by num_epochs, :348-349).
+
+    `train_loss` of the history is the weighted total, the three losses under their own keys are unweighted.  Evaluation: model.eval(), rpn.proposals_dense
+    per validation batch into DetectionEvaluator's dense form (no host wait per batch), the limits of [300, 1000, rpn_post_nms_top_n_test] not above the last
+    (:533-535), AP at 0.25 and 0.5 over each scene's `top_k` best; record keys as DetectionTrainer's.  `model_best.pt` when recall at 0.5 under the largest limit
+    improves (:363-367), `epoch_{n}.pt` at every evaluated epoch, of which the `keep_checkpoints` newest stay.
+
+    freeze_backbone (run_rpn.py:193-195): the backbone is left out of the flat buffers (FlatParameters(exclude=)) and runs without a graph
+    (model.backbone_no_grad), in eval(): only model.rpn is stepped and weight-decayed.  The checkpoint carries the backbone regardless (:294-300).
+
+    train_boxes / val_boxes: one [G, 6|7] array per scene."""
+
+    _save_checkpoint, _load_checkpoint = staticmethod(save_rpn_checkpoint), staticmethod(load_rpn_checkpoint)
+    KEYS = ("loss_objectness", "loss_rpn_box_reg", "loss_rpn_box_reg_2d")
+
+    def __init__(self, model, train_scenes, train_boxes, val_scenes=None, val_boxes=None, resolution: int = None, batch_size: int = 1, num_epochs: int = 100,
+                 lr: float = 1e-4, weight_decay: float = 0.01, clip_grad_norm: float = 0.1, reg_loss_weight: float = 5.0, reg_loss_weight_2d: float = 0.0,
+                 eval_interval: int = 1, keep_checkpoints: int = 1, top_k: int = None, freeze_backbone: bool = False, normalize_density: bool = True,
+                 flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = None, save_path: str = None, log=print,
+                 train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None):
+        from .finetune import rpn_loss_fn
+        self.freeze_backbone = bool(freeze_backbone)
+        args = dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, reg_loss_weight=reg_loss_weight,
+                    reg_loss_weight_2d=reg_loss_weight_2d, batch_size=batch_size * world, num_epochs=num_epochs, keep_checkpoints=keep_checkpoints, top_k=top_k,
+                    freeze_backbone=self.freeze_backbone, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
+                    rot_scale_prob=rot_scale_prob)
+        self._setup(model, model.backbone, train_scenes, train_boxes, val_scenes, val_boxes, resolution, rpn_loss_fn(model),
+                    {"loss_rpn_box_reg": reg_loss_weight, "loss_rpn_box_reg_2d": reg_loss_weight_2d}, self.KEYS,
+                    dict(args=args, batch_size=batch_size, num_epochs=num_epochs, schedule_epochs=schedule_epochs, lr=lr, weight_decay=weight_decay,
+                         clip_grad_norm=clip_grad_norm, eval_interval=eval_interval, keep_checkpoints=keep_checkpoints, top_k=top_k, save_path=save_path, log=log,
+                         seed=seed, rank=rank, world=world, reducer=reducer, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
+                         rot_scale_prob=rot_scale_prob),
+                    (model.backbone,) if self.freeze_backbone else ())
+        if self.freeze_backbone:
+            model.backbone_no_grad = True
+        self.limits = proposal_limits(model.rpn._post_nms_top_n["testing"])
+        self.best_metric = None
+
+    @torch.no_grad()
+    def evaluate(self):
+        from .det_eval import DetectionEvaluator
+        self.model.eval()
+        ev = DetectionEvaluator(limits=self.limits, ap_thresholds=(0.25, 0.5), top_k=self.top_k)
+        try:
+            for meshes, gt, gt_counts in self._val_batches():
+                boxes, scores, _, _, counts = self.model.proposals_dense(meshes)
+                ev.update(boxes, scores, counts, gt, gt_counts)
+        finally:
+            self._train_mode()
+        out = ev.compute()                                            # the evaluation's one synchronisation
+        rec = {}
+        for l in self.limits:
+            for key in ("25", "50", "ar"):
+                rec[f"recall_{key}_top_{l}"] = float(out[f"recall_{key}_top_{l}"]["ar"])
+        rec["ap_25"], rec["ap_50"] = float(out["ap_25"]["ap"]), float(out["ap_50"]["ap"])
+        return rec
+
+    def _samplers(self):
+        return [self.model.rpn.loss]
+
+    def _keep_best(self, epoch: int, rec: dict):
+        metric = rec[f"recall_50_top_{self.limits[-1]}"]
+        if self.best_metric is None or metric > self.best_metric:
+            self.best_metric = metric
+            self._save("model_best.pt", epoch)
+        self._newest(epoch)
+
+
+class TwoStageTrainer(_BoxTrainer):
+    """Epoch loop of run_rpn_detect.py:279-390, 441-551 for detector.TwoStageDetector (the conventions of _FinetuneTrainer), the two stages joined: the
+    proposals come from the detector's own first stage, not from stored files.  loss = loss_objectness + reg_loss_weight * loss_rpn_box_reg of the box head
+    (obj_only: the regression term gets weight 0, :359-363), and with model.train_rpn the first stage's losses under their "rpn_" keys, weighted as run_rpn.py
+    weights them (rpn_reg_loss_weight, rpn_reg_loss_weight_2d).  OneCycle over (schedule_epochs or num_epochs) * steps_per_epoch steps.
+
+    The mode follows from model.train_rpn and freeze_first_stage (None: not model.train_rpn), see resolve_mode:
+      head       train_rpn off, frozen: the reference's default without --fine_tune.  The first stage is left out of the flat buffers and runs without a graph
+                 (model.first_stage_no_grad), in eval(); only roi_model is stepped; the checkpoint's "backbone_state_dict" is None.
+      joint      train_rpn on: everything trains, the five losses are logged.
+      fine_tune  train_rpn off, not frozen: the pooling's gradient trains the backbone under a first-stage head that stays as it is (the detector's behaviour
+                 without a trainer; its proposals follow the moving features with nothing holding them, so choose it knowingly).
+      heads      train_rpn on, frozen: the backbone alone is frozen; both heads train on its detached features.
+
+    Evaluation: detections_dense per validation batch into DetectionEvaluator(ap_thresholds=(0.25, 0.5), top_k) -> ap_25, ap_50.  `model_best_ap25.pt` /
+    `model_best_ap50.pt` whenever that AP improves, `epoch_{n}.pt` at every evaluated epoch, of which the `keep_checkpoints` newest stay (:327-340).  Stated
+    deviations: the first evaluation writes both best files (the reference's only initialises its best values); epochs count from 1, as in the other trainers.
+    init_from_rpn(path) loads an RPNTrainer's (or the reference's run_rpn.py) checkpoint into the first stage: the hand-over the reference does on disk."""
+
+    _load_checkpoint = staticmethod(load_two_stage_checkpoint)
+
+    @staticmethod
+    def resolve_mode(train_rpn: bool, freeze_first_stage=None):
+        """-> (mode, frozen): mode in "head" | "joint" | "fine_tune" | "heads"; frozen: "first_stage", "backbone" or None"""
+        train_rpn = bool(train_rpn)
+        freeze = (not train_rpn) if freeze_first_stage is None else bool(freeze_first_stage)
+        if train_rpn:
+            return ("heads", "backbone") if freeze else ("joint", None)
+        return ("head", "first_stage") if freeze else ("fine_tune", None)
+
+    def __init__(self, model, train_scenes, train_boxes, val_scenes=None, val_boxes=None, resolution: int = None, batch_size: int = 2, num_epochs: int = 100,
+                 lr: float = 1e-4, weight_decay: float = 5e-4, clip_grad_norm: float = 0.1, reg_loss_weight: float = 5.0, rpn_reg_loss_weight: float = 5.0,
+                 rpn_reg_loss_weight_2d: float = 0.0, obj_only: bool = False, freeze_first_stage: bool = None, eval_interval: int = 1, keep_checkpoints: int = 1,
+                 top_k: int = None, normalize_density: bool = True, flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0,
+                 schedule_epochs: int = None, save_path: str = None, log=print, train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None):
+        from .finetune import roi_loss_fn
+        if obj_only and model.is_reg:
+            raise ValueError("TwoStageTrainer: obj_only trains no box regression, but the detector decodes with it (is_reg=True): build TwoStageDetector(..., "
+                             "is_reg=False), whose detections are the proposals themselves")
+        self.mode, frozen = self.resolve_mode(model.train_rpn, freeze_first_stage)
+        self.frozen = frozen
+        self.obj_only = bool(obj_only)
+        exclude = {"first_stage": (model.rpn_network,), "backbone": (model.rpn_network.backbone,), None: ()}[frozen]
+        weights = {"loss_rpn_box_reg": 0.0 if obj_only else reg_loss_weight}
+        keys = ("loss_objectness", "loss_rpn_box_reg")
+        if model.train_rpn:
+            weights.update({"rpn_loss_rpn_box_reg": rpn_reg_loss_weight, "rpn_loss_rpn_box_reg_2d": rpn_reg_loss_weight_2d})
+            keys += ("rpn_loss_objectness", "rpn_loss_rpn_box_reg", "rpn_loss_rpn_box_reg_2d")
+        args = dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, reg_loss_weight=reg_loss_weight,
+                    rpn_reg_loss_weight=rpn_reg_loss_weight, rpn_reg_loss_weight_2d=rpn_reg_loss_weight_2d, obj_only=self.obj_only, mode=self.mode,
+                    fine_tune=self.mode != "head", batch_size=batch_size * world, num_epochs=num_epochs, keep_checkpoints=keep_checkpoints, top_k=top_k,
+                    normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob, rot_scale_prob=rot_scale_prob)
+        self._setup(model, model.rpn_network.backbone, train_scenes, train_boxes, val_scenes, val_boxes, resolution, roi_loss_fn(model), weights, keys,
+                    dict(args=args, batch_size=batch_size, num_epochs=num_epochs, schedule_epochs=schedule_epochs, lr=lr, weight_decay=weight_decay,
+                         clip_grad_norm=clip_grad_norm, eval_interval=eval_interval, keep_checkpoints=keep_checkpoints, top_k=top_k, save_path=save_path, log=log,
+                         seed=seed, rank=rank, world=world, reducer=reducer, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
+                         rot_scale_prob=rot_scale_prob),
+                    exclude)
+        model.first_stage_no_grad = frozen is not None
+        self.best_metric = {}
+
+    def _save_checkpoint(self, path, model, epoch, train_args, opt=None, step=None):
+        save_two_stage_checkpoint(path, model, epoch, train_args, opt, step, fine_tune=self.mode != "head")
+
+    def init_from_rpn(self, path: str, backbone_only: bool = False) -> dict:
+        """the first stage from a save_rpn_checkpoint file (or the reference's run_rpn.py checkpoint): backbone and RPN head, strictly; the parameters keep their
+        storage, so the flat buffers stay valid"""
+        ck = load_rpn_checkpoint(path, self.model.rpn_network, backbone_only=backbone_only)
+        self.flat.check()
+        return ck
+
+    @torch.no_grad()
+    def evaluate(self):
+        from .det_eval import DetectionEvaluator
+        self.model.eval()
+        ev = DetectionEvaluator(limits=(None,), ap_thresholds=(0.25, 0.5), top_k=self.top_k)
+        try:
+            for meshes, gt, gt_counts in self._val_batches():
+                boxes, scores, counts = self.model.detections_dense(meshes)
+                ev.update(boxes, scores, counts, gt, gt_counts)
+        finally:
+            self._train_mode()
+        out = ev.compute()                                            # the evaluation's one synchronisation
+        return {"ap_25": float(out["ap_25"]["ap"]), "ap_50": float(out["ap_50"]["ap"])}
+
+    def _samplers(self):
+        return [self.model.roi_model.sample_model] + ([self.model.rpn_network.rpn.loss] if self.model.train_rpn else [])
+
+    def _keep_best(self, epoch: int, rec: dict):
+        for name in ("25", "50"):
+            ap = rec[f"ap_{name}"]
+            if name not in self.best_metric or ap > self.best_metric[name]:
+                self.best_metric[name] = ap
+                self._save(f"model_best_ap{name}.pt", epoch)
+        self._newest(epoch)
 
 
 # --------------------------------------------------------------------------------------------------
