@@ -748,6 +748,21 @@ NMH_API int nmh_pack_weights(int dt, const void* descs_dev, const int* blk2desc_
 NMH_API int nmh_grad_sqnorm(const float* g, int64_t n, double* acc, void* stream);
 NMH_API int nmh_clip_coef(const double* acc, float max_norm, float* coef, float* norm_out, void* stream);
 NMH_API int nmh_adamw_step(float* p, float* g, float* m, float* v, int64_t n, const float* hyper, const float* coef, void* stream);
+/* The same two passes with per-range settings over the flat buffer (one optimizer param group per range: layer-wise learning-rate decay,
+ * no-decay sets, frozen ranges).  The table is on the device: bounds int64 [R+1] with 0 = bounds[0] < bounds[1] < ... < bounds[R] = n and
+ * every interior boundary a multiple of 4 (a 16-byte group lies in one range); scale float [R][2] = (lr_scale, wd_scale), finite and >= 0.
+ * Range r steps with lr * lr_scale and weight_decay * wd_scale; one range (1, 1) gives the bits of nmh_adamw_step.  lr_scale == 0 is FROZEN
+ * (requires_grad = False, not torch's lr = 0): p, m and v of the range are not written and nmh_grad_sqnorm_ranges leaves its gradient out
+ * of the norm, which is what clip_grad_norm_ sees when frozen parameters have no gradient; the gradient is still cleared under zero_g.
+ * nmh_clip_coef sits between the two as before.
+ * Both entries check the table on the host and return -5, launching nothing, for R outside 1 .. NMH_ADAMW_MAX_RANGES, bounds that are not
+ * as above, a misaligned table or a negative / non-finite scale.  The check copies the table (12 R bytes) on a stream of the library's own
+ * and waits for that copy alone, never for `stream`; the table must therefore be complete in memory when the entry is called.  While
+ * `stream` is being captured the host may not copy, so only R and n are checked: pass a table once outside the capture first.  The kernels
+ * stay inside [0, R) and [0, n) for any table contents. */
+#define NMH_ADAMW_MAX_RANGES 4096
+NMH_API int nmh_grad_sqnorm_ranges(const float* g, int64_t n, const int64_t* bounds, const float* scale, int R, double* acc, void* stream);
+NMH_API int nmh_adamw_step_ranges(float* p, float* g, float* m, float* v, int64_t n, const float* hyper, const float* coef, const int64_t* bounds, const float* scale, int R, void* stream);
 
 #ifdef __cplusplus
 }

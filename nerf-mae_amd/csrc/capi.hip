@@ -23,6 +23,7 @@ const char* nmh_error_string(int code) {
   if (code == -1) return "nmh: unsupported operation";
   if (code == -2) return "nmh: shape constraint violated (channel counts must be multiples of 8; head_dim must be 32)";
   if (code == -3) return "nmh: row too wide for the layernorm kernels";
+  if (code == -5) return "nmh: bad range table (1 <= R <= NMH_ADAMW_MAX_RANGES; bounds ascending from 0 to n, interior boundaries multiples of 4; scales finite and >= 0)";
   if (code < 0) return "nmh: invalid argument";
   return hipGetErrorString((hipError_t)code);
 }
@@ -1097,4 +1098,17 @@ int nmh_clip_coef(const double* acc, float max_norm, float* coef, float* norm_ou
   CLR(); return k_clip_coef(acc, max_norm, coef, norm_out, ST); }
 int nmh_adamw_step(float* p, float* g, float* m, float* v, int64_t n, const float* hyper, const float* coef, void* stream) {
   CLR(); return k_adamw(p, g, m, v, (long)n, hyper, coef, ST); }
+int nmh_grad_sqnorm_ranges(const float* g, int64_t n, const int64_t* bounds, const float* scale, int R, double* acc, void* stream) {
+  CLR();
+  REQ(g, bounds, scale, acc);
+  if (((uintptr_t)bounds | (uintptr_t)scale) & 7) return -5;
+  return k_sqnorm_ranges(g, (long)n, reinterpret_cast<const long*>(bounds), scale, R, acc, ST);
+}
+int nmh_adamw_step_ranges(float* p, float* g, float* m, float* v, int64_t n, const float* hyper, const float* coef, const int64_t* bounds, const float* scale, int R,
+                          void* stream) {
+  CLR();
+  REQ(p, g, m, v, hyper, bounds, scale);
+  if (((uintptr_t)bounds | (uintptr_t)scale) & 7) return -5;
+  return k_adamw_ranges(p, g, m, v, (long)n, hyper, coef, reinterpret_cast<const long*>(bounds), scale, R, ST);
+}
 }

@@ -5,6 +5,9 @@
 // cat), unetr_block.py:99-105 + swin_mae3d.py:1513-1549 (head + loss), run_swin_mae3d.py:588-598,665-669 (AdamW, clip).
 #include "common.hpp"
 #include "kernels.hpp"
+#include "../../include/nerfmae_hip.h"   // NMH_ADAMW_MAX_RANGES
+#include <cmath>
+#include <mutex>
 
 static inline unsigned ew_blocks(long total, int cap = 16384) { long nb = (total + 255) / 256; return (unsigned)(nb > cap ? cap : (nb < 1 ? 1 : nb)); }
 
@@ -708,21 +711,27 @@ int k_clip_coef(const double* acc, float max_norm, float* coef, float* norm_out,
   NMH_CHECK_LAUNCH();
   return 0;
 }
+// one element's decoupled-weight-decay Adam update, shared by adamw_kernel and adamw_ranges_kernel (step = lr / bias_correction1, isq = 1 / sqrt(bias_correction2)):
+//   m = b1 m + (1 - b1) gc;  v = b2 v + (1 - b2) gc^2;  p = p (1 - lr wd) - step m / (sqrt(v) isq + eps),   gc = g * coef.
+// The fused multiply-adds are spelled out and the compiler's own contraction is off inside: every caller then rounds alike, whatever surrounds the inlined
+// body -- what "one range (1, 1) gives the bits of nmh_adamw_step" rests on.  The spelling is the one the compiler chose for adamw_kernel's 16-byte loop when
+// the choice was its own.
+__device__ __forceinline__ void adamw_update(float& pi, float& gi, float& mi, float& vi, float cf, float lr, float wd, float b1, float b2, float eps, float step,
+                                             float isq, bool zero_g) {
+#pragma clang fp contract(off)
+  const float gc = gi * cf;
+  mi = fmaf(b1, mi, (1.0f - b1) * gc);
+  vi = fmaf(b2, vi, ((1.0f - b2) * gc) * gc);
+  pi = fmaf(pi, fmaf(-lr, wd, 1.0f), -((step * mi) / fmaf(sqrtf(vi), isq, eps)));
+  if (zero_g) gi = 0.f;
+}
 // hyper = {lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2} on device (graph-replayable)
 __global__ void adamw_kernel(float* p, float* g, float* m, float* v, long n, const float* hyper, const float* coef) {
   const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], bc1 = hyper[5], bc2 = hyper[6];
   const bool zero_g = hyper[7] != 0.f;   // leave the gradient buffer cleared for the next step (saves the separate 280 MB fill)
   const float cf = coef ? *coef : 1.0f;
   const float step = lr / bc1, isq = 1.0f / sqrtf(bc2);
-  auto upd = [&](float& pi, float& gi, float& mi, float& vi) {
-    const float gc = gi * cf;
-    float pn = pi * (1.0f - lr * wd);
-    mi = b1 * mi + (1.0f - b1) * gc;
-    vi = b2 * vi + (1.0f - b2) * gc * gc;
-    pn -= step * mi / (sqrtf(vi) * isq + eps);
-    pi = pn;
-    if (zero_g) gi = 0.f;
-  };
+  auto upd = [&](float& pi, float& gi, float& mi, float& vi) { adamw_update(pi, gi, mi, vi, cf, lr, wd, b1, b2, eps, step, isq, zero_g); };
   // four parameters per thread and iteration (16-byte accesses: the four flat buffers are 16-byte aligned); scalar tail
   const long n4 = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) ? n >> 2 : 0;
   // streaming accesses (non-temporal: 8 x 280 MB pass through once per step) from SHORT blocks -- two iterations per thread: tools/probes/hbm_stream_probe.hip
@@ -743,12 +752,146 @@ __global__ void adamw_kernel(float* p, float* g, float* m, float* v, long n, con
     if (zero_g) g[i] = gi;
   }
 }
-int k_adamw(float* p, float* g, float* m, float* v, long n, const float* hyper, const float* coef, hipStream_t st) {
+// blocks of 256 threads for the two AdamW kernels: short blocks, `per` 16-byte groups per thread and tensor (see adamw_kernel)
+static unsigned adamw_grid(long n) {
   static const int per = getenv("NMH_ADAMW_ITERS") ? atoi(getenv("NMH_ADAMW_ITERS")) : 2;   // 16-byte groups per thread
   long nb = ((n >> 2) + 256L * per - 1) / (256L * per);
   if (nb < 1) nb = 1;
   if (nb > (1L << 30)) nb = 1L << 30;
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)nb), dim3(256), 0, st, p, g, m, v, n, hyper, coef);
+  return (unsigned)nb;
+}
+int k_adamw(float* p, float* g, float* m, float* v, long n, const float* hyper, const float* coef, hipStream_t st) {
+  hipLaunchKernelGGL(adamw_kernel, dim3(adamw_grid(n)), dim3(256), 0, st, p, g, m, v, n, hyper, coef);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- the same two passes under a per-range table: (lr_scale, wd_scale) per range of the flat buffer, lr_scale == 0 = frozen ----------
+// bounds[R+1] (int64, device): 0 = bounds[0] < ... < bounds[R] = n, every interior boundary a multiple of 4, so a 16-byte group lies in ONE
+// range and the range is looked up once per group; scale[R][2] (device) = (lr_scale, wd_scale), finite and >= 0.
+// Each block keeps the table in LDS: the scales first (8-byte reads), then the first GROUP of every range as a 32-bit index -- 12 bytes per
+// range, 48 KB at NMH_ADAMW_MAX_RANGES.  The lookup is a bisection over broadcast reads (every lane of a wave reads the same or a
+// neighbouring word); it never leaves [0, R), whatever the table holds.
+__device__ __forceinline__ void range_table_to_lds(float2* sc, int* gb, const long* bounds, const float* scale, int R) {
+  for (int r = threadIdx.x; r < R; r += blockDim.x) {
+    sc[r] = reinterpret_cast<const float2*>(scale)[r];
+    gb[r] = (int)(bounds[r] >> 2);
+  }
+  __syncthreads();
+}
+// the last r with gb[r] <= grp (gb[0] = 0)
+__device__ __forceinline__ int range_of_group(const int* gb, int R, int grp) {
+  int lo = 0, hi = R;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (gb[mid] <= grp) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+__global__ __launch_bounds__(256) void sqnorm_ranges_kernel(const float* g, long n, const long* bounds, const float* scale, int R, double* acc) {
+  extern __shared__ float2 rt_sc[];
+  int* gb = reinterpret_cast<int*>(rt_sc + R);
+  __shared__ float sh[4];
+  range_table_to_lds(rt_sc, gb, bounds, scale, R);
+  float s = 0.f;
+  for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (long)gridDim.x * blockDim.x * 4) {
+    if (rt_sc[range_of_group(gb, R, (int)(i >> 2))].x == 0.f) continue;   // a frozen range has no gradient as far as the clip is concerned
+    if (i + 3 < n) { const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + i)); s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]; }
+    else for (long j = i; j < n; ++j) s += g[j] * g[j];
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(acc, (double)(sh[0] + sh[1] + sh[2] + sh[3]));
+}
+// adamw_kernel with the range's lr * lr_scale and weight_decay * wd_scale; the same loop, accesses and update function, so one range (1, 1) gives its bits.
+// A frozen group stores nothing to p, m, v; its gradient is still cleared under zero_g.
+__global__ __launch_bounds__(256) void adamw_ranges_kernel(float* p, float* g, float* m, float* v, long n, const float* hyper, const float* coef,
+                                                           const long* bounds, const float* scale, int R) {
+  extern __shared__ float2 rt_sc[];
+  int* gb = reinterpret_cast<int*>(rt_sc + R);
+  range_table_to_lds(rt_sc, gb, bounds, scale, R);
+  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], bc1 = hyper[5], bc2 = hyper[6];
+  const bool zero_g = hyper[7] != 0.f;
+  const float cf = coef ? *coef : 1.0f;
+  const float isq = 1.0f / sqrtf(bc2);
+  const long n4 = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) ? n >> 2 : 0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    // the four loads are issued before the lookup, whose LDS reads then run under their latency
+    f32x4 pv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(p) + i), gv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(g) + i);
+    f32x4 mv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(m) + i), vv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(v) + i);
+    const float2 sc = rt_sc[range_of_group(gb, R, (int)i)];
+    if (sc.x != 0.f) {
+      const float lr_r = lr * sc.x, wd_r = wd * sc.y, step = lr_r / bc1;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float a = pv[k], b = gv[k], c = mv[k], d = vv[k];
+        adamw_update(a, b, c, d, cf, lr_r, wd_r, b1, b2, eps, step, isq, false);
+        pv[k] = a; mv[k] = c; vv[k] = d;
+      }
+      __builtin_nontemporal_store(pv, reinterpret_cast<f32x4*>(p) + i); __builtin_nontemporal_store(mv, reinterpret_cast<f32x4*>(m) + i);
+      __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v) + i);
+    }
+    if (zero_g) { const f32x4 z = {0.f, 0.f, 0.f, 0.f}; __builtin_nontemporal_store(z, reinterpret_cast<f32x4*>(g) + i); }
+  }
+  for (long i = n4 * 4 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float2 sc = rt_sc[range_of_group(gb, R, (int)(i >> 2))];
+    if (sc.x != 0.f) {
+      const float lr_r = lr * sc.x, wd_r = wd * sc.y;
+      float pi = p[i], gi = g[i], mi = m[i], vi = v[i];
+      adamw_update(pi, gi, mi, vi, cf, lr_r, wd_r, b1, b2, eps, lr_r / bc1, isq, false);
+      p[i] = pi; m[i] = mi; v[i] = vi;
+    }
+    if (zero_g) g[i] = 0.f;
+  }
+}
+// The entries' check of a table, on the host: -5 unless 1 <= R <= NMH_ADAMW_MAX_RANGES, bounds[0] = 0 < bounds[1] < ... < bounds[R] = n, every interior
+// boundary a multiple of 4 and every scale finite and >= 0.  The table is copied through a pinned buffer on a stream of the library's own,
+// so the caller's stream is never waited for (the table has to be complete in memory when the entry is called: it is built once, long
+// before the first step).  While `st` is being captured the host may not copy: only R and n are checked there, and the kernels stay inside
+// [0, R) and [0, n) for any contents.
+static int range_table_check(const long* bounds, const float* scale, int R, long n, hipStream_t st) {
+  if (R < 1 || R > NMH_ADAMW_MAX_RANGES || n < 1 || (n >> 2) > 0x7fffffffL) return -5;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  hipError_t e = hipStreamIsCapturing(st, &cs);
+  if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
+  if (cs != hipStreamCaptureStatusNone) return 0;
+  static std::mutex mu;
+  static hipStream_t side[64] = {};
+  static char* host = nullptr;
+  std::lock_guard<std::mutex> lock(mu);
+  const int dev = NmhPerDeviceOnce::dev();
+  const size_t nbnd = (size_t)(R + 1) * sizeof(long), nsc = (size_t)R * 2 * sizeof(float);
+  if (!host && (e = hipHostMalloc(reinterpret_cast<void**>(&host), (NMH_ADAMW_MAX_RANGES + 1) * sizeof(long) + NMH_ADAMW_MAX_RANGES * 2 * sizeof(float), hipHostMallocPortable)) != hipSuccess) {
+    host = nullptr; (void)hipGetLastError(); return (int)e;
+  }
+  if (!side[dev] && (e = hipStreamCreateWithFlags(&side[dev], hipStreamNonBlocking)) != hipSuccess) { side[dev] = nullptr; (void)hipGetLastError(); return (int)e; }
+  if ((e = hipMemcpyAsync(host, bounds, nbnd, hipMemcpyDeviceToHost, side[dev])) != hipSuccess ||
+      (e = hipMemcpyAsync(host + (NMH_ADAMW_MAX_RANGES + 1) * sizeof(long), scale, nsc, hipMemcpyDeviceToHost, side[dev])) != hipSuccess ||
+      (e = hipStreamSynchronize(side[dev])) != hipSuccess) { (void)hipGetLastError(); return (int)e; }
+  const long* b = reinterpret_cast<const long*>(host);
+  const float* s = reinterpret_cast<const float*>(host + (NMH_ADAMW_MAX_RANGES + 1) * sizeof(long));
+  if (b[0] != 0 || b[R] != n) return -5;
+  for (int r = 0; r < R; ++r) {
+    if (b[r + 1] <= b[r] || (r > 0 && (b[r] & 3))) return -5;
+    if (!(s[2 * r] >= 0.f) || !(s[2 * r + 1] >= 0.f) || std::isinf(s[2 * r]) || std::isinf(s[2 * r + 1])) return -5;
+  }
+  return 0;
+}
+int k_sqnorm_ranges(const float* g, long n, const long* bounds, const float* scale, int R, double* acc, hipStream_t st) {
+  const int rc = range_table_check(bounds, scale, R, n, st);
+  if (rc) return rc;
+  hipError_t e = nmh_zero_async(acc, sizeof(double), st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(sqnorm_ranges_kernel, dim3(ew_blocks((n + 3) / 4, 2048)), dim3(256), (size_t)R * 12, st, g, n, bounds, scale, R, acc);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
+int k_adamw_ranges(float* p, float* g, float* m, float* v, long n, const float* hyper, const float* coef, const long* bounds, const float* scale, int R,
+                   hipStream_t st) {
+  const int rc = range_table_check(bounds, scale, R, n, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(adamw_ranges_kernel, dim3(adamw_grid(n)), dim3(256), (size_t)R * 12, st, p, g, m, v, n, hyper, coef, bounds, scale, R);
   NMH_CHECK_LAUNCH();
   return 0;
 }

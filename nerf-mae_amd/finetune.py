@@ -7,8 +7,11 @@
                    state_dict), so those work on it unchanged.  exclude=(sub-modules) leaves a frozen part out of the buffers altogether.
   FinetuneStep     one eager step: check the views, forward, backward, clip + AdamW (three launches; the update clears the gradient buffer).
   fcos_loss_fn, rpn_loss_fn, voxel_loss_fn, loss_fn_for   the loss functions FinetuneStep takes, for the four downstream models.
+  param_ranges     per-range optimizer settings over the flat layout, from ordered rules: the table FusedAdamW(ranges=) steps with.
+  layer_decay_rules, no_decay_rules, freeze_rules, recipe_rules   the rules of the usual fine-tuning recipe.
 
-No kernel of its own: forward and backward are the models', the optimizer is nmh_grad_sqnorm / nmh_clip_coef / nmh_adamw_step (trainer.FusedAdamW).
+No kernel of its own: forward and backward are the models', the optimizer is nmh_grad_sqnorm / nmh_clip_coef / nmh_adamw_step (trainer.FusedAdamW), or their
+*_ranges forms under a table.
 
 Ordering of the gradient producers before the optimizer reads the buffer: every Function of this package that forks the side stream joins it
 before its backward returns, and the base's deferred weight gradients are issued and joined by _EmbedFn.backward and by the end-of-backward callback of its
@@ -18,14 +21,15 @@ Eager.  Data-parallel with a dist.FlatGradReducer (FinetuneStep(..., reducer=)):
 A graph capture of the detectors needs padded target lists first and is left out."""
 from __future__ import annotations
 
-from typing import Callable, Dict, Optional
+from typing import Callable, Dict, NamedTuple, Optional
 
 import torch
 from torch import nn
 
 from .model import SwinTransformer_MAE3D_New
 
-__all__ = ["FlatParameters", "FinetuneStep", "fcos_loss_fn", "rpn_loss_fn", "voxel_loss_fn", "loss_fn_for"]
+__all__ = ["FlatParameters", "FinetuneStep", "fcos_loss_fn", "rpn_loss_fn", "voxel_loss_fn", "loss_fn_for", "ParamRanges", "param_ranges", "layer_ids",
+           "layer_decay_rules", "no_decay_rules", "freeze_rules", "recipe_rules"]
 
 
 def _round8(n: int) -> int:
@@ -151,6 +155,166 @@ class FlatParameters:
         b = self.base
         if b is not None and (b._flat is None or b._flat.data_ptr() != p0 or b._flat_grad.data_ptr() != g0):
             raise RuntimeError("FlatParameters.check: the SwinTransformer_MAE3D_New flattened itself again; build a new FlatParameters and optimizer")
+
+
+# ---- per-range optimizer settings over the flat layout -------------------------------------------------------------------------
+class ParamRanges(NamedTuple):
+    """what param_ranges returns and FusedAdamW(ranges=) takes: the device table of nmh_adamw_step_ranges and its host record"""
+    bounds: torch.Tensor    # int64 [R+1] on the flat buffer's device
+    scale: torch.Tensor     # float32 [R, 2] = (lr_scale, wd_scale)
+    record: dict            # {"bounds": [int] * (R+1), "scale": [[lr_scale, wd_scale]] * R}: plain numbers, what a checkpoint's resume section stores
+
+
+def _selector(sel) -> Callable:
+    """a rule's selector -> predicate(name, param): a name prefix, a callable (name, param) -> bool, or a sub-module (its parameters)"""
+    if isinstance(sel, str):
+        return lambda name, p: name.startswith(sel)
+    if isinstance(sel, nn.Module):
+        ids = {id(p) for p in sel.parameters()}
+        return lambda name, p: id(p) in ids
+    if callable(sel):
+        return sel
+    raise TypeError(f"param_ranges: a selector is a name prefix, a callable (name, param) -> bool or a sub-module, not {type(sel).__name__}")
+
+
+def _selector_text(sel) -> str:
+    return repr(sel) if isinstance(sel, str) else f"{type(sel).__name__} (sub-module)" if isinstance(sel, nn.Module) else getattr(sel, "__name__", repr(sel))
+
+
+def param_ranges(flat, rules) -> ParamRanges:
+    """param_ranges(flat, rules): the per-range table of trainer.FusedAdamW(ranges=) over the flat layout of `flat`, an MAE model or a FlatParameters (anything
+    trainer.flat_layout takes).
+
+    rules: an ordered list of (selector, lr_scale, wd_scale).  For every parameter of the flat buffer, each of the two scales comes from the FIRST rule that
+    matches the parameter and states that scale; None in a rule leaves the scale to a later rule, and a scale no rule states is 1.  lr_scale 0 freezes the
+    parameter (no update, no moments, outside the clip norm: DESIGN.md 3.25).  A parameter's range runs up to the next parameter's offset, so the granule padding
+    behind it joins it; adjacent parameters with equal scales share one range.
+    Refused (ValueError): a negative or non-finite scale; a rule that matches no parameter of the flat buffer (a typo must not silently train everything; a
+    parameter that FlatParameters(exclude=) left out is not there to be selected); more ranges than ops.ADAMW_MAX_RANGES."""
+    import math
+    from . import ops
+    if flat._flat is None:
+        flat.flatten_parameters()
+    n = int(flat._flat.numel())
+    params = sorted(((int(flat._offsets[id(p)]), name, p) for name, p in flat.named_parameters() if id(p) in flat._offsets), key=lambda t: t[0])
+    if not params or params[0][0] != 0:
+        raise ValueError("param_ranges: the flat layout does not start at offset 0")
+    compiled = []
+    for k, rule in enumerate(rules):
+        if not isinstance(rule, (tuple, list)) or len(rule) != 3:
+            raise TypeError(f"param_ranges: rule {k} is not (selector, lr_scale, wd_scale)")
+        sel, ls, ws = rule
+        for what, s in (("lr_scale", ls), ("wd_scale", ws)):
+            if s is not None and not (math.isfinite(float(s)) and float(s) >= 0.0):
+                raise ValueError(f"param_ranges: rule {k} ({_selector_text(sel)}): {what} = {s}; a scale is finite and >= 0")
+        compiled.append((_selector(sel), None if ls is None else float(ls), None if ws is None else float(ws)))
+    matched = [False] * len(compiled)
+    f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))  # noqa: E731  (the value the device table holds: the record compares equal after a round trip)
+    bounds, scale = [], []
+    for off, name, p in params:
+        ls = ws = None
+        for k, (pred, rl, rw) in enumerate(compiled):
+            if (ls is not None and ws is not None) or not pred(name, p):
+                continue
+            matched[k] = True
+            ls, ws = rl if ls is None else ls, rw if ws is None else ws
+        s = [f32(1.0 if ls is None else ls), f32(1.0 if ws is None else ws)]
+        if not scale or scale[-1] != s:
+            bounds.append(off)
+            scale.append(s)
+    for k, hit in enumerate(matched):
+        if not hit:
+            raise ValueError(f"param_ranges: rule {k} ({_selector_text(rules[k][0])}) matches no parameter of the flat buffer")
+    bounds.append(n)
+    if len(scale) > ops.ADAMW_MAX_RANGES:
+        raise ValueError(f"param_ranges: {len(scale)} ranges, the kernels take {ops.ADAMW_MAX_RANGES}")
+    dev = flat._flat.device
+    return ParamRanges(torch.tensor(bounds, dtype=torch.int64).to(dev), torch.tensor(scale, dtype=torch.float32).reshape(-1, 2).to(dev),
+                       {"bounds": bounds, "scale": scale})
+
+
+def _encoder_of(module, who: str) -> SwinTransformer_MAE3D_New:
+    """the one SwinTransformer_MAE3D_New inside `module` (a module or a FlatParameters), found by identity as FlatParameters finds it"""
+    module = module.module if isinstance(module, FlatParameters) else module
+    bases = [m for m in module.modules() if isinstance(m, SwinTransformer_MAE3D_New)]
+    if len(bases) != 1:
+        raise ValueError(f"{who}: the module holds {len(bases)} SwinTransformer_MAE3D_New, it takes exactly one")
+    return bases[0]
+
+
+def layer_ids(module) -> Dict[int, int]:
+    """{id(parameter): layer id} of the encoder's parameters for layer-wise learning-rate decay, L = the number of Swin blocks: patch_partition and mask_token 0;
+    the k-th block over all stages (0-based) k + 1; a stage's PatchMerging3D the id of that stage's first block.  Every parameter that is not listed (decoders,
+    out, neck, heads) has id L + 1."""
+    from .model import PatchMerging3D, SwinBlock3D
+    base = _encoder_of(module, "layer_ids")
+    ids = {id(p): 0 for p in base.patch_partition.parameters()}
+    if "mask_token" in base._parameters:       # (the downstream backbones drop it)
+        ids[id(base.mask_token)] = 0
+    k = 0
+    for stage in base.stages:
+        merges = [m for m in stage if isinstance(m, PatchMerging3D)]
+        first = k + 1
+        for m in stage:
+            if isinstance(m, SwinBlock3D):
+                k += 1
+                ids.update({id(p): k for p in m.parameters()})
+        for m in merges:
+            ids.update({id(p): first for p in m.parameters()})
+    return ids
+
+
+def layer_decay_rules(module, decay: float):
+    """rules of layer-wise learning-rate decay over the encoder of `module`: lr_scale = decay ** (L + 1 - id) with the ids of layer_ids, one rule per id; what
+    lies after the encoder (id L + 1) keeps scale 1 and needs no rule.  Refused: a module without exactly one SwinTransformer_MAE3D_New."""
+    from .model import SwinBlock3D
+    base = _encoder_of(module, "layer_decay_rules")
+    if not float(decay) > 0.0:
+        raise ValueError(f"layer_decay_rules: decay = {decay}; it is positive (freeze_rules freezes)")
+    ids = layer_ids(base)
+    L = sum(isinstance(m, SwinBlock3D) for st in base.stages for m in st)
+    rules = []
+    for layer in sorted(set(ids.values())):
+        members = {i for i, l in ids.items() if l == layer}
+
+        def pred(name, p, members=members):
+            return id(p) in members
+        pred.__name__ = f"layer {layer}"
+        rules.append((pred, float(decay) ** (L + 1 - layer), None))
+    return rules
+
+
+def no_decay_rules(module):
+    """one rule, wd_scale 0, for every parameter with dim() <= 1 (norms, biases), the relative-position bias tables, mask_token and the parameters of fcos.Scale"""
+    from .fcos import Scale
+    module = module.module if isinstance(module, FlatParameters) else module
+    special = {id(p) for m in module.modules() if isinstance(m, Scale) for p in m.parameters()}
+    special |= {id(p) for name, p in module.named_parameters() if name.endswith("relative_position_bias_table") or name.split(".")[-1] == "mask_token"}
+
+    def no_decay(name, p):
+        return p.dim() <= 1 or id(p) in special
+    return [(no_decay, None, 0.0)]
+
+
+def freeze_rules(*selectors):
+    """lr_scale 0 for what each selector matches: those parameters, and their moments, are not written by the step"""
+    return [(s, 0.0, None) for s in selectors]
+
+
+def _selectors(freeze) -> tuple:
+    return (freeze,) if isinstance(freeze, (str, nn.Module)) or callable(freeze) else tuple(freeze)
+
+
+def selector_names(module, freeze) -> list:
+    """the trainers' `freeze` as a checkpoint's train_args record it: a prefix as it is, a sub-module by its name inside `module`, a callable by its __name__"""
+    names = {id(m): n for n, m in module.named_modules()}
+    return [s if isinstance(s, str) else names.get(id(s), type(s).__name__) if isinstance(s, nn.Module) else getattr(s, "__name__", repr(s)) for s in _selectors(freeze)]
+
+
+def recipe_rules(module, layer_decay: float = None, no_decay: bool = False, freeze=()):
+    """the trainers' three switches as one rule list: freeze first (it wins the lr_scale), then layer decay, then the no-decay set"""
+    freeze = _selectors(freeze)
+    return (freeze_rules(*freeze) + (layer_decay_rules(module, layer_decay) if layer_decay is not None else []) + (no_decay_rules(module) if no_decay else []))
 
 
 # ---- loss functions of the five downstream models ----------------------------------------------------------------------------------------------

@@ -1379,6 +1379,27 @@ def adamw_step(p, g, m, v, hyper, coef=None):
     lib().call("nmh_adamw_step", p, g, m, v, p.numel(), hyper, coef, _st())
 
 
+ADAMW_MAX_RANGES = 4096   # NMH_ADAMW_MAX_RANGES of include/nerfmae_hip.h (tests/test_param_ranges_cpu.py compares the two)
+
+
+def _range_table(bounds, scale):
+    """the device table of the two *_ranges entries: bounds int64 [R+1], scale fp32 [R, 2] -> R"""
+    R = bounds.numel() - 1
+    if bounds.dtype != torch.int64 or scale.dtype != torch.float32 or tuple(scale.shape) != (R, 2) or not (bounds.is_contiguous() and scale.is_contiguous()):
+        raise TypeError(f"range table: bounds int64 [R+1] and scale float32 [R, 2], contiguous; got {bounds.dtype} {tuple(bounds.shape)}, {scale.dtype} {tuple(scale.shape)}")
+    return R
+
+
+def grad_sqnorm_ranges(g, bounds, scale, acc):
+    """grad_sqnorm over the ranges whose lr_scale is not 0 (nmh_grad_sqnorm_ranges); NmhError for a table the entry refuses"""
+    lib().call("nmh_grad_sqnorm_ranges", g, g.numel(), bounds, scale, _range_table(bounds, scale), acc, _st())
+
+
+def adamw_step_ranges(p, g, m, v, hyper, bounds, scale, coef=None):
+    """adamw_step with lr * lr_scale and weight_decay * wd_scale per range; lr_scale 0 freezes the range (nmh_adamw_step_ranges)"""
+    lib().call("nmh_adamw_step_ranges", p, g, m, v, p.numel(), hyper, coef, bounds, scale, _range_table(bounds, scale), _st())
+
+
 # ---- FPN neck (nerf_rpn/model/fpn.py; SURVEY 8(f) rank 1) -----------------------------------------------------------------------
 def conv3d_k3_bias(X, Wp, bias, Cout, out=None):
     """conv3d_k3 with a per-output-channel fp32 bias in the epilogue: X (B,D,H,W,Cin) channels-last, Wp packed [Cout][27][Cin]."""

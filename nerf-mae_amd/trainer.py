@@ -66,7 +66,12 @@ class PinnedRing:
 
 
 class FusedAdamW:
-    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3, max_grad_norm=0.1):
+    """ranges: a finetune.param_ranges table over `model`'s flat layout, or None.  With a table the step runs the *_ranges kernels: range r steps with
+    lr * lr_scale[r] and weight_decay * wd_scale[r], a range with lr_scale 0 is frozen (parameters and moments not written, outside the clip norm), and `norm` is
+    the norm over the ranges that train.  The table is fixed here, on the device, so launch() stays graph-capturable; the scheduled lr of set_hyper() times the
+    fixed scale is what OneCycleLR does with a list of max_lr.  None: the one-setting kernels, exactly as without the keyword."""
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3, max_grad_norm=0.1, ranges=None):
         if model._flat is None:
             model.flatten_parameters()
         self.model, self.lr, self.betas, self.eps, self.wd, self.max_norm = model, lr, tuple(betas), eps, weight_decay, max_grad_norm
@@ -79,6 +84,16 @@ class FusedAdamW:
         self.hyper = torch.tensor([0.0, betas[0], betas[1], eps, 0.0, 1.0, 1.0, 0.0], device=flat.device)
         self.t = 0
         self.zero_grads_after_step = False   # the AdamW kernel also clears the flat gradient buffer (GraphedTrainStep turns it on)
+        self.ranges, self.range_record = None, None
+        if ranges is not None:
+            bounds, scale, record = ranges
+            if int(record["bounds"][-1]) != flat.numel() or bounds.device != flat.device or scale.device != flat.device:
+                raise ValueError(f"FusedAdamW: the range table ends at {record['bounds'][-1]} on {bounds.device}, the flat buffer has {flat.numel()} elements on "
+                                 f"{flat.device}: build it with finetune.param_ranges over the same object")
+            self.ranges, self.range_record = (bounds, scale), range_record(record)
+            if flat.is_cuda:
+                # the entries check a table on the host except inside a graph capture: once here, so a table they refuse never reaches a captured launch
+                ops.grad_sqnorm_ranges(model._flat_grad, bounds, scale, self.acc)
 
     def set_hyper(self, lr=None, beta1=None):
         if lr is not None:
@@ -104,6 +119,12 @@ class FusedAdamW:
     def launch(self):
         """the three device-side launches (graph-capturable): grad norm, clip coefficient, AdamW update"""
         g = self.model._flat_grad
+        if self.ranges is not None:
+            bounds, scale = self.ranges
+            ops.grad_sqnorm_ranges(g, bounds, scale, self.acc)
+            ops.clip_coef(self.acc, float(self.max_norm or 0.0), self.coef, self.norm)
+            ops.adamw_step_ranges(self.model._flat, g, self.m, self.v, self.hyper, bounds, scale, self.coef)
+            return
         ops.grad_sqnorm(g, self.acc)
         ops.clip_coef(self.acc, float(self.max_norm or 0.0), self.coef, self.norm)
         ops.adamw_step(self.model._flat, g, self.m, self.v, self.hyper, self.coef)
@@ -458,12 +479,27 @@ def resume_section(model, opt, step=None) -> dict:
     """what a TRUE resume needs, as save_checkpoint and save_detection_checkpoint store it under "resume": the AdamW moments over the flat buffer, step count,
     learning rate, betas, schedule position.  The moments are flat buffers in the model's parameter order: the layout (name -> offset, numel) travels with
     them, so a file written under another flat layout (e.g. the 4-element granule of earlier builds) is remapped by name instead of misaligned"""
-    return {"m": opt.m.detach().cpu(), "v": opt.v.detach().cpu(), "t": opt.t, "lr": opt.lr, "betas": tuple(opt.betas), "step": step, "layout": flat_layout(model)}
+    r = {"m": opt.m.detach().cpu(), "v": opt.v.detach().cpu(), "t": opt.t, "lr": opt.lr, "betas": tuple(opt.betas), "step": step, "layout": flat_layout(model)}
+    if getattr(opt, "range_record", None) is not None:     # FusedAdamW(ranges=): the table the moments were kept under; without one the section is as before
+        r["ranges"] = opt.range_record
+    return r
+
+
+def range_record(rec) -> dict:
+    """a range table's host record (finetune.ParamRanges.record, or a resume section's "ranges") in the one form that compares: ints and floats in lists"""
+    return {"bounds": [int(b) for b in rec["bounds"]], "scale": [[float(ls), float(ws)] for ls, ws in rec["scale"]]}
 
 
 def restore_resume(r: dict, model, opt, who: str):
     """the inverse of resume_section: the moments into opt.m / opt.v (remapped by parameter name when the file's flat layout is not this build's), then
     t, lr and betas.  `model` is whatever flat_layout takes (an MAE model or a finetune.FlatParameters)."""
+    tab_ck, tab_now = r.get("ranges"), getattr(opt, "range_record", None)
+    if (None if tab_ck is None else range_record(tab_ck)) != tab_now:
+        # the frozen ranges' moments in the file are whatever they were when freezing began (zero from the start): stepping them under another table, or
+        # freezing ranges whose moments are live, would be silent
+        raise RuntimeError(f"{who}: the file's optimizer state was kept {'without a range table' if tab_ck is None else 'under a range table of ' + str(len(tab_ck['scale'])) + ' ranges'}"
+                           f", this optimizer has {'none' if tab_now is None else ('one' if tab_ck is None else 'another one') + ' of ' + str(len(tab_now['scale'])) + ' ranges'}: build FusedAdamW with the "
+                           "same ranges= (the same layer_decay / no_decay / freeze)")
     lay_now, lay_ck = flat_layout(model), r.get("layout")
     if lay_ck is None or {k: list(v) for k, v in lay_ck.items()} == lay_now:
         if r["m"].numel() != opt.m.numel():
@@ -509,18 +545,21 @@ class Trainer:
 
     def __init__(self, model, train_scenes, val_scenes=None, batch_size: int = 4, num_epochs: int = 1, lr: float = 1e-4, weight_decay: float = 1e-3,
                  clip_grad_norm: float = 0.1, eval_interval: int = 1, save_path: str = None, normalize_density: bool = True, flip_prob: float = 0.0,
-                 rotate_prob: float = 0.0, rank: int = 0, world: int = 1, reducer=None, log=print, train_args: dict = None, seed: int = 0):
+                 rotate_prob: float = 0.0, rank: int = 0, world: int = 1, reducer=None, log=print, train_args: dict = None, seed: int = 0, no_decay: bool = False, freeze=()):
         from . import data, dist as _dist
+        from .finetune import param_ranges, recipe_rules, selector_names
         self.model, self.train_scenes, self.val_scenes = model, train_scenes, val_scenes
         self.batch, self.epochs, self.eval_interval, self.save_path = batch_size, num_epochs, eval_interval, save_path
         self.rank, self.world, self.log, self.seed = rank, world, log, seed
         self.args = dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, batch_size=batch_size * world,
-                         num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob)
+                         num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob, no_decay=bool(no_decay),
+                         freeze=selector_names(model, freeze))
         self._shard = _dist.shard_indices
         dev = model.mask_token.device
         self.batcher = data.GridBatcher(model.resolution, dev, normalize_density, flip_prob, rotate_prob)
         self.val_batcher = data.GridBatcher(model.resolution, dev, normalize_density)
-        self.opt = FusedAdamW(model, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
+        rules = recipe_rules(model, None, no_decay, freeze)     # per-range settings; none: the one-setting step
+        self.opt = FusedAdamW(model, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm, ranges=param_ranges(model, rules) if rules else None)
         # the reference's DataLoader has no drop_last: len(train_loader) is the ceiling, and it sizes OneCycleLR (run_swin_mae3d.py:594-598)
         self.steps_per_epoch = -(-len(self._shard(len(train_scenes), rank, world, 0)) // batch_size)
         if self.steps_per_epoch < 1:
@@ -714,6 +753,12 @@ class _FinetuneTrainer:
     exclude: sub-modules that are frozen as a whole.  They are handed to FlatParameters(exclude=), so the optimizer neither steps nor decays them and a reducer
     does not exchange them (the initial broadcast still sends them once), and they are put back into eval() after every model.train() of the loop.
 
+    layer_decay, no_decay, freeze (the defaults are the one group above): layer-wise learning-rate decay over the encoder's blocks
+    (finetune.layer_decay_rules), no weight decay on norms, biases, relative-position tables, mask_token and fcos.Scale (no_decay_rules), and selectors (name
+    prefixes, sub-modules, callables) of parameters that stay INSIDE the flat buffers but are not stepped (freeze_rules): the optimizer writes neither them nor
+    their moments and clips over the rest; their gradients are still computed and, data-parallel, exchanged.  `freeze` adds to `exclude`; a selector that matches
+    only what `exclude` left out is refused.  The three are recorded in train_args, and a resume under other settings is refused (restore_resume).
+
     A subclass supplies its checkpoint pair (_save_checkpoint, _load_checkpoint) and
       _logged(losses)         the step's detached losses -> the 1-D tensor that the epoch accumulates
       _record(vals)           the epoch's means of _logged, read back as a list -> the training part of the history record
@@ -723,14 +768,14 @@ class _FinetuneTrainer:
 
     def __init__(self, model, train_scenes, train_targets, val_scenes, val_targets, batcher, val_batcher, loss_fn, weights, args: dict, batch_size: int,
                  num_epochs: int, schedule_epochs: int, lr: float, weight_decay: float, clip_grad_norm: float, eval_interval: int, save_path: str, log, seed: int,
-                 rank: int, world: int, reducer, exclude=()):
+                 rank: int, world: int, reducer, exclude=(), layer_decay: float = None, no_decay: bool = False, freeze=()):
         import random
         from . import dist as _dist
-        from .finetune import FinetuneStep, FlatParameters
+        from .finetune import FinetuneStep, FlatParameters, param_ranges, recipe_rules, selector_names
         self.model, self.train_scenes, self.train_targets, self.val_scenes, self.val_targets = model, train_scenes, train_targets, val_scenes, val_targets
         self.batch, self.epochs, self.eval_interval, self.save_path, self.log, self.seed = batch_size, num_epochs, eval_interval, save_path, log, seed
         self.rank, self.world = rank, world
-        self.args = _plain(args)
+        self.args = _plain(dict(args, layer_decay=layer_decay, no_decay=bool(no_decay), freeze=selector_names(model, freeze)))
         self.batcher, self.val_batcher = batcher, val_batcher
         self.exclude = tuple(exclude)                            # the frozen part: outside the flat buffers, kept in eval()
         if reducer is not None:
@@ -746,7 +791,9 @@ class _FinetuneTrainer:
         self.reducer = reducer
         if world > 1:
             _dist.broadcast_flat_parameters(self.flat)   # DDP's initial broadcast: every rank starts from rank 0's weights
-        self.opt = FusedAdamW(self.flat, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
+        # per-range settings: a selector that matches nothing in the flat buffer -- a typo, or a part that `exclude` left out -- is refused
+        rules = recipe_rules(model, layer_decay, no_decay, freeze)
+        self.opt = FusedAdamW(self.flat, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm, ranges=param_ranges(self.flat, rules) if rules else None)
         self.steps_per_epoch = len(dp_epoch_plan(len(train_scenes), batch_size, rank, world, 0, seed))   # len(train_loader) without drop_last, the same on every rank
         self.sched = OneCycle(lr, schedule_epochs * self.steps_per_epoch)
         self.step_fn = FinetuneStep(self.flat, self.opt, loss_fn, weights=weights, reducer=reducer)
@@ -850,7 +897,8 @@ class DetectionTrainer(_FinetuneTrainer):
     def __init__(self, model, train_scenes, train_boxes, val_scenes=None, val_boxes=None, batch_size: int = 2, num_epochs: int = 1, lr: float = 3e-4,
                  weight_decay: float = 1e-3, clip_grad_norm: float = 0.1, reg_loss_weight: float = 1.0, eval_interval: int = 1, save_path: str = None,
                  normalize_density: bool = True, flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = 1000,
-                 log=print, train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None):
+                 log=print, train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None, layer_decay: float = None,
+                 no_decay: bool = False, freeze=()):
         from . import data
         from .finetune import fcos_loss_fn
         if len(train_scenes) != len(train_boxes) or (val_scenes is not None and len(val_scenes) != len(val_boxes or [])):
@@ -871,7 +919,8 @@ class DetectionTrainer(_FinetuneTrainer):
                          dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, reg_loss_weight=reg_loss_weight,
                               batch_size=batch_size * world, num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob,
                               rotate_prob=rotate_prob, rot_scale_prob=rot_scale_prob),
-                         batch_size, num_epochs, schedule_epochs, lr, weight_decay, clip_grad_norm, eval_interval, save_path, log, seed, rank, world, reducer)
+                         batch_size, num_epochs, schedule_epochs, lr, weight_decay, clip_grad_norm, eval_interval, save_path, log, seed, rank, world, reducer,
+                         layer_decay=layer_decay, no_decay=no_decay, freeze=freeze)
         self.top_n = int(model.args.fpn_post_nms_top_n)
         self.limits = [l for l in (300, 1000, self.top_n) if l <= self.top_n]
         self.ap_top_n = (train_args or {}).get("ap_top_n")
@@ -1007,7 +1056,8 @@ class _BoxTrainer(_FinetuneTrainer):
                                   data.DetectionBatcher(resolution, dev, c["normalize_density"], c["flip_prob"], c["rotate_prob"], c["rot_scale_prob"]),
                                   data.DetectionBatcher(resolution, dev, c["normalize_density"]), loss_fn, weights, c["args"], c["batch_size"], c["num_epochs"],
                                   c["schedule_epochs"] or c["num_epochs"], c["lr"], c["weight_decay"], c["clip_grad_norm"], c["eval_interval"], c["save_path"],
-                                  c["log"], c["seed"], c["rank"], c["world"], c["reducer"], exclude=exclude)
+                                  c["log"], c["seed"], c["rank"], c["world"], c["reducer"], exclude=exclude, layer_decay=c["layer_decay"], no_decay=c["no_decay"],
+                                  freeze=c["freeze"])
 
     def _logged(self, losses):
         return torch.stack([losses[k] for k in self.keys])
@@ -1057,7 +1107,7 @@ class RPNTrainer(_BoxTrainer):
                  lr: float = 1e-4, weight_decay: float = 0.01, clip_grad_norm: float = 0.1, reg_loss_weight: float = 5.0, reg_loss_weight_2d: float = 0.0,
                  eval_interval: int = 1, keep_checkpoints: int = 1, top_k: int = None, freeze_backbone: bool = False, normalize_density: bool = True,
                  flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = None, save_path: str = None, log=print,
-                 train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None):
+                 train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None, layer_decay: float = None, no_decay: bool = False, freeze=()):
         from .finetune import rpn_loss_fn
         self.freeze_backbone = bool(freeze_backbone)
         args = dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, reg_loss_weight=reg_loss_weight,
@@ -1069,7 +1119,7 @@ class RPNTrainer(_BoxTrainer):
                     dict(args=args, batch_size=batch_size, num_epochs=num_epochs, schedule_epochs=schedule_epochs, lr=lr, weight_decay=weight_decay,
                          clip_grad_norm=clip_grad_norm, eval_interval=eval_interval, keep_checkpoints=keep_checkpoints, top_k=top_k, save_path=save_path, log=log,
                          seed=seed, rank=rank, world=world, reducer=reducer, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
-                         rot_scale_prob=rot_scale_prob),
+                         rot_scale_prob=rot_scale_prob, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze),
                     (model.backbone,) if self.freeze_backbone else ())
         if self.freeze_backbone:
             model.backbone_no_grad = True
@@ -1140,7 +1190,8 @@ class TwoStageTrainer(_BoxTrainer):
                  lr: float = 1e-4, weight_decay: float = 5e-4, clip_grad_norm: float = 0.1, reg_loss_weight: float = 5.0, rpn_reg_loss_weight: float = 5.0,
                  rpn_reg_loss_weight_2d: float = 0.0, obj_only: bool = False, freeze_first_stage: bool = None, eval_interval: int = 1, keep_checkpoints: int = 1,
                  top_k: int = None, normalize_density: bool = True, flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0,
-                 schedule_epochs: int = None, save_path: str = None, log=print, train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None):
+                 schedule_epochs: int = None, save_path: str = None, log=print, train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None,
+                 layer_decay: float = None, no_decay: bool = False, freeze=()):
         from .finetune import roi_loss_fn
         if obj_only and model.is_reg:
             raise ValueError("TwoStageTrainer: obj_only trains no box regression, but the detector decodes with it (is_reg=True): build TwoStageDetector(..., "
@@ -1162,7 +1213,7 @@ class TwoStageTrainer(_BoxTrainer):
                     dict(args=args, batch_size=batch_size, num_epochs=num_epochs, schedule_epochs=schedule_epochs, lr=lr, weight_decay=weight_decay,
                          clip_grad_norm=clip_grad_norm, eval_interval=eval_interval, keep_checkpoints=keep_checkpoints, top_k=top_k, save_path=save_path, log=log,
                          seed=seed, rank=rank, world=world, reducer=reducer, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
-                         rot_scale_prob=rot_scale_prob),
+                         rot_scale_prob=rot_scale_prob, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze),
                     exclude)
         model.first_stage_no_grad = frozen is not None
         self.best_metric = {}
@@ -1239,7 +1290,7 @@ class VoxelTrainer(_FinetuneTrainer):
     def __init__(self, model, train_scenes, train_targets, val_scenes=None, val_targets=None, batch_size: int = 1, num_epochs: int = 1, lr: float = 5e-3,
                  weight_decay: float = 0.01, clip_grad_norm: float = 0.1, eval_interval: int = 1, save_path: str = None, normalize_density: bool = True,
                  flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = None, log=print,
-                 train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None):
+                 train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None, layer_decay: float = None, no_decay: bool = False, freeze=()):
         from . import data
         from .heads import SwinTransformer_VoxelSemantics_Pretrained_Skip, SwinTransformer_VoxelSR_Pretrained_Skip
         if isinstance(model, SwinTransformer_VoxelSemantics_Pretrained_Skip):
@@ -1266,7 +1317,7 @@ class VoxelTrainer(_FinetuneTrainer):
                               num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
                               rot_scale_prob=rot_scale_prob),
                          batch_size, num_epochs, schedule_epochs or num_epochs, lr, weight_decay, clip_grad_norm, eval_interval, save_path, log, seed, rank, world,
-                         reducer)
+                         reducer, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze)
         self.best_metric = None
 
     def _loss(self, meshes, tb):

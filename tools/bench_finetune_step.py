@@ -5,7 +5,13 @@ Two paths over models with the same weights and the same fixed batch, alternated
   stock   the same forward and backward, then torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW over the separate tensors and a zero_grad fill
           (the only way to train the detector before finetune.py existed)
 HIP events around forward, backward and optimizer (the stock path's zero fill counts as optimizer time); 10 warm-up steps, --steps (default 50, at least 50)
-timed steps per path.  Prints the median and mean of each part in ms and one JSON line.  Nothing is asserted on the times."""
+timed steps per path.  Prints the median and mean of each part in ms and one JSON line.  Nothing is asserted on the times.
+
+Then the optimizer alone over the fused path's flat buffers, two rows from the same run, alternated launch by launch:
+  uniform  FusedAdamW.launch(): nmh_grad_sqnorm, nmh_clip_coef, nmh_adamw_step
+  ranged   the same under the layer-decay (0.75) + no-decay table of this model: nmh_grad_sqnorm_ranges, nmh_clip_coef, nmh_adamw_step_ranges
+HIP events around the norm launch, around the update launch and around all three; --opt-repeats (default 100) timed launches per row after 10 warm-up ones,
+each figure as median [min .. max].  --optimizer-only skips the step timing."""
 import argparse
 import json
 import os
@@ -50,10 +56,13 @@ def main():
     ap.add_argument("--resolution", type=int, default=160)
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--backbone", default="swin_s")
+    ap.add_argument("--opt-repeats", type=int, default=100)
+    ap.add_argument("--optimizer-only", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_finetune_step needs an MI355X (no CPU fallback)")
-    from nerf_mae_amd.finetune import FinetuneStep, FlatParameters, fcos_loss_fn
+    from nerf_mae_amd import ops
+    from nerf_mae_amd.finetune import FinetuneStep, FlatParameters, fcos_loss_fn, param_ranges, recipe_rules
     from nerf_mae_amd.trainer import FusedAdamW
     A = build(args)
     B = build(args)
@@ -93,23 +102,73 @@ def main():
         e[3].record()
         return e
 
-    for _ in range(args.warmup):
-        fused()
-        stock()
-    torch.cuda.synchronize()
     rec = {"fused": [], "stock": []}
-    for _ in range(max(args.steps, 1)):
-        rec["fused"].append(fused())
-        rec["stock"].append(stock())
-    torch.cuda.synchronize()
+    if not args.optimizer_only:
+        for _ in range(args.warmup):
+            fused()
+            stock()
+        torch.cuda.synchronize()
+        for _ in range(max(args.steps, 1)):
+            rec["fused"].append(fused())
+            rec["stock"].append(stock())
+        torch.cuda.synchronize()
     result = {"metric": "fcos_finetune_step_ms", "backbone": args.backbone, "resolution": args.resolution, "batch": args.batch, "dtype": "bf16", "steps": args.steps,
               "warmup": args.warmup, "tensors": len([p for p in A.parameters() if p.requires_grad]), "elements": int(flat._flat.numel())}
     for name, runs in rec.items():
+        if not runs:
+            continue
         parts = {"forward": [e[0].elapsed_time(e[1]) for e in runs], "backward": [e[1].elapsed_time(e[2]) for e in runs],
                  "optimizer": [e[2].elapsed_time(e[3]) for e in runs], "step": [e[0].elapsed_time(e[3]) for e in runs]}
         result[name] = {k: {"median": round(statistics.median(v), 3), "mean": round(statistics.fmean(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
                         for k, v in parts.items()}
         print(f"{name:5s} " + "  ".join(f"{k} {result[name][k]['median']:.3f} ms (mean {result[name][k]['mean']:.3f})" for k in parts))
+    # ---- the optimizer alone: one setting against the per-range table, over the same buffers --------------------------------------------------
+    table = param_ranges(flat, recipe_rules(A, layer_decay=0.75, no_decay=True))
+    ropt = FusedAdamW(flat, lr=1e-4, weight_decay=1e-2, max_grad_norm=0.1, ranges=table)
+    flat._flat_grad.normal_(0.0, 1e-3)                                # a gradient that stays: neither optimizer clears it here
+    for o in (fopt, ropt):
+        o.zero_grads_after_step = False
+        o.set_hyper(lr=1e-6)
+        o.update_hyper()
+    g, (bounds, scale) = flat._flat_grad, ropt.ranges
+
+    def opt_uniform():
+        e = [ev() for _ in range(4)]
+        e[0].record()
+        ops.grad_sqnorm(g, fopt.acc)
+        e[1].record()
+        ops.clip_coef(fopt.acc, 0.1, fopt.coef, fopt.norm)
+        e[2].record()
+        ops.adamw_step(flat._flat, g, fopt.m, fopt.v, fopt.hyper, fopt.coef)
+        e[3].record()
+        return e
+
+    def opt_ranged():
+        e = [ev() for _ in range(4)]
+        e[0].record()
+        ops.grad_sqnorm_ranges(g, bounds, scale, ropt.acc)
+        e[1].record()
+        ops.clip_coef(ropt.acc, 0.1, ropt.coef, ropt.norm)
+        e[2].record()
+        ops.adamw_step_ranges(flat._flat, g, ropt.m, ropt.v, ropt.hyper, bounds, scale, ropt.coef)
+        e[3].record()
+        return e
+
+    for _ in range(10):
+        opt_uniform()
+        opt_ranged()
+    torch.cuda.synchronize()
+    orec = {"uniform": [], "ranged": []}
+    for _ in range(max(args.opt_repeats, 1)):
+        orec["uniform"].append(opt_uniform())
+        orec["ranged"].append(opt_ranged())
+    torch.cuda.synchronize()
+    result["optimizer_rows"] = {"ranges": len(table.record["scale"]), "repeats": args.opt_repeats, "bytes_per_launch_set": 8 * 4 * int(flat._flat.numel())}
+    print(f"optimizer alone over {flat._flat.numel()} elements, {len(table.record['scale'])} ranges, {args.opt_repeats} launches each, ms as median [min .. max]:")
+    for name, runs in orec.items():
+        parts = {"norm": [e[0].elapsed_time(e[1]) for e in runs], "update": [e[2].elapsed_time(e[3]) for e in runs], "three": [e[0].elapsed_time(e[3]) for e in runs]}
+        result["optimizer_rows"][name] = {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)} for k, v in parts.items()}
+        print(f"{name:8s} " + "  ".join(f"{k} {statistics.median(v):.4f} [{min(v):.4f} .. {max(v):.4f}]" for k, v in parts.items()))
     print(json.dumps(result))
 
 
