@@ -313,6 +313,28 @@ NMH_API int nmh_patch_embed_norm_fwd_kept(int dt, const void* y0, void* tok, con
 NMH_API int nmh_patch_embed_norm_bwd_kept(int dt, const void* dtok, const void* y0, const float* gamma, const float* mean, const float* rstd, void* dy0, float* dgamma, float* dbeta,
                                           int64_t rows, int C, const unsigned char* mask, float* dmask_token, int64_t tokens_per_sample, const int* rowmap, int64_t cap_rows,
                                           void* stream);
+/* Stage 0's first Swin block on the KEPT windows only.  With a mask that is constant on every 4x4x4 window of a g^3 token grid (g % 4 == 0) every removed window
+ * enters the shift-0 block as 64 rows of mask_token (no position), so all removed windows of a sample leave it with the same 64 rows.  Compact layout
+ * [B][cap_windows + 1][64][C]: slot k < cap_windows = the k-th kept window in raster order of windows (rows in the window's own (dz, dy, dx) order, zero rows behind
+ * the kept count), slot cap_windows = 64 rows of mask_token, the representative of every removed window of the sample.  C % 8 == 0, C <= 128 (nmh_block0_supported).
+ * nmh_block0_window_rows: mask [g^3] -> rowmap [g^3 + 2] with the meaning of nmh_patch_embed_kept_rows' but in window-major order (row = 64 slot + position;
+ *   rowmap[g^3] = 64 x kept windows, rowmap[g^3 + 1] = 1 if they did not fit), and wmap [nW + cap_windows], nW = (g / 4)^3: wmap[w] = slot of window w or -1,
+ *   wmap[nW + k] = window of slot k or -1.  The gather, GEMM and weight gradient of the patch embed take rowmap with cap_rows = 64 (cap_windows + 1).
+ * nmh_block0_embed_norm_fwd: LayerNorm + pos_embed of y0 [B][cap_windows + 1][64][C] on the kept rows (the arithmetic of nmh_layernorm_fwd), zero rows behind the
+ *   count, mask_token in the representative rows; mean / rstd per compact row.
+ * nmh_block0_embed_norm_bwd: its backward from the compact input gradient of the block; dy0 is zero outside the kept rows; dgamma / dbeta / dmask_token (the column
+ *   sum of the representative rows) += sums taken in a fixed order through partials (>= 256 * 3 C floats), no float atomics.
+ * nmh_block0_expand: compact block output -> dense [B][g^3][C]; every removed window receives the representative window's rows (exact copy).
+ * nmh_block0_reduce: dense gradient [B][g^3][C] -> compact: kept windows copied, representative row i = the fp32 sum of row i of every removed window of the sample
+ *   (16 contiguous segments of the window range in ascending order, then the 16 partial sums in ascending order), rounded once; windows behind the count zero. */
+NMH_API int nmh_block0_supported(int C);
+NMH_API int nmh_block0_window_rows(const unsigned char* mask, int g, int cap_windows, int* rowmap, int* wmap, void* stream);
+NMH_API int nmh_block0_embed_norm_fwd(int dt, const void* y0, void* out, const float* gamma, const float* beta, float eps, float* mean, float* rstd, const float* pos,
+                                      const float* mask_token, const int* wmap, int B, int g, int cap_windows, int C, void* stream);
+NMH_API int nmh_block0_embed_norm_bwd(int dt, const void* dx0, const void* y0, const float* gamma, const float* mean, const float* rstd, void* dy0, float* dgamma, float* dbeta,
+                                      float* dmask_token, float* partials, int64_t partial_floats, const int* wmap, int B, int g, int cap_windows, int C, void* stream);
+NMH_API int nmh_block0_expand(int dt, const void* yc, void* y, const int* wmap, int B, int g, int cap_windows, int C, void* stream);
+NMH_API int nmh_block0_reduce(int dt, const void* dy, void* dyc, const int* wmap, int B, int g, int cap_windows, int C, void* stream);
 /* ConvTranspose3d(kernel = stride = k) (unetr_block.py:151-158,193-198) as GEMMs with the pixel shuffle folded into the addressing,
  * channels-last.  x [B*v^3][Cin] coarse grid; cat/dcat [B*(v*k)^3][ldc] fine grid, the transpose conv occupies columns [0,Cout)
  * (the skip connection, if any, the rest).  Wt packed [(tap,co)][ci], Wd packed [ci][(tap,co)], dW fp32 [Cin][Cout][k^3]. */

@@ -448,6 +448,34 @@ int nmh_patch_embed_norm_bwd_kept(int dt, const void* dtok, const void* y0, cons
               rowmap, (long)cap_rows};
   return k_ln_bwd(a, ST);
 }
+int nmh_block0_supported(int C) { return k_b0_supported(C); }
+int nmh_block0_window_rows(const unsigned char* mask, int g, int cap_windows, int* rowmap, int* wmap, void* stream) {
+  CLR();
+  REQ(mask, rowmap, wmap);
+  return k_b0_rowmap(mask, g, cap_windows, rowmap, wmap, ST);
+}
+int nmh_block0_embed_norm_fwd(int dt, const void* y0, void* out, const float* gamma, const float* beta, float eps, float* mean, float* rstd, const float* pos,
+                              const float* mask_token, const int* wmap, int B, int g, int cap_windows, int C, void* stream) {
+  CLR();
+  REQ(y0, out, gamma, beta, mean, rstd, mask_token, wmap);
+  return k_b0_ln_fwd(dt, y0, out, gamma, beta, eps, mean, rstd, pos, mask_token, wmap, B, g, cap_windows, C, ST);
+}
+int nmh_block0_embed_norm_bwd(int dt, const void* dx0, const void* y0, const float* gamma, const float* mean, const float* rstd, void* dy0, float* dgamma, float* dbeta,
+                              float* dmask_token, float* partials, int64_t partial_floats, const int* wmap, int B, int g, int cap_windows, int C, void* stream) {
+  CLR();
+  REQ(dx0, y0, gamma, mean, rstd, dy0, dgamma, dbeta, dmask_token, partials, wmap);
+  return k_b0_ln_bwd(dt, dx0, y0, gamma, mean, rstd, dy0, dgamma, dbeta, dmask_token, partials, (long)partial_floats, wmap, B, g, cap_windows, C, ST);
+}
+int nmh_block0_expand(int dt, const void* yc, void* y, const int* wmap, int B, int g, int cap_windows, int C, void* stream) {
+  CLR();
+  REQ(yc, y, wmap);
+  return k_b0_expand(dt, yc, y, wmap, B, g, cap_windows, C, ST);
+}
+int nmh_block0_reduce(int dt, const void* dy, void* dyc, const int* wmap, int B, int g, int cap_windows, int C, void* stream) {
+  CLR();
+  REQ(dy, dyc, wmap);
+  return k_b0_reduce(dt, dy, dyc, wmap, B, g, cap_windows, C, ST);
+}
 int nmh_upconv_shuffle_fwd(int dt, const void* upre, const float* bias, const void* skip, void* out, int B, int v, int k, int Cout, void* stream) {
   CLR();
   return k_up_cat_fwd(dt, upre, bias, skip, out, B, v, k, Cout, ST);

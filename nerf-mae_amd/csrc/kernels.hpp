@@ -175,6 +175,19 @@ struct LnReduceItem { const float* part; float* dgamma; float* dbeta; long nb; i
 constexpr int LN_REDUCE_MAX = 96;
 int k_ln_param_reduce(const LnReduceItem* items, int n, hipStream_t st);
 
+// ---- block0.hip: stage 0's first Swin block on the kept windows only, compact layout [B][capW + 1][64][C] (slot capW = the representative all-mask window) ----
+constexpr int B0_LN_BWD_BLOCKS = 256;   // workgroups (at most) of k_b0_ln_bwd: part holds B0_LN_BWD_BLOCKS * 3 C floats
+int k_b0_supported(int C);
+// mask [g^3] (1 = removed, constant on every 4^3 window) -> rowmap [g^3 + 2] as k_mask_rowmap's, the rows in window-major order (64 * slot + in-window position);
+// wmap [nW + capW]: wmap[w] = slot of window w (-1: removed), wmap[nW + k] = window of slot k (-1: behind the kept count)
+int k_b0_rowmap(const unsigned char* mask, int g, int capW, int* rowmap, int* wmap, hipStream_t st);
+int k_b0_ln_fwd(int dt, const void* y0, void* out, const float* gamma, const float* beta, float eps, float* mean, float* rstd, const float* pos, const float* mask_token,
+                const int* wmap, int B, int g, int capW, int C, hipStream_t st);
+int k_b0_ln_bwd(int dt, const void* dx0, const void* y0, const float* gamma, const float* mean, const float* rstd, void* dy0, float* dgamma, float* dbeta, float* dmask_token,
+                float* part, long part_floats, const int* wmap, int B, int g, int capW, int C, hipStream_t st);
+int k_b0_expand(int dt, const void* yc, void* y, const int* wmap, int B, int g, int capW, int C, hipStream_t st);
+int k_b0_reduce(int dt, const void* dy, void* dyc, const int* wmap, int B, int g, int capW, int C, hipStream_t st);
+
 int k_window_scatter_residual(int dt, const void* yw, const void* x, void* out, const float* rowscale, int C, const WinMap& wm, hipStream_t st);
 int k_window_gather_scale(int dt, const void* dx, void* dyw, const float* rowscale, int C, const WinMap& wm, hipStream_t st);
 

@@ -72,6 +72,17 @@ def embed_capacity_rows(g: int, kept: Optional[int] = None, p_remove: Optional[f
     return int(min(tps, max(64, -(-kept // 64) * 64)))
 
 
+def mask_window_aligned(mask, ws: int = WS) -> bool:
+    """True if the (g,g,g) token mask is constant on every ws^3 window of the unshifted partition and g is a multiple of ws: the condition under which stage 0's
+    first block runs on the kept windows only (ops.BLOCK0_KEPT).  Tested on the host, where the mask is drawn."""
+    m = np.asarray(mask, dtype=np.uint8)
+    if m.ndim != 3 or len(set(m.shape)) != 1 or m.shape[0] == 0 or m.shape[0] % ws:
+        return False
+    nw = m.shape[0] // ws
+    v = (m != 0).reshape(nw, ws, nw, ws, nw, ws)
+    return bool((v == v[:, :1, :, :1, :, :1]).all())
+
+
 def draw_block_bits(g: Sequence[int], p_remove: float, block: int = 4, rng=random) -> np.ndarray:
     """the draws of `draw_block_mask` only: uint8 array (nb0, nb1, nb2), 1 = block removed (same RNG stream, same order)"""
     nb = [max(0, (gi - block) // block + 1) for gi in g]
@@ -463,6 +474,24 @@ class _EmbedFn(torch.autograd.Function):
         use_mask = mask_dev is not None
         kept = use_mask and ops.EMBED_KEPT and m._add_pos
         cap = min(tps, int(m._embed_cap)) if (kept and m._embed_cap) else tps
+        m._b0 = None
+        if kept and m._block0_kept_ok(g):
+            # stage 0's first block runs on the kept windows + one representative all-mask window per sample: the patch embed's rows are that block's input rows,
+            # [B][capW + 1][64][.] (csrc/block0.hip); _run_stage expands the block's output to the dense token grid
+            capW = max(1, min(cap // 64, (g // 4) ** 3))
+            rowmap, wmap = ops.block0_window_rows(mask_dev, g, capW)
+            capR = 64 * (capW + 1)
+            A = torch.empty((B * capR, 256), dtype=dtype, device=xb.device)
+            ops.patch_embed_gather_kept(xb, A, B, R, rowmap, capR)
+            conv, ln = m.patch_partition[0], m.patch_partition[2]
+            y0 = ops.gemm_nt(A, m._pk["pe.w"].view(C, 256), bias=conv.bias)
+            tok = torch.empty((B * capR, C), dtype=dtype, device=xb.device)
+            mean, rstd = torch.empty(B * capR, device=xb.device), torch.empty(B * capR, device=xb.device)
+            ops.block0_embed_norm_fwd(y0, ln.weight, ln.bias, tok, mean, rstd, m.pos_embed.view(-1, C), m.mask_token, wmap, B, g, capW, C)
+            ctx.m, ctx.saved, ctx.dims, ctx.b0 = m, (A, y0, mean, rstd, mask_dev, rowmap), (T, C, g, capR), (wmap, B, capW)
+            m._b0 = (wmap, g, capW)
+            return tok
+        ctx.b0 = None
         rowmap = ops.embed_kept_rows(mask_dev, cap) if kept else None
         rows = B * cap if kept else T
         A = torch.empty((rows, 256), dtype=dtype, device=xb.device)
@@ -489,7 +518,10 @@ class _EmbedFn(torch.autograd.Function):
         T, C, g, cap = ctx.dims
         conv, ln = m.patch_partition[0], m.patch_partition[2]
         dy0 = torch.empty_like(y0)
-        if rowmap is not None:
+        if ctx.b0 is not None:   # dtok: the compact input gradient of stage 0's first block
+            wmap, B, capW = ctx.b0
+            ops.block0_embed_norm_bwd(dtok.contiguous(), y0, ln.weight, mean, rstd, dy0, _gradbuf(ln.weight), _gradbuf(ln.bias), _gradbuf(m.mask_token), wmap, B, g, capW, C)
+        elif rowmap is not None:
             ops.embed_norm_bwd_kept(dtok.contiguous(), y0, ln.weight, mean, rstd, dy0, _gradbuf(ln.weight), _gradbuf(ln.bias), T, C, mask_dev, _gradbuf(m.mask_token),
                                     g ** 3, rowmap, cap)
         else:
@@ -503,6 +535,22 @@ class _EmbedFn(torch.autograd.Function):
         else:
             ops.gemm_tn(dy0, A, _gradbuf(conv.weight), dbias=_gradbuf(conv.bias))
         return None, None, None, None
+
+
+class _Block0ExpandFn(torch.autograd.Function):
+    """compact output of stage 0's first block [B][capW + 1][64][C] -> the dense token grid [B g^3, C]: every removed window receives the rows of its sample's
+    representative window (bit-identical to what the block computes for it).  Backward: the kept windows' gradients are copied, the representative row i receives
+    the fp32 sum of row i of every removed window, in a fixed order (csrc/block0.hip)."""
+
+    @staticmethod
+    def forward(ctx, xc, wmap, B, g, capW):
+        ctx.args = (wmap, B, g, capW, xc.shape[-1])
+        return ops.block0_expand(xc.contiguous(), wmap, B, g, capW, xc.shape[-1])
+
+    @staticmethod
+    def backward(ctx, dy):
+        wmap, B, g, capW, C = ctx.args
+        return ops.block0_reduce(dy.contiguous(), wmap, B, g, capW, C), None, None, None, None
 
 
 class _BlockSaved(NamedTuple):
@@ -1149,6 +1197,24 @@ class SwinTransformer_MAE3D_New(nn.Module):
         self._anchor = None
         self._reducer = None  # dist.GradReducer when data-parallel
         self._embed_cap = None   # rows per sample of the compact patch embed of the kept tokens (_EmbedFn); None = every token has a row
+        # the caller that drew the mask found it constant on every 4^3 window (mask_window_aligned): stage 0's first block may run on the kept windows only
+        self._block0_aligned = False
+        self._b0 = None          # (wmap, g, capW) of the compact tokens the last _EmbedFn.forward returned; taken by _run_stage(0)
+
+    def _block0_kept_ok(self, g: int) -> bool:
+        """the conditions of the kept-window path of stage 0's first block other than those of the compact patch embed (ops.BLOCK0_KEPT)"""
+        b0 = self.stages[0][0] if len(self.stages) and len(self.stages[0]) else None
+        return bool(ops.BLOCK0_KEPT and self._block0_aligned and g % 4 == 0 and isinstance(b0, SwinBlock3D) and not any(b0.shift_size)
+                    and ops.block0_supported(self.embed_dim))
+
+    def _embed(self, xb: Tensor, mask_dev: Tensor) -> Tensor:
+        """patch embed of a masked batch -> the input of stage 0: the dense token grid (B,g,g,g,C), or -- kept-window path -- the compact rows as the grid
+        (B, 4 (capW + 1), 4, 4, C) whose token order is its window order (self._b0 is set then)"""
+        B, g = xb.shape[0], xb.shape[2] // 4
+        tok = _EmbedFn.apply(self._anchor, self, xb, mask_dev)
+        if self._b0 is not None:
+            return tok.view(B, 4 * (self._b0[2] + 1), 4, 4, self.embed_dim)
+        return tok.view(B, g, g, g, self.embed_dim)
 
     # ---- flat buffers + packed weights ------------------------------------------------------------
     def _trainable(self):
@@ -1328,6 +1394,7 @@ class SwinTransformer_MAE3D_New(nn.Module):
             self._packer.wait_late()
         q = wgrad_queue_for(self, self.compute_dtype) if torch.is_grad_enabled() and x.requires_grad else None
         groups = red.chunk_groups if (red is not None and si == getattr(red, "chunk_stage", -1) and red.chunk_groups) else [list(self.stages[si])]
+        b0, self._b0 = (self._b0 if si == 0 else None), None   # x holds compact rows (_embed): the first block runs on them, its output is expanded
         for k, grp in enumerate(groups):
             if red is not None:
                 x = red.trigger(x, red.seg_stage(si, k))  # backward reaching here => this range's gradients are complete
@@ -1337,6 +1404,9 @@ class SwinTransformer_MAE3D_New(nn.Module):
                 if isinstance(mod, SwinBlock3D):
                     x = mod(x, None if sd_noise is None else sd_noise[bi])
                     bi += 1
+                    if b0 is not None:
+                        (wmap, g, capW), b0 = b0, None
+                        x = _Block0ExpandFn.apply(x.reshape(-1, x.shape[-1]), wmap, x.shape[0], g, capW).view(x.shape[0], g, g, g, x.shape[-1])
                 else:
                     x = mod(x)
         return x, bi
@@ -1394,10 +1464,11 @@ class SwinTransformer_MAE3D_New(nn.Module):
         mask_dev = block_mask.to(torch.uint8).contiguous().view(-1).to(device, non_blocking=True)
         # the mask was drawn on the host: the compact patch embed gets exactly the rows it needs (64-row granules)
         cap_was, self._embed_cap = self._embed_cap, embed_capacity_rows(g, kept=int(g ** 3 - int(block_mask.to(torch.int64).sum())))
+        al_was, self._block0_aligned = self._block0_aligned, ops.BLOCK0_KEPT and mask_window_aligned(block_mask.cpu().numpy())
         try:
-            tok = _EmbedFn.apply(self._anchor, self, xb, mask_dev).view(B, g, g, g, self.embed_dim)
+            tok = self._embed(xb, mask_dev)
         finally:
-            self._embed_cap = cap_was
+            self._embed_cap, self._block0_aligned = cap_was, al_was
         feats = self.forward_encoder(tok, sd_noise)
         want_pred = is_eval or return_pred
         pred = torch.empty((B, 4, R, R, R), device=device) if want_pred else None
@@ -1417,7 +1488,7 @@ class SwinTransformer_MAE3D_New(nn.Module):
         B, R = xb.shape[0], self.resolution
         g = R // 4
         self._packer.run()
-        tok = _EmbedFn.apply(self._anchor, self, xb, mask_dev).view(B, g, g, g, self.embed_dim)
+        tok = self._embed(xb, mask_dev)   # (the caller answers for self._embed_cap and self._block0_aligned: it draws the masks)
         losses = self._decode_and_loss(self.forward_encoder(tok), xb, ext, mask_dev, None)
         return losses[0], losses[1], losses[2]
 

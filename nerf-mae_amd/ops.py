@@ -737,6 +737,63 @@ def embed_norm_bwd_kept(dtok, y0, gamma, mean, rstd, dy0, dgamma, dbeta, rows, C
     return dy0
 
 
+# stage 0's first Swin block on the kept windows plus one representative all-mask window per sample (csrc/block0.hip; model._EmbedFn / _Block0ExpandFn)
+BLOCK0_KEPT = __import__("os").environ.get("NMH_BLOCK0_KEPT", "1") != "0"
+BLOCK0_LN_PARTIAL_ROWS = 256   # csrc/kernels.hpp: B0_LN_BWD_BLOCKS
+
+
+def block0_supported(C: int) -> bool:
+    return bool(lib().call("nmh_block0_supported", C))
+
+
+def block0_window_rows(mask, g, cap_windows):
+    """token mask [g^3] uint8 (1 = removed, constant on every 4^3 window) -> (rowmap int32 [g^3 + 2] in window-major order, wmap int32 [nW + cap_windows])
+    (include/nerfmae_hip.h: nmh_block0_window_rows)"""
+    _chk(mask)
+    n = g ** 3
+    if mask.numel() != n or g % 4:
+        raise RuntimeError("block0_window_rows: mask must hold g^3 tokens, g a multiple of 4")
+    rowmap = torch.empty(n + 2, dtype=torch.int32, device=mask.device)
+    wmap = torch.empty((g // 4) ** 3 + int(cap_windows), dtype=torch.int32, device=mask.device)
+    lib().call("nmh_block0_window_rows", mask, g, int(cap_windows), rowmap, wmap, _st())
+    return rowmap, wmap
+
+
+def block0_embed_norm_fwd(y0, gamma, beta, out, mean, rstd, pos, mask_token, wmap, B, g, cap_windows, C, eps=1e-5):
+    _chk(y0, gamma, beta, out, mean, rstd, pos, mask_token, wmap)
+    lib().call("nmh_block0_embed_norm_fwd", dt_of(y0), y0, out, gamma, beta, eps, mean, rstd, pos, mask_token, wmap, B, g, int(cap_windows), C, _st())
+    return out
+
+
+def block0_embed_norm_bwd(dx0, y0, gamma, mean, rstd, dy0, dgamma, dbeta, dmask_token, wmap, B, g, cap_windows, C):
+    _chk(dx0, y0, gamma, mean, rstd, dy0, dgamma, dbeta, dmask_token, wmap)
+    part = torch.empty((BLOCK0_LN_PARTIAL_ROWS, 3 * C), dtype=torch.float32, device=y0.device)
+    lib().call("nmh_block0_embed_norm_bwd", dt_of(y0), dx0, y0, gamma, mean, rstd, dy0, dgamma, dbeta, dmask_token, part, part.numel(), wmap, B, g, int(cap_windows), C, _st())
+    return dy0
+
+
+def block0_expand(yc, wmap, B, g, cap_windows, C, out=None):
+    """compact [B][cap_windows + 1][64][C] -> dense [B * g^3, C]"""
+    _chk(yc, wmap, out)
+    if yc.numel() != B * (cap_windows + 1) * 64 * C:
+        raise RuntimeError("block0_expand: compact tensor must be [B][cap_windows + 1][64][C]")
+    if out is None:
+        out = torch.empty((B * g ** 3, C), dtype=yc.dtype, device=yc.device)
+    lib().call("nmh_block0_expand", dt_of(yc), yc, out, wmap, B, g, int(cap_windows), C, _st())
+    return out
+
+
+def block0_reduce(dy, wmap, B, g, cap_windows, C, out=None):
+    """dense gradient [B * g^3, C] -> compact [B * (cap_windows + 1) * 64, C]"""
+    _chk(dy, wmap, out)
+    if dy.numel() != B * g ** 3 * C:
+        raise RuntimeError("block0_reduce: dense tensor must be [B][g^3][C]")
+    if out is None:
+        out = torch.empty((B * (cap_windows + 1) * 64, C), dtype=dy.dtype, device=dy.device)
+    lib().call("nmh_block0_reduce", dt_of(dy), dy, out, wmap, B, g, int(cap_windows), C, _st())
+    return out
+
+
 def layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, src_mode=0, geom: Optional[WinGeom] = None, dres=None,
                   mask=None, dmask_token=None, tokens_per_sample=1, dyw=None, dyw_scale=None, wq=None):
     """dyw (mode 0, with geom): second output = dx in window order times dyw_scale[sample] (fused window gather).

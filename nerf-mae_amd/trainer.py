@@ -163,6 +163,9 @@ class GraphedTrainStep:
         # against it in __call__ (a mask that keeps more tokens re-captures the step with a row for every token)
         from .model import embed_capacity_rows
         self._embed_cap = embed_capacity_rows(g, p_remove=model.masking_prob)
+        # stage 0's first block on the kept windows only (ops.BLOCK0_KEPT): captured for masks that are constant on every 4^3 window, as the block masks are;
+        # every mask is checked in __call__ (one that is not re-captures the step with the dense block)
+        self._block0 = bool(ops.BLOCK0_KEPT and g % 4 == 0)
         self.losses = None
         self._ext_host = None
         self._g1 = self._g2 = None
@@ -194,10 +197,11 @@ class GraphedTrainStep:
 
     def _capture(self):
         cap_was, self.model._embed_cap = self.model._embed_cap, self._embed_cap
+        al_was, self.model._block0_aligned = self.model._block0_aligned, self._block0
         try:
             self._capture_graphs()
         finally:
-            self.model._embed_cap = cap_was
+            self.model._embed_cap, self.model._block0_aligned = cap_was, al_was
 
     def _capture_graphs(self):
         import os
@@ -285,14 +289,14 @@ class GraphedTrainStep:
     def _split_a(self, zero=True):
         """forward + decoder backward.  The encoder features enter the decoder (and every later piece enters the next) through detached
         leaves, so each piece is its own autograd graph whose incoming gradients are the `.grad` of those leaves."""
-        from .model import _EmbedFn, _StageFlushFn, SwinBlock3D, wgrad_queue_for
+        from .model import _StageFlushFn, SwinBlock3D, wgrad_queue_for
         m = self.model
         if zero:
             m.zero_grad()
         B, R = self.x.shape[0], m.resolution
         g = R // 4
         m._packer.run(late_split=False)   # the stages are captured into separate graphs
-        tok = _EmbedFn.apply(m._anchor, m, self.x, self.mask).view(B, g, g, g, m.embed_dim)
+        tok = m._embed(self.x, self.mask)
         sd = m._draw_sd_noise(B, tok.device)
         m._wq.sync_after_flush = False
         f0, bi = m._run_stage(0, tok, sd, 0)
@@ -381,6 +385,12 @@ class GraphedTrainStep:
                     self._pin_mask = PinnedRing((self.mask.numel(),), torch.uint8)
                 self._pin_mask.upload(torch.from_numpy(full), self.mask)
                 bits = None
+        if block_mask is not None and self._block0:
+            from .model import mask_window_aligned
+            if not (bits is not None and np.asarray(bits).shape[0] * 4 == g) and not mask_window_aligned(np.asarray(block_mask)):
+                self._block0 = False   # a mask that cuts through 4^3 windows: the step is captured again with the dense first block, as on a capacity overflow
+                torch.cuda.synchronize()
+                self._capture()
         if block_mask is not None and self._embed_cap < g ** 3:
             kept = g ** 3 - (64 * int(np.asarray(bits).sum()) if bits is not None else int(np.asarray(block_mask).sum()))
             if kept > self._embed_cap:   # (eight standard deviations above the mean kept count: not expected to happen in a training run)
