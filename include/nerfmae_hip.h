@@ -770,6 +770,16 @@ NMH_API int nmh_pack_weights(int dt, const void* descs_dev, const int* blk2desc_
 NMH_API int nmh_grad_sqnorm(const float* g, int64_t n, double* acc, void* stream);
 NMH_API int nmh_clip_coef(const double* acc, float max_norm, float* coef, float* norm_out, void* stream);
 NMH_API int nmh_adamw_step(float* p, float* g, float* m, float* v, int64_t n, const float* hyper, const float* coef, void* stream);
+/* Gradient accumulation: k micro-batches per optimizer step, each weighted 1/k as DDP weights its ranks (run_swin_mae3d.py:355-357, 665-669).
+ * g holds the SUM G of the k micro-gradients (every weight-gradient kernel adds into it; zero_g of the previous step cleared it) and acc = |G|^2 from
+ * nmh_grad_sqnorm or nmh_grad_sqnorm_ranges.  nmh_clip_coef_mean in the place of nmh_clip_coef: with inv_k = *inv_k_dev (device fp32, 1/k),
+ *   nrm = sqrt(acc) * inv_k;  coef = inv_k * min(1, max_norm / (nrm + 1e-6))  (coef = inv_k with max_norm <= 0);  norm_out = nrm,
+ * the norm of the mean gradient, what clip_grad_norm_ reports after DDP; the AdamW entries, which multiply g by coef, then step on the clipped mean.
+ * Evaluated in fp64 and rounded once; with *inv_k_dev == 1 coef and norm_out are the bits of nmh_clip_coef.
+ * nmh_grad_scale stores inv_k (in (0, 1], else -4) into inv_k_dev as the kernel argument of a one-thread launch, as nmh_step_params stores hyper: no copy,
+ * no host wait, and the value may change between replays of a captured optimizer graph (the ragged last step of an epoch). */
+NMH_API int nmh_clip_coef_mean(const double* acc, float max_norm, const float* inv_k_dev, float* coef, float* norm_out, void* stream);
+NMH_API int nmh_grad_scale(float inv_k, float* inv_k_dev, void* stream);
 /* The same two passes with per-range settings over the flat buffer (one optimizer param group per range: layer-wise learning-rate decay,
  * no-decay sets, frozen ranges).  The table is on the device: bounds int64 [R+1] with 0 = bounds[0] < bounds[1] < ... < bounds[R] = n and
  * every interior boundary a multiple of 4 (a 16-byte group lies in one range); scale float [R][2] = (lr_scale, wd_scale), finite and >= 0.

@@ -1124,6 +1124,16 @@ int nmh_det_eval_pr(int64_t M, const unsigned char* bits, const int* n_det, cons
 }
 int nmh_clip_coef(const double* acc, float max_norm, float* coef, float* norm_out, void* stream) {
   CLR(); return k_clip_coef(acc, max_norm, coef, norm_out, ST); }
+int nmh_clip_coef_mean(const double* acc, float max_norm, const float* inv_k_dev, float* coef, float* norm_out, void* stream) {
+  CLR();
+  REQ(acc, inv_k_dev, coef);
+  return k_clip_coef_mean(acc, max_norm, inv_k_dev, coef, norm_out, ST);
+}
+int nmh_grad_scale(float inv_k, float* inv_k_dev, void* stream) {
+  CLR();
+  REQ(inv_k_dev);
+  return k_grad_scale(inv_k, inv_k_dev, ST);
+}
 int nmh_adamw_step(float* p, float* g, float* m, float* v, int64_t n, const float* hyper, const float* coef, void* stream) {
   CLR(); return k_adamw(p, g, m, v, (long)n, hyper, coef, ST); }
 int nmh_grad_sqnorm_ranges(const float* g, int64_t n, const int64_t* bounds, const float* scale, int R, double* acc, void* stream) {

@@ -456,6 +456,9 @@ struct PackDesc { const float* src; void* dst; int mode; int d0, d1, d2; long n;
 int k_pack_weights(int dt, const PackDesc* descs_dev, const int* blk2desc_dev, const long* blkstart_dev, int nblocks, hipStream_t st);
 int k_sqnorm(const float* g, long n, double* acc, hipStream_t st);
 int k_clip_coef(const double* acc, float max_norm, float* coef, float* norm_out, hipStream_t st);
+// gradient accumulation: the clip of the mean of k micro-gradients from the squared norm of their sum (inv_k: device scalar 1 / k, set by k_grad_scale)
+int k_clip_coef_mean(const double* acc, float max_norm, const float* inv_k, float* coef, float* norm_out, hipStream_t st);
+int k_grad_scale(float inv_k, float* inv_k_dev, hipStream_t st);
 int k_adamw(float* p, float* g, float* m, float* v, long n, const float* hyper /*lr,b1,b2,eps,wd,bc1,bc2,zero_g*/, const float* coef, hipStream_t st);
 // the two passes under a range table: bounds[R+1] (device int64), scale[R][2] = (lr_scale, wd_scale); -5 for a table the host check refuses (misc.hip)
 int k_sqnorm_ranges(const float* g, long n, const long* bounds, const float* scale, int R, double* acc, hipStream_t st);

@@ -711,6 +711,29 @@ int k_clip_coef(const double* acc, float max_norm, float* coef, float* norm_out,
   NMH_CHECK_LAUNCH();
   return 0;
 }
+// Gradient accumulation: g holds the SUM G of k micro-gradients, acc = |G|^2.  The step is taken on the mean G / k: its norm is |G| / k, and the factor the AdamW
+// kernels multiply g by is the clip coefficient of the mean times 1 / k.  The factors are multiplied in fp64 and rounded once; with *inv_k == 1 every product is
+// exact, so coef and norm_out are the bits of clip_coef_kernel.
+__global__ void clip_coef_mean_kernel(const double* acc, float max_norm, const float* inv_k, float* coef, float* norm_out) {
+  const double ik = (double)*inv_k;
+  double nrm = sqrt(*acc) * ik;
+  double c = (double)max_norm / (nrm + 1e-6);
+  *coef = (float)(ik * (max_norm > 0.f ? (c < 1.0 ? c : 1.0) : 1.0));
+  if (norm_out) *norm_out = (float)nrm;
+}
+int k_clip_coef_mean(const double* acc, float max_norm, const float* inv_k, float* coef, float* norm_out, hipStream_t st) {
+  hipLaunchKernelGGL(clip_coef_mean_kernel, dim3(1), dim3(1), 0, st, acc, max_norm, inv_k, coef, norm_out);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
+// 1 / k of the step as a kernel argument (see step_params_kernel: no host-to-device copy); the value may change between replays of a captured optimizer graph
+__global__ void grad_scale_kernel(float inv_k, float* __restrict__ inv_k_dev) { *inv_k_dev = inv_k; }
+int k_grad_scale(float inv_k, float* inv_k_dev, hipStream_t st) {
+  if (!(inv_k > 0.f) || inv_k > 1.f) return -4;      // 1 / k of k >= 1 micro-batches (NaN fails the first test)
+  hipLaunchKernelGGL(grad_scale_kernel, dim3(1), dim3(1), 0, st, inv_k, inv_k_dev);
+  NMH_CHECK_LAUNCH();
+  return 0;
+}
 // one element's decoupled-weight-decay Adam update, shared by adamw_kernel and adamw_ranges_kernel (step = lr / bias_correction1, isq = 1 / sqrt(bias_correction2)):
 //   m = b1 m + (1 - b1) gc;  v = b2 v + (1 - b2) gc^2;  p = p (1 - lr wd) - step m / (sqrt(v) isq + eps),   gc = g * coef.
 // The fused multiply-adds are spelled out and the compiler's own contraction is off inside: every caller then rounds alike, whatever surrounds the inlined

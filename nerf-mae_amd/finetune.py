@@ -368,6 +368,7 @@ class FinetuneStep:
     the optimizer's three launches.  The AdamW kernel clears the gradient buffer (opt.zero_grads_after_step), so no step starts with a zero fill; the buffer is
     cleared once here.  Returns the UNWEIGHTED losses as detached device tensors (a bare tensor under the key "loss"); nothing waits for the host.
     Set the step's learning rate and beta1 with opt.set_hyper() before the call.
+    Gradient accumulation: accumulate(*batch) for all micro-batches of a step but the last, then __call__ with the last.
 
     reducer: a dist.FlatGradReducer over the same FlatParameters.  When it is active (more than one rank, or NMH_DP_FORCE=1) the base gets it as its _reducer,
     so the forward places the segment triggers, and reducer.finish() runs between backward and the update: every rank then steps on the mean gradient.  With
@@ -386,6 +387,7 @@ class FinetuneStep:
             flat_params.base._reducer = self.reducer
         opt.zero_grads_after_step = True
         flat_params.zero_grad()
+        self._held, self.last = [], None     # the losses of the accumulate() calls since the last step; the last step's own batch's losses
 
     def forward(self, *batch):
         """check() + forward -> (the loss dict as loss_fn returned it, the weighted total); __call__ without the backward and the update (tools/bench_finetune_step.py
@@ -400,11 +402,37 @@ class FinetuneStep:
             total = t if total is None else total + t
         return losses, total
 
+    def accumulate(self, *batch):
+        """a micro-batch of the coming optimizer step: check(), forward and backward only -- the gradients add to the buffer's (every weight-gradient kernel adds,
+        and the AdamW kernel of the step before cleared it).  With a reducer the base's _reducer is taken away for the call, so no trigger issues a collective: the
+        step's one exchange is __call__'s.  Returns the unweighted detached losses.  From the first call on the optimizer clips the mean of the accumulated sum
+        (FusedAdamW.mean_clip), which for a step of one batch is the clip of before, bit for bit."""
+        self.opt.mean_clip = True
+        base = self.flat.base if self.reducer is not None else None
+        if base is not None:
+            base._reducer = None
+        try:
+            losses, total = self.forward(*batch)
+            total.backward()
+        finally:
+            if base is not None:
+                base._reducer = self.reducer
+        self._held.append({k: v.detach() for k, v in losses.items()})
+        return self._held[-1]
+
     def __call__(self, *batch):
+        """the optimizer step.  After j calls of accumulate() since the last step: the mean of the j + 1 gradients is clipped and stepped, each weighing 1 / (j + 1)
+        whatever its batch size (as DDP weighs ranks), exchanged once, and the mean of the j + 1 loss dicts is returned; `last` keeps this batch's own losses."""
         losses, total = self.forward(*batch)
         total.backward()
         # every gradient launch is ordered before this point on the current stream (module docstring): no join here
         if self.reducer is not None:
             self.reducer.finish()   # the ranges no trigger launched, then the join of the comm stream
+        if self.opt.mean_clip:
+            self.opt.set_grad_scale(1.0 / (len(self._held) + 1))
         self.opt.step()
-        return {k: v.detach() for k, v in losses.items()}
+        self.last = {k: v.detach() for k, v in losses.items()}
+        if not self._held:
+            return self.last
+        held, self._held = self._held + [self.last], []
+        return {k: sum(h[k] for h in held) / len(held) for k in self.last}

@@ -1432,6 +1432,18 @@ def clip_coef(acc, max_norm, coef, norm_out=None):
     lib().call("nmh_clip_coef", acc, max_norm, coef, norm_out, _st())
 
 
+def clip_coef_mean(acc, max_norm, inv_k_dev, coef, norm_out=None):
+    """clip_coef for a gradient buffer that holds the SUM of k micro-gradients: coef = inv_k * (clip coefficient of the mean), norm_out = the mean's norm"""
+    _chk(inv_k_dev, coef, norm_out)
+    lib().call("nmh_clip_coef_mean", acc, max_norm, inv_k_dev, coef, norm_out, _st())
+
+
+def grad_scale(inv_k, inv_k_dev):
+    """1 / k -> the device scalar clip_coef_mean reads, as a kernel argument (no copy, no host wait; not graph-capturable, like step_params)"""
+    _chk(inv_k_dev)
+    lib().call("nmh_grad_scale", float(inv_k), inv_k_dev, _st())
+
+
 def adamw_step(p, g, m, v, hyper, coef=None):
     lib().call("nmh_adamw_step", p, g, m, v, p.numel(), hyper, coef, _st())
 

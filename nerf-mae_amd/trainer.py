@@ -69,9 +69,16 @@ class FusedAdamW:
     """ranges: a finetune.param_ranges table over `model`'s flat layout, or None.  With a table the step runs the *_ranges kernels: range r steps with
     lr * lr_scale[r] and weight_decay * wd_scale[r], a range with lr_scale 0 is frozen (parameters and moments not written, outside the clip norm), and `norm` is
     the norm over the ranges that train.  The table is fixed here, on the device, so launch() stays graph-capturable; the scheduled lr of set_hyper() times the
-    fixed scale is what OneCycleLR does with a list of max_lr.  None: the one-setting kernels, exactly as without the keyword."""
+    fixed scale is what OneCycleLR does with a list of max_lr.  None: the one-setting kernels, exactly as without the keyword.
 
-    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3, max_grad_norm=0.1, ranges=None):
+    accumulate: k micro-batches per optimizer step.  With k > 1 -- asked for here, or by the step object that drives the optimizer
+    (GraphedTrainStep(accumulate=k), FinetuneStep.accumulate) -- the gradient buffer holds the SUM of the micro-gradients when launch() runs, and the middle launch
+    is ops.clip_coef_mean: clip and update act on the mean, weight `grad_scale` = 1 / (micro-batches of this step) each, set by set_grad_scale(); `norm` is the
+    mean gradient's norm.  With 1 the launches are the three of before.  k is part of a checkpoint's resume section; a resume under another k is refused."""
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3, max_grad_norm=0.1, ranges=None, accumulate: int = 1):
+        if int(accumulate) < 1:
+            raise ValueError(f"FusedAdamW: accumulate >= 1, got {accumulate}")
         if model._flat is None:
             model.flatten_parameters()
         self.model, self.lr, self.betas, self.eps, self.wd, self.max_norm = model, lr, tuple(betas), eps, weight_decay, max_grad_norm
@@ -84,6 +91,10 @@ class FusedAdamW:
         self.hyper = torch.tensor([0.0, betas[0], betas[1], eps, 0.0, 1.0, 1.0, 0.0], device=flat.device)
         self.t = 0
         self.zero_grads_after_step = False   # the AdamW kernel also clears the flat gradient buffer (GraphedTrainStep turns it on)
+        self.accumulate = int(accumulate)    # micro-batches per optimizer step, as the checkpoints record it
+        self.mean_clip = self.accumulate > 1  # launch() clips the mean of an accumulated sum (a step object may turn it on)
+        self.inv_k = torch.ones(1, device=flat.device)   # 1 / (micro-batches of this step), read by ops.clip_coef_mean
+        self.grad_scale = 1.0                # ... and the value last sent
         self.ranges, self.range_record = None, None
         if ranges is not None:
             bounds, scale, record = ranges
@@ -101,6 +112,25 @@ class FusedAdamW:
         if beta1 is not None:
             self.betas = (beta1, self.betas[1])
 
+    def set_grad_scale(self, inv_k: float):
+        """the weight of each micro-gradient in this step's mean, 1 / (number of micro-batches): sent when it changes (NOT graph-capturable: a kernel argument
+        of a tiny launch, as update_hyper's values; a captured launch() reads it on every replay)"""
+        inv_k = float(inv_k)
+        if not 0.0 < inv_k <= 1.0:
+            raise ValueError(f"FusedAdamW.set_grad_scale: 1 / k of k >= 1 micro-batches, got {inv_k}")
+        if inv_k != self.grad_scale:
+            if self.inv_k.is_cuda:
+                ops.grad_scale(inv_k, self.inv_k)
+            else:
+                self.inv_k.fill_(inv_k)
+            self.grad_scale = inv_k
+
+    def _clip(self):
+        if self.mean_clip:
+            ops.clip_coef_mean(self.acc, float(self.max_norm or 0.0), self.inv_k, self.coef, self.norm)
+        else:
+            ops.clip_coef(self.acc, float(self.max_norm or 0.0), self.coef, self.norm)
+
     def update_hyper(self, upload: bool = True):
         """advance the step counter and hand {lr, betas, eps, wd, bias corrections} to the device (NOT graph-capturable: the values are
         kernel arguments of a tiny launch, ops.step_params -- no host-to-device copy, so the host never waits for the stream).
@@ -117,16 +147,16 @@ class FusedAdamW:
                 self.hyper.copy_(torch.tensor(self.hyper_host, dtype=torch.float32))
 
     def launch(self):
-        """the three device-side launches (graph-capturable): grad norm, clip coefficient, AdamW update"""
+        """the three device-side launches (graph-capturable): grad norm, clip coefficient (of the mean, under accumulation), AdamW update"""
         g = self.model._flat_grad
         if self.ranges is not None:
             bounds, scale = self.ranges
             ops.grad_sqnorm_ranges(g, bounds, scale, self.acc)
-            ops.clip_coef(self.acc, float(self.max_norm or 0.0), self.coef, self.norm)
+            self._clip()
             ops.adamw_step_ranges(self.model._flat, g, self.m, self.v, self.hyper, bounds, scale, self.coef)
             return
         ops.grad_sqnorm(g, self.acc)
-        ops.clip_coef(self.acc, float(self.max_norm or 0.0), self.coef, self.norm)
+        self._clip()
         ops.adamw_step(self.model._flat, g, self.m, self.v, self.hyper, self.coef)
 
     def step(self):
@@ -148,12 +178,32 @@ class GraphedTrainStep:
     extents, the token mask (host python `random`, as the reference) and the optimizer hyper-parameters.  Stochastic-depth
     noise is drawn inside the graph by torch's graph-safe Philox generator.
     With data parallelism the gradient exchange is ONE flat all-reduce between the backward graph and the optimizer graph
-    (RCCL collectives are kept out of the captured region)."""
+    (RCCL collectives are kept out of the captured region).
+
+    accumulate = k > 1: k micro-batches of `batch` grids per optimizer step, each with its own block mask and its own loss normalisation, the
+    mean of their gradients stepped -- by definition the k-rank data-parallel step, not the step of one batch of k * batch grids.  Two graphs in one pool: forward +
+    backward, which adds into the gradient buffer (the AdamW kernel of the previous step cleared it) and adds its three losses into a device accumulator; and
+    clip-of-the-mean + AdamW, which also turns the accumulator into the mean losses.  __call__(micro_batches, masks) replays the first once per micro-batch and the
+    second once; begin(masks) / micro(j) / finish() are the same step in pieces, for a caller that fills `x` itself.  Fewer than k micro-batches (the ragged last step
+    of an epoch) weigh 1 / k' each.  Data-parallel: the pieces of the split step without any collective for all but the last micro-step, whose replay is the step of
+    before, so every gradient range is exchanged once per optimizer step; the collectives inside the graph (NMH_DP_CAPTURE_COMM=1) would run k times and are refused.
+    accumulate = 1 is the step of before: the same graphs, the same launches."""
 
     MAX_EXT_ROWS, MAX_MASK_BITS = 16, 4096   # capacity of one nmh_step_params launch (csrc/misc.hip: ext[48], bits[128])
 
-    def __init__(self, model, opt: FusedAdamW, batch: int, reducer=None, warmup: int = 2):
+    def __init__(self, model, opt: FusedAdamW, batch: int, reducer=None, warmup: int = 2, accumulate: int = 1):
+        import os
+        if int(accumulate) < 1:
+            raise ValueError(f"GraphedTrainStep: accumulate >= 1, got {accumulate}")
+        if accumulate > 1 and reducer is not None and os.environ.get("NMH_DP_CAPTURE_COMM", "0") == "1":
+            raise ValueError("GraphedTrainStep: NMH_DP_CAPTURE_COMM=1 puts the collectives inside the backward graph, which accumulate > 1 replays once per "
+                             "micro-batch; gradient accumulation exchanges each range once per optimizer step, between the replays (unset the variable)")
+        if opt.accumulate not in (1, int(accumulate)):
+            raise ValueError(f"GraphedTrainStep: accumulate = {accumulate}, but the optimizer was built with accumulate = {opt.accumulate}")
         self.model, self.opt, self.reducer = model, opt, reducer
+        self.accumulate = int(accumulate)
+        if self.accumulate > 1:
+            opt.accumulate, opt.mean_clip = self.accumulate, True
         dev = model.mask_token.device
         R, g = model.resolution, model.resolution // 4
         self.x = torch.zeros((batch, 4, R, R, R), device=dev)
@@ -167,6 +217,10 @@ class GraphedTrainStep:
         # every mask is checked in __call__ (one that is not re-captures the step with the dense block)
         self._block0 = bool(ops.BLOCK0_KEPT and g % 4 == 0)
         self.losses = None
+        if self.accumulate > 1:
+            # outside the graphs' pool: the sum of the micro-batches' three losses, and their mean (the optimizer graph writes it and clears the sum)
+            self._loss_sum, self.losses = torch.zeros(3, device=dev), torch.zeros(3, device=dev)
+            self._n_micro = self._done = 0
         self._ext_host = None
         self._g1 = self._g2 = None
         self._gb, self._ranges = [], []
@@ -252,8 +306,13 @@ class GraphedTrainStep:
                 out = self._fwd_bwd(zero=False)
                 if self.comm_captured:
                     self.reducer.finish()      # ranges whose trigger did not fire (the embed tail) + join of the comm stream
-                self.losses = torch.stack([o.detach() for o in out[:3]])
-                self.opt.launch()
+                self._keep_losses(out)
+                if self.accumulate == 1:
+                    self.opt.launch()
+            if self.accumulate > 1:
+                self._g2 = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self._g2, pool=self._g1.pool(), stream=s, capture_error_mode=_CAPTURE_MODE):
+                    self._optimizer_piece()
             return
         # data parallel, collectives outside the graphs: the step is cut where gradient ranges complete, and the collectives run BETWEEN the replays on the comm
         # stream (RCCL stays outside the captured regions), overlapping the next piece of the backward:
@@ -265,7 +324,7 @@ class GraphedTrainStep:
         #   g2 = clip + AdamW
         with torch.cuda.graph(self._g1, stream=s, capture_error_mode=_CAPTURE_MODE):
             out = self._split_a(zero=False)
-            self.losses = torch.stack([o.detach() for o in out[:3]])
+            self._keep_losses(out)
         pool = self._g1.pool()
         self._gb = []
         for k in range(len(self._pieces["back"])):
@@ -275,8 +334,23 @@ class GraphedTrainStep:
             self._gb.append(gk)
         self._g2 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._g2, pool=pool, stream=s, capture_error_mode=_CAPTURE_MODE):
-            self.opt.launch()
+            self._optimizer_piece()
         self._pieces = None
+
+    def _keep_losses(self, out):
+        """inside a capture, after the forward: the step's three losses; under accumulation added to the sum over the micro-batches"""
+        losses = torch.stack([o.detach() for o in out[:3]])
+        if self.accumulate > 1:
+            self._loss_sum += losses
+        else:
+            self.losses = losses
+
+    def _optimizer_piece(self):
+        """inside a capture: clip + AdamW; under accumulation also the mean of the micro-batches' losses, and their sum cleared for the next step"""
+        self.opt.launch()
+        if self.accumulate > 1:
+            torch.mul(self._loss_sum, self.opt.inv_k, out=self.losses)
+            self._loss_sum.zero_()
 
     # ---- the step in autograd pieces (data-parallel graph mode) ----------------------------------------------------------------------
     def _stage2_chunks(self):
@@ -354,67 +428,142 @@ class GraphedTrainStep:
             ops.add_inplace(e1.grad, d[1].grad)     # stage 1's output feeds stage 2 and decoder3's skip connection
             torch.autograd.backward([f1, f0], [e1.grad, d[0].grad])
 
-    def __call__(self, grids=None, block_mask=None):
-        """grids: optional list of (4,a0,a1,a2) tensors (copied into the static batch); block_mask: uint8 (g,g,g) host tensor"""
-        if grids is not None:
-            self.x.zero_()
-            ext = []
-            for i, t in enumerate(grids):
-                a0, a1, a2 = t.shape[1:]
-                self.x[i, :, :a0, :a1, :a2].copy_(t, non_blocking=True)
-                ext.append([a0, a1, a2])
-            self.set_extents(ext)
-        if self._g1 is None:
-            self._capture()
-        self.opt.update_hyper(upload=False)
+    def _load(self, grids):
+        """a list of (4,a0,a1,a2) tensors -> the static batch and its extents"""
+        self.x.zero_()
+        ext = []
+        for i, t in enumerate(grids):
+            a0, a1, a2 = t.shape[1:]
+            self.x[i, :, :a0, :a1, :a2].copy_(t, non_blocking=True)
+            ext.append([a0, a1, a2])
+        self.set_extents(ext)
+
+    def _mask_bits(self, block_mask, upload: bool = True):
+        """the block bits that travel as kernel arguments, or None for a mask that has to be uploaded whole -- which happens here unless upload=False"""
+        from .model import block_bits_of_mask
         g = self.model.resolution // 4
-        bits = None
-        if block_mask is not None:
-            from .model import block_bits_of_mask
-            bits = block_mask if isinstance(block_mask, np.ndarray) and block_mask.shape != (g, g, g) else block_bits_of_mask(block_mask)
-            if bits is None:   # an arbitrary (not block-structured) token mask: uploaded through the event-guarded pinned ring
+        bits = block_mask if isinstance(block_mask, np.ndarray) and block_mask.shape != (g, g, g) else block_bits_of_mask(block_mask)
+        if bits is None:   # an arbitrary (not block-structured) token mask: uploaded through the event-guarded pinned ring
+            if upload:
                 if getattr(self, "_pin_mask", None) is None:
                     self._pin_mask = PinnedRing((self.mask.numel(),), torch.uint8)
                 self._pin_mask.upload(torch.as_tensor(block_mask).to(torch.uint8), self.mask)
-            elif bits.shape[0] ** 3 > self.MAX_MASK_BITS:   # more blocks than the launch's argument struct holds (resolution > 256): full mask upload
-                from .model import draw_block_mask  # noqa: F401  (same block fill, done on the host)
+        elif bits.shape[0] ** 3 > self.MAX_MASK_BITS:   # more blocks than the launch's argument struct holds (resolution > 256): full mask upload
+            if upload:
                 full = np.zeros((g, g, g), dtype=np.uint8)
                 blk = np.asarray(bits, dtype=np.uint8).repeat(4, 0).repeat(4, 1).repeat(4, 2)
                 full[:blk.shape[0], :blk.shape[1], :blk.shape[2]] = blk
                 if getattr(self, "_pin_mask", None) is None:
                     self._pin_mask = PinnedRing((self.mask.numel(),), torch.uint8)
                 self._pin_mask.upload(torch.from_numpy(full), self.mask)
-                bits = None
-        if block_mask is not None and self._block0:
+            bits = None
+        return bits
+
+    def _fit_capture(self, block_mask, bits):
+        """capture the step again where `block_mask` does not fit what was captured: a mask that cuts through 4^3 windows, or keeps more tokens than the embed has
+        rows for.  The warm-up of a capture clears the gradient buffer, so under accumulation this runs for every mask of a step before its first replay."""
+        g = self.model.resolution // 4
+        if self._block0:
             from .model import mask_window_aligned
             if not (bits is not None and np.asarray(bits).shape[0] * 4 == g) and not mask_window_aligned(np.asarray(block_mask)):
                 self._block0 = False   # a mask that cuts through 4^3 windows: the step is captured again with the dense first block, as on a capacity overflow
                 torch.cuda.synchronize()
                 self._capture()
-        if block_mask is not None and self._embed_cap < g ** 3:
+        if self._embed_cap < g ** 3:
             kept = g ** 3 - (64 * int(np.asarray(bits).sum()) if bits is not None else int(np.asarray(block_mask).sum()))
             if kept > self._embed_cap:   # (eight standard deviations above the mean kept count: not expected to happen in a training run)
                 self._embed_cap = g ** 3
                 torch.cuda.synchronize()
                 self._capture()
+
+    def _send(self, bits, hyper):
+        """mask bits + optimizer hyper-parameters + extents as kernel arguments of one launch: nothing in the step waits on a copy.
+        The argument struct holds 16 samples' extents (nmh_step_params): larger batches send the rest in further launches."""
+        g = self.model.resolution // 4
         ext, self._ext_host = self._ext_host, None
-        # mask bits + optimizer hyper-parameters + extents as kernel arguments of one launch: nothing in the step waits on a copy.
-        # The argument struct holds 16 samples' extents (nmh_step_params): larger batches send the rest in further launches.
         first = ext[:self.MAX_EXT_ROWS] if ext is not None else None
         ops.step_params(tokmask=self.mask if bits is not None else None, block_bits=bits, nb=0 if bits is None else bits.shape[0], g=g,
-                        hyper=self.opt.hyper_host, hyper_dev=self.opt.hyper, extents=first, extents_dev=self.ext if ext is not None else None)
+                        hyper=hyper, hyper_dev=self.opt.hyper if hyper is not None else None, extents=first, extents_dev=self.ext if ext is not None else None)
         if ext is not None:
             for i0 in range(self.MAX_EXT_ROWS, len(ext), self.MAX_EXT_ROWS):
                 ops.step_params(extents=ext[i0:i0 + self.MAX_EXT_ROWS], extents_dev=self.ext[i0:i0 + self.MAX_EXT_ROWS])
+
+    def _replay_dp(self, exchange: bool):
+        """the pieces of the data-parallel step after g1, up to the optimizer graph; exchange=False: a micro-step that only accumulates, no collective"""
+        red, b = self.reducer, self.reducer.stage_bounds
+        if exchange:
+            red.allreduce_range(b[5], b[6], overlap=self.overlap)
+        for gk, (lo, hi) in zip(self._gb, self._ranges):
+            gk.replay()
+            if exchange:
+                red.allreduce_range(lo, hi, overlap=self.overlap)
+        if exchange:
+            red.wait()
+
+    def __call__(self, grids=None, block_mask=None):
+        """grids: optional list of (4,a0,a1,a2) tensors (copied into the static batch); block_mask: uint8 (g,g,g) host tensor.
+        accumulate > 1: `grids` is the list of the step's micro-batches, each such a list, and `block_mask` the list of their masks, one per micro-batch;
+        1 <= len <= accumulate.  Returns the mean of the micro-batches' losses."""
+        if self.accumulate > 1:
+            if grids is None or block_mask is None or len(grids) != len(block_mask):
+                raise ValueError("GraphedTrainStep(accumulate > 1): one list of grids and one block mask per micro-batch")
+            self._load(grids[0])       # (a capture in begin() warms up on the static batch)
+            self.begin(block_mask)
+            for j, mb in enumerate(grids):
+                if j > 0:
+                    self._load(mb)
+                self.micro(j)
+            return self.finish()
+        if grids is not None:
+            self._load(grids)
+        if self._g1 is None:
+            self._capture()
+        self.opt.update_hyper(upload=False)
+        bits = None
+        if block_mask is not None:
+            bits = self._mask_bits(block_mask)
+            self._fit_capture(block_mask, bits)
+        self._send(bits, self.opt.hyper_host)
         self._g1.replay()
         if self._g2 is not None:
-            red, b = self.reducer, self.reducer.stage_bounds
-            red.allreduce_range(b[5], b[6], overlap=self.overlap)
-            for gk, (lo, hi) in zip(self._gb, self._ranges):
-                gk.replay()
-                red.allreduce_range(lo, hi, overlap=self.overlap)
-            red.wait()
+            self._replay_dp(exchange=True)
             self._g2.replay()
+        return self.losses
+
+    # ---- accumulate > 1: the optimizer step in pieces ---------------------------------------------------------------------------------------
+    def begin(self, masks):
+        """start an optimizer step of len(masks) micro-batches: advance the optimizer's step count, set the micro-gradients' weight 1 / len(masks), and make
+        the captured step fit EVERY mask of the step before its first replay (a later capture would clear the gradients accumulated so far)"""
+        if self.accumulate == 1:
+            raise RuntimeError("GraphedTrainStep.begin: the step was built without accumulation; call it")
+        if not 1 <= len(masks) <= self.accumulate:
+            raise ValueError(f"GraphedTrainStep.begin: 1 .. {self.accumulate} micro-batches, got {len(masks)}")
+        if self._done != self._n_micro:
+            raise RuntimeError(f"GraphedTrainStep.begin: the step before has run {self._done} of its {self._n_micro} micro-batches")
+        if self._g1 is None:
+            self._capture()
+        for bm in masks:
+            self._fit_capture(bm, self._mask_bits(bm, upload=False))
+        self.opt.update_hyper(upload=False)
+        self.opt.set_grad_scale(1.0 / len(masks))
+        self._masks, self._n_micro, self._done = list(masks), len(masks), 0
+
+    def micro(self, j: int):
+        """micro-batch j of the step, now in `x` with its extents set: forward + backward added to the gradient buffer.  Data-parallel: the last one exchanges."""
+        if j != self._done or j >= self._n_micro:
+            raise RuntimeError(f"GraphedTrainStep.micro: micro-batch {j} after {self._done} of {self._n_micro}")
+        self._send(self._mask_bits(self._masks[j]), self.opt.hyper_host if j == 0 else None)
+        self._g1.replay()
+        if self._gb:
+            self._replay_dp(exchange=j == self._n_micro - 1)
+        self._done += 1
+
+    def finish(self):
+        """clip + AdamW on the mean gradient -> the mean of the micro-batches' losses (device tensor; valid until the next step's finish())"""
+        if self._n_micro == 0 or self._done != self._n_micro:
+            raise RuntimeError(f"GraphedTrainStep.finish: {self._done} of {self._n_micro} micro-batches have run")
+        self._g2.replay()
+        self._n_micro = self._done = 0
         return self.losses
 
 
@@ -492,6 +641,8 @@ def resume_section(model, opt, step=None) -> dict:
     r = {"m": opt.m.detach().cpu(), "v": opt.v.detach().cpu(), "t": opt.t, "lr": opt.lr, "betas": tuple(opt.betas), "step": step, "layout": flat_layout(model)}
     if getattr(opt, "range_record", None) is not None:     # FusedAdamW(ranges=): the table the moments were kept under; without one the section is as before
         r["ranges"] = opt.range_record
+    if getattr(opt, "accumulate", 1) != 1:                 # FusedAdamW(accumulate=k): the micro-batches per optimizer step the run was scheduled under
+        r["accumulate"] = int(opt.accumulate)
     return r
 
 
@@ -510,6 +661,12 @@ def restore_resume(r: dict, model, opt, who: str):
         raise RuntimeError(f"{who}: the file's optimizer state was kept {'without a range table' if tab_ck is None else 'under a range table of ' + str(len(tab_ck['scale'])) + ' ranges'}"
                            f", this optimizer has {'none' if tab_now is None else ('one' if tab_ck is None else 'another one') + ' of ' + str(len(tab_now['scale'])) + ' ranges'}: build FusedAdamW with the "
                            "same ranges= (the same layer_decay / no_decay / freeze)")
+    k_ck, k_now = int(r.get("accumulate", 1)), int(getattr(opt, "accumulate", 1))
+    if k_ck != k_now:
+        # the file's step count, schedule position and moments belong to optimizer steps of k_ck micro-batches: under another k the same epochs hold another
+        # number of steps, and the OneCycle schedule built for them is another one
+        raise RuntimeError(f"{who}: the file's run took optimizer steps of {k_ck} micro-batch{'es' if k_ck != 1 else ''} (accumulate = {k_ck}), this one is set up "
+                           f"with accumulate = {k_now}: resume with the same accumulate=")
     lay_now, lay_ck = flat_layout(model), r.get("layout")
     if lay_ck is None or {k: list(v) for k, v in lay_ck.items()} == lay_now:
         if r["m"].numel() != opt.m.numel():
@@ -547,38 +704,62 @@ def _format_record(rec: dict) -> str:
     return " ".join(f"{k}={v:.5g}" if isinstance(v, float) else f"{k}={v}" for k, v in rec.items())
 
 
+def accum_epoch_plan(batches, k: int):
+    """the optimizer steps of one epoch under gradient accumulation: the epoch's batches, in order, in groups of k -- every step has k micro-batches but the last,
+    which has what is left (1 .. k; its micro-gradients weigh 1 / that many).  k = 1: one batch per step.  Raises on k < 1."""
+    if int(k) != k or k < 1:
+        raise ValueError(f"accum_epoch_plan: k >= 1 micro-batches per optimizer step, got {k}")
+    batches = list(batches)
+    return [batches[i:i + k] for i in range(0, len(batches), k)]
+
+
 class Trainer:
     """Epoch loop of run_swin_mae3d.py:600-709 without wandb: OneCycle schedule stepped every iteration, HIP-graph train step,
     evaluation every `eval_interval` epochs, `model_best.pt` by validation PSNR (:620-629) and `epoch_{k}.pt`; rank 0 writes.
     `train_scenes` / `val_scenes`: sequences of stored scenes ((W,L,H,4) arrays or paths); sharded across ranks with
-    DistributedSampler semantics (dist.shard_indices)."""
+    DistributedSampler semantics (dist.shard_indices).
+
+    accumulate = k: an optimizer step takes k consecutive batches of the epoch as micro-batches (accum_epoch_plan; the last step of an epoch
+    takes what is left), each with its own mask, and steps on the mean of their gradients: the reference's recipe of batch_size * world * k grids on fewer GPUs.
+    steps_per_epoch, global_step, the optimizer's step count and the OneCycle schedule count OPTIMIZER steps; the logged loss is the mean over them of the
+    per-step mean; train_args["batch_size"] = batch_size * world * k and train_args["accumulate"] = k.  resume(path) continues after the file's epoch, at an
+    optimizer-step boundary; a file written under another k is refused.  INVARIANT (data-parallel): every rank runs the same number of optimizer steps with the
+    same number of micro-steps in each, because dist.shard_indices pads the shards to equal length -- the last micro-step of each optimizer step holds the
+    collectives, and a rank that ran one fewer would hang the others."""
 
     def __init__(self, model, train_scenes, val_scenes=None, batch_size: int = 4, num_epochs: int = 1, lr: float = 1e-4, weight_decay: float = 1e-3,
                  clip_grad_norm: float = 0.1, eval_interval: int = 1, save_path: str = None, normalize_density: bool = True, flip_prob: float = 0.0,
-                 rotate_prob: float = 0.0, rank: int = 0, world: int = 1, reducer=None, log=print, train_args: dict = None, seed: int = 0, no_decay: bool = False, freeze=()):
+                 rotate_prob: float = 0.0, rank: int = 0, world: int = 1, reducer=None, log=print, train_args: dict = None, seed: int = 0, no_decay: bool = False, freeze=(),
+                 accumulate: int = 1):
         from . import data, dist as _dist
         from .finetune import param_ranges, recipe_rules, selector_names
         self.model, self.train_scenes, self.val_scenes = model, train_scenes, val_scenes
         self.batch, self.epochs, self.eval_interval, self.save_path = batch_size, num_epochs, eval_interval, save_path
         self.rank, self.world, self.log, self.seed = rank, world, log, seed
-        self.args = dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, batch_size=batch_size * world,
-                         num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob, no_decay=bool(no_decay),
-                         freeze=selector_names(model, freeze))
+        if int(accumulate) != accumulate or accumulate < 1:
+            raise ValueError(f"Trainer: accumulate >= 1, got {accumulate}")
+        self.accumulate = int(accumulate)
+        self.args = dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, batch_size=batch_size * world * self.accumulate,
+                         accumulate=self.accumulate, num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
+                         no_decay=bool(no_decay), freeze=selector_names(model, freeze))
         self._shard = _dist.shard_indices
         dev = model.mask_token.device
         self.batcher = data.GridBatcher(model.resolution, dev, normalize_density, flip_prob, rotate_prob)
         self.val_batcher = data.GridBatcher(model.resolution, dev, normalize_density)
         rules = recipe_rules(model, None, no_decay, freeze)     # per-range settings (DESIGN.md 3.25); none: the one-setting step
-        self.opt = FusedAdamW(model, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm, ranges=param_ranges(model, rules) if rules else None)
-        # the reference's DataLoader has no drop_last: len(train_loader) is the ceiling, and it sizes OneCycleLR (run_swin_mae3d.py:594-598)
-        self.steps_per_epoch = -(-len(self._shard(len(train_scenes), rank, world, 0)) // batch_size)
-        if self.steps_per_epoch < 1:
+        self.opt = FusedAdamW(model, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm, ranges=param_ranges(model, rules) if rules else None,
+                              accumulate=self.accumulate)
+        # the reference's DataLoader has no drop_last: len(train_loader) is the ceiling, and it sizes OneCycleLR (run_swin_mae3d.py:594-598); under accumulation
+        # the scheduler is stepped once per optimizer step, so it is sized by those
+        self.micro_per_epoch = -(-len(self._shard(len(train_scenes), rank, world, 0)) // batch_size)
+        if self.micro_per_epoch < 1:
             raise ValueError("Trainer: empty training shard")
+        self.steps_per_epoch = len(accum_epoch_plan(range(self.micro_per_epoch), self.accumulate))
         if world > 1:
             _dist.broadcast_parameters(model)   # DDP's initial broadcast: every rank starts from rank 0's weights
         self.sched = OneCycle(lr, num_epochs * self.steps_per_epoch)
-        self.step_fn = GraphedTrainStep(model, self.opt, batch_size, reducer=reducer)
-        self.global_step, self.best_metric, self.history = 0, None, []
+        self.step_fn = GraphedTrainStep(model, self.opt, batch_size, reducer=reducer, accumulate=self.accumulate)
+        self.global_step, self.start_epoch, self.best_metric, self.history = 0, 1, None, []
 
     def _scene(self, s):
         from . import data
@@ -591,7 +772,9 @@ class Trainer:
         self.model.train()
         idx = self._shard(len(self.train_scenes), self.rank, self.world, epoch, seed=self.seed)
         g = self.model.resolution // 4
-        batches = [[self.train_scenes[i] for i in idx[b * self.batch:(b + 1) * self.batch]] for b in range(self.steps_per_epoch)]
+        batches = [[self.train_scenes[i] for i in idx[b * self.batch:(b + 1) * self.batch]] for b in range(self.micro_per_epoch)]
+        sizes = [len(step) for step in accum_epoch_plan(range(len(batches)), self.accumulate)]     # micro-batches of every optimizer step
+        si = mi = 0
         # input pipeline: batch k+1 is loaded, staged through pinned rings, copied and prepared on a copy stream by a background thread
         # while step k runs (the reference's DataLoader workers); the losses are read back once per epoch, not per step, so the host
         # keeps queueing replays ahead of the device
@@ -612,9 +795,22 @@ class Trainer:
                 self.step_fn.x[n:].zero_()
                 ext = ext + [[0, 0, 0]] * (self.batch - n)
             self.step_fn.set_extents(ext)
-            lr, b1 = self.sched.at(self.global_step)
-            self.opt.set_hyper(lr=lr, beta1=b1)
-            losses = self.step_fn(None, draw_block_mask((g, g, g), self.model.masking_prob, rng=random))
+            if self.accumulate > 1:
+                if mi == 0:
+                    lr, b1 = self.sched.at(self.global_step)
+                    self.opt.set_hyper(lr=lr, beta1=b1)
+                    # one mask per micro-batch, as every DDP rank draws its own; all of them now: begin() fits the captured step to every one before the first replay
+                    self.step_fn.begin([draw_block_mask((g, g, g), self.model.masking_prob, rng=random) for _ in range(sizes[si])])
+                self.step_fn.micro(mi)
+                mi += 1
+                if mi < sizes[si]:
+                    continue
+                losses = self.step_fn.finish()
+                si, mi = si + 1, 0
+            else:
+                lr, b1 = self.sched.at(self.global_step)
+                self.opt.set_hyper(lr=lr, beta1=b1)
+                losses = self.step_fn(None, draw_block_mask((g, g, g), self.model.masking_prob, rng=random))
             self.global_step += 1
             loss_acc += losses[0]
         self.prefetch_stats = getattr(pf, "stats", None)
@@ -633,11 +829,20 @@ class Trainer:
         self.model.train()
         return sum(ps) / len(ps), sum(ms) / len(ms)
 
+    def resume(self, path: str) -> dict:
+        """continue a run from a file that fit() wrote: weights, optimizer state, schedule position; fit() then starts at the epoch after the file's, which is an
+        optimizer-step boundary (no step spans two epochs).  A file written under another `accumulate` is refused (restore_resume)."""
+        ck = load_checkpoint(path, self.model, self.opt)
+        self.start_epoch = int(ck["epoch"]) + 1
+        step = ck.get("resume", {}).get("step")
+        self.global_step = int(step) if step is not None else (self.start_epoch - 1) * self.steps_per_epoch
+        return ck
+
     def fit(self):
         import os
         if self.save_path and self.rank == 0:
             os.makedirs(self.save_path, exist_ok=True)
-        for epoch in range(1, self.epochs + 1):
+        for epoch in range(self.start_epoch, self.epochs + 1):
             loss = self.train_epoch(epoch)
             rec = {"epoch": epoch, "train_loss": loss}
             if self.rank == 0 and _eval_epoch(self.val_scenes, epoch, self.eval_interval, self.epochs):
@@ -754,7 +959,8 @@ class _FinetuneTrainer:
     rank and train_args["batch_size"] = batch_size * world (:614); every rank holds all scenes and trains on its shard (dp_epoch_plan).  INVARIANT: every rank
     runs the same number of steps per epoch with the same batch sizes, the ragged last one included, because dist.shard_indices pads the shards to equal length
     -- each step holds collectives (the loss normalisers, the gradient ranges), and a rank that ran one step fewer would hang the others.  The constructor
-    broadcasts rank 0's parameters.  `reducer`: a dist.FlatGradReducer over a finetune.FlatParameters of this model, which the trainer then adopts (that is how
+    broadcasts rank 0's parameters.  Under accumulation the same holds for the micro-steps of every optimizer step (accum_epoch_plan over equal-length plans), and only
+    the last micro-step of a step exchanges gradients.  `reducer`: a dist.FlatGradReducer over a finetune.FlatParameters of this model, which the trainer then adopts (that is how
     bf16 buckets are chosen); None with world > 1 builds one with fp32 buckets.  The augmentation draws of rank r come from random.Random(seed + 1000003 * r),
     scene by scene, batch by batch, and nothing else uses that generator.  The accumulated epoch losses are averaged over the ranks in ONE all-reduce per epoch
     (the reference: a barrier and four all-reduces per step, :747-751).  Evaluation and files are rank 0's; the other ranks wait at one barrier per evaluated
@@ -769,6 +975,11 @@ class _FinetuneTrainer:
     their moments and clips over the rest; their gradients are still computed and, data-parallel, exchanged.  `freeze` adds to `exclude`; a selector that matches
     only what `exclude` left out is refused.  The three are recorded in train_args, and a resume under other settings is refused (restore_resume).
 
+    accumulate = k: an optimizer step takes k consecutive batches of the epoch's plan as micro-batches (accum_epoch_plan; an epoch's last step takes what
+    is left) through FinetuneStep.accumulate and steps on the mean of their gradients.  steps_per_epoch, global_step, the optimizer's step count and the schedule
+    count optimizer steps; the logged losses are the mean over them of the per-step mean; train_args records accumulate and batch_size = batch * world * k; resume
+    continues at an optimizer-step boundary, and a file written under another k is refused (restore_resume).
+
     A subclass supplies its checkpoint pair (_save_checkpoint, _load_checkpoint) and
       _logged(losses)         the step's detached losses -> the 1-D tensor that the epoch accumulates
       _record(vals)           the epoch's means of _logged, read back as a list -> the training part of the history record
@@ -778,14 +989,19 @@ class _FinetuneTrainer:
 
     def __init__(self, model, train_scenes, train_targets, val_scenes, val_targets, batcher, val_batcher, loss_fn, weights, args: dict, batch_size: int,
                  num_epochs: int, schedule_epochs: int, lr: float, weight_decay: float, clip_grad_norm: float, eval_interval: int, save_path: str, log, seed: int,
-                 rank: int, world: int, reducer, exclude=(), layer_decay: float = None, no_decay: bool = False, freeze=()):
+                 rank: int, world: int, reducer, exclude=(), layer_decay: float = None, no_decay: bool = False, freeze=(), accumulate: int = 1):
         import random
         from . import dist as _dist
         from .finetune import FinetuneStep, FlatParameters, param_ranges, recipe_rules, selector_names
         self.model, self.train_scenes, self.train_targets, self.val_scenes, self.val_targets = model, train_scenes, train_targets, val_scenes, val_targets
         self.batch, self.epochs, self.eval_interval, self.save_path, self.log, self.seed = batch_size, num_epochs, eval_interval, save_path, log, seed
         self.rank, self.world = rank, world
-        self.args = _plain(dict(args, layer_decay=layer_decay, no_decay=bool(no_decay), freeze=selector_names(model, freeze)))
+        if int(accumulate) != accumulate or accumulate < 1:
+            raise ValueError(f"{type(self).__name__}: accumulate >= 1, got {accumulate}")
+        self.accumulate = int(accumulate)
+        # (the subclasses pass batch_size = batch * world, the reference's --batch_size; an optimizer step under accumulation takes `accumulate` times as many)
+        self.args = _plain(dict(args, batch_size=batch_size * world * self.accumulate, accumulate=self.accumulate, layer_decay=layer_decay, no_decay=bool(no_decay),
+                                freeze=selector_names(model, freeze)))
         self.batcher, self.val_batcher = batcher, val_batcher
         self.exclude = tuple(exclude)                            # the frozen part: outside the flat buffers, kept in eval()
         if reducer is not None:
@@ -803,8 +1019,10 @@ class _FinetuneTrainer:
             _dist.broadcast_flat_parameters(self.flat)   # DDP's initial broadcast: every rank starts from rank 0's weights
         # per-range settings: a selector that matches nothing in the flat buffer -- a typo, or a part that `exclude` left out -- is refused
         rules = recipe_rules(model, layer_decay, no_decay, freeze)
-        self.opt = FusedAdamW(self.flat, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm, ranges=param_ranges(self.flat, rules) if rules else None)
-        self.steps_per_epoch = len(dp_epoch_plan(len(train_scenes), batch_size, rank, world, 0, seed))   # len(train_loader) without drop_last, the same on every rank
+        self.opt = FusedAdamW(self.flat, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm, ranges=param_ranges(self.flat, rules) if rules else None,
+                              accumulate=self.accumulate)
+        self.micro_per_epoch = len(dp_epoch_plan(len(train_scenes), batch_size, rank, world, 0, seed))   # len(train_loader) without drop_last, the same on every rank
+        self.steps_per_epoch = len(accum_epoch_plan(range(self.micro_per_epoch), self.accumulate))      # optimizer steps: what the schedule counts
         self.sched = OneCycle(lr, schedule_epochs * self.steps_per_epoch)
         self.step_fn = FinetuneStep(self.flat, self.opt, loss_fn, weights=weights, reducer=reducer)
         self._rng = random.Random(seed + 1000003 * rank)         # the augmentation draws: another sequence on every rank
@@ -838,11 +1056,19 @@ class _FinetuneTrainer:
     def train_epoch(self, epoch: int):
         self._train_mode()
         acc = None
-        for ids in dp_epoch_plan(len(self.train_scenes), self.batch, self.rank, self.world, epoch, self.seed):     # the DataLoader's shuffle, this rank's shard
-            meshes, targets = self._batch(ids)
+        batches = dp_epoch_plan(len(self.train_scenes), self.batch, self.rank, self.world, epoch, self.seed)     # the DataLoader's shuffle, this rank's shard
+        for step in accum_epoch_plan(batches, self.accumulate):
             lr, b1 = self.sched.at(self.global_step)
             self.opt.set_hyper(lr=lr, beta1=b1)
-            parts = self._logged(self.step_fn(meshes, targets))
+            parts = None
+            for ids in step[:-1]:               # all micro-batches but the last: forward and backward only, no collective
+                p = self._logged(self.step_fn.accumulate(*self._batch(ids)))
+                parts = p if parts is None else parts + p
+            out = self.step_fn(*self._batch(step[-1]))
+            if parts is None:                   # a step of one batch: the call's own losses, as without accumulation
+                parts = self._logged(out)
+            else:                               # (the call returns the step's mean; `last` keeps this batch's own losses, which _logged pairs with its side values)
+                parts = (parts + self._logged(self.step_fn.last)) / len(step)
             self.global_step += 1
             acc = parts if acc is None else acc + parts
         if self.world > 1:
@@ -908,7 +1134,7 @@ class DetectionTrainer(_FinetuneTrainer):
                  weight_decay: float = 1e-3, clip_grad_norm: float = 0.1, reg_loss_weight: float = 1.0, eval_interval: int = 1, save_path: str = None,
                  normalize_density: bool = True, flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = 1000,
                  log=print, train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None, layer_decay: float = None,
-                 no_decay: bool = False, freeze=()):
+                 no_decay: bool = False, freeze=(), accumulate: int = 1):
         from . import data
         from .finetune import fcos_loss_fn
         if len(train_scenes) != len(train_boxes) or (val_scenes is not None and len(val_scenes) != len(val_boxes or [])):
@@ -930,7 +1156,7 @@ class DetectionTrainer(_FinetuneTrainer):
                               batch_size=batch_size * world, num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob,
                               rotate_prob=rotate_prob, rot_scale_prob=rot_scale_prob),
                          batch_size, num_epochs, schedule_epochs, lr, weight_decay, clip_grad_norm, eval_interval, save_path, log, seed, rank, world, reducer,
-                         layer_decay=layer_decay, no_decay=no_decay, freeze=freeze)
+                         layer_decay=layer_decay, no_decay=no_decay, freeze=freeze, accumulate=accumulate)
         self.top_n = int(model.args.fpn_post_nms_top_n)
         self.limits = [l for l in (300, 1000, self.top_n) if l <= self.top_n]
         self.ap_top_n = (train_args or {}).get("ap_top_n")
@@ -1067,7 +1293,7 @@ class _BoxTrainer(_FinetuneTrainer):
                                   data.DetectionBatcher(resolution, dev, c["normalize_density"]), loss_fn, weights, c["args"], c["batch_size"], c["num_epochs"],
                                   c["schedule_epochs"] or c["num_epochs"], c["lr"], c["weight_decay"], c["clip_grad_norm"], c["eval_interval"], c["save_path"],
                                   c["log"], c["seed"], c["rank"], c["world"], c["reducer"], exclude=exclude, layer_decay=c["layer_decay"], no_decay=c["no_decay"],
-                                  freeze=c["freeze"])
+                                  freeze=c["freeze"], accumulate=c["accumulate"])
 
     def _logged(self, losses):
         return torch.stack([losses[k] for k in self.keys])
@@ -1086,8 +1312,11 @@ class _BoxTrainer(_FinetuneTrainer):
         """_FinetuneTrainer.resume, and the samplers' counters: each draws once per step (rpn_sample, roi_targets: "the counter advances by one"), so the
         run continues with the draws an uninterrupted one would make when the counters are set to the file's step"""
         ck = super().resume(path)
+        # under accumulation a draw per MICRO-step: whole epochs of micro_per_epoch, then `accumulate` per optimizer step (only an epoch's last step is short)
+        epochs_done, rest = divmod(self.global_step, self.steps_per_epoch)
+        draws = epochs_done * self.micro_per_epoch + min(rest * self.accumulate, self.micro_per_epoch)
         for s in self._samplers():
-            s.rng_state = torch.tensor([s.seed, self.global_step], dtype=torch.int64, device=self.flat._flat.device)
+            s.rng_state = torch.tensor([s.seed, draws], dtype=torch.int64, device=self.flat._flat.device)
         return ck
 
     def _newest(self, epoch: int):
@@ -1117,7 +1346,8 @@ class RPNTrainer(_BoxTrainer):
                  lr: float = 1e-4, weight_decay: float = 0.01, clip_grad_norm: float = 0.1, reg_loss_weight: float = 5.0, reg_loss_weight_2d: float = 0.0,
                  eval_interval: int = 1, keep_checkpoints: int = 1, top_k: int = None, freeze_backbone: bool = False, normalize_density: bool = True,
                  flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = None, save_path: str = None, log=print,
-                 train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None, layer_decay: float = None, no_decay: bool = False, freeze=()):
+                 train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None, layer_decay: float = None, no_decay: bool = False, freeze=(),
+                 accumulate: int = 1):
         from .finetune import rpn_loss_fn
         self.freeze_backbone = bool(freeze_backbone)
         args = dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, reg_loss_weight=reg_loss_weight,
@@ -1129,7 +1359,7 @@ class RPNTrainer(_BoxTrainer):
                     dict(args=args, batch_size=batch_size, num_epochs=num_epochs, schedule_epochs=schedule_epochs, lr=lr, weight_decay=weight_decay,
                          clip_grad_norm=clip_grad_norm, eval_interval=eval_interval, keep_checkpoints=keep_checkpoints, top_k=top_k, save_path=save_path, log=log,
                          seed=seed, rank=rank, world=world, reducer=reducer, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
-                         rot_scale_prob=rot_scale_prob, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze),
+                         rot_scale_prob=rot_scale_prob, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze, accumulate=accumulate),
                     (model.backbone,) if self.freeze_backbone else ())
         if self.freeze_backbone:
             model.backbone_no_grad = True
@@ -1201,7 +1431,7 @@ class TwoStageTrainer(_BoxTrainer):
                  rpn_reg_loss_weight_2d: float = 0.0, obj_only: bool = False, freeze_first_stage: bool = None, eval_interval: int = 1, keep_checkpoints: int = 1,
                  top_k: int = None, normalize_density: bool = True, flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0,
                  schedule_epochs: int = None, save_path: str = None, log=print, train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None,
-                 layer_decay: float = None, no_decay: bool = False, freeze=()):
+                 layer_decay: float = None, no_decay: bool = False, freeze=(), accumulate: int = 1):
         from .finetune import roi_loss_fn
         if obj_only and model.is_reg:
             raise ValueError("TwoStageTrainer: obj_only trains no box regression, but the detector decodes with it (is_reg=True): build TwoStageDetector(..., "
@@ -1223,7 +1453,7 @@ class TwoStageTrainer(_BoxTrainer):
                     dict(args=args, batch_size=batch_size, num_epochs=num_epochs, schedule_epochs=schedule_epochs, lr=lr, weight_decay=weight_decay,
                          clip_grad_norm=clip_grad_norm, eval_interval=eval_interval, keep_checkpoints=keep_checkpoints, top_k=top_k, save_path=save_path, log=log,
                          seed=seed, rank=rank, world=world, reducer=reducer, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
-                         rot_scale_prob=rot_scale_prob, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze),
+                         rot_scale_prob=rot_scale_prob, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze, accumulate=accumulate),
                     exclude)
         model.first_stage_no_grad = frozen is not None
         self.best_metric = {}
@@ -1300,7 +1530,8 @@ class VoxelTrainer(_FinetuneTrainer):
     def __init__(self, model, train_scenes, train_targets, val_scenes=None, val_targets=None, batch_size: int = 1, num_epochs: int = 1, lr: float = 5e-3,
                  weight_decay: float = 0.01, clip_grad_norm: float = 0.1, eval_interval: int = 1, save_path: str = None, normalize_density: bool = True,
                  flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = None, log=print,
-                 train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None, layer_decay: float = None, no_decay: bool = False, freeze=()):
+                 train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None, layer_decay: float = None, no_decay: bool = False, freeze=(),
+                 accumulate: int = 1):
         from . import data
         from .heads import SwinTransformer_VoxelSemantics_Pretrained_Skip, SwinTransformer_VoxelSR_Pretrained_Skip
         if isinstance(model, SwinTransformer_VoxelSemantics_Pretrained_Skip):
@@ -1327,7 +1558,7 @@ class VoxelTrainer(_FinetuneTrainer):
                               num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
                               rot_scale_prob=rot_scale_prob),
                          batch_size, num_epochs, schedule_epochs or num_epochs, lr, weight_decay, clip_grad_norm, eval_interval, save_path, log, seed, rank, world,
-                         reducer, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze)
+                         reducer, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze, accumulate=accumulate)
         self.best_metric = None
 
     def _loss(self, meshes, tb):

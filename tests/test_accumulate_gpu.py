@@ -1,0 +1,433 @@
+"""Gradient accumulation: k micro-batches per optimizer step, each with its own mask and its own loss normalisation, the MEAN of their
+gradients clipped and stepped -- by definition the k-rank data-parallel step, so the reference everywhere is the hand average of
+tests/test_dist_gpu.py::test_two_ranks_one_gpu_match_single_process_average (eager forward / backward per micro-batch, _flat_grad = their mean, the step of an
+optimizer WITHOUT accumulation) and the bound is that test's: max|d| / max|ref| < 1e-5 over the parameters.  The smallest model that has every gradient path
+(TINY, resolution 32, fp32, stochastic depth 0); eps = 1 keeps the update linear in tiny gradients, so the atomics' summation order is not amplified to +-lr."""
+import functools
+import os
+import queue
+import random
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TINY = dict(embed_dim=32, depths=[2, 2, 2, 2], num_heads=[1, 2, 4, 8])
+OPT = dict(lr=1e-3, weight_decay=1e-3, max_grad_norm=0.1, eps=1.0)
+PTOL = 1e-5
+
+
+def _build():
+    from nerf_mae_amd.model import SwinTransformer_MAE3D
+    torch.manual_seed(5)
+    m = SwinTransformer_MAE3D(patch_size=[4] * 3, window_size=[4] * 3, resolution=32, masking_prob=0.75, stochastic_depth_prob=0.0,
+                              compute_dtype=torch.float32, **TINY).cuda()
+    m.train()
+    m.flatten_parameters()
+    return m
+
+
+def _grid(seed):
+    from oracle import mae3d_oracle as O
+    return O.synthetic_grid((32, 32, 32), seed).cuda()
+
+
+def _mask(seed):
+    from oracle import mae3d_oracle as O
+    return O.draw_block_mask((8, 8, 8), 0.75, rng=random.Random(seed))
+
+
+def _one_block_mask():
+    bm = torch.zeros(8, 8, 8, dtype=torch.uint8)
+    bm[:4, :4, :4] = 1
+    return bm
+
+
+def _ranges(m, ranged):
+    from nerf_mae_amd.finetune import no_decay_rules, param_ranges
+    return param_ranges(m, no_decay_rules(m)) if ranged else None
+
+
+def _hand_average(micro, steps, ranged=False):
+    """`steps` optimizer steps on the mean gradient of the micro-batches `micro` = [(grid seed, mask), ...], by hand -> per step: the parameters after it, the
+    mean of the eager losses [3], the norm of the mean gradient (float64)"""
+    from nerf_mae_amd.trainer import FusedAdamW
+    m = _build()
+    opt = FusedAdamW(m, ranges=_ranges(m, ranged), **OPT)
+    out = []
+    for _ in range(steps):
+        gs, ls = [], []
+        for seed, bm in micro:
+            m.zero_grad()
+            res = m([_grid(seed)], block_mask=bm)
+            res[0].backward()
+            gs.append(m._flat_grad.clone())
+            ls.append(torch.stack([r.detach() for r in res[:3]]))
+        mean = sum(gs) / len(gs)
+        m._flat_grad.copy_(mean)
+        opt.step()
+        torch.cuda.synchronize()
+        out.append((m._flat.detach().cpu().clone(), (sum(ls) / len(ls)).cpu(), mean.double().norm().item()))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def reference(ranged=False):
+    """two steps on grids 40, 41 under the masks of Random(9), Random(10): computed once, shared, left unchanged"""
+    return _hand_average([(40, _mask(9)), (41, _mask(10))], 2, ranged)
+
+
+def _perr(flat, ref):
+    return ((flat.detach().cpu() - ref).abs().max() / ref.abs().max()).item()
+
+
+def _accumulated(k, micro, steps, ranged=False):
+    """-> (model, optimizer, step object, the losses each call returned)"""
+    from nerf_mae_amd.trainer import FusedAdamW, GraphedTrainStep
+    m = _build()
+    opt = FusedAdamW(m, ranges=_ranges(m, ranged), **OPT)
+    step = GraphedTrainStep(m, opt, 1, accumulate=k)
+    losses = [step([[_grid(s)] for s, _ in micro], [bm for _, bm in micro]).clone() for _ in range(steps)]
+    torch.cuda.synchronize()
+    return m, opt, step, losses
+
+
+# ---- 1. the kernel ------------------------------------------------------------------------------------------------------------------------------------
+def _ulps(a, b):
+    return abs(int(np.float32(a).view(np.int32)) - int(np.float32(b).view(np.int32)))
+
+
+@pytest.mark.parametrize("max_norm", [0.0, 0.1])
+def test_clip_coef_mean_against_the_formula_in_float64(max_norm):
+    """nrm = sqrt(acc) * inv_k; coef = inv_k * min(1, max_norm / (nrm + 1e-6)), or inv_k with max_norm <= 0 -- in float64 on the inv_k the kernel reads (the
+    fp32 value), rounded to fp32.  Equal, or 1 fp32 ulp apart where the kernel associates the product differently.  inv_k = 1: the bits of ops.clip_coef."""
+    from nerf_mae_amd import ops
+    coef, norm, inv = (torch.full((1,), -7.0, device="cuda") for _ in range(3))
+    coef1, norm1 = torch.zeros(1, device="cuda"), torch.zeros(1, device="cuda")
+    for acc_v in (0.0, 1e-30, 1e-4, 1.0, 1e8):
+        acc = torch.tensor([acc_v], dtype=torch.float64, device="cuda")
+        for k in (1, 2, 3, 7):
+            ik32 = np.float32(1.0 / k)
+            ops.grad_scale(float(ik32), inv)
+            ops.clip_coef_mean(acc, max_norm, inv, coef, norm)
+            ik = np.float64(ik32)
+            nrm = np.sqrt(np.float64(acc_v)) * ik
+            want_c = ik * min(1.0, np.float64(np.float32(max_norm)) / (nrm + 1e-6)) if max_norm > 0 else ik
+            got_c, got_n = coef.item(), norm.item()
+            print(f"  [clip_coef_mean] acc {acc_v:g} k {k} max_norm {max_norm}: coef {got_c:.9g} (want {np.float32(want_c):.9g}), norm {got_n:.9g} (want {np.float32(nrm):.9g})")
+            assert inv.item() == float(ik32)
+            assert _ulps(got_c, want_c) <= 1, (acc_v, k, got_c, want_c)
+            assert _ulps(got_n, nrm) <= 1, (acc_v, k, got_n, nrm)
+            if k == 1:
+                ops.clip_coef(acc, max_norm, coef1, norm1)
+                assert torch.equal(coef, coef1) and torch.equal(norm, norm1), (acc_v, coef.item(), coef1.item(), norm.item(), norm1.item())
+
+
+def test_grad_scale_refuses_what_is_not_one_over_k():
+    from nerf_mae_amd import ops
+    from nerf_mae_amd._lib import NmhError
+    inv = torch.ones(1, device="cuda")
+    for bad in (0.0, -0.5, 1.5, float("nan")):
+        with pytest.raises(NmhError):
+            ops.grad_scale(bad, inv)
+    torch.cuda.synchronize()
+    assert inv.item() == 1.0
+
+
+# ---- 2, 6. the captured step equals the k-rank average ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ranged", [False, True], ids=["one-setting", "ranged"])
+def test_accumulated_graph_step_equals_the_hand_average(ranged):
+    """accumulate = 2, two optimizer steps; ranged: the *_ranges kernels under the no-decay table, against the hand average stepped by a ranged optimizer"""
+    ref = reference(ranged)
+    m, opt, step, losses = _accumulated(2, [(40, _mask(9)), (41, _mask(10))], 2, ranged)
+    assert step._g2 is not None and not step._gb, "two graphs: forward + backward, and the optimizer"
+    assert opt.t == 2 and opt.accumulate == 2
+    for i, (got, (_, want, _)) in enumerate(zip(losses, ref)):
+        rel = ((got.cpu() - want).abs() / want.abs()).max().item()
+        print(f"  [accumulate 2{' ranged' if ranged else ''}] step {i}: loss {got.cpu().tolist()} vs eager mean {want.tolist()} rel {rel:.2e}")
+        assert rel < 5e-6
+    err = _perr(m._flat, ref[1][0])
+    print(f"  [accumulate 2{' ranged' if ranged else ''}] parameters after two steps: {err:.2e}")
+    assert err < PTOL
+    assert not m._flat_grad.any(), "the optimizer kernel leaves the gradient buffer cleared for the next accumulation"
+
+
+def test_accumulated_step_without_a_binding_clip_still_steps_on_the_mean():
+    """where the clip binds, the clip of the SUM already rescales to the clipped mean, so the step above cannot tell whether 1 / k reached the update; with the
+    clip off (max_grad_norm = 0) the update sees coef = 1 / k alone.  One step, the same micro-batches, the same bound."""
+    from nerf_mae_amd.trainer import FusedAdamW, GraphedTrainStep
+    micro = [(40, _mask(9)), (41, _mask(10))]
+    kw = dict(OPT, max_grad_norm=0.0)
+    ref = _build()
+    ropt = FusedAdamW(ref, **kw)
+    gs = []
+    for seed, bm in micro:
+        ref.zero_grad()
+        ref([_grid(seed)], block_mask=bm)[0].backward()
+        gs.append(ref._flat_grad.clone())
+    ref._flat_grad.copy_((gs[0] + gs[1]) / 2)
+    ropt.step()
+    m = _build()
+    opt = FusedAdamW(m, **kw)
+    GraphedTrainStep(m, opt, 1, accumulate=2)([[_grid(s)] for s, _ in micro], [bm for _, bm in micro])
+    torch.cuda.synchronize()
+    err = _perr(m._flat, ref._flat.detach().cpu())
+    # ... and on the UPDATE, which is what a wrong weight changes (with eps = 1 a doubled gradient nearly doubles it) and which the bound on the parameters, three
+    # orders above an update of lr = 1e-3, cannot see: both runs round every parameter to fp32 (2^-24 |p| each, 2^-22 max|p| allowed for the two), and the
+    # gradients differ by the order of fp32 sums, far inside 1e-3 of the largest update
+    p0 = _build()._flat.detach().cpu()
+    pr, pa = ref._flat.detach().cpu(), m._flat.detach().cpu()
+    upd, d, pmax = (pr - p0).abs().max().item(), (pa - pr).abs().max().item(), pr.abs().max().item()
+    print(f"  [accumulate 2, clip off] parameters {err:.2e}; coef {opt.coef.item()}; update max {upd:.3e}, difference {d:.3e}, allowed {2 ** -22 * pmax + 1e-3 * upd:.3e}")
+    assert opt.coef.item() == 0.5
+    assert err < PTOL
+    assert upd > 10 * 2 ** -22 * pmax, "the step moved the parameters well beyond their rounding: a halved or doubled update would exceed the bound below"
+    assert d <= 2 ** -22 * pmax + 1e-3 * upd
+
+
+# ---- 3. the ragged step -----------------------------------------------------------------------------------------------------------------------------------
+def test_a_step_with_fewer_micro_batches_weighs_them_by_their_number():
+    ref_p, ref_l, ref_norm = reference()[0]
+    m, opt, step, losses = _accumulated(3, [(40, _mask(9)), (41, _mask(10))], 1)
+    err, nerr = _perr(m._flat, ref_p), abs(opt.norm.item() - ref_norm) / ref_norm
+    print(f"  [accumulate 3, two micro-batches] parameters {err:.2e}, norm {opt.norm.item():.6g} vs {ref_norm:.6g} rel {nerr:.2e}")
+    assert err < PTOL
+    assert nerr < 1e-5
+    assert opt.grad_scale == 0.5 and opt.inv_k.item() == 0.5
+    assert ((losses[0].cpu() - ref_l).abs() / ref_l.abs()).max().item() < 5e-6
+    with pytest.raises(ValueError):
+        step([[_grid(40)]] * 4, [_mask(9)] * 4)          # more micro-batches than the step was built for
+
+
+# ---- 4. accumulate = 1 is the step of before ----------------------------------------------------------------------------------------------------------------
+def test_accumulate_one_is_the_step_without_the_keyword():
+    from nerf_mae_amd.trainer import FusedAdamW, GraphedTrainStep
+    res = []
+    for kw in ({}, {"accumulate": 1}):
+        m = _build()
+        opt = FusedAdamW(m, **OPT)
+        step = GraphedTrainStep(m, opt, 1, **kw)
+        ls = [step([_grid(40 + i)], _mask(9 + i)).clone() for i in range(2)]
+        torch.cuda.synchronize()
+        assert step._g2 is None and not step._gb, "a single process without accumulation holds ONE graph: no separate optimizer graph"
+        assert opt.mean_clip is False and opt.accumulate == 1
+        res.append((m._flat.detach().cpu().clone(), torch.stack(ls).cpu()))
+    err = _perr(res[1][0], res[0][0])
+    print(f"  [accumulate 1] against the step without the keyword: {err:.2e}")
+    assert err < 2e-6
+    assert torch.allclose(res[0][1], res[1][1], rtol=2e-5, atol=0)
+
+
+# ---- 5. a re-capture happens before the accumulation starts ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("why", ["capacity", "unaligned"])
+def test_a_mask_that_needs_a_new_capture_does_not_lose_the_first_micro_gradient(why):
+    """the second micro-batch's mask does not fit the captured step.  capacity: zeros(8, 8, 8) with one block removed keeps 448 tokens -- more than the embed's
+    captured rows, which on this 8^3 token grid (where the sizing rule already gives a row to every token) are set to what the first micro-batch's mask keeps,
+    before the first capture.  unaligned: a mask that cuts through 4^3 windows, which the kept-windows first block cannot run.  The warm-up of the new capture
+    clears the gradient buffer, so it has to happen before the first micro-replay: the step must equal the hand average."""
+    from nerf_mae_amd import ops
+    from nerf_mae_amd.trainer import FusedAdamW, GraphedTrainStep
+    bm0 = _mask(9)
+    if why == "capacity":
+        bm1 = _one_block_mask()
+        cap = 512 - int(bm0.sum())
+        assert 64 <= cap < 512 - int(bm1.sum()) == 448
+    else:
+        from nerf_mae_amd.model import mask_window_aligned
+        bm1 = torch.roll(_mask(10), 2, 0)
+        bm1[:2] = 0
+        assert not mask_window_aligned(bm1.numpy())
+    recaptures = why == "capacity" or bool(ops.BLOCK0_KEPT)      # (with the kept-windows first block switched off every mask fits: the equality still holds)
+    micro = [(40, bm0), (41, bm1)]
+    (ref_p, ref_l, _), = _hand_average(micro, 1)
+    m = _build()
+    opt = FusedAdamW(m, **OPT)
+    step = GraphedTrainStep(m, opt, 1, accumulate=2)
+    if why == "capacity":
+        step._embed_cap = cap
+    step._load([_grid(40)])
+    step._capture()                                       # the step as captured for masks like the first
+    g1 = step._g1
+    loss = step([[_grid(40)], [_grid(41)]], [bm0, bm1]).clone()
+    torch.cuda.synchronize()
+    if recaptures:
+        assert step._g1 is not g1, "the step was captured again"
+        assert (step._embed_cap == 512) if why == "capacity" else (step._block0 is False)
+    err = _perr(m._flat, ref_p)
+    print(f"  [re-capture, {why}] parameters {err:.2e}")
+    assert err < PTOL
+    assert ((loss.cpu() - ref_l).abs() / ref_l.abs()).max().item() < 5e-6
+
+
+def test_the_pieces_refuse_to_run_out_of_order():
+    from nerf_mae_amd.trainer import FusedAdamW, GraphedTrainStep
+    m = _build()
+    with pytest.raises(ValueError):
+        GraphedTrainStep(m, FusedAdamW(m, **OPT), 1, accumulate=0)
+    with pytest.raises(ValueError):
+        GraphedTrainStep(m, FusedAdamW(m, accumulate=3, **OPT), 1, accumulate=2)
+    step = GraphedTrainStep(m, FusedAdamW(m, **OPT), 1, accumulate=2)
+    with pytest.raises(RuntimeError):
+        step.finish()                                     # nothing begun
+    with pytest.raises(ValueError):
+        step.begin([])
+
+
+# ---- 7. FinetuneStep ----------------------------------------------------------------------------------------------------------------------------------------
+def test_finetune_step_accumulates_and_steps_on_the_mean():
+    """a module without an encoder: the FPN neck on 8^3 / 4^3 inputs, loss = sum of squares of its outputs.  accumulate(a) then __call__(b) = one step on the
+    mean of the two separately computed gradients; the returned dict is the mean of the two loss dicts"""
+    from nerf_mae_amd.finetune import FinetuneStep, FlatParameters
+    from nerf_mae_amd.fpn import FPN
+    from nerf_mae_amd.trainer import FusedAdamW
+
+    def build():
+        torch.manual_seed(3)
+        fpn = FPN([32, 64], 32, 2, compute_dtype=torch.float32).cuda().train()
+        flat = FlatParameters(fpn, torch.device("cuda"))
+        opt = FusedAdamW(flat, **OPT)
+        return fpn, flat, opt, FinetuneStep(flat, opt, lambda xs: sum((o * o).sum() for o in fpn(xs)))
+
+    gen = torch.Generator().manual_seed(17)
+    # (leaves that require a gradient: the neck's autograd node hangs on its inputs, as under a backbone)
+    a, b = ([(0.1 * torch.randn(1, c, s, s, s, generator=gen)).cuda().requires_grad_() for c, s in ((32, 8), (64, 4))] for _ in range(2))
+    _, flat, opt, step = build()
+    la = step.accumulate(a)
+    assert opt.t == 0 and flat._flat_grad.any(), "accumulate() runs forward and backward only"
+    out = step(b)
+    lb = step.last
+    torch.cuda.synchronize()
+    assert opt.t == 1 and opt.grad_scale == 0.5 and not flat._flat_grad.any()
+    assert torch.allclose(out["loss"], (la["loss"] + lb["loss"]) / 2, rtol=1e-6, atol=0)
+    # by hand: each gradient on its own, their mean, the step of an optimizer without accumulation
+    _, flat2, opt2, step2 = build()
+    gs, ls = [], []
+    for batch in (a, b):
+        flat2.zero_grad()
+        losses, total = step2.forward(batch)
+        total.backward()
+        gs.append(flat2._flat_grad.clone())
+        ls.append(losses["loss"].detach())
+    flat2._flat_grad.copy_((gs[0] + gs[1]) / 2)
+    opt2.zero_grads_after_step = True
+    opt2.step()
+    torch.cuda.synchronize()
+    assert opt2.mean_clip is False
+    err = _perr(flat._flat, flat2._flat.detach().cpu())
+    nerr = abs(opt.norm.item() - opt2.norm.item()) / opt2.norm.item()
+    print(f"  [FinetuneStep accumulate] parameters {err:.2e}, norm {opt.norm.item():.6g} vs {opt2.norm.item():.6g}")
+    assert err < PTOL and nerr < 1e-5
+    assert torch.allclose(la["loss"], ls[0], rtol=1e-5, atol=0) and torch.allclose(lb["loss"], ls[1], rtol=1e-5, atol=0)
+    # a step without accumulate() after one with: weight 1 again
+    step(a)
+    assert opt.grad_scale == 1.0 and step.last is not None and not step._held
+
+
+# ---- 8. data-parallel with accumulation -------------------------------------------------------------------------------------------------------------------
+def _dp_worker(rank, world, port, q):
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from nerf_mae_amd.dist import GradReducer, broadcast_parameters
+        from nerf_mae_amd.trainer import FusedAdamW, GraphedTrainStep
+        m = _build()
+        broadcast_parameters(m)
+        red = GradReducer(m, comm_dtype=None)             # fp32 buckets
+        calls = []
+        inner = red.allreduce_range
+        red.allreduce_range = lambda lo, hi, **kw: (calls.append((lo, hi)), inner(lo, hi, **kw))[1]
+        opt = FusedAdamW(m, **OPT)
+        step = GraphedTrainStep(m, opt, 1, reducer=red, accumulate=2)
+        step([[_grid(40 + 2 * rank)], [_grid(41 + 2 * rank)]], [_mask(9), _mask(10)])
+        torch.cuda.synchronize()
+        assert step._gb and step._g2 is not None, "the split data-parallel step"
+        assert len(calls) == len(set(calls)) == 1 + len(step._gb), f"every gradient range exchanged once per optimizer step: {calls}"
+        flat = m._flat.detach().cpu()
+        both = [torch.empty_like(flat) for _ in range(world)]
+        dist.all_gather(both, flat)
+        assert torch.equal(both[0], both[1]), (both[0] - both[1]).abs().max()
+        q.put((rank, "ok", flat.numpy() if rank == 0 else None))      # numpy: pickled by value
+    except Exception:  # noqa: BLE001
+        import traceback
+        q.put((rank, traceback.format_exc(), None))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_two_ranks_accumulating_match_the_hand_average_of_four():
+    """two ranks on one GPU over gloo, split-graph mode, fp32 buckets, accumulate = 2: rank r's micro-batches are grids 40 + 2r and 41 + 2r.  One optimizer
+    step; both ranks end bit-identical (asserted in the workers) and equal the single-process hand average of the four gradients"""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = 29800 + (os.getpid() % 2000)
+    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    try:
+        res = [q.get(timeout=300) for _ in procs]
+    except queue.Empty:
+        for p in procs:
+            p.terminate()
+        pytest.fail("a rank did not report within 300 s: both terminated")
+    for p in procs:
+        p.join(60)
+    flat2 = None
+    for rank, msg, flat in res:
+        assert msg == "ok", f"rank {rank}: {msg}"
+        if flat is not None:
+            flat2 = torch.from_numpy(flat)
+    (ref_p, _, _), = _hand_average([(40, _mask(9)), (41, _mask(10)), (42, _mask(9)), (43, _mask(10))], 1)
+    err = _perr(flat2, ref_p)
+    print(f"  [2 ranks x accumulate 2] parameters against the hand average of four: {err:.2e}")
+    assert err < PTOL
+
+
+def test_collectives_inside_the_graph_are_refused_with_accumulation(monkeypatch):
+    from nerf_mae_amd.dist import GradReducer
+    from nerf_mae_amd.trainer import FusedAdamW, GraphedTrainStep
+    m = _build()
+    monkeypatch.setenv("NMH_DP_CAPTURE_COMM", "1")
+    with pytest.raises(ValueError, match="NMH_DP_CAPTURE_COMM"):
+        GraphedTrainStep(m, FusedAdamW(m, **OPT), 1, reducer=GradReducer(m), accumulate=2)
+    GraphedTrainStep(m, FusedAdamW(m, **OPT), 1, reducer=GradReducer(m))       # without accumulation it is taken as before
+
+
+# ---- 9. the epoch loop --------------------------------------------------------------------------------------------------------------------------------------
+def test_trainer_counts_optimizer_steps_and_refuses_a_resume_under_another_k(tmp_path):
+    from nerf_mae_amd import data
+    from nerf_mae_amd.model import SwinTransformer_MAE3D
+    from nerf_mae_amd.trainer import Trainer, save_checkpoint
+
+    def model():
+        torch.manual_seed(0)
+        return SwinTransformer_MAE3D(patch_size=[4] * 3, window_size=[4] * 3, resolution=32, masking_prob=0.75, stochastic_depth_prob=0.1,
+                                     compute_dtype=torch.float32, **TINY).cuda()
+
+    scenes = [data.synthetic_scene((32, 32, 32), i) for i in range(5)]
+    kw = dict(batch_size=1, num_epochs=1, lr=1e-3, log=lambda s: None)
+    tr = Trainer(model(), scenes, accumulate=2, **kw)
+    assert tr.steps_per_epoch == 3 and tr.micro_per_epoch == 5 and tr.sched.total == 3
+    assert tr.args["accumulate"] == 2 and tr.args["batch_size"] == 2
+    before = tr.model._flat.detach().clone()
+    hist = tr.fit()
+    torch.cuda.synchronize()
+    assert tr.global_step == 3 and tr.opt.t == 3
+    assert tr.opt.grad_scale == 1.0, "the epoch's last step had one micro-batch"
+    assert np.isfinite(hist[0]["train_loss"]) and hist[0]["train_loss"] > 0
+    assert not torch.equal(before, tr.model._flat) and not tr.model._flat_grad.any()
+    path = str(tmp_path / "acc.pt")
+    save_checkpoint(path, tr.model, 1, tr.args, tr.opt, tr.global_step)
+    with pytest.raises(RuntimeError, match="accumulate"):
+        Trainer(model(), scenes, accumulate=1, **kw).resume(path)
+    tr2 = Trainer(model(), scenes, accumulate=2, **dict(kw, num_epochs=2))
+    ck = tr2.resume(path)
+    assert ck["resume"]["accumulate"] == 2 and ck["train_args"]["accumulate"] == 2
+    assert tr2.start_epoch == 2 and tr2.global_step == 3 and tr2.opt.t == 3
+    assert torch.equal(tr2.model._flat, tr.model._flat) and torch.equal(tr2.opt.m, tr.opt.m)
