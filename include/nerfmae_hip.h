@@ -363,6 +363,15 @@ NMH_API int nmh_mae_tail_fwd(int dt, const void* y, const float* stats, const vo
 NMH_API int64_t nmh_tail_residual_pack_numel(void);
 NMH_API int nmh_tail_residual_pack(const float* pack_ws, void* Wr, void* stream);
 NMH_API int nmh_mae_tail_fwd_from_coarse(int dt, const void* y, const float* stats, const void* xcoarse, const void* Wr, const float* bt, const float* Wout, const float* bout, const float* target, const int* extents, const unsigned char* tokmask, int B, int R, int C, double* sums, float* losses, float* pred, float* dpred, float slope, double* bwd_sums, unsigned char* sign_mask, void* stream);
+/* nmh_mae_tail_fwd_from_coarse over the valid box of each sample alone: ceil(extent / 4) coarse cells per axis.  PRECONDITION: target is zero outside the
+ * extents (zero-padded scenes).  d(pred) is then exactly zero in the padding and contributes nothing to the losses, their counts, or bwd_sums, so the pass
+ * neither visits nor WRITES it: dpred and sign_mask keep their old content outside the box, and only nmh_mae_tail_bwd_box may read them.  Inside the box
+ * every byte equals the full walk's; the sums differ by the order of their fp32 partials.  pred must be NULL (-4). */
+NMH_API int nmh_mae_tail_fwd_from_coarse_box(int dt, const void* y, const float* stats, const void* xcoarse, const void* Wr, const float* bt, const float* Wout, const float* bout, const float* target, const int* extents, const unsigned char* tokmask, int B, int R, int C, double* sums, float* losses, float* pred, float* dpred, float slope, double* bwd_sums, unsigned char* sign_mask, void* stream);
+/* The single apply pass of nmh_mae_tail_bwd (bwd_sums and sign_mask given, bf16, 48 channels) behind nmh_mae_tail_fwd_from_coarse_box: a voxel outside
+ * its sample's box takes d(pred) = 0 without reading dpred or sign_mask there (dy = rstd (-S1/V - xhat S2/V), dr = 0, as the full walk gives).
+ * extents: the same device array [B][3]; V = R^3, R a multiple of 4, R <= 256. */
+NMH_API int nmh_mae_tail_bwd_box(int dt, const void* y, const float* stats, const float* dpred, const double* loss_sums, const float* Wout, double* in_sums, void* dy, void* dr, float slope, float* dWout, float* dbout, int B, int R, int C, const double* bwd_sums, const unsigned char* sign_mask, const int* extents, void* stream);
 /* Backward of the decoder tail d0 = lrelu(IN(y) + r) -> 1x1 head -> loss in two elementwise passes that never materialise d(d0)
  * (swin_mae3d.py:1496-1549 + unetr_block.py:62-71 backward): d(d0) = Wout^T dpred is recomputed per element from dpred/loss_sums
  * (both from nmh_mae_loss_fwd).  in_sums[b][c] = {sum g, sum g*yhat}, dy = IN-backward, dr = g; dWout/dbout accumulate the head

@@ -524,6 +524,24 @@ int nmh_mae_tail_fwd_from_coarse(int dt, const void* y, const float* stats, cons
   if (rc) return rc;
   return k_loss_finalize(sums, losses, ST);
 }
+int nmh_mae_tail_fwd_from_coarse_box(int dt, const void* y, const float* stats, const void* xcoarse, const void* Wr, const float* bt, const float* Wout, const float* bout,
+                                     const float* target, const int* extents, const unsigned char* tokmask, int B, int R, int C, double* sums, float* losses, float* pred,
+                                     float* dpred, float slope, double* bwd_sums, unsigned char* sign_mask, void* stream) {
+  CLR();
+  REQ(y, stats, xcoarse, Wr, bt, Wout, bout, target, extents, tokmask, sums, losses, dpred, bwd_sums, sign_mask);
+  if (pred) return -4;   // the box walk leaves the padding unwritten
+  LossArgs a{dt, nullptr, Wout, bout, target, extents, tokmask, B, R, C, sums, nullptr, dpred, bwd_sums, sign_mask};
+  int rc = k_tail_fwd_coarse(a, y, stats, xcoarse, Wr, bt, slope, ST, true);
+  if (rc) return rc;
+  return k_loss_finalize(sums, losses, ST);
+}
+int nmh_mae_tail_bwd_box(int dt, const void* y, const float* stats, const float* dpred, const double* loss_sums, const float* Wout, double* in_sums, void* dy, void* dr,
+                         float slope, float* dWout, float* dbout, int B, int R, int C, const double* bwd_sums, const unsigned char* sign_mask, const int* extents,
+                         void* stream) {
+  CLR();
+  REQ(y, stats, dpred, loss_sums, Wout, in_sums, dy, dr, dWout, dbout, bwd_sums, sign_mask, extents);
+  return k_tail_bwd(dt, nullptr, nullptr, y, stats, dpred, loss_sums, Wout, in_sums, dy, dr, slope, dWout, dbout, B, (long)R * R * R, C, bwd_sums, ST, sign_mask, extents, R);
+}
 int nmh_mae_tail_bwd(int dt, const void* d0, const void* r, const void* y, const float* stats, const float* dpred, const double* loss_sums, const float* Wout, double* in_sums,
                      void* dy, void* dr, float slope, float* dWout, float* dbout, int B, int64_t V, int C, const double* bwd_sums, const unsigned char* sign_mask,
                      void* stream) {

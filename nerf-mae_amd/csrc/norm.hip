@@ -5,6 +5,7 @@
 // unetr_block.py:57-71 (IN eps=1e-5, no affine; LeakyReLU 0.01).
 #include "common.hpp"
 #include "kernels.hpp"
+#include "tail_box.hpp"
 #include <cstdlib>
 #include <type_traits>
 
@@ -1006,11 +1007,15 @@ int k_in_bwd_apply_bg(int dt, const void* dout, const void* x, const float* stat
 // written by the loss forward) instead of being written by one kernel and re-read by two.  Pass 0 (APPLY=0): IN-backward sums
 // {sum g, sum g*xhat} with g = d(d0) * lrelu'(d0), plus the head weight gradient dW[o][c] = sum_v dp[v][o] d0[v][c];
 // pass 1 (APPLY=1): dx = rstd (g - S1/V - xhat S2/V), dr = g.  Same thread mapping as the InstanceNorm kernels above.
+// extents != nullptr (the apply pass behind tail_fwd_coarse_kernel<true>, with the sign mask): d(pred) and the sign mask exist inside each sample's box of cells alone
+// (tail_box.hpp).  A voxel row outside it reads voxel 0 of its sample instead -- the same loads at an address that stays in cache, no branch around them -- and takes
+// d = 0: dx = rstd (-u1 - xhat u2), dr = 0, what the full walk's zero d(pred) row gives.  A run-time argument of the SAME instantiation, not a template parameter:
+// two instantiations contract the four-term head dot product differently (a bf16 tie of the last place here and there), one gives the same bits in both modes.
 template <typename T, int APPLY, bool ST = false, bool NT = false>
 __global__ __launch_bounds__(256, ST ? 4 : 1) void tail_bwd_kernel(const T* __restrict__ d0, const T* __restrict__ rres, const T* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ dp,
                                                        const double* __restrict__ lsums, const float* __restrict__ Wout, double* in_sums, T* __restrict__ dx,
                                                        T* __restrict__ dr, float slope, float* dWout, float* dbout, long V, int C, long vpb,
-                                                       const unsigned char* __restrict__ smask) {
+                                                       const unsigned char* __restrict__ smask, const int* __restrict__ extents = nullptr, unsigned R = 0u, unsigned mR = 0u) {
   extern __shared__ float sred[];  // [6][C]
   const int CL = C >> 3, NV = 256 / CL;
   const int cl = threadIdx.x % CL, vl = threadIdx.x / CL, b = blockIdx.y;
@@ -1054,6 +1059,11 @@ __global__ __launch_bounds__(256, ST ? 4 : 1) void tail_bwd_kernel(const T* __re
       }
     }
   }
+  unsigned bz = ~0u, by = ~0u, bx = ~0u;   // the sample's box in voxels (no extents: everything is inside)
+  if (APPLY && extents) {
+    const TailBox tb = tail_box_make(extents[b * 3], extents[b * 3 + 1], extents[b * 3 + 2], (int)(R >> 2));
+    bz = 4u * tb.Ez; by = 4u * tb.Ey; bx = 4u * tb.Ex;
+  }
   if (vl < NV) {
     const long v0 = (long)blockIdx.x * vpb;
     long v1 = v0 + vpb;
@@ -1069,17 +1079,20 @@ __global__ __launch_bounds__(256, ST ? 4 : 1) void tail_bwd_kernel(const T* __re
         const long v = vb + (long)u * NV;
         if (v < v1) {
           const long o = ((long)b * V + v) * C + cl * 8;
+          const bool inb = !APPLY || tail_box_has_voxel((unsigned)v, R, mR, bz, by, bx);
+          const long vm = (long)b * V + (inb ? v : 0L);   // the row whose d(pred) and sign byte are read
           if (ST) {
-            const uint2 mw = *reinterpret_cast<const uint2*>(smask + ((long)b * V + v) * 8);
+            const uint2 mw = *reinterpret_cast<const uint2*>(smask + vm * 8);
             mb[u] = ((cl < 4 ? mw.x : mw.y) >> (8 * (cl & 3))) & 0xffu;
           } else if (APPLY && smask) {   // only the sign of d0 is needed (the sums came out of the forward pass): one byte instead of 16
-            const uint2 mw = *reinterpret_cast<const uint2*>(smask + ((long)b * V + v) * 8);   // 8-byte rows (C = 48: 6 used), one load per voxel row
+            const uint2 mw = *reinterpret_cast<const uint2*>(smask + vm * 8);   // 8-byte rows (C = 48: 6 used), one load per voxel row
             const unsigned m8 = ((cl < 4 ? mw.x : mw.y) >> (8 * (cl & 3))) & 0xffu;
 #pragma unroll
             for (int j = 0; j < 8; ++j) ov[ST ? 0 : u][j] = (m8 >> j) & 1u ? 1.0f : -1.0f;
           } else Vec8<T>::load((d0 ? d0 : rres) + o, ov[ST ? 0 : u]);
           if (NT) Vec8<T>::load_nt(x + o, xv[u]); else Vec8<T>::load(x + o, xv[u]);
-          dq[u] = *reinterpret_cast<const float4*>(dp + ((long)b * V + v) * 4);
+          dq[u] = *reinterpret_cast<const float4*>(dp + vm * 4);
+          if (APPLY && !inb) dq[u] = make_float4(0.f, 0.f, 0.f, 0.f);
           if (!ST && !d0 && !(APPLY && smask)) {  // d0 was not stored by the forward: rebuild it bit-exactly (same fp32 expression, same rounding) from x and r
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -1152,11 +1165,15 @@ __global__ void tail_sums_finalize_kernel(const double* __restrict__ bs, const d
   }
 }
 int k_tail_bwd(int dt, const void* d0, const void* r, const void* xin, const float* in_stats, const float* dp, const double* loss_sums, const float* Wout, double* in_sums,
-               void* dx, void* dr, float slope, float* dWout, float* dbout, int B, long V, int C, const double* bwd_sums, hipStream_t st, const unsigned char* sign_mask) {
+               void* dx, void* dr, float slope, float* dWout, float* dbout, int B, long V, int C, const double* bwd_sums, hipStream_t st, const unsigned char* sign_mask,
+               const int* extents, int R) {
   if (C % 8 || C / 8 > 256 || (!d0 && !r && !(sign_mask && bwd_sums))) return -2;
   if (sign_mask && (!bwd_sums || C != 48)) return -4;   // the sums pass needs d0 itself; the mask has 8-byte rows for 48 channels
   const long vpb = in_vox_per_block(V, B);
   const bool nt = bwd_sums && sign_mask && in_apply_streaming(V, B, C, dt);
+  // extents: d(pred) and the sign mask were written inside each sample's box alone (k_tail_fwd_coarse with box) -- the single apply pass with the sign mask only
+  if (extents && (!bwd_sums || !sign_mask || dt != NMH_DT_BF16 || R % 4 || R < 4 || R > 256 || (long)R * R * R != V)) return -4;
+  const unsigned mR = extents ? (unsigned)((0x100000000ULL + (unsigned)R - 1) / (unsigned)R) : 0u;
   static const int tail_sv = getenv("NMH_TAIL_STREAM_VPB") ? atoi(getenv("NMH_TAIL_STREAM_VPB")) : 0;
   const long vpa = nt && tail_sv > 0 ? tail_sv : in_apply_vpb(V, B, C, nt, 16);   // (round 5, four waves per SIMD: 1.93 ms with 16, 1.98 / 1.99 / 2.04 with 32 / 64 / 128)
   dim3 g0((unsigned)((V + vpb - 1) / vpb), B), g1((unsigned)((V + vpa - 1) / vpa), B);
@@ -1165,13 +1182,13 @@ int k_tail_bwd(int dt, const void* d0, const void* r, const void* xin, const flo
     hipLaunchKernelGGL(tail_sums_finalize_kernel, dim3((n + 255) / 256), dim3(256), 0, st, bwd_sums, loss_sums, in_sums, dWout, dbout, B, C);
     if (nt && in_stream_nt())
       hipLaunchKernelGGL((tail_bwd_kernel<bf16_t, 1, true, true>), g1, dim3(256), 0, st, (const bf16_t*)d0, (const bf16_t*)r, (const bf16_t*)xin, in_stats, dp, loss_sums, Wout, in_sums, (bf16_t*)dx,
-                         (bf16_t*)dr, slope, dWout, dbout, V, C, vpa, sign_mask);
+                         (bf16_t*)dr, slope, dWout, dbout, V, C, vpa, sign_mask, extents, (unsigned)R, mR);
     else if (nt)
       hipLaunchKernelGGL((tail_bwd_kernel<bf16_t, 1, true, false>), g1, dim3(256), 0, st, (const bf16_t*)d0, (const bf16_t*)r, (const bf16_t*)xin, in_stats, dp, loss_sums, Wout, in_sums, (bf16_t*)dx,
-                         (bf16_t*)dr, slope, dWout, dbout, V, C, vpa, sign_mask);
+                         (bf16_t*)dr, slope, dWout, dbout, V, C, vpa, sign_mask, extents, (unsigned)R, mR);
     else if (dt == NMH_DT_BF16)
       hipLaunchKernelGGL((tail_bwd_kernel<bf16_t, 1>), g1, dim3(256), 0, st, (const bf16_t*)d0, (const bf16_t*)r, (const bf16_t*)xin, in_stats, dp, loss_sums, Wout, in_sums, (bf16_t*)dx,
-                         (bf16_t*)dr, slope, dWout, dbout, V, C, vpa, sign_mask);
+                         (bf16_t*)dr, slope, dWout, dbout, V, C, vpa, sign_mask, extents, (unsigned)R, mR);
     else
       hipLaunchKernelGGL((tail_bwd_kernel<float, 1>), g1, dim3(256), 0, st, (const float*)d0, (const float*)r, (const float*)xin, in_stats, dp, loss_sums, Wout, in_sums, (float*)dx,
                          (float*)dr, slope, dWout, dbout, V, C, vpa, sign_mask);
@@ -1656,6 +1673,11 @@ __global__ __launch_bounds__(256) void tail_fwd_mfma_kernel(const bf16_t* __rest
 #ifndef TAILC_RS
 #define TAILC_RS 112
 #endif
+// BOX (round 7): the walk covers the cells of the sample's valid box alone (tail_box.hpp) -- the target is zero outside the extents (the caller's word), so d(pred) is
+// exactly zero there and neither the sums nor the backward (tail_bwd_kernel with extents) need those voxels; nothing is written outside the box.  The workgroup's
+// share is its part of the BOX's cell count, a step is 16 consecutive box cells, and the last step of a sample may be short: its surplus lanes are clamped
+// to the sample's last box cell (no branch around a load), contribute nothing (rm = occ = false) and store nothing.
+template <bool BOX>
 __global__ __launch_bounds__(512) void tail_fwd_coarse_kernel(const bf16_t* __restrict__ x, const float* __restrict__ stats, const bf16_t* __restrict__ xcoarse,
                                                               const bf16_t* __restrict__ Wr, const float* __restrict__ bt, LossArgs a, long V, float slope, int cpb,
                                                               unsigned mg1, unsigned mg2) {
@@ -1664,6 +1686,13 @@ __global__ __launch_bounds__(512) void tail_fwd_coarse_kernel(const bf16_t* __re
   __shared__ float sacc[8];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), vi = lane & 15, g = lane >> 4;
   const int h = wave >> 2, wq = wave & 3, cls = blockIdx.y, dz = cls >> 2, dy = cls & 3, b = blockIdx.z;
+  TailBox tb = {};
+  unsigned kbeg = 0u, kend = 0u;
+  if (BOX) {   // per workgroup, in scalars: the box, its two magic numbers and this workgroup's share of it
+    tb = tail_box_make(a.extents[b * 3], a.extents[b * 3 + 1], a.extents[b * 3 + 2], a.R >> 2);
+    tail_box_range(tb.n, gridDim.x, blockIdx.x, kbeg, kend);
+    if (kbeg >= kend) return;   // (the whole workgroup: a box smaller than the grid's ranges)
+  }
   char* const wl = smem + WBYTES + wave * WLDS;
   unsigned char* const sm = reinterpret_cast<unsigned char*>(smem) + WBYTES + NW * WLDS + wave * 256;
   char* const dT = smem + WBYTES + NW * WLDS + NW * 256 + wave * 256;
@@ -1723,23 +1752,36 @@ __global__ __launch_bounds__(512) void tail_fwd_coarse_kernel(const bf16_t* __re
   //   chunk arithmetic;  T: the targets (HBM), requested in step k - 2 behind its loss part -- the HBM streams are a step and a half ahead
   //   (round 6: with everything one step ahead the pass moved 2.3 TB/s -- fewer bytes in flight per wave than the pass that also read r, at the same latency)
   struct OpsB { uint4 xc[3]; unsigned tm, vox; int ins; };
-  struct OpsX { uint4 xa[2]; uint2 xb[2]; unsigned v0; int ins; };   // v0 / ins: voxel index and extent test of the cells requested last (passed on to that step's B set)
+  struct OpsX { uint4 xa[2]; uint2 xb[2]; unsigned v0; int ins; unsigned cell; };   // v0 / ins: voxel index and extent test of the cells requested last (passed on to that step's B set)
+  //                                                                                   BOX: + the lane's grid cell; ins bit 0: inside the extents, bit 1: a cell of the box (not a surplus lane)
   struct OpsT { float tg[4]; };
   OpsB Bq[2]; OpsX Xq[2]; OpsT Tq[2];
-  auto issueB = [&](unsigned c0, unsigned v0, int ins, OpsB& o) {   // (v0, ins): as computed when the step's y2 rows were requested
-    const unsigned cell = c0 + (unsigned)vi;
-    o.vox = v0; o.ins = ins;
+  auto issueB = [&](unsigned c0, const OpsX& nx, OpsB& o) {   // nx: the X set whose y2 rows were requested for that step (voxel, extent test, BOX: grid cell)
+    const unsigned cell = BOX ? nx.cell : c0 + (unsigned)vi;
+    o.vox = nx.v0; o.ins = nx.ins;
     const char* const pc = cs_ + (unsigned long)cell * 192u + 16 * g;
     o.xc[0] = *reinterpret_cast<const uint4*>(pc); o.xc[1] = *reinterpret_cast<const uint4*>(pc + 64); o.xc[2] = *reinterpret_cast<const uint4*>(pc + 128);
     o.tm = a.tokmask[cell];
   };
   auto issueX = [&](unsigned c0, OpsX& o) {
-    const unsigned cell = c0 + (unsigned)vi;
-    const unsigned zc = __umulhi(cell, mg2), rem = cell - zc * gd2, yc = __umulhi(rem, mg1), xc_ = rem - yc * gd;
+    unsigned zc, yc, xc_;
+    bool live = true;
+    if (BOX) {
+      const unsigned k = c0 + (unsigned)vi;
+      live = k < tb.n;
+      tail_box_unravel(tb, live ? k : tb.n - 1u, zc, yc, xc_);
+      o.cell = (zc * gd + yc) * gd + xc_;
+    } else {
+      const unsigned cell = c0 + (unsigned)vi;
+      zc = __umulhi(cell, mg2);
+      const unsigned rem = cell - zc * gd2;
+      yc = __umulhi(rem, mg1); xc_ = rem - yc * gd;
+    }
     const unsigned zf = 4u * zc + (unsigned)dz, yf = 4u * yc + (unsigned)dy, xf = 4u * xc_ + 2u * (unsigned)h;
     const unsigned v0 = (zf * Ru + yf) * Ru + xf;
     o.v0 = v0;
     o.ins = ((int)zf < e0 && (int)yf < e1 && (int)xf + tl < e2) ? 1 : 0;
+    if (BOX) o.ins = live ? o.ins | 2 : 0;
     const char* const p = xs_ + (unsigned long)v0 * 96u;
     o.xa[0] = *reinterpret_cast<const uint4*>(p + 16 * g); o.xa[1] = *reinterpret_cast<const uint4*>(p + 96 + 16 * g);
     o.xb[0] = *reinterpret_cast<const uint2*>(p + 64 + 8 * g); o.xb[1] = *reinterpret_cast<const uint2*>(p + 160 + 8 * g);
@@ -1792,7 +1834,7 @@ __global__ __launch_bounds__(512) void tail_fwd_coarse_kernel(const bf16_t* __re
     *reinterpret_cast<uint2*>(p + 2 * OPB) = make_uint2(xpk.x, xpk.y); *reinterpret_cast<uint2*>(p + 2 * OPB + 16 * RS) = make_uint2(xpk.z, xpk.w);
     *reinterpret_cast<uint2*>(p + 3 * OPB) = make_uint2(ypk.x, ypk.y); *reinterpret_cast<uint2*>(p + 3 * OPB + 16 * RS) = make_uint2(ypk.z, ypk.w);
   };
-  const unsigned cbeg = blockIdx.x * (unsigned)cpb, cend = cbeg + (unsigned)cpb < ncell ? cbeg + (unsigned)cpb : ncell;
+  const unsigned cbeg = BOX ? kbeg : blockIdx.x * (unsigned)cpb, cend = BOX ? kend : (cbeg + (unsigned)cpb < ncell ? cbeg + (unsigned)cpb : ncell);
   auto step = [&](unsigned c0, auto parity) {
     constexpr int PS = decltype(parity)::value;
     const OpsB& o = Bq[PS];
@@ -1800,7 +1842,7 @@ __global__ __launch_bounds__(512) void tail_fwd_coarse_kernel(const bf16_t* __re
     OpsT& ot = Tq[PS];
     // (requests past the wave's last step re-read the current one's addresses: no branch around a load -- with one the compiler can no longer count the loads in
     //  flight and waits for all but the newest in front of the first use of this step's operands)
-    issueB(c0 + 64u < cend ? c0 + 64u : c0, Xq[PS ^ 1].v0, Xq[PS ^ 1].ins, Bq[PS ^ 1]);   // (the other X set still holds the next step's cells)
+    issueB(c0 + 64u < cend ? c0 + 64u : c0, Xq[PS ^ 1], Bq[PS ^ 1]);   // (the other X set still holds the next step's cells)
     // the residual of both tiles: r[t][cb] = lane (cell vi, g): channels chan(cb, 4g + i)
     Frag<bf16_t> xcf[3];
 #pragma unroll
@@ -1846,15 +1888,16 @@ __global__ __launch_bounds__(512) void tail_fwd_coarse_kernel(const bf16_t* __re
     if (g < 2) {   // lane (vi, g): the four outputs of voxel o.vox + g
       const long vq = (long)o.vox + g;
       const float p0 = P[0] + bo0, p1 = P[1] + bo1, p2 = P[2] + bo2, p3 = P[3] + bo3;
-      const bool occ = ot.tg[3] > 0.01f, rm = o.tm != 0u && o.ins != 0;
+      const bool live = !BOX || (o.ins & 2) != 0;
+      const bool occ = ot.tg[3] > 0.01f && live, rm = o.tm != 0u && (BOX ? (o.ins & 1) != 0 : o.ins != 0);
       const float d0f = p0 - ot.tg[0], d1f = p1 - ot.tg[1], d2f = p2 - ot.tg[2];
       const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-p3)), d3f = sg - ot.tg[3];
       const float q0 = occ ? 2.f * d0f : 0.f, q1 = occ ? 2.f * d1f : 0.f, q2 = occ ? 2.f * d2f : 0.f, q3 = rm ? 2.f * sg * (1.f - sg) * d3f : 0.f;
       l_rgb += occ ? d0f * d0f + d1f * d1f + d2f * d2f : 0.f; l_a += rm ? d3f * d3f : 0.f;
       n_rgb += occ ? 1.f : 0.f; n_a += rm ? 1.f : 0.f;
       ds0 += q0; ds1 += q1; ds2 += q2; ds3 += q3;
-      *reinterpret_cast<float4*>(a.dp + ((long)b * V + vq) * 4) = make_float4(q0, q1, q2, q3);
-      if (a.pred) { a.pred[((long)b * 4 + 0) * V + vq] = p0; a.pred[((long)b * 4 + 1) * V + vq] = p1; a.pred[((long)b * 4 + 2) * V + vq] = p2; a.pred[((long)b * 4 + 3) * V + vq] = p3; }
+      if (live) *reinterpret_cast<float4*>(a.dp + ((long)b * V + vq) * 4) = make_float4(q0, q1, q2, q3);
+      if (!BOX && a.pred) { a.pred[((long)b * 4 + 0) * V + vq] = p0; a.pred[((long)b * 4 + 1) * V + vq] = p1; a.pred[((long)b * 4 + 2) * V + vq] = p2; a.pred[((long)b * 4 + 3) * V + vq] = p3; }
       bf16_t* const dt_ = reinterpret_cast<bf16_t*>(dT) + g * 16 + vi;   // [o][tile][16]
       const unsigned q01 = pk_bf16(q0, q1), q23 = pk_bf16(q2, q3);
       dt_[0] = (bf16_t)(q01 & 0xffffu); dt_[32] = (bf16_t)(q01 >> 16); dt_[64] = (bf16_t)(q23 & 0xffffu); dt_[96] = (bf16_t)(q23 >> 16);
@@ -1862,7 +1905,7 @@ __global__ __launch_bounds__(512) void tail_fwd_coarse_kernel(const bf16_t* __re
     issueT(ox.v0, ot);   // (ox.v0: already that of the step after next)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if (lane < 32)   // lane = 16 tile + cell
+    if (lane < 32 && (!BOX || (o.ins & 2) != 0))   // lane = 16 tile + cell
       *reinterpret_cast<uint2*>(a.sign_mask + ((long)b * V + o.vox + g) * 8) = *reinterpret_cast<const uint2*>(sm + lane * 8);
     Frag<bf16_t> df;
     {
@@ -1887,7 +1930,7 @@ __global__ __launch_bounds__(512) void tail_fwd_coarse_kernel(const bf16_t* __re
   {
     unsigned c0 = cbeg + 16u * (unsigned)wq;
     if (c0 < cend) {
-      issueX(c0, Xq[0]); issueB(c0, Xq[0].v0, Xq[0].ins, Bq[0]); issueT(Xq[0].v0, Tq[0]);
+      issueX(c0, Xq[0]); issueB(c0, Xq[0], Bq[0]); issueT(Xq[0].v0, Tq[0]);
       issueX(c0 + 64u < cend ? c0 + 64u : c0, Xq[1]); issueT(Xq[1].v0, Tq[1]);
       for (; c0 + 64u < cend; c0 += 128u) {   // two steps per trip: straight-line code between the requests and their uses
         step(c0, std::integral_constant<int, 0>{});
@@ -1958,9 +2001,12 @@ int k_tail_r_pack(const float* ws, void* Wr, hipStream_t st) {
   return 0;
 }
 // training pass only (d(pred), the backward sums and the sign mask are all written): bf16, 48 channels, R a multiple of 4 with (R/4)^3 a multiple of 16, R <= 256
-int k_tail_fwd_coarse(const LossArgs& a, const void* x, const float* stats, const void* xcoarse, const void* Wr, const float* bt, float slope, hipStream_t st) {
+// box: walk the valid box of each sample alone (the target must be zero outside the extents; d(pred) and the sign mask are then NOT written outside the box, and
+// pred cannot be asked for)
+int k_tail_fwd_coarse(const LossArgs& a, const void* x, const float* stats, const void* xcoarse, const void* Wr, const float* bt, float slope, hipStream_t st, bool box) {
   const long V = (long)a.R * a.R * a.R;
   const int gd = a.R / 4;
+  if (box && a.pred) return -4;
   if (a.dt != NMH_DT_BF16 || a.Cd != 48 || a.R % 4 || a.R > 256 || ((long)gd * gd * gd) % 16 || !a.dp || !a.bwd_sums || !a.sign_mask || !(slope > 0.f && slope < 1.f)) return -4;
   hipError_t e = nmh_zero_async(a.sums, 8 * sizeof(double), st);
   if (e != hipSuccess) return (int)e;
@@ -1969,7 +2015,9 @@ int k_tail_fwd_coarse(const LossArgs& a, const void* x, const float* stats, cons
   constexpr int LDS = 36 * 1024 + 8 * 4 * 32 * TAILC_RS + 8 * 256 + 8 * 256 + 6 * 1024;
   static NmhPerDeviceOnce attr_set;
   if (attr_set.need()) {
-    e = hipFuncSetAttribute((const void*)tail_fwd_coarse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    e = hipFuncSetAttribute((const void*)tail_fwd_coarse_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    if (e != hipSuccess) return (int)e;
+    e = hipFuncSetAttribute((const void*)tail_fwd_coarse_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     if (e != hipSuccess) return (int)e;
     attr_set.set();
   }
@@ -1979,7 +2027,10 @@ int k_tail_fwd_coarse(const LossArgs& a, const void* x, const float* stats, cons
   if (cpb > (ncell + 63) / 64 * 64) cpb = (ncell + 63) / 64 * 64;
   const unsigned mg1 = (unsigned)((0x100000000ULL + (unsigned)gd - 1) / (unsigned)gd), mg2 = (unsigned)((0x100000000ULL + (unsigned)(gd * gd) - 1) / (unsigned)(gd * gd));
   dim3 grid((unsigned)((ncell + cpb - 1) / cpb), 16, a.B);
-  hipLaunchKernelGGL(tail_fwd_coarse_kernel, grid, dim3(512), LDS, st, (const bf16_t*)x, stats, (const bf16_t*)xcoarse, (const bf16_t*)Wr, bt, a, V, slope, cpb, mg1, mg2);
+  if (box)   // (the same grid: a workgroup takes its share of the box's cells instead of cpb grid cells)
+    hipLaunchKernelGGL(tail_fwd_coarse_kernel<true>, grid, dim3(512), LDS, st, (const bf16_t*)x, stats, (const bf16_t*)xcoarse, (const bf16_t*)Wr, bt, a, V, slope, cpb, mg1, mg2);
+  else
+    hipLaunchKernelGGL(tail_fwd_coarse_kernel<false>, grid, dim3(512), LDS, st, (const bf16_t*)x, stats, (const bf16_t*)xcoarse, (const bf16_t*)Wr, bt, a, V, slope, cpb, mg1, mg2);
   NMH_CHECK_LAUNCH();
   return 0;
 }

@@ -279,11 +279,12 @@ class UpSwitches(NamedTuple):
     side_stream: bool
     c48mb_min_voxels: int
     c64_min_voxels: int
+    tail_box: bool = True
 
     @classmethod
     def current(cls) -> "UpSwitches":
         return cls(ops.TAIL_FROM_COARSE, ops.TAIL_SIGN_MASK, ops.CCONV_WGRAD, ops.CCONV_CENTERED, ops.C48_BWD_REDUCE, ops.INBWD_BG, ops.DEFER_DECODER_WGRAD,
-                   ops.side_stream.enabled, ops.C48MB_MIN_VOXELS, ops.C64_MIN_VOXELS)
+                   ops.side_stream.enabled, ops.C48MB_MIN_VOXELS, ops.C64_MIN_VOXELS, ops.TAIL_BOX)
 
 
 # conv family -> packed layouts of (conv1 forward, conv1 input gradient, conv2 forward, conv2 input gradient), in order of preference
@@ -331,12 +332,18 @@ class UpPlan(NamedTuple):
     wgrad_main_stream: bool
     defer_conv_wgrad: bool   # small-level conv weight gradients: queued on the encoder's weight-gradient queue and issued with its next flush, one fork for all of them
     defer_upconv_wgrad: bool # the transpose conv's weight gradient likewise (decoder1 too: only its conv weight gradients stay out of the queue)
+    # residual_in_tail on a batch whose target is ZERO outside each sample's extents (the model padded it: forward / forward_static), no pred asked for: the tail
+    # forward walks, and the tail backward reads d(pred) and the sign mask in, the valid box of each sample alone -- d(pred) is exactly zero in the padding
+    # (csrc/tail_box.hpp); neither is written outside the box
+    tail_box: bool = False
 
 
 def plan_up_block(cin: int, cout: int, k: int, has_proj: bool, layouts, dec1, B: int, v: int, dtype, x_grad: bool, tail: bool, tail_sums: bool,
-                  has_queue: bool, sw: UpSwitches) -> UpPlan:
+                  has_queue: bool, sw: UpSwitches, tail_pred: bool = False, tail_zero_padded: bool = False) -> UpPlan:
     """layouts: the keys of _CONV_LAYOUTS' rows packed for the block; dec1: `_Dec1Pack.optional()` of the record built for THIS block, or None;
-    tail / tail_sums: a loss tail is attached / its model's fuse_tail_sums; has_queue: the block has a weight-gradient queue.  Pure: plain values in, UpPlan out."""
+    tail / tail_sums: a loss tail is attached / its model's fuse_tail_sums; has_queue: the block has a weight-gradient queue; tail_pred: the tail is asked for
+    pred; tail_zero_padded: the caller vouches that the tail's target is zero outside each sample's extents -- the precondition of `tail_box`, true where the
+    model pads the batch itself (forward, forward_static behind the batcher) and nowhere else.  Pure: plain values in, UpPlan out."""
     S = v * k
     bf16 = dtype == torch.bfloat16
     fits = S ** 3 * (2 * cout if has_proj else cout) * 2 < 2 ** 32
@@ -357,7 +364,8 @@ def plan_up_block(cin: int, cout: int, k: int, has_proj: bool, layouts, dec1, B:
     return UpPlan(family, *_CONV_LAYOUTS[family], proj=has_proj, epilogue_stats=main, composed_fwd=composed_fwd, composed_bwd=composed_bwd, centered=centered,
                   residual_in_tail=residual_in_tail, fused_tail=fused_tail, x_grad=x_grad, tail_bwd_sums=tail_bwd_sums, sign_mask=sign_mask, fused_reduce=fused_reduce,
                   bg_norm_bwd=centered or (fused_reduce and sw.inbwd_bg and cout == 48 and bf16 and sw.side_stream), wgrad_main_stream=main,
-                  defer_conv_wgrad=queue and not main, defer_upconv_wgrad=queue)
+                  defer_conv_wgrad=queue and not main, defer_upconv_wgrad=queue,
+                  tail_box=residual_in_tail and tail_bwd_sums and sign_mask and tail_zero_padded and not tail_pred and sw.tail_box)
 
 
 class BlockSwitches(NamedTuple):
@@ -794,7 +802,7 @@ class _UpBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, skip, mod, B, v, tail=None):
-        """tail = (model, xb, extents, tokmask, pred_out): the block is the last decoder level and the 1x1 head + loss are
+        """tail = (model, xb, extents, tokmask, pred_out[, zero_padded]): the block is the last decoder level and the 1x1 head + loss are
         evaluated here, so that backward can fuse the loss gradient with the backward of the last InstanceNorm; returns the
         loss triple instead of the feature map."""
         m: "UpBlock3D" = mod
@@ -865,7 +873,7 @@ class _UpBlockFn(torch.autograd.Function):
         if tail is None:
             return out
         assert p.fused_tail
-        model, xb, extents, tokmask, pred_out = tail
+        model, xb, extents, tokmask, pred_out = tail[:5]
         lsums = torch.empty(8, dtype=torch.float64, device=dev)
         losses = torch.empty(3, device=dev)
         dpred = torch.empty((B * V, 4), device=dev) if p.x_grad else None
@@ -874,11 +882,11 @@ class _UpBlockFn(torch.autograd.Function):
         # the 1x1 head and the loss terms in the same pass over (y2, cat)
         if p.residual_in_tail:
             ops.mae_tail_fwd_from_coarse(y2, st2, xc, d1.tail_residual, m.transp_conv.bias, model.out.conv.weight, model.out.conv.bias, xb, extents, tokmask,
-                                         B, S, Cout, lsums, losses, dpred, bsum, smask, pred=pred_out)
+                                         B, S, Cout, lsums, losses, dpred, bsum, smask, pred=pred_out, box=p.tail_box)
         else:
             ops.mae_tail_fwd(y2, st2, cat, out, model.out.conv.weight, model.out.conv.bias, xb, extents, tokmask, B, S, Cout, lsums, losses,
                              pred_out, dpred, bwd_sums=bsum, sign_mask=smask)
-        ctx.tail = (model, lsums, dpred, bsum, smask)
+        ctx.tail = (model, lsums, dpred, bsum, smask, extents if p.tail_box else None)
         return losses
 
     @staticmethod
@@ -897,10 +905,10 @@ class _UpBlockFn(torch.autograd.Function):
         dy2 = torch.empty_like(y2)
         dcat = torch.empty((B * V, Cc), dtype=dtype, device=dev)
         if ctx.tail is not None:   # d(loss)/d(losses[0]) == 1 (the reference calls loss.backward()); d(d0) is never materialised
-            model, lsums, dpred, bsum, smask = ctx.tail
+            model, lsums, dpred, bsum, smask, box_extents = ctx.tail
             ops.mae_tail_bwd(None, y2, st2, dpred, lsums, model.out.conv.weight, sums2, dy2, dcat,
                              _gradbuf(model.out.conv.weight), _gradbuf(model.out.conv.bias), B, V, Cout, r=None if p.sign_mask else cat, bwd_sums=bsum,
-                             sign_mask=smask)
+                             sign_mask=smask, extents=box_extents, R=S if box_extents is not None else None)
         elif p.proj:
             dout = dout.contiguous()
             sums3 = ops.acc_zeros((B, Cout, 2), dev)
@@ -1126,7 +1134,8 @@ class UpBlock3D(nn.Module):
         layouts = {n for row in _CONV_LAYOUTS.values() for n in row if self._key + n in pk.views}
         dec1 = pk.dec1.optional() if (pk.dec1 is not None and pk.dec1.block is self) else None
         return plan_up_block(self.cin, self.cout, self.k, self.has_proj, layouts, dec1, B, v, dtype, x_grad, tail is not None,
-                             tail is not None and tail[0].fuse_tail_sums, self._wq is not None, UpSwitches.current())
+                             tail is not None and tail[0].fuse_tail_sums, self._wq is not None, UpSwitches.current(),
+                             tail_pred=tail is not None and len(tail) > 4 and tail[4] is not None, tail_zero_padded=tail is not None and len(tail) > 5 and bool(tail[5]))
 
     def forward(self, x, skip=None, tail=None):
         """channels-last (B,v,v,v,Cin) [+ skip (B,kv,kv,kv,Cout)] -> (B,kv,kv,kv,Cout), or the loss triple when `tail` is given"""
@@ -1449,7 +1458,7 @@ class SwinTransformer_MAE3D_New(nn.Module):
 
     def _decode_and_loss(self, feats, xb, ext, mask_dev, pred):
         if self.fuse_tail:
-            return self.forward_decoder(feats, tail=(self, xb, ext, mask_dev, pred))
+            return self.forward_decoder(feats, tail=(self, xb, ext, mask_dev, pred, True))   # (xb: zero outside ext -- transform / the batcher padded it)
         d0 = self.forward_decoder(feats)
         return _LossFn.apply(d0.reshape(-1, d0.shape[-1]), self, xb, ext, mask_dev, pred)
 
@@ -1484,7 +1493,9 @@ class SwinTransformer_MAE3D_New(nn.Module):
 
     def forward_static(self, xb: Tensor, ext: Tensor, mask_dev: Tensor):
         """graph-capturable training forward: everything already on the device (padded batch (B,4,R,R,R) fp32, extents [B,3]
-        int32, token mask [g^3] uint8); no host<->device traffic, no python RNG."""
+        int32, token mask [g^3] uint8); no host<->device traffic, no python RNG.
+        PRECONDITION: xb is ZERO outside each sample's extents, as `transform` and the batcher's slots make it -- the tail then walks each sample's valid box
+        alone (UpPlan.tail_box, ops.TAIL_BOX); on a batch padded with anything else, set ops.TAIL_BOX = False."""
         B, R = xb.shape[0], self.resolution
         g = R // 4
         self._packer.run()

@@ -1211,24 +1211,42 @@ def tail_from_coarse_ok(R: int, C: int, Cin: int, dtype) -> bool:
     return dtype == torch.bfloat16 and C == 48 and Cin == 96 and R % 4 == 0 and R <= 256 and ((R // 4) ** 3) % 16 == 0
 
 
-def mae_tail_fwd_from_coarse(y, stats, xcoarse, Wr, bt, Wout, bout, target, extents, tokmask, B, R, C, sums, losses, dpred, bwd_sums, sign_mask, pred=None, slope=0.01):
-    """mae_tail_fwd (training form: d(pred), the backward's sums and the sign mask are all written) with the residual ConvT_{k=s=4}(xcoarse) + bt formed inside"""
+# the tail walks each sample's valid box alone (csrc/tail_box.hpp): the zero padding of a scene contributes nothing to the loss or its gradient
+TAIL_BOX = __import__("os").environ.get("NMH_TAIL_BOX", "1") != "0"
+
+
+def mae_tail_fwd_from_coarse(y, stats, xcoarse, Wr, bt, Wout, bout, target, extents, tokmask, B, R, C, sums, losses, dpred, bwd_sums, sign_mask, pred=None, slope=0.01,
+                             box=False):
+    """mae_tail_fwd (training form: d(pred), the backward's sums and the sign mask are all written) with the residual ConvT_{k=s=4}(xcoarse) + bt formed inside.
+    box=True: only the ceil(extent / 4) cells per axis of each sample's valid box are walked.  The caller vouches that `target` is zero outside the extents;
+    dpred and sign_mask are then left UNWRITTEN outside the box (only mae_tail_bwd(..., extents=, R=) may consume them), and pred cannot be requested."""
+    if box and pred is not None:
+        raise ValueError("mae_tail_fwd_from_coarse: the box walk does not write pred")
     _chk(y, stats, xcoarse, Wr, bt, Wout, bout, target, extents, tokmask, sums, losses, pred, dpred, bwd_sums, sign_mask)
     if not tail_from_coarse_ok(R, C, xcoarse.shape[-1], y.dtype) or xcoarse.dtype != torch.bfloat16 or xcoarse.numel() != B * (R // 4) ** 3 * 96:
         raise ValueError("mae_tail_fwd_from_coarse: bf16, 48 channels from a 96-channel coarse tensor of edge R / 4, (R / 4)^3 a multiple of 16")
     if sums.numel() < 8 or bwd_sums.numel() < B * C * 4 + 4 * C or sign_mask.dtype != torch.uint8 or sign_mask.numel() < B * R ** 3 * 8 or dpred.numel() < B * R ** 3 * 4:
         raise ValueError("mae_tail_fwd_from_coarse: sums[8], bwd_sums[B*C*4 + 4*C], sign_mask[B*R^3*8], dpred[B*R^3*4]")
     ev = _prof(("mae_tail_fwd", B, R, C), y.numel() * y.element_size() + xcoarse.numel() * 2 + B * R ** 3 * (16 * (2 + (pred is not None)) + 8))
-    lib().call("nmh_mae_tail_fwd_from_coarse", dt_of(y), y, stats, xcoarse, Wr, bt, Wout, bout, target, extents, tokmask, B, R, C, sums, losses, pred, dpred, slope,
-               bwd_sums, sign_mask, _st())
+    lib().call("nmh_mae_tail_fwd_from_coarse_box" if box else "nmh_mae_tail_fwd_from_coarse", dt_of(y), y, stats, xcoarse, Wr, bt, Wout, bout, target, extents, tokmask,
+               B, R, C, sums, losses, pred, dpred, slope, bwd_sums, sign_mask, _st())
     if ev is not None:
         ev.record(torch.cuda.current_stream())
     return losses
 
 
-def mae_tail_bwd(d0, y, stats, dpred, loss_sums, Wout, in_sums, dy, dr, dWout, dbout, B, V, C, slope=0.01, r=None, bwd_sums=None, sign_mask=None):
-    """d0 may be None when r (the forward's residual input) is given: the kernel rebuilds d0 from y, stats and r"""
-    _chk(d0, r, y, stats, dpred, loss_sums, Wout, in_sums, dy, dr, dWout, dbout, bwd_sums, sign_mask)
+def mae_tail_bwd(d0, y, stats, dpred, loss_sums, Wout, in_sums, dy, dr, dWout, dbout, B, V, C, slope=0.01, r=None, bwd_sums=None, sign_mask=None, extents=None, R=None):
+    """d0 may be None when r (the forward's residual input) is given: the kernel rebuilds d0 from y, stats and r.
+    extents (+ R, V = R^3): dpred and sign_mask come from mae_tail_fwd_from_coarse(box=True) and hold each sample's box alone; outside it d(pred) = 0 is used unread"""
+    _chk(d0, r, y, stats, dpred, loss_sums, Wout, in_sums, dy, dr, dWout, dbout, bwd_sums, sign_mask, extents)
+    if extents is not None:
+        if R is None or R ** 3 != V or bwd_sums is None or sign_mask is None or d0 is not None or r is not None or extents.dtype != torch.int32 or extents.numel() < 3 * B:
+            raise ValueError("mae_tail_bwd: the box walk takes extents int32 [B, 3] with R (V = R^3), bwd_sums and sign_mask, and neither d0 nor r")
+        ev = _prof(("mae_tail_bwd", B, V, C), 3 * y.numel() * y.element_size() + B * V * 24)
+        lib().call("nmh_mae_tail_bwd_box", dt_of(y), y, stats, dpred, loss_sums, Wout, in_sums, dy, dr, slope, dWout, dbout, B, R, C, bwd_sums, sign_mask, extents, _st())
+        if ev is not None:
+            ev.record(torch.cuda.current_stream())
+        return
     if d0 is None and r is None and (sign_mask is None or bwd_sums is None):
         raise ValueError("mae_tail_bwd needs d0, r, or the forward's sign mask together with its bwd_sums")
     # two passes (sums, then apply): y and r (or d0) read twice, d(pred) read twice, dy and dr written once
