@@ -88,6 +88,8 @@ class GradReducer:
     # ---- the layout: what a subclass over another flat buffer overrides ------------------------------------------------------------------------
     def _encoder(self):
         """the module whose `stages` bound the segments (flattened if it was not); None: the whole buffer is one segment"""
+        if hasattr(self.model, "refuse_frozen_stages"):
+            self.model.refuse_frozen_stages("GradReducer")   # (the fine-tuning exchange, FlatGradReducer, skips a frozen prefix)
         if self.model._flat is None:
             self.model.flatten_parameters()
         return self.model
@@ -197,21 +199,26 @@ class GradReducer:
         self.allreduce_range(lo, hi)
         self.pending.append(seg)
 
-    def allreduce_flat(self):
-        """the whole flat gradient buffer in one message on the current stream"""
+    def allreduce_flat(self, lo: int = 0):
+        """the flat gradient buffer from element `lo` on (all of it by default) in one message on the current stream"""
         if not self.active:
             return
-        self._exchange(0, self.model._flat_grad.numel())
+        self._exchange(lo, self.model._flat_grad.numel())
+
+    def first_live_segment(self) -> int:
+        """the first segment that is exchanged: 0 (FlatGradReducer: the one behind the encoder's frozen prefix)"""
+        return 0
 
     def finish(self):
         """call after backward: reduce any segment whose trigger did not fire, then join the comm stream"""
         if not self.active:
             return
+        live = self.first_live_segment()
         if self.on_gpu and dist.get_backend(self.group) != "nccl":
-            self.allreduce_flat()
+            self.allreduce_flat(self.bounds[live])
             self.pending = []
             return
-        for seg in range(self.nseg):
+        for seg in range(live, self.nseg):
             if seg not in self.pending:
                 self.launch(seg)
         if self.on_gpu:
@@ -226,7 +233,8 @@ class FlatGradReducer(GradReducer):
     The tail is [end of stage 3's parameters, n): whatever the base keeps behind stage 3 (decoder4..2 under a voxel head, nothing under the FPN backbone), then
     the neck, the heads, encoder1 / decoder1 / the output convs and the Scales.  Every bound is a multiple of 8, the granule of both layouts.  A module without
     a SwinTransformer_MAE3D_New is one segment, which is its tail.  model.forward_encoder places the stage triggers (it reads trigger, seg_stage, chunk_stage and
-    chunk_groups of base._reducer); fpn.SwinTransformer_FPN_Pretrained_Skip.forward places the tail's."""
+    chunk_groups of base._reducer); fpn.SwinTransformer_FPN_Pretrained_Skip.forward places the tail's.  A frozen prefix of the encoder is not exchanged
+    (first_live_segment)."""
 
     def __init__(self, flat_params, process_group=None, comm_dtype: Optional[torch.dtype] = None, stage_chunks: Optional[int] = None):
         self.flat = flat_params
@@ -244,6 +252,16 @@ class FlatGradReducer(GradReducer):
 
     def seg_tail(self) -> int:
         return self.nseg - 1
+
+    def first_live_segment(self) -> int:
+        """behind the encoder's frozen prefix (model.frozen_stages = k, read now: a trainer may set it after this reducer was built): the segments embed and stage
+        0 .. k-1 get no trigger (model.forward_encoder) and finish() skips them -- no backward kernel writes their ranges of the gradient buffer, so every rank
+        holds the same zeros there.  k = all stages: the tail, which no trigger can reach then (no encoder tensor requires a gradient) and finish() exchanges."""
+        enc = self.flat.base
+        k = getattr(enc, "frozen_stages", 0) if enc is not None else 0
+        if not k:
+            return 0
+        return self.seg_stage(k) if k < len(enc.stages) else self.seg_tail()
 
 
 def broadcast_parameters(model, src: int = 0, group=None):

@@ -9,6 +9,7 @@
   fcos_loss_fn, rpn_loss_fn, voxel_loss_fn, loss_fn_for   the loss functions FinetuneStep takes, for the four downstream models.
   param_ranges     per-range optimizer settings over the flat layout, from ordered rules: the table FusedAdamW(ranges=) steps with.
   layer_decay_rules, no_decay_rules, freeze_rules, recipe_rules   the rules of the usual fine-tuning recipe.
+  frozen_stage_rules   the frozen prefix of the encoder (patch embed + stages[:k]): its freeze rules, and the encoder told to end the backward there.
 
 No kernel of its own: forward and backward are the models', the optimizer is nmh_grad_sqnorm / nmh_clip_coef / nmh_adamw_step (trainer.FusedAdamW), or their
 *_ranges forms under a table.
@@ -29,7 +30,7 @@ from torch import nn
 from .model import SwinTransformer_MAE3D_New
 
 __all__ = ["FlatParameters", "FinetuneStep", "fcos_loss_fn", "rpn_loss_fn", "voxel_loss_fn", "loss_fn_for", "ParamRanges", "param_ranges", "layer_ids",
-           "layer_decay_rules", "no_decay_rules", "freeze_rules", "recipe_rules"]
+           "layer_decay_rules", "no_decay_rules", "freeze_rules", "frozen_stage_rules", "recipe_rules"]
 
 
 def _round8(n: int) -> int:
@@ -301,6 +302,26 @@ def freeze_rules(*selectors):
     return [(s, 0.0, None) for s in selectors]
 
 
+def frozen_stage_rules(module, k: int):
+    """the frozen prefix of the one encoder inside `module` (a module or a FlatParameters): sets encoder.frozen_stages = k -- the patch embed and stages[:k] then
+    run without a graph, no backward kernel runs for them, none of their activations is kept and no reducer exchanges their ranges -- and returns
+    the freeze rules of exactly those parameters: patch_partition, mask_token where the encoder has one, stages[0] .. stages[k-1].  The two belong together: a
+    prefix that is not stepped-as-frozen would still decay under its zero gradient.  The table equals the one of freeze=(patch_partition, *stages[:k]) (plus
+    mask_token).  k = 0: no prefix, no rule.  Refused (ValueError): k outside 0 .. len(stages), a module without exactly one SwinTransformer_MAE3D_New."""
+    base = _encoder_of(module, "frozen_stage_rules")
+    base.frozen_stages = k          # (the setter checks the range)
+    if not base.frozen_stages:
+        return []
+    sels = [base.patch_partition]
+    if "mask_token" in base._parameters:       # (the downstream backbones drop it)
+        token = base.mask_token
+
+        def mask_token(name, p):
+            return p is token
+        sels.append(mask_token)
+    return freeze_rules(*sels, *base.stages[:base.frozen_stages])
+
+
 def _selectors(freeze) -> tuple:
     return (freeze,) if isinstance(freeze, (str, nn.Module)) or callable(freeze) else tuple(freeze)
 
@@ -311,10 +332,12 @@ def selector_names(module, freeze) -> list:
     return [s if isinstance(s, str) else names.get(id(s), type(s).__name__) if isinstance(s, nn.Module) else getattr(s, "__name__", repr(s)) for s in _selectors(freeze)]
 
 
-def recipe_rules(module, layer_decay: float = None, no_decay: bool = False, freeze=()):
-    """the trainers' three switches as one rule list: freeze first (it wins the lr_scale), then layer decay, then the no-decay set"""
+def recipe_rules(module, layer_decay: float = None, no_decay: bool = False, freeze=(), freeze_stages: int = 0):
+    """the trainers' switches as one rule list: freeze and the frozen prefix first (they win the lr_scale), then layer decay, then the no-decay set.  freeze_stages
+    != 0 also sets the encoder's frozen_stages (frozen_stage_rules); 0 leaves the encoder as it is"""
     freeze = _selectors(freeze)
-    return (freeze_rules(*freeze) + (layer_decay_rules(module, layer_decay) if layer_decay is not None else []) + (no_decay_rules(module) if no_decay else []))
+    return (freeze_rules(*freeze) + (frozen_stage_rules(module, freeze_stages) if freeze_stages else [])
+            + (layer_decay_rules(module, layer_decay) if layer_decay is not None else []) + (no_decay_rules(module) if no_decay else []))
 
 
 # ---- loss functions of the five downstream models ----------------------------------------------------------------------------------------------

@@ -17,7 +17,7 @@ import torch
 from torch import Tensor, nn
 
 from . import conv_layer, ops
-from .model import SWIN_CONFIGS, SwinTransformer_MAE3D_New, _EmbedFn, _gradbuf, _Packer
+from .model import SWIN_CONFIGS, SwinTransformer_MAE3D_New, _gradbuf, _Packer
 
 
 class _FPNFn(torch.autograd.Function):
@@ -61,7 +61,8 @@ class _FPNFn(torch.autograd.Function):
             C = f.shape[-1]
             lconv = fpn.lateral_convs[i]
             keep.append(dl)
-            dfeats.append(ops.gemm_nt(dl.view(-1, Co), pk[f"l{i}.wT"].view(C, Co)).view(f.shape))
+            # (a feature of the encoder's frozen prefix takes no gradient: model.frozen_stages)
+            dfeats.append(ops.gemm_nt(dl.view(-1, Co), pk[f"l{i}.wT"].view(C, Co)).view(f.shape) if ctx.needs_input_grad[i + 1] else None)
             with ops.side_stream():
                 ops.gemm_tn(dl.view(-1, Co), f.view(-1, C), _gradbuf(lconv.weight).view(Co, C), dbias=_gradbuf(lconv.bias))
         ops.join_side()
@@ -110,6 +111,10 @@ class FPN(nn.Module):
         """feats: channels-last (B,D,H,W,C_i) tensors in the compute dtype (what the encoder kernels produce)"""
         assert len(feats) == len(self.in_channels)
         self._pack()
+        if torch.is_grad_enabled() and not any(f.requires_grad for f in feats):
+            # every level comes from a frozen encoder (model.frozen_stages = all stages): the neck's parameters are not inputs of _FPNFn, so without an input that
+            # requires a gradient its backward would not run at all.  The coarsest (smallest) level becomes a leaf; its gradient is computed for nothing.
+            feats = list(feats[:-1]) + [feats[-1].detach().requires_grad_()]
         return _FPNFn.apply(self, *feats)
 
     def forward(self, inputs):
@@ -170,7 +175,7 @@ class SwinTransformer_FPN_Pretrained_Skip(nn.Module):
         B, R = x.shape[0], x.shape[2]
         g = R // 4
         # patch_partition + pos_embed in one pass (feature_extractor.py:1179-1180), no masking
-        tok = _EmbedFn.apply(b._anchor, b, x.float().contiguous(), None).view(B, g, g, g, b.embed_dim)
+        tok = b._embed_nomask(x.float().contiguous()).view(B, g, g, g, b.embed_dim)
         feats = b.forward_encoder(tok)
         red = b._reducer
         if red is not None and hasattr(red, "seg_tail"):

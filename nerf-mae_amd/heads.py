@@ -14,7 +14,7 @@ import torch
 from torch import Tensor, nn
 
 from . import conv_layer, ops
-from .model import SWIN_CONFIGS, OutBlock3D, ResBlock3D, SwinTransformer_MAE3D_New, UpBlock3D, _EmbedFn, _gradbuf
+from .model import SWIN_CONFIGS, OutBlock3D, ResBlock3D, SwinTransformer_MAE3D_New, UpBlock3D, _gradbuf
 
 
 class UnetrBasicBlock3D(nn.Module):
@@ -222,9 +222,13 @@ class _VoxelHeadBase(nn.Module):
         g = R // 4
         x8 = ops.grid_to_cl8(xb, self.compute_dtype)
         enc1 = _ResBlock8Fn.apply(b._anchor, self, x8, B, R)
-        tok = _EmbedFn.apply(b._anchor, b, xb, None).view(B, g, g, g, b.embed_dim)      # + pos_embed inside the LayerNorm kernel, no mask
+        tok = b._embed_nomask(xb).view(B, g, g, g, b.embed_dim)      # + pos_embed inside the LayerNorm kernel, no mask
         feats = b.forward_encoder(tok)
         b._packer.join()
+        if torch.is_grad_enabled() and not feats[3].requires_grad:
+            # the whole encoder is a frozen prefix (model.frozen_stages): decoder4's parameters are not inputs of _UpBlockFn, so its backward needs an input that
+            # requires a gradient to run at all.  The coarsest feature becomes a leaf; its gradient is computed for nothing.
+            feats[3] = feats[3].detach().requires_grad_()
         d = b.decoder4(feats[3], feats[2])
         d = b.decoder3(d, feats[1])
         d = b.decoder2(d, feats[0])

@@ -968,7 +968,7 @@ class _UpBlockFn(torch.autograd.Function):
                     ops.gemm_tn(dy3, cat, g_c3)
         # ---- transpose conv (+ skip)
         dskip = None
-        if p.proj:
+        if p.proj and ctx.needs_input_grad[1]:   # (a skip of the frozen prefix needs none: model.frozen_stages)
             dskip = torch.empty((B * V, Cout), dtype=dtype, device=dev)
             ops.copy_cols(dcat[:, Cout:], dskip)
         dx = torch.empty((B * v ** 3, Cin), dtype=dtype, device=dev)
@@ -1028,7 +1028,7 @@ class PatchPartition(nn.Sequential):
         m._ensure_ready(x.device)
         m._add_pos = False
         try:
-            tok = _EmbedFn.apply(m._anchor, m, x.float().contiguous(), None)
+            tok = m._embed_nomask(x.float().contiguous())
         finally:
             m._add_pos = True
         g = x.shape[2] // 4
@@ -1209,6 +1209,36 @@ class SwinTransformer_MAE3D_New(nn.Module):
         # the caller that drew the mask found it constant on every 4^3 window (mask_window_aligned): stage 0's first block may run on the kept windows only
         self._block0_aligned = False
         self._b0 = None          # (wmap, g, capW) of the compact tokens the last _EmbedFn.forward returned; taken by _run_stage(0)
+        self._frozen_stages = 0  # the frozen prefix: patch embed + stages[:k] run without a graph (frozen_stages)
+
+    @property
+    def frozen_stages(self) -> int:
+        """k: the patch embed (patch_partition, mask_token) and stages[:k] are a frozen prefix -- they run with autograd off in whatever mode they are in (train():
+        the stochastic-depth factors of the one _draw_sd_noise draw), keep nothing for a backward, get no weight-gradient flush and no reducer trigger, and the
+        backward pass ends at the input of stage k.  Their gradient views are never written.  0: no prefix.  Fine-tuning only (forward_encoder and the callers of
+        _embed_nomask); the optimizer side is finetune.frozen_stage_rules."""
+        return self._frozen_stages
+
+    @frozen_stages.setter
+    def frozen_stages(self, k):
+        n = len(self.stages)
+        if isinstance(k, bool) or int(k) != k or not 0 <= int(k) <= n:
+            raise ValueError(f"frozen_stages = {k!r}: an integer from 0 (nothing frozen) to {n} (the patch embed and all {n} stages); to freeze anything but a "
+                             "leading prefix use freeze= (finetune.freeze_rules)")
+        self._frozen_stages = int(k)
+
+    def refuse_frozen_stages(self, who: str):
+        """the MAE pre-training path does not implement the frozen prefix: refuse instead of training something untested"""
+        if self._frozen_stages:
+            raise ValueError(f"{who}: the encoder has frozen_stages = {self._frozen_stages}; the MAE pre-training path does not implement the frozen prefix -- set "
+                             "frozen_stages = 0 (freeze= still keeps ranges from being stepped), or fine-tune through finetune.FinetuneStep")
+
+    def _embed_nomask(self, xb: Tensor) -> Tensor:
+        """the unmasked patch embed of the downstream models -> (B g^3, C) tokens; under a frozen prefix without a graph (no _EmbedFn context is kept)"""
+        if self._frozen_stages:
+            with torch.no_grad():
+                return _EmbedFn.apply(self._anchor, self, xb, None)
+        return _EmbedFn.apply(self._anchor, self, xb, None)
 
     def _block0_kept_ok(self, g: int) -> bool:
         """the conditions of the kept-window path of stage 0's first block other than those of the compact patch embed (ops.BLOCK0_KEPT)"""
@@ -1408,7 +1438,7 @@ class SwinTransformer_MAE3D_New(nn.Module):
             if red is not None:
                 x = red.trigger(x, red.seg_stage(si, k))  # backward reaching here => this range's gradients are complete
             if q is not None:
-                x = _StageFlushFn.apply(x, q, si == 0 and k == 0)
+                x = _StageFlushFn.apply(x, q, si == self._frozen_stages and k == 0)   # the first live stage's flush ends the backward pass
             for mod in grp:
                 if isinstance(mod, SwinBlock3D):
                     x = mod(x, None if sd_noise is None else sd_noise[bi])
@@ -1426,7 +1456,18 @@ class SwinTransformer_MAE3D_New(nn.Module):
         if sd_noise is None:
             sd_noise = self._draw_sd_noise(tok.shape[0], tok.device)
         self._wq.sync_after_flush = red is not None   # a gradient all-reduce of the range follows the flush: join before it
+        nf = self._frozen_stages
         for si in range(len(self.stages)):
+            if si < nf:
+                # the frozen prefix: no graph, no flush, no trigger, no fork -- the feature goes to the neck / decoder as it is
+                with torch.no_grad():
+                    x, bi = self._run_stage(si, x, sd_noise, bi, None)
+                feats.append(x)
+                if si + 1 == nf and si + 1 < len(self.stages) and torch.is_grad_enabled():
+                    # the boundary: a leaf that requires a gradient, so that the first live stage keeps its plans (plan_swin_block: x_grad) and gets its flush,
+                    # which is the one that ends the backward pass.  Its gradient (one LayerNorm backward's dx store) is computed for nothing.
+                    x = x.detach().requires_grad_()
+                continue
             x, bi = self._run_stage(si, x, sd_noise, bi, red)
             if si + 1 < len(self.stages) and torch.is_grad_enabled() and x.requires_grad:
                 x, skip = _Fork2Fn.apply(x)     # consumed by the next stage and by a decoder / neck
@@ -1463,6 +1504,7 @@ class SwinTransformer_MAE3D_New(nn.Module):
         return _LossFn.apply(d0.reshape(-1, d0.shape[-1]), self, xb, ext, mask_dev, pred)
 
     def forward(self, x: List[Tensor], is_eval: bool = False, block_mask: Optional[Tensor] = None, sd_noise=None, return_pred: bool = False):
+        self.refuse_frozen_stages("SwinTransformer_MAE3D_New.forward")
         device = self.mask_token.device
         self._ensure_ready(device)
         xb, ext = self.transform(x, device)

@@ -200,6 +200,7 @@ class GraphedTrainStep:
                              "micro-batch; gradient accumulation exchanges each range once per optimizer step, between the replays (unset the variable)")
         if opt.accumulate not in (1, int(accumulate)):
             raise ValueError(f"GraphedTrainStep: accumulate = {accumulate}, but the optimizer was built with accumulate = {opt.accumulate}")
+        model.refuse_frozen_stages("GraphedTrainStep")
         self.model, self.opt, self.reducer = model, opt, reducer
         self.accumulate = int(accumulate)
         if self.accumulate > 1:
@@ -738,6 +739,7 @@ class Trainer:
         self.rank, self.world, self.log, self.seed = rank, world, log, seed
         if int(accumulate) != accumulate or accumulate < 1:
             raise ValueError(f"Trainer: accumulate >= 1, got {accumulate}")
+        model.refuse_frozen_stages("Trainer")
         self.accumulate = int(accumulate)
         self.args = dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, batch_size=batch_size * world * self.accumulate,
                          accumulate=self.accumulate, num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
@@ -975,6 +977,11 @@ class _FinetuneTrainer:
     their moments and clips over the rest; their gradients are still computed and, data-parallel, exchanged.  `freeze` adds to `exclude`; a selector that matches
     only what `exclude` left out is refused.  The three are recorded in train_args, and a resume under other settings is refused (restore_resume).
 
+    freeze_stages = k: the encoder's frozen prefix -- patch embed and stages[:k] -- is frozen as freeze=(patch_partition, *stages[:k]) freezes it
+    AND its backward is not run: no gradient kernel, no activation kept, no range exchanged (finetune.frozen_stage_rules, model.frozen_stages).  The prefix stays
+    in train() mode and keeps its stochastic-depth draws.  Recorded in train_args; the range table makes a resume under another k refused.  Refused: k outside
+    0 .. len(stages), a model without exactly one encoder, and an encoder that `exclude` left out as a whole.
+
     accumulate = k: an optimizer step takes k consecutive batches of the epoch's plan as micro-batches (accum_epoch_plan; an epoch's last step takes what
     is left) through FinetuneStep.accumulate and steps on the mean of their gradients.  steps_per_epoch, global_step, the optimizer's step count and the schedule
     count optimizer steps; the logged losses are the mean over them of the per-step mean; train_args records accumulate and batch_size = batch * world * k; resume
@@ -989,10 +996,11 @@ class _FinetuneTrainer:
 
     def __init__(self, model, train_scenes, train_targets, val_scenes, val_targets, batcher, val_batcher, loss_fn, weights, args: dict, batch_size: int,
                  num_epochs: int, schedule_epochs: int, lr: float, weight_decay: float, clip_grad_norm: float, eval_interval: int, save_path: str, log, seed: int,
-                 rank: int, world: int, reducer, exclude=(), layer_decay: float = None, no_decay: bool = False, freeze=(), accumulate: int = 1):
+                 rank: int, world: int, reducer, exclude=(), layer_decay: float = None, no_decay: bool = False, freeze=(), accumulate: int = 1,
+                 freeze_stages: int = 0):
         import random
         from . import dist as _dist
-        from .finetune import FinetuneStep, FlatParameters, param_ranges, recipe_rules, selector_names
+        from .finetune import FinetuneStep, FlatParameters, _encoder_of, param_ranges, recipe_rules, selector_names
         self.model, self.train_scenes, self.train_targets, self.val_scenes, self.val_targets = model, train_scenes, train_targets, val_scenes, val_targets
         self.batch, self.epochs, self.eval_interval, self.save_path, self.log, self.seed = batch_size, num_epochs, eval_interval, save_path, log, seed
         self.rank, self.world = rank, world
@@ -1001,9 +1009,17 @@ class _FinetuneTrainer:
         self.accumulate = int(accumulate)
         # (the subclasses pass batch_size = batch * world, the reference's --batch_size; an optimizer step under accumulation takes `accumulate` times as many)
         self.args = _plain(dict(args, batch_size=batch_size * world * self.accumulate, accumulate=self.accumulate, layer_decay=layer_decay, no_decay=bool(no_decay),
-                                freeze=selector_names(model, freeze)))
+                                freeze=selector_names(model, freeze), freeze_stages=freeze_stages))
         self.batcher, self.val_batcher = batcher, val_batcher
         self.exclude = tuple(exclude)                            # the frozen part: outside the flat buffers, kept in eval()
+        who = type(self).__name__
+        if isinstance(freeze_stages, bool) or int(freeze_stages) != freeze_stages:
+            raise ValueError(f"{who}: freeze_stages = {freeze_stages!r}; it is the number of leading encoder stages to freeze, 0 for none")
+        if freeze_stages:
+            left_out = {id(m) for e in self.exclude for m in e.modules()}
+            if id(_encoder_of(model, who)) in left_out:
+                raise ValueError(f"{who}: freeze_stages = {freeze_stages} with the backbone left out as a whole (freeze_backbone / a frozen first stage / exclude=): "
+                                 "an excluded encoder is already frozen entirely and runs without a graph; drop one of the two")
         if reducer is not None:
             if getattr(reducer.model, "module", None) is not model:
                 raise ValueError(f"{type(self).__name__}: the reducer must be a dist.FlatGradReducer over a finetune.FlatParameters of this model")
@@ -1018,7 +1034,9 @@ class _FinetuneTrainer:
         if world > 1:
             _dist.broadcast_flat_parameters(self.flat)   # DDP's initial broadcast: every rank starts from rank 0's weights
         # per-range settings: a selector that matches nothing in the flat buffer -- a typo, or a part that `exclude` left out -- is refused
-        rules = recipe_rules(model, layer_decay, no_decay, freeze)
+        if self.flat.base is not None:
+            self.flat.base.frozen_stages = freeze_stages         # (0 too: a prefix that an earlier trainer left on the encoder would run unstepped but decayed)
+        rules = recipe_rules(model, layer_decay, no_decay, freeze, freeze_stages)
         self.opt = FusedAdamW(self.flat, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm, ranges=param_ranges(self.flat, rules) if rules else None,
                               accumulate=self.accumulate)
         self.micro_per_epoch = len(dp_epoch_plan(len(train_scenes), batch_size, rank, world, 0, seed))   # len(train_loader) without drop_last, the same on every rank
@@ -1134,7 +1152,7 @@ class DetectionTrainer(_FinetuneTrainer):
                  weight_decay: float = 1e-3, clip_grad_norm: float = 0.1, reg_loss_weight: float = 1.0, eval_interval: int = 1, save_path: str = None,
                  normalize_density: bool = True, flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = 1000,
                  log=print, train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None, layer_decay: float = None,
-                 no_decay: bool = False, freeze=(), accumulate: int = 1):
+                 no_decay: bool = False, freeze=(), accumulate: int = 1, freeze_stages: int = 0):
         from . import data
         from .finetune import fcos_loss_fn
         if len(train_scenes) != len(train_boxes) or (val_scenes is not None and len(val_scenes) != len(val_boxes or [])):
@@ -1156,7 +1174,7 @@ class DetectionTrainer(_FinetuneTrainer):
                               batch_size=batch_size * world, num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob,
                               rotate_prob=rotate_prob, rot_scale_prob=rot_scale_prob),
                          batch_size, num_epochs, schedule_epochs, lr, weight_decay, clip_grad_norm, eval_interval, save_path, log, seed, rank, world, reducer,
-                         layer_decay=layer_decay, no_decay=no_decay, freeze=freeze, accumulate=accumulate)
+                         layer_decay=layer_decay, no_decay=no_decay, freeze=freeze, accumulate=accumulate, freeze_stages=freeze_stages)
         self.top_n = int(model.args.fpn_post_nms_top_n)
         self.limits = [l for l in (300, 1000, self.top_n) if l <= self.top_n]
         self.ap_top_n = (train_args or {}).get("ap_top_n")
@@ -1293,7 +1311,7 @@ class _BoxTrainer(_FinetuneTrainer):
                                   data.DetectionBatcher(resolution, dev, c["normalize_density"]), loss_fn, weights, c["args"], c["batch_size"], c["num_epochs"],
                                   c["schedule_epochs"] or c["num_epochs"], c["lr"], c["weight_decay"], c["clip_grad_norm"], c["eval_interval"], c["save_path"],
                                   c["log"], c["seed"], c["rank"], c["world"], c["reducer"], exclude=exclude, layer_decay=c["layer_decay"], no_decay=c["no_decay"],
-                                  freeze=c["freeze"], accumulate=c["accumulate"])
+                                  freeze=c["freeze"], accumulate=c["accumulate"], freeze_stages=c["freeze_stages"])
 
     def _logged(self, losses):
         return torch.stack([losses[k] for k in self.keys])
@@ -1347,7 +1365,7 @@ class RPNTrainer(_BoxTrainer):
                  eval_interval: int = 1, keep_checkpoints: int = 1, top_k: int = None, freeze_backbone: bool = False, normalize_density: bool = True,
                  flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = None, save_path: str = None, log=print,
                  train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None, layer_decay: float = None, no_decay: bool = False, freeze=(),
-                 accumulate: int = 1):
+                 accumulate: int = 1, freeze_stages: int = 0):
         from .finetune import rpn_loss_fn
         self.freeze_backbone = bool(freeze_backbone)
         args = dict(train_args or {}, lr=lr, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm, reg_loss_weight=reg_loss_weight,
@@ -1359,7 +1377,8 @@ class RPNTrainer(_BoxTrainer):
                     dict(args=args, batch_size=batch_size, num_epochs=num_epochs, schedule_epochs=schedule_epochs, lr=lr, weight_decay=weight_decay,
                          clip_grad_norm=clip_grad_norm, eval_interval=eval_interval, keep_checkpoints=keep_checkpoints, top_k=top_k, save_path=save_path, log=log,
                          seed=seed, rank=rank, world=world, reducer=reducer, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
-                         rot_scale_prob=rot_scale_prob, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze, accumulate=accumulate),
+                         rot_scale_prob=rot_scale_prob, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze, accumulate=accumulate,
+                         freeze_stages=freeze_stages),
                     (model.backbone,) if self.freeze_backbone else ())
         if self.freeze_backbone:
             model.backbone_no_grad = True
@@ -1431,7 +1450,7 @@ class TwoStageTrainer(_BoxTrainer):
                  rpn_reg_loss_weight_2d: float = 0.0, obj_only: bool = False, freeze_first_stage: bool = None, eval_interval: int = 1, keep_checkpoints: int = 1,
                  top_k: int = None, normalize_density: bool = True, flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0,
                  schedule_epochs: int = None, save_path: str = None, log=print, train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None,
-                 layer_decay: float = None, no_decay: bool = False, freeze=(), accumulate: int = 1):
+                 layer_decay: float = None, no_decay: bool = False, freeze=(), accumulate: int = 1, freeze_stages: int = 0):
         from .finetune import roi_loss_fn
         if obj_only and model.is_reg:
             raise ValueError("TwoStageTrainer: obj_only trains no box regression, but the detector decodes with it (is_reg=True): build TwoStageDetector(..., "
@@ -1453,7 +1472,8 @@ class TwoStageTrainer(_BoxTrainer):
                     dict(args=args, batch_size=batch_size, num_epochs=num_epochs, schedule_epochs=schedule_epochs, lr=lr, weight_decay=weight_decay,
                          clip_grad_norm=clip_grad_norm, eval_interval=eval_interval, keep_checkpoints=keep_checkpoints, top_k=top_k, save_path=save_path, log=log,
                          seed=seed, rank=rank, world=world, reducer=reducer, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
-                         rot_scale_prob=rot_scale_prob, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze, accumulate=accumulate),
+                         rot_scale_prob=rot_scale_prob, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze, accumulate=accumulate,
+                         freeze_stages=freeze_stages),
                     exclude)
         model.first_stage_no_grad = frozen is not None
         self.best_metric = {}
@@ -1531,7 +1551,7 @@ class VoxelTrainer(_FinetuneTrainer):
                  weight_decay: float = 0.01, clip_grad_norm: float = 0.1, eval_interval: int = 1, save_path: str = None, normalize_density: bool = True,
                  flip_prob: float = 0.0, rotate_prob: float = 0.0, rot_scale_prob: float = 0.0, schedule_epochs: int = None, log=print,
                  train_args: dict = None, seed: int = 0, rank: int = 0, world: int = 1, reducer=None, layer_decay: float = None, no_decay: bool = False, freeze=(),
-                 accumulate: int = 1):
+                 accumulate: int = 1, freeze_stages: int = 0):
         from . import data
         from .heads import SwinTransformer_VoxelSemantics_Pretrained_Skip, SwinTransformer_VoxelSR_Pretrained_Skip
         if isinstance(model, SwinTransformer_VoxelSemantics_Pretrained_Skip):
@@ -1558,7 +1578,7 @@ class VoxelTrainer(_FinetuneTrainer):
                               num_epochs=num_epochs, normalize_density=normalize_density, flip_prob=flip_prob, rotate_prob=rotate_prob,
                               rot_scale_prob=rot_scale_prob),
                          batch_size, num_epochs, schedule_epochs or num_epochs, lr, weight_decay, clip_grad_norm, eval_interval, save_path, log, seed, rank, world,
-                         reducer, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze, accumulate=accumulate)
+                         reducer, layer_decay=layer_decay, no_decay=no_decay, freeze=freeze, accumulate=accumulate, freeze_stages=freeze_stages)
         self.best_metric = None
 
     def _loss(self, meshes, tb):

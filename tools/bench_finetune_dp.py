@@ -10,6 +10,9 @@ against is the step without the reducer IN THE SAME RUN.
 N > 1 GPUs (python -m torch.distributed.run --nproc_per_node N tools/bench_finetune_dp.py [--comm fp32]): every rank runs the step with the reducer over
 RCCL on the same batch; rank 0 prints the step time and timing_report(): per-range ms and the exposed comm time.
 
+--freeze-stages K: every model of the run trains under freeze_stages=K, and the bytes exchanged per step -- the ranges from the first live
+segment on -- are reported beside the whole buffer's.
+
 Prints one JSON line at the end.  Nothing is asserted on the times."""
 import argparse
 import json
@@ -52,6 +55,7 @@ def main():
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--backbone", default="swin_s")
     ap.add_argument("--comm", default="bf16", choices=["bf16", "fp32"], help="bucket dtype of the N > 1 run")
+    ap.add_argument("--freeze-stages", type=int, default=0, help="K: every model of the run trains under freeze_stages=K (DESIGN.md 3.27)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_finetune_dp needs an MI355X (no CPU fallback)")
@@ -65,7 +69,7 @@ def main():
     dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
     import bench_finetune_step as one
     from nerf_mae_amd.dist import FlatGradReducer, broadcast_flat_parameters
-    from nerf_mae_amd.finetune import FinetuneStep, FlatParameters, fcos_loss_fn
+    from nerf_mae_amd.finetune import FinetuneStep, FlatParameters, fcos_loss_fn, param_ranges, recipe_rules
     from nerf_mae_amd.trainer import FusedAdamW
     meshes, targets = one.batch(args)
     result = {"metric": "fcos_finetune_dp_step_ms", "backbone": args.backbone, "resolution": args.resolution, "batch": args.batch, "dtype": "bf16",
@@ -81,7 +85,11 @@ def main():
         flat = FlatParameters(m)
         red = None if comm is None else FlatGradReducer(flat, comm_dtype=torch.bfloat16 if comm == "bf16" else None)
         broadcast_flat_parameters(flat)
-        opt = FusedAdamW(flat, lr=1e-4, weight_decay=1e-2, max_grad_norm=0.1)
+        rules = recipe_rules(m, freeze_stages=args.freeze_stages)
+        opt = FusedAdamW(flat, lr=1e-4, weight_decay=1e-2, max_grad_norm=0.1, ranges=param_ranges(flat, rules) if rules else None)
+        if red is not None:
+            n, lo = int(red.bounds[-1]), int(red.bounds[red.first_live_segment()])
+            result["exchanged_per_step"] = {"freeze_stages": args.freeze_stages, "elements": n - lo, "of": n, "bytes_fp32": 4 * (n - lo), "bytes_bf16": 2 * (n - lo)}
         return FinetuneStep(flat, opt, fcos_loss_fn(m), reducer=red), red, m
 
     def timed(step):
@@ -102,6 +110,9 @@ def main():
             print(f"{'segment':24s} {'lo':>10s} {'hi':>10s} {'elements':>10s} {'fp32 bytes':>12s} {'bf16 bytes':>12s}")
             for r in result["segments"]:
                 print(f"{r['segment']:24s} {r['lo']:10d} {r['hi']:10d} {r['elements']:10d} {r['bytes_fp32']:12d} {r['bytes_bf16']:12d}")
+            x = result["exchanged_per_step"]
+            print(f"exchanged per step under freeze_stages = {x['freeze_stages']}: {x['elements']} of {x['of']} elements, {x['bytes_fp32']} bytes in fp32 buckets, "
+                  f"{x['bytes_bf16']} in bf16")
             for _ in range(args.warmup):
                 for s in paths.values():
                     s(meshes, targets)

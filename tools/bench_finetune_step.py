@@ -11,7 +11,13 @@ Then the optimizer alone over the fused path's flat buffers, two rows from the s
   uniform  FusedAdamW.launch(): nmh_grad_sqnorm, nmh_clip_coef, nmh_adamw_step
   ranged   the same under the layer-decay (0.75) + no-decay table of this model: nmh_grad_sqnorm_ranges, nmh_clip_coef, nmh_adamw_step_ranges
 HIP events around the norm launch, around the update launch and around all three; --opt-repeats (default 100) timed launches per row after 10 warm-up ones,
-each figure as median [min .. max].  --optimizer-only skips the step timing."""
+each figure as median [min .. max].  --optimizer-only skips the step timing.
+
+--freeze-stages K runs, instead of the above, two rows over two models with the same weights, the same batch and the same range table, alternated
+step by step in one process with the same events and warm-ups:
+  freeze=        FinetuneStep under freeze=(patch_partition, *stages[:K]): the prefix is not stepped, its backward runs (the path before freeze_stages existed)
+  freeze_stages  FinetuneStep under freeze_stages=K: the prefix runs without a graph and the backward ends at stage K
+forward, backward, optimizer and step as median [min .. max], and torch.cuda.max_memory_allocated() over one step of each row, measured after the timed steps."""
 import argparse
 import json
 import os
@@ -49,6 +55,65 @@ def batch(args):
     return [xb[i] for i in range(args.batch)], targets
 
 
+def freeze_rows(args):
+    from nerf_mae_amd.finetune import FinetuneStep, FlatParameters, fcos_loss_fn, param_ranges, recipe_rules
+    from nerf_mae_amd.trainer import FusedAdamW
+    K = args.freeze_stages
+    P = build(args)
+    Q = build(args)
+    Q.load_state_dict(P.state_dict(), strict=True)
+    meshes, targets = batch(args)
+    rows = {}
+    for name, m in (("freeze=", P), ("freeze_stages", Q)):
+        m = m.cuda().train()
+        flat = FlatParameters(m)
+        base = flat.base
+        rules = recipe_rules(m, freeze=(base.patch_partition, *base.stages[:K])) if name == "freeze=" else recipe_rules(m, freeze_stages=K)
+        opt = FusedAdamW(flat, lr=1e-4, weight_decay=1e-2, max_grad_norm=0.1, ranges=param_ranges(flat, rules))
+        rows[name] = (flat, opt, FinetuneStep(flat, opt, fcos_loss_fn(m)))
+    assert rows["freeze="][1].range_record == rows["freeze_stages"][1].range_record
+
+    def one(name):
+        flat, opt, step = rows[name]
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e[0].record()
+        losses, total = step.forward(meshes, targets)
+        e[1].record()
+        total.backward()
+        e[2].record()
+        opt.step()
+        e[3].record()
+        return e
+
+    for _ in range(args.warmup):
+        for name in rows:
+            one(name)
+    torch.cuda.synchronize()
+    rec = {name: [] for name in rows}
+    for _ in range(max(args.steps, 1)):
+        for name in rows:
+            rec[name].append(one(name))
+    torch.cuda.synchronize()
+    result = {"metric": "fcos_finetune_freeze_stages_ms", "backbone": args.backbone, "resolution": args.resolution, "batch": args.batch, "dtype": "bf16",
+              "steps": args.steps, "warmup": args.warmup, "freeze_stages": K, "elements": int(rows["freeze="][0]._flat.numel()),
+              "frozen_elements": int(rows["freeze="][1].range_record["bounds"][1])}
+    print(f"freeze_stages = {K}, {args.backbone} {args.resolution}^3 batch {args.batch}, {args.steps} steps each, ms as median [min .. max]:")
+    for name, runs in rec.items():
+        parts = {"forward": [e[0].elapsed_time(e[1]) for e in runs], "backward": [e[1].elapsed_time(e[2]) for e in runs],
+                 "optimizer": [e[2].elapsed_time(e[3]) for e in runs], "step": [e[0].elapsed_time(e[3]) for e in runs]}
+        result[name] = {k: {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)} for k, v in parts.items()}
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        held = torch.cuda.memory_allocated()
+        one(name)
+        torch.cuda.synchronize()
+        result[name]["max_memory_allocated_mib"] = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
+        result[name]["allocated_before_the_step_mib"] = round(held / 2 ** 20, 1)
+        print(f"{name:13s} " + "  ".join(f"{k} {statistics.median(v):.3f} [{min(v):.3f} .. {max(v):.3f}]" for k, v in parts.items())
+              + f"  peak {result[name]['max_memory_allocated_mib']:.1f} MiB (held before the step {result[name]['allocated_before_the_step_mib']:.1f})")
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
@@ -58,9 +123,12 @@ def main():
     ap.add_argument("--backbone", default="swin_s")
     ap.add_argument("--opt-repeats", type=int, default=100)
     ap.add_argument("--optimizer-only", action="store_true")
+    ap.add_argument("--freeze-stages", type=int, default=0, help="K > 0: time freeze= over the prefix against freeze_stages=K instead (DESIGN.md 3.27)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_finetune_step needs an MI355X (no CPU fallback)")
+    if args.freeze_stages:
+        return freeze_rows(args)
     from nerf_mae_amd import ops
     from nerf_mae_amd.finetune import FinetuneStep, FlatParameters, fcos_loss_fn, param_ranges, recipe_rules
     from nerf_mae_amd.trainer import FusedAdamW
