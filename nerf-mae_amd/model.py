@@ -83,6 +83,38 @@ def mask_window_aligned(mask, ws: int = WS) -> bool:
     return bool((v == v[:, :1, :, :1, :, :1]).all())
 
 
+class EmbedBound(NamedTuple):
+    """what the caller that draws the masks promises about them (it answers for it: the model does not look at a mask on the device).  The default promises
+    nothing: a row for every token, masks that may cut through windows."""
+    rows: Optional[int] = None   # no mask keeps more tokens per sample than this (rows per sample of the compact patch embed); None: g^3
+    aligned: bool = False        # every mask is constant on every 4^3 window (mask_window_aligned): stage 0's first block may run on the kept windows only
+
+
+def bound_of_mask(g: int, mask) -> EmbedBound:
+    """the bound of one known (g,g,g) mask (the eager forward, which draws its mask on the host): exactly the rows it needs, in 64-row granules"""
+    m = np.asarray(mask)
+    return EmbedBound(embed_capacity_rows(g, kept=g ** 3 - int(m.sum(dtype=np.int64))), mask_window_aligned(m))
+
+
+def mask_kept_aligned(g: int, block_mask, bits=None):
+    """(kept tokens, window-aligned) of a mask for `refit_bound`; bits: the (nb,nb,nb) block bits it travels as, if it does -- with nb * 4 == g every bit is
+    one window, aligned without looking"""
+    if bits is None:
+        m = np.asarray(block_mask)
+        return g ** 3 - int(m.sum()), mask_window_aligned(m)
+    bits = np.asarray(bits)
+    return g ** 3 - 64 * int(bits.sum()), bool(bits.shape[0] * 4 == g or mask_window_aligned(np.asarray(block_mask)))
+
+
+def refit_bound(bound: EmbedBound, g: int, kept: int, aligned: bool) -> Optional[EmbedBound]:
+    """a captured step and the next mask (`mask_kept_aligned`): None if the mask fits what was captured, else the bound to capture the step again with -- a row
+    for every token if it keeps more than bound.rows (eight standard deviations above the mean kept count: not expected to happen in a training run), the dense
+    first block if it cuts through 4^3 windows, both in ONE widened bound if it does both.  Pure."""
+    rows = g ** 3 if bound.rows is not None and bound.rows < g ** 3 and kept > bound.rows else bound.rows
+    new = EmbedBound(rows, bool(bound.aligned and aligned))
+    return None if new == bound else new
+
+
 def draw_block_bits(g: Sequence[int], p_remove: float, block: int = 4, rng=random) -> np.ndarray:
     """the draws of `draw_block_mask` only: uint8 array (nb0, nb1, nb2), 1 = block removed (same RNG stream, same order)"""
     nb = [max(0, (gi - block) // block + 1) for gi in g]
@@ -338,6 +370,21 @@ class UpPlan(NamedTuple):
     tail_box: bool = False
 
 
+class LossTail(NamedTuple):
+    """the 1x1 head + loss attached to the last decoder level (_UpBlockFn.forward, built by _decode_and_loss)"""
+    model: "SwinTransformer_MAE3D_New"
+    xb: Optional[Tensor] = None        # the padded batch (B,4,R,R,R): the target
+    extents: Optional[Tensor] = None   # [B,3] int32
+    tokmask: Optional[Tensor] = None   # [g^3] uint8
+    pred_out: Optional[Tensor] = None  # (B,4,R,R,R) to receive the prediction, or None
+    zero_padded: bool = False          # the caller vouches that xb is zero outside each sample's extents (plan_up_block: tail_zero_padded)
+
+    @classmethod
+    def of(cls, tail) -> Optional["LossTail"]:
+        """None, a LossTail, or the plain tuple (model, xb, extents, tokmask, pred_out[, zero_padded]) that callers passed before the record had names"""
+        return tail if tail is None or isinstance(tail, cls) else cls(*tail)
+
+
 def plan_up_block(cin: int, cout: int, k: int, has_proj: bool, layouts, dec1, B: int, v: int, dtype, x_grad: bool, tail: bool, tail_sums: bool,
                   has_queue: bool, sw: UpSwitches, tail_pred: bool = False, tail_zero_padded: bool = False) -> UpPlan:
     """layouts: the keys of _CONV_LAYOUTS' rows packed for the block; dec1: `_Dec1Pack.optional()` of the record built for THIS block, or None;
@@ -430,6 +477,43 @@ def plan_swin_block(C: int, heads: int, hidden: int, tokens: int, rows: int, B: 
                      token_bwd=bool(token_bwd), queue_wgrad=bool(sw.grouped_wgrad and bf16 and has_queue))
 
 
+class EmbedSwitches(NamedTuple):
+    """the `ops` switches `plan_embed` depends on, as plain values"""
+    embed_kept: bool
+    block0_kept: bool
+
+    @classmethod
+    def current(cls) -> "EmbedSwitches":
+        return cls(ops.EMBED_KEPT, ops.BLOCK0_KEPT)
+
+
+class EmbedPlan(NamedTuple):
+    """what the patch embed and stage 0's first block run on: decided once per forward by `plan_embed`, kept on ctx like the other two plans"""
+    # "dense": a row for every token
+    # "rows": with a mask the embedding of a removed token is never read -- it is replaced by mask_token -- so the im2row, the GEMM rows, the LayerNorm rows and the
+    #   weight-gradient contraction run on the KEPT tokens only, in compact rows [B][rows][.]; the output is the dense token grid
+    # "windows": the kept windows + one representative all-mask window per sample, [B][capW + 1][64][.] (csrc/block0.hip): the patch embed's rows are the input rows
+    #   of stage 0's first block, whose output _run_stage expands to the dense token grid
+    path: str
+    rows: int        # rows per sample of the im2row / GEMM / LayerNorm
+    capW: int        # window slots per sample in front of the representative one (0 unless path == "windows")
+    add_pos: bool    # + pos_embed inside the LayerNorm kernel
+
+
+def plan_embed(g: int, mask: bool, add_pos: bool, capacity: Optional[int], aligned: bool, block0_ok: bool, sw: EmbedSwitches) -> EmbedPlan:
+    """g^3 tokens per sample; mask: a token mask is applied; capacity / aligned: the caller's EmbedBound; block0_ok: stage 0 starts with an unshifted SwinBlock3D
+    of a width ops.block0_supported takes.  Pure: plain values in, EmbedPlan out."""
+    tps = g ** 3
+    kept = mask and sw.embed_kept and add_pos
+    if not kept:
+        return EmbedPlan("dense", tps, 0, bool(add_pos))
+    cap = min(tps, int(capacity)) if capacity else tps
+    if sw.block0_kept and aligned and g % 4 == 0 and block0_ok:
+        capW = max(1, min(cap // 64, (g // 4) ** 3))
+        return EmbedPlan("windows", 64 * (capW + 1), capW, True)
+    return EmbedPlan("rows", cap, 0, True)
+
+
 def wgrad_queue_for(owner, dtype) -> Optional["ops.WgradQueue"]:
     """the weight-gradient queue of `owner` (the model or one of its blocks) if gradients of this compute dtype go through it -- the grouped kernel takes bf16
     operands -- else None: each weight gradient is then a launch of its own"""
@@ -466,83 +550,69 @@ def _gradbuf(p: nn.Parameter) -> Tensor:
 # autograd Functions (one per block; explicit backward launching the HIP dgrad/wgrad kernels)
 # --------------------------------------------------------------------------------------------------
 class _EmbedFn(torch.autograd.Function):
-    """patch conv (im2row + GEMM) -> LayerNorm -> + pos_embed -> masked tokens <- mask_token (swin_mae3d.py:1455-1463).
-    With a mask (training) the embedding of a removed token is never read -- it is replaced by mask_token -- so the im2row, the GEMM rows, the LayerNorm rows and
-    the weight-gradient contraction run on the KEPT tokens only, in compact rows [B][cap][.] (ops.EMBED_KEPT; cap = model._embed_cap rows per sample, sized by
-    the caller that drew the mask).  Same values for every token that is read: the gradients differ from the full pass only by the order of fp32 sums."""
+    """patch conv (im2row + GEMM) -> LayerNorm -> + pos_embed -> masked tokens <- mask_token (swin_mae3d.py:1455-1463), on the rows of the EmbedPlan given
+    (model._embed / _embed_nomask).  Same values for every token that is read: the gradients of the compact paths differ from the full pass only by the order of
+    fp32 sums.  Returns (tokens, wmap): wmap is the window map of the "windows" path, which _run_stage(0) needs, else None."""
 
     @staticmethod
-    def forward(ctx, anchor, mod, xb, mask_dev):
+    def forward(ctx, anchor, mod, xb, mask_dev, plan):
         m: "SwinTransformer_MAE3D_New" = mod
+        p: EmbedPlan = plan
         m._wq.reset()   # first op of every forward pass: drops whatever a failed backward left queued
         B, R = xb.shape[0], xb.shape[2]
         g = R // 4
         tps = g ** 3
-        T, C, dtype = B * tps, m.embed_dim, m.compute_dtype
-        use_mask = mask_dev is not None
-        kept = use_mask and ops.EMBED_KEPT and m._add_pos
-        cap = min(tps, int(m._embed_cap)) if (kept and m._embed_cap) else tps
-        m._b0 = None
-        if kept and m._block0_kept_ok(g):
-            # stage 0's first block runs on the kept windows + one representative all-mask window per sample: the patch embed's rows are that block's input rows,
-            # [B][capW + 1][64][.] (csrc/block0.hip); _run_stage expands the block's output to the dense token grid
-            capW = max(1, min(cap // 64, (g // 4) ** 3))
-            rowmap, wmap = ops.block0_window_rows(mask_dev, g, capW)
-            capR = 64 * (capW + 1)
-            A = torch.empty((B * capR, 256), dtype=dtype, device=xb.device)
-            ops.patch_embed_gather_kept(xb, A, B, R, rowmap, capR)
-            conv, ln = m.patch_partition[0], m.patch_partition[2]
-            y0 = ops.gemm_nt(A, m._pk["pe.w"].view(C, 256), bias=conv.bias)
-            tok = torch.empty((B * capR, C), dtype=dtype, device=xb.device)
-            mean, rstd = torch.empty(B * capR, device=xb.device), torch.empty(B * capR, device=xb.device)
-            ops.block0_embed_norm_fwd(y0, ln.weight, ln.bias, tok, mean, rstd, m.pos_embed.view(-1, C), m.mask_token, wmap, B, g, capW, C)
-            ctx.m, ctx.saved, ctx.dims, ctx.b0 = m, (A, y0, mean, rstd, mask_dev, rowmap), (T, C, g, capR), (wmap, B, capW)
-            m._b0 = (wmap, g, capW)
-            return tok
-        ctx.b0 = None
-        rowmap = ops.embed_kept_rows(mask_dev, cap) if kept else None
-        rows = B * cap if kept else T
-        A = torch.empty((rows, 256), dtype=dtype, device=xb.device)
-        if kept:
-            ops.patch_embed_gather_kept(xb, A, B, R, rowmap, cap)
-        else:
+        C, dtype, dev = m.embed_dim, m.compute_dtype, xb.device
+        rowmap = wmap = None
+        if p.path == "windows":
+            rowmap, wmap = ops.block0_window_rows(mask_dev, g, p.capW)
+        elif p.path == "rows":
+            rowmap = ops.embed_kept_rows(mask_dev, p.rows)
+        A = torch.empty((B * p.rows, 256), dtype=dtype, device=dev)
+        if rowmap is None:
             ops.patch_embed_gather(xb, A, B, R)
+        else:
+            ops.patch_embed_gather_kept(xb, A, B, R, rowmap, p.rows)
         conv, ln = m.patch_partition[0], m.patch_partition[2]
         y0 = ops.gemm_nt(A, m._pk["pe.w"].view(C, 256), bias=conv.bias)
-        tok = torch.empty((T, C), dtype=dtype, device=xb.device)
-        mean, rstd = torch.empty(T, device=xb.device), torch.empty(T, device=xb.device)
-        if kept:
-            ops.embed_norm_fwd_kept(y0, ln.weight, ln.bias, tok, mean, rstd, T, C, m.pos_embed.view(-1, C), mask_dev, m.mask_token, tps, rowmap, cap)
+        T = B * (p.rows if p.path == "windows" else tps)   # rows of the output: compact on the "windows" path alone
+        tok = torch.empty((T, C), dtype=dtype, device=dev)
+        mean, rstd = torch.empty(T, device=dev), torch.empty(T, device=dev)
+        if p.path == "windows":
+            ops.block0_embed_norm_fwd(y0, ln.weight, ln.bias, tok, mean, rstd, m.pos_embed.view(-1, C), m.mask_token, wmap, B, g, p.capW, C)
+            ctx.mark_non_differentiable(wmap)
+        elif p.path == "rows":
+            ops.embed_norm_fwd_kept(y0, ln.weight, ln.bias, tok, mean, rstd, T, C, m.pos_embed.view(-1, C), mask_dev, m.mask_token, tps, rowmap, p.rows)
         else:
-            ops.layernorm_fwd(y0, ln.weight, ln.bias, tok, mean, rstd, T, C, pos=m.pos_embed.view(-1, C) if m._add_pos else None,
-                              mask=mask_dev, mask_token=m.mask_token if use_mask else None, tokens_per_sample=tps)
-        ctx.m, ctx.saved, ctx.dims = m, (A, y0, mean, rstd, mask_dev, rowmap), (T, C, g, cap)
-        return tok
+            ops.layernorm_fwd(y0, ln.weight, ln.bias, tok, mean, rstd, T, C, pos=m.pos_embed.view(-1, C) if p.add_pos else None,
+                              mask=mask_dev, mask_token=m.mask_token if mask_dev is not None else None, tokens_per_sample=tps)
+        ctx.m, ctx.plan, ctx.saved, ctx.dims = m, p, (A, y0, mean, rstd, mask_dev, rowmap, wmap), (B, g, C)
+        return tok, wmap
 
     @staticmethod
-    def backward(ctx, dtok):
-        m = ctx.m
-        A, y0, mean, rstd, mask_dev, rowmap = ctx.saved
-        T, C, g, cap = ctx.dims
+    def backward(ctx, dtok, _dwmap=None):
+        m, p = ctx.m, ctx.plan
+        A, y0, mean, rstd, mask_dev, rowmap, wmap = ctx.saved
+        B, g, C = ctx.dims
+        tps = g ** 3
         conv, ln = m.patch_partition[0], m.patch_partition[2]
         dy0 = torch.empty_like(y0)
-        if ctx.b0 is not None:   # dtok: the compact input gradient of stage 0's first block
-            wmap, B, capW = ctx.b0
-            ops.block0_embed_norm_bwd(dtok.contiguous(), y0, ln.weight, mean, rstd, dy0, _gradbuf(ln.weight), _gradbuf(ln.bias), _gradbuf(m.mask_token), wmap, B, g, capW, C)
-        elif rowmap is not None:
-            ops.embed_norm_bwd_kept(dtok.contiguous(), y0, ln.weight, mean, rstd, dy0, _gradbuf(ln.weight), _gradbuf(ln.bias), T, C, mask_dev, _gradbuf(m.mask_token),
-                                    g ** 3, rowmap, cap)
+        if p.path == "windows":   # dtok: the compact input gradient of stage 0's first block
+            ops.block0_embed_norm_bwd(dtok.contiguous(), y0, ln.weight, mean, rstd, dy0, _gradbuf(ln.weight), _gradbuf(ln.bias), _gradbuf(m.mask_token), wmap, B, g, p.capW, C)
+        elif p.path == "rows":
+            ops.embed_norm_bwd_kept(dtok.contiguous(), y0, ln.weight, mean, rstd, dy0, _gradbuf(ln.weight), _gradbuf(ln.bias), B * tps, C, mask_dev,
+                                    _gradbuf(m.mask_token), tps, rowmap, p.rows)
         else:
-            ops.layernorm_bwd(dtok.contiguous(), y0, ln.weight, mean, rstd, dy0, _gradbuf(ln.weight), _gradbuf(ln.bias), T, C,
-                              mask=mask_dev, dmask_token=_gradbuf(m.mask_token) if mask_dev is not None else None, tokens_per_sample=g ** 3)
+            ops.layernorm_bwd(dtok.contiguous(), y0, ln.weight, mean, rstd, dy0, _gradbuf(ln.weight), _gradbuf(ln.bias), B * tps, C,
+                              mask=mask_dev, dmask_token=_gradbuf(m.mask_token) if mask_dev is not None else None, tokens_per_sample=tps)
         q = wgrad_queue_for(m, dy0.dtype)
         if q is not None:
-            q.add(dy0, A, _gradbuf(conv.weight).view(C, 256), dbias=_gradbuf(conv.bias), rows_per_sample=cap if rowmap is not None else g ** 3)
+            q.add(dy0, A, _gradbuf(conv.weight).view(C, 256), dbias=_gradbuf(conv.bias), rows_per_sample=p.rows)
             q.flush(foreground=True)
             q.join()      # the backward pass ends here: every deferred weight gradient has been issued and joined
         else:
             ops.gemm_tn(dy0, A, _gradbuf(conv.weight), dbias=_gradbuf(conv.bias))
-        return None, None, None, None
+        return None, None, None, None, None
 
 
 class _Block0ExpandFn(torch.autograd.Function):
@@ -802,7 +872,7 @@ class _UpBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, skip, mod, B, v, tail=None):
-        """tail = (model, xb, extents, tokmask, pred_out[, zero_padded]): the block is the last decoder level and the 1x1 head + loss are
+        """tail (a LossTail): the block is the last decoder level and the 1x1 head + loss are
         evaluated here, so that backward can fuse the loss gradient with the backward of the last InstanceNorm; returns the
         loss triple instead of the feature map."""
         m: "UpBlock3D" = mod
@@ -873,7 +943,7 @@ class _UpBlockFn(torch.autograd.Function):
         if tail is None:
             return out
         assert p.fused_tail
-        model, xb, extents, tokmask, pred_out = tail[:5]
+        model, xb, extents, tokmask, pred_out = tail.model, tail.xb, tail.extents, tail.tokmask, tail.pred_out
         lsums = torch.empty(8, dtype=torch.float64, device=dev)
         losses = torch.empty(3, device=dev)
         dpred = torch.empty((B * V, 4), device=dev) if p.x_grad else None
@@ -1026,11 +1096,7 @@ class PatchPartition(nn.Sequential):
     def forward(self, x):
         m = self._owner()
         m._ensure_ready(x.device)
-        m._add_pos = False
-        try:
-            tok = m._embed_nomask(x.float().contiguous())
-        finally:
-            m._add_pos = True
+        tok = m._embed_nomask(x.float().contiguous(), add_pos=False)
         g = x.shape[2] // 4
         return tok.view(x.shape[0], g, g, g, -1)
 
@@ -1129,19 +1195,19 @@ class UpBlock3D(nn.Module):
     _wq = None   # the model's weight-gradient queue (set by its _build_packer; a block packed on its own, as by heads.py, has none)
 
     def _plan(self, B, v, dtype, x_grad, tail) -> UpPlan:
-        """plan_up_block on this block's packed layouts, the tail = (model, ...) of _UpBlockFn.forward and the switches as they are now"""
-        pk = self._pk
+        """plan_up_block on this block's packed layouts, the LossTail of _UpBlockFn.forward (or None) and the switches as they are now"""
+        pk, tail = self._pk, LossTail.of(tail)
         layouts = {n for row in _CONV_LAYOUTS.values() for n in row if self._key + n in pk.views}
         dec1 = pk.dec1.optional() if (pk.dec1 is not None and pk.dec1.block is self) else None
         return plan_up_block(self.cin, self.cout, self.k, self.has_proj, layouts, dec1, B, v, dtype, x_grad, tail is not None,
-                             tail is not None and tail[0].fuse_tail_sums, self._wq is not None, UpSwitches.current(),
-                             tail_pred=tail is not None and len(tail) > 4 and tail[4] is not None, tail_zero_padded=tail is not None and len(tail) > 5 and bool(tail[5]))
+                             tail is not None and tail.model.fuse_tail_sums, self._wq is not None, UpSwitches.current(),
+                             tail_pred=tail is not None and tail.pred_out is not None, tail_zero_padded=tail is not None and bool(tail.zero_padded))
 
     def forward(self, x, skip=None, tail=None):
         """channels-last (B,v,v,v,Cin) [+ skip (B,kv,kv,kv,Cout)] -> (B,kv,kv,kv,Cout), or the loss triple when `tail` is given"""
         B, v = x.shape[0], x.shape[1]
         S = v * self.k
-        out = _UpBlockFn.apply(x.reshape(-1, self.cin), skip.reshape(-1, self.cout) if self.use_skip else None, self, B, v, tail)
+        out = _UpBlockFn.apply(x.reshape(-1, self.cin), skip.reshape(-1, self.cout) if self.use_skip else None, self, B, v, LossTail.of(tail))
         return out if tail is not None else out.view(B, S, S, S, self.cout)
 
 
@@ -1202,13 +1268,8 @@ class SwinTransformer_MAE3D_New(nn.Module):
         nn.init.normal_(self.mask_token, std=0.02)
         self._flat = self._flat_grad = None
         self._packer = None
-        self._add_pos = True
         self._anchor = None
         self._reducer = None  # dist.GradReducer when data-parallel
-        self._embed_cap = None   # rows per sample of the compact patch embed of the kept tokens (_EmbedFn); None = every token has a row
-        # the caller that drew the mask found it constant on every 4^3 window (mask_window_aligned): stage 0's first block may run on the kept windows only
-        self._block0_aligned = False
-        self._b0 = None          # (wmap, g, capW) of the compact tokens the last _EmbedFn.forward returned; taken by _run_stage(0)
         self._frozen_stages = 0  # the frozen prefix: patch embed + stages[:k] run without a graph (frozen_stages)
 
     @property
@@ -1233,27 +1294,32 @@ class SwinTransformer_MAE3D_New(nn.Module):
             raise ValueError(f"{who}: the encoder has frozen_stages = {self._frozen_stages}; the MAE pre-training path does not implement the frozen prefix -- set "
                              "frozen_stages = 0 (freeze= still keeps ranges from being stepped), or fine-tune through finetune.FinetuneStep")
 
-    def _embed_nomask(self, xb: Tensor) -> Tensor:
+    def _embed_nomask(self, xb: Tensor, add_pos: bool = True) -> Tensor:
         """the unmasked patch embed of the downstream models -> (B g^3, C) tokens; under a frozen prefix without a graph (no _EmbedFn context is kept)"""
+        p = self._plan_embed(xb.shape[2] // 4, False, add_pos)
         if self._frozen_stages:
             with torch.no_grad():
-                return _EmbedFn.apply(self._anchor, self, xb, None)
-        return _EmbedFn.apply(self._anchor, self, xb, None)
+                return _EmbedFn.apply(self._anchor, self, xb, None, p)[0]
+        return _EmbedFn.apply(self._anchor, self, xb, None, p)[0]
 
-    def _block0_kept_ok(self, g: int) -> bool:
-        """the conditions of the kept-window path of stage 0's first block other than those of the compact patch embed (ops.BLOCK0_KEPT)"""
+    def _plan_embed(self, g: int, mask: bool, add_pos: bool = True, bound: Optional[EmbedBound] = None) -> EmbedPlan:
+        """plan_embed on this model's first block, the caller's bound (None: EmbedBound(), which promises nothing) and the switches as they are now"""
+        bound = bound or EmbedBound()
         b0 = self.stages[0][0] if len(self.stages) and len(self.stages[0]) else None
-        return bool(ops.BLOCK0_KEPT and self._block0_aligned and g % 4 == 0 and isinstance(b0, SwinBlock3D) and not any(b0.shift_size)
-                    and ops.block0_supported(self.embed_dim))
+        block0_ok = bool(mask and bound.aligned and isinstance(b0, SwinBlock3D) and not any(b0.shift_size)
+                         and ops.block0_supported(self.embed_dim))   # (the library is asked only where the answer can matter)
+        return plan_embed(g, mask, add_pos, bound.rows, bound.aligned, block0_ok, EmbedSwitches.current())
 
-    def _embed(self, xb: Tensor, mask_dev: Tensor) -> Tensor:
-        """patch embed of a masked batch -> the input of stage 0: the dense token grid (B,g,g,g,C), or -- kept-window path -- the compact rows as the grid
-        (B, 4 (capW + 1), 4, 4, C) whose token order is its window order (self._b0 is set then)"""
+    def _embed(self, xb: Tensor, mask_dev: Tensor, bound: Optional[EmbedBound] = None):
+        """patch embed of a masked batch -> (the input of stage 0, b0).  b0 = None: the dense token grid (B,g,g,g,C); kept-window path: the compact rows as the
+        grid (B, 4 (capW + 1), 4, 4, C) whose token order is its window order, and b0 = (wmap, g, capW), which _run_stage(0) takes.  The caller answers for
+        `bound`: it draws the masks."""
         B, g = xb.shape[0], xb.shape[2] // 4
-        tok = _EmbedFn.apply(self._anchor, self, xb, mask_dev)
-        if self._b0 is not None:
-            return tok.view(B, 4 * (self._b0[2] + 1), 4, 4, self.embed_dim)
-        return tok.view(B, g, g, g, self.embed_dim)
+        p = self._plan_embed(g, True, bound=bound)
+        tok, wmap = _EmbedFn.apply(self._anchor, self, xb, mask_dev, p)
+        if p.path == "windows":
+            return tok.view(B, 4 * (p.capW + 1), 4, 4, self.embed_dim), (wmap, g, p.capW)
+        return tok.view(B, g, g, g, self.embed_dim), None
 
     # ---- flat buffers + packed weights ------------------------------------------------------------
     def _trainable(self):
@@ -1424,8 +1490,9 @@ class SwinTransformer_MAE3D_New(nn.Module):
         noise = torch.bernoulli(keep).div_(keep)
         return [(noise[2 * i], noise[2 * i + 1]) for i in range(len(blocks))]
 
-    def _run_stage(self, si: int, x: Tensor, sd_noise, bi: int, red=None):
+    def _run_stage(self, si: int, x: Tensor, sd_noise, bi: int, red=None, b0=None):
         """stage `si` on channels-last x; `bi` = index of the stage's first block in `sd_noise`.  Returns (output, next block index).
+        b0 (stage 0): the (wmap, g, capW) of _embed -- x holds compact rows, the first block runs on them and its output is expanded to the dense token grid.
         With a data-parallel reducer the stage (each block group of the chunked stage, dist.GradReducer) is preceded by the trigger that
         launches its gradient range's all-reduce -- backward order: blocks of the group, the flush that issues (and joins) their queued weight
         gradients, then the trigger."""
@@ -1433,7 +1500,6 @@ class SwinTransformer_MAE3D_New(nn.Module):
             self._packer.wait_late()
         q = wgrad_queue_for(self, self.compute_dtype) if torch.is_grad_enabled() and x.requires_grad else None
         groups = red.chunk_groups if (red is not None and si == getattr(red, "chunk_stage", -1) and red.chunk_groups) else [list(self.stages[si])]
-        b0, self._b0 = (self._b0 if si == 0 else None), None   # x holds compact rows (_embed): the first block runs on them, its output is expanded
         for k, grp in enumerate(groups):
             if red is not None:
                 x = red.trigger(x, red.seg_stage(si, k))  # backward reaching here => this range's gradients are complete
@@ -1450,7 +1516,8 @@ class SwinTransformer_MAE3D_New(nn.Module):
                     x = mod(x)
         return x, bi
 
-    def forward_encoder(self, tok: Tensor, sd_noise=None):
+    def forward_encoder(self, tok: Tensor, sd_noise=None, b0=None):
+        """b0: what _embed returned beside `tok` (None: tok is the dense token grid)"""
         feats, x, bi = [], tok, 0
         red = self._reducer
         if sd_noise is None:
@@ -1461,14 +1528,14 @@ class SwinTransformer_MAE3D_New(nn.Module):
             if si < nf:
                 # the frozen prefix: no graph, no flush, no trigger, no fork -- the feature goes to the neck / decoder as it is
                 with torch.no_grad():
-                    x, bi = self._run_stage(si, x, sd_noise, bi, None)
+                    x, bi = self._run_stage(si, x, sd_noise, bi, None, b0 if si == 0 else None)
                 feats.append(x)
                 if si + 1 == nf and si + 1 < len(self.stages) and torch.is_grad_enabled():
                     # the boundary: a leaf that requires a gradient, so that the first live stage keeps its plans (plan_swin_block: x_grad) and gets its flush,
                     # which is the one that ends the backward pass.  Its gradient (one LayerNorm backward's dx store) is computed for nothing.
                     x = x.detach().requires_grad_()
                 continue
-            x, bi = self._run_stage(si, x, sd_noise, bi, red)
+            x, bi = self._run_stage(si, x, sd_noise, bi, red, b0 if si == 0 else None)
             if si + 1 < len(self.stages) and torch.is_grad_enabled() and x.requires_grad:
                 x, skip = _Fork2Fn.apply(x)     # consumed by the next stage and by a decoder / neck
                 feats.append(skip)
@@ -1499,7 +1566,7 @@ class SwinTransformer_MAE3D_New(nn.Module):
 
     def _decode_and_loss(self, feats, xb, ext, mask_dev, pred):
         if self.fuse_tail:
-            return self.forward_decoder(feats, tail=(self, xb, ext, mask_dev, pred, True))   # (xb: zero outside ext -- transform / the batcher padded it)
+            return self.forward_decoder(feats, tail=LossTail(self, xb, ext, mask_dev, pred, zero_padded=True))   # (xb: zero outside ext -- transform / the batcher padded it)
         d0 = self.forward_decoder(feats)
         return _LossFn.apply(d0.reshape(-1, d0.shape[-1]), self, xb, ext, mask_dev, pred)
 
@@ -1514,13 +1581,8 @@ class SwinTransformer_MAE3D_New(nn.Module):
             block_mask = draw_block_mask((g, g, g), self.masking_prob)
         mask_dev = block_mask.to(torch.uint8).contiguous().view(-1).to(device, non_blocking=True)
         # the mask was drawn on the host: the compact patch embed gets exactly the rows it needs (64-row granules)
-        cap_was, self._embed_cap = self._embed_cap, embed_capacity_rows(g, kept=int(g ** 3 - int(block_mask.to(torch.int64).sum())))
-        al_was, self._block0_aligned = self._block0_aligned, ops.BLOCK0_KEPT and mask_window_aligned(block_mask.cpu().numpy())
-        try:
-            tok = self._embed(xb, mask_dev)
-        finally:
-            self._embed_cap, self._block0_aligned = cap_was, al_was
-        feats = self.forward_encoder(tok, sd_noise)
+        tok, b0 = self._embed(xb, mask_dev, bound_of_mask(g, block_mask.cpu().numpy()))
+        feats = self.forward_encoder(tok, sd_noise, b0)
         want_pred = is_eval or return_pred
         pred = torch.empty((B, 4, R, R, R), device=device) if want_pred else None
         losses = self._decode_and_loss(feats, xb, ext, mask_dev, pred)
@@ -1533,16 +1595,16 @@ class SwinTransformer_MAE3D_New(nn.Module):
             return loss, loss_rgb, loss_alpha, patch(pred), tgt[..., 3:] > 0.01, tgt
         return loss, loss_rgb, loss_alpha
 
-    def forward_static(self, xb: Tensor, ext: Tensor, mask_dev: Tensor):
+    def forward_static(self, xb: Tensor, ext: Tensor, mask_dev: Tensor, bound: Optional[EmbedBound] = None):
         """graph-capturable training forward: everything already on the device (padded batch (B,4,R,R,R) fp32, extents [B,3]
-        int32, token mask [g^3] uint8); no host<->device traffic, no python RNG.
+        int32, token mask [g^3] uint8); no host<->device traffic, no python RNG.  bound: what the caller, who draws the masks, promises about them.
         PRECONDITION: xb is ZERO outside each sample's extents, as `transform` and the batcher's slots make it -- the tail then walks each sample's valid box
         alone (UpPlan.tail_box, ops.TAIL_BOX); on a batch padded with anything else, set ops.TAIL_BOX = False."""
         B, R = xb.shape[0], self.resolution
         g = R // 4
         self._packer.run()
-        tok = self._embed(xb, mask_dev)   # (the caller answers for self._embed_cap and self._block0_aligned: it draws the masks)
-        losses = self._decode_and_loss(self.forward_encoder(tok), xb, ext, mask_dev, None)
+        tok, b0 = self._embed(xb, mask_dev, bound)
+        losses = self._decode_and_loss(self.forward_encoder(tok, b0=b0), xb, ext, mask_dev, None)
         return losses[0], losses[1], losses[2]
 
     def encoder_features(self, xb: Tensor) -> List[Tensor]:

@@ -210,13 +210,11 @@ class GraphedTrainStep:
         self.x = torch.zeros((batch, 4, R, R, R), device=dev)
         self.ext = torch.full((batch, 3), R, dtype=torch.int32, device=dev)
         self.mask = torch.zeros(g ** 3, dtype=torch.uint8, device=dev)
-        # rows per sample of the compact patch embed of the kept tokens (model._EmbedFn): fixed at capture from the mask distribution; every mask is checked
-        # against it in __call__ (a mask that keeps more tokens re-captures the step with a row for every token)
-        from .model import embed_capacity_rows
-        self._embed_cap = embed_capacity_rows(g, p_remove=model.masking_prob)
-        # stage 0's first block on the kept windows only (ops.BLOCK0_KEPT): captured for masks that are constant on every 4^3 window, as the block masks are;
-        # every mask is checked in __call__ (one that is not re-captures the step with the dense block)
-        self._block0 = bool(ops.BLOCK0_KEPT and g % 4 == 0)
+        # what the step is captured for (model.EmbedBound): rows per sample of the compact patch embed of the kept tokens, from the mask distribution, and masks
+        # that are constant on every 4^3 window, as the block masks are (stage 0's first block on the kept windows only, ops.BLOCK0_KEPT).  Every mask is checked
+        # against it in __call__ / begin (_fit_capture): one that keeps more tokens, or cuts through windows, re-captures the step with the widened bound
+        from .model import EmbedBound, embed_capacity_rows
+        self.bound = EmbedBound(embed_capacity_rows(g, p_remove=model.masking_prob), bool(ops.BLOCK0_KEPT and g % 4 == 0))
         self.losses = None
         if self.accumulate > 1:
             # outside the graphs' pool: the sum of the micro-batches' three losses, and their mean (the optimizer graph writes it and clears the sum)
@@ -246,19 +244,11 @@ class GraphedTrainStep:
     def _fwd_bwd(self, zero=True):
         if zero:
             self.model.zero_grad()
-        out = self.model.forward_static(self.x, self.ext, self.mask)
+        out = self.model.forward_static(self.x, self.ext, self.mask, self.bound)
         out[0].backward()
         return out
 
     def _capture(self):
-        cap_was, self.model._embed_cap = self.model._embed_cap, self._embed_cap
-        al_was, self.model._block0_aligned = self.model._block0_aligned, self._block0
-        try:
-            self._capture_graphs()
-        finally:
-            self.model._embed_cap, self.model._block0_aligned = cap_was, al_was
-
-    def _capture_graphs(self):
         import os
         import torch.distributed as tdist
         ops.side_stream.auto(self.x.shape[0])
@@ -371,10 +361,10 @@ class GraphedTrainStep:
         B, R = self.x.shape[0], m.resolution
         g = R // 4
         m._packer.run(late_split=False)   # the stages are captured into separate graphs
-        tok = m._embed(self.x, self.mask)
+        tok, b0 = m._embed(self.x, self.mask, self.bound)
         sd = m._draw_sd_noise(B, tok.device)
         m._wq.sync_after_flush = False
-        f0, bi = m._run_stage(0, tok, sd, 0)
+        f0, bi = m._run_stage(0, tok, sd, 0, b0=b0)
         f1, bi = m._run_stage(1, f0, sd, bi)
         e1 = f1.detach().requires_grad_()
         groups = self._stage2_chunks()
@@ -463,19 +453,13 @@ class GraphedTrainStep:
     def _fit_capture(self, block_mask, bits):
         """capture the step again where `block_mask` does not fit what was captured: a mask that cuts through 4^3 windows, or keeps more tokens than the embed has
         rows for.  The warm-up of a capture clears the gradient buffer, so under accumulation this runs for every mask of a step before its first replay."""
+        from .model import mask_kept_aligned, refit_bound
         g = self.model.resolution // 4
-        if self._block0:
-            from .model import mask_window_aligned
-            if not (bits is not None and np.asarray(bits).shape[0] * 4 == g) and not mask_window_aligned(np.asarray(block_mask)):
-                self._block0 = False   # a mask that cuts through 4^3 windows: the step is captured again with the dense first block, as on a capacity overflow
-                torch.cuda.synchronize()
-                self._capture()
-        if self._embed_cap < g ** 3:
-            kept = g ** 3 - (64 * int(np.asarray(bits).sum()) if bits is not None else int(np.asarray(block_mask).sum()))
-            if kept > self._embed_cap:   # (eight standard deviations above the mean kept count: not expected to happen in a training run)
-                self._embed_cap = g ** 3
-                torch.cuda.synchronize()
-                self._capture()
+        new = refit_bound(self.bound, g, *mask_kept_aligned(g, block_mask, bits))
+        if new is not None:
+            self.bound = new
+            torch.cuda.synchronize()
+            self._capture()
 
     def _send(self, bits, hyper):
         """mask bits + optimizer hyper-parameters + extents as kernel arguments of one launch: nothing in the step waits on a copy.

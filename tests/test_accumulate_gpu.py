@@ -249,7 +249,7 @@ def test_a_mask_that_needs_a_new_capture_does_not_lose_the_first_micro_gradient(
     opt = FusedAdamW(m, **OPT)
     step = GraphedTrainStep(m, opt, 1, accumulate=2)
     if why == "capacity":
-        step._embed_cap = cap
+        step.bound = step.bound._replace(rows=cap)
     step._load([_grid(40)])
     step._capture()                                       # the step as captured for masks like the first
     g1 = step._g1
@@ -257,7 +257,7 @@ def test_a_mask_that_needs_a_new_capture_does_not_lose_the_first_micro_gradient(
     torch.cuda.synchronize()
     if recaptures:
         assert step._g1 is not g1, "the step was captured again"
-        assert (step._embed_cap == 512) if why == "capacity" else (step._block0 is False)
+        assert (step.bound.rows == 512) if why == "capacity" else (step.bound.aligned is False)
     err = _perr(m._flat, ref_p)
     print(f"  [re-capture, {why}] parameters {err:.2e}")
     assert err < PTOL

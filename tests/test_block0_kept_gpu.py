@@ -213,10 +213,10 @@ def test_a_mask_that_cuts_through_windows_takes_the_dense_block(monkeypatch, dty
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_capacity_above_the_kept_window_count(monkeypatch, dtype):
-    """what a captured step runs with: forward_static with model._embed_cap above the kept count -- zero windows behind the count.  Bounds: those of the capacity
+    """what a captured step runs with: forward_static with the bound's rows above the kept count -- zero windows behind the count.  Bounds: those of the capacity
     part of test_patch_embed_of_the_kept_tokens_only_changes_nothing"""
     from nerf_mae_amd import ops
-    from nerf_mae_amd.model import embed_capacity_rows
+    from nerf_mae_amd.model import EmbedBound, embed_capacity_rows
     _, hip = _pair(SWIN_T, dtype, res=32, init="default")
     xs, bm = _inputs(), _masks()["bernoulli"]
     calls = []
@@ -229,16 +229,12 @@ def test_capacity_above_the_kept_window_count(monkeypatch, dtype):
     assert exact < 512
     outs = []
     for cap in (exact, 512):
-        hip._embed_cap, hip._block0_aligned = cap, True
-        try:
-            hip.zero_grad()
-            torch.manual_seed(3)
-            l = hip.forward_static(xb, ext, md)
-            l[0].backward()
-            torch.cuda.synchronize()
-            outs.append((l[0].item(), hip._flat_grad.clone()))
-        finally:
-            hip._embed_cap, hip._block0_aligned = None, False
+        hip.zero_grad()
+        torch.manual_seed(3)
+        l = hip.forward_static(xb, ext, md, EmbedBound(cap, aligned=True))
+        l[0].backward()
+        torch.cuda.synchronize()
+        outs.append((l[0].item(), hip._flat_grad.clone()))
     assert calls == [exact // 64, 8]                                     # both ran the kept-window path, with these slot counts
     assert abs(outs[1][0] - outs[0][0]) <= 5e-6 * abs(outs[0][0])
     assert relerr(outs[1][1], outs[0][1]) <= (2e-5 if dtype == torch.float32 else 5e-3)
@@ -257,7 +253,7 @@ def test_captured_step_replays_the_kept_window_block_and_falls_back(monkeypatch)
     xs = _inputs()
     opt = FusedAdamW(hip, lr=0.0, weight_decay=0.0, max_grad_norm=0.1)     # lr 0: the weights stay put
     step = GraphedTrainStep(hip, opt, 2)
-    step._embed_cap = 256                                                 # four window slots: above the first mask's count, equal to the second's
+    step.bound = step.bound._replace(rows=256)                                           # four window slots: above the first mask's count, equal to the second's
     calls = []
     real_expand = ops.block0_expand
     monkeypatch.setattr(ops, "block0_expand", lambda *a, **k: (calls.append(1), real_expand(*a, **k))[1])
@@ -267,12 +263,12 @@ def test_captured_step_replays_the_kept_window_block_and_falls_back(monkeypatch)
     m2 = torch.ones(8, 8, 8, dtype=torch.uint8)
     m2[:4, 4:, :] = 0
     m2[4:, :4, :] = 0                                                     # four windows kept
-    assert step._block0
+    assert step.bound.aligned
     for i, bm in enumerate((m1, m2, m1, _unaligned())):
         n0 = len(calls)
         losses = step(xs if i == 0 else None, bm)
         torch.cuda.synchronize()
-        captured_b0 = len(calls) > n0
+        with_block0 = len(calls) > n0
         gn = opt.norm.item()
         ref.zero_grad()
         want = ref(xs, block_mask=bm)
@@ -281,5 +277,5 @@ def test_captured_step_replays_the_kept_window_block_and_falls_back(monkeypatch)
         wn = ref._flat_grad.double().norm().item()
         assert abs(losses[0].item() - want[0].item()) <= 2e-5 * abs(want[0].item()), (i, losses[0].item(), want[0].item())
         assert abs(gn - wn) <= 5e-3 * wn, (i, gn, wn)
-        assert step._block0 == (i < 3)
-        assert captured_b0 == (i == 0)                                    # captured with the kept-window block once; the fall-back capture holds none
+        assert step.bound.aligned == (i < 3)
+        assert with_block0 == (i == 0)                                  # captured with the kept-window block once; the fall-back capture holds none

@@ -232,6 +232,30 @@ def test_up_block_plan_in_fp32_is_the_generic_path():
     assert m.decoder2._plan(2, 4, torch.float32, True, None).proj
 
 
+def test_loss_tail_record_reaches_the_up_block_plan(monkeypatch):
+    """UpBlock3D._plan hands plan_up_block tail_pred = "pred_out is given" and tail_zero_padded = the record's flag (False where it is left out), as it did with
+    the 5- and 6-element tuples; no tail: neither"""
+    from types import SimpleNamespace
+    from nerf_mae_amd import model as M
+    seen = []
+    monkeypatch.setattr(M, "plan_up_block", lambda *a, **kw: seen.append((a[10], a[11], kw["tail_pred"], kw["tail_zero_padded"])))   # (tail, tail_sums, ...)
+    stub = SimpleNamespace(fuse_tail_sums=True)
+    blk = M.UpBlock3D(96, 48, 4, use_skip=False)
+    blk._pk = SimpleNamespace(views={}, dec1=None)
+    blk._key, blk._wq = "decoder1.", None
+    pred = torch.empty(1)
+    assert M.LossTail._fields == ("model", "xb", "extents", "tokmask", "pred_out", "zero_padded")
+    for tail in (M.LossTail(stub, None, None, None, None), M.LossTail(stub, None, None, None, None, True), M.LossTail(stub, None, None, None, pred, True),
+                 M.LossTail(stub, None, None, None, pred, zero_padded=False), None):
+        blk._plan(2, 8, torch.bfloat16, True, tail)
+    assert seen == [(True, True, False, False), (True, True, False, True), (True, True, True, True), (True, True, True, False), (False, False, False, False)]
+    # the plain tuples of before are read as the record (LossTail.of): 1, 5 and 6 elements
+    for old, new in (((stub,), M.LossTail(stub)), ((stub, None, None, None, pred), M.LossTail(stub, pred_out=pred)),
+                     ((stub, None, None, None, None, True), M.LossTail(stub, zero_padded=True))):
+        assert M.LossTail.of(old) == new and M.LossTail.of(new) is new
+    assert M.LossTail.of(None) is None
+
+
 def test_up_block_plan_of_the_other_levels_and_backbones():
     from nerf_mae_amd.model import plan_up_block
     bf, sw = torch.bfloat16, _switches()
@@ -344,6 +368,118 @@ def test_swin_block_plans_itself_and_names_its_queue(monkeypatch):
     assert wgrad_queue_for(m, torch.float32) is None and wgrad_queue_for(m, torch.bfloat16) is m._wq and wgrad_queue_for(blk, torch.bfloat16) is m._wq
     monkeypatch.setattr(ops, "GROUPED_WGRAD", False)
     assert wgrad_queue_for(m, torch.bfloat16) is None
+
+
+# ---- the patch embed's plan (model.plan_embed): which rows the embed and stage 0's first block run on, asked with plain values
+def _embed_switches(**kw):
+    from nerf_mae_amd.model import EmbedSwitches
+    return EmbedSwitches(**dict(dict(embed_kept=True, block0_kept=True), **kw))   # the defaults of the ops switches
+
+
+def _embed_plan(g, mask=True, add_pos=True, capacity=None, aligned=True, block0_ok=True, sw=None):
+    from nerf_mae_amd.model import plan_embed
+    return plan_embed(g, mask, add_pos, capacity, aligned, block0_ok, sw or _embed_switches())
+
+
+def test_embed_plan_of_the_mae_step_and_of_the_test_sizes():
+    from nerf_mae_amd.model import EmbedPlan, embed_capacity_rows
+    # 32^3 (g = 8: 8 windows): no capacity given = a row, or a window slot, for everything
+    assert _embed_plan(8) == EmbedPlan("windows", 64 * 9, 8, True)
+    assert _embed_plan(8, capacity=192) == EmbedPlan("windows", 64 * 4, 3, True)
+    assert _embed_plan(8, aligned=False) == EmbedPlan("rows", 512, 0, True)
+    assert _embed_plan(8, capacity=192, aligned=False) == EmbedPlan("rows", 192, 0, True)
+    # 160^3 (g = 40: 1000 windows), the capacity a captured step takes from the mask distribution
+    cap40 = embed_capacity_rows(40, p_remove=0.75)
+    assert cap40 % 64 == 0 and 64000 // 4 < cap40 < 0.4 * 64000
+    assert _embed_plan(40, capacity=cap40) == EmbedPlan("windows", 64 * (cap40 // 64 + 1), cap40 // 64, True)
+    assert _embed_plan(40, capacity=cap40, aligned=False) == EmbedPlan("rows", cap40, 0, True)
+    assert _embed_plan(40) == EmbedPlan("windows", 64 * 1001, 1000, True)
+    assert _embed_plan(40, aligned=False) == EmbedPlan("rows", 64000, 0, True)
+    assert _embed_plan(40, capacity=10 ** 6, aligned=False).rows == 64000         # never more rows than tokens
+    # g % 4 != 0: kept rows, never windows
+    assert _embed_plan(10) == EmbedPlan("rows", 1000, 0, True) and _embed_plan(10, capacity=320) == EmbedPlan("rows", 320, 0, True)
+    # a first block that does not qualify: kept rows
+    assert _embed_plan(8, capacity=192, block0_ok=False) == EmbedPlan("rows", 192, 0, True)
+    # no mask, or no position embedding (patch_partition alone): a row for every token, whatever the caller promises
+    assert _embed_plan(8, mask=False, capacity=192) == EmbedPlan("dense", 512, 0, True)
+    assert _embed_plan(8, mask=False, add_pos=False) == EmbedPlan("dense", 512, 0, False)
+    assert _embed_plan(8, add_pos=False, capacity=192) == EmbedPlan("dense", 512, 0, False)
+    # window slots and rows at g = 8: capW = max(1, min(cap // 64, 8)), rows = 64 (capW + 1)
+    for cap, capW in ((64, 1), (192, 3), (256, 4), (512, 8), (1024, 8), (32, 1)):      # (cap // 64 above the window count; cap < 64)
+        p = _embed_plan(8, capacity=cap)
+        assert (p.path, p.capW, p.rows) == ("windows", capW, 64 * (capW + 1)), (cap, p)
+    assert _embed_plan(8, capacity=32, aligned=False).rows == 32
+    with pytest.raises(AttributeError):
+        p.path = "dense"
+
+
+def test_embed_plan_switches_change_what_they_gate_alone(monkeypatch):
+    from nerf_mae_amd import ops
+    from nerf_mae_amd.model import EmbedPlan, EmbedSwitches
+    w, r = _embed_plan(8, capacity=192), _embed_plan(8, capacity=192, aligned=False)
+    assert _embed_plan(8, capacity=192, sw=_embed_switches(block0_kept=False)) == w._replace(path="rows", rows=192, capW=0) == r
+    assert _embed_plan(8, capacity=192, aligned=False, sw=_embed_switches(block0_kept=False)) == r
+    for kw in (dict(), dict(aligned=False)):
+        assert _embed_plan(8, capacity=192, sw=_embed_switches(embed_kept=False), **kw) == EmbedPlan("dense", 512, 0, True)    # (the window path needs the kept rows)
+    assert _embed_plan(8, mask=False, sw=_embed_switches(embed_kept=False, block0_kept=False)) == _embed_plan(8, mask=False)
+    for name, field in (("EMBED_KEPT", "embed_kept"), ("BLOCK0_KEPT", "block0_kept")):
+        before = EmbedSwitches.current()
+        monkeypatch.setattr(ops, name, not getattr(before, field))
+        assert EmbedSwitches.current() == before._replace(**{field: not getattr(before, field)})
+
+
+def _cuts_windows():
+    m = torch.ones(8, 8, 8, dtype=torch.uint8)
+    m[:2] = 0          # 128 tokens kept, through the middle of four windows
+    return m
+
+
+def test_refit_bound_against_the_conditions_the_step_held_inline():
+    """model.refit_bound (on model.mask_kept_aligned) against what GraphedTrainStep._fit_capture held inline: with an aligned bound, a mask that is neither block
+    bits with nb * 4 == g nor constant on every window drops the alignment; with fewer rows than tokens, a mask that keeps more than the rows takes a row for
+    every token; otherwise the capture stays.  The two limits broken at once give one widened bound (the inline form captured twice)."""
+    from nerf_mae_amd.model import EmbedBound, block_bits_of_mask, bound_of_mask, embed_capacity_rows, mask_kept_aligned, mask_window_aligned, refit_bound
+    g = 8
+    few = torch.ones(8, 8, 8, dtype=torch.uint8)
+    few[:4, :4, :4] = 0          # one block kept: 64 tokens
+    many = torch.zeros(8, 8, 8, dtype=torch.uint8)
+    many[:4, :4, :4] = 1         # seven blocks kept: 448 tokens
+    cut = _cuts_windows()
+    masks = {"few": few.numpy(), "many": many.numpy(), "cut": cut.numpy(), "all": np.ones((8, 8, 8), np.uint8), "none": np.zeros((8, 8, 8), np.uint8)}
+
+    def inline(bound, block_mask, bits):     # _fit_capture of before, on a bound; rows = None stands for g^3
+        aligned, rows = bound.aligned, g ** 3 if bound.rows is None else bound.rows
+        if aligned and not (bits is not None and np.asarray(bits).shape[0] * 4 == g) and not mask_window_aligned(np.asarray(block_mask)):
+            aligned = False
+        if rows < g ** 3 and g ** 3 - (64 * int(np.asarray(bits).sum()) if bits is not None else int(np.asarray(block_mask).sum())) > rows:
+            rows = g ** 3
+        return EmbedBound(rows, aligned)
+
+    full = lambda b: b._replace(rows=g ** 3 if b.rows is None else b.rows)   # noqa: E731
+    for rows in (None, 64, 128, 256, 448, 512):
+        for al in (False, True):
+            bound = EmbedBound(rows, al)
+            for name, m in masks.items():
+                for bits in (None, block_bits_of_mask(m)):
+                    got, want = refit_bound(bound, g, *mask_kept_aligned(g, m, bits)), inline(bound, m, bits)
+                    assert full(bound if got is None else got) == want, (bound, name, bits is not None, got, want)
+                    assert (got is None) == (want == full(bound)), (bound, name, bits is not None, got, want)     # None exactly where nothing changes
+    # the cases by name
+    assert mask_kept_aligned(g, masks["few"]) == (64, True) and mask_kept_aligned(g, masks["many"]) == (448, True) and mask_kept_aligned(g, masks["cut"]) == (128, False)
+    assert refit_bound(EmbedBound(64, False), g, 64, True) is None                                   # fits
+    assert refit_bound(EmbedBound(64, False), g, 448, True) == EmbedBound(512, False)                 # widened to a row for every token
+    assert refit_bound(EmbedBound(128, True), g, 128, False) == EmbedBound(128, False)                # alignment dropped, capacity kept
+    assert refit_bound(EmbedBound(64, True), g, 128, False) == EmbedBound(512, False)                 # both at once: one widened bound
+    assert refit_bound(EmbedBound(512, False), g, 512, False) is None and refit_bound(EmbedBound(None, False), g, 512, False) is None   # everything fits
+    # block bits with nb * 4 == g are aligned without looking: the mask itself is not read
+    bits = block_bits_of_mask(masks["few"])
+    assert bits.shape == (2, 2, 2) and mask_kept_aligned(g, object(), bits) == (64, True)
+    assert mask_kept_aligned(10, np.zeros((2, 2, 2), np.uint8), np.zeros((2, 2, 2), np.uint8)) == (1000, False)      # g % 4 != 0: bits are no windows
+    # the bound of a known mask: what the eager forward computed
+    for name, m in masks.items():
+        assert bound_of_mask(g, m) == EmbedBound(embed_capacity_rows(g, kept=512 - int(m.sum())), mask_window_aligned(m)), name
+    assert bound_of_mask(g, masks["cut"]) == EmbedBound(128, False) and bound_of_mask(g, masks["all"]) == EmbedBound(64, True)
+    assert bound_of_mask(g, few) == EmbedBound(64, True)      # a host tensor, as forward() holds it
 
 
 def test_stage_flush_policy_for_every_input():

@@ -218,7 +218,7 @@ def test_patch_embed_of_the_kept_tokens_only_changes_nothing(monkeypatch, dtype)
     the others by mask_token).  Against the full pass: the same loss, and gradients that differ by the order of fp32 sums only -- with a ragged second sample,
     with a capacity larger than the kept count (zeroed tail rows), with one block removed and with every block removed"""
     from nerf_mae_amd import ops
-    from nerf_mae_amd.model import embed_capacity_rows
+    from nerf_mae_amd.model import EmbedBound, embed_capacity_rows
     from oracle import mae3d_oracle as O
     ora, hip = _pair(SWIN_T, dtype, res=32, init="default")
     xs = [O.synthetic_grid((32, 32, 32), 41).cuda(), O.synthetic_grid((32, 30, 27), 42).cuda()]
@@ -239,23 +239,19 @@ def test_patch_embed_of_the_kept_tokens_only_changes_nothing(monkeypatch, dtype)
         assert abs(res[0][0] - res[1][0]) <= 5e-6 * abs(res[0][0]), (res[0][0], res[1][0])   # (run-to-run: the InstanceNorm statistics are sums of fp64 atomics of fp32 partials)
         assert relerr(res[1][1], res[0][1]) <= max(4 * noise, 2e-6 if dtype == torch.float32 else 2e-3), (relerr(res[1][1], res[0][1]), noise)
         assert torch.isfinite(res[1][1]).all()
-    # a capacity above the kept count (what a captured step runs with): forward_static with model._embed_cap set
+    # a capacity above the kept count (what a captured step runs with): forward_static with the bound's rows given
     monkeypatch.setattr(ops, "EMBED_KEPT", True)
     bm = masks[0]
     xb, ext = hip.transform(xs, torch.device("cuda"))
     md = bm.to(torch.uint8).contiguous().view(-1).cuda()
     outs = []
     for cap in (None, 512, embed_capacity_rows(8, kept=int(512 - int(bm.sum())))):
-        hip._embed_cap = cap
-        try:
-            hip.zero_grad()
-            torch.manual_seed(3)
-            l = hip.forward_static(xb, ext, md)
-            l[0].backward()
-            torch.cuda.synchronize()
-            outs.append((l[0].item(), hip._flat_grad.clone()))
-        finally:
-            hip._embed_cap = None
+        hip.zero_grad()
+        torch.manual_seed(3)
+        l = hip.forward_static(xb, ext, md, EmbedBound(rows=cap))
+        l[0].backward()
+        torch.cuda.synchronize()
+        outs.append((l[0].item(), hip._flat_grad.clone()))
     for o in outs[1:]:
         assert abs(o[0] - outs[0][0]) <= 5e-6 * abs(outs[0][0])
         assert relerr(o[1], outs[0][1]) <= (2e-5 if dtype == torch.float32 else 5e-3)
@@ -420,7 +416,7 @@ def test_graphed_step_recaptures_when_a_mask_keeps_more_tokens_than_the_embed_ca
     xs = [O.synthetic_grid((32, 32, 32), 61).cuda(), O.synthetic_grid((32, 30, 27), 62).cuda()]
     opt = FusedAdamW(hip, lr=0.0, weight_decay=0.0, max_grad_norm=0.1)     # lr 0: the weights stay put, the losses depend on the mask only
     step = GraphedTrainStep(hip, opt, 2)
-    step._embed_cap = 64
+    step.bound = step.bound._replace(rows=64)
     few = torch.ones(8, 8, 8, dtype=torch.uint8)
     few[:4, :4, :4] = 0          # one block kept: 64 tokens, fits
     many = torch.zeros(8, 8, 8, dtype=torch.uint8)
@@ -430,7 +426,7 @@ def test_graphed_step_recaptures_when_a_mask_keeps_more_tokens_than_the_embed_ca
         torch.cuda.synchronize()
         want = ref(xs, block_mask=bm)
         assert abs(losses[0].item() - want[0].item()) <= 2e-5 * abs(want[0].item()), (i, losses[0].item(), want[0].item())
-        assert step._embed_cap == (64 if i == 0 else 512)
+        assert step.bound.rows == (64 if i == 0 else 512)
 
 
 def test_training_trace_matches_reference_golden(golden):

@@ -1,7 +1,6 @@
 import random, sys, torch
 sys.path.insert(0, '.')
 from tests.test_model_gpu import _pair, TINY, relerr
-from nerf_mae_amd import model as M
 from oracle import mae3d_oracle as O
 ora, h32 = _pair(TINY, torch.float32)
 _, h16 = _pair(TINY, torch.bfloat16)
@@ -14,7 +13,7 @@ for name, m in (('f32', h32), ('b16', h16)):
     xb, ext = m.transform([t.cuda() for t in xs], dev)
     mask_dev = bm.to(torch.uint8).view(-1).cuda()
     with torch.no_grad():
-        tok = M._EmbedFn.apply(m._anchor, m, xb, mask_dev).view(2, 8, 8, 8, -1)
+        tok, _ = m._embed(xb, mask_dev)   # (no bound: never the kept-window rows, tok is the dense grid)
         rec = [('tok', tok)]
         x = tok
         feats = []
